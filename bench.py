@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the triangle-fill path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one frame of the reference's per-frame protocol (app.rs:170,208-213):
 clear -> set_light_direction -> set_camera -> render, with the finished frame left in HBM
@@ -9,8 +9,15 @@ clear -> set_light_direction -> set_camera -> render, with the finished frame le
 readback inside the timed region; the readback-inclusive rate is reported beside it).
 At N=1 the K steps are submitted through tr_scene_render_frames (the library's throughput path: the
 same K frames, each into render targets of its own, but `config.frames_per_launch` of them rendered
-by one launch of each kernel); `--submit frame` issues the four calls per frame instead, and the
-default run reports that rate too (`per_frame_protocol`).
+by one launch of each kernel); `--submit frame` issues the four calls per frame instead, and a
+`--full` run reports that rate too (`per_frame_protocol`).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`, ...); N_shaded comes from one CPU-oracle frame.  `--full` adds everything else:
+the parity check of the GPU frame against the oracle, the orbit / per-frame / latency / read-back
+legs, per-kernel device times and the roofline, the CPU baseline, BASELINE.json's configs (N=1)
+and the scale_config leg (N>1).  `--dump-outputs DIR` writes the last timed frame (a fixed,
+seeded sample of its pixels when the whole frame would exceed 64 MB as float32) to DIR/*.npy.
 
 Workload at N=1: diablo.obj, -s phong, 4096x4096 -- the configuration the metric
 "Mpixels/s shaded (z-test + Phong) at 4096x4096" is quoted on.  `value` =
@@ -26,9 +33,9 @@ final framebuffer is all-gathered over RCCL/xGMI every frame (north_star); frame
 double-buffered so that the gather of frame f runs on a second stream under the render of
 frame f+1.  Total work is fixed, so "scaling" is "strong".
 
-The reference's assets are used when present ($TR_ASSETS, assets/_ref copied by
-__graft_entry__.build(), or /root/reference/assets); otherwise a procedural sphere with the same
-polygon count stands in and `config.workload` says so.
+The reference's assets are used when present ($TR_ASSETS, or assets/_ref copied by
+__graft_entry__.build()); otherwise a procedural sphere with the same polygon count stands in and
+`config.workload` says so.
 """
 import argparse
 import hashlib
@@ -46,10 +53,26 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21   # 24 MB of float32 RGB
+DUMP_SEED = 20260
+
+
+def dump_outputs(path, frame):
+    """The last timed frame as float32 .npy files under `path`: the whole [H, W, 3] frame when it fits
+    DUMP_BYTES_MAX, else the RGB of a fixed, seeded sample of its pixels (row-major indices, sorted)."""
+    os.makedirs(path, exist_ok=True)
+    H, W = frame.shape[:2]
+    if frame.size * 4 <= DUMP_BYTES_MAX:
+        np.save(os.path.join(path, "frame_rgb.npy"), frame.astype(np.float32))
+        return
+    pix = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(path, "frame_rgb_sample.npy"), frame.reshape(H * W, 3)[pix].astype(np.float32))
+    np.save(os.path.join(path, "frame_sample_pixel.npy"), pix.astype(np.float64))
 
 
 def find_assets(name):
-    for root in (os.environ.get("TR_ASSETS"), os.path.join(REPO, "assets", "_ref"), "/root/reference/assets"):
+    for root in (os.environ.get("TR_ASSETS"), os.path.join(REPO, "assets", "_ref")):
         if root and os.path.isfile(os.path.join(root, name, "model.obj")):
             return os.path.join(root, name)
     return None
@@ -347,6 +370,10 @@ def main():
     ap.add_argument("--pipeline", default="phong")
     ap.add_argument("--model", default="diablo")
     ap.add_argument("--grid", type=int, default=1, help="n x n instancing (configs[4] uses 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity against the oracle, orbit / per-frame / latency / read-back legs, "
+                         "per-kernel times and roofline, CPU baseline, BASELINE configs (N=1), scale_config (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame to DIR/*.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the orbit / latency / read-back legs (profiling runs)")
@@ -369,6 +396,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -542,8 +571,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, read_frame())
 
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     # ---- metric 2: frames/s with the camera orbiting by 2*pi/200 per frame ---------
     # (deterministic stand-in for the reference's keyboard orbit, app.rs:173-200); not `value`.
     orbit_frames, orbit_elapsed, orbit_status = 200, None, None
@@ -617,17 +648,19 @@ def main():
 
     # ---- per-kernel device time of the same steps, HIP events on the kernels' own dispatches ----------
     # (ends on the headline frame: the parity check below reads it)
-    scene.profile_enable(True)
-    if use_dist:
-        sharded.enable_timing(True)
-    run(min(args.steps, 400) if use_dist else args.steps)
-    device_idle()
-    prof = scene.profile_read()
-    intervals = np.sort(scene.profile_frame_intervals())
-    scene.profile_enable(False)
+    prof, intervals = {}, np.zeros(0)
+    if args.full:
+        scene.profile_enable(True)
+        if use_dist:
+            sharded.enable_timing(True)
+        run(min(args.steps, 400) if use_dist else args.steps)
+        device_idle()
+        prof = scene.profile_read()
+        intervals = np.sort(scene.profile_frame_intervals())
+        scene.profile_enable(False)
 
     per_rank = None
-    if use_dist:
+    if use_dist and args.full:
         mine = dict({"rank": rank, "band_rows": list(band)}, **sharded.timings())
         mine["k_tile_us"] = round(prof["k_tile"]["total_ms"] / max(prof["k_tile"]["frames"], 1) * 1e3, 2) if "k_tile" in prof else None
         sharded.enable_timing(False)
@@ -639,8 +672,8 @@ def main():
     if rank == 0:
         from oracle import oracle as O
 
-        # N_shaded and the algorithmic bytes come from the CPU oracle on the same frame; the
-        # same run checks the GPU frame (whole frame: all bands gathered) bit for bit.
+        # N_shaded and the algorithmic bytes come from the CPU oracle on the same frame; a --full
+        # run checks the GPU frame (whole frame: all bands gathered) bit for bit.
         cpu = O.Scene(W, H, mesh, texs, pipe)
         cpu.clear()
         cpu.set_light_direction(lt)
@@ -651,15 +684,17 @@ def main():
         stats = cpu.stats()
         color = stats[1] if pipe in ("shadow", "occlusion") else stats[0]
         n_shaded = color["frag_accept"]
-        gpu_frame = read_frame()
-        ref_frame = cpu.get_frame_buffer()
-        diff = np.abs(gpu_frame.astype(np.int16) - ref_frame.astype(np.int16))
-        # specular calls powf: exact when the library reproduces the host libm's (tr_specular_exact), else 1 LSB
-        tol = 1 if pipe == "specular" and not T.load_library().tr_specular_exact() else 0
-        parity_ok = bool(diff.max() <= tol)
+        diff, tol, parity_ok = None, None, None
+        if args.full:
+            gpu_frame = read_frame()
+            ref_frame = cpu.get_frame_buffer()
+            diff = np.abs(gpu_frame.astype(np.int16) - ref_frame.astype(np.int16))
+            # specular calls powf: exact when the library reproduces the host libm's (tr_specular_exact), else 1 LSB
+            tol = 1 if pipe == "specular" and not T.load_library().tr_specular_exact() else 0
+            parity_ok = bool(diff.max() <= tol)
 
         cpu_baseline = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             frames, spent = 1, t_one
             while spent < args.cpu_seconds and frames < 1000:
                 cpu.clear()
@@ -764,33 +799,36 @@ def main():
             "exchange_dense_bytes_per_frame": int(band_bytes * (world - 1)) if use_dist else 0,
             "scaling_measured": "unmeasured here: one GPU per box (SCALE is the driver's 8-GPU run)" if world == 1 else "this run",
             "frames_per_s": round(args.steps / elapsed, 1),
-            "frames_per_s_orbit": round(orbit_frames / orbit_elapsed, 1) if orbit_elapsed and orbit_status == 0 else None,
             "framebuffer_mpixels_per_s": round(W * H * args.steps / elapsed / 1e6, 1),
-            "per_frame_protocol": {"ms_per_step": round(per_frame_elapsed / per_frame_steps * 1e3, 5),
-                                   "value": round(n_shaded * per_frame_steps / per_frame_elapsed / 1e6, 2),
-                                   "steps": per_frame_steps,
-                                   "what": "the same frames through clear / set_light_direction / set_camera / render "
-                                           "(frames nobody reads in between are held back and fused by the library)",
-                                   "unfused_ms_per_step": round(unfused_elapsed / per_frame_steps * 1e3, 5),
-                                   "unfused_value": round(n_shaded * per_frame_steps / unfused_elapsed / 1e6, 2),
-                                   "unfused_what": "TR_OPT_NO_AUTO_GROUP: one launch of each kernel per frame"}
-            if per_frame_elapsed else None,
-            "t_frame_us": t_frame,
-            "latency_us": latency_us,
-            # everything the scene holds on the device once all the loops above have run (record pools, work lists,
-            # render targets of every frame in flight, textures): free memory before the scene minus free memory now
-            "device_memory_mb": round((free_before_scene - torch.cuda.mem_get_info(device_index)[0]) / 1e6, 1),
-            "readback_inclusive_mpixels_per_s": round(n_shaded / readback / 1e6, 1) if readback else None,
-            "readback_inclusive_frame_us": round(readback * 1e6, 1) if readback else None,
-            "parity_vs_oracle": {"ok": parity_ok, "max_abs_rgb_diff": int(diff.max()), "tolerance": tol},
             "device_status": status,
-            "kernel_us": {k: round(v["total_ms"] / max(v["launches"], 1) * 1e3, 2) for k, v in prof.items()},
-            "kernel_us_per_frame": {k: round(v["total_ms"] / max(v["frames"], 1) * 1e3, 2) for k, v in prof.items()},
-            "per_rank": per_rank,
-            "roofline": roofline,
-            "cpu_baseline": cpu_baseline,
         }
-        # ---- SURVEY.md 8d "Report": every BASELINE config that fits one GPU, in the same run (default flags only) ----
+        if args.full:
+            out.update({
+                "frames_per_s_orbit": round(orbit_frames / orbit_elapsed, 1) if orbit_elapsed and orbit_status == 0 else None,
+                "per_frame_protocol": {"ms_per_step": round(per_frame_elapsed / per_frame_steps * 1e3, 5),
+                                       "value": round(n_shaded * per_frame_steps / per_frame_elapsed / 1e6, 2),
+                                       "steps": per_frame_steps,
+                                       "what": "the same frames through clear / set_light_direction / set_camera / render "
+                                               "(frames nobody reads in between are held back and fused by the library)",
+                                       "unfused_ms_per_step": round(unfused_elapsed / per_frame_steps * 1e3, 5),
+                                       "unfused_value": round(n_shaded * per_frame_steps / unfused_elapsed / 1e6, 2),
+                                       "unfused_what": "TR_OPT_NO_AUTO_GROUP: one launch of each kernel per frame"}
+                if per_frame_elapsed else None,
+                "t_frame_us": t_frame,
+                "latency_us": latency_us,
+                # everything the scene holds on the device once all the loops above have run (record pools, work lists,
+                # render targets of every frame in flight, textures): free memory before the scene minus free memory now
+                "device_memory_mb": round((free_before_scene - torch.cuda.mem_get_info(device_index)[0]) / 1e6, 1),
+                "readback_inclusive_mpixels_per_s": round(n_shaded / readback / 1e6, 1) if readback else None,
+                "readback_inclusive_frame_us": round(readback * 1e6, 1) if readback else None,
+                "parity_vs_oracle": {"ok": parity_ok, "max_abs_rgb_diff": int(diff.max()), "tolerance": tol},
+                "kernel_us": {k: round(v["total_ms"] / max(v["launches"], 1) * 1e3, 2) for k, v in prof.items()},
+                "kernel_us_per_frame": {k: round(v["total_ms"] / max(v["frames"], 1) * 1e3, 2) for k, v in prof.items()},
+                "per_rank": per_rank,
+                "roofline": roofline,
+                "cpu_baseline": cpu_baseline,
+            })
+        # ---- SURVEY.md 8d "Report": every BASELINE config that fits one GPU, in the same run (--full, default flags) ----
         default_run = (world == 1 and not use_dist and extras and not args.no_configs and pipe == "phong" and W == 4096
                        and args.model == "diablo" and args.grid == 1)
         if default_run:
@@ -808,7 +846,7 @@ def main():
     scale = None
     # (TR_BENCH_FORCE_SCALE=1 with TR_BENCH_FORCE_DIST=1: the leg with a single rank, a rehearsal of the RCCL transports'
     # plumbing on a one-GPU box, where RCCL cannot have a second rank)
-    if use_dist and not args.no_scale and (world > 1 or os.environ.get("TR_BENCH_FORCE_SCALE") == "1"):
+    if use_dist and args.full and not args.no_scale and (world > 1 or os.environ.get("TR_BENCH_FORCE_SCALE") == "1"):
         scale = measure_scale_config(T, torch, dist, args, exchange_kind, rank, world, device_index)
     if out is not None:
         if scale is not None:
@@ -818,7 +856,7 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
-    if out is not None and not out["parity_vs_oracle"]["ok"]:
+    if out is not None and args.full and not out["parity_vs_oracle"]["ok"]:
         raise SystemExit("GPU frame differs from the oracle")
     if out is not None and out.get("scale_config") and not out["scale_config"]["parity_vs_oracle"]["ok"]:
         raise SystemExit("scale_config: the assembled frame differs from the oracle")

@@ -3,7 +3,7 @@ for rep in 1 2 3; do
 for v in main r03; do
   unset TR_LIBRARY
   [ $v = r03 ] && export TR_LIBRARY=scratch/r03/libtiny_renderer.so
-  python bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | python -c "
+  python bench.py --steps 20 --warmup 5 --full --no-cpu 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ for v in main "$@"; do
   unset TR_LIBRARY
   [ $v != main ] && export TR_LIBRARY=scratch/$v/tiny_renderer_amd/lib/libtiny_renderer.so
   [ $v = r03 ] && export TR_LIBRARY=scratch/r03/libtiny_renderer.so
-  python bench.py $args --no-cpu --no-extras 2>/dev/null | python -c "
+  python bench.py $args --full --no-cpu --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -11,7 +11,7 @@ def line(path):
             return {k: d.get(k) for k in KEEP}
     raise SystemExit("no bench line in " + path)
 out = {"dense (bands pulled by the DMA engines)": line(dense), "sparse (k_push_tiles)": line(sparse),
-       "what": "bench.py --gpus 2 --exchange peer [--sparse] --steps 40 --warmup 8 with BOTH rank processes on one MI355X "
+       "what": "bench.py --gpus 2 --exchange peer [--sparse] --full --steps 40 --warmup 8 with BOTH rank processes on one MI355X "
                "(TR_BENCH_SHARE_GPU=1): a functional rehearsal of the N > 1 path with a real peer (band scenes, groups, exchange, "
                "assembled frame = oracle), NOT a speed claim: the ranks share the GPU's compute units and exchange through its "
                "memory, not xGMI"}

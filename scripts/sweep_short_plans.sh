@@ -1,5 +1,5 @@
 # The driver's short run (bench.py --steps 20 --warmup 5) under different group plans (experiment hooks of tr_scene.cpp)
-run() { python bench.py --steps 20 --warmup 5 --no-cpu --no-extras --no-configs 2>/dev/null | python -c "
+run() { python bench.py --steps 20 --warmup 5 --full --no-cpu --no-extras --no-configs 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

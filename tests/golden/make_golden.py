@@ -7,6 +7,10 @@ They let `-m "not gpu"` tests detect any drift of the oracle, and `-m gpu` tests
 against the same fingerprints without re-deriving them.
 
     python tests/golden/make_golden.py          # rewrites the json next to this script
+
+Each model scene also has "fixture:" entries: the same scene with tests/golden/assets standing in for
+the model's folder (its own OBJ, procedural maps; tests/helpers.py), which the tests use where the
+model's assets are absent.
 """
 import hashlib
 import json
@@ -57,16 +61,42 @@ def key(name, W, Hh, ca, la, pipe):
     return "%s/%dx%d/cam%+.2f/light%+.2f/%s" % (name, W, Hh, ca, la, pipe)
 
 
+def fixture_key(name, W, Hh, ca, la, pipe):
+    """The same scene with tests/golden/assets standing in for the model's folder (its OBJ, procedural maps)."""
+    return "fixture:" + key(name, W, Hh, ca, la, pipe)
+
+
+def gold_key(name, W, Hh, ca, la, pipe):
+    """Key of what scene_inputs(name) renders here: the model's own assets, or the fixture standing in for them."""
+    from tests import helpers as H
+    k = fixture_key if name != "synthetic" and H.asset_source(name) == "fixture" else key
+    return k(name, W, Hh, ca, la, pipe)
+
+
+# the fingerprints that depend on the geometry alone: the fixture's equal the model's own
+GEOMETRY_FIELDS = ("err", "z", "winner", "accepts", "shadow")
+
+
+def fixture_inputs(name):
+    from tests import helpers as H
+    d = H._fixture_dir(name)
+    return None if d is None else (H.load_obj_py(os.path.join(d, "model.obj")), H.fixture_maps())
+
+
 def main():
-    res = {}
+    # (merged into what is there: a box without the models' own assets keeps their entries)
+    path = os.path.join(HERE, "oracle_hashes.json")
+    res = json.load(open(path)) if os.path.exists(path) else {}
     for name, W, Hh, ca, la in CASES:
         inputs = scene_inputs(name)
         if inputs is None:
             print("skipping %s: assets not available" % name)
             continue
+        fixture = fixture_inputs(name) if name != "synthetic" else None
         for pipe in PIPES:
-            res[key(name, W, Hh, ca, la, pipe)] = fingerprints(name, W, Hh, ca, la, pipe, inputs)
-    path = os.path.join(HERE, "oracle_hashes.json")
+            res[gold_key(name, W, Hh, ca, la, pipe)] = fingerprints(name, W, Hh, ca, la, pipe, inputs)
+            if fixture is not None:
+                res[fixture_key(name, W, Hh, ca, la, pipe)] = fingerprints(name, W, Hh, ca, la, pipe, fixture)
     json.dump(res, open(path, "w"), indent=1, sort_keys=True)
     print("wrote %d fingerprints to %s" % (len(res), path))
 

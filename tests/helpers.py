@@ -13,22 +13,71 @@ if REPO not in sys.path:
 TEX_FILES = ("texture.tga", "normal_map.tga", "normal_map_tangent.tga", "specular_map.tga")
 
 
+FIXTURES = os.path.join(REPO, "tests", "golden", "assets")
+_fixture_root = None
+
+
 def asset_root():
-    """Directory holding <model>/model.obj etc.: $TR_ASSETS, the git-ignored copy made by
-    __graft_entry__.build() (assets/_ref), or the reference checkout when present."""
-    for p in (os.environ.get("TR_ASSETS"), os.path.join(REPO, "assets", "_ref"),
-              "/root/reference/assets"):
+    """Directory holding <model>/model.obj etc.: $TR_ASSETS or the git-ignored copy made by
+    __graft_entry__.build() (assets/_ref), when present."""
+    for p in (os.environ.get("TR_ASSETS"), os.path.join(REPO, "assets", "_ref")):
         if p and os.path.isdir(p):
             return p
     return None
 
 
-def asset_dir(name):
+def _real_asset_dir(name):
     root = asset_root()
     if root is None:
         return None
     d = os.path.join(root, name)
     return d if os.path.isfile(os.path.join(d, "model.obj")) else None
+
+
+def fixture_maps():
+    """The four maps of the committed fixtures: the procedural 1024^2 maps of synthetic_scene
+    (diffuse, two normal maps, specular)."""
+    import tiny_renderer_amd as T
+    return T.synthetic_scene(n_lat=1, n_lon=1, tex_size=1024)[1]
+
+
+def _fixture_dir(name):
+    """tests/golden/assets/<name>.obj.xz (the model's own OBJ) with fixture_maps() written as
+    RLE TGAs (by PIL), unpacked once per process into a temporary asset folder."""
+    global _fixture_root
+    import atexit
+    import lzma
+    import shutil
+    import tempfile
+    src = os.path.join(FIXTURES, name + ".obj.xz")
+    if not os.path.isfile(src):
+        return None
+    if _fixture_root is None:
+        _fixture_root = tempfile.mkdtemp(prefix="tr_assets_")
+        atexit.register(shutil.rmtree, _fixture_root, True)
+    d = os.path.join(_fixture_root, name)
+    if not os.path.isfile(os.path.join(d, "model.obj")):
+        from PIL import Image
+        os.makedirs(d, exist_ok=True)
+        for f, m in zip(TEX_FILES, fixture_maps()):
+            Image.fromarray(m).save(os.path.join(d, f), compression="tga_rle")
+        with lzma.open(src, "rb") as fi, open(os.path.join(d, "model.obj.part"), "wb") as fo:
+            shutil.copyfileobj(fi, fo)
+        os.replace(os.path.join(d, "model.obj.part"), os.path.join(d, "model.obj"))
+    return d
+
+
+def asset_source(name):
+    """"assets" when the model's own folder is present, "fixture" when the committed fixture
+    stands in for it (same OBJ, procedural maps), None when neither exists."""
+    if _real_asset_dir(name):
+        return "assets"
+    return "fixture" if os.path.isfile(os.path.join(FIXTURES, name + ".obj.xz")) else None
+
+
+def asset_dir(name):
+    """<name>'s asset folder: the model's own (asset_root()) or else the fixture's."""
+    return _real_asset_dir(name) or _fixture_dir(name)
 
 
 def load_obj_py(path):

@@ -1082,7 +1082,7 @@ def test_bench_sharded_path_over_rccl_with_one_rank(built, exchange):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(H.REPO, "bench.py"), "--gpus", "1", "--exchange", exchange, "--size", "1024",
-                        "--steps", "12", "--warmup", "4", "--no-cpu", "--scale-size", "1024", "--scale-grid", "2", "--scale-steps", "8"],
+                        "--steps", "12", "--warmup", "4", "--full", "--no-cpu", "--scale-size", "1024", "--scale-grid", "2", "--scale-steps", "8"],
                        env=env, cwd=H.REPO, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -1134,11 +1134,12 @@ def test_peer_exchange_two_processes_one_gpu(diablo, sparse):
     import os
     import subprocess
     import sys
-    env = dict(os.environ, TR_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    # (bench.py reads the model from the folder the `diablo` fixture came from)
+    env = dict(os.environ, TR_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", TR_ASSETS=os.path.dirname(H.asset_dir("diablo")))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(H.REPO, "bench.py"), "--gpus", "2", "--exchange", "peer", "--size", "1024",
-                        "--steps", "40", "--warmup", "5", "--no-cpu", "--scale-size", "2048", "--scale-grid", "4", "--scale-steps", "12"]
+                        "--steps", "40", "--warmup", "5", "--full", "--no-cpu", "--scale-size", "2048", "--scale-grid", "4", "--scale-steps", "12"]
                        + (["--sparse"] if sparse else []), env=env, cwd=H.REPO, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     import json
