@@ -939,6 +939,10 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     const int32_t lx = (int32_t)(lane & 7u), ly = (int32_t)(lane >> 3);
     const uint4 *bin = reinterpret_cast<const uint4 *>(a.bins) + (size_t)work.offset * P;  // the tile's records in the pool
     const bool resident = n <= (uint32_t)NMAX;  // the whole bin stays in LDS through shading
+    // the same address for the scalar loads of the coverage visits (uniform, but loaded into vector registers)
+    const uint64_t bin_addr = reinterpret_cast<uint64_t>(bin);
+    const constant_ptr<uint32_t> bin_s = (constant_ptr<uint32_t>)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(bin_addr >> 32)) << 32) |
+                                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bin_addr));
 
     // ---- initial keys, coverage + depth resolve: one body for both forms ------------------------
     auto resolve = [&](auto shared_tag) {
@@ -993,14 +997,11 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
             // wave jj mod TILE_WAVES, a round covers 64 * TILE_WAVES records
             for (uint32_t j0 = 0; j0 < m; j0 += SH ? 64u * (uint32_t)TILE_WAVES : 64u) {
                 const uint32_t jj = SH ? j0 + lane * (uint32_t)TILE_WAVES + wave : j0 + lane;
-                uint4 r0 = make_uint4(1u, 0u, 0u, 0u), r1 = make_uint4(0, 0, 0, 0), r2 = r1, r3 = r1;  // (no record: an empty box)
-                uint32_t ry = 0u;
+                uint4 r0 = make_uint4(1u, 0u, 0u, 0u), r1 = make_uint4(0, 0, 0, 0), r2 = r1;  // (no record: an empty box)
                 if (jj < m) {
                     r0 = s_rec[jj * P + 0];
                     r1 = s_rec[jj * P + 1];
                     r2 = s_rec[jj * P + 2];
-                    r3 = s_rec[jj * P + 3];
-                    ry = s_rec[jj * P + (P - 1)].w;
                 }
                 // piece 0: the polygon's clamped box and what k_setup found out about it inside THIS tile
                 // (pair_masks, tr_shaders.h): the cells of a small pair, the block columns of a large one
@@ -1019,41 +1020,44 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
                 // block: what a visit iterates over
                 uint32_t lmask = (some && !small) ? pair_block_columns(r0.z, r0.w, SHARED && SCAN_ITEMS, pb, tile_x0) : 0u;
                 if (!SH) lmask = (lmask >> (NBX * wave)) & ((1u << NBX) - 1u);
-                // The polygon's part of to_barycentric_coord (scene.rs:178-187), for the 64 records
-                // of this round at once (lane l = record l).  Orientation is normalised so that
-                // cross.z > 0: negating a0, a1, b0, b1 flips the sign of cross.x and cross.y exactly,
-                // and dividing them by -cross.z (reciprocal -y) gives bit-identical quotients, so one
-                // branch-free form of the inside test serves both windings.
-                float la0 = __uint_as_float(r1.z), la1 = __uint_as_float(r2.x);
-                float lb0 = __uint_as_float(r1.w), lb1 = __uint_as_float(r2.y);
-                float lcz = la0 * lb1 - la1 * lb0;
-                float lry = __uint_as_float(ry);
-                if (lcz < 0.0f) {
-                    la0 = -la0; la1 = -la1; lb0 = -lb0; lb1 = -lb1;
-                    lcz = -lcz;
-                    lry = -lry;
-                }
+                // The polygon's part of to_barycentric_coord (scene.rs:178-187).  Orientation is normalised so
+                // that cross.z > 0: negating a0, a1, b0, b1 flips the sign of cross.x and cross.y exactly, and
+                // dividing them by -cross.z (reciprocal -y) gives bit-identical quotients, so one branch-free form
+                // of the inside test serves both windings.  cross.z is formed for the 64 records of this round at
+                // once (lane l = record l); a visit takes it and the block columns from lane l (two v_readlane) and
+                // everything else with scalar loads of the record in the tile's bin -- a few hundred bytes per tile,
+                // resident in the scalar cache -- negating by the sign bit (bit l of `flip`) where cross.z < 0.
+                // (Only the comparisons here use the normalised form: shading reads the raw fields, whose zero
+                // signs its quotients keep.)
+                const float lcz_raw = __uint_as_float(r1.z) * __uint_as_float(r2.y) - __uint_as_float(r2.x) * __uint_as_float(r1.w);
+                const unsigned long long flip = __ballot(lcz_raw < 0.0f);
+                const float lcz = lcz_raw < 0.0f ? -lcz_raw : lcz_raw;
                 unsigned long long todo = (TR_DBG_SKIP & 4) ? 0ull : __ballot(lmask != 0u);
                 while (todo) {
                     const uint32_t l = (uint32_t)__builtin_ctzll(todo);
                     todo &= todo - 1ull;
-                    const uint32_t boxx = (uint32_t)bcast(r0.x, l), boxy = (uint32_t)bcast(r0.y, l);
+                    const uint32_t slot1 = SH ? c0 + j0 + l * (uint32_t)TILE_WAVES + wave + 1u : c0 + j0 + l + 1u;
+                    const constant_ptr<uint32_t> rec = bin_s + (slot1 - 1u) * (uint32_t)(4 * P);  // (word 4 i + c = piece i, component c)
+                    const uint4 g0 = make_uint4(rec[0], rec[1], 0u, 0u), g1 = make_uint4(rec[4], rec[5], rec[6], rec[7]);
+                    const uint4 g2 = make_uint4(rec[8], rec[9], rec[10], rec[11]), g3 = make_uint4(rec[12], rec[13], 0u, 0u);
+                    const uint32_t gry = rec[4 * P - 1];
+                    const uint32_t sgn = ((uint32_t)(flip >> l) & 1u) << 31;
+                    const uint32_t boxx = g0.x, boxy = g0.y;
                     const int32_t bx0 = imax((int32_t)(boxx & 0xFFFFu), qx0), bx1 = imin((int32_t)(boxx >> 16), qx0 + QUAD - 1);
                     const int32_t by0 = imax((int32_t)(boxy & 0xFFFFu), qy0), by1 = imin((int32_t)(boxy >> 16), qy0 + TILE_H - 1);
-                    const int32_t x0 = bcast(r1.x, l), y0 = bcast(r1.y, l);
-                    const float z0 = __int_as_float(bcast(r2.z, l)), z1 = __int_as_float(bcast(r2.w, l));
-                    const float z2 = __int_as_float(bcast(r3.x, l));
-                    const uint32_t id = (uint32_t)bcast(r3.y, l);
-                    const uint32_t slot1 = SH ? c0 + j0 + l * (uint32_t)TILE_WAVES + wave + 1u : c0 + j0 + l + 1u;
+                    const int32_t x0 = (int32_t)g1.x, y0 = (int32_t)g1.y;
+                    const float z0 = __uint_as_float(g2.z), z1 = __uint_as_float(g2.w);
+                    const float z2 = __uint_as_float(g3.x);
+                    const uint32_t id = g3.y;
                     uint32_t cols = (uint32_t)bcast(lmask, l);
                     Edge2T<V2> e;
-                    e.a0 = splat2v<V2>(__int_as_float(bcast(__float_as_uint(la0), l)));
-                    e.a1 = splat2v<V2>(__int_as_float(bcast(__float_as_uint(la1), l)));
-                    e.b0 = splat2v<V2>(__int_as_float(bcast(__float_as_uint(lb0), l)));
-                    e.b1 = splat2v<V2>(__int_as_float(bcast(__float_as_uint(lb1), l)));
+                    e.a0 = splat2v<V2>(__uint_as_float(g1.z ^ sgn));
+                    e.a1 = splat2v<V2>(__uint_as_float(g2.x ^ sgn));
+                    e.b0 = splat2v<V2>(__uint_as_float(g1.w ^ sgn));
+                    e.b1 = splat2v<V2>(__uint_as_float(g2.y ^ sgn));
                     const float cz = __int_as_float(bcast(__float_as_uint(lcz), l));
                     e.cz = splat2v<V2>(cz);
-                    e.y = splat2v<V2>(__int_as_float(bcast(__float_as_uint(lry), l)));
+                    e.y = splat2v<V2>(__uint_as_float(gry ^ sgn));
                     // this lane's two pixels: (px, pya) in block row 0 and (px, pyb) in block row 1
                     const int32_t pya = qy0 + ly, pyb = qy0 + 8 + ly;
                     const V2 b2 = mk2v<V2>((float)isub(y0, pya), (float)isub(y0, pyb));
@@ -1289,33 +1293,54 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     uint8_t *const fb_strip = DEPTH ? nullptr : fb + ((int64_t)(H - sy0 - STRIP_ROWS) * W + sx0) * 3;
     const uint32_t Wu = (uint32_t)W, W3 = 3u * (uint32_t)W;
     const bool col_live = px < W;
+    // What a step's keys and stores need of the lane is the same in every step; only the step's first row r0 (even,
+    // uniform) moves them, and it moves them by scalars:
+    //   key slot   key_slot(x, strip_y + r0 + hrow) = (key_slot(x, hrow) ^ ((r0' & 7) << 3)) + ((r0' >> 3) * NBX << 6),
+    //              r0' = strip_y + r0 -- the rows of an 8x8 block sit in slot bits 3..5 (r0' even: it and hrow share no bit),
+    //              the block row above bit 6;
+    //   depth      row r0 + hrow at depth_strip + r0 * W (scalar) + (hrow * W + hx);
+    //   colour     rows r0 / r0 + 1 at fb_strip + (STRIP_ROWS - 2 - r0) * 3W (scalar) + ((1 - hrow) * 3W + 3 hx / 4 hx).
+    // So the step loop forms no address arithmetic of its own beyond one XOR per key.
+    const uint32_t key_lane = key_slot<QUAD_COLUMN>((uint32_t)strip_x + (uint32_t)hx, (uint32_t)hrow);
+    const uint32_t zlane = mul24((uint32_t)hrow, Wu) + (uint32_t)hx;
+    const uint32_t clane = mul24(1u - (uint32_t)hrow, W3);
+    // the dword form of the colour row: dword j of the 96-byte row = bytes 4j..4j+3 = pixel p0 = 4j/3 from byte (4j)%3 on,
+    // topped up from pixel p0+1 -- the two permutes' byte addresses (ds_bpermute) and shifts of this lane
+    const uint32_t cj = (uint32_t)hx, cp0 = (4u * cj) / 3u, co = (4u * cj) % 3u;
+    const int32_t perm0 = (int32_t)((half_base + (cp0 & 31u)) << 2), perm1 = (int32_t)((half_base + ((cp0 + 1u) & 31u)) << 2);
+    const uint32_t csh0 = 8u * co, csh1 = 24u - 8u * co;
+    const bool cdw_live = cj < 24u && (sx0 * 3 + (int32_t)(4u * cj)) < W * 3;
 
-    // Reads a pixel's key and returns the bin slot + 1 of its survivor (0: none)
+    // Reads a pixel's key and returns the bin slot + 1 of its survivor (0: none): pixel (hx, r0 + hrow) of the strip
     // (zbits: the f32 bits of the depth the resolve compared for that pixel -- what a depth pass stores, below)
-    auto survivor_slot = [&](uint32_t sx, uint32_t sy, uint32_t &zbits) -> uint32_t {
+    auto survivor_slot = [&](uint32_t r0, uint32_t &zbits) -> uint32_t {
         if (SHARED && shared_tile) {
             // tie-break word: low 12 bits = bin slot + 1 of a fragment, 0xFFF / 0 = the buffer's old content
-            const uint2 key = s_key[shared_key_slot((uint32_t)strip_x + sx, (uint32_t)strip_y + sy)];
+            const uint2 key = s_key[shared_key_slot((uint32_t)strip_x + (uint32_t)hx, (uint32_t)strip_y + r0 + (uint32_t)hrow)];
             const uint32_t f = key.x & 0xFFFu;
             zbits = (key.y & 0x80000000u) ? key.y ^ 0x80000000u : ~key.y;  // (depth_order_bits undone; both zeros read +0)
             return (f == 0xFFFu) ? 0u : f;
         }
+        const uint32_t ry = (uint32_t)strip_y + r0;
+        const uint32_t slot = (key_lane ^ ((ry & 7u) << 3)) + (((ry >> 3) * (uint32_t)(QUAD_COLUMN / 8)) << 6);
         // (the whole 8-byte key: 64 lanes x 8 bytes in a row are conflict-free as ds_read_b64, the upper dwords alone as
         // ds_read_b32 are a two-way bank conflict)
 #if TR_KEY_B64
-        const uint2 key = s_key[key_slot<QUAD_COLUMN>((uint32_t)strip_x + sx, (uint32_t)strip_y + sy)];
+        const uint2 key = s_key[slot];
         uint32_t keep = key.x;
         asm volatile("" : "+v"(keep));   // (keeps the compiler from narrowing the read again)
         zbits = keep;
         return key.y;
 #else
         zbits = 0u;
-        return s_key[key_slot<QUAD_COLUMN>((uint32_t)strip_x + sx, (uint32_t)strip_y + sy)].y;
+        return s_key[slot].y;
 #endif
     };
     // Two pixels of a lane through the fragment stage, each against its own polygon: pixel u at (pxs[u], pys[u]),
-    // survivor in bin slot wslot[u] if won[u].  Lanes without a survivor run the same loads on record 0 and
-    // discard the result, so the code is branch-free.  RESIDENT: the bin's records are in LDS (nearly always);
+    // survivor in bin slot wslot[u] if won[u] -- for records in LDS the key's slot + 1 as it was read (no select: a lane
+    // without a survivor reads the 96 bytes in front of record 0, or record slot + 1 - 1 of a pixel outside the band, and
+    // discards the result), for records in global memory the slot itself (record 0 for a lane without a survivor).
+    // So the code is branch-free.  RESIDENT: the bin's records are in LDS (nearly always);
     // PAIR: the two-pixel closures (tr_shaders.h) -- returns true when a surviving pixel left their guarded
     // range anywhere in the wave (the caller then runs the step again with the plain closures; keeping those
     // out of the fast loop's body matters: inline, as the fallback of each step, their registers were live
@@ -1331,8 +1356,8 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
         // so that 32 fewer registers are live (123 -> under 96: a fifth wave per SIMD).
         constexpr int TOP = P < 6 ? P : 6;
         uint4 qa[TOP], qb[TOP];
-        const uint4 *const ra = RESIDENT ? s_rec + mul24(wslot[0], (uint32_t)P) : bin + (size_t)wslot[0] * P;
-        const uint4 *const rb = RESIDENT ? s_rec + mul24(wslot[1], (uint32_t)P) : bin + (size_t)wslot[1] * P;
+        const uint4 *const ra = RESIDENT ? s_rec + ((int32_t)mul24(wslot[0], (uint32_t)P) - P) : bin + (size_t)wslot[0] * P;
+        const uint4 *const rb = RESIDENT ? s_rec + ((int32_t)mul24(wslot[1], (uint32_t)P) - P) : bin + (size_t)wslot[1] * P;
 #pragma unroll
         for (int i = 1; i < TOP; i++) {
             qa[i] = RESIDENT ? ra[i] : gload(ra + i);
@@ -1460,38 +1485,34 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
         return redo;
     };
 
-    // One pixel of a lane to memory: row `row` of the strip (this lane's column hx), `live` = inside frame and band,
-    // `put` = its depth (and winner word) changes.  Depth goes out straight from registers as whole 128-byte lines;
-    // colour is packed to dwords with two lane permutes and stored flipped (scene.rs:92-97 folded in).
-    auto store_pixel = [&](int32_t row, int32_t py_, bool live, bool won, float zv, uint32_t rgbv, uint32_t triv, bool with_winner) {
-        const uint32_t zoff = mul24((uint32_t)row, Wu) + (uint32_t)hx;
-        const uint32_t coff = mul24((uint32_t)(STRIP_ROWS - 1 - row), W3);  // the row's first byte
+    // Pixel u of a lane's step to memory: row r0 + u * 2 + hrow of the strip (r0: the step's first row), `live` = inside
+    // frame and band, `put` = its depth (and winner word) changes.  Depth goes out straight from registers as whole
+    // 128-byte lines; colour is packed to dwords with two lane permutes and stored flipped (scene.rs:92-97 folded in).
+    // aligned4: the frame's width is a multiple of 4 (TileArgs::aligned4), so a colour row is whole dwords (a uniform branch).
+    auto store_pixel = [&](uint32_t r0, bool row_live, bool live, bool won, float zv, uint32_t rgbv,
+                           uint32_t triv, bool with_winner) {
+        uint8_t *const fb_row = DEPTH ? nullptr : fb_strip + (int64_t)((int32_t)(STRIP_ROWS - 2) - (int32_t)r0) * (int64_t)W3;
         if (!DEPTH && !fresh && live && !won && st_c) {
             // untouched pixel of an accumulate render: its colour may share a dword with a
             // touched neighbour, so fetch it
-            const uint8_t *old = fb_strip + (coff + 3u * (uint32_t)hx);
+            const uint8_t *old = fb_row + (clane + 3u * (uint32_t)hx);
             rgbv = pack_rgb(gload(old), gload(old + 1), gload(old + 2));
         }
         // depth: only pixels that changed (or every live pixel of a fresh tile)
         const bool put = live && (won || zfresh);
         // (TileArgs::store: a cleared frame's colour pass may leave its depth on the chip -- nothing reads the z buffer
         // of such a frame unless a getter or an accumulating render asks, and then the pass is repeated for the depth alone)
-        if (put && st_z) gstore(depth_strip + zoff, zv);
+        if (put && st_z) gstore(depth_strip + (int64_t)r0 * W + zlane, zv);
         if (!DEPTH && st_c) {
-            if (winner_strip && put && with_winner) gstore(winner_strip + zoff, triv);
+            if (winner_strip && put && with_winner) gstore(winner_strip + (int64_t)r0 * W + zlane, triv);
             if (aligned4) {
-                // dword j of the 96-byte row = bytes 4j..4j+3 = pixel p0 = 4j/3 from byte (4j)%3
-                // on, topped up from pixel p0+1
-                const uint32_t j = (uint32_t)hx;
-                const uint32_t p0 = (4u * j) / 3u, o = (4u * j) % 3u;
-                const uint32_t c0 = (uint32_t)__shfl((int)rgbv, (int)(half_base + (p0 & 31u)), 64);
-                const uint32_t c1 = (uint32_t)__shfl((int)rgbv, (int)(half_base + ((p0 + 1u) & 31u)), 64);
-                const uint32_t dw = (c0 >> (8u * o)) | (c1 << (24u - 8u * o));
-                const bool row_live = py_ >= band_y0 && py_ < band_y1;
-                if (j < 24u && row_live && (sx0 * 3 + (int32_t)(4u * j)) < W * 3)
-                    gstore(reinterpret_cast<uint32_t *>(fb_strip + (coff + 4u * j)), dw);
+                const uint32_t c0 = (uint32_t)__builtin_amdgcn_ds_bpermute(perm0, (int)rgbv);
+                const uint32_t c1 = (uint32_t)__builtin_amdgcn_ds_bpermute(perm1, (int)rgbv);
+                const uint32_t dw = (c0 >> csh0) | (c1 << csh1);
+                if (cdw_live && row_live)
+                    gstore(reinterpret_cast<uint32_t *>(fb_row + (clane + 4u * cj)), dw);
             } else if (put) {
-                uint8_t *p = fb_strip + (coff + 3u * (uint32_t)hx);
+                uint8_t *p = fb_row + (clane + 3u * (uint32_t)hx);
                 gstore(p, (uint8_t)(rgbv & 0xFFu));
                 gstore(p + 1, (uint8_t)((rgbv >> 8) & 0xFFu));
                 gstore(p + 2, (uint8_t)((rgbv >> 16) & 0xFFu));
@@ -1506,21 +1527,23 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     // two paths merge.  Returns the steps to run again with the plain closures (every store of a step is
     // repeated, so the second run simply overwrites the first).
     auto shade_steps = [&](auto in_lds, auto pair_tag, uint32_t step_mask) -> uint32_t {
+    constexpr bool RESIDENT = decltype(in_lds)::value;
     uint32_t redo = 0u;
 #pragma unroll 1
     for (int32_t sstep = 0; sstep < NSTEP; sstep++) {
         if (!((step_mask >> sstep) & 1u)) continue;
-        int32_t row[2], py[2];
-        bool live[2], won[2];
+        int32_t py[2];
+        bool row_live[2], live[2], won[2];
         uint32_t wslot[2], zkey[2];
 #pragma unroll
         for (int u = 0; u < 2; u++) {
-            row[u] = sstep * 4 + u * 2 + hrow;  // within the strip
-            py[u] = sy0 + row[u];
-            live[u] = col_live && py[u] >= band_y0 && py[u] < band_y1;
-            const uint32_t s1 = survivor_slot((uint32_t)hx, (uint32_t)row[u], zkey[u]);
+            const uint32_t r0 = (uint32_t)(sstep * 4 + u * 2);  // the pixel's row in the strip: r0 + hrow
+            py[u] = sy0 + (int32_t)r0 + hrow;
+            row_live[u] = py[u] >= band_y0 && py[u] < band_y1;
+            live[u] = col_live && row_live[u];
+            const uint32_t s1 = survivor_slot(r0, zkey[u]);
             won[u] = live[u] && s1 != 0u;
-            wslot[u] = won[u] ? s1 - 1u : 0u;
+            wslot[u] = RESIDENT ? s1 : (won[u] ? s1 - 1u : 0u);  // (shade_two)
         }
         uint32_t tri[2] = { NO_WINNER, NO_WINNER }, rgb[2] = { 0u, 0u };
         float zout[2] = { bits_f32(TR_F32_MIN_BITS), bits_f32(TR_F32_MIN_BITS) };
@@ -1543,7 +1566,8 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
             if (shade_two(in_lds, pair_tag, pxs, py, won, wslot, zout, rgb, tri)) redo |= 1u << sstep;
         }
 #pragma unroll
-        for (int u = 0; u < 2; u++) store_pixel(row[u], py[u], live[u], won[u], zout[u], rgb[u], tri[u], true);
+        for (int u = 0; u < 2; u++)
+            store_pixel((uint32_t)(sstep * 4 + u * 2), row_live[u], live[u], won[u], zout[u], rgb[u], tri[u], true);
     }
     return redo;
     };
