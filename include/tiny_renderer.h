@@ -166,6 +166,33 @@ typedef struct tr_frame_params {
     float look_from[3], look_at[3], up[3];
 } tr_frame_params;
 int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, void *const *frame_buffers_device);
+/* Instanced rendering (nothing of the kind upstream): draw the scene's mesh many times, each copy placed by one entry
+ * of a table.  Instance k draws every polygon of the mesh with each position component p replaced by
+ *     fl(fl(p * scale) + offset)         -- a multiply, then an add, each rounded once (no fused multiply-add)
+ * and the mesh's own normals and texture coordinates.  Polygons are drawn in instance-major order: instance k,
+ * triangle t is polygon k * n_tri + t -- the winner tap, the depth test's tie order and the culling see the mesh
+ * concatenated n_instances times.  So a scene with table T renders bit for bit what a scene created from that
+ * concatenated, host-transformed mesh renders, in every pipeline.  No rotations: normals are not transformed.
+ * n_instances == 0 (instances may then be NULL) draws the mesh itself, untransformed -- the default, and NOT the same as
+ * one instance {0, 0, 0, 1}: -0.0 * 1 + 0 is +0.0.  n_tri * n_instances must stay below 0xFFFFFFF0 (TR_E_INVALID).
+ * The table is scene state like the camera: renders issued after the call draw it; frames issued before (also those
+ * tr_scene_render holds back to fuse) keep the one they were issued with.  It is copied: the caller may reuse its
+ * memory at once.  A table larger than the scene has seen grows the scene's record pools as tr_scene_create would
+ * size them for the concatenated mesh (and waits for the scene's queued work to do so).  Errors change nothing. */
+typedef struct tr_instance {
+    float offset[3];
+    float scale;
+} tr_instance; /* 16 bytes */
+int tr_scene_set_instances(tr_scene *s, uint32_t n_instances, const tr_instance *instances);
+/* tr_scene_render_frames with a table per frame: frame i is exactly
+ *     tr_scene_set_instances(s, n_instances, instances + i * n_instances); tr_scene_clear; set_light_direction;
+ *     set_camera; tr_scene_render
+ * (still one fused launch per kernel for the frames of a group).  The scene is left with the last frame's table
+ * current; tr_scene_select_frame makes a kept frame's table current with its light and camera.  Plain
+ * tr_scene_render_frames draws the scene's current table in every frame. */
+int tr_scene_render_frames_instanced(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
+                                     const tr_instance *instances /* n_frames * n_instances */,
+                                     void *const *frame_buffers_device);
 int tr_scene_frames_per_launch(tr_scene *s); /* frames per group of this scene */
 int tr_scene_frames_kept(tr_scene *s);       /* frames of the last tr_scene_render_frames call that still exist
                                                 (0 after a tr_scene_render) */

@@ -61,6 +61,11 @@ class FrameParams(C.Structure):
                 ("up", C.c_float * 3)]
 
 
+class Instance(C.Structure):
+    """tr_instance (include/tiny_renderer.h): one placement of the mesh, p * scale + offset."""
+    _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float)]
+
+
 class BandTiles(C.Structure):
     """tr_band_tiles (include/tiny_renderer.h): a scene's band of a frame buffer, tile by tile."""
     _fields_ = [("frame_buffer_device", C.c_void_p), ("clean_device", C.c_void_p), ("width", C.c_uint32),
@@ -91,6 +96,8 @@ SYMBOLS = {
     "tr_scene_render": (C.c_int, [C.c_void_p]),
     "tr_scene_set_auto_group": (C.c_int, [C.c_void_p, C.c_int]),
     "tr_scene_render_frames": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_instances": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_render_frames_instanced": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_frames_per_launch": (C.c_int, [C.c_void_p]),
     "tr_scene_frames_kept": (C.c_int, [C.c_void_p]),
     "tr_scene_select_frame": (C.c_int, [C.c_void_p, C.c_uint32]),

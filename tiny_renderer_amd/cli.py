@@ -36,9 +36,13 @@ def main(argv=None):
                     help="--gpus N: how the bands travel (ShardedScene): torch = RCCL all-gather through torch.distributed, rccl = "
                          "the library's own RCCL communicator, peer / peer-sparse = the library's peer transport (these two also "
                          "run with several ranks on one GPU)")
+    ap.add_argument("--instances", type=int, default=1,
+                    help="draw the model N x N times, scaled by 1/N on a grid (instanced rendering; 1 = the model itself)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.instances < 1:
+        ap.error("--instances must be >= 1")
 
     # --gpus N > 1 outside a launcher: start the N ranks from here, before anything touches a GPU
     world_env = os.environ.get("WORLD_SIZE")
@@ -94,6 +98,9 @@ def main(argv=None):
         scene = ShardedScene(args.width, args.height, mesh, texs, args.pipeline, device=local, exchange=args.exchange)
     else:
         scene = T.Scene(args.width, args.height, mesh, texs, args.pipeline, device=args.device)
+    if args.instances > 1:
+        say("instances: %d x %d grid" % (args.instances, args.instances))
+        scene.set_instances(T.grid_instances(args.instances))
     rc = _run(args, T, scene, sharded, rank, say)
     if sharded:
         import torch.distributed as dist

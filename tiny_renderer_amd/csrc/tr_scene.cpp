@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -161,8 +162,27 @@ struct tr_scene {
     float at[3] = { 0.0f, 0.0f, 0.0f };
     float up[3] = { 0.0f, 1.0f, 0.0f };
 
-    DevMesh mesh = {};
+    DevMesh mesh = {};         // what a pass rendered now draws: the mesh under the current instance table
     DevTextures tex = {};
+    // Instance tables (tr_scene_set_instances).  A table is copied to the device once, into a block that is never
+    // written again while anybody may render with it: the scene's current table, frames held back, the frames a
+    // replay or a depth-only repeat may render again (InstRef), and work already queued -- each block has one event
+    // per stream that the chains reading it run on, recorded behind the last such chain.  A block is reused (or freed)
+    // only when no InstRef holds it and those events have completed.
+    struct InstBlock {
+        float *d = nullptr;      // cap x {offset xyz, scale}
+        uint32_t cap = 0;
+        hipEvent_t used[3] = {}; // behind the last chain on the main stream, setup_stream, setup_stream2 that read it
+    };
+    struct InstRef {
+        std::shared_ptr<InstBlock> blk;  // null: no table (the mesh itself)
+        uint32_t off = 0, n = 0;         // entries [off, off + n) of the block
+    };
+    InstRef inst;                    // the current table
+    std::vector<std::shared_ptr<InstBlock>> inst_blocks;  // every block the scene owns
+    uint32_t n_rows = 0;             // polygons of the mesh (rows of d_tri)
+    uint64_t poly_cap = 0;           // polygons of a pass the per-pass record arrays hold
+    bool auto_bin_cap = true;        // tr_options.bin_capacity was 0: the pools follow the polygon count
     DevFrame frame = {};       // the rows this scene owns (colour passes)
     DevFrame frame_full = {};  // the whole frame: depth passes fill the entire shadow buffer, whose
                                // lookups are in light space and can land anywhere (shader.rs:774-778)
@@ -206,6 +226,7 @@ struct tr_scene {
     uint64_t pass_seq = 0;
     struct PendingTile {
         int fs, tile_waves, shared, kernel_id;
+        uint32_t n_poly = 0;        // polygons of the pass
         bool fused_single = false;  // the pass starts from cleared targets without a winner tap: the fused launches' kernels (launch_tile)
         uint64_t p_seq;
         TileArgs args;
@@ -247,6 +268,7 @@ struct tr_scene {
         // ensure_depth() repeats the colour pass for the depth alone when somebody wants the z buffer.
         bool z_deferred = false;
         tr_frame_params z_params = {};
+        InstRef z_inst;  // ... and the instance table it was rendered with
     };
     std::vector<FrameSlot> slots;
     int cur_slot = 0;
@@ -266,6 +288,7 @@ struct tr_scene {
         bool in_flight = false;
         uint32_t pool_cap = 0, frames = 0;  // what the set was allocated for
         uint32_t g = 0;                    // frames of the group it holds now
+        uint32_t n_poly = 0;               // polygons of its largest frame (frames may draw different instance tables)
         int tile_waves[2] = { 4, 4 }, shared[2] = { 0, 0 };  // the tile kernels' layout, per pass (decided with the setup)
         bool chain_on_main = false;        // its setup was queued on the main stream itself (nothing was in flight)
         uint32_t *lit = nullptr;           // [frame] x lit_words: the frames' lit texel images (scenes with the lit path)
@@ -283,6 +306,7 @@ struct tr_scene {
     struct DeferredFrame {
         tr_frame_params p;
         uint8_t *fb;  // the colour target that was current at its render()
+        InstRef inst; // the instance table that was current at its render()
     };
     std::vector<DeferredFrame> deferred;
     bool auto_group = true;
@@ -293,6 +317,7 @@ struct tr_scene {
         std::vector<tr_frame_params> params;
         std::vector<void *> fbs;  // the caller's buffers, or empty
         std::vector<int> slot;
+        std::vector<InstRef> inst;  // their instance tables
         uint64_t first_seq = 0;   // pass number of the first of them
     } tail;
     bool last_was_group = false;
@@ -344,7 +369,8 @@ struct tr_scene {
         float light[3], from[3], at[3], up[3];
         bool z_fb_cleared, shadow_cleared;
         bool valid;
-    } last = {};
+        InstRef inst;
+    } last;
 
     bool profiling = false;
     std::vector<EventPair> events;
@@ -481,6 +507,107 @@ int need_z(tr_scene *s, int k)
     return TR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Instance tables
+// ---------------------------------------------------------------------------------------------
+
+// What a pass drawing under table `r` reads (DevMesh, tr_types.h).
+DevMesh mesh_of(const tr_scene *s, const tr_scene::InstRef &r)
+{
+    DevMesh m = {};
+    m.tri = s->d_tri;
+    m.n_tri = s->n_rows;
+    if (r.n) {
+        m.inst = r.blk->d + 4u * (size_t)r.off;
+        m.n_rows = s->n_rows;
+        m.n_tri = s->n_rows * r.n;  // (below 0xFFFFFFF0: checked by set_instances)
+    }
+    return m;
+}
+
+// Makes `r` the scene's current table.
+void use_inst(tr_scene *s, const tr_scene::InstRef &r)
+{
+    s->inst = r;
+    s->mesh = mesh_of(s, r);
+}
+
+// A chain that reads table `m` (a DevMesh of mesh_of) has been queued on `st`: the block may not be written or freed
+// until what is queued there now has run.  (No table: nothing to do -- the scene without instances queues nothing more.)
+int note_inst_use(tr_scene *s, const DevMesh &m, hipStream_t st)
+{
+    if (!m.inst) return TR_OK;
+    const int k = st == s->setup_stream ? 1 : st == s->setup_stream2 ? 2 : 0;
+    for (const std::shared_ptr<tr_scene::InstBlock> &b : s->inst_blocks)
+        if (m.inst >= b->d && m.inst < b->d + 4u * (size_t)b->cap) {
+            if (!b->used[k]) HIP_TRY(hipEventCreateWithFlags(&b->used[k], hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(b->used[k], st));
+            return TR_OK;
+        }
+    return tr::fail(TR_E_INVALID, "instance table not owned by the scene");
+}
+
+void free_inst_block(tr_scene::InstBlock &b)
+{
+    for (hipEvent_t &e : b.used) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    if (b.d) (void)hipFree(b.d);
+    b.d = nullptr;
+    b.cap = 0;
+}
+
+// Waits for the chains that read block `b` (a block nobody holds any more: no new ones can be queued).
+int inst_block_idle(tr_scene::InstBlock &b)
+{
+    for (hipEvent_t e : b.used)
+        if (e) HIP_TRY(hipEventSynchronize(e));
+    return TR_OK;
+}
+
+// Copies `n` entries of `h` into a block of their own: one nobody holds whose readers have run, else a new one.
+int upload_instances(tr_scene *s, uint32_t n, const float *h, tr_scene::InstRef &out)
+{
+    std::shared_ptr<tr_scene::InstBlock> pick;
+    // free blocks: prefer one whose readers have finished; a free block too small for the table is given back
+    for (size_t i = 0; i < s->inst_blocks.size();) {
+        std::shared_ptr<tr_scene::InstBlock> &b = s->inst_blocks[i];
+        if (b.use_count() > 1) {
+            i++;
+            continue;
+        }
+        if (b->cap < n) {
+            int st = inst_block_idle(*b);
+            if (st != TR_OK) return st;
+            free_inst_block(*b);
+            s->inst_blocks.erase(s->inst_blocks.begin() + (long)i);
+            continue;
+        }
+        bool done = true;
+        for (hipEvent_t e : b->used) done = done && (!e || hipEventQuery(e) == hipSuccess);
+        if (!pick || done) pick = b;
+        if (done) break;
+        i++;
+    }
+    if (pick) {
+        int st = inst_block_idle(*pick);  // (usually long done)
+        if (st != TR_OK) return st;
+    } else {
+        pick = std::make_shared<tr_scene::InstBlock>();
+        int st = dev_alloc(&pick->d, 4u * (size_t)n);
+        if (st != TR_OK) return st;
+        pick->cap = n;
+        s->inst_blocks.push_back(pick);
+    }
+    HIP_TRY(hipMemcpy(pick->d, h, 16u * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(nullptr));  // (the scene's streams do not wait for the null stream)
+    out.blk = pick;
+    out.off = 0;
+    out.n = n;
+    return TR_OK;
+}
+
 hipEvent_t take_event(tr_scene *s)
 {
     if (!s->event_pool.empty()) {
@@ -552,13 +679,13 @@ int launch_pending_tile(tr_scene *s, const tr_scene::PendingTile &t)
 {
     int status = TR_OK;
     if (!s->profiling) {
-        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, s->mesh.n_tri, nullptr, 0, s->stream, nullptr, s->ev_tile[t.p_seq % RING], 0u,
+        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, nullptr, 0, s->stream, nullptr, s->ev_tile[t.p_seq % RING], 0u,
                              t.fused_single);
         if (rc) status = launch_status(rc, "k_tile");
         if (rc) s->broken = true;  // (its chain has run: the set's counters were not zeroed, the pass's ranges never consumed)
     } else {
         EventPair ep = { take_event(s), take_event(s), t.kernel_id, 1u };
-        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, s->mesh.n_tri, nullptr, 0, s->stream, ep.a, ep.b, 0u, t.fused_single);
+        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, nullptr, 0, s->stream, ep.a, ep.b, 0u, t.fused_single);
         if (rc) status = launch_status(rc, "k_tile");
         if (rc) s->broken = true;
         s->events.push_back(ep);
@@ -776,10 +903,13 @@ int recover_from_overflow(tr_scene *s, unsigned long long first_bad_seq)
     memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
     memcpy(s->light, s->last.light, 12); memcpy(s->from, s->last.from, 12);
     memcpy(s->at, s->last.at, 12); memcpy(s->up, s->last.up, 12);
+    const tr_scene::InstRef inst_now = s->inst;
+    use_inst(s, s->last.inst);
     const bool z_now = s->z_fb_cleared, sh_now = s->shadow_cleared;
     s->z_fb_cleared = true;
     s->shadow_cleared = s->last.shadow_cleared;
     st = render_frame(s);
+    use_inst(s, inst_now);
     // a clear() issued after the overflowing render stays pending
     s->z_fb_cleared = s->z_fb_cleared || z_now;
     s->shadow_cleared = s->shadow_cleared || sh_now;
@@ -905,18 +1035,18 @@ void lit_args(const tr_scene *s, uint32_t *lit, SetupArgs &sa, TileArgs &ta)
 // tile go by that total; whether its waves share a tile's bin still goes by the size of ONE frame, which is
 // what decides how unevenly the polygons fall on a tile's columns (800^2 african_head, 16 frames per launch,
 // k_tile per frame: 4 waves columns 4.6 us, 4 waves shared 3.3, 8 shared 3.6, 16 shared 4.4) ...
-void tile_layout(const tr_scene *s, uint64_t tiles_in_launch, uint32_t tiles_per_frame, int &tile_waves, int &shared)
+void tile_layout(const tr_scene *s, uint64_t tiles_in_launch, uint32_t tiles_per_frame, uint32_t n_poly, int &tile_waves, int &shared)
 {
     tile_waves = s->tile_waves ? (int)s->tile_waves : tiles_in_launch <= 1024u ? 16 : tiles_in_launch <= 4608u ? 8 : 4;
     // ... or by how many polygons a tile gets: many small ones are visited once per tile instead of once per
     // column they touch.  k_tile per frame, columns -> shared, polygons per tile of the frame: 8192^2 x64 grid
     // specular (9.8) 371 -> 350 us, the same with phong 259 -> 230, 4096^2 x16 (9.8) 66.9 -> 60.0, x9 (5.5)
     // 50.4 -> 47.6, x4 (2.5) 38.9 -> 38.5, one model (0.6) 33.5 -> 35.4
-    const bool dense = (uint64_t)s->mesh.n_tri >= 3ull * (tiles_per_frame ? tiles_per_frame : 1u);
+    const bool dense = (uint64_t)n_poly >= 3ull * (tiles_per_frame ? tiles_per_frame : 1u);
     shared = s->tile_mode ? (s->tile_mode == 2 ? 1 : 0) : tile_mode_auto((tiles_per_frame <= 2048u || dense) ? 1 : 0);
     // the shared keys pack polygon id and bin slot into 32 bits: beyond their fields, resolve by columns.  Decided
     // HERE, once per pass: k_setup prepares the pairs' masks for the form the tile kernel will run (SetupArgs::cells)
-    if (s->mesh.n_tri > (1u << 20)) shared = 0;  // (a TILE with more records than the slot field holds resolves by columns: k_tile)
+    if (n_poly > (1u << 20)) shared = 0;  // (a TILE with more records than the slot field holds resolves by columns: k_tile)
 }
 
 // May a cleared frame's colour pass leave its depth on the chip?  Not with the winner tap or the tile stamps (single
@@ -969,7 +1099,8 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
 
     const uint32_t n_tiles_pass = frame.ntx * frame.nty;
     tr_scene::PendingTile pt;
-    tile_layout(s, n_tiles_pass, n_tiles_pass, pt.tile_waves, pt.shared);
+    tile_layout(s, n_tiles_pass, n_tiles_pass, s->mesh.n_tri, pt.tile_waves, pt.shared);
+    pt.n_poly = s->mesh.n_tri;
 
     SetupArgs sa = {};   // (every member defined: the kernels take the struct by value)
     sa.mesh = s->mesh;
@@ -1024,6 +1155,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
             slot.z_deferred = true;
             memcpy(slot.z_params.light, s->light, 12); memcpy(slot.z_params.look_from, s->from, 12);
             memcpy(slot.z_params.look_at, s->at, 12); memcpy(slot.z_params.up, s->up, 12);
+            slot.z_inst = s->inst;
         } else {
             // (an accumulating render has had the slot's depth made real before it came here: ensure_depth, tr_scene_render)
             slot.z_deferred = false;
@@ -1084,6 +1216,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
         }
         HIP_TRY(hipEventRecord(s->ev_setup[p_seq % RING], chain));
     }
+    if ((st = note_inst_use(s, sa.mesh, chain)) != TR_OK) return st;
     pt.fs = depth_only ? p.fs : tile_fs(s, p.fs);
     pt.kernel_id = depth_pass ? K_TILE_DEPTH : K_TILE;
     pt.p_seq = p_seq;
@@ -1156,11 +1289,14 @@ int ensure_depth(tr_scene *s)
     memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
     const tr_frame_params &q = slot.z_params;
     memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+    const tr_scene::InstRef inst_now = s->inst;
+    use_inst(s, slot.z_inst);
     const PipelineDesc &pd = kPipelines[s->pipeline];
     const int host_status = s->host_status;
     st = run_pass(s, pd.pass[pd.n_passes - 1], true);
     if (st == TR_OK) st = submit_pending_tiles(s);
     s->host_status = host_status;
+    use_inst(s, inst_now);
     memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
     return st;
 }
@@ -1229,7 +1365,7 @@ int ensure_slots(tr_scene *s, uint32_t n)
 }
 
 size_t group_bins_per_frame(const tr_scene *s) { return (size_t)s->pool_cap * s->rec_pieces; }
-size_t group_recs_per_frame(const tr_scene *s) { return (size_t)(s->mesh.n_tri ? s->mesh.n_tri : 1u) * s->rec_pieces; }
+size_t group_recs_per_frame(const tr_scene *s) { return (size_t)(s->poly_cap ? s->poly_cap : 1u) * s->rec_pieces; }
 size_t group_counts_per_frame(const tr_scene *s) { return (size_t)s->n_tiles_full + 16u; }
 
 void free_group_set(tr_scene::GroupSet &gs);
@@ -1362,7 +1498,7 @@ static bool use_work_units()
 // lengths in page-locked memory: the frame that needs most decides (a fused launch's frames share the grid).
 static uint32_t group_units(const tr_scene *s, const tr_scene::GroupSet &gs, uint32_t pi, uint32_t n_tiles_pass)
 {
-    if (!gs.h_lens || s->mesh.n_tri == 0 || gs.g > (uint32_t)GROUP_MAX) return 0u;  // (no polygons: no k_bin)
+    if (!gs.h_lens || gs.n_poly == 0 || gs.g > (uint32_t)GROUP_MAX) return 0u;  // (no polygons: no k_bin)
     uint32_t lens[GROUP_MAX * LEN_WORDS];
     const volatile uint32_t *w = gs.h_lens + (size_t)pi * gs.frames * LEN_WORDS;
     for (uint32_t i = 0; i < gs.g * LEN_WORDS; i++) lens[i] = w[i];
@@ -1370,9 +1506,11 @@ static uint32_t group_units(const tr_scene *s, const tr_scene::GroupSet &gs, uin
 }
 
 // Queues the setup of g <= frames-per-group cleared frames, one launch per kernel and pass.  Frame j takes
-// light and camera from p[j], its targets from slot slot_of[j] and its colour buffer from fbs[j] (fbs == null:
-// the slot's own).  The tile kernels follow with submit_groups.
-int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int *slot_of, uint32_t g, bool forget_callers_buffers = false)
+// light and camera from p[j], its instance table from insts[j] (insts == null: the scene's current one), its targets
+// from slot slot_of[j] and its colour buffer from fbs[j] (fbs == null: the slot's own).  The tile kernels follow with
+// submit_groups.
+int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *insts, void *const *fbs, const int *slot_of, uint32_t g,
+              bool forget_callers_buffers = false)
 {
     const PipelineDesc &pd = kPipelines[s->pipeline];
     const uint32_t np = (uint32_t)pd.n_passes;
@@ -1403,9 +1541,15 @@ int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int
     const SetupArgs *d_setup = reinterpret_cast<const SetupArgs *>(gs.d_tables);
     const TileArgs *d_tile = reinterpret_cast<const TileArgs *>(gs.d_tables + (size_t)np * G * sizeof(SetupArgs));
 
+    // the frames share the launches' grids: the one with most polygons sizes them
+    uint32_t n_poly = 0;
+    for (uint32_t j = 0; j < g; j++) {
+        const uint32_t n = mesh_of(s, insts ? insts[j] : s->inst).n_tri;
+        n_poly = n > n_poly ? n : n_poly;
+    }
     for (uint32_t pi = 0; pi < np; pi++) {
         const DevFrame &fr = pd.pass[pi].fs == FS_DEPTH ? s->frame_full : s->frame;
-        tile_layout(s, (uint64_t)fr.ntx * fr.nty * g, fr.ntx * fr.nty, gs.tile_waves[pi], gs.shared[pi]);
+        tile_layout(s, (uint64_t)fr.ntx * fr.nty * g, fr.ntx * fr.nty, n_poly, gs.tile_waves[pi], gs.shared[pi]);
     }
     float keep[12];
     memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
@@ -1417,6 +1561,8 @@ int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int
         tr_scene::FrameSlot &slot = s->slots[(size_t)slot_of[j]];
         slot.z_deferred = defer_depth(s);   // (what the slot's z is then: this frame)
         slot.z_params = p[j];
+        slot.z_inst = insts ? insts[j] : s->inst;
+        const DevMesh mesh = mesh_of(s, slot.z_inst);
         uint8_t *fb = fbs ? (uint8_t *)fbs[j] : nullptr;
         const bool callers = fb != nullptr;
         if (!fb) st = slot_own_fb(s, slot_of[j], &fb);
@@ -1433,7 +1579,7 @@ int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int
             st = pass_uniforms(s, pass, sa.u);
             if (st != TR_OK) break;
             const DevFrame &frame = depth_pass ? s->frame_full : s->frame;
-            sa.mesh = s->mesh;
+            sa.mesh = mesh;
             sa.frame = frame;
             sa.tile_count = gs.count + e * group_counts_per_frame(s);
             sa.recs = gs.recs + e * group_recs_per_frame(s);
@@ -1482,7 +1628,10 @@ int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int
                            hipMemcpyHostToDevice, chain));
     for (uint32_t pi = 0; pi < np; pi++) {
         const PassDesc &pass = pd.pass[pi];
-        const SetupArgs &sa0 = h_setup[(size_t)pi * G];
+        // (the launches' shape: the first frame's arguments with the group's largest polygon count; every frame's
+        // kernels read their own entry of the table)
+        SetupArgs sa0 = h_setup[(size_t)pi * G];
+        sa0.mesh.n_tri = n_poly;
         const uint32_t n_tiles_pass = sa0.frame.ntx * sa0.frame.nty;
         EventPair ep = { nullptr, nullptr, K_SETUP, g }, eo = { nullptr, nullptr, K_ORDER, g }, eb = { nullptr, nullptr, K_BIN, g };
         if (s->profiling) {
@@ -1507,13 +1656,16 @@ int run_group(tr_scene *s, const tr_frame_params *p, void *const *fbs, const int
         if (s->profiling) {
             s->events.push_back(ep);
             s->events.push_back(eo);
-            if (s->mesh.n_tri) s->events.push_back(eb);
+            if (n_poly) s->events.push_back(eb);
             else { s->event_pool.push_back(eb.a); s->event_pool.push_back(eb.b); }
         }
     }
     HIP_TRY(hipEventRecord(gs.ev_setup, chain));
+    for (uint32_t j = 0; j < g; j++)
+        if ((st = note_inst_use(s, h_setup[j].mesh, chain)) != TR_OK) return st;
     gs.chain_on_main = chain_on_main;
     gs.g = g;
+    gs.n_poly = n_poly;
     gs.in_flight = true;
     s->pass_seq += (uint64_t)g * np;
     s->group_seq++;
@@ -1550,7 +1702,7 @@ int submit_group_tiles(tr_scene *s, bool wait_for_setup)
         // Workgroups per frame: exactly the pass's work units when its chain has completed (the host has seen the event:
         // the lists' lengths are in page-locked memory), else one per tile
         const uint32_t units = (chain_done && use_work_units()) ? group_units(s, gs, pi, ta0.frame.ntx * ta0.frame.nty) : 0u;
-        int rc = launch_tile(tile_fs(s, pass.fs), ta0, tile_waves, shared, s->mesh.n_tri, d_tile + (size_t)pi * G, g, s->stream, ep.a,
+        int rc = launch_tile(tile_fs(s, pass.fs), ta0, tile_waves, shared, gs.n_poly, d_tile + (size_t)pi * G, g, s->stream, ep.a,
                              (!s->profiling && last) ? gs.ev_tile : ep.b, units);
         if (rc) {
             s->broken = true;  // (the group's chains have run: counters not zeroed, ranges never consumed)
@@ -1654,6 +1806,8 @@ int flush_deferred(tr_scene *s, bool hold_back)
         uint8_t *fb_now = s->d_fb;
         const tr_frame_params &q = fr[0].p;
         memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+        const tr_scene::InstRef inst_now = s->inst;
+        use_inst(s, fr[0].inst);
         s->z_fb_cleared = s->shadow_cleared = true;
         if (fr[0].fb != fb_now) st = use_slot(s, s->cur_slot, fr[0].fb == s->slots[(size_t)s->cur_slot].fb ? nullptr : fr[0].fb);
         if (st == TR_OK) st = render_frame(s);
@@ -1665,6 +1819,7 @@ int flush_deferred(tr_scene *s, bool hold_back)
         s->z_fb_cleared = s->z_fb_cleared || z_now;
         s->shadow_cleared = s->shadow_cleared || sh_now;
         memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
+        use_inst(s, inst_now);
         return st;
     }
     // per-frame tile kernels issued before these frames go first (same targets)
@@ -1674,11 +1829,13 @@ int flush_deferred(tr_scene *s, bool hold_back)
     if (hold_back && (st = prepare_long_runs(s, true)) != TR_OK) return st;  // (a loop that fills groups: see there)
     if ((st = ensure_slots(s, G < g ? g : G)) != TR_OK) return st;
     tr_frame_params params[GROUP_MAX];
+    tr_scene::InstRef insts[GROUP_MAX];
     void *fbs[GROUP_MAX];
     int slot_of[GROUP_MAX];
     std::vector<const void *> wanted(g);
     for (uint32_t j = 0; j < g; j++) {
         params[j] = fr[j].p;
+        insts[j] = fr[j].inst;
         wanted[j] = fr[j].fb;
     }
     // which slot and which colour target every frame gets (tr_plan.h, plan_deferred): the last one the current targets,
@@ -1692,13 +1849,14 @@ int flush_deferred(tr_scene *s, bool hold_back)
         if (targets[j].unreplayable)
             s->unreplayable_seq = s->pass_seq + (uint64_t)(j + 1u) * (uint64_t)kPipelines[s->pipeline].n_passes;
     }
-    st = run_group(s, params, fbs, slot_of, g);
+    st = run_group(s, params, insts, fbs, slot_of, g);
     if (st == TR_OK) st = hold_back ? submit_groups(s, false) : finish_groups(s);
     return st;
 }
 
-// n cleared frames, frame i into slot i % G; afterwards the last one is the scene's current frame.
-int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const *fbs)
+// n cleared frames, frame i into slot i % G, drawing instance table insts[i] (insts == null: the current one);
+// afterwards the last one is the scene's current frame.
+int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_scene::InstRef *insts, void *const *fbs)
 {
     int st = submit_pending(s);  // per-frame renders issued before go first
     if (st != TR_OK) return st;
@@ -1726,6 +1884,7 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const
             if ((st = use_slot(s, (int)(i % G), fbs ? (uint8_t *)fbs[i] : nullptr, fbs != nullptr)) != TR_OK) return st;
             memcpy(s->light, p[i].light, 12); memcpy(s->from, p[i].look_from, 12);
             memcpy(s->at, p[i].look_at, 12); memcpy(s->up, p[i].up, 12);
+            if (insts) use_inst(s, insts[i]);
             s->z_fb_cleared = s->shadow_cleared = true;
             if ((st = render_frame(s)) != TR_OK) return st;
         }
@@ -1735,7 +1894,8 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const
         for (size_t k = 0; k < sizes.size(); i0 += sizes[k], k++) {
             const uint32_t g = sizes[k];
             for (uint32_t j = 0; j < g; j++) slot_of[j] = (int)((i0 + j) % S);
-            st = run_group(s, p + i0, fbs ? fbs + i0 : nullptr, slot_of, g, fbs && !(s->flags & TR_OPT_TRUST_FRAME_BUFFERS));
+            st = run_group(s, p + i0, insts ? insts + i0 : nullptr, fbs ? fbs + i0 : nullptr, slot_of, g,
+                           fbs && !(s->flags & TR_OPT_TRUST_FRAME_BUFFERS));
             if (st == TR_OK) st = submit_groups(s, false);
             if (st != TR_OK) {
                 // (a singular camera in frame i0 .. i0 + g - 1, or the device refused a launch): the groups before are
@@ -1745,6 +1905,7 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const
                 s->tail.params.clear();
                 s->tail.fbs.clear();
                 s->tail.slot.clear();
+                s->tail.inst.clear();
                 s->last_was_group = true;
                 s->last.valid = false;
                 return st;
@@ -1754,6 +1915,7 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const
         // the scene now stands where the per-frame calls would have left it
         const tr_frame_params &l = p[n - 1];
         memcpy(s->light, l.light, 12); memcpy(s->from, l.look_from, 12); memcpy(s->at, l.look_at, 12); memcpy(s->up, l.up, 12);
+        if (insts) use_inst(s, insts[n - 1]);
         s->z_fb_cleared = s->shadow_cleared = false;
         if ((st = use_slot(s, (int)((n - 1) % S), fbs ? (uint8_t *)fbs[n - 1] : nullptr)) != TR_OK) return st;
     }
@@ -1763,6 +1925,8 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, void *const
     s->tail.fbs.clear();
     if (fbs) s->tail.fbs.assign(fbs + (n - kept), fbs + n);
     s->tail.slot.resize(kept);
+    s->tail.inst.assign(kept, s->inst);
+    if (insts) s->tail.inst.assign(insts + (n - kept), insts + n);
     for (uint32_t k = 0; k < kept; k++) s->tail.slot[k] = (int)((n - kept + k) % (s->d_winner ? G : S));
     s->tail.first_seq = first_seq + (uint64_t)(n - kept) * np;
     if (fbs && n > kept) s->unreplayable_seq = s->tail.first_seq;  // older frames' buffers: theirs for good
@@ -1778,19 +1942,23 @@ int replay_tail(tr_scene *s)
     if (kept == 0) return TR_OK;
     const int cur = s->cur_slot;
     uint8_t *cur_fb = s->d_fb;
+    const tr_scene::InstRef inst_now = s->inst;
     int st = TR_OK;
     if (s->d_winner) {
         for (uint32_t k = 0; k < kept && st == TR_OK; k++) {
             st = use_slot(s, s->tail.slot[k], s->tail.fbs.empty() ? nullptr : (uint8_t *)s->tail.fbs[k]);
             const tr_frame_params &q = s->tail.params[k];
             memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+            use_inst(s, s->tail.inst[k]);
             s->z_fb_cleared = s->shadow_cleared = true;
             if (st == TR_OK) st = render_frame(s);
         }
     } else {
-        st = run_group(s, s->tail.params.data(), s->tail.fbs.empty() ? nullptr : s->tail.fbs.data(), s->tail.slot.data(), kept);
+        st = run_group(s, s->tail.params.data(), s->tail.inst.data(), s->tail.fbs.empty() ? nullptr : s->tail.fbs.data(),
+                       s->tail.slot.data(), kept);
         if (st == TR_OK) st = finish_groups(s);
     }
+    use_inst(s, inst_now);
     if (st != TR_OK) return st;
     return use_slot(s, cur, cur_fb == s->slots[(size_t)cur].fb ? nullptr : cur_fb);  // the selection the caller had
 }
@@ -1802,6 +1970,68 @@ int find_pipeline(const char *name)
     for (int i = 0; i < P_COUNT; i++)
         if (!strcmp(name, kPipelines[i].name)) return i;
     return -1;
+}
+
+// Records in a pass's pool for `n_poly` polygons: tr_options.bin_capacity, or 0 = automatic -- twice an estimate from
+// the frame and the polygon count: a model that fills half the frame with half of its polygons facing the viewer has
+// polygons with boxes of side s = sqrt(2 W H / n), each meeting (1 + s/128)(1 + s/16) tiles of 128x16: 5.0 pairs
+// per polygon for the reference's model at 4096^2 (measured 2.4), 1.32 for its 8x8 grid at 8192^2 (measured
+// 1.29) -- at least 65 536 records (6 MiB) and at most 16 Mi; a pass that wants more makes the pools grow (and is
+// rendered again)
+uint32_t pool_cap_for(uint32_t width, uint32_t height, uint64_t n_poly, uint64_t bin_capacity)
+{
+    uint64_t cap = bin_capacity;
+    if (!cap) {
+        const double n = (double)(n_poly ? n_poly : 1u);
+        const double side = sqrt(2.0 * (double)width * (double)height / n);
+        const double pairs = 0.5 * (1.0 + side / (double)TILE_W) * (1.0 + side / (double)TILE_H) * n;
+        cap = (uint64_t)(2.0 * pairs);
+        cap = cap < 65536u ? 65536u : cap > (16u << 20) ? (16u << 20) : cap;
+    }
+    if (cap < 64) cap = 64;
+    if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
+    return (uint32_t)cap;
+}
+
+// A table of n instances is about to be drawn: the per-pass record arrays and (automatic bin capacity) the pools grow to
+// what tr_scene_create gives the mesh replicated n times.  Never shrinks.  Waits for the scene's queued work when
+// something grows (a new, larger table: not the steady state).
+int grow_for_instances(tr_scene *s, uint32_t n)
+{
+    const uint64_t polys = (uint64_t)s->n_rows * (n ? n : 1u);
+    const uint32_t cap = s->auto_bin_cap ? pool_cap_for(s->width, s->height, polys, 0) : s->pool_cap;
+    if (polys <= s->poly_cap && cap <= s->pool_cap) return TR_OK;
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->setup_stream));
+    HIP_TRY(hipStreamSynchronize(s->setup_stream2));
+    for (tr_scene::GroupSet &gs : s->grp) gs.in_flight = false;  // (their tile kernels have run)
+    if (polys > s->poly_cap) {
+        s->poly_cap = polys;
+        for (int k = 0; k < LOOKAHEAD; k++) {
+            dev_free(s->d_recs[k]);
+            if ((st = dev_alloc(&s->d_recs[k], (size_t)polys * s->rec_pieces))) return st;
+        }
+        for (tr_scene::GroupSet &gs : s->grp) free_group_set(gs);  // (allocated again, larger, when next used)
+    }
+    if (cap > s->pool_cap) {
+        s->pool_cap = cap;
+        for (int k = 0; k < LOOKAHEAD; k++) {
+            dev_free(s->d_bins[k]);
+            if ((st = dev_alloc(&s->d_bins[k], (size_t)s->pool_cap * s->rec_pieces))) return st;
+        }
+        // (the frame groups' bins follow pool_cap when their set is next used)
+    }
+    return TR_OK;
+}
+
+// tr_scene_set_instances / tr_scene_render_frames_instanced: n == 0 is "no table".
+int check_instances(const tr_scene *s, uint32_t n, const void *inst)
+{
+    if (n && !inst) return tr::fail(TR_E_INVALID, "null instance table");
+    if ((uint64_t)s->n_rows * n >= 0xFFFFFFF0ull) return tr::fail(TR_E_INVALID, "too many polygons (mesh polygons x instances)");
+    return TR_OK;
 }
 
 void destroy(tr_scene *s)
@@ -1816,6 +2046,10 @@ void destroy(tr_scene *s)
     }
     for (hipEvent_t e : s->event_pool) (void)hipEventDestroy(e);
     dev_free(s->d_tri);
+    if (s->setup_stream) (void)hipStreamSynchronize(s->setup_stream);
+    if (s->setup_stream2) (void)hipStreamSynchronize(s->setup_stream2);
+    for (const std::shared_ptr<tr_scene::InstBlock> &b : s->inst_blocks) free_inst_block(*b);
+    s->inst_blocks.clear();
     for (int k = 0; k < 4; k++) dev_free(s->d_texel[k]);
     dev_free(s->d_packed);
     for (int k = 0; k < LOOKAHEAD; k++) dev_free(s->d_lit[k]);
@@ -1957,8 +2191,9 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
         if ((st = dev_alloc(&s->d_tri, rows.size()))) return st;
         HIP_TRY(hipMemcpy(s->d_tri, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
     }
-    s->mesh.tri = s->d_tri;
-    s->mesh.n_tri = mesh->n_tri;
+    s->n_rows = mesh->n_tri;
+    s->poly_cap = mesh->n_tri;
+    use_inst(s, tr_scene::InstRef());
 
     // textures: rgb8 -> rgba8 so a texel is one aligned dword fetch
     std::vector<uint32_t> rgba[4];
@@ -2025,17 +2260,8 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
     // per polygon for the reference's model at 4096^2 (measured 2.4), 1.32 for its 8x8 grid at 8192^2 (measured
     // 1.29) -- at least 65 536 records (6 MiB) and at most 16 Mi; a pass that wants more makes the pools grow (and is
     // rendered again)
-    uint64_t cap = o.bin_capacity;
-    if (!cap) {
-        const double n = (double)(mesh->n_tri ? mesh->n_tri : 1u);
-        const double side = sqrt(2.0 * (double)width * (double)height / n);
-        const double pairs = 0.5 * (1.0 + side / (double)TILE_W) * (1.0 + side / (double)TILE_H) * n;
-        cap = (uint64_t)(2.0 * pairs);
-        cap = cap < 65536u ? 65536u : cap > (16u << 20) ? (16u << 20) : cap;
-    }
-    if (cap < 64) cap = 64;
-    if (cap > 0x7FFFFFFFull) cap = 0x7FFFFFFFull;
-    s->pool_cap = (uint32_t)cap;
+    s->auto_bin_cap = o.bin_capacity == 0;
+    s->pool_cap = pool_cap_for(width, height, mesh->n_tri, o.bin_capacity);
     s->rec_pieces = (pipe == P_DARBOUX) ? REC_PIECES_LARGE : REC_PIECES_SMALL;
     for (int k = 0; k < LOOKAHEAD; k++) {
         if ((st = dev_alloc(&s->d_bins[k], (size_t)s->pool_cap * s->rec_pieces))) return st;
@@ -2312,6 +2538,7 @@ int tr_scene_render(tr_scene *s)
     s->last.z_fb_cleared = s->z_fb_cleared;
     s->last.shadow_cleared = s->shadow_cleared;
     s->last.valid = true;
+    s->last.inst = s->inst;
     s->last_was_group = false;
     if (!frame_is_groupable(s)) {
         // frames held back before it go first (it may render onto the last of them)
@@ -2337,6 +2564,7 @@ int tr_scene_render(tr_scene *s)
     memcpy(f.p.light, s->light, 12); memcpy(f.p.look_from, s->from, 12);
     memcpy(f.p.look_at, s->at, 12); memcpy(f.p.up, s->up, 12);
     f.fb = s->d_fb;
+    f.inst = s->inst;
     s->deferred.push_back(f);
     s->z_fb_cleared = s->shadow_cleared = false;  // the frame has consumed the clear
     // (a loop that has filled sixteen groups in a row without anybody looking at a frame is a long run: its groups grow)
@@ -2357,7 +2585,48 @@ int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params
         for (uint32_t i = 0; i < n_frames; i++)
             if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
     HIP_TRY(hipSetDevice(s->device));
-    return render_frames(s, n_frames, frames, frame_buffers_device);
+    return render_frames(s, n_frames, frames, nullptr, frame_buffers_device);
+}
+
+int tr_scene_set_instances(tr_scene *s, uint32_t n_instances, const tr_instance *instances)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    int st = check_instances(s, n_instances, instances);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((st = grow_for_instances(s, n_instances)) != TR_OK) return st;
+    tr_scene::InstRef r;
+    if (n_instances && (st = upload_instances(s, n_instances, &instances[0].offset[0], r)) != TR_OK) return st;
+    use_inst(s, r);
+    return TR_OK;
+}
+
+int tr_scene_render_frames_instanced(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
+                                     const tr_instance *instances, void *const *frame_buffers_device)
+{
+    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    int st = check_instances(s, n_instances, instances);
+    if (st != TR_OK) return st;
+    if (n_frames == 0) return TR_OK;
+    if ((uint64_t)n_frames * n_instances > 0xFFFFFFFFull) return tr::fail(TR_E_INVALID, "instance tables too large");
+    if (frame_buffers_device)
+        for (uint32_t i = 0; i < n_frames; i++)
+            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((st = grow_for_instances(s, n_instances)) != TR_OK) return st;
+    // all the frames' tables as one block: frame i draws entries [i n, (i + 1) n)
+    std::vector<tr_scene::InstRef> insts(n_frames);
+    if (n_instances) {
+        tr_scene::InstRef all;
+        if ((st = upload_instances(s, n_frames * n_instances, &instances[0].offset[0], all)) != TR_OK) return st;
+        for (uint32_t i = 0; i < n_frames; i++) {
+            insts[i] = all;
+            insts[i].off = i * n_instances;
+            insts[i].n = n_instances;
+        }
+    }
+    return render_frames(s, n_frames, frames, insts.data(), frame_buffers_device);
 }
 
 int tr_scene_frames_per_launch(tr_scene *s) { return s ? (int)group_size(s) : tr::fail(TR_E_INVALID, "null scene"); }
@@ -2377,6 +2646,7 @@ int tr_scene_select_frame(tr_scene *s, uint32_t back)
     const size_t k = s->tail.params.size() - 1u - back;
     const tr_frame_params &q = s->tail.params[k];
     memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+    use_inst(s, s->tail.inst[k]);
     return use_slot(s, s->tail.slot[k], s->tail.fbs.empty() ? nullptr : (uint8_t *)s->tail.fbs[k]);
 }
 

@@ -53,7 +53,13 @@ template <int VS>
 TR_HD bool vertex_stage(const DevMesh &mesh, const DevUniforms &u, uint32_t t, RasterRec &r,
                         float *vary, uint32_t &err)
 {
-    const float *row = mesh.tri + (size_t)TRI_FLOATS * t;
+    // instance k = t / n_rows draws row t - k * n_rows (one division per polygon)
+    uint32_t k = 0, rt = t;
+    if (mesh.inst) {
+        k = t / mesh.n_rows;
+        rt = t - k * mesh.n_rows;
+    }
+    const float *row = mesh.tri + (size_t)TRI_FLOATS * rt;
     float m[TRI_FLOATS];
 #if defined(__HIP_DEVICE_COMPILE__)
     {
@@ -70,6 +76,23 @@ TR_HD bool vertex_stage(const DevMesh &mesh, const DevUniforms &u, uint32_t t, R
 #else
     for (int i = 0; i < TRI_FLOATS; i++) m[i] = row[i];
 #endif
+    if (mesh.inst) {
+        // the instance's placement: p * scale + offset, two roundings (the library is built with -ffp-contract=off).
+        // (One 16-byte load per lane: a wave's lanes take polygons `waves` apart (chain_polygon), so they rarely
+        // share an instance; the table is small and stays in cache.)
+#if defined(__HIP_DEVICE_COMPILE__)
+        const float4 q = reinterpret_cast<const float4 *>(mesh.inst)[k];
+        const float ox = q.x, oy = q.y, oz = q.z, sc = q.w;
+#else
+        const float ox = mesh.inst[4 * k], oy = mesh.inst[4 * k + 1], oz = mesh.inst[4 * k + 2], sc = mesh.inst[4 * k + 3];
+#endif
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            m[3 * i + 0] = m[3 * i + 0] * sc + ox;
+            m[3 * i + 1] = m[3 * i + 1] * sc + oy;
+            m[3 * i + 2] = m[3 * i + 2] * sc + oz;
+        }
+    }
     vec3 p0 = make3(m[0], m[1], m[2]);
     vec3 p1 = make3(m[3], m[4], m[5]);
     vec3 p2 = make3(m[6], m[7], m[8]);

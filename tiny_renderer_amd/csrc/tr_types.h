@@ -128,9 +128,14 @@ struct DevTextures {
 // per-frame vertex stage is a single coalesced sweep instead of index -> attribute chains:
 //   [0..8] positions p0 p1 p2 | [9..17] normals n0 n1 n2 | [18..23] tex coords u0 v0 u1 v1 u2 v2
 constexpr int TRI_FLOATS = 24;
+// Instancing (tr_scene_set_instances): with a table, polygon t of a pass is row t % n_rows of instance t / n_rows,
+// its positions p replaced by p * scale + offset (multiply, then add, each rounded once).  Without one (inst null,
+// the default) polygon t is row t, untransformed -- not the same as one instance {0, 0, 0, 1}: -0 * 1 + 0 = +0.
 struct DevMesh {
-    const float *tri;  // n_tri * TRI_FLOATS
-    uint32_t n_tri;
+    const float *tri;  // rows * TRI_FLOATS
+    uint32_t n_tri;    // polygons of a pass: the rows, or n_rows * instances with a table
+    const float *inst = nullptr;  // instances x {offset x, y, z, scale}, 16-byte aligned; null: the mesh itself
+    uint32_t n_rows = 0;          // rows of `tri` (with a table)
 };
 
 // Fills one row of DevMesh::tri from the indexed arrays (util.rs:25-31, shader.rs:136-147,363-367).

@@ -26,6 +26,14 @@ def _mesh_struct(mesh, keep):
                      nrm.shape[0], idx.shape[0])
 
 
+def _instance_table(instances, per_frame=False):
+    """[n, 4] float32 (offset x, y, z, scale) -- or [n_frames, n, 4] with per_frame -- as a contiguous array."""
+    a = np.ascontiguousarray(instances, np.float32)
+    if a.shape[-1:] != (4,) or a.ndim != (3 if per_frame else 2):
+        raise ValueError("instance table must be [%sn, 4] float32 (offset xyz, scale)" % ("n_frames, " if per_frame else ""))
+    return a
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -34,12 +42,13 @@ class Scene:
           (p0,t0,n0,p1,t1,n1,p2,t2,n2 -- obj::raw::RawObj as the path reads it).
     textures: uint8 [h,w,3] arrays in Scene::new's order.
     Extra keyword options are the tr_options of include/tiny_renderer.h.
+    instances: optional [n, 4] float32 instance table (set_instances) drawn from the first frame on.
     """
 
     def __init__(self, width, height, mesh, textures, shader_pipeline_name, *, device=-1,
                  winner_tap=False, tile_stamps=False, band_rows=None, stream=None, frame_buffer_device=None,
                  bin_capacity=0, tile_waves=0, tile_mode=0, frames_per_launch=0, auto_group=True,
-                 trust_frame_buffers=False, max_frame_slots=0, store_depth=False):
+                 trust_frame_buffers=False, max_frame_slots=0, store_depth=False, instances=None):
         L = load_library()
         self.width, self.height = int(width), int(height)
         keep = []
@@ -74,6 +83,8 @@ class Scene:
                                 shader_pipeline_name.encode(), C.byref(o), C.byref(h)))
         self._h = h
         self.pipeline = shader_pipeline_name
+        if instances is not None:
+            self.set_instances(instances)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -106,11 +117,23 @@ class Scene:
         """Whether render() may hold cleared frames back to fuse them (default on; tr_scene_set_auto_group)."""
         check(load_library().tr_scene_set_auto_group(self._h, 1 if on else 0))
 
-    def render_frames(self, frames, frame_buffers_device=None):
+    def set_instances(self, instances):
+        """tr_scene_set_instances: draw the mesh once per row of the [n, 4] float32 table (offset x, y, z, scale),
+        positions p * scale + offset, instance-major polygon order; None or an empty table: the mesh itself."""
+        L = load_library()
+        if instances is None or len(instances) == 0:
+            check(L.tr_scene_set_instances(self._h, 0, None))
+            return
+        a = _instance_table(instances)
+        check(L.tr_scene_set_instances(self._h, a.shape[0], a.ctypes.data))
+
+    def render_frames(self, frames, frame_buffers_device=None, instances=None):
         """tr_scene_render_frames: `frames` is an [n, 12] float32 array (or a list of (light, look_from,
         look_at, up) tuples): per frame light direction, look_from, look_at, up.  Frame i is what
         clear(); set_light_direction; set_camera; render() produces; the frames of a group are rendered by
-        one launch per kernel.  frame_buffers_device: optional list of n device pointers (colour targets)."""
+        one launch per kernel.  frame_buffers_device: optional list of n device pointers (colour targets).
+        instances: optional [n, n_instances, 4] float32 -- frame i draws table instances[i] (what set_instances
+        before its render would do; tr_scene_render_frames_instanced); None: the current table in every frame."""
         if not isinstance(frames, np.ndarray):
             frames = np.asarray([np.concatenate([np.asarray(v, np.float32).reshape(3) for v in f]) for f in frames],
                                 np.float32)
@@ -120,7 +143,14 @@ class Scene:
             if len(frame_buffers_device) != len(frames):
                 raise ValueError("one frame buffer per frame")
             fbs = (C.c_void_p * len(frames))(*[int(q) for q in frame_buffers_device])
-        check(load_library().tr_scene_render_frames(self._h, len(frames), frames.ctypes.data, fbs))
+        if instances is None:
+            check(load_library().tr_scene_render_frames(self._h, len(frames), frames.ctypes.data, fbs))
+            return
+        inst = _instance_table(instances, per_frame=True)
+        if inst.shape[0] != len(frames):
+            raise ValueError("one instance table per frame")
+        check(load_library().tr_scene_render_frames_instanced(self._h, len(frames), frames.ctypes.data, inst.shape[1],
+                                                              inst.ctypes.data if inst.size else None, fbs))
 
     @property
     def frames_per_launch(self):

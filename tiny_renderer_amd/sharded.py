@@ -188,7 +188,7 @@ class ShardedScene:
         self._used = [False, False]
         self._last_was_cleared = True
         self._last_tensor = None   # where the newest frame is when it came from render_frames (else _fbs[_slot])
-        self._last_group = None    # (frames, set) of the newest group: rendered again if its bins overflowed
+        self._last_group = None    # (frames, set, instance tables) of the newest group: rendered again if its bins overflowed
         self._timing = None        # enable_timing: [(render start, render end, gather start, gather end, frames)]
 
     def enable_timing(self, on=True):
@@ -259,18 +259,27 @@ class ShardedScene:
         self._last_tensor = None
         self._last_group = None
 
-    def render_frames(self, frames):
+    def set_instances(self, instances):
+        """Scene.set_instances on this rank's band scene (collective in spirit: every rank draws the same table)."""
+        self._scene.set_instances(instances)
+
+    def render_frames(self, frames, instances=None):
         """Many frames per call (Scene.render_frames on every rank); afterwards only the LAST frame is exposed
         (get_frame_buffer): each rank renders its band of a group of
         frames by one launch of each kernel into a set of frame tensors of the group's size, and the bands
         of the group are exchanged frame by frame on the second stream while the next group renders into
         the other set.  Frame i is what clear(); set_light_direction; set_camera; render() gives; afterwards
-        the last frame is the one get_frame_buffer() returns.  Collective: all ranks pass the same frames."""
+        the last frame is the one get_frame_buffer() returns.  instances: optional [n, n_instances, 4] float32, frame
+        i's instance table (Scene.render_frames).  Collective: all ranks pass the same frames."""
         import numpy as np
         torch, dist = self._torch, self._dist
         frames = np.ascontiguousarray(frames, np.float32).reshape(-1, 12)
         if len(frames) == 0:
             return
+        if instances is not None:
+            instances = np.ascontiguousarray(instances, np.float32)
+            if len(instances) != len(frames):
+                raise ValueError("one instance table per frame")
         G = self._scene.frames_per_launch
         if not hasattr(self, "_gsets"):
             # two sets of G frame slots: an exchange of its own for them (the library's exchanges own their slots: up to 64)
@@ -290,7 +299,8 @@ class ShardedScene:
                 if self._gused[b]:
                     self._render.wait_event(self._ggathered[b])   # the set's previous exchange has finished
                 t0 = self._stamp(self._render) if self._timing is not None else None
-                self._scene.render_frames(frames[i0:i0 + g], [t.data_ptr() for t in self._gsets[b][:g]])
+                self._scene.render_frames(frames[i0:i0 + g], [t.data_ptr() for t in self._gsets[b][:g]],
+                                          instances=None if instances is None else instances[i0:i0 + g])
                 t1 = self._stamp(self._render) if self._timing is not None else None
                 self._grendered[b].record(self._render)
             with torch.cuda.stream(self._comm):
@@ -302,7 +312,7 @@ class ShardedScene:
                     self._timing.append((t0, t1, t2, self._stamp(self._comm), g))
                 self._ggathered[b].record(self._comm)
             self._gused[b] = True
-            self._last_group = (frames[i0:i0 + g].copy(), b)
+            self._last_group = (frames[i0:i0 + g].copy(), b, None if instances is None else instances[i0:i0 + g].copy())
         self._last_tensor = self._gsets[self._gset][g - 1]
         q = frames[-1]
         self._scene.set_light_direction(q[0:3])
@@ -337,9 +347,9 @@ class ShardedScene:
             if not self._last_was_cleared:
                 raise TinyRendererError(TR_E_BIN_OVERFLOW, "bins overflowed during an accumulating render: clear and render again")
             if self._last_group is not None:
-                again, b = self._last_group
+                again, b, again_inst = self._last_group
                 self._gset = b ^ 1       # ... into the same set of frame tensors
-                self.render_frames(again)
+                self.render_frames(again, instances=again_inst)
                 continue
             self._scene.clear()          # same light and camera: the scene still holds them
             self._cleared = True

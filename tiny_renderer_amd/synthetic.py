@@ -57,6 +57,32 @@ def synthetic_scene(n_lat=31, n_lon=81, tex_size=1024, radius=0.8):
     return mesh, [diffuse, normal_map(0x5EED0001), normal_map(0x5EED0002), spec]
 
 
+def grid_instances(n=8):
+    """instanced_grid's placements as an instance table ([n*n, 4] float32: offset x, y, z, scale; (i major, j
+    minor)) for Scene.set_instances: the library's rule p * scale + offset reproduces instanced_grid(mesh, n)'s
+    positions bit for bit."""
+    table = np.empty((n * n, 4), np.float32)
+    for i in range(n):
+        for j in range(n):
+            table[i * n + j] = ((2 * i + 1) / n - 1.0, (2 * j + 1) / n - 1.0, 0.0, np.float32(1.0 / n))
+    return table
+
+
+def apply_instances(mesh, table):
+    """The mesh a table of instances draws, built on the host: positions p * scale + offset (two float32
+    roundings) per instance, concatenated in table order; shared normals and uvs.  What an instanced scene must
+    render bit for bit."""
+    pos, idx = np.asarray(mesh["pos"], np.float32), np.asarray(mesh["idx"], np.uint32)
+    table = np.asarray(table, np.float32).reshape(-1, 4)
+    all_pos, all_idx = [], []
+    for k, (ox, oy, oz, sc) in enumerate(table):
+        all_pos.append(((pos * sc).astype(np.float32) + np.array([ox, oy, oz], np.float32)).astype(np.float32))
+        q = idx.copy()
+        q[:, 0::3] += np.uint32(k * pos.shape[0])
+        all_idx.append(q)
+    return {"pos": np.concatenate(all_pos), "tex": mesh["tex"], "nrm": mesh["nrm"], "idx": np.concatenate(all_idx)}
+
+
 def instanced_grid(mesh, n=8):
     """BASELINE.json configs[4]: n x n grid of scaled copies, instance (i, j) =
     p / n + ((2i+1)/n - 1, (2j+1)/n - 1, 0), shared normals and uvs, polygons concatenated in
