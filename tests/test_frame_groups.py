@@ -265,8 +265,9 @@ def test_group_with_winner_tap_and_profile(small_synthetic):
 
 def test_full_size_group_equals_per_frame_path(diablo):
     """4096^2 (BASELINE configs[2] geometry), automatic group size: every kept frame of a group call equals the
-    per-frame path's frame for the same light and camera (itself checked against the oracle at 800^2 /
-    2048^2 and by properties at this size)."""
+    per-frame path's frame for the same light and camera.  The per-frame scene has the winner tap, which pins it to
+    the per-frame kernels (itself checked against the oracle at this size, test_baseline_configs_at_full_size): without
+    it a cleared frame on its own runs the very kernel the group runs, and the test would compare that with itself."""
     import tiny_renderer_amd as T
     mesh, texs = diablo
     n = 6
@@ -274,7 +275,7 @@ def test_full_size_group_equals_per_frame_path(diablo):
     gpu = T.Scene(4096, 4096, mesh, texs, "phong")
     assert gpu.frames_per_launch == 4
     gpu.render_frames(p)
-    one = T.Scene(4096, 4096, mesh, texs, "phong")
+    one = T.Scene(4096, 4096, mesh, texs, "phong", winner_tap=True)
     for back in range(gpu.frames_kept()):
         q = p[n - 1 - back]
         one.clear(), one.set_light_direction(q[0:3]), one.set_camera(q[3:6], q[6:9], q[9:12]), one.render()
