@@ -62,6 +62,12 @@ def as_u8(x):
     return _as_int(x, 0.0, 255.0, np.uint8)
 
 
+def wrap_i32(d):
+    """An i32 difference as a release build computes it (two's complement wrap; scene.rs:178-186 subtracts raster
+    coordinates that `as i32` may have saturated).  Python ints or int64 arrays."""
+    return (d + 2147483648) % 4294967296 - 2147483648
+
+
 # ---- nalgebra 0.31 operations, in the order SURVEY.md Appendix A reads them -------------------------------------------
 def dot3(a, b):
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
@@ -404,8 +410,8 @@ class Scene:
                 ii, jj = np.meshgrid(np.arange(x_min, x_max + 1), np.arange(y_min, y_max + 1), indexing="ij")
                 ii, jj = ii.ravel(), jj.ravel()
                 # to_barycentric_coord: integer differences, THEN the conversion to f32
-                v1 = [f32(x[1] - x[0]), f32(x[2] - x[0]), (x[0] - ii).astype(f32)]
-                v2 = [f32(y[1] - y[0]), f32(y[2] - y[0]), (y[0] - jj).astype(f32)]
+                v1 = [f32(wrap_i32(x[1] - x[0])), f32(wrap_i32(x[2] - x[0])), wrap_i32(x[0] - ii).astype(f32)]
+                v2 = [f32(wrap_i32(y[1] - y[0])), f32(wrap_i32(y[2] - y[0])), wrap_i32(y[0] - jj).astype(f32)]
                 raw = cross(v1, v2)
                 raw = [np.broadcast_to(np.asarray(c, f32), ii.shape) for c in raw]
                 with np.errstate(all="ignore"):

@@ -103,16 +103,18 @@ def test_bands_reassemble(small_synthetic):
     assert np.array_equal(out, fb)
 
 
-@pytest.mark.parametrize("seed", range(6))
+MASK_SEEDS = range(6)
+
+
+@pytest.mark.parametrize("seed", MASK_SEEDS)
 def test_pair_masks_never_lose_a_fragment(seed):
     """k_setup stores with every (polygon, tile) pair which cells / block columns of the box can hold a
     fragment (pair_masks, tr_shaders.h) and the tile kernel looks nowhere else.  The emulation skips the
     same pixels: far-away vertices, slivers and nearly collinear triples (edge functions that round in
     f32) are where a margin that is too small would lose fragments -- the frame must stay the oracle's
     and no covered pixel may lie outside the masks."""
-    from tests.test_random_meshes import far_soup
-    W, Hh = [(8192, 48), (4096, 130), (1000, 1000)][seed % 3]
-    mesh, texs = far_soup(7000 + seed, 160)
+    from tests.test_random_meshes import far_case
+    (W, Hh), _, _, mesh, texs = far_case(seed, base=7000)
     before = E.mask_counts()
     s = O.Scene(W, Hh, mesh, texs, "phong")
     s.clear()

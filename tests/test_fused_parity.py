@@ -21,7 +21,7 @@ import numpy as np
 import pytest
 
 from tests import helpers as H
-from tests.test_random_meshes import far_soup
+from tests.test_random_meshes import FAR_SEEDS, far_case
 
 EXACT = ("default", "phong", "normal_map", "darboux", "shadow", "occlusion")
 ALL = EXACT + ("specular",)
@@ -453,14 +453,11 @@ def test_ladder_parity(built, path, waves, mode, pipe):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", ["group2", "single2"])
-@pytest.mark.parametrize("seed", range(9))
+@pytest.mark.parametrize("seed", FAR_SEEDS)
 def test_far_vertices_and_slivers_fused(built, seed, path):
     """test_far_vertices_and_slivers_gpu's soups, sizes, layouts and pipelines (f32 rounding of the edge functions, the
     block rejection margins) through the fused kernels; a second light makes the frames of a group differ."""
-    W, Hh = [(8192, 48), (4096, 130), (1000, 1000)][seed % 3]
-    waves = [4, 8, 16][(seed // 3) % 3]
-    pipe = ["phong", "normal_map", "default"][seed % 3]
-    mesh, texs = far_soup(5000 + seed, 160)
+    (W, Hh), waves, pipe, mesh, texs = far_case(seed)
     views = np.stack([view(0.0, 0.4), view(0.0, 0.9), view(0.0, 0.4)])
     expect = oracle_views(W, Hh, mesh, texs, pipe, views)
     assert all(o["err"] == 0 for o in expect), "the reference would panic on this soup"

@@ -64,9 +64,46 @@ def test_resolve_matches_serial_order_cpu(seed, n_tri, grid, pipe, ca, size):
         assert np.array_equal(sh.view(np.uint32), s.shadow_f32().view(np.uint32))
 
 
+TIE_SEEDS = range(12)
+TIE_GROUP_SEEDS = range(8)
+FAR_SEEDS = range(9)
+
+
+def tie_case(seed):
+    """test_resolve_matches_serial_order_gpu's input of a seed: (W, H), pipeline, camera angle, mesh, textures."""
+    rng = np.random.default_rng(1000 + seed)
+    n_tri = int(rng.integers(1, 400))
+    grid = int(rng.choice([2, 3, 5, 9]))
+    pipe = ["default", "phong", "shadow", "occlusion", "darboux", "normal_map"][seed % 6]
+    size = [(96, 64), (130, 50), (257, 33), (640, 480)][seed % 4]
+    mesh, texs = soup(seed, n_tri, grid)
+    return size, pipe, [0.0, 0.3, 3.14159][seed % 3], mesh, texs
+
+
+def tie_group_case(seed):
+    """The frame-group twin's input: (W, H), pipeline, five (camera angle, light angle) views, mesh, textures."""
+    rng = np.random.default_rng(2000 + seed)
+    n_tri = int(rng.integers(1, 400))
+    grid = int(rng.choice([2, 3, 5, 9]))
+    pipe = ["default", "phong", "shadow", "occlusion", "darboux", "normal_map", "specular", "phong"][seed % 8]
+    size = [(96, 64), (130, 50), (257, 33), (640, 480)][seed % 4]
+    mesh, texs = soup(seed + 50, n_tri, grid)
+    views = [(ca, 0.4 + 0.3 * k) for k, ca in enumerate([0.0, 0.3, 3.14159, 0.3, 0.0])]
+    return size, pipe, views, mesh, texs
+
+
+def far_case(seed, base=5000):
+    """The far-vertex tests' input of a seed: (W, H), tile_waves, pipeline, mesh, textures (far_soup(base + seed))."""
+    size = [(8192, 48), (4096, 130), (1000, 1000)][seed % 3]
+    waves = [4, 8, 16][(seed // 3) % 3]
+    pipe = ["phong", "normal_map", "default"][seed % 3]  # (no shadow-buffer lookups: they would leave their range)
+    mesh, texs = far_soup(base + seed, 160)
+    return size, waves, pipe, mesh, texs
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 2])
-@pytest.mark.parametrize("seed", range(12))
+@pytest.mark.parametrize("seed", TIE_SEEDS)
 def test_resolve_matches_serial_order_gpu(built, seed, mode):
     """Polygon soups on a coarse vertex grid: many fragments of equal depth at the same pixel (shared
     vertices and edges, coplanar overlaps), where the survivor is decided by polygon order alone --
@@ -74,13 +111,7 @@ def test_resolve_matches_serial_order_gpu(built, seed, mode):
     the order packed under the depth in one 64-bit atomic maximum), and, with accumulating renders,
     against what the buffers held before."""
     import tiny_renderer_amd as T
-    rng = np.random.default_rng(1000 + seed)
-    n_tri = int(rng.integers(1, 400))
-    grid = int(rng.choice([2, 3, 5, 9]))
-    pipe = ["default", "phong", "shadow", "occlusion", "darboux", "normal_map"][seed % 6]
-    W, Hh = [(96, 64), (130, 50), (257, 33), (640, 480)][seed % 4]
-    mesh, texs = soup(seed, n_tri, grid)
-    ca = [0.0, 0.3, 3.14159][seed % 3]
+    (W, Hh), pipe, ca, mesh, texs = tie_case(seed)
     err, s = oracle_frame(W, Hh, mesh, texs, pipe, ca, 0.4)
     if err:
         pytest.skip("the reference would panic on this soup")
@@ -102,18 +133,12 @@ def test_resolve_matches_serial_order_gpu(built, seed, mode):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 2])
-@pytest.mark.parametrize("seed", range(8))
+@pytest.mark.parametrize("seed", TIE_GROUP_SEEDS)
 def test_resolve_matches_serial_order_gpu_frame_groups(built, seed, mode):
     """The same tie soups through tr_scene_render_frames: five views of a soup rendered by one launch of each
     kernel (groups of 3 + 2), every frame against the oracle's serial loop."""
     import tiny_renderer_amd as T
-    rng = np.random.default_rng(2000 + seed)
-    n_tri = int(rng.integers(1, 400))
-    grid = int(rng.choice([2, 3, 5, 9]))
-    pipe = ["default", "phong", "shadow", "occlusion", "darboux", "normal_map", "specular", "phong"][seed % 8]
-    W, Hh = [(96, 64), (130, 50), (257, 33), (640, 480)][seed % 4]
-    mesh, texs = soup(seed + 50, n_tri, grid)
-    views = [(ca, 0.4 + 0.3 * k) for k, ca in enumerate([0.0, 0.3, 3.14159, 0.3, 0.0])]
+    (W, Hh), pipe, views, mesh, texs = tie_group_case(seed)
     expect = []
     for ca, la in views:
         err, s = oracle_frame(W, Hh, mesh, texs, pipe, ca, la)
@@ -176,17 +201,14 @@ def far_soup(seed, n_tri):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed", range(9))
+@pytest.mark.parametrize("seed", FAR_SEEDS)
 def test_far_vertices_and_slivers_gpu(built, seed):
     """The tile kernel drops 8x8 blocks that lie outside an edge by more than a rounding margin
     before testing pixels: with far-away vertices the edge functions round in f32 (products up to
     ~1e17), so this is where a margin that is too small would lose fragments.  Wide frames keep the
     screen coordinates themselves large, too."""
     import tiny_renderer_amd as T
-    W, Hh = [(8192, 48), (4096, 130), (1000, 1000)][seed % 3]
-    waves = [4, 8, 16][(seed // 3) % 3]
-    pipe = ["phong", "normal_map", "default"][seed % 3]  # (no shadow-buffer lookups: they would leave their range)
-    mesh, texs = far_soup(5000 + seed, 160)
+    (W, Hh), waves, pipe, mesh, texs = far_case(seed)
     err, s = oracle_frame(W, Hh, mesh, texs, pipe, 0.0, 0.4)
     if err:
         pytest.skip("the reference would panic on this soup")

@@ -305,7 +305,18 @@ TR_HD void pair_masks(int32_t bx0, int32_t bx1, int32_t by0, int32_t by1, int32_
     const float e0x = b1, e0y = -a1, e1x = -b0, e1y = a0, e2x = b0 - b1, e2y = a1 - a0;
     const float e0 = a1 * oy - ox * b1, e1 = ox * b0 - a0 * oy;
     const float e2 = cz - (e0 + e1);
-    const float margin = 4.76837158e-7f /* 2^-21 */ *
+    // The per-pixel operands are the WRAPPING i32 differences x0 - px, y0 - py (scene.rs:181,186 in a release build):
+    // linear in the pixel only while none of them wraps between two pixels of the tile.  A vertex 0 behind the camera's
+    // plane w = 0 has raster coordinates that `as i32` saturates to i32::MIN, and then x0 - px is -2^31 at px = 0 and
+    // +2^31 - px from px = 1 on: the estimate below does not hold for such a tile, every cell of the box is kept (an
+    // infinite margin) and the exact per-pixel test decides.  (A difference that has wrapped before the tile's first
+    // pixel stays linear inside the tile; px >= 0, so a difference can only wrap downwards.)  e0, e1, e2 and the slopes
+    // are finite (products of two i32-valued floats), so +inf passes through the additions, fma_est and fminf below as
+    // +inf, never as NaN, and every `worst >= 0` holds.
+    constexpr int32_t I32_MIN = -2147483647 - 1;
+    const bool wraps = isub(x0, tile_x0) < I32_MIN + (TILE_W - 1) ||
+                       isub(y0, tile_y0) < I32_MIN + (TILE_H - 1);
+    const float margin = wraps ? __builtin_inff() : 4.76837158e-7f /* 2^-21 */ *
                          (((fabsf(a1) + fabsf(a0)) * (fabsf(oy) + (float)TILE_H) +
                            (fabsf(b1) + fabsf(b0)) * (fabsf(ox) + (small ? 8.0f * SCAN_MAX_CHUNKS : (float)TILE_W))) + cz);
     const float px0 = fmaxf(e0x, 0.0f), px1 = fmaxf(e1x, 0.0f), px2 = fmaxf(e2x, 0.0f);
