@@ -230,6 +230,26 @@ void *tr_host_alloc(size_t bytes); /* page-locked host memory mapped into the de
 void tr_host_free(void *p);
 int tr_scene_host_buffer_written(tr_scene *s, void *p);
 
+/* Supersampled output (nothing of the kind upstream, which takes one sample per pixel): the scene's current frame,
+ * rendered at W x H, box-filtered on the device by factor f = 2, 4 or 8 into a frame of W/f x H/f pixels, tightly
+ * packed rgb8, row 0 = top.  With F the image tr_scene_get_frame_buffer would return,
+ *     out[Y][X][c] = ( sum over dy, dx in [0, f) of F[f*Y + dy][f*X + dx][c]  +  f*f/2 ) / (f*f)     (integer division)
+ * -- the stored u8 values, per channel, rounded half up; no gamma, no weights.  "Current frame" is what the getters
+ * mean: the last render's, a frame chosen with tr_scene_select_frame, the caller's buffer after
+ * tr_scene_set_frame_buffer_device.  W and H must be multiples of f, and so must tr_options.band_row0/1 of a band
+ * scene (a block of f x f pixels then never straddles a 128x16 tile or the band); anything else is TR_E_INVALID and
+ * changes nothing.  Tiles the scene knows to hold the cleared colour are not read (k_resolve stores their zeros).
+ * tr_scene_resolve is asynchronous like tr_scene_get_frame_buffer_async: it submits what tr_scene_render holds back and
+ * enqueues the resolve behind the renders issued so far; a later render is ordered after it; `out` holds the result
+ * after tr_scene_sync.  `out`: 3*(W/f)*(H/f) bytes of device memory, or memory from tr_host_alloc (the kernel then
+ * stores through the mapped address: only the resolved frame crosses to the host); other host memory is TR_E_INVALID.
+ * A whole-frame scene writes every byte of `out` on every call; a band scene writes output rows
+ * [band_row0/f, band_row1/f) and nothing else, so the ranks of a sharded frame can resolve into one buffer.
+ * tr_scene_get_resolved takes any host memory, synchronizes and returns the frame's sticky status like
+ * tr_scene_get_frame_buffer (rows outside a band scene's band are zeros). */
+int tr_scene_resolve(tr_scene *s, uint32_t factor, void *out);
+int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

@@ -38,7 +38,12 @@ def main(argv=None):
                          "run with several ranks on one GPU)")
     ap.add_argument("--instances", type=int, default=1,
                     help="draw the model N x N times, scaled by 1/N on a grid (instanced rendering; 1 = the model itself)")
+    ap.add_argument("--ssaa", type=int, default=1, choices=(1, 2, 4, 8),
+                    help="supersampling: render at F * width x F * height and write the width x height picture, each pixel "
+                         "the rounded mean of its F x F samples (resolved on the GPU: Scene.resolve)")
     args = ap.parse_args(argv)
+    if args.ssaa > 1 and (args.gpus > 1 or args.view != "frame"):
+        ap.error("--ssaa resolves the colour frame of one GPU: use --gpus 1 and --view frame")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.instances < 1:
@@ -97,7 +102,9 @@ def main(argv=None):
             raise SystemExit("process group has %d ranks, --gpus says %d" % (dist.get_world_size(), args.gpus))
         scene = ShardedScene(args.width, args.height, mesh, texs, args.pipeline, device=local, exchange=args.exchange)
     else:
-        scene = T.Scene(args.width, args.height, mesh, texs, args.pipeline, device=args.device)
+        if args.ssaa > 1:
+            say("supersampling: rendering %d x %d" % (args.width * args.ssaa, args.height * args.ssaa))
+        scene = T.Scene(args.width * args.ssaa, args.height * args.ssaa, mesh, texs, args.pipeline, device=args.device)
     if args.instances > 1:
         say("instances: %d x %d grid" % (args.instances, args.instances))
         scene.set_instances(T.grid_instances(args.instances))
@@ -130,7 +137,7 @@ def _run(args, T, scene, sharded, rank, say):
             scene.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
             scene.render()
             if not args.no_readback:
-                img = scene.get_frame_buffer()
+                img = _view(scene, args.view, args.ssaa)
             elif fps_counter % 64 == 63:
                 scene.sync()  # keep the queue bounded
             fps_counter += 1
@@ -139,7 +146,7 @@ def _run(args, T, scene, sharded, rank, say):
                 fps_counter, fps_t = 0, now
         scene.sync()
         if args.out:
-            img = _view(scene, args.view)
+            img = _view(scene, args.view, args.ssaa)
             if rank == 0:
                 write_frame(T, args.out, img)
         return 0
@@ -162,7 +169,7 @@ def _run(args, T, scene, sharded, rank, say):
         scene.set_light_direction([float(np.sin(la)), 0.0, float(np.cos(la))])   # app.rs:203-208
         scene.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])  # app.rs:200-209
         scene.render()                                                       # app.rs:210
-    img = _view(scene, args.view)
+    img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238
     if args.out and rank == 0:
@@ -170,9 +177,9 @@ def _run(args, T, scene, sharded, rank, say):
     return 0
 
 
-def _view(scene, view):
+def _view(scene, view, ssaa=1):
     if view == "frame":
-        return scene.get_frame_buffer()
+        return scene.resolve(ssaa) if ssaa > 1 else scene.get_frame_buffer()
     return {"z": scene.get_z_buffer, "shadow": scene.get_shadow_buffer}[view]()
 
 

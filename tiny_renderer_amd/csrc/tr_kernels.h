@@ -50,6 +50,11 @@ int launch_read_back(const uint8_t *fb, uint8_t *host, const uint32_t *fb_clean,
 // (k_push_tiles; remote_clean: this rank's record of the peer's copy; poisoned: the exchange's error word).
 int launch_push_tiles(const uint8_t *fb, uint8_t *peer, const uint32_t *fb_clean, uint32_t *remote_clean, const DevFrame &frame,
                       const uint32_t *poisoned, unsigned long long *bytes, hipStream_t st);
+// The band's frame box-filtered by `factor` (2, 4, 8; width, height and the band's rows are multiples of it) into
+// `out`, a frame of width / factor x height / factor pixels (device memory or the device address of mapped host
+// memory): k_resolve.  fb_clean: the target's colour-clean flags (tiles not read, stored as zeros) or null.
+int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, const DevFrame &frame, uint32_t factor,
+                   hipStream_t st);
 int launch_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32, int32_t *out_i32,
                     uint32_t *out_u8, float *out_div, float *out_div_ref, hipStream_t st);
 // Peer exchange flags (tr_exchange.cpp): system-scope store of a generation number; waits that poll

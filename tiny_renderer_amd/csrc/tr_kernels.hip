@@ -30,6 +30,7 @@
 
 #include "tr_kernels.h"
 #include "tr_plan.h"
+#include "tr_resolve.h"
 #include "tr_shaders.h"
 
 namespace tr {
@@ -1705,6 +1706,83 @@ __global__ __launch_bounds__(256) void k_push_tiles(const uint8_t *__restrict__ 
     if (threadIdx.x == 0u) remote_clean[t] = zeros ? 1u : 0u;
 }
 
+// Supersampled output (tr_scene_resolve): the band's frame, box-filtered by F = 2, 4 or 8 on its stored u8 values
+// (tr_resolve.h) into a frame of width / F x height / F pixels.  Tiles are the 128 x 16 source tiles of k_read_back;
+// F divides both sides and the launcher's caller requires width, height and the band's rows to be multiples of F, so
+// a source block never straddles a tile or the band.  A tile whose colour-clean flag is up holds the cleared colour:
+// it is not read, its output pixels are stored as zeros (three quarters of a frame of the reference's model).
+// A lane takes 16 source pixels -- three 16-byte pieces -- of each of F rows and owns the 16 / F output pixels below
+// them; lanes run along the row first.  A tile has 8 * 16 / F such shares, a wavefront takes 64 of them: one tile at
+// F = 2, two at 4, four at 8.  WIDE: width % 16 == 0 and both buffers aligned for 16-byte loads and 8 / 4 / 2-byte
+// stores (the launcher checks); otherwise the same shares through byte loads and stores, which also serves the
+// last columns of a width that is not a multiple of 16.
+template <int F, bool WIDE>
+__global__ __launch_bounds__(64) void k_resolve(const uint8_t *__restrict__ fb, uint8_t *__restrict__ out,
+                                                const uint32_t *__restrict__ fb_clean, DevFrame frame)
+{
+    constexpr uint32_t SHARES = 8u * (uint32_t)(TILE_H / F);  // of one tile: 64, 32, 16
+    constexpr int OUT_BYTES = 48 / F, OUT_WORDS = (OUT_BYTES + 3) / 4;
+    const uint32_t t = blockIdx.x * (64u / SHARES) + threadIdx.x / SHARES;
+    if (t >= frame.ntx * frame.nty) return;
+    const uint32_t share = threadIdx.x % SHARES;
+    const int32_t W = (int32_t)frame.width, H = (int32_t)frame.height;
+    const int32_t x = (int32_t)(t % frame.ntx) * TILE_W + (int32_t)(share % 8u) * 16;
+    const int32_t y = (frame.ty_base + (int32_t)(t / frame.ntx)) * TILE_H + (int32_t)(share / 8u) * F;  // lowest of the F rows
+    if (x >= W || y < frame.band_y0 || y + F > frame.band_y1) return;
+    const bool zeros = fb_clean != nullptr && fb_clean[t] != 0u;
+    const int32_t row = H - y - F;  // first of the F buffer rows (row 0 = top); output row = row / F
+    const int32_t n_bytes = min(16, W - x) * 3;  // of a source row (WIDE: always 48)
+    uint32_t res[OUT_WORDS];
+    if (zeros) {
+#pragma unroll
+        for (int w = 0; w < OUT_WORDS; w++) res[w] = 0u;
+    } else {
+        uint32_t src[F * 12];
+        const uint8_t *p = fb + ((size_t)row * (size_t)W + (size_t)x) * 3u;
+#pragma unroll
+        for (int r = 0; r < F; r++) {
+            const uint8_t *q = p + (size_t)r * (size_t)W * 3u;
+            if (WIDE) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(q + 16 * k);
+                    src[r * 12 + 4 * k + 0] = v.x;
+                    src[r * 12 + 4 * k + 1] = v.y;
+                    src[r * 12 + 4 * k + 2] = v.z;
+                    src[r * 12 + 4 * k + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int w = 0; w < 12; w++) {
+                    uint32_t v = 0u;
+#pragma unroll
+                    for (int b = 0; b < 4; b++)
+                        if (4 * w + b < n_bytes) v |= (uint32_t)q[4 * w + b] << (8 * b);
+                    src[r * 12 + w] = v;
+                }
+            }
+        }
+        resolve_block<F>(src, res);
+    }
+    uint8_t *o = out + ((size_t)(row / F) * (size_t)(W / F) + (size_t)(x / F)) * 3u;
+    if (WIDE) {
+        if (F == 2) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) reinterpret_cast<uint2 *>(o)[k] = make_uint2(res[2 * k], res[2 * k + 1]);
+        } else if (F == 4) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) reinterpret_cast<uint32_t *>(o)[k] = res[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; k++) reinterpret_cast<uint16_t *>(o)[k] = (uint16_t)(res[k >> 1] >> (16 * (k & 1)));
+        }
+    } else {
+#pragma unroll
+        for (int b = 0; b < OUT_BYTES; b++)
+            if (b * F < n_bytes) o[b] = (uint8_t)(res[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
 // tr_selftest_device_math: the device forms of the casts and of the shared-reciprocal division,
 // applied to caller-chosen operands so the host can compare them with its own.
 __global__ __launch_bounds__(256) void k_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32,
@@ -2096,6 +2174,35 @@ int launch_push_tiles(const uint8_t *fb, uint8_t *peer, const uint32_t *fb_clean
     hipLaunchKernelGGL(k_push_tiles, dim3(n_tiles), dim3(256), 0, st, fb, peer, fb_clean, remote_clean, frame, poisoned, bytes);
     TR_LAUNCH_CHECK();
     return 0;
+}
+
+template <int F>
+static int launch_resolve_f(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, const DevFrame &frame, bool wide,
+                            hipStream_t st)
+{
+    const uint32_t n_tiles = frame.ntx * frame.nty, per_block = 64u / (8u * (uint32_t)(TILE_H / F));
+    const dim3 grid((n_tiles + per_block - 1u) / per_block);
+    if (wide)
+        hipLaunchKernelGGL((k_resolve<F, true>), grid, dim3(64), 0, st, fb, out, fb_clean, frame);
+    else
+        hipLaunchKernelGGL((k_resolve<F, false>), grid, dim3(64), 0, st, fb, out, fb_clean, frame);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, const DevFrame &frame, uint32_t factor,
+                   hipStream_t st)
+{
+    if (frame.ntx * frame.nty == 0) return 0;
+    if ((factor != 2u && factor != 4u && factor != 8u) || frame.width % factor || frame.height % factor ||
+        frame.band_y0 % (int32_t)factor || frame.band_y1 % (int32_t)factor)
+        return (int)hipErrorInvalidValue;
+    // the wide path: source rows in 16-byte pieces, a share's 48 / factor output bytes in three aligned stores
+    const uintptr_t store = 16u / factor, out_row = (uintptr_t)(frame.width / factor) * 3u;
+    const bool wide = frame.width % 16u == 0u && (uintptr_t)fb % 16u == 0u && (uintptr_t)out % store == 0u && out_row % store == 0u;
+    if (factor == 2u) return launch_resolve_f<2>(fb, out, fb_clean, frame, wide, st);
+    if (factor == 4u) return launch_resolve_f<4>(fb, out, fb_clean, frame, wide, st);
+    return launch_resolve_f<8>(fb, out, fb_clean, frame, wide, st);
 }
 
 int launch_selftest_shadow(const float *plain, const float *stale, const uint32_t *sclean, uint32_t W, uint32_t H,

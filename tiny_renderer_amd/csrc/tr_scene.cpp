@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -322,6 +322,8 @@ struct tr_scene {
     } tail;
     bool last_was_group = false;
     uint8_t *d_view = nullptr;  // scratch for get_z_buffer / get_shadow_buffer
+    uint8_t *d_resolved = nullptr;  // tr_scene_get_resolved's device buffer, of the largest resolved size asked for so far
+    size_t resolved_bytes = 0;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
     // memory not written".  Raised by the tile kernel for the empty tiles of a cleared frame (and by
@@ -2095,6 +2097,7 @@ void destroy(tr_scene *s)
         if (g.ev_tile) (void)hipEventDestroy(g.ev_tile);
     }
     dev_free(s->d_view);
+    dev_free(s->d_resolved);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
     for (tr_scene::HostFlags &f : s->host_flags) dev_free(f.clean);
@@ -2323,6 +2326,34 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
 // after the copy (TR_E_OOB_LOOKUP / TR_E_BIN_OVERFLOW frames are still delivered); TR_E_HIP ends
 // the call.
 bool fatal(int st) { return st == TR_E_HIP || st == TR_E_NOMEM || st == TR_E_INVALID; }
+
+// tr_scene_resolve / tr_scene_get_resolved: is `factor` one this scene's frame can be resolved by?  (A source block
+// of factor x factor pixels must not straddle a 128 x 16 tile or the scene's band.)
+int check_resolve(const tr_scene *s, uint32_t factor)
+{
+    if (factor != 2u && factor != 4u && factor != 8u) return tr::fail(TR_E_INVALID, "resolve: the factor must be 2, 4 or 8");
+    if (s->width % factor || s->height % factor)
+        return tr::fail(TR_E_INVALID, "resolve: the frame's width and height must be multiples of the factor");
+    if (s->frame.band_y0 % (int32_t)factor || s->frame.band_y1 % (int32_t)factor)
+        return tr::fail(TR_E_INVALID, "resolve: the band's rows (tr_options.band_row0/1) must be multiples of the factor");
+    return TR_OK;
+}
+
+// Enqueues the resolve of the current frame into `out_device` behind everything issued so far.
+int enqueue_resolve(tr_scene *s, uint32_t factor, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);
+    if (st != TR_OK) return st;
+    st = submit_pending(s);
+    if (st != TR_OK) return st;
+    {
+        Timed t(s, K_RESOLVE);
+        int rc = launch_resolve(s->d_fb, out_device, s->d_fbclean, s->frame, factor, s->stream);
+        if (rc) return launch_status(rc, "k_resolve");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
 
 int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, size_t bytes)
 {
@@ -2789,6 +2820,69 @@ int tr_scene_get_frame_buffer_async(tr_scene *s, uint8_t *rgb)
     // be repaired by rendering again, and tr_scene_sync will say so (TR_E_BIN_OVERFLOW)
     s->observed_seq = s->pass_seq;
     return TR_OK;
+}
+
+int tr_scene_resolve(tr_scene *s, uint32_t factor, void *out)
+{
+    if (!s || !out) return tr::fail(TR_E_INVALID, "null argument");
+    int st = check_resolve(s, factor);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)(s->width / factor) * (s->height / factor) * 3;
+    // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
+    void *target = nullptr;
+    bool known_host = false;
+    {
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(out);
+        if (it != g_host_allocs.end()) {
+            known_host = true;
+            if (it->second.bytes >= bytes) {
+                target = it->second.device;
+                // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
+                it->second.writer = 0u;
+                it->second.gen += 1u;
+            }
+        }
+    }
+    if (known_host && !target) return tr::fail(TR_E_INVALID, "tr_scene_resolve: the host buffer is smaller than the resolved frame");
+    if (!target) {
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, "tr_scene_resolve: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_resolved takes any host memory)");
+        }
+        if (attr.type != hipMemoryTypeDevice)
+            return tr::fail(TR_E_INVALID, "tr_scene_resolve: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_resolved takes any host memory)");
+        target = out;
+    }
+    st = enqueue_resolve(s, factor, (uint8_t *)target);
+    if (st != TR_OK) return st;
+    // every pass issued so far is now in a consumer's hands (as in tr_scene_get_frame_buffer_async)
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb)
+{
+    if (!s || !rgb) return tr::fail(TR_E_INVALID, "null argument");
+    int st = check_resolve(s, factor);
+    if (st != TR_OK) return st;
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const size_t bytes = (size_t)(s->width / factor) * (s->height / factor) * 3;
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
+        s->resolved_bytes = 0;
+        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
+        s->resolved_bytes = bytes;
+    }
+    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
+    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
+    if (!whole_frame) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    st = enqueue_resolve(s, factor, s->d_resolved);
+    if (st != TR_OK) return st;
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
 }
 
 int tr_scene_band_tiles(tr_scene *s, const void *frame_buffer_device, tr_band_tiles *out)

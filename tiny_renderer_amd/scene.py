@@ -191,6 +191,55 @@ class Scene:
         check(load_library().tr_scene_get_frame_buffer_async(self._h, out.ctypes.data))
         return out
 
+    # --- supersampled output (tr_scene_resolve / tr_scene_get_resolved) ------------------------
+    def _resolved_shape(self, factor):
+        """(H / f, W / f, 3) of the frame resolved by `factor`; ValueError for what the host alone can rule out."""
+        f = int(factor)
+        if f != factor or f not in (2, 4, 8):
+            raise ValueError("resolve factor must be 2, 4 or 8, not %r" % (factor,))
+        if self.width % f or self.height % f:
+            raise ValueError("a %d x %d frame cannot be resolved by %d: width and height must be multiples of it"
+                             % (self.width, self.height, f))
+        return self.height // f, self.width // f, 3
+
+    def resolve(self, factor, out=None, strict=True):
+        """The current frame box-filtered by `factor` (2, 4 or 8) on the device: an [H / f, W / f, 3] uint8 array,
+        out[Y, X, c] = (sum of the f x f block of get_frame_buffer() + f * f / 2) // (f * f).  Synchronizes."""
+        shape = self._resolved_shape(factor)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.dtype != np.uint8 or out.nbytes != shape[0] * shape[1] * 3 or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a contiguous [H / f, W / f, 3] uint8 array")
+        code = load_library().tr_scene_get_resolved(self._h, int(factor), out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return out
+
+    def pinned_resolved(self, factor):
+        """A page-locked [H / f, W / f, 3] uint8 array for resolve_into (freed with the scene)."""
+        shape = self._resolved_shape(factor)
+        n = shape[0] * shape[1] * 3
+        p = load_library().tr_host_alloc(n)
+        if not p:
+            raise MemoryError("tr_host_alloc(%d)" % n)
+        self._pinned.append(p)
+        return np.ctypeslib.as_array((C.c_uint8 * n).from_address(p)).reshape(shape)
+
+    def resolve_into(self, factor, target):
+        """Enqueue the resolve of the current frame behind the renders issued so far (tr_scene_resolve); the result is
+        there after sync().  `target`: a device pointer (int) to 3 * (W / f) * (H / f) bytes, or an array from
+        pinned_resolved.  A band scene writes output rows [band_row0 / f, band_row1 / f) only."""
+        shape = self._resolved_shape(factor)
+        if isinstance(target, np.ndarray):
+            if target.nbytes != shape[0] * shape[1] * 3 or not target.flags["C_CONTIGUOUS"]:
+                raise ValueError("target must be a contiguous [H / f, W / f, 3] uint8 array (pinned_resolved)")
+            ptr = target.ctypes.data
+        else:
+            ptr = int(target) if target is not None else None
+        check(load_library().tr_scene_resolve(self._h, int(factor), ptr))
+        return target
+
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
         the array's content at the next get_frame_buffer_async)."""
