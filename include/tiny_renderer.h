@@ -172,7 +172,8 @@ int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params
  * and the mesh's own normals and texture coordinates.  Polygons are drawn in instance-major order: instance k,
  * triangle t is polygon k * n_tri + t -- the winner tap, the depth test's tie order and the culling see the mesh
  * concatenated n_instances times.  So a scene with table T renders bit for bit what a scene created from that
- * concatenated, host-transformed mesh renders, in every pipeline.  No rotations: normals are not transformed.
+ * concatenated, host-transformed mesh renders, in every pipeline.  No rotations: normals are not transformed (for
+ * those, tr_instance_xform below).
  * n_instances == 0 (instances may then be NULL) draws the mesh itself, untransformed -- the default, and NOT the same as
  * one instance {0, 0, 0, 1}: -0.0 * 1 + 0 is +0.0.  n_tri * n_instances must stay below 0xFFFFFFF0 (TR_E_INVALID).
  * The table is scene state like the camera: renders issued after the call draw it; frames issued before (also those
@@ -193,6 +194,43 @@ int tr_scene_set_instances(tr_scene *s, uint32_t n_instances, const tr_instance 
 int tr_scene_render_frames_instanced(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
                                      const tr_instance *instances /* n_frames * n_instances */,
                                      void *const *frame_buffers_device);
+/* Instance transforms: the second kind of instance table, for copies that are turned, sheared, scaled per axis or
+ * mirrored.  Instance k draws every polygon of the mesh with each position (x, y, z) and each vertex normal (a, b, c)
+ * replaced, component r = 0..2, by
+ *     p'_r = fl( fl( fl( fl(m[4r]*x) + fl(m[4r+1]*y) ) + fl(m[4r+2]*z) ) + m[4r+3] )
+ *     n'_r = fl( fl( fl(n[3r]*a) + fl(n[3r+1]*b) ) + fl(n[3r+2]*c) )
+ * -- every multiply and every add rounded once, in this order; no fused multiply-add.  Texture coordinates are the
+ * mesh's own, the polygon order is instance-major as for tr_instance.  So a scene with table T renders, bit for bit and
+ * in every pipeline, what a scene created from the concatenated mesh transformed this way on the host renders
+ * (tr_instance_transform_mesh builds its positions and normals); a mirroring entry (det < 0) flips the winding and with
+ * it the culling, exactly as it does for that mesh.
+ * `n` is the caller's: the library does not derive it from `m`.  The reference normalises every transformed normal
+ * (shader.rs:368-371, 562-584), so any positive multiple of the inverse transpose of m's linear part gives the same
+ * picture up to rounding.
+ * Object-space normal maps do not turn: the closures of `normal_map` and `specular` take their normal from
+ * normal_map.tga in object space (util.rs:51-56), so those two pipelines light a turned instance as if it were not
+ * turned (their geometry, depth and culling do follow m).  `default`, `phong`, `darboux`, `shadow` and `occlusion`
+ * follow the transform through positions and vertex normals.
+ * One table at a time: a scene has one table, of either kind; setting one kind replaces the other, and n_instances == 0
+ * in either call draws the mesh itself.  Everything else -- the copy, frames issued earlier keeping their table, pool
+ * growth, the limit n_tri * n_instances < 0xFFFFFFF0, errors changing nothing -- is as for tr_scene_set_instances. */
+typedef struct tr_instance_xform {
+    float m[12];   /* position transform, row-major 3 x 4: row r = m[4r+0..2] (linear part), m[4r+3] (translation) */
+    float n[9];    /* normal transform, row-major 3 x 3 */
+    float pad[3];  /* ignored; keeps entries 16-byte aligned (six 16-byte loads) */
+} tr_instance_xform; /* 96 bytes */
+int tr_scene_set_instance_transforms(tr_scene *s, uint32_t n_instances, const tr_instance_xform *table);
+/* tr_scene_render_frames_instanced for transform tables: frame i draws table + i * n_instances; one fused launch per
+ * kernel for the frames of a group; the last frame's table is left current, tr_scene_select_frame restores a kept
+ * frame's. */
+int tr_scene_render_frames_transformed(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
+                                       const tr_instance_xform *table /* n_frames * n_instances */,
+                                       void *const *frame_buffers_device);
+/* The rule above on the host (no GPU needed, like tr_prepare_uniforms): positions and normals of the concatenated mesh
+ * that `table` draws, instance-major, computed by the very inline function the vertex stage calls.  mesh->tex and
+ * mesh->idx are not read. */
+int tr_instance_transform_mesh(const tr_mesh *mesh, uint32_t n_instances, const tr_instance_xform *table,
+                               float *pos_out /* n_instances*n_pos*3 */, float *nrm_out /* n_instances*n_nrm*3 */);
 int tr_scene_frames_per_launch(tr_scene *s); /* frames per group of this scene */
 int tr_scene_frames_kept(tr_scene *s);       /* frames of the last tr_scene_render_frames call that still exist
                                                 (0 after a tr_scene_render) */

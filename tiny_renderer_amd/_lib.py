@@ -66,6 +66,11 @@ class Instance(C.Structure):
     _fields_ = [("offset", C.c_float * 3), ("scale", C.c_float)]
 
 
+class InstanceXform(C.Structure):
+    """tr_instance_xform (include/tiny_renderer.h): a row-major 3 x 4 for positions, a row-major 3 x 3 for normals."""
+    _fields_ = [("m", C.c_float * 12), ("n", C.c_float * 9), ("pad", C.c_float * 3)]
+
+
 class BandTiles(C.Structure):
     """tr_band_tiles (include/tiny_renderer.h): a scene's band of a frame buffer, tile by tile."""
     _fields_ = [("frame_buffer_device", C.c_void_p), ("clean_device", C.c_void_p), ("width", C.c_uint32),
@@ -98,6 +103,9 @@ SYMBOLS = {
     "tr_scene_render_frames": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_set_instances": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "tr_scene_render_frames_instanced": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_instance_transforms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_render_frames_transformed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_instance_transform_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frames_per_launch": (C.c_int, [C.c_void_p]),
     "tr_scene_frames_kept": (C.c_int, [C.c_void_p]),
     "tr_scene_select_frame": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -38,6 +38,9 @@ def main(argv=None):
                          "run with several ranks on one GPU)")
     ap.add_argument("--instances", type=int, default=1,
                     help="draw the model N x N times, scaled by 1/N on a grid (instanced rendering; 1 = the model itself)")
+    ap.add_argument("--instance-yaw", type=float, default=None, metavar="DEG",
+                    help="with --instances N: turn grid cell (i, j) by (i * N + j) * DEG degrees about y (instance transforms; "
+                         "placed and scaled as --instances alone places them)")
     ap.add_argument("--ssaa", type=int, default=1, choices=(1, 2, 4, 8),
                     help="supersampling: render at F * width x F * height and write the width x height picture, each pixel "
                          "the rounded mean of its F x F samples (resolved on the GPU: Scene.resolve)")
@@ -105,7 +108,11 @@ def main(argv=None):
         if args.ssaa > 1:
             say("supersampling: rendering %d x %d" % (args.width * args.ssaa, args.height * args.ssaa))
         scene = T.Scene(args.width * args.ssaa, args.height * args.ssaa, mesh, texs, args.pipeline, device=args.device)
-    if args.instances > 1:
+    if args.instance_yaw is not None:
+        say("instances: %d x %d grid, cell (i, j) turned by (i * %d + j) * %g degrees about y"
+            % (args.instances, args.instances, args.instances, args.instance_yaw))
+        scene.set_instance_transforms(yawed_grid(T, args.instances, args.instance_yaw))
+    elif args.instances > 1:
         say("instances: %d x %d grid" % (args.instances, args.instances))
         scene.set_instances(T.grid_instances(args.instances))
     rc = _run(args, T, scene, sharded, rank, say)
@@ -115,6 +122,14 @@ def main(argv=None):
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def yawed_grid(T, n, degrees):
+    """--instance-yaw: grid_instances(n)'s offsets and scale as a transform table, cell k = i * n + j turned by
+    k * degrees about y."""
+    grid = T.grid_instances(n)
+    yaw = np.deg2rad(np.arange(n * n, dtype=np.float64) * degrees)
+    return T.rotation_instances(yaw, 0.0, 0.0, grid[:, 0:3], grid[:, 3])
 
 
 def _run(args, T, scene, sharded, rank, say):

@@ -20,8 +20,9 @@ namespace tr {
 // work lists from the TILE kernel's table (TileArgs::tile_count / order / list_len).
 // Vertex stage: every polygon's record into a.recs, its tiles' counters bumped.
 // `hurry`: nothing else is on the GPU and the caller's tile kernel waits for the chain (shapes for latency, not for
-// running beside a tile kernel).
-int launch_setup(int vs_kind, const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, bool hurry, hipStream_t st,
+// running beside a tile kernel).  `xform`: a frame of the launch draws a transform table (DevMesh::inst_xform) -- the
+// kernel with that branch; false: the kernel without it, which must then not meet such a table.
+int launch_setup(int vs_kind, const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, bool xform, bool hurry, hipStream_t st,
                  hipEvent_t start, hipEvent_t done);
 // The frame's lit texel image (k_lit: the normal-map / specular closure once per texel); a.lit, a.texel_set etc. say where.
 int launch_lit(int fs, const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t done);

@@ -68,7 +68,7 @@ constexpr uint32_t CHAIN_THREADS = 64 * CHAIN_WAVES;
 // Polygon t's record (P pieces) for the pass `a` describes: vertex closure, truncating projection, clamped box.
 // A polygon that draws nothing (culled, off screen, degenerate, t beyond the mesh) gets the canonical empty box
 // (bx0 = 1 > bx1 = 0) and nothing else.  Returns the device error bits the vertex stage raised.
-template <int VS, int P>
+template <int VS, int P, bool XF>
 __device__ __forceinline__ uint32_t setup_record(const SetupArgs &a, uint32_t t, uint4 (&o)[P])
 {
     uint32_t err = 0;
@@ -80,7 +80,7 @@ __device__ __forceinline__ uint32_t setup_record(const SetupArgs &a, uint32_t t,
     float v[VARY_STRIDE];
 #pragma unroll
     for (int i = 0; i < VARY_STRIDE; i++) v[i] = 0.0f;
-    const bool keep = vertex_stage<VS>(a.mesh, a.u, t, r, v, err);
+    const bool keep = vertex_stage<VS, XF>(a.mesh, a.u, t, r, v, err);
     if (keep)
         finish_raster_rec(r, a.frame);
     else
@@ -182,7 +182,8 @@ __device__ __forceinline__ uint32_t chain_polygon(uint32_t block, uint32_t polys
     return lane < polys ? lane * waves + wave : 0xFFFFFFFFu;
 }
 
-template <int VS>
+// XF: some frame of the launch draws a transform table (DevMesh::inst_xform); false: the kernel without that branch.
+template <int VS, bool XF>
 __device__ __forceinline__ void setup_body(const SetupArgs &a, uint32_t block, uint32_t polys)
 {
     constexpr int P = (VS == VS_DARBOUX) ? REC_PIECES_LARGE : REC_PIECES_SMALL;
@@ -195,7 +196,7 @@ __device__ __forceinline__ void setup_body(const SetupArgs &a, uint32_t block, u
     if (block == 0u && threadIdx.x < 16u) a.tile_count[a.frame.ntx * a.frame.nty + threadIdx.x] = 0u;
     const uint32_t t = chain_polygon(block, polys);
     uint4 rec[P];
-    const uint32_t err = setup_record<VS, P>(a, t, rec);
+    const uint32_t err = setup_record<VS, P, XF>(a, t, rec);
     if (t < a.mesh.n_tri) {
         uint4 *o = reinterpret_cast<uint4 *>(a.recs) + (size_t)t * P;
         o[0] = rec[0];
@@ -211,10 +212,10 @@ __device__ __forceinline__ void setup_body(const SetupArgs &a, uint32_t block, u
     }
 }
 
-template <int VS>
+template <int VS, bool XF>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_setup(SetupArgs a, uint32_t polys)
 {
-    setup_body<VS>(a, blockIdx.x, polys);
+    setup_body<VS, XF>(a, blockIdx.x, polys);
 }
 
 // k_bin: copies every polygon's record into the range of each tile its box meets, with the pair's coverage masks.
@@ -310,10 +311,10 @@ using constant_ptr = const __attribute__((address_space(4))) T *;
 
 // The same for a group of frames in one launch (tr_scene_render_frames): blockIdx.y = frame, whose
 // arguments are entry y of a table in device memory.
-template <int VS>
+template <int VS, bool XF>
 __global__ __launch_bounds__(CHAIN_THREADS) void k_setup_group(const SetupArgs *__restrict__ table, uint32_t polys)
 {
-    setup_body<VS>(*(const SetupArgs *)((constant_ptr<SetupArgs>)table + blockIdx.y), blockIdx.x, polys);
+    setup_body<VS, XF>(*(const SetupArgs *)((constant_ptr<SetupArgs>)table + blockIdx.y), blockIdx.x, polys);
 }
 
 template <int P>
@@ -1972,9 +1973,10 @@ static uint32_t chain_polys(uint32_t n_tri, uint32_t frames, bool hurry)
 }
 int rec_pieces_for_fs(int fs) { return fs == FS_DARBOUX ? REC_PIECES_LARGE : REC_PIECES_SMALL; }
 
-int launch_setup(int vs, const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, bool hurry, hipStream_t st,
+int launch_setup(int vs, const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, bool xform, bool hurry, hipStream_t st,
                  hipEvent_t start, hipEvent_t done)
 {
+    if (!group && xform != (a.mesh.inst_xform != 0u)) return (int)hipErrorInvalidValue;
     if ((int)a.rec_pieces != rec_pieces_for_vs(vs)) return (int)hipErrorInvalidValue;
     if (group && (n_frames == 0 || n_frames > 65535u)) return (int)hipErrorInvalidValue;
     // (an empty mesh: the first workgroup still zeroes the pass's list words)
@@ -1989,10 +1991,14 @@ int launch_setup(int vs, const SetupArgs &a, const SetupArgs *group, uint32_t n_
     const dim3 grid(a.mesh.n_tri ? (waves + per_group - 1u) / per_group : 1u, group ? n_frames : 1u), block(64u * per_group);
 #define TR_SETUP_CASE(V)                                                                   \
     case V:                                                                                \
-        if (group)                                                                         \
-            hipExtLaunchKernelGGL(k_setup_group<V>, grid, block, 0, st, start, done, 0, group, polys); \
+        if (group && xform)                                                                \
+            hipExtLaunchKernelGGL((k_setup_group<V, true>), grid, block, 0, st, start, done, 0, group, polys); \
+        else if (group)                                                                    \
+            hipExtLaunchKernelGGL((k_setup_group<V, false>), grid, block, 0, st, start, done, 0, group, polys); \
+        else if (xform)                                                                    \
+            hipExtLaunchKernelGGL((k_setup<V, true>), grid, block, 0, st, start, done, 0, a, polys); \
         else                                                                               \
-            hipExtLaunchKernelGGL(k_setup<V>, grid, block, 0, st, start, done, 0, a, polys);      \
+            hipExtLaunchKernelGGL((k_setup<V, false>), grid, block, 0, st, start, done, 0, a, polys); \
         break;
     switch (vs) {
     TR_SETUP_CASE(VS_DEFAULT)

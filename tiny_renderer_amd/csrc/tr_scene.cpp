@@ -170,8 +170,9 @@ struct tr_scene {
     // per stream that the chains reading it run on, recorded behind the last such chain.  A block is reused (or freed)
     // only when no InstRef holds it and those events have completed.
     struct InstBlock {
-        float *d = nullptr;      // cap x {offset xyz, scale}
-        uint32_t cap = 0;
+        float *d = nullptr;      // the entries: `stride` floats each
+        uint64_t cap = 0;        // floats the block holds
+        uint32_t stride = tr::INST_FLOATS;  // floats per entry: INST_FLOATS {offset xyz, scale} or INST_XFORM_FLOATS (a transform table)
         hipEvent_t used[3] = {}; // behind the last chain on the main stream, setup_stream, setup_stream2 that read it
     };
     struct InstRef {
@@ -520,7 +521,8 @@ DevMesh mesh_of(const tr_scene *s, const tr_scene::InstRef &r)
     m.tri = s->d_tri;
     m.n_tri = s->n_rows;
     if (r.n) {
-        m.inst = r.blk->d + 4u * (size_t)r.off;
+        m.inst = r.blk->d + (size_t)r.blk->stride * r.off;
+        m.inst_xform = r.blk->stride == (uint32_t)INST_XFORM_FLOATS ? 1u : 0u;
         m.n_rows = s->n_rows;
         m.n_tri = s->n_rows * r.n;  // (below 0xFFFFFFF0: checked by set_instances)
     }
@@ -541,7 +543,7 @@ int note_inst_use(tr_scene *s, const DevMesh &m, hipStream_t st)
     if (!m.inst) return TR_OK;
     const int k = st == s->setup_stream ? 1 : st == s->setup_stream2 ? 2 : 0;
     for (const std::shared_ptr<tr_scene::InstBlock> &b : s->inst_blocks)
-        if (m.inst >= b->d && m.inst < b->d + 4u * (size_t)b->cap) {
+        if (m.inst >= b->d && m.inst < b->d + b->cap) {
             if (!b->used[k]) HIP_TRY(hipEventCreateWithFlags(&b->used[k], hipEventDisableTiming));
             HIP_TRY(hipEventRecord(b->used[k], st));
             return TR_OK;
@@ -568,9 +570,11 @@ int inst_block_idle(tr_scene::InstBlock &b)
     return TR_OK;
 }
 
-// Copies `n` entries of `h` into a block of their own: one nobody holds whose readers have run, else a new one.
-int upload_instances(tr_scene *s, uint32_t n, const float *h, tr_scene::InstRef &out)
+// Copies `n` entries of `h`, `stride` floats each (the table's kind), into a block of their own: one nobody holds whose
+// readers have run, else a new one.
+int upload_instances(tr_scene *s, uint32_t n, uint32_t stride, const float *h, tr_scene::InstRef &out)
 {
+    const uint64_t floats = (uint64_t)n * stride;
     std::shared_ptr<tr_scene::InstBlock> pick;
     // free blocks: prefer one whose readers have finished; a free block too small for the table is given back
     for (size_t i = 0; i < s->inst_blocks.size();) {
@@ -579,7 +583,7 @@ int upload_instances(tr_scene *s, uint32_t n, const float *h, tr_scene::InstRef 
             i++;
             continue;
         }
-        if (b->cap < n) {
+        if (b->cap < floats) {
             int st = inst_block_idle(*b);
             if (st != TR_OK) return st;
             free_inst_block(*b);
@@ -597,12 +601,13 @@ int upload_instances(tr_scene *s, uint32_t n, const float *h, tr_scene::InstRef 
         if (st != TR_OK) return st;
     } else {
         pick = std::make_shared<tr_scene::InstBlock>();
-        int st = dev_alloc(&pick->d, 4u * (size_t)n);
+        int st = dev_alloc(&pick->d, (size_t)floats);
         if (st != TR_OK) return st;
-        pick->cap = n;
+        pick->cap = floats;
         s->inst_blocks.push_back(pick);
     }
-    HIP_TRY(hipMemcpy(pick->d, h, 16u * (size_t)n, hipMemcpyHostToDevice));
+    pick->stride = stride;
+    HIP_TRY(hipMemcpy(pick->d, h, sizeof(float) * (size_t)floats, hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(nullptr));  // (the scene's streams do not wait for the null stream)
     out.blk = pick;
     out.off = 0;
@@ -1194,7 +1199,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
         if (s->profiling) s->events.push_back(el);
     }
     if (!s->profiling) {
-        int rc = launch_setup(p.vs, sa, nullptr, 0, chain_on_main, chain, nullptr, nullptr);
+        int rc = launch_setup(p.vs, sa, nullptr, 0, sa.mesh.inst_xform != 0u, chain_on_main, chain, nullptr, nullptr);
         if (rc) return launch_status(rc, "k_setup");
         rc = launch_order(ta, n_tiles_pass, nullptr, 0, chain, nullptr, s->mesh.n_tri ? nullptr : s->ev_setup[p_seq % RING]);
         if (rc) return launch_status(rc, "k_order");
@@ -1203,7 +1208,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
     } else {
         // profiling: timing events on the dispatches themselves, then the pipeline's event separately
         EventPair ep = { take_event(s), take_event(s), K_SETUP, 1u };
-        int rc = launch_setup(p.vs, sa, nullptr, 0, chain_on_main, chain, ep.a, ep.b);
+        int rc = launch_setup(p.vs, sa, nullptr, 0, sa.mesh.inst_xform != 0u, chain_on_main, chain, ep.a, ep.b);
         if (rc) return launch_status(rc, "k_setup");
         s->events.push_back(ep);
         EventPair eo = { take_event(s), take_event(s), K_ORDER, 1u };
@@ -1649,7 +1654,9 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
             if (rc) return launch_status(rc, "k_lit");
             if (s->profiling) s->events.push_back(el);
         }
-        rc = launch_setup(pass.vs, sa0, d_setup + (size_t)pi * G, g, chain_on_main, chain, ep.a, ep.b);
+        bool xform = false;  // does any frame of the group draw a transform table?
+        for (uint32_t j = 0; j < g; j++) xform = xform || h_setup[(size_t)pi * G + j].mesh.inst_xform != 0u;
+        rc = launch_setup(pass.vs, sa0, d_setup + (size_t)pi * G, g, xform, chain_on_main, chain, ep.a, ep.b);
         if (rc) return launch_status(rc, "k_setup");
         rc = launch_order(h_tile[(size_t)pi * G], n_tiles_pass, d_tile + (size_t)pi * G, g, chain, eo.a, eo.b);
         if (rc) return launch_status(rc, "k_order");
@@ -2619,45 +2626,102 @@ int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params
     return render_frames(s, n_frames, frames, nullptr, frame_buffers_device);
 }
 
-int tr_scene_set_instances(tr_scene *s, uint32_t n_instances, const tr_instance *instances)
+// tr_scene_set_instances / tr_scene_set_instance_transforms: `table` holds n entries of `stride` floats.
+static int set_table(tr_scene *s, uint32_t n, uint32_t stride, const float *table)
 {
     if (!s) return tr::fail(TR_E_INVALID, "null scene");
-    int st = check_instances(s, n_instances, instances);
+    int st = check_instances(s, n, table);
     if (st != TR_OK) return st;
     HIP_TRY(hipSetDevice(s->device));
-    if ((st = grow_for_instances(s, n_instances)) != TR_OK) return st;
+    if ((st = grow_for_instances(s, n)) != TR_OK) return st;
     tr_scene::InstRef r;
-    if (n_instances && (st = upload_instances(s, n_instances, &instances[0].offset[0], r)) != TR_OK) return st;
+    if (n && (st = upload_instances(s, n, stride, table, r)) != TR_OK) return st;
     use_inst(s, r);
     return TR_OK;
+}
+
+// tr_scene_render_frames_instanced / tr_scene_render_frames_transformed: frame i draws entries [i n, (i + 1) n) of `tables`.
+static int render_frames_tables(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n, uint32_t stride,
+                                const float *tables, void *const *frame_buffers_device)
+{
+    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    int st = check_instances(s, n, tables);
+    if (st != TR_OK) return st;
+    if (n_frames == 0) return TR_OK;
+    if ((uint64_t)n_frames * n > 0xFFFFFFFFull) return tr::fail(TR_E_INVALID, "instance tables too large");
+    if (frame_buffers_device)
+        for (uint32_t i = 0; i < n_frames; i++)
+            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((st = grow_for_instances(s, n)) != TR_OK) return st;
+    // all the frames' tables as one block: frame i draws entries [i n, (i + 1) n)
+    std::vector<tr_scene::InstRef> insts(n_frames);
+    if (n) {
+        tr_scene::InstRef all;
+        if ((st = upload_instances(s, n_frames * n, stride, tables, all)) != TR_OK) return st;
+        for (uint32_t i = 0; i < n_frames; i++) {
+            insts[i] = all;
+            insts[i].off = i * n;
+            insts[i].n = n;
+        }
+    }
+    return render_frames(s, n_frames, frames, insts.data(), frame_buffers_device);
+}
+
+int tr_scene_set_instances(tr_scene *s, uint32_t n_instances, const tr_instance *instances)
+{
+    static_assert(sizeof(tr_instance) == sizeof(float) * tr::INST_FLOATS, "tr_instance is four floats");
+    return set_table(s, n_instances, tr::INST_FLOATS, reinterpret_cast<const float *>(instances));
+}
+
+int tr_scene_set_instance_transforms(tr_scene *s, uint32_t n_instances, const tr_instance_xform *table)
+{
+    static_assert(sizeof(tr_instance_xform) == sizeof(float) * tr::INST_XFORM_FLOATS, "tr_instance_xform is 24 floats");
+    return set_table(s, n_instances, tr::INST_XFORM_FLOATS, reinterpret_cast<const float *>(table));
 }
 
 int tr_scene_render_frames_instanced(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
                                      const tr_instance *instances, void *const *frame_buffers_device)
 {
-    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
-    int st = check_instances(s, n_instances, instances);
-    if (st != TR_OK) return st;
-    if (n_frames == 0) return TR_OK;
-    if ((uint64_t)n_frames * n_instances > 0xFFFFFFFFull) return tr::fail(TR_E_INVALID, "instance tables too large");
-    if (frame_buffers_device)
-        for (uint32_t i = 0; i < n_frames; i++)
-            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((st = grow_for_instances(s, n_instances)) != TR_OK) return st;
-    // all the frames' tables as one block: frame i draws entries [i n, (i + 1) n)
-    std::vector<tr_scene::InstRef> insts(n_frames);
-    if (n_instances) {
-        tr_scene::InstRef all;
-        if ((st = upload_instances(s, n_frames * n_instances, &instances[0].offset[0], all)) != TR_OK) return st;
-        for (uint32_t i = 0; i < n_frames; i++) {
-            insts[i] = all;
-            insts[i].off = i * n_instances;
-            insts[i].n = n_instances;
+    return render_frames_tables(s, n_frames, frames, n_instances, tr::INST_FLOATS, reinterpret_cast<const float *>(instances),
+                                frame_buffers_device);
+}
+
+int tr_scene_render_frames_transformed(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_instances,
+                                       const tr_instance_xform *table, void *const *frame_buffers_device)
+{
+    return render_frames_tables(s, n_frames, frames, n_instances, tr::INST_XFORM_FLOATS, reinterpret_cast<const float *>(table),
+                                frame_buffers_device);
+}
+
+// The concatenated mesh a transform table draws, on the host: the vertex stage's own xform_position / xform_normal
+// (tr_shaders.h) over the indexed arrays.  Needs no GPU.
+int tr_instance_transform_mesh(const tr_mesh *mesh, uint32_t n_instances, const tr_instance_xform *table, float *pos_out,
+                               float *nrm_out)
+{
+    if (!mesh || (n_instances && !table)) return tr::fail(TR_E_INVALID, "null argument");
+    if ((mesh->n_pos && (!mesh->pos || !pos_out)) || (mesh->n_nrm && (!mesh->nrm || !nrm_out)))
+        return tr::fail(TR_E_INVALID, "null array");
+    for (uint32_t k = 0; k < n_instances; k++) {
+        const tr_instance_xform &e = table[k];
+        float *po = pos_out + (size_t)k * mesh->n_pos * 3u, *no = nrm_out + (size_t)k * mesh->n_nrm * 3u;
+        for (uint32_t i = 0; i < mesh->n_pos; i++) {
+            float x = mesh->pos[3u * i], y = mesh->pos[3u * i + 1u], z = mesh->pos[3u * i + 2u];
+            tr::xform_position(e.m, x, y, z);
+            po[3u * i] = x;
+            po[3u * i + 1u] = y;
+            po[3u * i + 2u] = z;
+        }
+        for (uint32_t i = 0; i < mesh->n_nrm; i++) {
+            float a = mesh->nrm[3u * i], b = mesh->nrm[3u * i + 1u], c = mesh->nrm[3u * i + 2u];
+            tr::xform_normal(e.n, a, b, c);
+            no[3u * i] = a;
+            no[3u * i + 1u] = b;
+            no[3u * i + 2u] = c;
         }
     }
-    return render_frames(s, n_frames, frames, insts.data(), frame_buffers_device);
+    return TR_OK;
 }
 
 int tr_scene_frames_per_launch(tr_scene *s) { return s ? (int)group_size(s) : tr::fail(TR_E_INVALID, "null scene"); }

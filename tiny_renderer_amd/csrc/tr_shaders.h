@@ -47,9 +47,29 @@ TR_HD bool project_vertex(const float *mat, vec3 p, int32_t &rx, int32_t &ry, fl
     return true;
 }
 
+// One entry of a transform table (tr_instance_xform, include/tiny_renderer.h) applied to a position and to a vertex
+// normal: e = the row-major 3 x 4 (linear part | translation), n = the row-major 3 x 3.  Every product and every sum is
+// rounded once, left to right -- ((e0 x + e1 y) + e2 z) + e3 -- which is the whole contract: the vertex stage and
+// tr_instance_transform_mesh (the host's statement of what an instanced scene draws) both call these and nothing else.
+TR_HD void xform_position(const float *e, float &x, float &y, float &z)
+{
+    const float px = x, py = y, pz = z;
+    x = ((e[0] * px + e[1] * py) + e[2] * pz) + e[3];
+    y = ((e[4] * px + e[5] * py) + e[6] * pz) + e[7];
+    z = ((e[8] * px + e[9] * py) + e[10] * pz) + e[11];
+}
+TR_HD void xform_normal(const float *n, float &a, float &b, float &c)
+{
+    const float na = a, nb = b, nc = c;
+    a = (n[0] * na + n[1] * nb) + n[2] * nc;
+    b = (n[3] * na + n[4] * nb) + n[5] * nc;
+    c = (n[6] * na + n[7] * nb) + n[8] * nc;
+}
+
 // Runs vertex closure `VS` for polygon `t`.  Returns true when the polygon is kept; fills the
-// raster coordinates / z of `r` and the varyings.  `err` collects DevErr bits.
-template <int VS>
+// raster coordinates / z of `r` and the varyings.  `err` collects DevErr bits.  XF = false leaves the transform tables'
+// branch out: k_setup's instantiations for launches that draw none are the code they were before that branch existed.
+template <int VS, bool XF = true>
 TR_HD bool vertex_stage(const DevMesh &mesh, const DevUniforms &u, uint32_t t, RasterRec &r,
                         float *vary, uint32_t &err)
 {
@@ -76,7 +96,33 @@ TR_HD bool vertex_stage(const DevMesh &mesh, const DevUniforms &u, uint32_t t, R
 #else
     for (int i = 0; i < TRI_FLOATS; i++) m[i] = row[i];
 #endif
-    if (mesh.inst) {
+    if (XF && mesh.inst && mesh.inst_xform) {
+        // the instance's transform (a table of the second kind): positions for every closure, vertex normals where the
+        // closure reads them -- the face normal of VS_DEFAULT is formed from the transformed positions below.  Six
+        // 16-byte loads per lane (four where the normals' rows are not wanted), ahead of everything that reads `m`.
+        float e[INST_XFORM_FLOATS];
+#if defined(__HIP_DEVICE_COMPILE__)
+        {
+            const float4 *e4 = reinterpret_cast<const float4 *>(mesh.inst) + (size_t)(INST_XFORM_FLOATS / 4) * k;
+#pragma unroll
+            for (int i = 0; i < INST_XFORM_FLOATS / 4; i++) {
+                const float4 q = e4[i];
+                e[4 * i] = q.x;
+                e[4 * i + 1] = q.y;
+                e[4 * i + 2] = q.z;
+                e[4 * i + 3] = q.w;
+            }
+        }
+#else
+        for (int i = 0; i < INST_XFORM_FLOATS; i++) e[i] = mesh.inst[(size_t)INST_XFORM_FLOATS * k + i];
+#endif
+#pragma unroll
+        for (int i = 0; i < 3; i++) xform_position(e, m[3 * i + 0], m[3 * i + 1], m[3 * i + 2]);
+        if (VS == VS_PHONG || VS == VS_DARBOUX) {
+#pragma unroll
+            for (int i = 0; i < 3; i++) xform_normal(e + 12, m[9 + 3 * i], m[10 + 3 * i], m[11 + 3 * i]);
+        }
+    } else if (mesh.inst) {
         // the instance's placement: p * scale + offset, two roundings (the library is built with -ffp-contract=off).
         // (One 16-byte load per lane: a wave's lanes take polygons `waves` apart (chain_polygon), so they rarely
         // share an instance; the table is small and stays in cache.)

@@ -131,12 +131,19 @@ constexpr int TRI_FLOATS = 24;
 // Instancing (tr_scene_set_instances): with a table, polygon t of a pass is row t % n_rows of instance t / n_rows,
 // its positions p replaced by p * scale + offset (multiply, then add, each rounded once).  Without one (inst null,
 // the default) polygon t is row t, untransformed -- not the same as one instance {0, 0, 0, 1}: -0 * 1 + 0 = +0.
+// A table of the second kind (tr_scene_set_instance_transforms, inst_xform != 0) has 24 floats per instance -- a
+// row-major 3 x 4 for the positions, a row-major 3 x 3 for the vertex normals, 3 floats unused -- applied by
+// xform_position / xform_normal (tr_shaders.h).
+constexpr int INST_FLOATS = 4;         // floats per entry of an offset/scale table (tr_instance)
+constexpr int INST_XFORM_FLOATS = 24;  // ... of a transform table (tr_instance_xform)
 struct DevMesh {
     const float *tri;  // rows * TRI_FLOATS
     uint32_t n_tri;    // polygons of a pass: the rows, or n_rows * instances with a table
-    const float *inst = nullptr;  // instances x {offset x, y, z, scale}, 16-byte aligned; null: the mesh itself
+    const float *inst = nullptr;  // instances x {offset x, y, z, scale} or x 24 floats, 16-byte aligned; null: the mesh itself
     uint32_t n_rows = 0;          // rows of `tri` (with a table)
+    uint32_t inst_xform = 0;      // 1: `inst` is a transform table (in what was the structure's tail padding: no member moves)
 };
+static_assert(sizeof(DevMesh) == 32, "DevMesh keeps its size and layout");
 
 // Fills one row of DevMesh::tri from the indexed arrays (util.rs:25-31, shader.rs:136-147,363-367).
 inline void gather_polygon(const float *pos, const float *tex, const float *nrm, const uint32_t *ix, float *out)

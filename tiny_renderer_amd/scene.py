@@ -34,6 +34,27 @@ def _instance_table(instances, per_frame=False):
     return a
 
 
+def _transform_table(table, per_frame=False):
+    """[n, 24] float32 (tr_instance_xform: m 3 x 4, n 3 x 3, 3 unused) -- or [n_frames, n, 24] with per_frame."""
+    a = np.ascontiguousarray(table, np.float32)
+    if a.shape[-1:] != (24,) or a.ndim != (3 if per_frame else 2):
+        raise ValueError("instance transform table must be [%sn, 24] float32 (instance_transforms builds one)"
+                         % ("n_frames, " if per_frame else ""))
+    return a
+
+
+def transform_mesh(mesh, table):
+    """tr_instance_transform_mesh: (pos [n * n_pos, 3], nrm [n * n_nrm, 3]) of the concatenated mesh the [n, 24] transform
+    table draws, by the inline function the vertex stage calls, on the host (no GPU needed)."""
+    a = _transform_table(table)
+    keep = []
+    m = _mesh_struct(mesh, keep)
+    pos = np.empty((a.shape[0] * m.n_pos, 3), np.float32)
+    nrm = np.empty((a.shape[0] * m.n_nrm, 3), np.float32)
+    check(load_library().tr_instance_transform_mesh(C.byref(m), a.shape[0], a.ctypes.data, pos.ctypes.data, nrm.ctypes.data))
+    return pos, nrm
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -43,12 +64,17 @@ class Scene:
     textures: uint8 [h,w,3] arrays in Scene::new's order.
     Extra keyword options are the tr_options of include/tiny_renderer.h.
     instances: optional [n, 4] float32 instance table (set_instances) drawn from the first frame on.
+    instance_transforms: optional [n, 24] float32 transform table (set_instance_transforms) instead; a scene has one
+          table, so giving both is a ValueError.
     """
 
     def __init__(self, width, height, mesh, textures, shader_pipeline_name, *, device=-1,
                  winner_tap=False, tile_stamps=False, band_rows=None, stream=None, frame_buffer_device=None,
                  bin_capacity=0, tile_waves=0, tile_mode=0, frames_per_launch=0, auto_group=True,
-                 trust_frame_buffers=False, max_frame_slots=0, store_depth=False, instances=None):
+                 trust_frame_buffers=False, max_frame_slots=0, store_depth=False, instances=None,
+                 instance_transforms=None):
+        if instances is not None and instance_transforms is not None:
+            raise ValueError("a scene draws one table: instances= or instance_transforms=, not both")
         L = load_library()
         self.width, self.height = int(width), int(height)
         keep = []
@@ -85,6 +111,8 @@ class Scene:
         self.pipeline = shader_pipeline_name
         if instances is not None:
             self.set_instances(instances)
+        if instance_transforms is not None:
+            self.set_instance_transforms(instance_transforms)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -127,13 +155,28 @@ class Scene:
         a = _instance_table(instances)
         check(L.tr_scene_set_instances(self._h, a.shape[0], a.ctypes.data))
 
-    def render_frames(self, frames, frame_buffers_device=None, instances=None):
+    def set_instance_transforms(self, table):
+        """tr_scene_set_instance_transforms: draw the mesh once per row of the [n, 24] float32 table (instance_transforms
+        builds one: a 3 x 4 for positions, a 3 x 3 for vertex normals), replacing a table of either kind; None or an
+        empty table: the mesh itself."""
+        L = load_library()
+        if table is None or len(table) == 0:
+            check(L.tr_scene_set_instance_transforms(self._h, 0, None))
+            return
+        a = _transform_table(table)
+        check(L.tr_scene_set_instance_transforms(self._h, a.shape[0], a.ctypes.data))
+
+    def render_frames(self, frames, frame_buffers_device=None, instances=None, instance_transforms=None):
         """tr_scene_render_frames: `frames` is an [n, 12] float32 array (or a list of (light, look_from,
         look_at, up) tuples): per frame light direction, look_from, look_at, up.  Frame i is what
         clear(); set_light_direction; set_camera; render() produces; the frames of a group are rendered by
         one launch per kernel.  frame_buffers_device: optional list of n device pointers (colour targets).
         instances: optional [n, n_instances, 4] float32 -- frame i draws table instances[i] (what set_instances
-        before its render would do; tr_scene_render_frames_instanced); None: the current table in every frame."""
+        before its render would do; tr_scene_render_frames_instanced); None: the current table in every frame.
+        instance_transforms: the same with transform tables, [n, n_instances, 24] float32
+        (tr_scene_render_frames_transformed); at most one of the two."""
+        if instances is not None and instance_transforms is not None:
+            raise ValueError("one table per frame: instances= or instance_transforms=, not both")
         if not isinstance(frames, np.ndarray):
             frames = np.asarray([np.concatenate([np.asarray(v, np.float32).reshape(3) for v in f]) for f in frames],
                                 np.float32)
@@ -143,6 +186,13 @@ class Scene:
             if len(frame_buffers_device) != len(frames):
                 raise ValueError("one frame buffer per frame")
             fbs = (C.c_void_p * len(frames))(*[int(q) for q in frame_buffers_device])
+        if instance_transforms is not None:
+            xf = _transform_table(instance_transforms, per_frame=True)
+            if xf.shape[0] != len(frames):
+                raise ValueError("one instance transform table per frame")
+            check(load_library().tr_scene_render_frames_transformed(self._h, len(frames), frames.ctypes.data, xf.shape[1],
+                                                                    xf.ctypes.data if xf.size else None, fbs))
+            return
         if instances is None:
             check(load_library().tr_scene_render_frames(self._h, len(frames), frames.ctypes.data, fbs))
             return

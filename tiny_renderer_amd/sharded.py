@@ -263,22 +263,33 @@ class ShardedScene:
         """Scene.set_instances on this rank's band scene (collective in spirit: every rank draws the same table)."""
         self._scene.set_instances(instances)
 
-    def render_frames(self, frames, instances=None):
+    def set_instance_transforms(self, table):
+        """Scene.set_instance_transforms on this rank's band scene (every rank draws the same table)."""
+        self._scene.set_instance_transforms(table)
+
+    def render_frames(self, frames, instances=None, instance_transforms=None):
         """Many frames per call (Scene.render_frames on every rank); afterwards only the LAST frame is exposed
         (get_frame_buffer): each rank renders its band of a group of
         frames by one launch of each kernel into a set of frame tensors of the group's size, and the bands
         of the group are exchanged frame by frame on the second stream while the next group renders into
         the other set.  Frame i is what clear(); set_light_direction; set_camera; render() gives; afterwards
         the last frame is the one get_frame_buffer() returns.  instances: optional [n, n_instances, 4] float32, frame
-        i's instance table (Scene.render_frames).  Collective: all ranks pass the same frames."""
+        i's instance table (Scene.render_frames); instance_transforms: the same with [n, n_instances, 24] transform
+        tables (at most one of the two).  Collective: all ranks pass the same frames."""
         import numpy as np
         torch, dist = self._torch, self._dist
         frames = np.ascontiguousarray(frames, np.float32).reshape(-1, 12)
         if len(frames) == 0:
             return
-        if instances is not None:
-            instances = np.ascontiguousarray(instances, np.float32)
-            if len(instances) != len(frames):
+        if instances is not None and instance_transforms is not None:
+            raise ValueError("one table per frame: instances= or instance_transforms=, not both")
+        # the frames' tables, of either kind, and the keyword Scene.render_frames takes them by
+        tables, table_kw = instances, "instances"
+        if instance_transforms is not None:
+            tables, table_kw = instance_transforms, "instance_transforms"
+        if tables is not None:
+            tables = np.ascontiguousarray(tables, np.float32)
+            if len(tables) != len(frames):
                 raise ValueError("one instance table per frame")
         G = self._scene.frames_per_launch
         if not hasattr(self, "_gsets"):
@@ -300,7 +311,7 @@ class ShardedScene:
                     self._render.wait_event(self._ggathered[b])   # the set's previous exchange has finished
                 t0 = self._stamp(self._render) if self._timing is not None else None
                 self._scene.render_frames(frames[i0:i0 + g], [t.data_ptr() for t in self._gsets[b][:g]],
-                                          instances=None if instances is None else instances[i0:i0 + g])
+                                          **({} if tables is None else {table_kw: tables[i0:i0 + g]}))
                 t1 = self._stamp(self._render) if self._timing is not None else None
                 self._grendered[b].record(self._render)
             with torch.cuda.stream(self._comm):
@@ -312,7 +323,8 @@ class ShardedScene:
                     self._timing.append((t0, t1, t2, self._stamp(self._comm), g))
                 self._ggathered[b].record(self._comm)
             self._gused[b] = True
-            self._last_group = (frames[i0:i0 + g].copy(), b, None if instances is None else instances[i0:i0 + g].copy())
+            self._last_group = (frames[i0:i0 + g].copy(), b,
+                                {} if tables is None else {table_kw: tables[i0:i0 + g].copy()})
         self._last_tensor = self._gsets[self._gset][g - 1]
         q = frames[-1]
         self._scene.set_light_direction(q[0:3])
@@ -347,9 +359,9 @@ class ShardedScene:
             if not self._last_was_cleared:
                 raise TinyRendererError(TR_E_BIN_OVERFLOW, "bins overflowed during an accumulating render: clear and render again")
             if self._last_group is not None:
-                again, b, again_inst = self._last_group
+                again, b, again_tables = self._last_group
                 self._gset = b ^ 1       # ... into the same set of frame tensors
-                self.render_frames(again, instances=again_inst)
+                self.render_frames(again, **again_tables)
                 continue
             self._scene.clear()          # same light and camera: the scene still holds them
             self._cleared = True
