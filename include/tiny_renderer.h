@@ -231,6 +231,53 @@ int tr_scene_render_frames_transformed(tr_scene *s, uint32_t n_frames, const tr_
  * mesh->idx are not read. */
 int tr_instance_transform_mesh(const tr_mesh *mesh, uint32_t n_instances, const tr_instance_xform *table,
                                float *pos_out /* n_instances*n_pos*3 */, float *nrm_out /* n_instances*n_nrm*3 */);
+/* Morph targets (blend shapes; nothing of the kind upstream, whose mesh is frozen at Scene::new): the SHAPE of the mesh
+ * per frame.  A scene gets T targets, 1 <= T <= TR_MORPH_MAX_TARGETS (an interface limit, not a measured one); each is
+ * a set of deltas laid out like the mesh's own arrays -- dpos: n_pos * 3 floats, dnrm: n_nrm * 3 floats.  A pose is a
+ * weight vector w[0..T).  Every position component p with deltas d_k, and in the same way every normal component, is
+ * drawn as
+ *     v = p
+ *     for k = 0 .. T-1, in this order, skipping every k with w[k] == 0.0f (either sign):
+ *         v = fl( v + fl( w[k] * d_k ) )          -- one multiply, one add, each rounded once; no fused multiply-add
+ * Texture coordinates and indices are the mesh's own.  Skipping zero weights is part of the rule: a pose of zeros is
+ * the mesh itself bit for bit, -0.0 components and targets holding inf or nan included.  Normals are not renormalised
+ * (the reference normalises every transformed normal, shader.rs:368-371, 562-584).  So a scene under pose w renders,
+ * bit for bit and in every pipeline, what a scene created from the host-morphed mesh (tr_morph_mesh) renders.
+ * Object-space normal maps do not deform -- the caveat of tr_instance_xform: `normal_map` and `specular` follow the
+ * deformation in geometry, depth and culling but take their light from normal_map.tga.
+ * tr_scene_set_morph_targets copies the deltas (dpos: n_targets * n_pos * 3 floats, dnrm: n_targets * n_nrm * 3,
+ * target-major), gathers them per polygon as the mesh was and uploads them once; n_targets == 0 (the arrays may then be
+ * NULL) drops the targets and the current pose.  It waits for the scene's queued work.  New targets leave the scene
+ * without a pose as well (a pose belongs to the targets it was set under); frames already rendered are what they are.
+ * tr_scene_set_morph_weights: the pose is scene state like the camera -- renders issued after the call draw it, frames
+ * issued before (also those tr_scene_render holds back to fuse) keep theirs.  n_weights must be 0 or T; 0 draws the
+ * mesh itself straight from its own rows (no blend kernel runs).  The weights are copied.
+ * Morphing composes with instancing: the pose deforms the mesh, then the scene's current table, of either kind, places
+ * or turns the deformed mesh -- polygon order, winner tap, tie order and culling are those of the concatenated,
+ * host-morphed-then-transformed mesh.  One pose per frame applies to all instances.
+ * Errors (T above the limit, a weight count that is neither 0 nor T, a NULL where data is required) are TR_E_INVALID
+ * and change nothing. */
+#define TR_MORPH_MAX_TARGETS 64
+int tr_scene_set_morph_targets(tr_scene *s, uint32_t n_targets, const float *dpos, const float *dnrm);
+int tr_scene_set_morph_weights(tr_scene *s, uint32_t n_weights, const float *w);
+/* tr_scene_render_frames with a pose per frame: frame i is exactly
+ *     tr_scene_set_morph_weights(s, n_weights, weights + i * n_weights); tr_scene_clear; set_light_direction;
+ *     set_camera; tr_scene_render
+ * (still one fused launch per kernel for the frames of a group; their poses are blended by one launch of k_morph ahead
+ * of it).  The last frame's pose is left current; tr_scene_select_frame makes a kept frame's pose current with its light
+ * and camera.  The scene's current instance table applies to every frame.  Plain tr_scene_render_frames, _instanced and
+ * _transformed draw the current pose in every frame. */
+int tr_scene_render_frames_morphed(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_weights,
+                                   const float *weights /* n_frames * n_weights */, void *const *frame_buffers_device);
+/* Diagnostic: sets of posed rows (n_tri * 96 bytes each) the scene has on the device now -- those of the poses its frame
+ * slots, kept frames, held-back frames and current state hold, and free ones waiting to be used again.  Bounded by the
+ * frame slots plus the frames in flight, whatever the length of a tr_scene_render_frames_morphed call; free ones go back
+ * to the device beyond a group's worth and at tr_scene_set_morph_targets. */
+int tr_scene_debug_morph_rows(tr_scene *s);
+/* The rule above on the host (no GPU needed): positions and normals of `mesh` under pose w (n_targets weights),
+ * computed by the very inline function k_morph calls.  mesh->tex and mesh->idx are not read. */
+int tr_morph_mesh(const tr_mesh *mesh, uint32_t n_targets, const float *dpos, const float *dnrm, const float *w,
+                  float *pos_out /* n_pos*3 */, float *nrm_out /* n_nrm*3 */);
 int tr_scene_frames_per_launch(tr_scene *s); /* frames per group of this scene */
 int tr_scene_frames_kept(tr_scene *s);       /* frames of the last tr_scene_render_frames call that still exist
                                                 (0 after a tr_scene_render) */

@@ -78,6 +78,9 @@ class BandTiles(C.Structure):
                 ("band_y0", C.c_int32), ("band_y1", C.c_int32)]
 
 
+TR_MORPH_MAX_TARGETS = 64  # include/tiny_renderer.h
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double), ("frames", C.c_uint64)]
 
@@ -106,6 +109,11 @@ SYMBOLS = {
     "tr_scene_set_instance_transforms": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "tr_scene_render_frames_transformed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_instance_transform_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_morph_targets": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_morph_weights": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_render_frames_morphed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_debug_morph_rows": (C.c_int, [C.c_void_p]),
+    "tr_morph_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frames_per_launch": (C.c_int, [C.c_void_p]),
     "tr_scene_frames_kept": (C.c_int, [C.c_void_p]),
     "tr_scene_select_frame": (C.c_int, [C.c_void_p, C.c_uint32]),

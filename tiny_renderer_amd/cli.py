@@ -44,7 +44,13 @@ def main(argv=None):
     ap.add_argument("--ssaa", type=int, default=1, choices=(1, 2, 4, 8),
                     help="supersampling: render at F * width x F * height and write the width x height picture, each pixel "
                          "the rounded mean of its F x F samples (resolved on the GPU: Scene.resolve)")
+    ap.add_argument("--morph-to", default=None, metavar="OBJ",
+                    help="a second OBJ of the model's topology: one morph target (its positions and normals minus the "
+                         "model's), drawn at --morph-weight; with --frames N the weight runs a triangle wave between 0 and it")
+    ap.add_argument("--morph-weight", type=float, default=1.0, metavar="W", help="weight of the --morph-to target (default 1)")
     args = ap.parse_args(argv)
+    if args.morph_to and (args.gpus > 1 or args.seconds > 0):
+        ap.error("--morph-to poses the scene of one GPU, by frame count: use --gpus 1 and --frames")
     if args.ssaa > 1 and (args.gpus > 1 or args.view != "frame"):
         ap.error("--ssaa resolves the colour frame of one GPU: use --gpus 1 and --view frame")
     if args.gpus < 1:
@@ -115,6 +121,10 @@ def main(argv=None):
     elif args.instances > 1:
         say("instances: %d x %d grid" % (args.instances, args.instances))
         scene.set_instances(T.grid_instances(args.instances))
+    if args.morph_to:
+        say("morph target: %s, weight %g" % (args.morph_to, args.morph_weight))
+        scene.set_morph_targets(*T.morph_deltas(mesh, T.load_obj(args.morph_to)))
+        scene.set_morph_weights([args.morph_weight])
     rc = _run(args, T, scene, sharded, rank, say)
     if sharded:
         import torch.distributed as dist
@@ -130,6 +140,12 @@ def yawed_grid(T, n, degrees):
     grid = T.grid_instances(n)
     yaw = np.deg2rad(np.arange(n * n, dtype=np.float64) * degrees)
     return T.rotation_instances(yaw, 0.0, 0.0, grid[:, 0:3], grid[:, 3])
+
+
+def morph_wave(n_frames, weight):
+    """--morph-to over --frames N: [N, 1] weights, a triangle wave from 0 up to `weight` and back, one period per call."""
+    t = np.arange(n_frames, dtype=np.float64) / max(n_frames, 1)
+    return (weight * (1.0 - np.abs(2.0 * t - 1.0))).astype(np.float32).reshape(n_frames, 1)
 
 
 def _run(args, T, scene, sharded, rank, say):
@@ -177,7 +193,10 @@ def _run(args, T, scene, sharded, rank, say):
         p[:, 0:3] = [float(np.sin(la)), 0.0, float(np.cos(la))]
         for f, ca in enumerate(angles):
             p[f, 3:6], p[f, 6:9], p[f, 9:12] = [float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0]
-        scene.render_frames(p)
+        if args.morph_to:
+            scene.render_frames(p, morph_weights=morph_wave(args.frames, args.morph_weight))
+        else:
+            scene.render_frames(p)
         angles = []
     for ca in angles:
         scene.clear()                                                        # app.rs:170

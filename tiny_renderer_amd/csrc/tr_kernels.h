@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include "tr_morph.h"
 #include "tr_types.h"
 
 namespace tr {
@@ -56,6 +57,11 @@ int launch_push_tiles(const uint8_t *fb, uint8_t *peer, const uint32_t *fb_clean
 // memory): k_resolve.  fb_clean: the target's colour-clean flags (tiles not read, stored as zeros) or null.
 int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, const DevFrame &frame, uint32_t factor,
                    hipStream_t st);
+// Morph targets: the posed rows of n_frames frames (<= MORPH_MAX_FRAMES) by one launch -- frame f blends the mesh's
+// gathered rows `base` (n_rows x TRI_FLOATS) with the gathered delta rows `delta` (n_targets x n_rows x TRI_FLOATS) under
+// the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.
+int launch_morph(const float *base, const float *delta, uint32_t n_rows, uint32_t n_targets, const MorphTable &tab, uint32_t n_frames,
+                 hipStream_t st, hipEvent_t start, hipEvent_t done);
 int launch_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32, int32_t *out_i32,
                     uint32_t *out_u8, float *out_div, float *out_div_ref, hipStream_t st);
 // Peer exchange flags (tr_exchange.cpp): system-scope store of a generation number; waits that poll

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "tr_kernels.h"
+#include "tr_morph.h"
 #include "tr_plan.h"
 #include "tr_resolve.h"
 #include "tr_shaders.h"
@@ -1784,6 +1785,48 @@ __global__ __launch_bounds__(64) void k_resolve(const uint8_t *__restrict__ fb, 
     }
 }
 
+// Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
+// mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
+// pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
+// tr_morph.h has the rule.  A lane owns one 16-byte piece of a row: a row of 24 floats is positions [0..8], normals
+// [9..17], uvs [18..23], so pieces 0..3 of a row are blended whole, piece 4 in its first two floats (the last normal's
+// y and z) and piece 5 -- uvs -- is the mesh's own.  The weights are the same for every lane of the launch's frame:
+// scalar loads, and a target of weight zero is skipped by a wave-uniform branch before its deltas are loaded.
+// Per frame it reads the base rows and one set of delta rows per non-zero weight and writes the posed rows, all in
+// 16-byte pieces.  The target loop is serial -- scalar load of the weight, branch, the target's load, wait -- so a small
+// mesh is bound by that latency and the launch, not by memory.  No LDS, no atomics, no scratch.
+__global__ __launch_bounds__(256) void k_morph(const float4 *__restrict__ base, const float4 *__restrict__ delta, uint32_t n_pieces,
+                                               uint32_t n_targets, MorphTable tab)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_pieces) return;
+    const MorphFrame fr = tab.f[blockIdx.y];  // (the table is in the kernel's argument segment: scalar loads)
+    const constant_ptr<float> w = (constant_ptr<float>)fr.w;
+    float4 *__restrict__ dst = reinterpret_cast<float4 *>(fr.dst);
+    const float4 p = base[i];
+    float4 v = p;
+    for (uint32_t k = 0; k < n_targets; k++) {
+        const float wk = w[k];
+        if (wk != 0.0f) {
+            const float4 d = delta[(size_t)k * n_pieces + i];
+            v.x = morph_step(v.x, wk, d.x);
+            v.y = morph_step(v.y, wk, d.y);
+            v.z = morph_step(v.z, wk, d.z);
+            v.w = morph_step(v.w, wk, d.w);
+        }
+    }
+    const uint32_t piece = i % 6u;
+    if (piece >= 4u) {
+        v.z = p.z;
+        v.w = p.w;
+        if (piece == 5u) {
+            v.x = p.x;
+            v.y = p.y;
+        }
+    }
+    dst[i] = v;
+}
+
 // tr_selftest_device_math: the device forms of the casts and of the shared-reciprocal division,
 // applied to caller-chosen operands so the host can compare them with its own.
 __global__ __launch_bounds__(256) void k_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32,
@@ -2209,6 +2252,19 @@ int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, co
     if (factor == 2u) return launch_resolve_f<2>(fb, out, fb_clean, frame, wide, st);
     if (factor == 4u) return launch_resolve_f<4>(fb, out, fb_clean, frame, wide, st);
     return launch_resolve_f<8>(fb, out, fb_clean, frame, wide, st);
+}
+
+int launch_morph(const float *base, const float *delta, uint32_t n_rows, uint32_t n_targets, const MorphTable &tab, uint32_t n_frames,
+                 hipStream_t st, hipEvent_t start, hipEvent_t done)
+{
+    if (n_rows == 0 || n_frames == 0) return 0;
+    if (n_frames > (uint32_t)MORPH_MAX_FRAMES || n_rows > 0xFFFFFFFFu / 6u) return (int)hipErrorInvalidValue;
+    const uint32_t n_pieces = n_rows * 6u;  // 16-byte pieces of the rows
+    const dim3 grid((n_pieces + 255u) / 256u, n_frames);
+    hipExtLaunchKernelGGL(k_morph, grid, dim3(256), 0, st, start, done, 0, reinterpret_cast<const float4 *>(base),
+                          reinterpret_cast<const float4 *>(delta), n_pieces, n_targets, tab);
+    TR_LAUNCH_CHECK();
+    return 0;
 }
 
 int launch_selftest_shadow(const float *plain, const float *stale, const uint32_t *sclean, uint32_t W, uint32_t H,

@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -175,10 +175,48 @@ struct tr_scene {
         uint32_t stride = tr::INST_FLOATS;  // floats per entry: INST_FLOATS {offset xyz, scale} or INST_XFORM_FLOATS (a transform table)
         hipEvent_t used[3] = {}; // behind the last chain on the main stream, setup_stream, setup_stream2 that read it
     };
+    // Morph targets (tr_scene_set_morph_targets / _weights).  A pose is the host's copy of a weight vector and, from the
+    // first render that draws it, its posed rows on the device: what DevMesh::tri points at instead of d_tri.  The rows
+    // have the lifetime of an instance table's block: written once -- by k_morph, queued ahead of the first chain that
+    // reads them (blend_poses) -- and never again while anybody may render with them; the holders are the same (a pose
+    // travels in the InstRef beside the table).  When the last holder lets go, the rows go back to the scene's pool
+    // (pose_free) with one event per stream whose chains read them; they are handed out again when those have completed.
+    struct SharedEvent {
+        hipEvent_t ev = nullptr;
+        ~SharedEvent() { if (ev) (void)hipEventDestroy(ev); }
+    };
+    struct PoseRows {
+        float *d = nullptr;                     // n_rows * TRI_FLOATS
+        std::shared_ptr<SharedEvent> used[3];   // behind the last chain on the main stream, setup_stream, setup_stream2 that read them
+    };
+    struct Pose {
+        tr_scene *owner = nullptr;
+        std::vector<float> w;                   // the weights: n_targets of them
+        PoseRows rows;                          // (d null until a render is about to draw the pose: pose_rows)
+        bool blended = false;                   // k_morph has been queued for the rows
+        std::shared_ptr<SharedEvent> done;      // ... and this is recorded behind it, on `done_on`
+        hipStream_t done_on = nullptr;
+        bool done_seen = false;                 // the host has seen `done` completed: no chain needs to wait for it
+        ~Pose();
+    };
     struct InstRef {
         std::shared_ptr<InstBlock> blk;  // null: no table (the mesh itself)
         uint32_t off = 0, n = 0;         // entries [off, off + n) of the block
+        std::shared_ptr<Pose> pose;      // null: the mesh's own rows
     };
+    std::vector<PoseRows> pose_free;     // posed rows nobody holds
+    uint32_t pose_rows_live = 0;         // sets of posed rows allocated: held ones and free ones (tr_scene_debug_morph_rows)
+    uint32_t n_targets = 0;              // morph targets of the scene
+    float *d_delta = nullptr;            // their gathered delta rows: n_targets x n_rows x TRI_FLOATS (uv floats zero, unused)
+    std::vector<uint32_t> mesh_idx;      // the mesh's indices (n_rows * 9), kept to gather the targets' deltas
+    uint32_t n_pos = 0, n_nrm = 0;
+    // k_morph's weights on their way to the device: a ring of page-locked staging buffers and their device copies, one per
+    // launch in flight (GROUP_MAX frames x TR_MORPH_MAX_TARGETS floats each); `done` = the launch that last read it
+    struct MorphStage {
+        float *h = nullptr, *d = nullptr;
+        std::shared_ptr<SharedEvent> done;
+    } morph_stage[4];
+    uint64_t morph_launches = 0;
     InstRef inst;                    // the current table
     std::vector<std::shared_ptr<InstBlock>> inst_blocks;  // every block the scene owns
     uint32_t n_rows = 0;             // polygons of the mesh (rows of d_tri)
@@ -384,6 +422,12 @@ struct tr_scene {
     std::vector<float> frame_intervals_us;  // completion-to-completion time of consecutive colour-pass tile kernels
 };
 
+// The last holder of a pose lets go: its rows go back to the scene's pool with the events of their readers.
+tr_scene::Pose::~Pose()
+{
+    if (rows.d && owner) owner->pose_free.push_back(rows);
+}
+
 namespace {
 
 template <typename T>
@@ -518,7 +562,7 @@ int need_z(tr_scene *s, int k)
 DevMesh mesh_of(const tr_scene *s, const tr_scene::InstRef &r)
 {
     DevMesh m = {};
-    m.tri = s->d_tri;
+    m.tri = r.pose ? r.pose->rows.d : s->d_tri;  // (a pose's rows: null until pose_rows has run -- run_pass / run_group check)
     m.n_tri = s->n_rows;
     if (r.n) {
         m.inst = r.blk->d + (size_t)r.blk->stride * r.off;
@@ -612,6 +656,159 @@ int upload_instances(tr_scene *s, uint32_t n, uint32_t stride, const float *h, t
     out.blk = pick;
     out.off = 0;
     out.n = n;
+    return TR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Morph targets
+// ---------------------------------------------------------------------------------------------
+
+hipEvent_t take_event(tr_scene *s);
+int launch_status(int rc, const char *what);
+
+std::shared_ptr<tr_scene::SharedEvent> new_shared_event()
+{
+    std::shared_ptr<tr_scene::SharedEvent> e = std::make_shared<tr_scene::SharedEvent>();
+    if (hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess) {
+        e->ev = nullptr;
+        return nullptr;
+    }
+    return e;
+}
+
+// A pose of the scene's targets under weights w[0 .. n_targets).
+std::shared_ptr<tr_scene::Pose> make_pose(tr_scene *s, const float *w)
+{
+    std::shared_ptr<tr_scene::Pose> p = std::make_shared<tr_scene::Pose>();
+    p->owner = s;
+    p->w.assign(w, w + s->n_targets);
+    return p;
+}
+
+// Free rows beyond this many are given back to the device (trim_pose_pool): a group's worth may wait for their readers
+// while the next group takes its own.
+constexpr size_t POSE_FREE_MAX = GROUP_MAX;
+
+bool pose_rows_idle(const tr_scene::PoseRows &r)
+{
+    for (const std::shared_ptr<tr_scene::SharedEvent> &e : r.used)
+        if (e && hipEventQuery(e->ev) != hipSuccess) return false;
+    return true;
+}
+
+// Gives free rows whose readers have run back to the device until at most `keep` free sets are left (or the rest are
+// still being read).
+void trim_pose_pool(tr_scene *s, size_t keep)
+{
+    for (size_t i = 0; i < s->pose_free.size() && s->pose_free.size() > keep;) {
+        if (!pose_rows_idle(s->pose_free[i])) {
+            i++;
+            continue;
+        }
+        dev_free(s->pose_free[i].d);
+        s->pose_free.erase(s->pose_free.begin() + (long)i);
+        s->pose_rows_live--;
+    }
+}
+
+// Device memory for the pose's rows: rows nobody holds whose readers have run, else new ones.  A pose's holders are its
+// frame's slot, the kept frames, held-back frames and the current state -- tr_scene_render_frames_morphed makes its poses
+// group by group -- so the sets alive are bounded by the frame slots plus the groups in flight, not by the frames of a call.
+int pose_rows(tr_scene *s, tr_scene::Pose &p)
+{
+    if (p.rows.d) return TR_OK;
+    size_t pick = s->pose_free.size();
+    for (size_t i = 0; i < s->pose_free.size() && pick == s->pose_free.size(); i++)
+        if (pose_rows_idle(s->pose_free[i])) pick = i;
+    if (pick == s->pose_free.size() && s->pose_free.size() >= POSE_FREE_MAX) {
+        pick = 0;  // enough of them wait for their readers: the host waits for the oldest instead of allocating more
+        for (const std::shared_ptr<tr_scene::SharedEvent> &e : s->pose_free[0].used)
+            if (e) HIP_TRY(hipEventSynchronize(e->ev));
+    }
+    if (pick < s->pose_free.size()) {
+        p.rows.d = s->pose_free[pick].d;
+        s->pose_free.erase(s->pose_free.begin() + (long)pick);
+        if (s->pose_free.size() > POSE_FREE_MAX) trim_pose_pool(s, POSE_FREE_MAX);
+        return TR_OK;
+    }
+    int st = dev_alloc(&p.rows.d, (size_t)s->n_rows * TRI_FLOATS);
+    if (st == TR_OK) s->pose_rows_live++;
+    return st;
+}
+
+// Chains that read the rows of `poses` (null entries: none) have been queued on `st`: one event behind them, shared by
+// the poses, guards the rows' reuse.
+int note_pose_use(tr_scene *s, const std::shared_ptr<tr_scene::Pose> *poses, uint32_t n, hipStream_t st)
+{
+    const int k = st == s->setup_stream ? 1 : st == s->setup_stream2 ? 2 : 0;
+    std::shared_ptr<tr_scene::SharedEvent> e;
+    for (uint32_t j = 0; j < n; j++) {
+        if (!poses[j]) continue;
+        if (!e) {
+            e = new_shared_event();
+            if (!e) return tr::fail(TR_E_HIP, "hipEventCreate failed");
+            HIP_TRY(hipEventRecord(e->ev, st));
+        }
+        poses[j]->rows.used[k] = e;
+    }
+    return TR_OK;
+}
+
+// Before a chain on `chain` reads the rows of `poses` (null entries and repeats allowed): the ones not blended yet get
+// their rows and are blended by ONE launch of k_morph on `chain`; the chain waits for those blended on another stream.
+int blend_poses(tr_scene *s, const std::shared_ptr<tr_scene::Pose> *poses, uint32_t n, hipStream_t chain)
+{
+    tr_scene::Pose *todo[GROUP_MAX];
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        tr_scene::Pose *p = poses[j].get();
+        if (!p) continue;
+        if (p->blended) {
+            if (p->done_on != chain && !p->done_seen) {
+                if (hipEventQuery(p->done->ev) == hipSuccess) p->done_seen = true;
+                else HIP_TRY(hipStreamWaitEvent(chain, p->done->ev, 0));
+            }
+            continue;
+        }
+        bool listed = false;  // (a pose that several frames draw is blended once)
+        for (uint32_t i = 0; i < m; i++) listed = listed || todo[i] == p;
+        if (listed) continue;
+        if (p->w.size() != (size_t)s->n_targets || !s->d_delta) return tr::fail(TR_E_INVALID, "pose of targets the scene no longer has");
+        if (m >= (uint32_t)GROUP_MAX) return tr::fail(TR_E_INVALID, "too many poses for one launch");
+        int st = pose_rows(s, *p);
+        if (st != TR_OK) return st;
+        todo[m++] = p;
+    }
+    if (m == 0) return TR_OK;
+    const uint32_t T = s->n_targets;
+    tr_scene::MorphStage &stage = s->morph_stage[s->morph_launches % 4u];
+    int st = TR_OK;
+    if (!stage.h)
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&stage.h), sizeof(float) * GROUP_MAX * TR_MORPH_MAX_TARGETS, hipHostMallocDefault));
+    if (!stage.d && (st = dev_alloc(&stage.d, (size_t)GROUP_MAX * TR_MORPH_MAX_TARGETS)) != TR_OK) return st;
+    if (stage.done) HIP_TRY(hipEventSynchronize(stage.done->ev));  // (four launches ago: long done)
+    MorphTable tab = {};
+    for (uint32_t j = 0; j < m; j++) {
+        memcpy(stage.h + (size_t)j * T, todo[j]->w.data(), sizeof(float) * T);
+        tab.f[j].w = stage.d + (size_t)j * T;
+        tab.f[j].dst = todo[j]->rows.d;
+    }
+    HIP_TRY(hipMemcpyAsync(stage.d, stage.h, sizeof(float) * (size_t)m * T, hipMemcpyHostToDevice, chain));
+    EventPair ep = { nullptr, nullptr, K_MORPH, m };
+    if (s->profiling) { ep.a = take_event(s); ep.b = take_event(s); }
+    int rc = launch_morph(s->d_tri, s->d_delta, s->n_rows, T, tab, m, chain, ep.a, ep.b);
+    if (rc) return launch_status(rc, "k_morph");
+    if (s->profiling) s->events.push_back(ep);
+    std::shared_ptr<tr_scene::SharedEvent> done = new_shared_event();
+    if (!done) return tr::fail(TR_E_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(done->ev, chain));
+    stage.done = done;
+    s->morph_launches++;
+    for (uint32_t j = 0; j < m; j++) {
+        todo[j]->blended = true;
+        todo[j]->done = done;
+        todo[j]->done_on = chain;
+    }
     return TR_OK;
 }
 
@@ -1190,6 +1387,12 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
     hipStream_t chain = chain_on_main ? s->stream : (s->two_setup_streams && (p_seq & 1u)) ? s->setup_stream2 : s->setup_stream;
     if (!chain_on_main && p_seq >= (uint64_t)LOOKAHEAD)
         HIP_TRY(hipStreamWaitEvent(chain, s->ev_tile[(p_seq - LOOKAHEAD) % RING], 0));
+    // the pose's rows first (once per pose: the passes of a frame read the same rows)
+    if (s->inst.pose) {
+        if ((st = blend_poses(s, &s->inst.pose, 1u, chain)) != TR_OK) return st;
+        sa.mesh.tri = s->mesh.tri = s->inst.pose->rows.d;
+    }
+    if (!sa.mesh.tri && sa.mesh.n_tri) return tr::fail(TR_E_INVALID, "no rows to draw");
     // the chain: vertex stage + counting, work lists + pool ranges, records into the ranges
     if (lit_pass) {  // (first in the chain: it needs nothing but the frame's constants)
         EventPair el = { nullptr, nullptr, K_LIT, 1u };
@@ -1224,6 +1427,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
         HIP_TRY(hipEventRecord(s->ev_setup[p_seq % RING], chain));
     }
     if ((st = note_inst_use(s, sa.mesh, chain)) != TR_OK) return st;
+    if ((st = note_pose_use(s, &s->inst.pose, 1u, chain)) != TR_OK) return st;
     pt.fs = depth_only ? p.fs : tile_fs(s, p.fs);
     pt.kernel_id = depth_pass ? K_TILE_DEPTH : K_TILE;
     pt.p_seq = p_seq;
@@ -1569,7 +1773,12 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
         slot.z_deferred = defer_depth(s);   // (what the slot's z is then: this frame)
         slot.z_params = p[j];
         slot.z_inst = insts ? insts[j] : s->inst;
+        if (slot.z_inst.pose && (st = pose_rows(s, *slot.z_inst.pose)) != TR_OK) break;
         const DevMesh mesh = mesh_of(s, slot.z_inst);
+        if (!mesh.tri && mesh.n_tri) {
+            st = tr::fail(TR_E_INVALID, "no rows to draw");
+            break;
+        }
         uint8_t *fb = fbs ? (uint8_t *)fbs[j] : nullptr;
         const bool callers = fb != nullptr;
         if (!fb) st = slot_own_fb(s, slot_of[j], &fb);
@@ -1631,6 +1840,10 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
 
     // tables to the device, then per pass: vertex stage + binning of all frames, their work lists
     hipStream_t chain = chain_on_main ? s->stream : s->setup_stream;
+    // the frames' poses: blended by one launch ahead of the chain that reads their rows (both passes of a frame do)
+    std::shared_ptr<tr_scene::Pose> poses[GROUP_MAX];
+    for (uint32_t j = 0; j < g; j++) poses[j] = s->slots[(size_t)slot_of[j]].z_inst.pose;
+    if ((st = blend_poses(s, poses, g, chain)) != TR_OK) return st;
     HIP_TRY(hipMemcpyAsync(gs.d_tables, gs.h_tables, (size_t)np * G * (sizeof(SetupArgs) + sizeof(TileArgs)),
                            hipMemcpyHostToDevice, chain));
     for (uint32_t pi = 0; pi < np; pi++) {
@@ -1672,6 +1885,7 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
     HIP_TRY(hipEventRecord(gs.ev_setup, chain));
     for (uint32_t j = 0; j < g; j++)
         if ((st = note_inst_use(s, h_setup[j].mesh, chain)) != TR_OK) return st;
+    if ((st = note_pose_use(s, poses, g, chain)) != TR_OK) return st;
     gs.chain_on_main = chain_on_main;
     gs.g = g;
     gs.n_poly = n_poly;
@@ -1864,8 +2078,11 @@ int flush_deferred(tr_scene *s, bool hold_back)
 }
 
 // n cleared frames, frame i into slot i % G, drawing instance table insts[i] (insts == null: the current one);
-// afterwards the last one is the scene's current frame.
-int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_scene::InstRef *insts, void *const *fbs)
+// afterwards the last one is the scene's current frame.  posed: frame i draws a pose of its own -- weights pose_w +
+// i * n_targets (pose_w null: no pose) -- made when its group is set up, so that only what holds a frame (its slot, the
+// kept frames, work in flight) holds a pose's rows: not the call.
+int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_scene::InstRef *insts, void *const *fbs,
+                  bool posed = false, const float *pose_w = nullptr)
 {
     int st = submit_pending(s);  // per-frame renders issued before go first
     if (st != TR_OK) return st;
@@ -1887,23 +2104,34 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_sc
         if ((st = ensure_group_set(s, s->grp[k], cp.set_frames)) != TR_OK) return st;
     s->host_status = TR_OK;
     const uint64_t first_seq = s->pass_seq;
+    const uint32_t kept = cp.kept;  // what is left of the call: its last min(n, G) frames
+    const bool per_frame = insts != nullptr || posed;
+    std::vector<tr_scene::InstRef> kept_refs;  // their tables and poses
+    auto ref_of = [&](uint32_t i) {
+        tr_scene::InstRef r = insts ? insts[i] : s->inst;
+        if (posed) r.pose = pose_w ? make_pose(s, pose_w + (size_t)i * s->n_targets) : nullptr;
+        if (i >= n - kept) kept_refs.push_back(r);
+        return r;
+    };
     if (s->d_winner) {
         // the winner tap is a single buffer: frame by frame through the ordinary path, slots all the same
         for (uint32_t i = 0; i < n; i++) {
             if ((st = use_slot(s, (int)(i % G), fbs ? (uint8_t *)fbs[i] : nullptr, fbs != nullptr)) != TR_OK) return st;
             memcpy(s->light, p[i].light, 12); memcpy(s->from, p[i].look_from, 12);
             memcpy(s->at, p[i].look_at, 12); memcpy(s->up, p[i].up, 12);
-            if (insts) use_inst(s, insts[i]);
+            if (per_frame) use_inst(s, ref_of(i));
             s->z_fb_cleared = s->shadow_cleared = true;
             if ((st = render_frame(s)) != TR_OK) return st;
         }
     } else {
         int slot_of[GROUP_MAX];
+        tr_scene::InstRef refs[GROUP_MAX];  // the group's tables and poses (a pose per frame: made here, group by group)
         uint32_t i0 = 0;
         for (size_t k = 0; k < sizes.size(); i0 += sizes[k], k++) {
             const uint32_t g = sizes[k];
             for (uint32_t j = 0; j < g; j++) slot_of[j] = (int)((i0 + j) % S);
-            st = run_group(s, p + i0, insts ? insts + i0 : nullptr, fbs ? fbs + i0 : nullptr, slot_of, g,
+            for (uint32_t j = 0; j < g && per_frame; j++) refs[j] = ref_of(i0 + j);
+            st = run_group(s, p + i0, per_frame ? refs : nullptr, fbs ? fbs + i0 : nullptr, slot_of, g,
                            fbs && !(s->flags & TR_OPT_TRUST_FRAME_BUFFERS));
             if (st == TR_OK) st = submit_groups(s, false);
             if (st != TR_OK) {
@@ -1924,23 +2152,22 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_sc
         // the scene now stands where the per-frame calls would have left it
         const tr_frame_params &l = p[n - 1];
         memcpy(s->light, l.light, 12); memcpy(s->from, l.look_from, 12); memcpy(s->at, l.look_at, 12); memcpy(s->up, l.up, 12);
-        if (insts) use_inst(s, insts[n - 1]);
+        if (per_frame) use_inst(s, kept_refs.back());
         s->z_fb_cleared = s->shadow_cleared = false;
         if ((st = use_slot(s, (int)((n - 1) % S), fbs ? (uint8_t *)fbs[n - 1] : nullptr)) != TR_OK) return st;
     }
-    // what is left of the call: its last min(n, G) frames
-    const uint32_t kept = cp.kept;
     s->tail.params.assign(p + (n - kept), p + n);
     s->tail.fbs.clear();
     if (fbs) s->tail.fbs.assign(fbs + (n - kept), fbs + n);
     s->tail.slot.resize(kept);
     s->tail.inst.assign(kept, s->inst);
-    if (insts) s->tail.inst.assign(insts + (n - kept), insts + n);
+    if (per_frame) s->tail.inst = kept_refs;
     for (uint32_t k = 0; k < kept; k++) s->tail.slot[k] = (int)((n - kept + k) % (s->d_winner ? G : S));
     s->tail.first_seq = first_seq + (uint64_t)(n - kept) * np;
     if (fbs && n > kept) s->unreplayable_seq = s->tail.first_seq;  // older frames' buffers: theirs for good
     s->last_was_group = true;
     s->last.valid = false;
+    if (s->pose_free.size() > POSE_FREE_MAX) trim_pose_pool(s, POSE_FREE_MAX);
     return TR_OK;
 }
 
@@ -2059,6 +2286,21 @@ void destroy(tr_scene *s)
     if (s->setup_stream2) (void)hipStreamSynchronize(s->setup_stream2);
     for (const std::shared_ptr<tr_scene::InstBlock> &b : s->inst_blocks) free_inst_block(*b);
     s->inst_blocks.clear();
+    // poses: every holder lets go, their rows come back to the pool, the pool goes
+    s->inst = tr_scene::InstRef();
+    s->last.inst = tr_scene::InstRef();
+    s->deferred.clear();
+    s->tail.inst.clear();
+    for (tr_scene::FrameSlot &fs : s->slots) fs.z_inst = tr_scene::InstRef();
+    for (tr_scene::PoseRows &r : s->pose_free) dev_free(r.d);
+    s->pose_free.clear();
+    s->pose_rows_live = 0;
+    dev_free(s->d_delta);
+    for (tr_scene::MorphStage &m : s->morph_stage) {
+        if (m.h) (void)hipHostFree(m.h);
+        dev_free(m.d);
+        m.done.reset();
+    }
     for (int k = 0; k < 4; k++) dev_free(s->d_texel[k]);
     dev_free(s->d_packed);
     for (int k = 0; k < LOOKAHEAD; k++) dev_free(s->d_lit[k]);
@@ -2202,6 +2444,9 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
         HIP_TRY(hipMemcpy(s->d_tri, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
     }
     s->n_rows = mesh->n_tri;
+    s->mesh_idx.assign(mesh->idx, mesh->idx + 9u * (size_t)mesh->n_tri);  // (for the gather of morph targets)
+    s->n_pos = mesh->n_pos;
+    s->n_nrm = mesh->n_nrm;
     s->poly_cap = mesh->n_tri;
     use_inst(s, tr_scene::InstRef());
 
@@ -2636,6 +2881,7 @@ static int set_table(tr_scene *s, uint32_t n, uint32_t stride, const float *tabl
     if ((st = grow_for_instances(s, n)) != TR_OK) return st;
     tr_scene::InstRef r;
     if (n && (st = upload_instances(s, n, stride, table, r)) != TR_OK) return st;
+    r.pose = s->inst.pose;  // (the table places the mesh under the current pose)
     use_inst(s, r);
     return TR_OK;
 }
@@ -2666,6 +2912,7 @@ static int render_frames_tables(tr_scene *s, uint32_t n_frames, const tr_frame_p
             insts[i].n = n;
         }
     }
+    for (uint32_t i = 0; i < n_frames; i++) insts[i].pose = s->inst.pose;  // every frame draws the current pose
     return render_frames(s, n_frames, frames, insts.data(), frame_buffers_device);
 }
 
@@ -2693,6 +2940,98 @@ int tr_scene_render_frames_transformed(tr_scene *s, uint32_t n_frames, const tr_
 {
     return render_frames_tables(s, n_frames, frames, n_instances, tr::INST_XFORM_FLOATS, reinterpret_cast<const float *>(table),
                                 frame_buffers_device);
+}
+
+int tr_scene_set_morph_targets(tr_scene *s, uint32_t n_targets, const float *dpos, const float *dnrm)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    if (n_targets > (uint32_t)TR_MORPH_MAX_TARGETS) return tr::fail(TR_E_INVALID, "more than TR_MORPH_MAX_TARGETS morph targets");
+    if (n_targets && ((s->n_pos && !dpos) || (s->n_nrm && !dnrm))) return tr::fail(TR_E_INVALID, "null delta array");
+    HIP_TRY(hipSetDevice(s->device));
+    // the deltas gathered per polygon like the mesh's rows (uv floats: zero, never read as deltas)
+    std::vector<float> rows((size_t)n_targets * s->n_rows * TRI_FLOATS, 0.0f);
+    const std::vector<float> no_tex(3, 0.0f);
+    for (uint32_t k = 0; k < n_targets; k++)
+        for (uint32_t t = 0; t < s->n_rows; t++) {
+            uint32_t ix[9];
+            memcpy(ix, &s->mesh_idx[9u * (size_t)t], sizeof ix);
+            ix[1] = ix[4] = ix[7] = 0u;
+            gather_polygon(dpos + (size_t)k * s->n_pos * 3u, no_tex.data(), dnrm + (size_t)k * s->n_nrm * 3u, ix,
+                           &rows[((size_t)k * s->n_rows + t) * TRI_FLOATS]);
+        }
+    float *d_new = nullptr;
+    int st = TR_OK;
+    if (n_targets && (st = dev_alloc(&d_new, rows.size())) != TR_OK) return st;
+    // frames issued so far keep their poses: they go to the device, and everything queued runs, before the deltas change
+    if ((st = submit_pending(s)) != TR_OK) {
+        dev_free(d_new);
+        return st;
+    }
+    hipError_t e = hipStreamSynchronize(s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
+    if (e == hipSuccess && n_targets) e = hipMemcpy(d_new, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
+    if (e != hipSuccess) {
+        dev_free(d_new);
+        HIP_TRY(e);
+    }
+    dev_free(s->d_delta);
+    s->d_delta = d_new;
+    s->n_targets = n_targets;
+    trim_pose_pool(s, 0);  // (everything queued has run: the free rows go back to the device)
+    // no pose of the old targets stays current (frames already rendered keep their rows)
+    tr_scene::InstRef r = s->inst;
+    r.pose.reset();
+    use_inst(s, r);
+    return TR_OK;
+}
+
+int tr_scene_set_morph_weights(tr_scene *s, uint32_t n_weights, const float *w)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
+    if (n_weights && !w) return tr::fail(TR_E_INVALID, "null weights");
+    tr_scene::InstRef r = s->inst;
+    r.pose = n_weights ? make_pose(s, w) : nullptr;
+    use_inst(s, r);
+    return TR_OK;
+}
+
+int tr_scene_render_frames_morphed(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_weights,
+                                   const float *weights, void *const *frame_buffers_device)
+{
+    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
+    if (n_weights && n_frames && !weights) return tr::fail(TR_E_INVALID, "null weights");
+    if (n_frames == 0) return TR_OK;
+    if (frame_buffers_device)
+        for (uint32_t i = 0; i < n_frames; i++)
+            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
+    HIP_TRY(hipSetDevice(s->device));
+    // the current table under a pose per frame
+    return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, true, n_weights ? weights : nullptr);
+}
+
+int tr_scene_debug_morph_rows(tr_scene *s)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    return (int)s->pose_rows_live;
+}
+
+// The rule of tr_morph.h over the indexed arrays, on the host.  Needs no GPU.
+int tr_morph_mesh(const tr_mesh *mesh, uint32_t n_targets, const float *dpos, const float *dnrm, const float *w, float *pos_out,
+                  float *nrm_out)
+{
+    if (!mesh || (n_targets && !w)) return tr::fail(TR_E_INVALID, "null argument");
+    if (n_targets > (uint32_t)TR_MORPH_MAX_TARGETS) return tr::fail(TR_E_INVALID, "more than TR_MORPH_MAX_TARGETS morph targets");
+    if ((mesh->n_pos && (!mesh->pos || !pos_out || (n_targets && !dpos))) || (mesh->n_nrm && (!mesh->nrm || !nrm_out || (n_targets && !dnrm))))
+        return tr::fail(TR_E_INVALID, "null array");
+    const size_t np = (size_t)mesh->n_pos * 3u, nn = (size_t)mesh->n_nrm * 3u;
+    for (size_t i = 0; i < np; i++) pos_out[i] = tr::morph_component(mesh->pos[i], n_targets, w, dpos + i, np);
+    for (size_t i = 0; i < nn; i++) nrm_out[i] = tr::morph_component(mesh->nrm[i], n_targets, w, dnrm + i, nn);
+    return TR_OK;
 }
 
 // The concatenated mesh a transform table draws, on the host: the vertex stage's own xform_position / xform_normal

@@ -55,6 +55,56 @@ def transform_mesh(mesh, table):
     return pos, nrm
 
 
+def _morph_deltas(mesh, dpos, dnrm):
+    """(dpos [T, n_pos, 3], dnrm [T, n_nrm, 3]) float32, contiguous, checked against the mesh's arrays."""
+    n_pos = np.asarray(mesh["pos"]).reshape(-1, 3).shape[0]
+    n_nrm = np.asarray(mesh["nrm"]).reshape(-1, 3).shape[0]
+    dp = np.ascontiguousarray(dpos, np.float32)
+    dn = np.ascontiguousarray(dnrm, np.float32)
+    if dp.ndim != 3 or dn.ndim != 3 or dp.shape[1:] != (n_pos, 3) or dn.shape[1:] != (n_nrm, 3) or dp.shape[0] != dn.shape[0]:
+        raise ValueError("morph targets must be dpos [T, %d, 3] and dnrm [T, %d, 3] float32" % (n_pos, n_nrm))
+    if dp.shape[0] > _lib.TR_MORPH_MAX_TARGETS:
+        raise ValueError("at most %d morph targets" % _lib.TR_MORPH_MAX_TARGETS)
+    return dp, dn
+
+
+def _morph_weights(w, n_targets, per_frame=False):
+    """[T] float32 -- or [n_frames, T] with per_frame -- as a contiguous array."""
+    a = np.ascontiguousarray(w, np.float32)
+    if a.ndim != (2 if per_frame else 1) or a.shape[-1] != n_targets:
+        raise ValueError("morph weights must be [%s%d] float32 (one weight per target)" % ("n_frames, " if per_frame else "", n_targets))
+    return a
+
+
+def morph_deltas(base, target):
+    """One morph target from a second mesh of identical topology: (dpos [1, n_pos, 3], dnrm [1, n_nrm, 3]) =
+    target - base in float32; stack several with np.concatenate for set_morph_targets."""
+    if not np.array_equal(np.asarray(base["idx"], np.uint32).reshape(-1, 9), np.asarray(target["idx"], np.uint32).reshape(-1, 9)):
+        raise ValueError("morph target has different indices: the meshes must share their topology")
+    out = []
+    for key in ("pos", "nrm"):
+        b = np.asarray(base[key], np.float32).reshape(-1, 3)
+        t = np.asarray(target[key], np.float32).reshape(-1, 3)
+        if b.shape != t.shape:
+            raise ValueError("morph target has %d %s entries, the mesh %d" % (t.shape[0], key, b.shape[0]))
+        out.append((t - b)[None])
+    return out[0], out[1]
+
+
+def morph_mesh(mesh, dpos, dnrm, weights):
+    """tr_morph_mesh: (pos [n_pos, 3], nrm [n_nrm, 3]) of `mesh` under the pose `weights` [T] of the targets dpos
+    [T, n_pos, 3], dnrm [T, n_nrm, 3], by the inline function k_morph calls, on the host (no GPU needed)."""
+    dp, dn = _morph_deltas(mesh, dpos, dnrm)
+    w = _morph_weights(weights, dp.shape[0])
+    keep = []
+    m = _mesh_struct(mesh, keep)
+    pos = np.empty((m.n_pos, 3), np.float32)
+    nrm = np.empty((m.n_nrm, 3), np.float32)
+    check(load_library().tr_morph_mesh(C.byref(m), dp.shape[0], dp.ctypes.data, dn.ctypes.data, w.ctypes.data,
+                                       pos.ctypes.data, nrm.ctypes.data))
+    return pos, nrm
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -109,6 +159,8 @@ class Scene:
                                 shader_pipeline_name.encode(), C.byref(o), C.byref(h)))
         self._h = h
         self.pipeline = shader_pipeline_name
+        self._mesh_shape = {"pos": np.empty((m.n_pos, 3), np.float32), "nrm": np.empty((m.n_nrm, 3), np.float32)}
+        self.n_morph_targets = 0
         if instances is not None:
             self.set_instances(instances)
         if instance_transforms is not None:
@@ -166,7 +218,34 @@ class Scene:
         a = _transform_table(table)
         check(L.tr_scene_set_instance_transforms(self._h, a.shape[0], a.ctypes.data))
 
-    def render_frames(self, frames, frame_buffers_device=None, instances=None, instance_transforms=None):
+    def set_morph_targets(self, dpos, dnrm=None):
+        """tr_scene_set_morph_targets: T morph targets as deltas dpos [T, n_pos, 3] and dnrm [T, n_nrm, 3] float32
+        (morph_deltas builds one from a second mesh); None or no targets: drops them.  Leaves the scene without a pose."""
+        L = load_library()
+        if dpos is None or len(dpos) == 0:
+            check(L.tr_scene_set_morph_targets(self._h, 0, None, None))
+            self.n_morph_targets = 0
+            return
+        if dnrm is None:
+            raise ValueError("morph targets need dnrm beside dpos")
+        dp, dn = _morph_deltas(self._mesh_shape, dpos, dnrm)
+        check(L.tr_scene_set_morph_targets(self._h, dp.shape[0], dp.ctypes.data, dn.ctypes.data))
+        self.n_morph_targets = dp.shape[0]
+
+    def set_morph_weights(self, weights):
+        """tr_scene_set_morph_weights: the pose drawn from now on, [T] float32; None or empty: the mesh itself."""
+        L = load_library()
+        if weights is None or len(weights) == 0:
+            check(L.tr_scene_set_morph_weights(self._h, 0, None))
+            return
+        w = _morph_weights(weights, self.n_morph_targets)
+        check(L.tr_scene_set_morph_weights(self._h, w.shape[0], w.ctypes.data))
+
+    def debug_morph_rows(self):
+        """tr_scene_debug_morph_rows: sets of posed rows the scene has on the device now (held and free)."""
+        return check(load_library().tr_scene_debug_morph_rows(self._h))
+
+    def render_frames(self, frames, frame_buffers_device=None, instances=None, instance_transforms=None, morph_weights=None):
         """tr_scene_render_frames: `frames` is an [n, 12] float32 array (or a list of (light, look_from,
         look_at, up) tuples): per frame light direction, look_from, look_at, up.  Frame i is what
         clear(); set_light_direction; set_camera; render() produces; the frames of a group are rendered by
@@ -174,9 +253,14 @@ class Scene:
         instances: optional [n, n_instances, 4] float32 -- frame i draws table instances[i] (what set_instances
         before its render would do; tr_scene_render_frames_instanced); None: the current table in every frame.
         instance_transforms: the same with transform tables, [n, n_instances, 24] float32
-        (tr_scene_render_frames_transformed); at most one of the two."""
+        (tr_scene_render_frames_transformed); at most one of the two.
+        morph_weights: [n, T] float32 -- frame i draws the pose morph_weights[i] (what set_morph_weights before its
+        render would do; tr_scene_render_frames_morphed) under the scene's current table; not together with a table per
+        frame."""
         if instances is not None and instance_transforms is not None:
             raise ValueError("one table per frame: instances= or instance_transforms=, not both")
+        if morph_weights is not None and (instances is not None or instance_transforms is not None):
+            raise ValueError("morph_weights= draws the scene's current table: no table per frame beside it")
         if not isinstance(frames, np.ndarray):
             frames = np.asarray([np.concatenate([np.asarray(v, np.float32).reshape(3) for v in f]) for f in frames],
                                 np.float32)
@@ -186,6 +270,13 @@ class Scene:
             if len(frame_buffers_device) != len(frames):
                 raise ValueError("one frame buffer per frame")
             fbs = (C.c_void_p * len(frames))(*[int(q) for q in frame_buffers_device])
+        if morph_weights is not None:
+            w = _morph_weights(morph_weights, self.n_morph_targets, per_frame=True)
+            if w.shape[0] != len(frames):
+                raise ValueError("one pose per frame")
+            check(load_library().tr_scene_render_frames_morphed(self._h, len(frames), frames.ctypes.data, w.shape[1],
+                                                                w.ctypes.data if w.size else None, fbs))
+            return
         if instance_transforms is not None:
             xf = _transform_table(instance_transforms, per_frame=True)
             if xf.shape[0] != len(frames):
