@@ -281,6 +281,11 @@ int tr_morph_mesh(const tr_mesh *mesh, uint32_t n_targets, const float *dpos, co
 int tr_scene_frames_per_launch(tr_scene *s); /* frames per group of this scene */
 int tr_scene_frames_kept(tr_scene *s);       /* frames of the last tr_scene_render_frames call that still exist
                                                 (0 after a tr_scene_render) */
+/* 1 when the scene's newest fused tile launches (the passes of its last group of frames, or a lone cleared frame's
+ * colour pass) ran the tile kernels compiled for frames made of whole tiles only -- width a multiple of 128, the band
+ * whole tile rows inside the frame -- else 0 (also before the first such launch).  Speed only: the frames are the
+ * same either way.  TR_INTERIOR=0 in the environment (read once per process) keeps every launch on the general kernels. */
+int tr_scene_interior_tiles(tr_scene *s);
 /* Makes the frame `back` frames before the last one of that call (0 = the last) the scene's current frame: getters,
  * tr_scene_frame_buffer_device and later renders refer to its targets, light and camera. */
 int tr_scene_select_frame(tr_scene *s, uint32_t back);

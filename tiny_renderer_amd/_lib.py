@@ -116,6 +116,7 @@ SYMBOLS = {
     "tr_morph_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frames_per_launch": (C.c_int, [C.c_void_p]),
     "tr_scene_frames_kept": (C.c_int, [C.c_void_p]),
+    "tr_scene_interior_tiles": (C.c_int, [C.c_void_p]),
     "tr_scene_select_frame": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tr_scene_get_frame_buffer": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_buffer_async": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -43,6 +43,10 @@ int launch_bin(const SetupArgs &a, const SetupArgs *group, uint32_t n_frames, bo
 int launch_tile(int fs_kind, const TileArgs &a, int tile_waves, int shared, uint32_t n_polygons, const TileArgs *group,
                 uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t done, uint32_t units_per_frame = 0,
                 bool fused_single = false);
+// Does that launch run the interior form of its kernel -- compiled for frames made of whole tiles only (k_tile, INTERIOR:
+// no per-pixel frame or band tests)?  The same arguments as launch_tile's; `fused`: a fused launch (group != null) or a
+// fused_single one.  (TR_INTERIOR=0 in the environment: never.)
+bool tile_launch_is_interior(int fs_kind, const TileArgs &a, int tile_waves, int shared, uint32_t n_polygons, bool fused);
 int launch_materialize_depth(float *zbuf, uint32_t *zclean, const DevFrame &frame, hipStream_t st);
 // The band's tiles of frame buffer `fb` into the page-locked host buffer `host` (device address of it), skipping the
 // tiles that are zeros on both sides (fb_clean: the target's colour-clean flags; host_clean: the host buffer's own)

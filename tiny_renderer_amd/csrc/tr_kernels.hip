@@ -25,6 +25,7 @@
 // No MFMA anywhere: the path is compare/gather/stream work bound by HBM writes.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <stdlib.h>
 
 #include <type_traits>
 
@@ -777,10 +778,16 @@ __device__ __forceinline__ uint32_t depth_order_bits(float z)
 // repeat of a colour pass is such a launch).  MODE 1 / 2: a fused launch; 2 = transient depth, decided at COMPILE time --
 // a run-time flag skipped the stores but kept the arithmetic behind them (the survivors' z, the depth addresses), and
 // with it the gain (same box: 28.5 -> 28.3 us per frame against 27.4 for the compiled-out form).
-template <int FS, int TILE_WAVES, bool SHARED, int MODE>
+// INTERIOR: every frame of the launch is made of whole tiles only (tile_frame_is_interior below: the width a multiple
+// of TILE_W, the band whole tile rows inside the frame), decided by the launcher for the whole launch.  Every pixel of
+// every tile is then inside frame and band, so the per-pixel "is this pixel mine" tests of the shading steps (col_live,
+// row_live, live, cdw_live), the byte-store arm of frames whose width is no multiple of 4 and the scalar registers
+// pinned for the band's rows are not compiled at all.  Only the four-wave column kernels of fused launches have the form.
+template <int FS, int TILE_WAVES, bool SHARED, int MODE, bool INTERIOR = false>
 TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ table, uint32_t n_frames)
 {
     constexpr bool GROUP = MODE != 0;
+    static_assert(!INTERIOR || (GROUP && !SHARED && TILE_WAVES == 4), "the interior form exists for the fused four-wave column kernels");
     static_assert(TILE_WAVES == 4 || TILE_WAVES == 8 || TILE_WAVES == 16, "a wave covers a 32, 16 or 8 pixel wide column of the tile");
     constexpr int TILE_THREADS = 64 * TILE_WAVES;
     constexpr int QUAD_COLUMN = TILE_W / TILE_WAVES;  // width of a wave's column when columns are owned
@@ -914,11 +921,19 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     const int32_t tile_x0 = tx * TILE_W, tile_y0 = ty * TILE_H;
     int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
     // what every shading step reads of the frame's arguments: into scalar registers once (TR_KEEP_SCALAR)
-    int32_t band_y0 = a.frame.band_y0, band_y1 = a.frame.band_y1;
-    uint32_t aligned4 = a.aligned4;
+    // (an interior frame: the band's rows and aligned4 are never read -- no load, no register)
+    int32_t band_y0 = 0, band_y1 = 0;
+    uint32_t aligned4 = 1u;
     uint8_t *fb = a.fb;
     DevTextures tex = a.tex;
-    TR_KEEP_SCALAR(W); TR_KEEP_SCALAR(H); TR_KEEP_SCALAR(band_y0); TR_KEEP_SCALAR(band_y1); TR_KEEP_SCALAR(aligned4); TR_KEEP_SCALAR(fb);
+    TR_KEEP_SCALAR(W); TR_KEEP_SCALAR(H);
+    if constexpr (!INTERIOR) {
+        band_y0 = a.frame.band_y0;
+        band_y1 = a.frame.band_y1;
+        aligned4 = a.aligned4;
+        TR_KEEP_SCALAR(band_y0); TR_KEEP_SCALAR(band_y1); TR_KEEP_SCALAR(aligned4);
+    }
+    TR_KEEP_SCALAR(fb);
     TR_KEEP_SCALAR(tex.packed); TR_KEEP_SCALAR(tex.packed_bpr); TR_KEEP_SCALAR(tex.w[0]); TR_KEEP_SCALAR(tex.h[0]);
     // the wave index is uniform: say so, so that quadrant bounds and the block loop stay scalar
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), lane = tid & 63u;
@@ -955,6 +970,13 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
         constexpr int QPIX = QUAD * TILE_H;
         const int32_t qx0 = SH ? tile_x0 : tile_x0 + (int32_t)wave * QUAD;
         uint2 *wkey = SH ? s_key : s_key + wave * QPIX;
+        // What the resolve reads of W, H and the band: only the guards of the initial keys' depth loads below, which
+        // exist for an accumulating render (!zfresh) -- a fused launch, and with it every INTERIOR kernel, starts from
+        // cleared targets (zfresh is a constant there) and compiles none of them.  Visits, coverage iterations and
+        // scan-line items never compare against W, H or the band in any kernel: a polygon's box is clamped to the frame
+        // by the vertex stage and to the wave's region here (bx0..bx1, by0..by1, pair_box), so coverage stays inside
+        // the tile, and the keys are LDS.
+        static_assert(!INTERIOR || GROUP, "an interior kernel reads no previous depth");
         // this lane's key in block column 0 (block row 0; block row 1 follows SH ? 8 rows : NBX blocks later)
         const uint32_t key_lane = SH ? shared_key_slot((uint32_t)lx, (uint32_t)ly) : lane;
         // ---- initial keys -------------------------------------------------------------------
@@ -1295,7 +1317,8 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     uint32_t *const winner_strip = (!GROUP && a.winner) ? a.winner + ((int64_t)sy0 * W + sx0) : nullptr;
     uint8_t *const fb_strip = DEPTH ? nullptr : fb + ((int64_t)(H - sy0 - STRIP_ROWS) * W + sx0) * 3;
     const uint32_t Wu = (uint32_t)W, W3 = 3u * (uint32_t)W;
-    const bool col_live = px < W;
+    // (INTERIOR: px < tile_x0 + TILE_W <= ntx * TILE_W = W)
+    const bool col_live = INTERIOR || px < W;
     // What a step's keys and stores need of the lane is the same in every step; only the step's first row r0 (even,
     // uniform) moves them, and it moves them by scalars:
     //   key slot   key_slot(x, strip_y + r0 + hrow) = (key_slot(x, hrow) ^ ((r0' & 7) << 3)) + ((r0' >> 3) * NBX << 6),
@@ -1312,7 +1335,8 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
     const uint32_t cj = (uint32_t)hx, cp0 = (4u * cj) / 3u, co = (4u * cj) % 3u;
     const int32_t perm0 = (int32_t)((half_base + (cp0 & 31u)) << 2), perm1 = (int32_t)((half_base + ((cp0 + 1u) & 31u)) << 2);
     const uint32_t csh0 = 8u * co, csh1 = 24u - 8u * co;
-    const bool cdw_live = cj < 24u && (sx0 * 3 + (int32_t)(4u * cj)) < W * 3;
+    // (INTERIOR: the strip's 96 bytes end at 3 (sx0 + STRIP) <= 3 W: a lane constant)
+    const bool cdw_live = cj < 24u && (INTERIOR || (sx0 * 3 + (int32_t)(4u * cj)) < W * 3);
 
     // Reads a pixel's key and returns the bin slot + 1 of its survivor (0: none): pixel (hx, r0 + hrow) of the strip
     // (zbits: the f32 bits of the depth the resolve compared for that pixel -- what a depth pass stores, below)
@@ -1508,7 +1532,7 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
         if (put && st_z) gstore(depth_strip + (int64_t)r0 * W + zlane, zv);
         if (!DEPTH && st_c) {
             if (winner_strip && put && with_winner) gstore(winner_strip + (int64_t)r0 * W + zlane, triv);
-            if (aligned4) {
+            if (INTERIOR || aligned4) {   // (INTERIOR: W is a multiple of TILE_W = 128 -- no byte-store arm)
                 const uint32_t c0 = (uint32_t)__builtin_amdgcn_ds_bpermute(perm0, (int)rgbv);
                 const uint32_t c1 = (uint32_t)__builtin_amdgcn_ds_bpermute(perm1, (int)rgbv);
                 const uint32_t dw = (c0 >> csh0) | (c1 << csh1);
@@ -1542,7 +1566,8 @@ TR_TILE_KERNEL_ATTRS void k_tile(TileArgs args, const TileArgs *__restrict__ tab
         for (int u = 0; u < 2; u++) {
             const uint32_t r0 = (uint32_t)(sstep * 4 + u * 2);  // the pixel's row in the strip: r0 + hrow
             py[u] = sy0 + (int32_t)r0 + hrow;
-            row_live[u] = py[u] >= band_y0 && py[u] < band_y1;
+            // (INTERIOR: tile rows ty_base .. ty_base + nty - 1 are rows band_y0 .. band_y1 - 1 exactly, and band_y1 <= H)
+            row_live[u] = INTERIOR || (py[u] >= band_y0 && py[u] < band_y1);
             live[u] = col_live && row_live[u];
             const uint32_t s1 = survivor_slot(r0, zkey[u]);
             won[u] = live[u] && s1 != 0u;
@@ -2120,6 +2145,34 @@ int launch_order(const TileArgs &one, uint32_t n_tiles, const TileArgs *group, u
     return 0;
 }
 
+// (TR_INTERIOR=0: frames of whole tiles run the general kernels like any other, as before round 6)
+static bool interior_kernels()
+{
+    static const bool on = !getenv("TR_INTERIOR") || atoi(getenv("TR_INTERIOR")) != 0;
+    return on;
+}
+
+// Is the frame made of whole tiles only -- every pixel of every tile of its grid inside the frame and the band?
+// (Every frame of a fused launch has the frame and band of its scene: `a`, what the frames have in common, says it.)
+static bool tile_frame_is_interior(const DevFrame &f)
+{
+    return f.width % (uint32_t)TILE_W == 0u && f.ntx * (uint32_t)TILE_W == f.width &&
+           (int64_t)f.band_y0 == (int64_t)f.ty_base * TILE_H && (int64_t)f.band_y1 == ((int64_t)f.ty_base + (int64_t)f.nty) * TILE_H &&
+           f.band_y1 >= 0 && (uint32_t)f.band_y1 <= f.height;
+}
+
+// The kernels that exist in the interior form (k_tile, INTERIOR): the fused four-wave column kernels of the light closures
+template <int F, int WAVES, bool SHARED>
+constexpr bool TILE_HAS_INTERIOR = WAVES == 4 && !SHARED &&
+                                   (F == FS_DEFAULT || F == FS_PHONG || F == FS_LIT || F == FS_DEPTH || F == FS_SHADOW2);
+
+bool tile_launch_is_interior(int fs, const TileArgs &a, int tile_waves, int shared, uint32_t n_polygons, bool fused)
+{
+    if (n_polygons > SHARED_MAX_POLYGONS) shared = 0;  // (launch_tile)
+    const bool has = fs == FS_DEFAULT || fs == FS_PHONG || fs == FS_LIT || fs == FS_DEPTH || fs == FS_SHADOW2;
+    return fused && has && tile_waves == 4 && !shared && interior_kernels() && tile_frame_is_interior(a.frame);
+}
+
 template <int WAVES, bool SHARED>
 static int launch_tile_waves(int fs, const TileArgs &a, uint32_t n_tiles, const TileArgs *group, uint32_t n_frames,
                              hipStream_t st, hipEvent_t start, hipEvent_t done, bool fused_single)
@@ -2134,8 +2187,19 @@ static int launch_tile_waves(int fs, const TileArgs &a, uint32_t n_tiles, const 
     const dim3 grid(n_tiles * (fused ? n_frames : 1u)), block(64 * WAVES);
     // (a fused launch whose frames leave their depth on the chip: `a` -- what the group's frames have in common -- says so)
     const bool transient = fused && fs != FS_DEPTH && a.store == TR_STORE_COLOR;
+    // (a frame of whole tiles: the same kernels without their per-pixel frame and band tests)
+    const bool interior = tile_launch_is_interior(fs, a, WAVES, SHARED ? 1 : 0, 0u, fused);
 #define TR_TILE_CASE(F)                                                                                                  \
     case F:                                                                                                              \
+        if constexpr (TILE_HAS_INTERIOR<F, WAVES, SHARED>) {                                                             \
+            if (interior) {                                                                                              \
+                if (transient)                                                                                           \
+                    hipExtLaunchKernelGGL((k_tile<F, WAVES, SHARED, (F == FS_DEPTH ? 1 : 2), true>), grid, block, 0, st, start, done, 0, a, group, n_frames); \
+                else                                                                                                     \
+                    hipExtLaunchKernelGGL((k_tile<F, WAVES, SHARED, 1, true>), grid, block, 0, st, start, done, 0, a, group, n_frames); \
+                break;                                                                                                   \
+            }                                                                                                            \
+        }                                                                                                                \
         if (transient)                                                                                                   \
             hipExtLaunchKernelGGL((k_tile<F, WAVES, SHARED, (F == FS_DEPTH ? 1 : 2)>), grid, block, 0, st, start, done, 0, a, group, n_frames); \
         else if (fused)                                                                                                  \

@@ -272,6 +272,9 @@ struct tr_scene {
     };
     std::vector<PendingTile> pending;  // passes whose setup is queued and whose tile kernel is not yet
     uint64_t tiles_submitted = 0;      // tile kernels handed to the main stream so far
+    // did the newest fused tile launches (every pass of a group, or a fused_single pass) run the interior form of their
+    // kernels (tile_launch_is_interior, tr_kernels.h)?  -1: no fused launch yet (tr_scene_interior_tiles)
+    int fused_interior = -1;
     uint64_t last_submitted_seq = 0;   // pass number of the newest of them (its ev_tile tells whether the stream is idle)
     uint32_t tile_waves = 0;     // tr_options.tile_waves: 4, 8, 16 or 0 = by tile count
     uint32_t tile_mode = 0;      // tr_options.tile_mode: 1 columns, 2 shared bin, 0 = automatic
@@ -896,6 +899,7 @@ int launch_pending_tile(tr_scene *s, const tr_scene::PendingTile &t)
         if (hipEventRecord(s->ev_tile[t.p_seq % RING], s->stream) != hipSuccess && status == TR_OK)
             status = tr::fail(TR_E_HIP, "hipEventRecord");
     }
+    if (t.fused_single) s->fused_interior = tile_launch_is_interior(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, true) ? 1 : 0;
     s->tiles_submitted += 1;
     s->last_submitted_seq = t.p_seq;
     return status;
@@ -1908,6 +1912,7 @@ int submit_group_tiles(tr_scene *s, bool wait_for_setup)
     const TileArgs *d_tile = reinterpret_cast<const TileArgs *>(gs.d_tables + (size_t)np * G * sizeof(SetupArgs));
     s->group_submitted++;
     if (wait_for_setup) HIP_TRY(hipStreamWaitEvent(s->stream, gs.ev_setup, 0));
+    bool interior = true;  // (every pass of the group)
     // (has the chain completed?  "no wait needed" alone does not say so: a chain on the main stream itself needs none either)
     const bool chain_done = !wait_for_setup && !gs.chain_on_main && hipEventQuery(gs.ev_setup) == hipSuccess;
     for (uint32_t pi = 0; pi < np; pi++) {
@@ -1932,7 +1937,9 @@ int submit_group_tiles(tr_scene *s, bool wait_for_setup)
             return launch_status(rc, "k_tile");
         }
         if (s->profiling) s->events.push_back(ep);
+        interior = interior && tile_launch_is_interior(tile_fs(s, pass.fs), ta0, tile_waves, shared, gs.n_poly, true);
     }
+    s->fused_interior = interior ? 1 : 0;
     if (s->profiling) HIP_TRY(hipEventRecord(gs.ev_tile, s->stream));
     s->groups_unfenced = true;
     if (!s->own_stream) s->observed_seq = s->pass_seq;  // a caller's stream: handed on (see recover_from_overflow)
@@ -3061,6 +3068,12 @@ int tr_instance_transform_mesh(const tr_mesh *mesh, uint32_t n_instances, const 
         }
     }
     return TR_OK;
+}
+
+int tr_scene_interior_tiles(tr_scene *s)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    return s->fused_interior > 0 ? 1 : 0;
 }
 
 int tr_scene_frames_per_launch(tr_scene *s) { return s ? (int)group_size(s) : tr::fail(TR_E_INVALID, "null scene"); }

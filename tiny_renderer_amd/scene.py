@@ -297,6 +297,10 @@ class Scene:
     def frames_per_launch(self):
         return check(load_library().tr_scene_frames_per_launch(self._h))
 
+    def interior_tiles(self):
+        """Did the newest fused tile launches run the kernels compiled for frames made of whole tiles only?"""
+        return bool(check(load_library().tr_scene_interior_tiles(self._h)))
+
     def frames_kept(self):
         return check(load_library().tr_scene_frames_kept(self._h))
 
