@@ -139,6 +139,41 @@ def light(angle):
     return [float(np.sin(a)), 0.0, float(np.cos(a))]
 
 
+TILE_W, TILE_H = 128, 16            # csrc/tr_types.h
+LIT_PIXELS_PER_TEXEL = 16           # a scene takes the lit-texel path by itself from sixteen pixels per texel
+INTERIOR_PIPES = ("default", "phong", "shadow")   # every pass has the interior form
+LIT_PIPES = ("normal_map", "specular")            # ... only as FS_LIT, on the lit-texel path
+
+
+def lit_path(W, Hh, texs, pipe):
+    """Does a scene of `pipe` run the normal-map / specular closure once per texel (k_lit; the tile kernels then run
+    FS_LIT)?  TR_LIT in the environment decides when it is set; else the frame has at least sixteen pixels per texel of
+    the first image.  (The four images of every input here have one size, which the path needs.)"""
+    if pipe not in LIT_PIPES:
+        return False
+    force = os.environ.get("TR_LIT")
+    if force is not None:
+        return int(force) != 0
+    return W * Hh >= LIT_PIXELS_PER_TEXEL * texs[0].shape[0] * texs[0].shape[1]
+
+
+def expect_interior(W, Hh, pipe, waves, mode, band=None, lit=False):
+    """Must a fused launch of this scene have run the INTERIOR form of the tile kernels?  The documented rule
+    (tr_scene_interior_tiles, include/tiny_renderer.h), restated -- not the launcher's code: the form exists
+    for the four-wave column kernels (`waves`, `mode`: what the scene pins or is known to choose; anything else, 0
+    included, says no) of the closures FS_DEFAULT, FS_PHONG, FS_LIT, FS_DEPTH and FS_SHADOW2, and runs when the width is
+    a multiple of 128 and the band (output rows [row0, row1), row 0 = top; None: the whole frame) consists of whole
+    16-row tile rows inside the frame -- tile rows count from the BOTTOM row of the frame.  The query says yes only when
+    EVERY pass of the pipeline ran the form: occlusion's depth pass has it, its colour pass does not.
+    lit: the scene is on the lit-texel path (lit_path above)."""
+    if waves != 4 or mode != 1 or W % TILE_W:
+        return False
+    r0, r1 = (0, Hh) if band is None else band
+    if not (0 <= r0 < r1 <= Hh) or (Hh - r0) % TILE_H or (Hh - r1) % TILE_H:
+        return False
+    return pipe in INTERIOR_PIPES or (pipe in LIT_PIPES and bool(lit))
+
+
 def save_png(path, rgb):
     from PIL import Image
     Image.fromarray(rgb).save(path)

@@ -129,6 +129,8 @@ def test_group_tile_layouts(small_synthetic, pipe, waves, mode):
     p = params(n)
     gpu = T.Scene(W, Hh, mesh, texs, pipe, tile_waves=waves, tile_mode=mode, frames_per_launch=4)
     gpu.render_frames(p)
+    # which form of the tile kernels ran: 400 wide is no frame of whole tiles -- the general one in every layout
+    assert gpu.interior_tiles() == H.expect_interior(W, Hh, pipe, waves, mode)
     check_kept(gpu, oracle_frames(W, Hh, mesh, texs, pipe, p), pipe, n)
     gpu.close()
 

@@ -71,10 +71,16 @@ def _grab(gpu, pipe):
 
 def _tile_launches(prof):
     return {k: (prof.get(k, {"launches": 0, "frames": 0})["launches"], prof.get(k, {"launches": 0, "frames": 0})["frames"])
-            for k in ("k_tile", "k_tile_depth", "k_bin")}
+            for k in ("k_tile", "k_tile_depth", "k_bin", "k_lit")}
 
 
-def fused_pair(W, Hh, mesh, texs, pipe, views, path="group2", expect=None, oracle_mesh=None, **opts):
+def _assert_form(gpu, interior, what):
+    if interior is not None:
+        assert gpu.interior_tiles() == interior, \
+            "%s: the %s form of the tile kernels ran" % (what, "INTERIOR" if gpu.interior_tiles() else "general")
+
+
+def fused_pair(W, Hh, mesh, texs, pipe, views, path="group2", expect=None, oracle_mesh=None, interior=None, lit=None, **opts):
     """Renders `views` ([n, 12]: light and camera per frame) through a scene WITHOUT a winner tap by one of FUSED_PATHS and
     returns (kept, want): the frames the GPU kept (newest first for the group paths; every frame in turn for single2)
     beside the oracle's frames for the same views.  Asserts from the profile that the colour pass ran as ONE k_tile launch
@@ -82,7 +88,11 @@ def fused_pair(W, Hh, mesh, texs, pipe, views, path="group2", expect=None, oracl
     depth pass of a two-pass pipeline likewise, and that reading the z buffer repeats the pass exactly when the depth was
     transient (MODE 2) -- which a MODE 0 or MODE 1 launch in its place would not do.
     expect: oracle frames computed before (oracle_views(...) of the same views); oracle_mesh: what the oracle renders when
-    the scene draws something else than `mesh` itself (an instance table)."""
+    the scene draws something else than `mesh` itself (an instance table).
+    interior: which FORM of the kernels must have run (Scene.interior_tiles(): every pass of the newest fused launches in
+    the form compiled for frames of whole tiles) -- H.expect_interior(...) where the caller pins the layout, a literal with
+    its reason where the scene chooses; asked after the launches (single2: after every render) and before any getter.
+    lit: must k_lit have run (once per group or render) or not at all; None: not looked at."""
     import tiny_renderer_amd as T
     assert path in FUSED_PATHS
     views = np.ascontiguousarray(views, np.float32).reshape(-1, 12)
@@ -106,6 +116,8 @@ def fused_pair(W, Hh, mesh, texs, pipe, views, path="group2", expect=None, oracl
             assert ran["k_tile"] == (1, 1), ran
             assert ran["k_tile_depth"] == ((1, 1) if n_pass == 2 else (0, 0)), ran
             assert ran["k_bin"] == (n_pass, n_pass), ran
+            assert lit is None or ran["k_lit"] == ((1, 1) if lit else (0, 0)), ran
+            _assert_form(gpu, interior, "%s, %dx%d, render %d" % (pipe, W, Hh, i))
             kept.append(_grab(gpu, pipe))
             again = _tile_launches(gpu.profile_read())
             assert again["k_tile"][0] == 2, "the depth was not transient: not the MODE 2 kernel (%r)" % (again,)
@@ -123,6 +135,8 @@ def fused_pair(W, Hh, mesh, texs, pipe, views, path="group2", expect=None, oracl
         assert ran["k_tile"] == (groups, n), ran
         assert ran["k_tile_depth"] == ((groups, n) if n_pass == 2 else (0, 0)), ran
         assert ran["k_bin"] == (groups * n_pass, n * n_pass), ran
+        assert lit is None or ran["k_lit"] == ((groups, n) if lit else (0, 0)), ran
+        _assert_form(gpu, interior, "%s, %dx%d, path %s" % (pipe, W, Hh, path))
         n_kept = gpu.frames_kept()
         assert n_kept == min(n, g)
         for back in range(n_kept):
@@ -169,11 +183,25 @@ def five_frames(a, b):
 
 # ---- 1. full-size real models through the fused paths ---------------------------------------------------------------
 
-def _full_size(mesh, texs, pipe, size, path, a, b):
+def _full_size(mesh, texs, pipe, size, path, a, b, interior, expect=None, **opts):
+    """size: the side of a square frame, or (width, height).  interior: the form that must have run (fused_pair)."""
     # (frames_per_launch=4 is what a 4096^2 scene chooses by itself; pinned so that every size gets groups of 4 + 1)
-    kept, want = fused_pair(size, size, mesh, texs, pipe, five_frames(a, b), path=path, frames_per_launch=4)
+    W, Hh = size if isinstance(size, tuple) else (size, size)
+    kept, want = fused_pair(W, Hh, mesh, texs, pipe, five_frames(a, b), path=path, expect=expect, interior=interior,
+                            frames_per_launch=4, **opts)
     assert len(kept) == (2 if path == "single2" else 4)
     assert_fused_parity(kept, want, pipe)
+
+
+# Which form the scenes that choose their own layout must run (tile_layout, csrc/tr_scene.cpp: 16 waves up to 1024 tiles in
+# a launch, 8 up to 4608, else 4; the waves share a tile's bin -- no interior form -- up to 2048 tiles per frame or from three
+# polygons per tile).  diablo has 5022 polygons.
+#   4096^2        32 x 256 = 8192 tiles per frame (32768 in a launch of four), 0.6 polygons per tile: 4 waves, columns --
+#                 phong and shadow (depth pass: the same grid) have the form in every pass, darboux's closure has none
+#   8192^2 x64    64 x 512 = 32768 tiles, 321 408 polygons = 9.8 per tile: dense, the shared resolve
+#   2048^2        16 x 128 = 2048 tiles per frame: the shared resolve
+#   800^2         7 x 50 = 350 tiles per frame, 1400 in a launch of four: 16 or 8 waves (and partial tiles)
+AUTO_INTERIOR = {("phong", 4096): True, ("shadow", 4096): True, ("darboux", 4096): False, ("specular", 8192): False}
 
 
 @pytest.mark.gpu
@@ -188,7 +216,7 @@ def test_baseline_configs_at_full_size_fused(diablo, cfg, path):
     mesh, texs = diablo
     if grid > 1:
         mesh = T.instanced_grid(mesh, grid)
-    _full_size(mesh, texs, pipe, size, path, view(0.0, 0.0), view(0.11, 0.23))
+    _full_size(mesh, texs, pipe, size, path, view(0.0, 0.0), view(0.11, 0.23), interior=AUTO_INTERIOR[(pipe, size)])
 
 
 @pytest.mark.gpu
@@ -196,7 +224,7 @@ def test_baseline_configs_at_full_size_fused(diablo, cfg, path):
 def test_african_head_default_800_fused(african_head, path):
     """BASELINE.json configs[0]."""
     mesh, texs = african_head
-    _full_size(mesh, texs, "default", 800, path, view(0.0, 0.0), view(0.37, -0.5))
+    _full_size(mesh, texs, "default", 800, path, view(0.0, 0.0), view(0.37, -0.5), interior=False)  # (8 or 16 waves)
 
 
 @pytest.mark.gpu
@@ -204,7 +232,7 @@ def test_african_head_default_800_fused(african_head, path):
 def test_diablo_phong_2048_fused(diablo, path):
     """BASELINE.json configs[1]."""
     mesh, texs = diablo
-    _full_size(mesh, texs, "phong", 2048, path, view(0.0, 0.0), view(0.37, -0.5))
+    _full_size(mesh, texs, "phong", 2048, path, view(0.0, 0.0), view(0.37, -0.5), interior=False)  # (shared resolve)
 
 
 @pytest.mark.gpu
@@ -213,7 +241,66 @@ def test_diablo_phong_2048_fused(diablo, path):
 def test_diablo_800_fused(diablo, pipe, path):
     """test_diablo_800's two views -- angles (0, 0) and (0.7, -1.1) -- as the two views of the five frames."""
     mesh, texs = diablo
-    _full_size(mesh, texs, pipe, 800, path, view(0.0, 0.0), view(0.7, -1.1))
+    _full_size(mesh, texs, pipe, 800, path, view(0.0, 0.0), view(0.7, -1.1), interior=False)  # (8 or 16 waves)
+
+
+# ---- 2. a real model through BOTH forms of the four-wave column kernels -------------------------------------------------
+#
+# No real model reaches the general four-wave column kernels by itself (800^2: 8 or 16 waves; 2048^2: the shared resolve;
+# 4096^2: the interior form), and the interior form's closures beside phong and shadow meet a real model nowhere else.  The
+# layout is pinned here and the size decides the form: 768 = 6 x 128 = 48 x 16 is whole tiles, 800 is not.
+
+FOUR_COLUMNS = dict(tile_waves=4, tile_mode=1)
+LIT_PIPES = H.LIT_PIPES
+
+
+def _both_forms_cases():
+    """(size, pipeline, TR_LIT, path): every pipeline through group2 and single2, phong and shadow through group1 as well,
+    the two texel closures once more on the lit path -- the cases of one (size, pipeline) side by side, sharing an oracle."""
+    out = []
+    for size in (768, 800):
+        for pipe in ALL:
+            paths = FUSED_PATHS if pipe in ("phong", "shadow") else ("group2", "single2")
+            out += [(size, pipe, None, path) for path in paths]
+            if pipe in LIT_PIPES:
+                out.append((size, pipe, "1", "group2"))
+    return out
+
+
+_both_forms_oracle = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,pipe,force_lit,path", _both_forms_cases())
+def test_diablo_both_forms_of_the_column_kernels(diablo, monkeypatch, size, pipe, force_lit, path):
+    """test_diablo_800_fused's two views in the four-wave column layout at 768^2 (6 x 48 whole tiles) and 800^2: at 768^2
+    default, phong, shadow and the lit path's FS_LIT run the interior form, darboux and the closures per fragment have
+    none, and occlusion is the mixed case -- an interior depth pass before a general colour pass, for which the query must
+    say no; at 800^2 everything runs the general kernels.  H.expect_interior says which, fused_pair asserts it."""
+    mesh, texs = diablo
+    if force_lit is not None:
+        monkeypatch.setenv("TR_LIT", force_lit)
+    lit = H.lit_path(size, size, texs, pipe)
+    assert lit == (force_lit == "1"), "1024^2 images: these frames take the lit path only when told to"
+    a, b = view(0.0, 0.0), view(0.7, -1.1)
+    if (size, pipe) not in _both_forms_oracle:   # (one entry: the cases of a size and pipeline follow each other)
+        _both_forms_oracle.clear()
+        _both_forms_oracle[(size, pipe)] = oracle_views(size, size, mesh, texs, pipe, five_frames(a, b))
+    interior = H.expect_interior(size, size, pipe, 4, 1, lit=lit)
+    assert interior == (size == 768 and (pipe in ("default", "phong", "shadow") or lit))
+    _full_size(mesh, texs, pipe, size, path, a, b, interior, expect=_both_forms_oracle[(size, pipe)],
+               lit=lit if pipe in LIT_PIPES else None, **FOUR_COLUMNS)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["group2", "group1"])
+@pytest.mark.parametrize("pipe", ["phong", "shadow"])
+def test_headline_layout_in_the_general_form_at_full_size(diablo, pipe, path):
+    """4096 x 4088: the 32 x 256 tiles and the layout a 4096^2 scene chooses by itself (AUTO_INTERIOR above: 4 waves,
+    columns), but the top tile row is half a tile high -- the general MODE 2 and MODE 1 kernels, the depth pass included,
+    at the size of the headline workload."""
+    mesh, texs = diablo
+    _full_size(mesh, texs, pipe, (4096, 4088), path, view(0.0, 0.0), view(0.11, 0.23), interior=False)
 
 
 # ---- 3. a bin-length ladder: every n across every threshold, in one frame ------------------------------------------
@@ -237,6 +324,11 @@ def test_diablo_800_fused(diablo, pipe, path):
 # Other thresholds on n: shared_tile = n >= 2 * WAVES (8, 16, 32) && n <= SHARED_MAX_SLOTS (4093); the staging chunks
 # (multiples of NMAX); k_order's work-list buckets; the empty list's chunks of 32 tiles.
 LADDER_W = 128
+# The ladder's other widths -- every polygon ends at column 123, so the designed bins hold at each: 125 has a partial tile
+# column (the lanes of columns 125 ... 127 are dead) and, no multiple of 4, takes the byte-store arm; 124 takes the dword
+# arm with a partial last strip.  Neither is a frame of whole tiles: what 128 runs in the interior form they run in the
+# general one.
+LADDER_WIDTHS = (LADDER_W, 125, 124)
 DENSE = list(range(1, 449))
 COUNTS = DENSE + [1000, 4092, 4093, 4094] + [0] * 8 + [50]
 LADDER_SEED = 7
@@ -249,8 +341,8 @@ LADDER_POOL = 2 * sum(COUNTS)
 LADDER_LIGHTS = ((0.0, 0.0, 1.0), (0.012, 0.0, 1.1), (-0.012, 0.0, 1.1))
 
 
-def ladder_mesh(counts, seed):
-    """A frame LADDER_W = 128 pixels wide and 16 * len(counts) high is one column of 128x16 tiles; tile k (counted from the
+def ladder_mesh(counts, seed, width=LADDER_W):
+    """A frame `width` <= 128 pixels wide and 16 * len(counts) high is one column of 128x16 tiles; tile k (counted from the
     bottom row of the raster, the order of the tile kernel's tile index) receives exactly counts[k] polygons, each wholly
     inside the tile's rectangle (>= 4 pixels from its left and right edge, >= 1 from the lower and upper one), front
     facing, with integer raster vertices that are not collinear (so each covers its own vertices' pixels at least).
@@ -259,9 +351,10 @@ def ladder_mesh(counts, seed):
     polygons (tilted ones only where they still face the camera in object space), so that overlapping fragments tie
     exactly and polygon order decides.  The polygons are shuffled: a tile's polygon indices are neither contiguous nor
     ordered by size.
-    Object-space vertices come from the wanted raster positions through the inverse (float64) of the oracle's vpmv for
-    camera angle 0.  Returns (mesh, textures); mesh["tile_of"][t] is the tile polygon t was made for."""
+    Object-space vertices come from the wanted raster positions -- the same at every width -- through the inverse
+    (float64) of the oracle's vpmv for camera angle 0 in a frame of that width.  Returns (mesh, textures); mesh["tile_of"][t] is the tile polygon t was made for."""
     from oracle import oracle as O
+    assert 124 <= width <= 128, "every polygon must lie inside the frame's one tile column"
     rng = np.random.default_rng(seed)
     counts = np.asarray(counts, np.int64)
     Hh = 16 * len(counts)
@@ -287,7 +380,7 @@ def ladder_mesh(counts, seed):
     tilt = rng.random(n) < 1.0 / 3.0
     # raster position (px + 0.5, py + 0.5) truncates to (px, py) whatever the last bits of the float32 transform do
     cam = H.camera(0.0)
-    err, u = O.prepare(0, LADDER_W, Hh, H.light(0.0), *cam)
+    err, u = O.prepare(0, width, Hh, H.light(0.0), *cam)
     assert err == 0
     M = np.array(u.vpmv, np.float64).reshape(4, 4).T                # column major
     xs, ys = px + 0.5, py + 0.5
@@ -322,37 +415,42 @@ def ladder_mesh(counts, seed):
     return {"pos": pos, "tex": tex, "nrm": nrm, "idx": idx, "tile_of": tile_of[order]}, texs
 
 
-def ladder_views(n=3):
-    """Camera at angle 0 (the bins keep their designed lengths), n slightly different lights.  The lights that leave the
+def ladder_views(n=3, width=LADDER_W):
+    """The ladder's views at one of LADDER_WIDTHS -- the same at each: test_ladder_design_holds checks them width by width.
+    Camera at angle 0 (the bins keep their designed lengths), n slightly different lights.  The lights that leave the
     camera's axis are also farther away than the camera: the light's view of the ladder is then a little smaller than the
     camera's and every lookup of the shadow pipeline stays inside the shadow buffer (on the axis at distance 1 the polygons
     of the first and the last tile sit one pixel from its edge; the oracle reports any lookup out of range)."""
+    assert width in LADDER_WIDTHS, "a width the design test does not cover"
     out = np.stack([view(0.0, 0.0)] * n)
     out[:, 0:3] = LADDER_LIGHTS[:n]
     return out
 
 
 _ladder = {}
+# pipeline -> the widths a parity test renders it at (test_ladder_parity, ..._general_form, ..._default_and_lit)
+LADDER_ORACLE_WIDTHS = {"phong": LADDER_WIDTHS, "shadow": LADDER_WIDTHS, "darboux": (LADDER_W,),
+                        "default": (LADDER_W, 125), "normal_map": (LADDER_W, 125)}
 
 
-def ladder():
-    if "mesh" not in _ladder:
-        _ladder["mesh"] = ladder_mesh(COUNTS, LADDER_SEED)
-    return _ladder["mesh"]
+def ladder(width=LADDER_W):
+    if ("mesh", width) not in _ladder:
+        _ladder[("mesh", width)] = ladder_mesh(COUNTS, LADDER_SEED, width)
+    return _ladder[("mesh", width)]
 
 
-def ladder_oracle(pipe):
-    """The oracle's three ladder frames of a pipeline, rendered once per session."""
-    if pipe not in _ladder:
-        mesh, texs = ladder()
-        _ladder[pipe] = oracle_views(LADDER_W, 16 * len(COUNTS), mesh, texs, pipe, ladder_views())
-    return _ladder[pipe]
+def ladder_oracle(pipe, width=LADDER_W):
+    """The oracle's three ladder frames of a pipeline at a width, rendered once per session."""
+    if (pipe, width) not in _ladder:
+        mesh, texs = ladder(width)
+        _ladder[(pipe, width)] = oracle_views(width, 16 * len(COUNTS), mesh, texs, pipe, ladder_views(3, width))
+    return _ladder[(pipe, width)]
 
 
-def check_ladder_design(counts, seed):
-    mesh, texs = ladder() if (list(counts) == COUNTS and seed == LADDER_SEED) else ladder_mesh(counts, seed)
+def check_ladder_design(counts, seed, width=LADDER_W):
+    mesh, texs = ladder(width) if (list(counts) == COUNTS and seed == LADDER_SEED) else ladder_mesh(counts, seed, width)
     Hh = 16 * len(counts)
-    o = oracle_views(LADDER_W, Hh, mesh, texs, "phong", ladder_views(1))[0]
+    o = oracle_views(width, Hh, mesh, texs, "phong", ladder_views(1, width))[0]
     assert o["err"] == 0
     assert o["tri_kept"] == sum(counts) == mesh["idx"].shape[0], "a polygon was culled"
     win = o["winner"]
@@ -380,33 +478,39 @@ def test_ladder_counts_cover_the_thresholds():
 
 def test_ladder_design_holds(built):
     """CPU: the ladder is the input it claims to be -- nothing culled or degenerate, every polygon inside its own tile's
-    rows, every busy tile lit.  (A condition on the generator, not on the code under test.)"""
-    check_ladder_design(COUNTS, LADDER_SEED)
-    # the three lights of the parity test: no lookup outside the shadow buffer, the same polygons kept
-    for pipe in ("phong", "darboux", "shadow"):
-        for o in ladder_oracle(pipe):
-            assert o["err"] == 0 and o["tri_kept"] == sum(COUNTS) and o["rgb"].any()
+    rows, every busy tile lit -- at every width the parity tests render it.  (A condition on the generator, not on the
+    code under test.)"""
+    for width in LADDER_WIDTHS:
+        check_ladder_design(COUNTS, LADDER_SEED, width)
+    # the three lights of the parity tests: no lookup outside the shadow buffer or (default, normal_map) the 32 x 32 images,
+    # the same polygons kept
+    for pipe, widths in LADDER_ORACLE_WIDTHS.items():
+        for width in widths:
+            for o in ladder_oracle(pipe, width):
+                assert o["err"] == 0 and o["tri_kept"] == sum(COUNTS) and o["rgb"].any(), (pipe, width)
 
 
 @pytest.mark.gpu
 def test_ladder_bins_hold_the_designed_counts(built):
     """GPU, input check: the polygons the tile kernel finds in each tile's bin (column 2 of the tile stamps; MODE 0) are
-    COUNTS tile for tile -- n is known exactly, in every tile."""
+    COUNTS tile for tile -- n is known exactly, in every tile, at the whole-tile width and at one with a partial tile."""
     import tiny_renderer_amd as T
-    mesh, texs = ladder()
-    q = ladder_views(1)[0]
-    gpu = T.Scene(LADDER_W, 16 * len(COUNTS), mesh, texs, "phong", tile_stamps=True, bin_capacity=LADDER_POOL)
-    gpu.clear()
-    gpu.set_light_direction(q[0:3])
-    gpu.set_camera(q[3:6], q[6:9], q[9:12])
-    gpu.render()
-    assert gpu.sync() == 0
-    stamps = gpu.debug_tile_stamps()
-    assert stamps.shape[0] == len(COUNTS)
-    got = stamps[:, 2].astype(np.int64)
-    bad = np.nonzero(got != np.asarray(COUNTS))[0]
-    assert bad.size == 0, "tiles %s hold %s polygons, designed %s" % (bad[:8], got[bad[:8]], np.asarray(COUNTS)[bad[:8]])
-    gpu.close()
+    for width in (LADDER_W, 125):
+        mesh, texs = ladder(width)
+        q = ladder_views(1, width)[0]
+        gpu = T.Scene(width, 16 * len(COUNTS), mesh, texs, "phong", tile_stamps=True, bin_capacity=LADDER_POOL)
+        gpu.clear()
+        gpu.set_light_direction(q[0:3])
+        gpu.set_camera(q[3:6], q[6:9], q[9:12])
+        gpu.render()
+        assert gpu.sync() == 0
+        stamps = gpu.debug_tile_stamps()
+        assert stamps.shape[0] == len(COUNTS)
+        got = stamps[:, 2].astype(np.int64)
+        bad = np.nonzero(got != np.asarray(COUNTS))[0]
+        assert bad.size == 0, \
+            "width %d: tiles %s hold %s polygons, designed %s" % (width, bad[:8], got[bad[:8]], np.asarray(COUNTS)[bad[:8]])
+        gpu.close()
 
 
 def _ladder_note(flipped):
@@ -444,9 +548,51 @@ def test_ladder_parity(built, path, waves, mode, pipe):
         gpu.close()
         return
     kept, want = fused_pair(W, Hh, mesh, texs, pipe, views, path=path, expect=expect, tile_waves=waves, tile_mode=mode,
-                            frames_per_launch=3, bin_capacity=LADDER_POOL)
+                            interior=H.expect_interior(W, Hh, pipe, waves, mode), frames_per_launch=3, bin_capacity=LADDER_POOL)
     assert len(kept) == 3
     assert_fused_parity(kept, want, pipe, _ladder_note(False), _ladder_note(True))
+
+
+def _ladder_case(width, pipe, path, interior, lit=None):
+    """One ladder case in the four-wave column layout at a width: the form and (lit given) k_lit asserted, z, shadow and
+    rgb bits against the oracle's."""
+    mesh, texs = ladder(width)
+    kept, want = fused_pair(width, 16 * len(COUNTS), mesh, texs, pipe, ladder_views(3, width), path=path,
+                            expect=ladder_oracle(pipe, width), interior=interior, lit=lit, frames_per_launch=3,
+                            bin_capacity=LADDER_POOL, **FOUR_COLUMNS)
+    assert len(kept) == 3
+    assert_fused_parity(kept, want, pipe, _ladder_note(False), _ladder_note(True))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipe", ["phong", "shadow"])
+@pytest.mark.parametrize("width", [125, 124])
+@pytest.mark.parametrize("path", FUSED_PATHS)
+def test_ladder_parity_general_form(built, path, width, pipe):
+    """The ladder through the GENERAL four-wave column kernels of MODE 1 and MODE 2 -- FS_PHONG, FS_DEPTH, FS_SHADOW2: what
+    a 1080p or a 4100 wide frame gets in that layout -- at widths with real partial tiles (LADDER_WIDTHS).  At 128 the
+    same cases of test_ladder_parity run the interior form, so these are the only ones in which the general kernels meet a
+    bin beyond their resident budget (NMAX 41 or 68 in the table above), the staging chunks' multiples and the empty
+    chunks.  A failure names the tile and its n."""
+    assert not H.expect_interior(width, 16 * len(COUNTS), pipe, 4, 1)
+    _ladder_case(width, pipe, path, interior=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width,pipe,force_lit,path",
+                         [(w, p, f, path) for w in (LADDER_W, 125) for p, f in (("default", None), ("normal_map", "1"))
+                          for path in FUSED_PATHS] + [(LADDER_W, "normal_map", "0", "group2")])
+def test_ladder_parity_default_and_lit(built, monkeypatch, width, pipe, force_lit, path):
+    """The ladder through the two closures whose interior form met short bins only: FS_DEFAULT, and FS_LIT -- normal_map
+    on the lit-texel path (TR_LIT=1 as in test_lit_texel_path_on_small_frames; the profile must show k_lit) -- in the
+    interior form at 128 and the general one at 125.  One more case takes normal_map OFF the lit path at 128: FS_NORMAL_MAP
+    has no interior form, and the query must say so."""
+    if force_lit is not None:
+        monkeypatch.setenv("TR_LIT", force_lit)
+    lit = (force_lit == "1") if pipe == "normal_map" else None
+    interior = H.expect_interior(width, 16 * len(COUNTS), pipe, 4, 1, lit=bool(lit))
+    assert interior == (width == LADDER_W and force_lit != "0")
+    _ladder_case(width, pipe, path, interior, lit)
 
 
 # ---- 4. the remaining MODE-0-only stress inputs get fused twins ------------------------------------------------------
@@ -462,8 +608,12 @@ def test_far_vertices_and_slivers_fused(built, seed, path):
     expect = oracle_views(W, Hh, mesh, texs, pipe, views)
     assert all(o["err"] == 0 for o in expect), "the reference would panic on this soup"
     assert (expect[0]["winner"] != NO_WINNER).sum() > 1000
-    kept, want = fused_pair(W, Hh, mesh, texs, pipe, views, path=path, expect=expect, tile_waves=waves,
-                            tile_mode=1 + seed % 2, frames_per_launch=3)
+    mode = 1 + seed % 2
+    # (seed 0 -- 8192 x 48, phong, 4 waves, columns -- runs the interior form; 4096 x 130 and 1000^2 have partial tiles)
+    interior = H.expect_interior(W, Hh, pipe, waves, mode, lit=H.lit_path(W, Hh, texs, pipe))
+    assert interior == (seed == 0)
+    kept, want = fused_pair(W, Hh, mesh, texs, pipe, views, path=path, expect=expect, interior=interior, tile_waves=waves,
+                            tile_mode=mode, frames_per_launch=3)
     assert_fused_parity(kept, want, pipe)
 
 

@@ -149,9 +149,12 @@ def test_resolve_matches_serial_order_gpu_frame_groups(built, seed, mode):
     for k, (ca, la) in enumerate(views):
         p[k, 0:3] = H.light(la)
         p[k, 3:6], p[k, 6:9], p[k, 9:12] = H.camera(ca)
-    g = T.Scene(W, Hh, mesh, texs, pipe, tile_mode=mode, tile_waves=[0, 4, 8, 16][seed % 4], frames_per_launch=3)
+    waves = [0, 4, 8, 16][seed % 4]
+    g = T.Scene(W, Hh, mesh, texs, pipe, tile_mode=mode, tile_waves=waves, frames_per_launch=3)
     g.render_frames(p)
     assert g.frames_kept() == 3
+    # which form of the tile kernels ran (no size here is whole tiles under four waves: the general one, everywhere)
+    assert g.interior_tiles() == H.expect_interior(W, Hh, pipe, waves, mode, lit=H.lit_path(W, Hh, texs, pipe))
     exact = pipe != "specular" or bool(T.load_library().tr_specular_exact())
     for back in range(3):
         s = expect[len(views) - 1 - back]
