@@ -110,7 +110,9 @@ typedef struct tr_options {
                                   Speed only: results do not depend on it. */
     uint32_t tile_mode;        /* how a tile's wavefronts divide its work: 1 = each owns a column of the tile and
                                   sees every polygon of the bin, 2 = each owns a share of the bin and sees the
-                                  whole tile (depth resolve through LDS atomics), 0 = automatic.
+                                  whole tile (depth resolve through LDS atomics), 0 = automatic.  The shared mode
+                                  (2, pinned or chosen) is honoured up to 2^20 polygons per pass, counted as mesh
+                                  polygons x instances; beyond that the pass runs the column kernels (1).
                                   Speed only: results do not depend on it. */
     uint32_t frames_per_launch; /* tr_scene_render_frames: frames rendered by one launch of each kernel (1..32), 0 =
                                   automatic (by tile count: 4 at 4096x4096, 32 for small frames; a call of several

@@ -157,7 +157,10 @@ def lit_path(W, Hh, texs, pipe):
     return W * Hh >= LIT_PIXELS_PER_TEXEL * texs[0].shape[0] * texs[0].shape[1]
 
 
-def expect_interior(W, Hh, pipe, waves, mode, band=None, lit=False):
+SHARED_MAX_POLYGONS = 1 << 20      # the shared mode is honoured up to this many polygons per pass (mesh polygons x instances)
+
+
+def expect_interior(W, Hh, pipe, waves, mode, band=None, lit=False, n_poly=None):
     """Must a fused launch of this scene have run the INTERIOR form of the tile kernels?  The documented rule
     (tr_scene_interior_tiles, include/tiny_renderer.h), restated -- not the launcher's code: the form exists
     for the four-wave column kernels (`waves`, `mode`: what the scene pins or is known to choose; anything else, 0
@@ -165,7 +168,11 @@ def expect_interior(W, Hh, pipe, waves, mode, band=None, lit=False):
     a multiple of 128 and the band (output rows [row0, row1), row 0 = top; None: the whole frame) consists of whole
     16-row tile rows inside the frame -- tile rows count from the BOTTOM row of the frame.  The query says yes only when
     EVERY pass of the pipeline ran the form: occlusion's depth pass has it, its colour pass does not.
-    lit: the scene is on the lit-texel path (lit_path above)."""
+    lit: the scene is on the lit-texel path (lit_path above).
+    n_poly: the polygons of a pass (mesh polygons x instances; None: few) -- beyond 2^20 of them a pinned or chosen shared
+    mode (2) runs the column kernels, so it counts as mode 1 here."""
+    if n_poly is not None and n_poly > SHARED_MAX_POLYGONS and mode == 2:
+        mode = 1
     if waves != 4 or mode != 1 or W % TILE_W:
         return False
     r0, r1 = (0, Hh) if band is None else band
