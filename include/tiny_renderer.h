@@ -280,6 +280,57 @@ int tr_scene_debug_morph_rows(tr_scene *s);
  * computed by the very inline function k_morph calls.  mesh->tex and mesh->idx are not read. */
 int tr_morph_mesh(const tr_mesh *mesh, uint32_t n_targets, const float *dpos, const float *dnrm, const float *w,
                   float *pos_out /* n_pos*3 */, float *nrm_out /* n_nrm*3 */);
+/* Skinning (articulated deformation; nothing of the kind upstream): bones move the mesh per frame.  A skin gives every
+ * POSITION INDEX P of the mesh TR_SKIN_INFLUENCES = 4 pairs (bone index, weight); a palette is n_bones entries of
+ * tr_instance_xform -- m for positions, n for normals, pad ignored -- with 1 <= n_bones <= TR_SKIN_MAX_BONES (an
+ * interface limit, not a measured one).  Corner i of a polygon, with position p at position index P and normal a at its own
+ * normal index, is drawn as
+ *     acc = none
+ *     for j = 0 .. 3, in this order, skipping every j with weight[P][j] == 0.0f (either sign):
+ *         q   = palette[bone[P][j]].m applied to p      -- the rule of tr_instance_xform above, unchanged
+ *         t_r = fl( weight[P][j] * q_r )                -- r = 0..2
+ *         acc_r = (acc is none) ? t_r : fl( acc_r + t_r )
+ *     p' = (acc is none) ? p : acc
+ * and the normal by the same steps with palette[..].n applied to a -- under the influences of P: OBJ indexes normals
+ * separately, so a normal has none of its own.  No fused multiply-add; weights are used as given (the library does not
+ * normalise them); normals are not renormalised (the reference normalises every transformed normal).  Hence a corner
+ * whose four weights are zero keeps the mesh's own bit patterns, -0.0 included, whatever the palette holds (inf, nan),
+ * and a corner with one influence of weight 1.0f gets exactly what an instance-transform table of that one entry draws.
+ * Texture coordinates and the polygon order are the mesh's own.  Object-space normal maps do not deform -- the caveat
+ * of tr_instance_xform and of morph targets: `normal_map` and `specular` follow the deformation in geometry, depth and
+ * culling but take their light from normal_map.tga.
+ * Order of composition: the morph pose, if any, deforms the mesh; the palette skins the morphed rows; the scene's
+ * current instance table, of either kind, then places the result.
+ * tr_scene_set_skin copies bone and weight (n_pos * 4 each), gathers them per polygon as the mesh was and uploads them
+ * once; it waits for the scene's queued work and leaves the scene without a palette (the morph pose stays);
+ * n_bones == 0 (the arrays may then be NULL) drops the skin.  tr_scene_set_morph_targets leaves the palette current:
+ * the skin does not depend on the targets.
+ * tr_scene_set_bone_palette: scene state like the morph weights -- copied; renders issued after the call draw it,
+ * frames issued before (also held-back ones) keep theirs.  n_bones must be 0 or the skin's count; 0 means no palette:
+ * no skin kernel runs and the rows are the morph pose's or the mesh's own.
+ * Errors (a bone index >= n_bones, n_bones above the limit or not the skin's, a NULL where data is required) are
+ * TR_E_INVALID and change nothing. */
+#define TR_SKIN_INFLUENCES 4
+#define TR_SKIN_MAX_BONES 128
+int tr_scene_set_skin(tr_scene *s, uint32_t n_bones, const uint32_t *bone /* n_pos*4 */, const float *weight /* n_pos*4 */);
+int tr_scene_set_bone_palette(tr_scene *s, uint32_t n_bones, const tr_instance_xform *palette);
+/* tr_scene_render_frames with a palette per frame: frame i is exactly
+ *     tr_scene_set_bone_palette(s, n_bones, palettes + i * n_bones); tr_scene_clear; set_light_direction; set_camera;
+ *     tr_scene_render
+ * (one fused launch per kernel for the frames of a group; their rows are skinned by one launch of k_skin ahead of it,
+ * behind k_morph where there is a morph pose).  The last frame's palette is left current; tr_scene_select_frame
+ * restores a kept frame's.  The current morph pose and the current instance table apply to every frame.  Plain
+ * tr_scene_render_frames, _instanced, _transformed and _morphed draw the current palette in every frame. */
+int tr_scene_render_frames_skinned(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_bones,
+                                   const tr_instance_xform *palettes /* n_frames * n_bones */, void *const *frame_buffers_device);
+/* The rule above on the host (no GPU needed), by the very inline function k_skin calls.  A normal shared by corners
+ * with different positions gets different results, so the skinned mesh cannot reuse the mesh's index arrays: the
+ * output is unrolled -- corner 3t+i of polygon t gets a position and a normal of its own, idx_out holds per corner
+ * {3t+i, the mesh's texture index, 3t+i}; the polygon order is kept and mesh->tex is used as it is.  A scene under a
+ * palette renders, bit for bit and in every pipeline, what a scene created from this mesh renders. */
+int tr_skin_mesh(const tr_mesh *mesh, uint32_t n_bones, const uint32_t *bone, const float *weight,
+                 const tr_instance_xform *palette, float *pos_out /* n_tri*9 */, float *nrm_out /* n_tri*9 */,
+                 uint32_t *idx_out /* n_tri*9 */);
 int tr_scene_frames_per_launch(tr_scene *s); /* frames per group of this scene */
 int tr_scene_frames_kept(tr_scene *s);       /* frames of the last tr_scene_render_frames call that still exist
                                                 (0 after a tr_scene_render) */

@@ -79,6 +79,8 @@ class BandTiles(C.Structure):
 
 
 TR_MORPH_MAX_TARGETS = 64  # include/tiny_renderer.h
+TR_SKIN_INFLUENCES = 4
+TR_SKIN_MAX_BONES = 128
 
 
 class KernelTime(C.Structure):
@@ -114,6 +116,10 @@ SYMBOLS = {
     "tr_scene_render_frames_morphed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_debug_morph_rows": (C.c_int, [C.c_void_p]),
     "tr_morph_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_skin": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_bone_palette": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_render_frames_skinned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_skin_mesh": (C.c_int, [C.POINTER(Mesh), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frames_per_launch": (C.c_int, [C.c_void_p]),
     "tr_scene_frames_kept": (C.c_int, [C.c_void_p]),
     "tr_scene_interior_tiles": (C.c_int, [C.c_void_p]),

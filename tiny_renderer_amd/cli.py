@@ -48,7 +48,12 @@ def main(argv=None):
                     help="a second OBJ of the model's topology: one morph target (its positions and normals minus the "
                          "model's), drawn at --morph-weight; with --frames N the weight runs a triangle wave between 0 and it")
     ap.add_argument("--morph-weight", type=float, default=1.0, metavar="W", help="weight of the --morph-to target (default 1)")
+    ap.add_argument("--bend", type=float, default=None, metavar="DEG",
+                    help="skinning with a procedural two-bone rig: weights follow a smooth step in model height, the upper "
+                         "bone is turned about z by DEG degrees; with --frames N the angle ramps from 0 to DEG over the call")
     args = ap.parse_args(argv)
+    if args.bend is not None and (args.gpus > 1 or args.seconds > 0 or args.morph_to):
+        ap.error("--bend skins the scene of one GPU, by frame count, without --morph-to: use --gpus 1 and --frames")
     if args.morph_to and (args.gpus > 1 or args.seconds > 0):
         ap.error("--morph-to poses the scene of one GPU, by frame count: use --gpus 1 and --frames")
     if args.ssaa > 1 and (args.gpus > 1 or args.view != "frame"):
@@ -125,6 +130,10 @@ def main(argv=None):
         say("morph target: %s, weight %g" % (args.morph_to, args.morph_weight))
         scene.set_morph_targets(*T.morph_deltas(mesh, T.load_obj(args.morph_to)))
         scene.set_morph_weights([args.morph_weight])
+    if args.bend is not None:
+        say("two-bone rig: upper bone turned about z by %g degrees" % args.bend)
+        scene.set_skin(*bend_rig(mesh), n_bones=2)
+        scene.set_bone_palette(bend_palette(T, args.bend))
     rc = _run(args, T, scene, sharded, rank, say)
     if sharded:
         import torch.distributed as dist
@@ -146,6 +155,29 @@ def morph_wave(n_frames, weight):
     """--morph-to over --frames N: [N, 1] weights, a triangle wave from 0 up to `weight` and back, one period per call."""
     t = np.arange(n_frames, dtype=np.float64) / max(n_frames, 1)
     return (weight * (1.0 - np.abs(2.0 * t - 1.0))).astype(np.float32).reshape(n_frames, 1)
+
+
+def bend_rig(mesh):
+    """--bend: (bones [n_pos, 4] uint32, weights [n_pos, 4] float32) of a two-bone rig -- bone 0 holds the lower part of
+    the model, bone 1 the upper, blended by a smooth step in height over the middle third (the weights sum to one)."""
+    y = np.asarray(mesh["pos"], np.float64).reshape(-1, 3)[:, 1]
+    lo, hi = float(y.min()), float(y.max())
+    t = np.clip(((y - lo) / max(hi - lo, 1e-30) - 1.0 / 3.0) * 3.0, 0.0, 1.0)
+    upper = t * t * (3.0 - 2.0 * t)
+    bones = np.zeros((y.shape[0], 4), np.uint32)
+    bones[:, 1] = 1
+    weights = np.zeros((y.shape[0], 4), np.float32)
+    weights[:, 1] = upper.astype(np.float32)
+    weights[:, 0] = np.float32(1.0) - weights[:, 1]
+    return bones, weights
+
+
+def bend_palette(T, degrees):
+    """--bend: [2, 24] -- bone 0 at rest, bone 1 turned about z by `degrees` (`degrees` an array [N]: [N, 2, 24], one
+    palette per frame)."""
+    d = np.atleast_1d(np.asarray(degrees, np.float64))
+    pal = np.stack([T.rotation_instances([0.0, 0.0], 0.0, [0.0, np.deg2rad(a)], np.zeros((2, 3)), 1.0) for a in d])
+    return pal if np.ndim(degrees) else pal[0]
 
 
 def _run(args, T, scene, sharded, rank, say):
@@ -195,6 +227,8 @@ def _run(args, T, scene, sharded, rank, say):
             p[f, 3:6], p[f, 6:9], p[f, 9:12] = [float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0]
         if args.morph_to:
             scene.render_frames(p, morph_weights=morph_wave(args.frames, args.morph_weight))
+        elif args.bend is not None:
+            scene.render_frames(p, bone_palettes=bend_palette(T, args.bend * np.arange(1, args.frames + 1) / args.frames))
         else:
             scene.render_frames(p)
         angles = []

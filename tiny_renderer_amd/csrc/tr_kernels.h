@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include "tr_morph.h"
+#include "tr_skin.h"
 #include "tr_types.h"
 
 namespace tr {
@@ -66,6 +67,11 @@ int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, co
 // the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.
 int launch_morph(const float *base, const float *delta, uint32_t n_rows, uint32_t n_targets, const MorphTable &tab, uint32_t n_frames,
                  hipStream_t st, hipEvent_t start, hipEvent_t done);
+// Skinning: the skinned rows of n_frames frames (<= SKIN_MAX_FRAMES) by one launch -- frame f skins the rows tab.f[f].src
+// (n_rows x TRI_FLOATS; may be tab.f[f].dst) under the palette tab.f[f].pal (n_bones x 24 floats, device memory) and the
+// gathered influence rows `infl` (n_rows x SKIN_ROW_WORDS) into tab.f[f].dst: k_skin, tr_skin.h.
+int launch_skin(const uint32_t *infl, uint32_t n_rows, uint32_t n_bones, const SkinTable &tab, uint32_t n_frames, hipStream_t st,
+                hipEvent_t start, hipEvent_t done);
 int launch_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32, int32_t *out_i32,
                     uint32_t *out_u8, float *out_div, float *out_div_ref, hipStream_t st);
 // Peer exchange flags (tr_exchange.cpp): system-scope store of a generation number; waits that poll

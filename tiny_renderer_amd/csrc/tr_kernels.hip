@@ -34,6 +34,7 @@
 #include "tr_plan.h"
 #include "tr_resolve.h"
 #include "tr_shaders.h"
+#include "tr_skin.h"
 
 namespace tr {
 
@@ -1852,6 +1853,70 @@ __global__ __launch_bounds__(256) void k_morph(const float4 *__restrict__ base, 
     dst[i] = v;
 }
 
+// Skinning (tr_scene_set_bone_palette): the skinned rows of the frames of one launch.  Frame blockIdx.y skins the rows
+// tab.f[frame].src under its own palette into tab.f[frame].dst; tr_skin.h has the rule.  The workgroup first copies its
+// frame's palette into LDS in 16-byte pieces -- n_bones * 6 of them, up to 768 for 256 lanes: a loop -- because the
+// lanes then gather bones by index and the indices diverge across a wave: the gather is six ds_read_b128 per influence,
+// not scalar or global loads.  One lane owns one polygon: its row (six 16-byte loads, six 16-byte stores) and its
+// influence row (six 16-byte loads: 3 corners x 4 x {bone index, weight}).  src may be dst (a morph pose's rows, skinned
+// in place behind k_morph): a lane reads only its own row, and all of it, before it writes it -- so neither pointer is
+// __restrict__.  Floats 18..23, the uvs, pass through.  Every index into the row, the influences and a bone's entry is
+// a compile-time constant (the loops are unrolled): nothing goes to scratch.  No atomics.  
+struct LdsPalette {
+    const float4 *pal;
+    __device__ __forceinline__ void operator()(uint32_t b, float *e) const
+    {
+#pragma unroll
+        for (int i = 0; i < INST_XFORM_FLOATS / 4; i++) {
+            const float4 q = pal[(INST_XFORM_FLOATS / 4) * b + i];
+            e[4 * i] = q.x;
+            e[4 * i + 1] = q.y;
+            e[4 * i + 2] = q.z;
+            e[4 * i + 3] = q.w;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void k_skin(const uint4 *__restrict__ infl, uint32_t n_rows, uint32_t n_bones, SkinTable tab)
+{
+    __shared__ float4 pal[SKIN_MAX_BONES * (INST_XFORM_FLOATS / 4)];
+    const SkinFrame fr = tab.f[blockIdx.y];  // (the table is in the kernel's argument segment: scalar loads)
+    const float4 *gpal = reinterpret_cast<const float4 *>(fr.pal);
+    const uint32_t n_pieces = n_bones * (uint32_t)(INST_XFORM_FLOATS / 4);  // (n_bones <= SKIN_MAX_BONES: launch_skin)
+    for (uint32_t i = threadIdx.x; i < n_pieces; i += 256u) pal[i] = gpal[i];
+    __syncthreads();
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= n_rows) return;
+    const float4 *src = reinterpret_cast<const float4 *>(fr.src) + (size_t)(TRI_FLOATS / 4) * t;
+    float4 *dst = reinterpret_cast<float4 *>(fr.dst) + (size_t)(TRI_FLOATS / 4) * t;
+    const uint4 *in = infl + (size_t)(SKIN_ROW_WORDS / 4) * t;
+    float m[TRI_FLOATS];
+    uint32_t bone[3 * SKIN_INFLUENCES];
+    float weight[3 * SKIN_INFLUENCES];
+#pragma unroll
+    for (int i = 0; i < TRI_FLOATS / 4; i++) {
+        const float4 q = src[i];
+        m[4 * i] = q.x;
+        m[4 * i + 1] = q.y;
+        m[4 * i + 2] = q.z;
+        m[4 * i + 3] = q.w;
+    }
+#pragma unroll
+    for (int i = 0; i < SKIN_ROW_WORDS / 4; i++) {
+        const uint4 q = in[i];
+        bone[2 * i] = q.x;
+        weight[2 * i] = __uint_as_float(q.y);
+        bone[2 * i + 1] = q.z;
+        weight[2 * i + 1] = __uint_as_float(q.w);
+    }
+    const LdsPalette entry = { pal };
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+        skin_corner(entry, bone + SKIN_INFLUENCES * c, weight + SKIN_INFLUENCES * c, m + 3 * c, m + 9 + 3 * c);
+#pragma unroll
+    for (int i = 0; i < TRI_FLOATS / 4; i++) dst[i] = make_float4(m[4 * i], m[4 * i + 1], m[4 * i + 2], m[4 * i + 3]);
+}
+
 // tr_selftest_device_math: the device forms of the casts and of the shared-reciprocal division,
 // applied to caller-chosen operands so the host can compare them with its own.
 __global__ __launch_bounds__(256) void k_selftest(const float *x, const float *d, uint32_t n, uint32_t *out_u32,
@@ -2327,6 +2392,17 @@ int launch_morph(const float *base, const float *delta, uint32_t n_rows, uint32_
     const dim3 grid((n_pieces + 255u) / 256u, n_frames);
     hipExtLaunchKernelGGL(k_morph, grid, dim3(256), 0, st, start, done, 0, reinterpret_cast<const float4 *>(base),
                           reinterpret_cast<const float4 *>(delta), n_pieces, n_targets, tab);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_skin(const uint32_t *infl, uint32_t n_rows, uint32_t n_bones, const SkinTable &tab, uint32_t n_frames, hipStream_t st,
+                hipEvent_t start, hipEvent_t done)
+{
+    if (n_rows == 0 || n_frames == 0) return 0;
+    if (n_frames > (uint32_t)SKIN_MAX_FRAMES || n_bones == 0 || n_bones > (uint32_t)SKIN_MAX_BONES) return (int)hipErrorInvalidValue;
+    const dim3 grid((n_rows + 255u) / 256u, n_frames);
+    hipExtLaunchKernelGGL(k_skin, grid, dim3(256), 0, st, start, done, 0, reinterpret_cast<const uint4 *>(infl), n_rows, n_bones, tab);
     TR_LAUNCH_CHECK();
     return 0;
 }

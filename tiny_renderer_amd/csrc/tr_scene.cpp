@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -175,9 +175,11 @@ struct tr_scene {
         uint32_t stride = tr::INST_FLOATS;  // floats per entry: INST_FLOATS {offset xyz, scale} or INST_XFORM_FLOATS (a transform table)
         hipEvent_t used[3] = {}; // behind the last chain on the main stream, setup_stream, setup_stream2 that read it
     };
-    // Morph targets (tr_scene_set_morph_targets / _weights).  A pose is the host's copy of a weight vector and, from the
-    // first render that draws it, its posed rows on the device: what DevMesh::tri points at instead of d_tri.  The rows
-    // have the lifetime of an instance table's block: written once -- by k_morph, queued ahead of the first chain that
+    // Morph targets (tr_scene_set_morph_targets / _weights) and skinning (tr_scene_set_skin / _bone_palette).  A pose is
+    // the host's copy of a weight vector, of a bone palette, or of both (one with neither is no pose: the pointer is
+    // null) and, from the first render that draws it, its posed rows on the device: what DevMesh::tri points at instead
+    // of d_tri.  The rows have the lifetime of an instance table's block: written once -- by k_morph and, behind it,
+    // k_skin in place, queued ahead of the first chain that
     // reads them (blend_poses) -- and never again while anybody may render with them; the holders are the same (a pose
     // travels in the InstRef beside the table).  When the last holder lets go, the rows go back to the scene's pool
     // (pose_free) with one event per stream whose chains read them; they are handed out again when those have completed.
@@ -191,9 +193,10 @@ struct tr_scene {
     };
     struct Pose {
         tr_scene *owner = nullptr;
-        std::vector<float> w;                   // the weights: n_targets of them
+        std::vector<float> w;                   // the morph weights: n_targets of them, or none
+        std::vector<float> pal;                 // the bone palette: n_bones * INST_XFORM_FLOATS floats, or none
         PoseRows rows;                          // (d null until a render is about to draw the pose: pose_rows)
-        bool blended = false;                   // k_morph has been queued for the rows
+        bool blended = false;                   // k_morph / k_skin have been queued for the rows
         std::shared_ptr<SharedEvent> done;      // ... and this is recorded behind it, on `done_on`
         hipStream_t done_on = nullptr;
         bool done_seen = false;                 // the host has seen `done` completed: no chain needs to wait for it
@@ -217,6 +220,11 @@ struct tr_scene {
         std::shared_ptr<SharedEvent> done;
     } morph_stage[4];
     uint64_t morph_launches = 0;
+    uint32_t n_bones = 0;                // bones of the scene's skin (0: no skin)
+    uint32_t *d_skin = nullptr;          // its gathered influence rows: n_rows x SKIN_ROW_WORDS
+    // k_skin's palettes on their way to the device: the same ring (GROUP_MAX frames x TR_SKIN_MAX_BONES entries each)
+    MorphStage skin_stage[4];
+    uint64_t skin_launches = 0;
     InstRef inst;                    // the current table
     std::vector<std::shared_ptr<InstBlock>> inst_blocks;  // every block the scene owns
     uint32_t n_rows = 0;             // polygons of the mesh (rows of d_tri)
@@ -679,13 +687,27 @@ std::shared_ptr<tr_scene::SharedEvent> new_shared_event()
     return e;
 }
 
-// A pose of the scene's targets under weights w[0 .. n_targets).
-std::shared_ptr<tr_scene::Pose> make_pose(tr_scene *s, const float *w)
+// A pose of the scene's targets under weights w[0 .. n_targets) (null: no weights) and of its skin under the palette
+// pal[0 .. n_bones * INST_XFORM_FLOATS) (null: no palette); neither: no pose.
+std::shared_ptr<tr_scene::Pose> make_pose(tr_scene *s, const float *w, const float *pal)
 {
+    if (!w && !pal) return nullptr;
     std::shared_ptr<tr_scene::Pose> p = std::make_shared<tr_scene::Pose>();
     p->owner = s;
-    p->w.assign(w, w + s->n_targets);
+    if (w) p->w.assign(w, w + s->n_targets);
+    if (pal) p->pal.assign(pal, pal + (size_t)s->n_bones * INST_XFORM_FLOATS);
     return p;
+}
+
+// The halves of pose `p` (null: none) as make_pose takes them.  A half made under targets or a skin the scene has since
+// replaced (a kept frame's, selected again) is not carried over into a new pose: null.
+const float *pose_weights(const tr_scene *s, const std::shared_ptr<tr_scene::Pose> &p)
+{
+    return p && !p->w.empty() && p->w.size() == (size_t)s->n_targets ? p->w.data() : nullptr;
+}
+const float *pose_palette(const tr_scene *s, const std::shared_ptr<tr_scene::Pose> &p)
+{
+    return p && !p->pal.empty() && p->pal.size() == (size_t)s->n_bones * INST_XFORM_FLOATS ? p->pal.data() : nullptr;
 }
 
 // Free rows beyond this many are given back to the device (trim_pose_pool): a group's worth may wait for their readers
@@ -757,12 +779,27 @@ int note_pose_use(tr_scene *s, const std::shared_ptr<tr_scene::Pose> *poses, uin
     return TR_OK;
 }
 
+// One launch's worth of per-frame vectors (k_morph's weights, k_skin's palettes) through the ring `ring`: slot
+// `launches % 4`, allocated on first use for `floats` floats, free again once the launch that last read it has run.
+int take_stage(tr_scene::MorphStage *ring, uint64_t launches, size_t floats, tr_scene::MorphStage **out)
+{
+    tr_scene::MorphStage &stage = ring[launches % 4u];
+    int st = TR_OK;
+    if (!stage.h) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&stage.h), sizeof(float) * floats, hipHostMallocDefault));
+    if (!stage.d && (st = dev_alloc(&stage.d, floats)) != TR_OK) return st;
+    if (stage.done) HIP_TRY(hipEventSynchronize(stage.done->ev));  // (four launches ago: long done)
+    *out = &stage;
+    return TR_OK;
+}
+
 // Before a chain on `chain` reads the rows of `poses` (null entries and repeats allowed): the ones not blended yet get
-// their rows and are blended by ONE launch of k_morph on `chain`; the chain waits for those blended on another stream.
+// their rows; those with weights are blended by ONE launch of k_morph on `chain`, those with a palette are then skinned
+// by ONE launch of k_skin behind it (in place where k_morph wrote the rows, from the mesh's own rows otherwise), and one
+// event behind the last launch stands for both; the chain waits for those blended on another stream.
 int blend_poses(tr_scene *s, const std::shared_ptr<tr_scene::Pose> *poses, uint32_t n, hipStream_t chain)
 {
     tr_scene::Pose *todo[GROUP_MAX];
-    uint32_t m = 0;
+    uint32_t m = 0, m_morph = 0, m_skin = 0;
     for (uint32_t j = 0; j < n; j++) {
         tr_scene::Pose *p = poses[j].get();
         if (!p) continue;
@@ -776,37 +813,74 @@ int blend_poses(tr_scene *s, const std::shared_ptr<tr_scene::Pose> *poses, uint3
         bool listed = false;  // (a pose that several frames draw is blended once)
         for (uint32_t i = 0; i < m; i++) listed = listed || todo[i] == p;
         if (listed) continue;
-        if (p->w.size() != (size_t)s->n_targets || !s->d_delta) return tr::fail(TR_E_INVALID, "pose of targets the scene no longer has");
+        if (!p->w.empty() && (p->w.size() != (size_t)s->n_targets || !s->d_delta))
+            return tr::fail(TR_E_INVALID, "pose of targets the scene no longer has");
+        if (!p->pal.empty() && (p->pal.size() != (size_t)s->n_bones * INST_XFORM_FLOATS || !s->d_skin))
+            return tr::fail(TR_E_INVALID, "palette of a skin the scene no longer has");
+        if (p->w.empty() && p->pal.empty()) return tr::fail(TR_E_INVALID, "empty pose");
         if (m >= (uint32_t)GROUP_MAX) return tr::fail(TR_E_INVALID, "too many poses for one launch");
         int st = pose_rows(s, *p);
         if (st != TR_OK) return st;
         todo[m++] = p;
+        m_morph += p->w.empty() ? 0u : 1u;
+        m_skin += p->pal.empty() ? 0u : 1u;
     }
     if (m == 0) return TR_OK;
-    const uint32_t T = s->n_targets;
-    tr_scene::MorphStage &stage = s->morph_stage[s->morph_launches % 4u];
     int st = TR_OK;
-    if (!stage.h)
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&stage.h), sizeof(float) * GROUP_MAX * TR_MORPH_MAX_TARGETS, hipHostMallocDefault));
-    if (!stage.d && (st = dev_alloc(&stage.d, (size_t)GROUP_MAX * TR_MORPH_MAX_TARGETS)) != TR_OK) return st;
-    if (stage.done) HIP_TRY(hipEventSynchronize(stage.done->ev));  // (four launches ago: long done)
-    MorphTable tab = {};
-    for (uint32_t j = 0; j < m; j++) {
-        memcpy(stage.h + (size_t)j * T, todo[j]->w.data(), sizeof(float) * T);
-        tab.f[j].w = stage.d + (size_t)j * T;
-        tab.f[j].dst = todo[j]->rows.d;
+    tr_scene::MorphStage *morph_stage = nullptr, *skin_stage = nullptr;
+    if (m_morph) {
+        const uint32_t T = s->n_targets;
+        if ((st = take_stage(s->morph_stage, s->morph_launches, (size_t)GROUP_MAX * TR_MORPH_MAX_TARGETS, &morph_stage)) != TR_OK) return st;
+        tr_scene::MorphStage &stage = *morph_stage;
+        MorphTable tab = {};
+        uint32_t k = 0;
+        for (uint32_t j = 0; j < m; j++) {
+            if (todo[j]->w.empty()) continue;
+            memcpy(stage.h + (size_t)k * T, todo[j]->w.data(), sizeof(float) * T);
+            tab.f[k].w = stage.d + (size_t)k * T;
+            tab.f[k].dst = todo[j]->rows.d;
+            k++;
+        }
+        HIP_TRY(hipMemcpyAsync(stage.d, stage.h, sizeof(float) * (size_t)k * T, hipMemcpyHostToDevice, chain));
+        EventPair ep = { nullptr, nullptr, K_MORPH, k };
+        if (s->profiling) { ep.a = take_event(s); ep.b = take_event(s); }
+        int rc = launch_morph(s->d_tri, s->d_delta, s->n_rows, T, tab, k, chain, ep.a, ep.b);
+        if (rc) return launch_status(rc, "k_morph");
+        if (s->profiling) s->events.push_back(ep);
     }
-    HIP_TRY(hipMemcpyAsync(stage.d, stage.h, sizeof(float) * (size_t)m * T, hipMemcpyHostToDevice, chain));
-    EventPair ep = { nullptr, nullptr, K_MORPH, m };
-    if (s->profiling) { ep.a = take_event(s); ep.b = take_event(s); }
-    int rc = launch_morph(s->d_tri, s->d_delta, s->n_rows, T, tab, m, chain, ep.a, ep.b);
-    if (rc) return launch_status(rc, "k_morph");
-    if (s->profiling) s->events.push_back(ep);
+    if (m_skin) {
+        const size_t B = (size_t)s->n_bones * INST_XFORM_FLOATS;  // floats of a palette (a multiple of four: 16-byte pieces)
+        if ((st = take_stage(s->skin_stage, s->skin_launches, (size_t)GROUP_MAX * TR_SKIN_MAX_BONES * INST_XFORM_FLOATS, &skin_stage)) != TR_OK)
+            return st;
+        tr_scene::MorphStage &stage = *skin_stage;
+        SkinTable tab = {};
+        uint32_t k = 0;
+        for (uint32_t j = 0; j < m; j++) {
+            if (todo[j]->pal.empty()) continue;
+            memcpy(stage.h + (size_t)k * B, todo[j]->pal.data(), sizeof(float) * B);
+            tab.f[k].pal = stage.d + (size_t)k * B;
+            tab.f[k].src = todo[j]->w.empty() ? s->d_tri : todo[j]->rows.d;  // (the morphed rows, in place; else the mesh's own)
+            tab.f[k].dst = todo[j]->rows.d;
+            k++;
+        }
+        HIP_TRY(hipMemcpyAsync(stage.d, stage.h, sizeof(float) * (size_t)k * B, hipMemcpyHostToDevice, chain));
+        EventPair ep = { nullptr, nullptr, K_SKIN, k };
+        if (s->profiling) { ep.a = take_event(s); ep.b = take_event(s); }
+        int rc = launch_skin(s->d_skin, s->n_rows, s->n_bones, tab, k, chain, ep.a, ep.b);
+        if (rc) return launch_status(rc, "k_skin");
+        if (s->profiling) s->events.push_back(ep);
+    }
     std::shared_ptr<tr_scene::SharedEvent> done = new_shared_event();
     if (!done) return tr::fail(TR_E_HIP, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(done->ev, chain));
-    stage.done = done;
-    s->morph_launches++;
+    if (morph_stage) {
+        morph_stage->done = done;
+        s->morph_launches++;
+    }
+    if (skin_stage) {
+        skin_stage->done = done;
+        s->skin_launches++;
+    }
     for (uint32_t j = 0; j < m; j++) {
         todo[j]->blended = true;
         todo[j]->done = done;
@@ -2085,11 +2159,13 @@ int flush_deferred(tr_scene *s, bool hold_back)
 }
 
 // n cleared frames, frame i into slot i % G, drawing instance table insts[i] (insts == null: the current one);
-// afterwards the last one is the scene's current frame.  posed: frame i draws a pose of its own -- weights pose_w +
-// i * n_targets (pose_w null: no pose) -- made when its group is set up, so that only what holds a frame (its slot, the
-// kept frames, work in flight) holds a pose's rows: not the call.
+// afterwards the last one is the scene's current frame.  posed: frame i draws a pose of its own -- POSED_WEIGHTS: weights
+// pose_v + i * n_targets with the current palette, POSED_PALETTES: palette pose_v + i * n_bones * INST_XFORM_FLOATS with
+// the current weights (pose_v null: without that half) -- made when its group is set up, so that only what holds a frame
+// (its slot, the kept frames, work in flight) holds a pose's rows: not the call.
+enum PerFramePose { POSED_NONE = 0, POSED_WEIGHTS, POSED_PALETTES };
 int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_scene::InstRef *insts, void *const *fbs,
-                  bool posed = false, const float *pose_w = nullptr)
+                  PerFramePose posed = POSED_NONE, const float *pose_v = nullptr)
 {
     int st = submit_pending(s);  // per-frame renders issued before go first
     if (st != TR_OK) return st;
@@ -2112,11 +2188,15 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_sc
     s->host_status = TR_OK;
     const uint64_t first_seq = s->pass_seq;
     const uint32_t kept = cp.kept;  // what is left of the call: its last min(n, G) frames
-    const bool per_frame = insts != nullptr || posed;
+    const bool per_frame = insts != nullptr || posed != POSED_NONE;
     std::vector<tr_scene::InstRef> kept_refs;  // their tables and poses
+    const std::shared_ptr<tr_scene::Pose> pose0 = s->inst.pose;  // (its other half goes into every frame's pose)
     auto ref_of = [&](uint32_t i) {
         tr_scene::InstRef r = insts ? insts[i] : s->inst;
-        if (posed) r.pose = pose_w ? make_pose(s, pose_w + (size_t)i * s->n_targets) : nullptr;
+        if (posed == POSED_WEIGHTS)
+            r.pose = make_pose(s, pose_v ? pose_v + (size_t)i * s->n_targets : nullptr, pose_palette(s, pose0));
+        if (posed == POSED_PALETTES)
+            r.pose = make_pose(s, pose_weights(s, pose0), pose_v ? pose_v + (size_t)i * s->n_bones * INST_XFORM_FLOATS : nullptr);
         if (i >= n - kept) kept_refs.push_back(r);
         return r;
     };
@@ -2303,11 +2383,14 @@ void destroy(tr_scene *s)
     s->pose_free.clear();
     s->pose_rows_live = 0;
     dev_free(s->d_delta);
-    for (tr_scene::MorphStage &m : s->morph_stage) {
-        if (m.h) (void)hipHostFree(m.h);
-        dev_free(m.d);
-        m.done.reset();
-    }
+    dev_free(s->d_skin);
+    for (tr_scene::MorphStage *ring : { s->morph_stage, s->skin_stage })
+        for (int k = 0; k < 4; k++) {
+            tr_scene::MorphStage &m = ring[k];
+            if (m.h) (void)hipHostFree(m.h);
+            dev_free(m.d);
+            m.done.reset();
+        }
     for (int k = 0; k < 4; k++) dev_free(s->d_texel[k]);
     dev_free(s->d_packed);
     for (int k = 0; k < LOOKAHEAD; k++) dev_free(s->d_lit[k]);
@@ -2987,9 +3070,10 @@ int tr_scene_set_morph_targets(tr_scene *s, uint32_t n_targets, const float *dpo
     s->d_delta = d_new;
     s->n_targets = n_targets;
     trim_pose_pool(s, 0);  // (everything queued has run: the free rows go back to the device)
-    // no pose of the old targets stays current (frames already rendered keep their rows)
+    // no weights of the old targets stay current (frames already rendered keep their rows); the palette does: the skin
+    // does not depend on the targets
     tr_scene::InstRef r = s->inst;
-    r.pose.reset();
+    r.pose = make_pose(s, nullptr, pose_palette(s, s->inst.pose));
     use_inst(s, r);
     return TR_OK;
 }
@@ -3000,7 +3084,7 @@ int tr_scene_set_morph_weights(tr_scene *s, uint32_t n_weights, const float *w)
     if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
     if (n_weights && !w) return tr::fail(TR_E_INVALID, "null weights");
     tr_scene::InstRef r = s->inst;
-    r.pose = n_weights ? make_pose(s, w) : nullptr;
+    r.pose = make_pose(s, n_weights ? w : nullptr, pose_palette(s, s->inst.pose));  // (the palette stays)
     use_inst(s, r);
     return TR_OK;
 }
@@ -3018,7 +3102,7 @@ int tr_scene_render_frames_morphed(tr_scene *s, uint32_t n_frames, const tr_fram
             if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
     HIP_TRY(hipSetDevice(s->device));
     // the current table under a pose per frame
-    return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, true, n_weights ? weights : nullptr);
+    return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, POSED_WEIGHTS, n_weights ? weights : nullptr);
 }
 
 int tr_scene_debug_morph_rows(tr_scene *s)
@@ -3038,6 +3122,90 @@ int tr_morph_mesh(const tr_mesh *mesh, uint32_t n_targets, const float *dpos, co
     const size_t np = (size_t)mesh->n_pos * 3u, nn = (size_t)mesh->n_nrm * 3u;
     for (size_t i = 0; i < np; i++) pos_out[i] = tr::morph_component(mesh->pos[i], n_targets, w, dpos + i, np);
     for (size_t i = 0; i < nn; i++) nrm_out[i] = tr::morph_component(mesh->nrm[i], n_targets, w, dnrm + i, nn);
+    return TR_OK;
+}
+
+int tr_scene_set_skin(tr_scene *s, uint32_t n_bones, const uint32_t *bone, const float *weight)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    if (n_bones > (uint32_t)TR_SKIN_MAX_BONES) return tr::fail(TR_E_INVALID, "more than TR_SKIN_MAX_BONES bones");
+    if (n_bones && s->n_pos && (!bone || !weight)) return tr::fail(TR_E_INVALID, "null influence array");
+    for (size_t i = 0; n_bones && i < (size_t)s->n_pos * tr::SKIN_INFLUENCES; i++)
+        if (bone[i] >= n_bones) return tr::fail(TR_E_INVALID, "bone index beyond n_bones");
+    HIP_TRY(hipSetDevice(s->device));
+    // the influences gathered per polygon like the mesh's rows
+    std::vector<uint32_t> rows(n_bones ? (size_t)s->n_rows * tr::SKIN_ROW_WORDS : 0u);
+    if (n_bones) tr::gather_skin_rows(s->mesh_idx.data(), s->n_rows, bone, weight, rows.data());
+    uint32_t *d_new = nullptr;
+    int st = TR_OK;
+    if (n_bones && (st = dev_alloc(&d_new, rows.size())) != TR_OK) return st;
+    // frames issued so far keep their palettes: they go to the device, and everything queued runs, before the skin changes
+    if ((st = submit_pending(s)) != TR_OK) {
+        dev_free(d_new);
+        return st;
+    }
+    hipError_t e = hipStreamSynchronize(s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
+    if (e == hipSuccess && n_bones) e = hipMemcpy(d_new, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
+    if (e != hipSuccess) {
+        dev_free(d_new);
+        HIP_TRY(e);
+    }
+    dev_free(s->d_skin);
+    s->d_skin = d_new;
+    s->n_bones = n_bones;
+    trim_pose_pool(s, 0);  // (everything queued has run: the free rows go back to the device)
+    // no palette of the old skin stays current (frames already rendered keep their rows); the morph weights do
+    tr_scene::InstRef r = s->inst;
+    r.pose = make_pose(s, pose_weights(s, s->inst.pose), nullptr);
+    use_inst(s, r);
+    return TR_OK;
+}
+
+int tr_scene_set_bone_palette(tr_scene *s, uint32_t n_bones, const tr_instance_xform *palette)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "null scene");
+    if (n_bones != 0u && n_bones != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
+    if (n_bones && !palette) return tr::fail(TR_E_INVALID, "null palette");
+    tr_scene::InstRef r = s->inst;
+    r.pose = make_pose(s, pose_weights(s, s->inst.pose), n_bones ? reinterpret_cast<const float *>(palette) : nullptr);  // (the weights stay)
+    use_inst(s, r);
+    return TR_OK;
+}
+
+int tr_scene_render_frames_skinned(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_bones,
+                                   const tr_instance_xform *palettes, void *const *frame_buffers_device)
+{
+    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (n_bones != 0u && n_bones != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
+    if (n_bones && n_frames && !palettes) return tr::fail(TR_E_INVALID, "null palettes");
+    if (n_frames == 0) return TR_OK;
+    if (frame_buffers_device)
+        for (uint32_t i = 0; i < n_frames; i++)
+            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
+    HIP_TRY(hipSetDevice(s->device));
+    // the current table and morph weights under a palette per frame
+    return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, POSED_PALETTES,
+                         n_bones ? reinterpret_cast<const float *>(palettes) : nullptr);
+}
+
+// The rule of tr_skin.h over the indexed arrays, on the host: the unrolled skinned mesh.  Needs no GPU.
+int tr_skin_mesh(const tr_mesh *mesh, uint32_t n_bones, const uint32_t *bone, const float *weight, const tr_instance_xform *palette,
+                 float *pos_out, float *nrm_out, uint32_t *idx_out)
+{
+    if (!mesh) return tr::fail(TR_E_INVALID, "null argument");
+    if (n_bones == 0 || n_bones > (uint32_t)TR_SKIN_MAX_BONES) return tr::fail(TR_E_INVALID, "n_bones must be 1 .. TR_SKIN_MAX_BONES");
+    if (!palette || (mesh->n_pos && (!bone || !weight))) return tr::fail(TR_E_INVALID, "null argument");
+    if (mesh->n_tri && (!mesh->pos || !mesh->nrm || !mesh->idx || !pos_out || !nrm_out || !idx_out)) return tr::fail(TR_E_INVALID, "null array");
+    for (size_t i = 0; i < (size_t)mesh->n_pos * tr::SKIN_INFLUENCES; i++)
+        if (bone[i] >= n_bones) return tr::fail(TR_E_INVALID, "bone index beyond n_bones");
+    for (size_t i = 0; i < (size_t)mesh->n_tri * 9u; i += 3u)
+        if (mesh->idx[i] >= mesh->n_pos || mesh->idx[i + 2u] >= mesh->n_nrm) return tr::fail(TR_E_INVALID, "mesh index out of range");
+    tr::skin_mesh_unrolled(mesh->pos, mesh->nrm, mesh->idx, mesh->n_tri, bone, weight, reinterpret_cast<const float *>(palette), pos_out,
+                           nrm_out, idx_out);
     return TR_OK;
 }
 

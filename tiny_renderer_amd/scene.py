@@ -105,6 +105,50 @@ def morph_mesh(mesh, dpos, dnrm, weights):
     return pos, nrm
 
 
+def _skin(mesh, bones, weights):
+    """(bones [n_pos, 4] uint32, weights [n_pos, 4] float32) contiguous, checked against the mesh's positions."""
+    n_pos = np.asarray(mesh["pos"]).reshape(-1, 3).shape[0]
+    b = np.asarray(bones)
+    w = np.ascontiguousarray(weights, np.float32)
+    if b.shape != (n_pos, _lib.TR_SKIN_INFLUENCES) or w.shape != b.shape:
+        raise ValueError("a skin is bones [%d, 4] uint32 and weights [%d, 4] float32 (four influences per position)" % (n_pos, n_pos))
+    if b.size and (not np.issubdtype(b.dtype, np.integer) or b.min() < 0):
+        raise ValueError("bone indices must be non-negative integers")
+    return np.ascontiguousarray(b, np.uint32), w
+
+
+def _palette(palette, n_bones=None, per_frame=False):
+    """[n_bones, 24] float32 (tr_instance_xform per bone) -- or [n_frames, n_bones, 24] with per_frame."""
+    a = np.ascontiguousarray(palette, np.float32)
+    if a.shape[-1:] != (24,) or a.ndim != (3 if per_frame else 2) or a.shape[-2] == 0:
+        raise ValueError("a bone palette must be [%sn_bones, 24] float32 (instance_transforms builds one)"
+                         % ("n_frames, " if per_frame else ""))
+    if a.shape[-2] > _lib.TR_SKIN_MAX_BONES:
+        raise ValueError("at most %d bones" % _lib.TR_SKIN_MAX_BONES)
+    if n_bones is not None and a.shape[-2] != n_bones:
+        raise ValueError("the palette has %d bones, the skin %d" % (a.shape[-2], n_bones))
+    return a
+
+
+def skin_mesh(mesh, bones, weights, palette):
+    """tr_skin_mesh: the mesh skinned on the host (no GPU needed) by the inline function k_skin calls -- bones [n_pos, 4]
+    uint32 and weights [n_pos, 4] float32 per position index, palette [n_bones, 24] float32.  Returns a mesh dict whose
+    pos [n_tri * 3, 3], nrm [n_tri * 3, 3] and idx [n_tri, 9] are unrolled (a position and a normal per corner); tex and
+    everything else are the mesh's own."""
+    b, w = _skin(mesh, bones, weights)
+    pal = _palette(palette)
+    if b.size and int(b.max()) >= pal.shape[0]:
+        raise ValueError("bone index %d beyond the palette's %d bones" % (int(b.max()), pal.shape[0]))
+    keep = []
+    m = _mesh_struct(mesh, keep)
+    pos = np.empty((m.n_tri * 3, 3), np.float32)
+    nrm = np.empty((m.n_tri * 3, 3), np.float32)
+    idx = np.empty((m.n_tri, 9), np.uint32)
+    check(load_library().tr_skin_mesh(C.byref(m), pal.shape[0], b.ctypes.data, w.ctypes.data, pal.ctypes.data,
+                                      pos.ctypes.data, nrm.ctypes.data, idx.ctypes.data))
+    return dict(mesh, pos=pos, nrm=nrm, idx=idx)
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -161,6 +205,7 @@ class Scene:
         self.pipeline = shader_pipeline_name
         self._mesh_shape = {"pos": np.empty((m.n_pos, 3), np.float32), "nrm": np.empty((m.n_nrm, 3), np.float32)}
         self.n_morph_targets = 0
+        self.n_bones = 0
         if instances is not None:
             self.set_instances(instances)
         if instance_transforms is not None:
@@ -241,11 +286,42 @@ class Scene:
         w = _morph_weights(weights, self.n_morph_targets)
         check(L.tr_scene_set_morph_weights(self._h, w.shape[0], w.ctypes.data))
 
+    def set_skin(self, bones, weights=None, n_bones=None):
+        """tr_scene_set_skin: four influences per position index -- bones [n_pos, 4] uint32, weights [n_pos, 4] float32;
+        n_bones: the palette's size (default: the largest index + 1).  None: drops the skin.  Leaves the scene without a
+        palette."""
+        L = load_library()
+        if bones is None:
+            check(L.tr_scene_set_skin(self._h, 0, None, None))
+            self.n_bones = 0
+            return
+        if weights is None:
+            raise ValueError("a skin needs weights beside bones")
+        b, w = _skin(self._mesh_shape, bones, weights)
+        n = int(n_bones) if n_bones is not None else (int(b.max()) + 1 if b.size else 1)
+        if n < 1 or n > _lib.TR_SKIN_MAX_BONES:
+            raise ValueError("a skin has 1 .. %d bones" % _lib.TR_SKIN_MAX_BONES)
+        if b.size and int(b.max()) >= n:
+            raise ValueError("bone index %d beyond the skin's %d bones" % (int(b.max()), n))
+        check(L.tr_scene_set_skin(self._h, n, b.ctypes.data, w.ctypes.data))
+        self.n_bones = n
+
+    def set_bone_palette(self, palette):
+        """tr_scene_set_bone_palette: the palette drawn from now on, [n_bones, 24] float32 (instance_transforms builds
+        one); None or empty: no palette -- the morph pose's rows or the mesh's own."""
+        L = load_library()
+        if palette is None or len(palette) == 0:
+            check(L.tr_scene_set_bone_palette(self._h, 0, None))
+            return
+        a = _palette(palette, self.n_bones)
+        check(L.tr_scene_set_bone_palette(self._h, a.shape[0], a.ctypes.data))
+
     def debug_morph_rows(self):
         """tr_scene_debug_morph_rows: sets of posed rows the scene has on the device now (held and free)."""
         return check(load_library().tr_scene_debug_morph_rows(self._h))
 
-    def render_frames(self, frames, frame_buffers_device=None, instances=None, instance_transforms=None, morph_weights=None):
+    def render_frames(self, frames, frame_buffers_device=None, instances=None, instance_transforms=None, morph_weights=None,
+                      bone_palettes=None):
         """tr_scene_render_frames: `frames` is an [n, 12] float32 array (or a list of (light, look_from,
         look_at, up) tuples): per frame light direction, look_from, look_at, up.  Frame i is what
         clear(); set_light_direction; set_camera; render() produces; the frames of a group are rendered by
@@ -256,7 +332,12 @@ class Scene:
         (tr_scene_render_frames_transformed); at most one of the two.
         morph_weights: [n, T] float32 -- frame i draws the pose morph_weights[i] (what set_morph_weights before its
         render would do; tr_scene_render_frames_morphed) under the scene's current table; not together with a table per
-        frame."""
+        frame.
+        bone_palettes: [n, n_bones, 24] float32 -- frame i draws the palette bone_palettes[i] (what set_bone_palette
+        before its render would do; tr_scene_render_frames_skinned) under the scene's current morph pose and table; not
+        together with morph_weights= or a table per frame."""
+        if bone_palettes is not None and (morph_weights is not None or instances is not None or instance_transforms is not None):
+            raise ValueError("bone_palettes= draws the scene's current pose and table: nothing else per frame beside it")
         if instances is not None and instance_transforms is not None:
             raise ValueError("one table per frame: instances= or instance_transforms=, not both")
         if morph_weights is not None and (instances is not None or instance_transforms is not None):
@@ -270,6 +351,13 @@ class Scene:
             if len(frame_buffers_device) != len(frames):
                 raise ValueError("one frame buffer per frame")
             fbs = (C.c_void_p * len(frames))(*[int(q) for q in frame_buffers_device])
+        if bone_palettes is not None:
+            pal = _palette(bone_palettes, self.n_bones, per_frame=True)
+            if pal.shape[0] != len(frames):
+                raise ValueError("one palette per frame")
+            check(load_library().tr_scene_render_frames_skinned(self._h, len(frames), frames.ctypes.data, pal.shape[1],
+                                                                pal.ctypes.data, fbs))
+            return
         if morph_weights is not None:
             w = _morph_weights(morph_weights, self.n_morph_targets, per_frame=True)
             if w.shape[0] != len(frames):
