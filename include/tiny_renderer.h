@@ -393,6 +393,49 @@ int tr_scene_host_buffer_written(tr_scene *s, void *p);
 int tr_scene_resolve(tr_scene *s, uint32_t factor, void *out);
 int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb);
 
+/* Depth compositing (nothing of the kind upstream, whose Scene draws one mesh with one set of textures through one
+ * pipeline): the current frame of scene `src` is merged into the current frame of scene `dst` on the device, by the
+ * reference's own depth test (`if z_value <= z_buffer[index] { return false }`, shader.rs:175).  Per pixel, with zs and
+ * zd the z values tr_scene_read_z_f32 would return for src and dst:
+ *     covered = bits(zs) != bits(f32::MIN)    -- a pixel still at the cleared value was not drawn, and a drawn pixel never
+ *                                                holds that value: a fragment at f32::MIN fails the test against it
+ *     wins    = covered && !(zs <= zd)
+ * Where `wins`, dst's colour becomes src's three bytes, dst's z becomes zs and, if dst has the winner tap, its winner word
+ * becomes src's + winner_base (u32, wrapping); elsewhere dst is untouched.  Ties keep dst: the order of the calls is the
+ * tie order, as the polygon order is inside one scene.  NaN depth follows the test as written: a comparison with a NaN is
+ * false, so a covered src pixel whose z is NaN wins, and so does any covered src pixel over a NaN in dst.
+ * What it equals: the reference's fragment stages discard nowhere but at that test, so for the pipelines whose closures
+ * read nothing but the polygon, the uniforms and the textures -- `default`, `phong`, `normal_map`, `specular`, `darboux` --
+ * merging scene(B) into scene(A), same size, camera, light and textures, winner_base = A's polygon count, is bit for bit
+ * what one scene of the concatenated mesh A ++ B renders: colour, z and winner index.  `shadow` and `occlusion` merge by
+ * the same rule, but their closures read the scene's OWN shadow buffer: B casts no shadow on A, so the result is not that
+ * of a concatenated scene.  The scenes may differ in mesh, textures, pipeline, instance table, pose and options.
+ * Current frame: on both sides what the getters mean -- the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.
+ * Pending work: frames tr_scene_render holds back are submitted, on both scenes; a pending clear of dst is made real; the
+ * depth of either frame, if it was left on the chip (see TR_OPT_STORE_DEPTH), is fetched by the depth-only repeat of its
+ * pass.  Callers who composite every frame should create BOTH scenes with TR_OPT_STORE_DEPTH: the repeat then never runs.
+ * A src that is logically cleared (tr_scene_clear and nothing rendered since) covers nothing: the call returns TR_OK and
+ * does nothing.
+ * Asynchronous: k_composite is enqueued on dst's stream behind src's frame (an event recorded on src's stream), and src's
+ * stream then waits for it, so a later render of src cannot overwrite what the merge reads; the result is there after
+ * tr_scene_sync(dst).  Both scenes' passes issued so far count as handed on, as after tr_scene_get_frame_buffer_async:
+ * neither frame is rendered again behind the caller's back (a bin overflow among them is reported, TR_E_BIN_OVERFLOW).
+ * Tiles (128 x 16) in which src drew nothing are skipped on src's fast-clear flags without reading a pixel.
+ * Afterwards dst holds a drawn frame with its depth in memory: a tr_scene_render on dst without a clear depth-tests
+ * against the merged z as usual, further tr_scene_composite calls layer more scenes in, every getter sees the merged
+ * frame.  The shadow buffers are left alone and src is never written.  src's sticky device status stays src's own:
+ * tr_scene_sync(src) returns it.
+ * TR_E_INVALID, nothing changed and nothing queued: a NULL scene, dst == src, different devices, different width or
+ * height, different tr_options.band_row0/1, dst with TR_OPT_WINNER_TAP and src without. */
+int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base);
+/* The rule above on the host (no GPU needed), by the very inline function k_composite calls: n_pixels pixels, all arrays
+ * in one pixel order of the caller's choosing; z_dst, rgb_dst (3 bytes per pixel) and win_dst are updated in place.
+ * win_dst may be NULL (no winner words; win_src is then not read). */
+int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t *win_dst /* or NULL */,
+                      const float *z_src, const uint8_t *rgb_src, const uint32_t *win_src /* or NULL */,
+                      uint32_t winner_base);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

@@ -51,7 +51,20 @@ def main(argv=None):
     ap.add_argument("--bend", type=float, default=None, metavar="DEG",
                     help="skinning with a procedural two-bone rig: weights follow a smooth step in model height, the upper "
                          "bone is turned about z by DEG degrees; with --frames N the angle ramps from 0 to DEG over the call")
+    ap.add_argument("--with", dest="with_path", default=None, metavar="DIR",
+                    help="a second asset folder: its model is rendered by a scene of its own -- own textures, same size, camera "
+                         "and light -- and merged into the picture by depth on the GPU (Scene.composite)")
+    ap.add_argument("--with-shader", default=None, metavar="PIPELINE", help="shader pipeline of the --with model (default: -s)")
+    ap.add_argument("--with-offset", default="0,0,0", metavar="X,Y,Z", help="where the --with model stands (an instance offset)")
     args = ap.parse_args(argv)
+    if args.with_path and (args.gpus > 1 or args.seconds > 0):
+        ap.error("--with merges two scenes of one GPU, by frame count: use --gpus 1 and --frames")
+    if args.with_path:
+        try:
+            args.with_offset = [float(v) for v in args.with_offset.split(",")]
+            assert len(args.with_offset) == 3
+        except (ValueError, AssertionError):
+            ap.error("--with-offset takes three numbers: x,y,z")
     if args.bend is not None and (args.gpus > 1 or args.seconds > 0 or args.morph_to):
         ap.error("--bend skins the scene of one GPU, by frame count, without --morph-to: use --gpus 1 and --frames")
     if args.morph_to and (args.gpus > 1 or args.seconds > 0):
@@ -134,6 +147,14 @@ def main(argv=None):
         say("two-bone rig: upper bone turned about z by %g degrees" % args.bend)
         scene.set_skin(*bend_rig(mesh), n_bones=2)
         scene.set_bone_palette(bend_palette(T, args.bend))
+    args.with_scene = None
+    if args.with_path:
+        say("second model from: %s/model.obj ('%s' shader pipeline, at %s)" % (args.with_path, args.with_shader or args.pipeline,
+                                                                              args.with_offset))
+        mesh2, texs2 = T.load_assets(args.with_path)
+        # (both scenes store their depth: the merge reads it -- include/tiny_renderer.h, tr_scene_composite)
+        args.with_scene = T.Scene(scene.width, scene.height, mesh2, texs2, args.with_shader or args.pipeline, device=args.device,
+                                  store_depth=True, instances=np.array([args.with_offset + [1.0]], np.float32))
     rc = _run(args, T, scene, sharded, rank, say)
     if sharded:
         import torch.distributed as dist
@@ -237,6 +258,15 @@ def _run(args, T, scene, sharded, rank, say):
         scene.set_light_direction([float(np.sin(la)), 0.0, float(np.cos(la))])   # app.rs:203-208
         scene.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])  # app.rs:200-209
         scene.render()                                                       # app.rs:210
+    if args.with_scene is not None:
+        # the second model under the last frame's camera and light, merged into the picture before it is read
+        ca = np.float32(args.camera_angle + (2.0 * np.pi * (args.frames - 1) / args.frames if args.frames > 1 else 0.0))
+        other = args.with_scene
+        other.clear()
+        other.set_light_direction([float(np.sin(la)), 0.0, float(np.cos(la))])
+        other.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
+        other.render()
+        scene.composite(other)
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include "tr_composite.h"
 #include "tr_morph.h"
 #include "tr_skin.h"
 #include "tr_types.h"
@@ -62,6 +63,9 @@ int launch_push_tiles(const uint8_t *fb, uint8_t *peer, const uint32_t *fb_clean
 // memory): k_resolve.  fb_clean: the target's colour-clean flags (tiles not read, stored as zeros) or null.
 int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, const DevFrame &frame, uint32_t factor,
                    hipStream_t st);
+// Depth compositing: src's frame into dst's over the tiles of dst's band, by the rule of tr_composite.h and through both
+// scenes' fast-clear flags: k_composite.  The caller orders the launch behind the work that produced both frames.
+int launch_composite(const CompositeArgs &a, hipStream_t st);
 // Morph targets: the posed rows of n_frames frames (<= MORPH_MAX_FRAMES) by one launch -- frame f blends the mesh's
 // gathered rows `base` (n_rows x TRI_FLOATS) with the gathered delta rows `delta` (n_targets x n_rows x TRI_FLOATS) under
 // the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.

@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "tr_composite.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
 #include "tr_plan.h"
@@ -1811,6 +1812,137 @@ __global__ __launch_bounds__(64) void k_resolve(const uint8_t *__restrict__ fb, 
     }
 }
 
+// Depth compositing (tr_scene_composite): scene src's current frame merged into scene dst's by the reference's depth
+// test (tr_composite.h has the rule).  One workgroup per 128 x 16 tile of dst's band, the tiles of k_read_back and
+// k_resolve; a lane owns 16 pixels of a row -- four 16-byte pieces of z, three of colour, four of winner words -- and
+// lanes run along the row first.
+//   * src's z flag up: nothing of src is drawn in the tile (its z memory means nothing) -- the workgroup leaves having
+//     loaded one word, before any barrier (three quarters of a frame of the reference's model);
+//   * dst's z flag up: every zd is f32::MIN, dst's z memory is not read;
+//   * the only barrier is the workgroup's vote "did any pixel win" (it also separates every lane's load of dst's z
+//     flag from lane 0's store to it).  No winner: dst's memory and flags are untouched;
+//   * otherwise lanes with a winning pixel load src's and dst's colour pieces, merge the winning pixels' bytes into
+//     what they read and store the pieces back, and store the merged z (and winner words); if dst's z flag was up
+//     EVERY lane inside the band and the width stores its z -- the rest of the tile as f32::MIN, as
+//     k_materialize_depth would -- and the flag comes down; dst's colour-clean flag comes down.
+// dst's colour needs no such care: a colour-clean tile holds real zeros.  Bytes per pixel of a tile that is read:
+// 4 + 4 + 3 + 3 read, up to 4 + 3 written (8 more each way with winner taps).
+// WIDE: width % 16 == 0 and every buffer 16-byte aligned (the launcher checks); otherwise the same shares through
+// element loads and stores guarded by the width, which also serve the last columns of a width that is not a
+// multiple of 16.  No LDS beyond the vote, no atomics, no scratch.
+template <bool WIDE>
+__global__ __launch_bounds__(8 * TILE_H) void k_composite(CompositeArgs a)
+{
+    static_assert(TILE_W == 128, "a row of a tile is eight shares of 16 pixels");
+    const uint32_t t = blockIdx.x;
+    if (a.src_zclean[t] != 0u) return;  // (workgroup-uniform, ahead of the barrier)
+    const bool dz_clean = a.dst_zclean[t] != 0u;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t x = (int32_t)(t % a.frame.ntx) * TILE_W + (int32_t)(threadIdx.x % 8u) * 16;
+    const int32_t y = (a.frame.ty_base + (int32_t)(t / a.frame.ntx)) * TILE_H + (int32_t)(threadIdx.x / 8u);
+    const bool inside = x < W && y >= a.frame.band_y0 && y < a.frame.band_y1;
+    const int32_t n_px = inside ? min(16, W - x) : 0;  // pixels of the share (WIDE: 16 or none)
+    const size_t zi = inside ? (size_t)y * (size_t)W + (size_t)x : 0u;
+    float zd[16];
+    uint32_t won = 0u;  // bit i: pixel i of the share takes src's fragment
+    if (inside) {
+        float zs[16];
+        if (WIDE) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const float4 s = reinterpret_cast<const float4 *>(a.src_z + zi)[k];
+                zs[4 * k + 0] = s.x, zs[4 * k + 1] = s.y, zs[4 * k + 2] = s.z, zs[4 * k + 3] = s.w;
+                float4 d = make_float4(bits_f32(TR_F32_MIN_BITS), bits_f32(TR_F32_MIN_BITS), bits_f32(TR_F32_MIN_BITS),
+                                       bits_f32(TR_F32_MIN_BITS));
+                if (!dz_clean) d = reinterpret_cast<const float4 *>(a.dst_z + zi)[k];
+                zd[4 * k + 0] = d.x, zd[4 * k + 1] = d.y, zd[4 * k + 2] = d.z, zd[4 * k + 3] = d.w;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                zs[i] = zd[i] = bits_f32(TR_F32_MIN_BITS);
+                if (i < n_px) {
+                    zs[i] = a.src_z[zi + i];
+                    if (!dz_clean) zd[i] = a.dst_z[zi + i];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (composite_wins(zs[i], zd[i])) {
+                won |= 1u << i;
+                zd[i] = zs[i];
+            }
+    }
+    if (__syncthreads_or((int)won) == 0) return;  // nothing of the tile changes
+    if (threadIdx.x == 0u) {
+        a.dst_fbclean[t] = 0u;
+        if (dz_clean) a.dst_zclean[t] = 0u;
+    }
+    if (!inside) return;
+    if (won != 0u || dz_clean) {  // the merged z: the winners', and a materialised tile's every pixel
+        if (WIDE) {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                reinterpret_cast<float4 *>(a.dst_z + zi)[k] = make_float4(zd[4 * k], zd[4 * k + 1], zd[4 * k + 2], zd[4 * k + 3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                if (i < n_px && (dz_clean || ((won >> i) & 1u))) a.dst_z[zi + i] = zd[i];
+        }
+    }
+    if (won == 0u) return;
+    const size_t ci = ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+    if (WIDE) {
+        uint32_t s[12], d[12];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const uint4 u = reinterpret_cast<const uint4 *>(a.src_fb + ci)[k];
+            const uint4 v = reinterpret_cast<const uint4 *>(a.dst_fb + ci)[k];
+            s[4 * k + 0] = u.x, s[4 * k + 1] = u.y, s[4 * k + 2] = u.z, s[4 * k + 3] = u.w;
+            d[4 * k + 0] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+        }
+        // byte b of the share belongs to pixel b / 3: a mask per word from the pixels' bits
+#pragma unroll
+        for (int w = 0; w < 12; w++) {
+            uint32_t m = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; b++)
+                if ((won >> ((4 * w + b) / 3)) & 1u) m |= 0xFFu << (8 * b);
+            d[w] = (d[w] & ~m) | (s[w] & m);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            reinterpret_cast<uint4 *>(a.dst_fb + ci)[k] = make_uint4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (i < n_px && ((won >> i) & 1u)) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) a.dst_fb[ci + 3 * i + c] = a.src_fb[ci + 3 * i + c];
+            }
+    }
+    if (a.dst_winner != nullptr) {
+        if (WIDE) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (((won >> (4 * k)) & 0xFu) == 0u) continue;
+                const uint4 u = reinterpret_cast<const uint4 *>(a.src_winner + zi)[k];
+                uint4 v = reinterpret_cast<const uint4 *>(a.dst_winner + zi)[k];
+                if ((won >> (4 * k + 0)) & 1u) v.x = composite_winner(u.x, a.winner_base);
+                if ((won >> (4 * k + 1)) & 1u) v.y = composite_winner(u.y, a.winner_base);
+                if ((won >> (4 * k + 2)) & 1u) v.z = composite_winner(u.z, a.winner_base);
+                if ((won >> (4 * k + 3)) & 1u) v.w = composite_winner(u.w, a.winner_base);
+                reinterpret_cast<uint4 *>(a.dst_winner + zi)[k] = v;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; i++)
+                if (i < n_px && ((won >> i) & 1u)) a.dst_winner[zi + i] = composite_winner(a.src_winner[zi + i], a.winner_base);
+        }
+    }
+}
+
 // Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
 // mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
 // pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
@@ -2381,6 +2513,25 @@ int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, co
     if (factor == 2u) return launch_resolve_f<2>(fb, out, fb_clean, frame, wide, st);
     if (factor == 4u) return launch_resolve_f<4>(fb, out, fb_clean, frame, wide, st);
     return launch_resolve_f<8>(fb, out, fb_clean, frame, wide, st);
+}
+
+int launch_composite(const CompositeArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.dst_z || !a.dst_fb || !a.dst_zclean || !a.dst_fbclean || !a.src_z || !a.src_fb || !a.src_zclean ||
+        (a.dst_winner && !a.src_winner))
+        return (int)hipErrorInvalidValue;
+    // the wide path: every share is whole 16-byte pieces of z, colour and winner words
+    const uintptr_t all = (uintptr_t)a.dst_z | (uintptr_t)a.dst_fb | (uintptr_t)a.dst_winner | (uintptr_t)a.src_z |
+                          (uintptr_t)a.src_fb | (uintptr_t)(a.dst_winner ? a.src_winner : nullptr);
+    const bool wide = a.frame.width % 16u == 0u && all % 16u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_composite<true>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_composite<false>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
 }
 
 int launch_morph(const float *base, const float *delta, uint32_t n_rows, uint32_t n_targets, const MorphTable &tab, uint32_t n_frames,

@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -270,6 +270,10 @@ struct tr_scene {
     bool two_setup_streams = true;
     hipEvent_t ev_setup[RING] = {};
     hipEvent_t ev_tile[RING] = {};
+    // tr_scene_composite orders two scenes' streams: as src, `ev_comp_ready` is recorded behind the frame on this scene's
+    // stream and dst's stream waits for it; as dst, `ev_comp_done` is recorded behind k_composite and src's stream waits
+    // for it (created at the first such call; each scene records only its own, so destroying one leaves the other's alone)
+    hipEvent_t ev_comp_ready = nullptr, ev_comp_done = nullptr;
     uint64_t pass_seq = 0;
     struct PendingTile {
         int fs, tile_waves, shared, kernel_id;
@@ -2400,6 +2404,8 @@ void destroy(tr_scene *s)
         if (s->ev_setup[k]) (void)hipEventDestroy(s->ev_setup[k]);
         if (s->ev_tile[k]) (void)hipEventDestroy(s->ev_tile[k]);
     }
+    if (s->ev_comp_ready) (void)hipEventDestroy(s->ev_comp_ready);
+    if (s->ev_comp_done) (void)hipEventDestroy(s->ev_comp_done);
     if (s->setup_stream) (void)hipStreamDestroy(s->setup_stream);
     if (s->setup_stream2) (void)hipStreamDestroy(s->setup_stream2);
     for (tr_scene::BinState *b : { &s->bin_color, &s->bin_depth }) {
@@ -3467,6 +3473,82 @@ int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb)
     st = enqueue_resolve(s, factor, s->d_resolved);
     if (st != TR_OK) return st;
     return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base)
+{
+    if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_scene_composite: null scene");
+    if (dst == src) return tr::fail(TR_E_INVALID, "tr_scene_composite: dst and src are the same scene");
+    if (dst->device != src->device) return tr::fail(TR_E_INVALID, "tr_scene_composite: the scenes are on different devices");
+    if (dst->width != src->width || dst->height != src->height)
+        return tr::fail(TR_E_INVALID, "tr_scene_composite: the scenes' frames differ in width or height");
+    if (dst->frame.band_y0 != src->frame.band_y0 || dst->frame.band_y1 != src->frame.band_y1)
+        return tr::fail(TR_E_INVALID, "tr_scene_composite: the scenes render different bands (tr_options.band_row0/1)");
+    if (dst->d_winner && !src->d_winner)
+        return tr::fail(TR_E_INVALID, "tr_scene_composite: dst has TR_OPT_WINNER_TAP and src has not");
+    if (dst->broken || src->broken)
+        return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(dst->device));
+    if (src->z_fb_cleared) return TR_OK;  // a logically cleared frame covers no pixel
+    // src: the frame on its way, its depth in memory behind valid flags
+    int st = submit_pending(src);
+    if (st == TR_OK) st = ensure_depth(src);
+    if (st == TR_OK) st = need_z(src, src->cur_slot);
+    // dst: the same, and a pending clear made real (its z: every flag up)
+    if (st == TR_OK) st = submit_pending(dst);
+    if (st == TR_OK && !dst->z_fb_cleared) st = ensure_depth(dst);
+    if (st == TR_OK) st = flush_clear_color(dst);
+    if (st == TR_OK) st = need_z(dst, dst->cur_slot);
+    if (st != TR_OK) return st;
+    if (!src->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&src->ev_comp_ready, hipEventDisableTiming));
+    if (!dst->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&dst->ev_comp_done, hipEventDisableTiming));
+    CompositeArgs a = {};
+    a.dst_z = dst->d_z;
+    a.dst_fb = dst->d_fb;
+    a.dst_winner = dst->d_winner;
+    a.dst_zclean = dst->d_zclean;
+    a.dst_fbclean = dst->d_fbclean;
+    a.src_z = src->d_z;
+    a.src_fb = src->d_fb;
+    a.src_winner = src->d_winner;
+    // (src's colour-clean flags say less than its z flags -- a set belongs to one colour buffer and is forgotten when a
+    // caller's buffer is handed over again or the winner tap was last written with another target's frame
+    // (select_fb_flags), while the z flags always describe the slot's depth: the skip goes by the z flags alone)
+    a.src_zclean = src->d_zclean;
+    a.frame = dst->frame;
+    a.winner_base = winner_base;
+    // behind src's frame on dst's stream; src's stream behind the merge: a later render of src does not overtake it
+    HIP_TRY(hipEventRecord(src->ev_comp_ready, src->stream));
+    HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_comp_ready, 0));
+    {
+        Timed t(dst, K_COMPOSITE);
+        int rc = launch_composite(a, dst->stream);
+        if (rc) return launch_status(rc, "k_composite");
+    }
+    HIP_TRY(hipEventRecord(dst->ev_comp_done, dst->stream));
+    HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_comp_done, 0));
+    dst->slots[(size_t)dst->cur_slot].z_deferred = false;  // (the merged depth is in memory)
+    dst->quiescent = src->quiescent = false;
+    // both frames are now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering one of them again
+    // after a bin overflow would undo the merge, or change what it read
+    dst->observed_seq = dst->pass_seq;
+    src->observed_seq = src->pass_seq;
+    return TR_OK;
+}
+
+// The rule of tr_composite.h over caller's arrays, on the host.  Needs no GPU.
+int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t *win_dst, const float *z_src, const uint8_t *rgb_src,
+                      const uint32_t *win_src, uint32_t winner_base)
+{
+    if (n_pixels && (!z_dst || !rgb_dst || !z_src || !rgb_src)) return tr::fail(TR_E_INVALID, "tr_composite_host: null argument");
+    if (n_pixels && win_dst && !win_src) return tr::fail(TR_E_INVALID, "tr_composite_host: win_dst without win_src");
+    for (size_t i = 0; i < n_pixels; i++) {
+        if (!composite_wins(z_src[i], z_dst[i])) continue;
+        z_dst[i] = z_src[i];
+        memcpy(rgb_dst + 3 * i, rgb_src + 3 * i, 3);
+        if (win_dst) win_dst[i] = composite_winner(win_src[i], winner_base);
+    }
+    return TR_OK;
 }
 
 int tr_scene_band_tiles(tr_scene *s, const void *frame_buffer_device, tr_band_tiles *out)

@@ -149,6 +149,31 @@ def skin_mesh(mesh, bones, weights, palette):
     return dict(mesh, pos=pos, nrm=nrm, idx=idx)
 
 
+def composite_host(z_dst, rgb_dst, z_src, rgb_src, win_dst=None, win_src=None, winner_base=0):
+    """tr_composite_host: the rule of Scene.composite on the host (no GPU needed), by the inline function k_composite
+    calls.  z [..] float32, rgb [.., 3] uint8 and optional winner words [..] uint32, all in one pixel order; src wins a
+    pixel where it is covered (z bits != f32::MIN) and not (zs <= zd).  Returns new (z, rgb) -- or (z, rgb, winner) with
+    win_dst -- and leaves its arguments alone."""
+    z = np.array(z_dst, np.float32, order="C")
+    rgb = np.array(rgb_dst, np.uint8, order="C")
+    zs = np.ascontiguousarray(z_src, np.float32)
+    rs = np.ascontiguousarray(rgb_src, np.uint8)
+    if zs.shape != z.shape or rgb.shape != z.shape + (3,) or rs.shape != rgb.shape:
+        raise ValueError("composite_host: z arrays of one shape, rgb arrays of that shape + (3,)")
+    win = ws = None
+    if win_dst is not None:
+        if win_src is None:
+            raise ValueError("composite_host: win_dst needs win_src")
+        win = np.array(win_dst, np.uint32, order="C")
+        ws = np.ascontiguousarray(win_src, np.uint32)
+        if win.shape != z.shape or ws.shape != z.shape:
+            raise ValueError("composite_host: winner arrays must have the shape of z")
+    check(load_library().tr_composite_host(z.size, z.ctypes.data, rgb.ctypes.data, win.ctypes.data if win is not None else None,
+                                           zs.ctypes.data, rs.ctypes.data, ws.ctypes.data if ws is not None else None,
+                                           int(winner_base) & 0xFFFFFFFF))
+    return (z, rgb) if win is None else (z, rgb, win)
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -472,6 +497,19 @@ class Scene:
             ptr = int(target) if target is not None else None
         check(load_library().tr_scene_resolve(self._h, int(factor), ptr))
         return target
+
+    def composite(self, src, winner_base=0):
+        """tr_scene_composite: merges the current frame of scene `src` into this scene's on the device -- src wins a
+        pixel where it drew one and is strictly nearer (the reference's depth test; ties keep this scene's pixel), taking
+        colour, z and, with winner taps, src's winner + winner_base.  Asynchronous; both scenes must have the same size
+        and band, and be on one device.  store_depth=True on both scenes avoids the depth-only repeat of their passes."""
+        if src is self:
+            raise ValueError("composite: src is this scene")
+        if not isinstance(src, Scene):
+            raise ValueError("composite: src must be a Scene")
+        if (src.width, src.height) != (self.width, self.height):
+            raise ValueError("composite: src is %d x %d, this scene %d x %d" % (src.width, src.height, self.width, self.height))
+        check(load_library().tr_scene_composite(self._h, src._h, int(winner_base) & 0xFFFFFFFF))
 
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
