@@ -436,6 +436,59 @@ int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t 
                       const float *z_src, const uint8_t *rgb_src, const uint32_t *win_src /* or NULL */,
                       uint32_t winner_base);
 
+/* Screen-space ambient occlusion (upstream has only the light-space `occlusion` pipeline, shader.rs:806-960, which
+ * costs a second geometry pass and replaces the picture by a grey one): the scene's CURRENT frame is darkened in place,
+ * on the device, from its own z buffer -- contact shadows and creases, for a frame of any pipeline and for a merged
+ * frame of two scenes (tr_scene_composite), at no geometry work.  The rule is the reference's occlusion closure
+ * (shader.rs:916-944) moved from the shadow buffer to the z buffer and from world-space steps to pixel offsets:
+ *   samples : ring k = 1..rings has radius r_k = (radius * k) / rings (integer division); sample i = 0..15 of a ring has
+ *             the offset dx = round(r_k * sin(2 pi i / 16)), dy = round(r_k * cos(2 pi i / 16)) -- f32 products of the
+ *             sixteen f32 sines, rounded half away from zero; duplicate offsets at small radii are kept and counted;
+ *   pixel   : with z0 its z value (what tr_scene_read_z_f32 returns): bits(z0) == bits(f32::MIN) -- not drawn -- stays
+ *             untouched.  Otherwise n = 16 * rings, inv_n = 1 / n, coef = 1, and for every ring, every sample, in order:
+ *                 zq = z at (x + dx, y + dy); outside the frame or on a pixel not drawn: f32::MIN
+ *                 if zq - threshold > z0:  s = min((zq - z0) / falloff, 1)  (a NaN s gives 1);  coef = coef - inv_n * s
+ *             and every colour channel c becomes (coef * c + (1 - coef) * 0.0) as u8 (saturating); with TR_AO_GREY c is
+ *             255 in all three channels: the reference's color_blend(white, black, coef).
+ * Every f32 operation rounds once, nothing is fused; a comparison with a NaN is false, so a NaN z0 or zq occludes
+ * nothing.  z, the winner words and the shadow buffer are never written. */
+#define TR_AO_MAX_RADIUS 16
+#define TR_AO_MAX_RINGS 4
+#define TR_AO_GREY 0x1u
+typedef struct tr_ao_params {
+    uint32_t struct_size;   /* = sizeof(tr_ao_params) */
+    uint32_t radius;        /* pixels, 1..TR_AO_MAX_RADIUS */
+    uint32_t rings;         /* 1..TR_AO_MAX_RINGS, rings <= radius */
+    uint32_t flags;         /* TR_AO_GREY or 0 */
+    float threshold;        /* the reference's 1.0; finite, >= 0 */
+    float falloff;          /* the reference's 20.0; finite, > 0 */
+} tr_ao_params;
+/* Shades the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device -- IN PLACE: every later consumer (the getters,
+ * tr_scene_resolve, the sparse read-back, tr_scene_composite in either role, an exchange) sees the shaded frame.
+ * Calling it twice shades twice.  Frames tr_scene_render holds back are submitted and the frame's depth, if it was left
+ * on the chip (see TR_OPT_STORE_DEPTH), is fetched by the depth-only repeat of its pass first.  A scene that is
+ * logically cleared (tr_scene_clear and nothing rendered since) has no drawn pixel: TR_OK, nothing happens.
+ * Asynchronous: k_ao is enqueued on the scene's stream, a later render is ordered behind it, the result is there after
+ * tr_scene_sync.  The scene's passes issued so far count as handed on, as after tr_scene_get_frame_buffer_async: a
+ * frame shaded in place is not rendered again behind the caller's back (a bin overflow among them is reported,
+ * TR_E_BIN_OVERFLOW).  Tiles (128 x 16) in which nothing is drawn are skipped on the fast-clear flags without reading
+ * a pixel.  Without TR_AO_GREY a tile whose colour is the cleared value keeps it; with it every tile that holds a
+ * drawn pixel counts as written.
+ * TR_E_INVALID, nothing changed and nothing queued: a NULL argument, a wrong struct_size, a radius or ring count out of
+ * range or rings > radius, a threshold that is not finite or negative, a falloff that is not finite or not positive,
+ * unknown flag bits, and a BAND scene (tr_options.band_row0/1 set): the samples at a band's border lie in rows another
+ * rank owns, and exchanging such a halo between ranks is deliberately not part of this call -- shade the gathered
+ * frame with a scene of the whole frame, or on the host. */
+int tr_scene_ambient_occlusion(tr_scene *s, const tr_ao_params *p);
+/* The rule above on the host (no GPU needed), by the very inline functions k_ao calls.  z: width * height floats, index
+ * x + y * width, y up (tr_scene_read_z_f32); rgb: the frame as tr_scene_get_frame_buffer returns it, row 0 = top,
+ * shaded in place.  The same parameter checks; width or height 0: TR_OK, nothing to do. */
+int tr_ao_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up */,
+               uint8_t *rgb /* row 0 = top, in place */, const tr_ao_params *p);
+/* The sample table of a call: 16 * rings pairs {dx, dy} in the rule's order (dxdy: 2 * 16 * rings values). */
+int tr_ao_offsets(uint32_t radius, uint32_t rings, int8_t *dxdy);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

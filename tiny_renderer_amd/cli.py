@@ -56,7 +56,18 @@ def main(argv=None):
                          "and light -- and merged into the picture by depth on the GPU (Scene.composite)")
     ap.add_argument("--with-shader", default=None, metavar="PIPELINE", help="shader pipeline of the --with model (default: -s)")
     ap.add_argument("--with-offset", default="0,0,0", metavar="X,Y,Z", help="where the --with model stands (an instance offset)")
+    ap.add_argument("--ao", type=int, default=0, metavar="RADIUS",
+                    help="screen-space ambient occlusion: darken the picture from its own z buffer on the GPU, samples on "
+                         "rings of up to RADIUS (1..16) pixels (Scene.ambient_occlusion; after --with, before --ssaa resolves)")
+    ap.add_argument("--ao-rings", type=int, default=1, metavar="N", help="rings of sixteen samples (1..4, at most RADIUS)")
+    ap.add_argument("--ao-grey", action="store_true", help="with --ao: the occlusion alone, white darkened to black")
     args = ap.parse_args(argv)
+    if (args.ao_rings != 1 or args.ao_grey) and not args.ao:
+        ap.error("--ao-rings and --ao-grey go with --ao RADIUS")
+    if args.ao and (args.gpus > 1 or args.seconds > 0 or args.view != "frame"):
+        ap.error("--ao shades the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+    if args.ao and not (1 <= args.ao <= 16 and 1 <= args.ao_rings <= min(4, args.ao)):
+        ap.error("--ao takes a radius of 1..16 pixels, --ao-rings 1..4 and at most the radius")
     if args.with_path and (args.gpus > 1 or args.seconds > 0):
         ap.error("--with merges two scenes of one GPU, by frame count: use --gpus 1 and --frames")
     if args.with_path:
@@ -267,6 +278,8 @@ def _run(args, T, scene, sharded, rank, say):
         other.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
         other.render()
         scene.composite(other)
+    if args.ao:
+        scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

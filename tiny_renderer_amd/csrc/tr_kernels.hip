@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
@@ -1943,6 +1944,151 @@ __global__ __launch_bounds__(8 * TILE_H) void k_composite(CompositeArgs a)
     }
 }
 
+// Screen-space ambient occlusion (tr_scene_ambient_occlusion): the frame's colour darkened in place from its own z
+// buffer (tr_ao.h has the rule).  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_composite.
+//   * the tile's own z flag up: nothing is drawn there -- the workgroup leaves having loaded one word, before any barrier;
+//   * staging: the tile's z and a halo of `radius` pixels go to LDS, as rows of 160 floats that start 16 pixels left of
+//     the tile, so that every 16-byte piece of a row is aligned in memory and lies in ONE tile: a piece in a tile whose z
+//     flag is up (its z memory is stale), or outside the frame, is filled with f32::MIN without a load.  The nine flags
+//     are workgroup-uniform: scalar loads, one bit each.  At most 48 rows: 30 KB;
+//   * samples: a lane owns one column of the tile and eight of its rows; lanes run along the row, so the 64 reads of a
+//     sample hit 64 consecutive words of LDS.  The offset of a sample is uniform (the table is a kernel argument), the
+//     eight rows are immediate offsets from it.  A pixel's samples are taken in the rule's order;
+//   * the coefficients go through 8 KB of LDS to the colour shares of k_composite -- a lane owns 16 pixels of a row,
+//     three 16-byte pieces -- behind the only other barrier, which is also the vote "is any pixel of the tile drawn";
+//     no: the workgroup leaves.  A lane loads, blends and stores its pieces only if a pixel of its share changes (a
+//     drawn pixel whose coefficient is 1 keeps its bytes: 1 * c + 0 * 0 = c);
+//   * TR_AO_GREY: drawn pixels become coef * 255 whatever they held, so the tile's colour-clean flag comes down (lane 0,
+//     behind the barrier).  Without it zeros blend to zeros and no flag changes.
+// z and the flags of z are only read.  WIDE: width % 16 == 0 and both buffers 16-byte aligned (the launcher checks);
+// otherwise the same through element accesses guarded by the width.  No atomics, no scratch.
+constexpr int AO_LDS_W = TILE_W + 2 * AO_MAX_RADIUS, AO_LDS_H = TILE_H + 2 * AO_MAX_RADIUS;
+constexpr int AO_THREADS = 256, AO_ROWS = TILE_W * TILE_H / AO_THREADS;  // rows of its column a lane owns
+constexpr float AO_NOT_DRAWN = 2.0f;  // (in place of a coefficient, which never exceeds 1)
+template <bool WIDE>
+__global__ __launch_bounds__(AO_THREADS) void k_ao(AoArgs a)
+{
+    static_assert(TILE_W == 128 && AO_MAX_RADIUS == 16 && AO_MAX_RADIUS <= TILE_H, "the halo lies in the eight tiles around");
+    const uint32_t t = blockIdx.x;
+    if (a.zclean[t] != 0u) return;  // (workgroup-uniform, ahead of the barriers)
+    __shared__ float s_z[AO_LDS_H * AO_LDS_W];
+    __shared__ float s_coef[TILE_H * TILE_W];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, R = (int32_t)a.radius;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t tx = (int32_t)t % ntx, ty = (int32_t)t / ntx;
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax: the tile at (tx + ax - 1, ty + ay - 1) reads as f32::MIN -- flag up, or no such tile
+    uint32_t stale = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            bool up = nx < 0 || nx >= ntx || ny < 0 || ny >= nty;
+            if (!up) up = a.zclean[ny * ntx + nx] != 0u;
+            if (up) stale |= 1u << (3 * ay + ax);
+        }
+    const int32_t rows = TILE_H + 2 * R;  // LDS row r is frame row y0 - R + r, LDS column c frame column x0 - 16 + c
+    const float z_min = bits_f32(TR_F32_MIN_BITS);
+    if (WIDE) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (AO_LDS_W / 4); p += AO_THREADS) {
+            const int32_t r = p / (AO_LDS_W / 4), j = p % (AO_LDS_W / 4);
+            if (4 * j + 3 < 16 - R || 4 * j >= 16 + TILE_W + R) continue;  // (no sample reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - R + r;
+            const int32_t ax = j < 4 ? 0 : j < 4 + TILE_W / 4 ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            float4 v = make_float4(z_min, z_min, z_min, z_min);
+            if (((stale >> (3 * ay + ax)) & 1u) == 0u && x < W && y < H)
+                v = *reinterpret_cast<const float4 *>(a.z + (size_t)y * (size_t)W + (size_t)x);
+            *reinterpret_cast<float4 *>(&s_z[r * AO_LDS_W + 4 * j]) = v;
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * AO_LDS_W; p += AO_THREADS) {
+            const int32_t r = p / AO_LDS_W, c = p % AO_LDS_W;
+            if (c < 16 - R || c >= 16 + TILE_W + R) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - R + r;
+            const int32_t ax = c < 16 ? 0 : c < 16 + TILE_W ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            float v = z_min;
+            if (((stale >> (3 * ay + ax)) & 1u) == 0u && x < W && y < H) v = a.z[(size_t)y * (size_t)W + (size_t)x];
+            s_z[r * AO_LDS_W + c] = v;
+        }
+    }
+    __syncthreads();
+    // samples: column `col`, rows row0 .. row0 + AO_ROWS - 1 of the tile
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, row0 = (int32_t)threadIdx.x / TILE_W * AO_ROWS;
+    const float *own = s_z + (R + row0) * AO_LDS_W + 16 + col;
+    float z0[AO_ROWS], coef[AO_ROWS];
+    uint32_t drawn = 0u;
+#pragma unroll
+    for (int k = 0; k < AO_ROWS; k++) {
+        z0[k] = own[k * AO_LDS_W];
+        coef[k] = 1.0f;
+        if (ao_drawn(z0[k])) drawn |= 1u << k;
+    }
+    if (drawn != 0u)
+        for (uint32_t i = 0; i < a.n_taps; i++) {
+            const int32_t off = (int32_t)a.taps.d[i][1] * AO_LDS_W + (int32_t)a.taps.d[i][0];
+#pragma unroll
+            for (int k = 0; k < AO_ROWS; k++)
+                if ((drawn >> k) & 1u) coef[k] = ao_sample(coef[k], z0[k], own[off + k * AO_LDS_W], a.rule);
+        }
+#pragma unroll
+    for (int k = 0; k < AO_ROWS; k++) s_coef[(row0 + k) * TILE_W + col] = ((drawn >> k) & 1u) ? coef[k] : AO_NOT_DRAWN;
+    if (__syncthreads_or((int)drawn) == 0) return;  // nothing of the tile is drawn
+    const bool grey = a.grey != 0u;
+    if (grey && threadIdx.x == 0u) a.fbclean[t] = 0u;
+    // colour: the shares of k_composite
+    if (threadIdx.x >= 8u * TILE_H) return;
+    const int32_t x = x0 + (int32_t)(threadIdx.x % 8u) * 16, row = (int32_t)(threadIdx.x / 8u), y = y0 + row;
+    if (x >= W || y >= H) return;
+    const int32_t n_px = min(16, W - x);  // (WIDE: 16)
+    float cf[16];
+    uint32_t is_drawn = 0u, changes = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float4 v = *reinterpret_cast<const float4 *>(&s_coef[row * TILE_W + (x - x0) + 4 * k]);
+        cf[4 * k + 0] = v.x, cf[4 * k + 1] = v.y, cf[4 * k + 2] = v.z, cf[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        if (cf[i] != AO_NOT_DRAWN) {
+            is_drawn |= 1u << i;
+            if (grey || cf[i] != 1.0f) changes |= 1u << i;
+        } else {
+            cf[i] = 1.0f;  // (keeps every byte)
+        }
+    }
+    if (changes == 0u) return;
+    const size_t ci = ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+    if (WIDE) {
+        uint32_t w[12];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const uint4 u = reinterpret_cast<const uint4 *>(a.fb + ci)[k];
+            w[4 * k + 0] = u.x, w[4 * k + 1] = u.y, w[4 * k + 2] = u.z, w[4 * k + 3] = u.w;
+        }
+        // byte b of the share is channel b % 3 of pixel b / 3
+#pragma unroll
+        for (int b = 0; b < 48; b++) {
+            const int i = b / 3, sh = 8 * (b % 4);
+            const uint32_t c = (grey && ((is_drawn >> i) & 1u)) ? 255u : (w[b / 4] >> sh) & 0xFFu;
+            w[b / 4] = (w[b / 4] & ~(0xFFu << sh)) | (ao_channel(c, cf[i]) << sh);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            reinterpret_cast<uint4 *>(a.fb + ci)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (i < n_px && ((changes >> i) & 1u)) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) {
+                    const uint32_t c = grey ? 255u : (uint32_t)a.fb[ci + 3 * i + ch];
+                    a.fb[ci + 3 * i + ch] = (uint8_t)ao_channel(c, cf[i]);
+                }
+            }
+    }
+}
+
 // Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
 // mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
 // pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
@@ -2530,6 +2676,27 @@ int launch_composite(const CompositeArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_composite<true>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
     else
         hipLaunchKernelGGL((k_composite<false>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_ao(const AoArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.z || !a.zclean || !a.fb || !a.fbclean) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), samples inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.radius == 0u || a.radius > (uint32_t)AO_MAX_RADIUS || a.n_taps > (uint32_t)(AO_MAX_RINGS * AO_RING))
+        return (int)hipErrorInvalidValue;
+    for (uint32_t i = 0; i < a.n_taps; i++)
+        if (abs((int)a.taps.d[i][0]) > (int)a.radius || abs((int)a.taps.d[i][1]) > (int)a.radius) return (int)hipErrorInvalidValue;
+    // the wide path: every share is whole 16-byte pieces of z and colour
+    const bool wide = a.frame.width % 16u == 0u && ((uintptr_t)a.z | (uintptr_t)a.fb) % 16u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_ao<true>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_ao<false>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

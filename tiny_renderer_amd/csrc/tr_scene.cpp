@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -3548,6 +3548,92 @@ int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t 
         memcpy(rgb_dst + 3 * i, rgb_src + 3 * i, 3);
         if (win_dst) win_dst[i] = composite_winner(win_src[i], winner_base);
     }
+    return TR_OK;
+}
+
+namespace {
+
+// tr_ao_params as both entry points accept them (`who` names the entry point in the error text).
+int check_ao_params(const tr_ao_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_ao_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_ao_params)");
+    if (p->radius < 1u || p->radius > (uint32_t)TR_AO_MAX_RADIUS)
+        return tr::fail(TR_E_INVALID, w + ": radius must be 1..TR_AO_MAX_RADIUS");
+    if (p->rings < 1u || p->rings > (uint32_t)TR_AO_MAX_RINGS || p->rings > p->radius)
+        return tr::fail(TR_E_INVALID, w + ": rings must be 1..TR_AO_MAX_RINGS and at most the radius");
+    if (p->flags & ~TR_AO_GREY) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0f) return tr::fail(TR_E_INVALID, w + ": threshold must be finite and >= 0");
+    if (!std::isfinite(p->falloff) || !(p->falloff > 0.0f)) return tr::fail(TR_E_INVALID, w + ": falloff must be finite and > 0");
+    return TR_OK;
+}
+
+}  // namespace
+
+static_assert(TR_AO_MAX_RADIUS == AO_MAX_RADIUS && TR_AO_MAX_RINGS == AO_MAX_RINGS && TR_AO_GREY == AO_GREY, "tr_ao.h restates the header");
+
+int tr_scene_ambient_occlusion(tr_scene *s, const tr_ao_params *p)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_ambient_occlusion: null scene");
+    int st = check_ao_params(p, "tr_scene_ambient_occlusion");
+    if (st != TR_OK) return st;
+    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+        return tr::fail(TR_E_INVALID, "tr_scene_ambient_occlusion: a band scene (tr_options.band_row0/1) cannot be shaded: "
+                                      "its border samples lie in another rank's rows");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->z_fb_cleared) return TR_OK;  // a logically cleared frame has no drawn pixel
+    // the frame on its way, its depth in memory behind valid flags
+    st = submit_pending(s);
+    if (st == TR_OK) st = ensure_depth(s);
+    if (st == TR_OK) st = need_z(s, s->cur_slot);
+    if (st != TR_OK) return st;
+    AoArgs a = {};
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.frame = s->frame;
+    a.radius = p->radius;
+    a.n_taps = (uint32_t)AO_RING * p->rings;
+    a.grey = (p->flags & TR_AO_GREY) ? 1u : 0u;
+    a.rule = ao_rule(p->threshold, p->falloff, p->rings);
+    ao_offsets(p->radius, p->rings, a.taps);
+    {
+        Timed t(s, K_AO);
+        int rc = launch_ao(a, s->stream);
+        if (rc) return launch_status(rc, "k_ao");
+    }
+    // (TR_AO_GREY lowers colour-clean flags of the DEVICE buffer; a record of a page-locked host buffer (HostFlags) says
+    // what that host buffer holds, which this call does not change: the next read-back compares the two as always)
+    s->quiescent = false;
+    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
+    // overflow would undo the shading
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+// The rule of tr_ao.h over caller's arrays, on the host.  Needs no GPU.
+int tr_ao_host(uint32_t width, uint32_t height, const float *z, uint8_t *rgb, const tr_ao_params *p)
+{
+    int st = check_ao_params(p, "tr_ao_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!z || !rgb) return tr::fail(TR_E_INVALID, "tr_ao_host: null argument");
+    ao_host(width, height, z, rgb, p->radius, p->rings, (p->flags & TR_AO_GREY) != 0u, p->threshold, p->falloff);
+    return TR_OK;
+}
+
+int tr_ao_offsets(uint32_t radius, uint32_t rings, int8_t *dxdy)
+{
+    tr_ao_params p = { (uint32_t)sizeof(tr_ao_params), radius, rings, 0u, 1.0f, 20.0f };
+    int st = check_ao_params(&p, "tr_ao_offsets");
+    if (st != TR_OK) return st;
+    if (!dxdy) return tr::fail(TR_E_INVALID, "tr_ao_offsets: null argument");
+    AoTaps taps;
+    ao_offsets(radius, rings, taps);
+    memcpy(dxdy, taps.d, (size_t)2 * AO_RING * rings);
     return TR_OK;
 }
 

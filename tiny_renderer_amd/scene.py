@@ -174,6 +174,56 @@ def composite_host(z_dst, rgb_dst, z_src, rgb_src, win_dst=None, win_src=None, w
     return (z, rgb) if win is None else (z, rgb, win)
 
 
+AO_MAX_RADIUS, AO_MAX_RINGS = 16, 4   # (TR_AO_MAX_RADIUS, TR_AO_MAX_RINGS)
+
+
+class AoParams(C.Structure):
+    """tr_ao_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("rings", C.c_uint32), ("flags", C.c_uint32),
+                ("threshold", C.c_float), ("falloff", C.c_float)]
+
+
+def ao_params(radius=8, rings=1, threshold=1.0, falloff=20.0, grey=False):
+    """tr_ao_params from the keyword arguments of Scene.ambient_occlusion / ambient_occlusion_host; ValueError for what
+    the library would refuse (include/tiny_renderer.h)."""
+    for name, v in (("radius", radius), ("rings", rings)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("ambient occlusion: %s must be an integer" % name)
+    if not 1 <= radius <= AO_MAX_RADIUS:
+        raise ValueError("ambient occlusion: radius must be 1..%d pixels" % AO_MAX_RADIUS)
+    if not 1 <= rings <= min(AO_MAX_RINGS, radius):
+        raise ValueError("ambient occlusion: rings must be 1..%d and at most the radius" % AO_MAX_RINGS)
+    threshold, falloff = float(threshold), float(falloff)
+    with np.errstate(over="ignore"):   # (as f32: what the library gets)
+        t32, f32 = np.float32(threshold), np.float32(falloff)
+    if not np.isfinite(t32) or t32 < 0.0:
+        raise ValueError("ambient occlusion: threshold must be finite and >= 0")
+    if not np.isfinite(f32) or not f32 > 0.0:
+        raise ValueError("ambient occlusion: falloff must be finite and > 0")
+    return AoParams(C.sizeof(AoParams), int(radius), int(rings), 1 if grey else 0, threshold, falloff)
+
+
+def ambient_occlusion_host(z, rgb, radius=8, rings=1, threshold=1.0, falloff=20.0, grey=False):
+    """tr_ao_host: the rule of Scene.ambient_occlusion on the host (no GPU needed), by the inline functions k_ao calls.
+    z [H, W] float32 with row 0 = bottom (read_z_f32), rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer).  Returns
+    the shaded frame and leaves its arguments alone."""
+    p = ao_params(radius, rings, threshold, falloff, grey)
+    zz = np.ascontiguousarray(z, np.float32)
+    out = np.array(rgb, np.uint8, order="C")
+    if zz.ndim != 2 or out.shape != zz.shape + (3,):
+        raise ValueError("ambient_occlusion_host: z [H, W] and rgb [H, W, 3]")
+    check(load_library().tr_ao_host(zz.shape[1], zz.shape[0], zz.ctypes.data, out.ctypes.data, C.addressof(p)))
+    return out
+
+
+def ao_offsets(radius, rings=1):
+    """tr_ao_offsets: the [16 * rings, 2] int8 sample offsets {dx, dy} of a call, in the rule's order."""
+    ao_params(radius, rings)
+    out = np.zeros((16 * int(rings), 2), np.int8)
+    check(load_library().tr_ao_offsets(int(radius), int(rings), out.ctypes.data))
+    return out
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -510,6 +560,15 @@ class Scene:
         if (src.width, src.height) != (self.width, self.height):
             raise ValueError("composite: src is %d x %d, this scene %d x %d" % (src.width, src.height, self.width, self.height))
         check(load_library().tr_scene_composite(self._h, src._h, int(winner_base) & 0xFFFFFFFF))
+
+    def ambient_occlusion(self, radius=8, rings=1, threshold=1.0, falloff=20.0, grey=False):
+        """tr_scene_ambient_occlusion: darkens the current frame in place on the device from its own z buffer -- `rings`
+        rings of sixteen samples out to `radius` pixels, a sample occludes where it is nearer by more than `threshold`,
+        by (zq - z0) / falloff, at most 1, a sixteenth (per ring) each; grey=True writes the occlusion alone (white to
+        black).  Asynchronous; every later consumer sees the shaded frame, and calling it twice shades twice.  Band
+        scenes are refused.  store_depth=True avoids the depth-only repeat of the frame's pass."""
+        p = ao_params(radius, rings, threshold, falloff, grey)
+        check(load_library().tr_scene_ambient_occlusion(self._h, C.addressof(p)))
 
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
