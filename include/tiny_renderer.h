@@ -489,6 +489,42 @@ int tr_ao_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up 
 /* The sample table of a call: 16 * rings pairs {dx, dy} in the rule's order (dxdy: 2 * 16 * rings values). */
 int tr_ao_offsets(uint32_t radius, uint32_t rings, int8_t *dxdy);
 
+/* Frame accumulation: the last n_frames frames of the last tr_scene_render_frames* call -- F_k, k = 0 .. n_frames - 1, is
+ * the image tr_scene_get_frame_buffer would return after tr_scene_select_frame(s, k) -- averaged on the device into
+ * one frame: motion blur of an animated mesh (a pose, palette, table or camera per frame) and temporal anti-aliasing
+ * without reading the frames back.  With integer weights w_k and D = sum of w_k, every byte b of the frame becomes
+ *     out[b] = (sum over k of w_k * F_k[b] + D / 2) / D
+ * -- integer division on the stored u8 values, rounded half up, no gamma.  1 <= n_frames <= TR_ACCUMULATE_MAX_FRAMES,
+ * 0 <= w_k <= 255, D >= 1; weights == NULL: every weight is 1.  A frame of weight 0 is not read.  Tiles (128 x 16) a
+ * frame left empty are skipped on its fast-clear flags (three quarters of each frame of the reference's model).
+ * Asynchronous, like tr_scene_resolve: k_accumulate is enqueued on the scene's stream behind the renders issued so far
+ * (frames held back are submitted, a pending clear is made real), a later render is ordered behind it, the result is
+ * there after tr_scene_sync.  The scene's passes issued so far count as handed on, as after
+ * tr_scene_get_frame_buffer_async: a bin overflow among them is reported (TR_E_BIN_OVERFLOW), not repaired by rendering
+ * again.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses); a pinned buffer that is too small, ordinary host memory
+ * and an `out` that overlaps a frame buffer the scene has rendered into (its own, a caller's) are TR_E_INVALID.  A scene
+ * of the whole frame writes every byte of `out` on every call, a band scene its band's rows and nothing else.  No frame
+ * of the scene is written.
+ * out == NULL: in place, into the scene's CURRENT frame, which must be one of the n_frames frames (else TR_E_INVALID).
+ * Every later consumer -- the getters, tr_scene_resolve (motion blur under supersampling: accumulate, then resolve),
+ * the sparse read-back, tr_scene_composite, tr_scene_band_tiles, an exchange -- sees the averaged frame; the other kept
+ * frames are not written; z, the winner words and the shadow buffer are NOT touched and remain those of the selected
+ * frame.  Calling it twice averages twice.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene, n_frames == 0,
+ * n_frames > TR_ACCUMULATE_MAX_FRAMES, n_frames > tr_scene_frames_kept(s) (so anything after a plain tr_scene_render), a
+ * weight above 255, every weight zero. */
+#define TR_ACCUMULATE_MAX_FRAMES 32
+int tr_scene_accumulate(tr_scene *s, uint32_t n_frames, const uint32_t *weights /* n_frames, or NULL */, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first (an overflowed group is rendered
+ * again before it is read), averages into a buffer of the library's, copies out and returns the frame's sticky status,
+ * like tr_scene_get_resolved.  Rows outside a band scene's band are zeros. */
+int tr_scene_get_accumulated(tr_scene *s, uint32_t n_frames, const uint32_t *weights, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline function k_accumulate calls: frames[k] points to the
+ * n_bytes bytes of F_k, out to n_bytes bytes.  The same checks of n_frames and weights; n_bytes == 0: TR_OK. */
+int tr_accumulate_host(size_t n_bytes, uint32_t n_frames, const uint8_t *const *frames, const uint32_t *weights, uint8_t *out);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

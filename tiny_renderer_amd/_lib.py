@@ -133,6 +133,9 @@ SYMBOLS = {
     "tr_scene_ambient_occlusion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_ao_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_ao_offsets": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
+    "tr_scene_accumulate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_accumulated": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_accumulate_host": (C.c_int, [C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_host_alloc": (C.c_void_p, [C.c_size_t]),
     "tr_host_free": (None, [C.c_void_p]),
     "tr_scene_host_buffer_written": (C.c_int, [C.c_void_p, C.c_void_p]),

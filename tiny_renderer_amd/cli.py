@@ -61,7 +61,16 @@ def main(argv=None):
                          "rings of up to RADIUS (1..16) pixels (Scene.ambient_occlusion; after --with, before --ssaa resolves)")
     ap.add_argument("--ao-rings", type=int, default=1, metavar="N", help="rings of sixteen samples (1..4, at most RADIUS)")
     ap.add_argument("--ao-grey", action="store_true", help="with --ao: the occlusion alone, white darkened to black")
+    ap.add_argument("--shutter", type=int, default=0, metavar="N",
+                    help="motion blur: the written frame is the average of the last N (1..32) frames of the run, made on "
+                         "the GPU (Scene.accumulate_in_place; needs --frames >= N; before --ssaa resolves)")
     args = ap.parse_args(argv)
+    if args.shutter and not 1 <= args.shutter <= 32:
+        ap.error("--shutter takes 1..32 frames")
+    if args.shutter and (args.gpus > 1 or args.ao or args.with_path):
+        ap.error("--shutter averages the frames of one scene on one GPU: not with --gpus > 1, --ao or --with")
+    if args.shutter and (args.seconds > 0 or args.view != "frame" or args.frames < args.shutter):
+        ap.error("--shutter N averages the last N colour frames of a run by frame count: use --frames >= N and --view frame")
     if (args.ao_rings != 1 or args.ao_grey) and not args.ao:
         ap.error("--ao-rings and --ao-grey go with --ao RADIUS")
     if args.ao and (args.gpus > 1 or args.seconds > 0 or args.view != "frame"):
@@ -142,7 +151,9 @@ def main(argv=None):
     else:
         if args.ssaa > 1:
             say("supersampling: rendering %d x %d" % (args.width * args.ssaa, args.height * args.ssaa))
-        scene = T.Scene(args.width * args.ssaa, args.height * args.ssaa, mesh, texs, args.pipeline, device=args.device)
+        # (--shutter N: the last N frames of the call must still exist when it ends -- a launch of N frames, N slots)
+        scene = T.Scene(args.width * args.ssaa, args.height * args.ssaa, mesh, texs, args.pipeline, device=args.device,
+                        frames_per_launch=args.shutter)
     if args.instance_yaw is not None:
         say("instances: %d x %d grid, cell (i, j) turned by (i * %d + j) * %g degrees about y"
             % (args.instances, args.instances, args.instances, args.instance_yaw))
@@ -250,7 +261,7 @@ def _run(args, T, scene, sharded, rank, say):
     angles = [np.float32(args.camera_angle + (2.0 * np.pi * f / args.frames if args.frames > 1 else 0.0))
               for f in range(args.frames)]
     la = np.float32(args.light_angle)
-    if args.frames > 1:
+    if args.frames > 1 or args.shutter:
         # many frames: the library's throughput path (the same frames, several per kernel launch; with --gpus every
         # rank renders its band of a group, and the bands are exchanged frame by frame)
         p = np.zeros((args.frames, 12), np.float32)
@@ -278,6 +289,8 @@ def _run(args, T, scene, sharded, rank, say):
         other.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
         other.render()
         scene.composite(other)
+    if args.shutter:
+        scene.accumulate_in_place(args.shutter)
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
     img = _view(scene, args.view, args.ssaa)

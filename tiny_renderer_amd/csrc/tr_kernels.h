@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_morph.h"
@@ -70,6 +71,10 @@ int launch_composite(const CompositeArgs &a, hipStream_t st);
 // Ambient occlusion: the frame's colour shaded in place from its own z buffer by the rule of tr_ao.h, through the
 // scene's fast-clear flags: k_ao.  The whole frame only (no band); the caller has made the depth real.
 int launch_ao(const AoArgs &a, hipStream_t st);
+// Frame accumulation: a.n frames averaged under their weights into a.out over the tiles of the band, by the rule of
+// tr_accumulate.h and through every frame's fast-clear flags: k_accumulate.  a.out_clean: the destination's flags when
+// a.out is one of the frames (in place), else null.  The caller orders the launch behind the work that produced the frames.
+int launch_accumulate(const AccumulateArgs &a, hipStream_t st);
 // Morph targets: the posed rows of n_frames frames (<= MORPH_MAX_FRAMES) by one launch -- frame f blends the mesh's
 // gathered rows `base` (n_rows x TRI_FLOATS) with the gathered delta rows `delta` (n_targets x n_rows x TRI_FLOATS) under
 // the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.

@@ -29,6 +29,7 @@
 
 #include <type_traits>
 
+#include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_kernels.h"
@@ -2089,6 +2090,99 @@ __global__ __launch_bounds__(AO_THREADS) void k_ao(AoArgs a)
     }
 }
 
+// Frame accumulation (tr_scene_accumulate): n kept frames of a call averaged under integer weights into `out`, byte by
+// byte on their stored u8 values (tr_accumulate.h has the rule).  One workgroup per 128 x 16 tile of the band, the tiles
+// of k_read_back and k_composite; a lane owns 16 pixels of a row -- three 16-byte pieces -- and lanes run along the row
+// first.  Frame pointers, flag pointers, weights and the divisor's constants are kernel arguments.
+//   * per tile the n colour-clean flags are workgroup-uniform (scalar loads); a frame whose flag is up holds zeros
+//     there and one of weight 0 counts for nothing: neither is read.  The others are the tile's contributors;
+//   * no contributor: every byte of the tile is (0 + D / 2) / D = 0.  Out of place the zeros are stored without a load;
+//     in place (out is one of the frames, out_clean its flags) a destination whose own flag is up holds them already and
+//     the workgroup leaves -- a destination that is drawn there but weighs nothing is zeroed;
+//   * otherwise a lane loads its pieces of every contributor, multiplies and adds byte by byte in 32-bit accumulators that
+//     start at D / 2, divides by the multiplier and shift of accumulate_div and stores its three pieces.  It has read
+//     its pieces of every frame before it writes them, and no other lane touches them: in place is safe;
+//   * in place over a destination flag that is up the tile now holds the average of what the others drew: lane 0 lowers
+//     the flag behind a barrier (every wave has read the flags by then), or k_resolve and the sparse read-back would
+//     take the tile for zeros.
+// WIDE: width % 16 == 0 and every buffer 16-byte aligned (the launcher checks); otherwise the same shares through byte
+// accesses guarded by the width, which also serve the last columns of a width that is not a multiple of 16.  Rows
+// outside the band are not touched.  No atomics, no LDS beyond the barrier, no scratch.
+template <bool WIDE>
+__global__ __launch_bounds__(8 * TILE_H) void k_accumulate(AccumulateArgs a)
+{
+    static_assert(TILE_W == 128, "a row of a tile is eight shares of 16 pixels");
+    const uint32_t t = blockIdx.x;
+    uint32_t contrib = 0u;  // bit k: frame k is read
+    for (uint32_t k = 0; k < a.n; k++) {
+        const uint32_t *flags = a.clean[k];
+        const bool zeros = a.w[k] == 0u || (flags != nullptr && flags[t] != 0u);
+        if (!zeros) contrib |= 1u << k;
+    }
+    const bool out_was_clean = a.out_clean != nullptr && a.out_clean[t] != 0u;
+    if (contrib == 0u && out_was_clean) return;  // (workgroup-uniform, ahead of the barrier)
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t x = (int32_t)(t % a.frame.ntx) * TILE_W + (int32_t)(threadIdx.x % 8u) * 16;
+    const int32_t y = (a.frame.ty_base + (int32_t)(t / a.frame.ntx)) * TILE_H + (int32_t)(threadIdx.x / 8u);
+    const bool inside = x < W && y >= a.frame.band_y0 && y < a.frame.band_y1;
+    if (inside) {
+        const int32_t n_bytes = min(16, W - x) * 3;  // of the share (WIDE: 48)
+        const size_t ci = ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+        uint32_t res[12];
+        if (contrib == 0u) {
+#pragma unroll
+            for (int w = 0; w < 12; w++) res[w] = 0u;
+        } else {
+            uint32_t acc[48];
+#pragma unroll
+            for (int b = 0; b < 48; b++) acc[b] = a.div.half;
+            for (uint32_t k = 0; k < a.n; k++) {
+                if (((contrib >> k) & 1u) == 0u) continue;
+                const uint8_t *p = a.fb[k] + ci;
+                const uint32_t wk = a.w[k] & 0xFFu;  // (<= 255, the launcher checks: a 24-bit multiply-add per byte)
+                uint32_t v[12];
+                if (WIDE) {
+#pragma unroll
+                    for (int q = 0; q < 3; q++) {
+                        const uint4 u = reinterpret_cast<const uint4 *>(p)[q];
+                        v[4 * q + 0] = u.x, v[4 * q + 1] = u.y, v[4 * q + 2] = u.z, v[4 * q + 3] = u.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int w = 0; w < 12; w++) {
+                        uint32_t u = 0u;
+#pragma unroll
+                        for (int b = 0; b < 4; b++)
+                            if (4 * w + b < n_bytes) u |= (uint32_t)p[4 * w + b] << (8 * b);
+                        v[w] = u;
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < 48; b++) acc[b] += wk * ((v[b >> 2] >> (8 * (b & 3))) & 0xFFu);
+            }
+#pragma unroll
+            for (int w = 0; w < 12; w++) {
+                res[w] = 0u;
+#pragma unroll
+                for (int b = 0; b < 4; b++) res[w] |= accumulate_div(acc[4 * w + b], a.div) << (8 * b);
+            }
+        }
+        uint8_t *o = a.out + ci;
+        if (WIDE) {
+#pragma unroll
+            for (int q = 0; q < 3; q++)
+                reinterpret_cast<uint4 *>(o)[q] = make_uint4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int b = 0; b < 48; b++)
+                if (b < n_bytes) o[b] = (uint8_t)(res[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+    if (!out_was_clean || contrib == 0u) return;  // (workgroup-uniform)
+    __syncthreads();
+    if (threadIdx.x == 0u) a.out_clean[t] = 0u;
+}
+
 // Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
 // mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
 // pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
@@ -2697,6 +2791,26 @@ int launch_ao(const AoArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_ao<true>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_ao<false>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_accumulate(const AccumulateArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.out || a.n == 0u || a.n > ACC_MAX_FRAMES || a.div.mul == 0u) return (int)hipErrorInvalidValue;
+    // the wide path: every share is whole 16-byte pieces of every buffer
+    uintptr_t low_bits = (uintptr_t)a.out;
+    for (uint32_t k = 0; k < a.n; k++) {
+        if (!a.fb[k] || a.w[k] > ACC_MAX_WEIGHT) return (int)hipErrorInvalidValue;
+        low_bits |= (uintptr_t)a.fb[k];
+    }
+    const bool wide = a.frame.width % 16u == 0u && low_bits % 16u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_accumulate<true>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_accumulate<false>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -376,7 +376,7 @@ struct tr_scene {
     } tail;
     bool last_was_group = false;
     uint8_t *d_view = nullptr;  // scratch for get_z_buffer / get_shadow_buffer
-    uint8_t *d_resolved = nullptr;  // tr_scene_get_resolved's device buffer, of the largest resolved size asked for so far
+    uint8_t *d_resolved = nullptr;  // tr_scene_get_resolved's / tr_scene_get_accumulated's device buffer, of the largest size asked for so far
     size_t resolved_bytes = 0;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
@@ -3634,6 +3634,167 @@ int tr_ao_offsets(uint32_t radius, uint32_t rings, int8_t *dxdy)
     AoTaps taps;
     ao_offsets(radius, rings, taps);
     memcpy(dxdy, taps.d, (size_t)2 * AO_RING * rings);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_ACCUMULATE_MAX_FRAMES == ACC_MAX_FRAMES, "tr_accumulate.h restates the header");
+
+// Frame count and weights as every accumulate entry point accepts them (`who` names the entry point in the error text;
+// kept: the frames there are to choose from).  The divisor goes to *D.
+int check_accumulate(uint32_t n, uint32_t kept, const uint32_t *weights, const char *who, uint32_t *D)
+{
+    const std::string w(who);
+    if (n == 0u || n > ACC_MAX_FRAMES) return tr::fail(TR_E_INVALID, w + ": n_frames must be 1..TR_ACCUMULATE_MAX_FRAMES");
+    if (n > kept)
+        return tr::fail(TR_E_INVALID, w + ": more frames than the last tr_scene_render_frames call left (tr_scene_frames_kept)");
+    uint32_t sum = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t wk = weights ? weights[k] : 1u;
+        if (wk > ACC_MAX_WEIGHT) return tr::fail(TR_E_INVALID, w + ": a weight above 255");
+        sum += wk;
+    }
+    if (sum == 0u) return tr::fail(TR_E_INVALID, w + ": every weight is zero");
+    *D = sum;
+    return TR_OK;
+}
+
+// The colour buffer of the frame tr_scene_select_frame(s, back) would make current.
+uint8_t *kept_frame_buffer(const tr_scene *s, uint32_t back)
+{
+    const size_t k = s->tail.params.size() - 1u - back;
+    return s->tail.fbs.empty() ? s->slots[(size_t)s->tail.slot[k]].fb : (uint8_t *)s->tail.fbs[k];
+}
+
+// Enqueues the average of the last n kept frames into `out_device` (null: in place, into the current frame) behind
+// everything issued so far.  n, weights and D have passed check_accumulate.
+int enqueue_accumulate(tr_scene *s, uint32_t n, const uint32_t *weights, uint32_t D, uint8_t *out_device)
+{
+    AccumulateArgs a = {};
+    bool current_is_among = false;
+    for (uint32_t k = 0; k < n; k++) {
+        uint8_t *fb = kept_frame_buffer(s, k);
+        if (!fb) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: a kept frame has no colour buffer");
+        a.fb[k] = fb;
+        a.w[k] = weights ? weights[k] : 1u;
+        // (a set that is not remembered any more: nothing known about the buffer, every tile is read)
+        for (const tr_scene::FbFlags &f : s->fb_flags)
+            if (f.fb == fb) a.clean[k] = f.clean;
+        current_is_among = current_is_among || fb == s->d_fb;
+    }
+    if (!out_device && !current_is_among)
+        return tr::fail(TR_E_INVALID, "tr_scene_accumulate: in place (out == NULL) the current frame must be one of the accumulated frames");
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st != TR_OK) return st;
+    a.out = out_device ? out_device : s->d_fb;
+    a.out_clean = out_device ? nullptr : s->d_fbclean;
+    a.frame = s->frame;
+    a.n = n;
+    a.div = accumulate_divisor(D);
+    {
+        Timed t(s, K_ACCUMULATE);
+        int rc = launch_accumulate(a, s->stream);
+        if (rc) return launch_status(rc, "k_accumulate");
+    }
+    // (in place a colour-clean flag of the DEVICE buffer may come down; a record of a page-locked host buffer (HostFlags)
+    // says what that host buffer holds, which this call does not change: the next read-back compares the two as always)
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_accumulate(tr_scene *s, uint32_t n_frames, const uint32_t *weights, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: null scene");
+    uint32_t D = 0;
+    int st = check_accumulate(n_frames, s->last_was_group ? (uint32_t)s->tail.params.size() : 0u, weights, "tr_scene_accumulate", &D);
+    if (st != TR_OK) return st;
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    void *target = nullptr;
+    if (out) {
+        // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
+        bool known_host = false;
+        {
+            std::lock_guard<std::mutex> lock(g_host_mutex);
+            auto it = g_host_allocs.find(out);
+            if (it != g_host_allocs.end()) {
+                known_host = true;
+                if (it->second.bytes >= bytes) {
+                    target = it->second.device;
+                    // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
+                    it->second.writer = 0u;
+                    it->second.gen += 1u;
+                }
+            }
+        }
+        if (known_host && !target) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: the host buffer is smaller than the frame");
+        if (!target) {
+            hipPointerAttribute_t attr = {};
+            if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
+                (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+                return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_accumulated takes any host memory)");
+            }
+            if (attr.type != hipMemoryTypeDevice)
+                return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_accumulated takes any host memory)");
+            target = out;
+        }
+        // `out` must not be (part of) a frame the kernel may read, or another one the scene keeps flags of
+        auto overlaps = [&](const uint8_t *fb) {
+            return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
+        };
+        bool hit = false;
+        for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
+        for (const tr_scene::FbFlags &f : s->fb_flags) hit = hit || overlaps(f.fb);
+        for (uint32_t k = 0; k < n_frames; k++) hit = hit || overlaps(kept_frame_buffer(s, k));
+        if (hit) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` overlaps a frame buffer of the scene (out == NULL accumulates in place)");
+    }
+    st = enqueue_accumulate(s, n_frames, weights, D, (uint8_t *)target);
+    if (st != TR_OK) return st;
+    // every pass issued so far is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering a frame
+    // again after a bin overflow would undo an average made in place, or change what one made elsewhere was made from
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+int tr_scene_get_accumulated(tr_scene *s, uint32_t n_frames, const uint32_t *weights, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_accumulated: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_accumulated: null argument");
+    uint32_t D = 0;
+    int st = check_accumulate(n_frames, s->last_was_group ? (uint32_t)s->tail.params.size() : 0u, weights, "tr_scene_get_accumulated", &D);
+    if (st != TR_OK) return st;
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
+        s->resolved_bytes = 0;
+        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
+        s->resolved_bytes = bytes;
+    }
+    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
+    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
+    if (!whole_frame) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    st = enqueue_accumulate(s, n_frames, weights, D, s->d_resolved);
+    if (st != TR_OK) return st;
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// The rule of tr_accumulate.h over caller's arrays, on the host.  Needs no GPU.
+int tr_accumulate_host(size_t n_bytes, uint32_t n_frames, const uint8_t *const *frames, const uint32_t *weights, uint8_t *out)
+{
+    uint32_t D = 0;
+    int st = check_accumulate(n_frames, n_frames, weights, "tr_accumulate_host", &D);
+    if (st != TR_OK) return st;
+    if (n_bytes == 0u) return TR_OK;
+    if (!frames || !out) return tr::fail(TR_E_INVALID, "tr_accumulate_host: null argument");
+    for (uint32_t k = 0; k < n_frames; k++)
+        if (!frames[k]) return tr::fail(TR_E_INVALID, "tr_accumulate_host: null frame");
+    accumulate_host(n_bytes, n_frames, frames, weights, out);
     return TR_OK;
 }
 

@@ -224,6 +224,43 @@ def ao_offsets(radius, rings=1):
     return out
 
 
+ACCUMULATE_MAX_FRAMES = 32   # (TR_ACCUMULATE_MAX_FRAMES)
+
+
+def accumulate_weights(n_frames, weights=None):
+    """(n, uint32 array or None) as tr_scene_accumulate takes them; ValueError for what the library would refuse
+    (include/tiny_renderer.h) as far as the host alone can tell."""
+    if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)):
+        raise ValueError("accumulate: n_frames must be an integer")
+    n = int(n_frames)
+    if not 1 <= n <= ACCUMULATE_MAX_FRAMES:
+        raise ValueError("accumulate: n_frames must be 1..%d" % ACCUMULATE_MAX_FRAMES)
+    if weights is None:
+        return n, None
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.shape[0] != n or w.dtype.kind not in "iu":
+        raise ValueError("accumulate: weights must be %d integers" % n)
+    if (w < 0).any() or (w > 255).any():
+        raise ValueError("accumulate: weights must be 0..255")
+    if not w.any():
+        raise ValueError("accumulate: every weight is zero")
+    return n, np.ascontiguousarray(w, np.uint32)
+
+
+def accumulate_host(frames, weights=None):
+    """tr_accumulate_host: the rule of Scene.accumulate on the host (no GPU needed), by the inline function k_accumulate
+    calls.  frames: n uint8 arrays of one shape (or an [n, ...] array), frames[k] weighted weights[k] (None: all 1);
+    returns (sum of w_k * F_k + D // 2) // D with D = sum of w_k, in the frames' shape."""
+    fr = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    n, w = accumulate_weights(len(fr), weights)
+    if any(f.shape != fr[0].shape for f in fr):
+        raise ValueError("accumulate_host: the frames differ in shape")
+    out = np.empty(fr[0].shape, np.uint8)
+    ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in fr])
+    check(load_library().tr_accumulate_host(out.size, n, ptrs, w.ctypes.data if w is not None else None, out.ctypes.data))
+    return out
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -569,6 +606,42 @@ class Scene:
         scenes are refused.  store_depth=True avoids the depth-only repeat of the frame's pass."""
         p = ao_params(radius, rings, threshold, falloff, grey)
         check(load_library().tr_scene_ambient_occlusion(self._h, C.addressof(p)))
+
+    # --- frame accumulation (tr_scene_accumulate / tr_scene_get_accumulated) -----------------------
+    def accumulate(self, n_frames, weights=None, strict=True):
+        """The last `n_frames` frames of the last render_frames call -- frame k is what select_frame(k) makes current --
+        averaged on the device under integer weights (0..255, None: all 1): an [H, W, 3] uint8 array,
+        (sum of w_k * F_k + D // 2) // D on the stored bytes with D = sum of w_k.  Synchronizes; no frame is changed."""
+        n, w = accumulate_weights(n_frames, weights)
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        code = load_library().tr_scene_get_accumulated(self._h, n, w.ctypes.data if w is not None else None, out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return out
+
+    def accumulate_into(self, n_frames, target, weights=None):
+        """Enqueue the average behind the renders issued so far (tr_scene_accumulate); the result is there after sync().
+        `target`: a device pointer (int) to 3 * W * H bytes that overlaps no frame buffer of the scene, or an array from
+        pinned_frame.  A band scene writes its band's rows only."""
+        n, w = accumulate_weights(n_frames, weights)
+        if target is None:
+            raise ValueError("accumulate_into: no target (accumulate_in_place averages into the current frame)")
+        if isinstance(target, np.ndarray):
+            if target.nbytes != self.width * self.height * 3 or not target.flags["C_CONTIGUOUS"]:
+                raise ValueError("target must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
+            ptr = target.ctypes.data
+        else:
+            ptr = int(target)
+        check(load_library().tr_scene_accumulate(self._h, n, w.ctypes.data if w is not None else None, ptr))
+        return target
+
+    def accumulate_in_place(self, n_frames, weights=None):
+        """tr_scene_accumulate with out = NULL: the average replaces the current frame, which must be one of the
+        n_frames frames; every later consumer (the getters, resolve, the sparse read-back, composite) sees it, the other
+        kept frames, z, winner words and the shadow buffer stay.  Asynchronous; calling it twice averages twice."""
+        n, w = accumulate_weights(n_frames, weights)
+        check(load_library().tr_scene_accumulate(self._h, n, w.ctypes.data if w is not None else None, None))
 
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
