@@ -525,6 +525,76 @@ int tr_scene_get_accumulated(tr_scene *s, uint32_t n_frames, const uint32_t *wei
  * n_bytes bytes of F_k, out to n_bytes bytes.  The same checks of n_frames and weights; n_bytes == 0: TR_OK. */
 int tr_accumulate_host(size_t n_bytes, uint32_t n_frames, const uint8_t *const *frames, const uint32_t *weights, uint8_t *out);
 
+/* Depth of field: the scene's CURRENT frame blurred by its own z buffer, on the device -- a focused subject in front of
+ * a soft background (or behind a soft foreground) for a frame of any pipeline, a merged frame (tr_scene_composite), a
+ * shaded one (tr_scene_ambient_occlusion) or an averaged one (tr_scene_accumulate), without reading colour and z back
+ * and without rendering jittered cameras.  The rule:
+ *   circle  : the circle of confusion of a pixel with depth z (what tr_scene_read_z_f32 returns):
+ *                 bits(z) == bits(f32::MIN), not drawn : coc = background_radius
+ *                 otherwise : coc = min(max_radius, (((|z - focus|) - range) * scale) as u32)
+ *             in f32, every operation rounded once, nothing fused; `as u32` truncates and saturates, NaN and negatives
+ *             give 0.  So a NaN z gives 0 and an infinite one max_radius.
+ *   weights : wt[r] = 32768 / ((2r + 1) * (2r + 1)), integer division, r = 0..8:
+ *             32768, 3640, 1310, 668, 404, 270, 193, 145, 113.
+ *   pixel   : with R = max_radius, the output at p = (x, y), per channel c, over the stored u8 values F:
+ *                 sw = 0, sc = 0
+ *                 for every q = (x + dx, y + dy), |dx| <= R, |dy| <= R, q inside the frame, max(|dx|, |dy|) <= coc(q):
+ *                     sw += wt[coc(q)];  sc += wt[coc(q)] * F_q[c]
+ *                 out_p[c] = (sc + sw / 2) / sw                      (u32 integer arithmetic, which cannot overflow)
+ *             Scatter written as gather: a pixel spreads over the square of its own circle with a weight inverse to
+ *             that square's area.  q = p always qualifies.  A q outside the frame contributes nothing.  Pixels that are
+ *             not drawn take part with their stored colour (a caller's buffer may hold a backdrop there) and
+ *             background_radius.
+ *   TR_DOF_SHOW_COC : every pixel of the output is coc(p) * 255 / max_radius in all three channels (integer division),
+ *             for choosing focus and scale by eye.
+ * z, the winner words and the shadow buffer are never written. */
+#define TR_DOF_MAX_RADIUS 8
+#define TR_DOF_SHOW_COC 0x1u
+typedef struct tr_dof_params {
+    uint32_t struct_size;        /* = sizeof(tr_dof_params) = 28 */
+    uint32_t max_radius;         /* pixels, 1..TR_DOF_MAX_RADIUS */
+    uint32_t background_radius;  /* circle of confusion of a pixel that is not drawn, 0..max_radius */
+    uint32_t flags;              /* TR_DOF_SHOW_COC or 0 */
+    float focus;                 /* z in focus (the units of tr_scene_read_z_f32); finite */
+    float range;                 /* half-width of the band around focus that stays sharp; finite, >= 0 */
+    float scale;                 /* pixels of radius per unit of z beyond the band; finite, > 0 */
+} tr_dof_params;
+/* Blurs the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_resolve: k_dof is
+ * enqueued on the scene's stream behind the renders issued so far (frames held back are submitted, a pending clear is
+ * made real, a depth left on the chip -- see TR_OPT_STORE_DEPTH -- is fetched by the depth-only repeat of the frame's
+ * pass), a later render is ordered behind it, the result is there after tr_scene_sync.  The scene's passes issued so
+ * far count as handed on, as after tr_scene_get_frame_buffer_async: a bin overflow among them is reported
+ * (TR_E_BIN_OVERFLOW), not repaired by rendering again.  Tiles (128 x 16) whose whole 3 x 3 neighbourhood holds the
+ * cleared colour are written as zeros on the fast-clear flags without reading a pixel; colour spreads into a cleared
+ * tile beside a drawn one.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses); every byte of `out` is written on every call, the
+ * scene's frame is not.
+ * out == NULL: in place.  The kernel writes a frame and a set of flags of the library's, and two device-to-device copies
+ * in stream order put them over the current frame and its colour-clean flags: every later consumer -- the getters,
+ * tr_scene_resolve, the sparse read-back, tr_scene_composite in either role, tr_scene_band_tiles -- sees the blurred
+ * frame; z, the winner words and the shadow buffer stay.  Calling it twice blurs twice.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since): out of place `out` becomes zeros
+ * (hipMemsetAsync, no kernel); in place TR_OK, nothing happens.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene or NULL params, a wrong
+ * struct_size, max_radius outside 1..TR_DOF_MAX_RADIUS, background_radius > max_radius, unknown flag bits, a focus that
+ * is not finite, a range that is not finite or negative, a scale that is not finite or not positive, ordinary host
+ * memory as `out`, a pinned buffer that is too small, an `out` that overlaps a frame buffer the scene has rendered into,
+ * and a BAND scene (tr_options.band_row0/1 set): the taps at a band's border lie in rows another rank owns. */
+int tr_scene_depth_of_field(tr_scene *s, const tr_dof_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first (an overflowed frame is rendered
+ * again before it is read), blurs into a buffer of the library's, copies out and returns the frame's sticky status,
+ * like tr_scene_get_resolved.  The scene's frame stays unblurred. */
+int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_dof calls.  z: width * height floats, index
+ * x + y * width, y up (tr_scene_read_z_f32); rgb: the frame as tr_scene_get_frame_buffer returns it, row 0 = top; out:
+ * like rgb, and not rgb.  The same parameter checks; width or height 0: TR_OK, nothing to do. */
+int tr_dof_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up */, const uint8_t *rgb /* row 0 = top */,
+                uint8_t *out /* != rgb */, const tr_dof_params *p);
+/* The circles of confusion of n depths under the parameters (coc: n bytes). */
+int tr_dof_coc(const tr_dof_params *p, uint32_t n, const float *z, uint8_t *coc);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

@@ -136,6 +136,10 @@ SYMBOLS = {
     "tr_scene_accumulate": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_get_accumulated": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_accumulate_host": (C.c_int, [C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_depth_of_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_depth_of_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_dof_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_dof_coc": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_host_alloc": (C.c_void_p, [C.c_size_t]),
     "tr_host_free": (None, [C.c_void_p]),
     "tr_scene_host_buffer_written": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -64,7 +64,30 @@ def main(argv=None):
     ap.add_argument("--shutter", type=int, default=0, metavar="N",
                     help="motion blur: the written frame is the average of the last N (1..32) frames of the run, made on "
                          "the GPU (Scene.accumulate_in_place; needs --frames >= N; before --ssaa resolves)")
+    ap.add_argument("--dof-focus", type=float, default=None, metavar="Z",
+                    help="depth of field: blur the picture by its own z buffer on the GPU, the depth Z (the units of the z "
+                         "buffer) stays sharp (Scene.depth_of_field; needs --dof-scale; after --with, --ao and --shutter, "
+                         "before --ssaa resolves)")
+    ap.add_argument("--dof-scale", type=float, default=None, metavar="S", help="pixels of blur radius per unit of z away from the sharp band")
+    ap.add_argument("--dof-radius", type=int, default=4, metavar="R", help="largest blur radius in pixels (1..8, default 4)")
+    ap.add_argument("--dof-range", type=float, default=0.0, metavar="B", help="half-width of the band of z around Z that stays sharp (default 0)")
+    ap.add_argument("--dof-background", type=int, default=0, metavar="R", help="blur radius of pixels that are not drawn (0..--dof-radius, default 0)")
+    ap.add_argument("--dof-show-coc", action="store_true", help="with --dof-focus: the blur radius of every pixel as a grey picture")
     args = ap.parse_args(argv)
+    args.dof = None
+    if (args.dof_focus is None) != (args.dof_scale is None):
+        ap.error("--dof-focus Z and --dof-scale S go together")
+    if args.dof_focus is None and (args.dof_radius != 4 or args.dof_range != 0.0 or args.dof_background != 0 or args.dof_show_coc):
+        ap.error("--dof-radius, --dof-range, --dof-background and --dof-show-coc go with --dof-focus Z --dof-scale S")
+    if args.dof_focus is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--dof-focus blurs the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import dof_params
+        try:
+            args.dof = dof_params(args.dof_focus, args.dof_scale, max_radius=args.dof_radius, background_radius=args.dof_background,
+                                  flags=1 if args.dof_show_coc else 0, range=args.dof_range)
+        except ValueError as e:
+            ap.error(str(e))
     if args.shutter and not 1 <= args.shutter <= 32:
         ap.error("--shutter takes 1..32 frames")
     if args.shutter and (args.gpus > 1 or args.ao or args.with_path):
@@ -293,6 +316,8 @@ def _run(args, T, scene, sharded, rank, say):
         scene.accumulate_in_place(args.shutter)
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
+    if args.dof is not None:
+        scene.depth_of_field(args.dof)
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

@@ -8,6 +8,7 @@
 #include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
+#include "tr_dof.h"
 #include "tr_morph.h"
 #include "tr_skin.h"
 #include "tr_types.h"
@@ -75,6 +76,10 @@ int launch_ao(const AoArgs &a, hipStream_t st);
 // tr_accumulate.h and through every frame's fast-clear flags: k_accumulate.  a.out_clean: the destination's flags when
 // a.out is one of the frames (in place), else null.  The caller orders the launch behind the work that produced the frames.
 int launch_accumulate(const AccumulateArgs &a, hipStream_t st);
+// Depth of field: a.fb blurred by a.z into a.out (which does not overlap it) by the rule of tr_dof.h, through the scene's
+// fast-clear flags of z and of colour: k_dof.  The whole frame only (no band); the caller has made the depth real.
+// a.out_clean: null, or the flags of `out` the kernel writes.
+int launch_dof(const DofArgs &a, hipStream_t st);
 // Morph targets: the posed rows of n_frames frames (<= MORPH_MAX_FRAMES) by one launch -- frame f blends the mesh's
 // gathered rows `base` (n_rows x TRI_FLOATS) with the gathered delta rows `delta` (n_targets x n_rows x TRI_FLOATS) under
 // the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.

@@ -32,6 +32,7 @@
 #include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
+#include "tr_dof.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
 #include "tr_plan.h"
@@ -2183,6 +2184,229 @@ __global__ __launch_bounds__(8 * TILE_H) void k_accumulate(AccumulateArgs a)
     if (threadIdx.x == 0u) a.out_clean[t] = 0u;
 }
 
+// Depth of field (tr_scene_depth_of_field): the frame's colour blurred by its own z buffer into `out`, never in place
+// (a tap reads a neighbour's colour); tr_dof.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame,
+// the tiles of k_ao.  The nine z flags and nine colour flags of the 3 x 3 neighbourhood are workgroup-uniform.
+//   * TR_DOF_SHOW_COC: a lane of the colour shares loads its 16 depths (none if the tile's z flag is up) and stores the
+//     grey circles; no LDS, no barrier;
+//   * all nine colour flags up (a tile outside the grid counts as up): every tap is black, the tile is zeros whatever
+//     the circles are -- stored without loading a pixel, ahead of any barrier;
+//   * staging: the tile and a halo of max_radius pixels go to LDS as rows of 160 pairs {packed pixel, wt[coc]} that
+//     start 16 pixels left of the tile, so that a 16-byte piece of z is aligned in memory and lies in ONE tile: a piece
+//     in a tile whose z flag is up gets f32::MIN without a load, one in a tile whose colour flag is up zeros without a
+//     load, and one outside the frame {0, wt[0]}: circle 0, which no tap at a distance >= 1 satisfies (only a lane whose
+//     own pixel is outside the frame sees it, and its result is never stored).  16 + 2 R rows of 1280 bytes: 23 KB at
+//     radius 1, 40 KB at radius 8 (dynamic LDS, so four to seven workgroups share a CU);
+//   * the vote: the largest circle among the staged pixels, through a wave reduction and four words of LDS behind the
+//     staging barrier.  No tap at a distance beyond it qualifies anywhere in the tile, so the loops run to it instead
+//     of max_radius; zero: the tile is a plain copy of its colour;
+//   * the gather: a lane owns one column of the tile and eight of its rows; lanes run along the row, so a tap reads 64
+//     consecutive pairs (one ds_read_b64, no bank conflict).  dx and dy are loop variables: the distance is scalar, the
+//     test one unsigned compare of the packed word, the weight a select, the sums four u32 per pixel (dof_tap);
+//   * the results go through the first 8 KB of the same LDS (a barrier on either side) to the colour shares of
+//     k_composite -- a lane owns 16 pixels of a row, three 16-byte pieces -- and every byte of the tile is stored;
+//   * out_clean, when given, gets the tile's flag: 1 where the tile was stored as zeros on the flags alone (its own
+//     colour flag was up, so its winner words are the cleared value too), 0 otherwise.
+// z, fb and every flag of the frame are only read.  WIDE: width % 16 == 0 and z, fb and out 16-byte aligned (the launcher
+// checks); otherwise the same through element accesses guarded by the width.  No atomics, no scratch.
+constexpr int DOF_LDS_W = TILE_W + 32;
+constexpr int DOF_THREADS = 256, DOF_ROWS = TILE_W * TILE_H / DOF_THREADS;  // rows of its column a lane owns
+
+// The 16 finished pixels of a share (24 bits each) into `o`: three 16-byte pieces, or n_px * 3 guarded bytes.
+template <bool WIDE>
+__device__ __forceinline__ void dof_store_share(uint8_t *o, const uint32_t (&px)[16], int32_t n_px)
+{
+    if (WIDE) {
+        uint32_t w[12];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            w[3 * g + 0] = px[4 * g] | (px[4 * g + 1] << 24);
+            w[3 * g + 1] = (px[4 * g + 1] >> 8) | (px[4 * g + 2] << 16);
+            w[3 * g + 2] = (px[4 * g + 2] >> 16) | (px[4 * g + 3] << 8);
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) reinterpret_cast<uint4 *>(o)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            if (i < n_px) {
+                o[3 * i + 0] = (uint8_t)(px[i] & 0xFFu);
+                o[3 * i + 1] = (uint8_t)((px[i] >> 8) & 0xFFu);
+                o[3 * i + 2] = (uint8_t)((px[i] >> 16) & 0xFFu);
+            }
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(DOF_THREADS) void k_dof(DofArgs a)
+{
+    static_assert(TILE_W == 128 && DOF_MAX_RADIUS <= 16 && DOF_MAX_RADIUS <= TILE_H, "the halo lies in the eight tiles around");
+    static_assert(DOF_THREADS == 4 * 64 && 8 * TILE_H <= DOF_THREADS, "four waves vote; the shares are the first lanes");
+    extern __shared__ uint2 s_px[];  // (TILE_H + 2 R) rows of DOF_LDS_W pairs; later the tile's results, one word each
+    __shared__ uint32_t s_max[4];
+    const uint32_t t = blockIdx.x;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, R = (int32_t)a.rule.max_radius;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t tx = (int32_t)t % ntx, ty = (int32_t)t / ntx;
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): no such tile / its z reads as f32::MIN / its colour as zeros
+    uint32_t none = 0u, zstale = 0u, czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) {
+                none |= bit, zstale |= bit, czero |= bit;
+            } else {
+                if (a.zclean[ny * ntx + nx] != 0u) zstale |= bit;
+                if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+            }
+        }
+    const uint32_t own_bit = 1u << 4;
+    // the colour shares of k_composite
+    const int32_t sx = x0 + (int32_t)(threadIdx.x % 8u) * 16, srow = (int32_t)(threadIdx.x / 8u), sy = y0 + srow;
+    const bool share = threadIdx.x < 8u * TILE_H && sx < W && sy < H;
+    const int32_t n_px = share ? min(16, W - sx) : 0;  // (WIDE: 16 or none)
+    uint8_t *o = share ? a.out + ((size_t)(H - 1 - sy) * (size_t)W + (size_t)sx) * 3u : nullptr;
+    uint32_t px[16];
+    if (a.show_coc != 0u) {  // (workgroup-uniform)
+        if (a.out_clean != nullptr && threadIdx.x == 0u)
+            a.out_clean[t] = ((czero & zstale & own_bit) != 0u && a.rule.background_radius == 0u) ? 1u : 0u;
+        if (!share) return;
+        const float *zp = a.z + (size_t)sy * (size_t)W + (size_t)sx;
+        float zv[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) zv[i] = bits_f32(TR_F32_MIN_BITS);
+        if ((zstale & own_bit) == 0u) {
+            if (WIDE) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const float4 v = reinterpret_cast<const float4 *>(zp)[k];
+                    zv[4 * k + 0] = v.x, zv[4 * k + 1] = v.y, zv[4 * k + 2] = v.z, zv[4 * k + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; i++)
+                    if (i < n_px) zv[i] = zp[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = dof_show(dof_coc(zv[i], a.rule), a.rule.max_radius) * 0x010101u;
+        dof_store_share<WIDE>(o, px, n_px);
+        return;
+    }
+    const bool all_zero = czero == 0x1FFu;
+    if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = all_zero ? 1u : 0u;
+    if (all_zero) {  // (workgroup-uniform, ahead of the barriers)
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = 0u;
+        dof_store_share<WIDE>(o, px, n_px);
+        return;
+    }
+    const int32_t rows = TILE_H + 2 * R;  // LDS row r is frame row y0 - R + r, LDS column c frame column x0 - 16 + c
+    uint32_t widest = 0u;                 // the largest circle this lane staged
+    if (WIDE) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (DOF_LDS_W / 4); p += DOF_THREADS) {
+            const int32_t r = p / (DOF_LDS_W / 4), j = p % (DOF_LDS_W / 4);
+            if (4 * j + 3 < 16 - R || 4 * j >= 16 + TILE_W + R) continue;  // (no tap reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - R + r;
+            const int32_t ax = j < 4 ? 0 : j < 4 + TILE_W / 4 ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            const bool inside = (none & bit) == 0u && x < W && y < H;
+            const float z_min = bits_f32(TR_F32_MIN_BITS);
+            float zv[4] = { z_min, z_min, z_min, z_min };
+            uint32_t c[4] = { 0u, 0u, 0u, 0u };
+            if (inside && (zstale & bit) == 0u) {
+                const float4 v = *reinterpret_cast<const float4 *>(a.z + (size_t)y * (size_t)W + (size_t)x);
+                zv[0] = v.x, zv[1] = v.y, zv[2] = v.z, zv[3] = v.w;
+            }
+            if (inside && (czero & bit) == 0u) {
+                // four pixels are twelve bytes at a multiple of four: three aligned words
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(a.fb + ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u);
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
+                c[0] = w0 & 0xFFFFFFu;
+                c[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                c[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                c[3] = w2 >> 8;
+            }
+            uint32_t e[8];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t coc = inside ? dof_coc(zv[k], a.rule) : 0u;
+                widest = max(widest, coc);
+                e[2 * k] = c[k] | (coc << 24);
+                e[2 * k + 1] = dof_weight(coc);
+            }
+            uint4 *d = reinterpret_cast<uint4 *>(&s_px[r * DOF_LDS_W + 4 * j]);
+            d[0] = make_uint4(e[0], e[1], e[2], e[3]);
+            d[1] = make_uint4(e[4], e[5], e[6], e[7]);
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * DOF_LDS_W; p += DOF_THREADS) {
+            const int32_t r = p / DOF_LDS_W, c = p % DOF_LDS_W;
+            if (c < 16 - R || c >= 16 + TILE_W + R) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - R + r;
+            const int32_t ax = c < 16 ? 0 : c < 16 + TILE_W ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            const bool inside = (none & bit) == 0u && x < W && y < H;
+            float zv = bits_f32(TR_F32_MIN_BITS);
+            uint32_t col = 0u;
+            if (inside && (zstale & bit) == 0u) zv = a.z[(size_t)y * (size_t)W + (size_t)x];
+            if (inside && (czero & bit) == 0u) {
+                const uint8_t *q = a.fb + ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+                col = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+            }
+            const uint32_t coc = inside ? dof_coc(zv, a.rule) : 0u;
+            widest = max(widest, coc);
+            s_px[r * DOF_LDS_W + c] = make_uint2(col | (coc << 24), dof_weight(coc));
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) widest = max(widest, (uint32_t)__shfl_xor((int)widest, off));
+    if (threadIdx.x % 64u == 0u) s_max[threadIdx.x / 64u] = widest;
+    __syncthreads();
+    const int32_t reach = (int32_t)__builtin_amdgcn_readfirstlane(max(max(s_max[0], s_max[1]), max(s_max[2], s_max[3])));
+    // the gather: column `col`, rows row0 .. row0 + DOF_ROWS - 1 of the tile
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, row0 = (int32_t)threadIdx.x / TILE_W * DOF_ROWS;
+    const uint2 *own = s_px + (R + row0) * DOF_LDS_W + 16 + col;
+    uint32_t res[DOF_ROWS];
+    if (reach == 0) {  // (workgroup-uniform) every circle is 0: only q = p qualifies, (32768 c + 16384) / 32768 = c
+#pragma unroll
+        for (int k = 0; k < DOF_ROWS; k++) res[k] = own[k * DOF_LDS_W].x & 0xFFFFFFu;
+    } else {
+        DofSums s[DOF_ROWS];
+#pragma unroll
+        for (int k = 0; k < DOF_ROWS; k++) s[k].w = s[k].r = s[k].g = s[k].b = 0u;
+        for (int32_t dy = -reach; dy <= reach; dy++)
+            for (int32_t dx = -reach; dx <= reach; dx++) {
+                const uint32_t dist = (uint32_t)max(abs(dx), abs(dy));
+                const uint2 *q = own + dy * DOF_LDS_W + dx;
+#pragma unroll
+                for (int k = 0; k < DOF_ROWS; k++) {
+                    const uint2 e = q[k * DOF_LDS_W];
+                    dof_tap(s[k], e.x, e.y, dist);
+                }
+            }
+#pragma unroll
+        for (int k = 0; k < DOF_ROWS; k++) res[k] = dof_finish(s[k]);
+    }
+    __syncthreads();  // every tap has been read: the results take the place of the first rows
+    uint32_t *s_out = reinterpret_cast<uint32_t *>(s_px);
+#pragma unroll
+    for (int k = 0; k < DOF_ROWS; k++) s_out[(row0 + k) * TILE_W + col] = res[k];
+    __syncthreads();
+    if (!share) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&s_out[srow * TILE_W + (sx - x0) + 4 * k]);
+        px[4 * k + 0] = v.x, px[4 * k + 1] = v.y, px[4 * k + 2] = v.z, px[4 * k + 3] = v.w;
+    }
+    dof_store_share<WIDE>(o, px, n_px);
+}
+
 // Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
 // mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
 // pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
@@ -2791,6 +3015,29 @@ int launch_ao(const AoArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_ao<true>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_ao<false>), dim3(n_tiles), dim3(AO_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_dof(const DofArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.z || !a.zclean || !a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.rule.max_radius == 0u || a.rule.max_radius > (uint32_t)DOF_MAX_RADIUS || a.rule.background_radius > a.rule.max_radius)
+        return (int)hipErrorInvalidValue;
+    // `out` is never the frame that is read
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // the wide path: every share is whole 16-byte pieces of z and colour
+    const bool wide = a.frame.width % 16u == 0u && ((uintptr_t)a.z | (uintptr_t)a.fb | (uintptr_t)a.out) % 16u == 0u;
+    const size_t lds = (size_t)(TILE_H + 2 * (int)a.rule.max_radius) * DOF_LDS_W * sizeof(uint2);
+    if (wide)
+        hipLaunchKernelGGL((k_dof<true>), dim3(n_tiles), dim3(DOF_THREADS), lds, st, a);
+    else
+        hipLaunchKernelGGL((k_dof<false>), dim3(n_tiles), dim3(DOF_THREADS), lds, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

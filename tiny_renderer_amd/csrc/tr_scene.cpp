@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -378,6 +378,10 @@ struct tr_scene {
     uint8_t *d_view = nullptr;  // scratch for get_z_buffer / get_shadow_buffer
     uint8_t *d_resolved = nullptr;  // tr_scene_get_resolved's / tr_scene_get_accumulated's device buffer, of the largest size asked for so far
     size_t resolved_bytes = 0;
+    // tr_scene_depth_of_field in place: the frame and the flags k_dof writes before both are copied over the current
+    // frame's (3 * W * H bytes, n_tiles words; allocated at the first such call)
+    uint8_t *d_dof_fb = nullptr;
+    uint32_t *d_dof_clean = nullptr;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
     // memory not written".  Raised by the tile kernel for the empty tiles of a cleared frame (and by
@@ -2443,6 +2447,8 @@ void destroy(tr_scene *s)
     }
     dev_free(s->d_view);
     dev_free(s->d_resolved);
+    dev_free(s->d_dof_fb);
+    dev_free(s->d_dof_clean);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
     for (tr_scene::HostFlags &f : s->host_flags) dev_free(f.clean);
@@ -3667,6 +3673,54 @@ uint8_t *kept_frame_buffer(const tr_scene *s, uint32_t back)
     return s->tail.fbs.empty() ? s->slots[(size_t)s->tail.slot[k]].fb : (uint8_t *)s->tail.fbs[k];
 }
 
+// `out` of tr_scene_accumulate / tr_scene_depth_of_field: memory from tr_host_alloc of at least `bytes` bytes (the
+// kernel stores through its mapped address, and the buffer's sparse read-back record lapses) or device memory, which
+// overlaps no frame buffer the scene keeps flags of, none of its slots and none of the last n_kept kept frames.  The
+// address the kernel stores to goes to *target.  who / getter / verb: the entry point's words in the error texts.
+int classify_out(tr_scene *s, void *out, size_t bytes, const char *who, const char *getter, const char *verb, uint32_t n_kept,
+                 void **target_out)
+{
+    const std::string w(who);
+    void *target = nullptr;
+    // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
+    bool known_host = false;
+    {
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(out);
+        if (it != g_host_allocs.end()) {
+            known_host = true;
+            if (it->second.bytes >= bytes) {
+                target = it->second.device;
+                // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
+                it->second.writer = 0u;
+                it->second.gen += 1u;
+            }
+        }
+    }
+    if (known_host && !target) return tr::fail(TR_E_INVALID, w + ": the host buffer is smaller than the frame");
+    if (!target) {
+        const std::string text = w + ": `out` is neither device memory nor from tr_host_alloc (" + getter + " takes any host memory)";
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, text);
+        }
+        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
+        target = out;
+    }
+    // `out` must not be (part of) a frame the kernel may read, or another one the scene keeps flags of
+    auto overlaps = [&](const uint8_t *fb) {
+        return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
+    };
+    bool hit = false;
+    for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
+    for (const tr_scene::FbFlags &f : s->fb_flags) hit = hit || overlaps(f.fb);
+    for (uint32_t k = 0; k < n_kept; k++) hit = hit || overlaps(kept_frame_buffer(s, k));
+    if (hit) return tr::fail(TR_E_INVALID, w + ": `out` overlaps a frame buffer of the scene (out == NULL " + verb + " in place)");
+    *target_out = target;
+    return TR_OK;
+}
+
 // Enqueues the average of the last n kept frames into `out_device` (null: in place, into the current frame) behind
 // everything issued so far.  n, weights and D have passed check_accumulate.
 int enqueue_accumulate(tr_scene *s, uint32_t n, const uint32_t *weights, uint32_t D, uint8_t *out_device)
@@ -3716,41 +3770,8 @@ int tr_scene_accumulate(tr_scene *s, uint32_t n_frames, const uint32_t *weights,
     const size_t bytes = (size_t)s->width * s->height * 3;
     void *target = nullptr;
     if (out) {
-        // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
-        bool known_host = false;
-        {
-            std::lock_guard<std::mutex> lock(g_host_mutex);
-            auto it = g_host_allocs.find(out);
-            if (it != g_host_allocs.end()) {
-                known_host = true;
-                if (it->second.bytes >= bytes) {
-                    target = it->second.device;
-                    // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
-                    it->second.writer = 0u;
-                    it->second.gen += 1u;
-                }
-            }
-        }
-        if (known_host && !target) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: the host buffer is smaller than the frame");
-        if (!target) {
-            hipPointerAttribute_t attr = {};
-            if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
-                (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
-                return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_accumulated takes any host memory)");
-            }
-            if (attr.type != hipMemoryTypeDevice)
-                return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_accumulated takes any host memory)");
-            target = out;
-        }
-        // `out` must not be (part of) a frame the kernel may read, or another one the scene keeps flags of
-        auto overlaps = [&](const uint8_t *fb) {
-            return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
-        };
-        bool hit = false;
-        for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
-        for (const tr_scene::FbFlags &f : s->fb_flags) hit = hit || overlaps(f.fb);
-        for (uint32_t k = 0; k < n_frames; k++) hit = hit || overlaps(kept_frame_buffer(s, k));
-        if (hit) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: `out` overlaps a frame buffer of the scene (out == NULL accumulates in place)");
+        st = classify_out(s, out, bytes, "tr_scene_accumulate", "tr_scene_get_accumulated", "accumulates", n_frames, &target);
+        if (st != TR_OK) return st;
     }
     st = enqueue_accumulate(s, n_frames, weights, D, (uint8_t *)target);
     if (st != TR_OK) return st;
@@ -3795,6 +3816,166 @@ int tr_accumulate_host(size_t n_bytes, uint32_t n_frames, const uint8_t *const *
     for (uint32_t k = 0; k < n_frames; k++)
         if (!frames[k]) return tr::fail(TR_E_INVALID, "tr_accumulate_host: null frame");
     accumulate_host(n_bytes, n_frames, frames, weights, out);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_DOF_MAX_RADIUS == DOF_MAX_RADIUS && TR_DOF_SHOW_COC == DOF_SHOW_COC && sizeof(tr_dof_params) == 28, "tr_dof.h restates the header");
+
+// tr_dof_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_dof_params(const tr_dof_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_dof_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_dof_params)");
+    if (p->max_radius < 1u || p->max_radius > (uint32_t)TR_DOF_MAX_RADIUS)
+        return tr::fail(TR_E_INVALID, w + ": max_radius must be 1..TR_DOF_MAX_RADIUS");
+    if (p->background_radius > p->max_radius) return tr::fail(TR_E_INVALID, w + ": background_radius must be at most max_radius");
+    if (p->flags & ~TR_DOF_SHOW_COC) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (!std::isfinite(p->focus)) return tr::fail(TR_E_INVALID, w + ": focus must be finite");
+    if (!std::isfinite(p->range) || p->range < 0.0f) return tr::fail(TR_E_INVALID, w + ": range must be finite and >= 0");
+    if (!std::isfinite(p->scale) || !(p->scale > 0.0f)) return tr::fail(TR_E_INVALID, w + ": scale must be finite and > 0");
+    return TR_OK;
+}
+
+DofRule dof_rule(const tr_dof_params *p)
+{
+    DofRule r;
+    r.focus = p->focus;
+    r.range = p->range;
+    r.scale = p->scale;
+    r.max_radius = p->max_radius;
+    r.background_radius = p->background_radius;
+    return r;
+}
+
+int check_dof_scene(const tr_scene *s, const char *who)
+{
+    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be blurred: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    return TR_OK;
+}
+
+// Enqueues the blur of the current frame into `out_device` (which overlaps no frame of the scene) behind everything
+// issued so far; out_clean: null, or where k_dof writes the flags of `out_device`.  The scene is not logically cleared.
+int enqueue_dof(tr_scene *s, const tr_dof_params *p, uint8_t *out_device, uint32_t *out_clean)
+{
+    // the frame on its way, its depth in memory behind valid flags
+    int st = submit_pending(s);
+    if (st == TR_OK) st = ensure_depth(s);
+    if (st == TR_OK) st = need_z(s, s->cur_slot);
+    if (st != TR_OK) return st;
+    DofArgs a = {};
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+    a.show_coc = (p->flags & TR_DOF_SHOW_COC) ? 1u : 0u;
+    a.rule = dof_rule(p);
+    {
+        Timed t(s, K_DOF);
+        int rc = launch_dof(a, s->stream);
+        if (rc) return launch_status(rc, "k_dof");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_depth_of_field(tr_scene *s, const tr_dof_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_depth_of_field: null scene");
+    int st = check_dof_params(p, "tr_scene_depth_of_field");
+    if (st == TR_OK) st = check_dof_scene(s, "tr_scene_depth_of_field");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    void *target = nullptr;
+    if (out) {
+        st = classify_out(s, out, bytes, "tr_scene_depth_of_field", "tr_scene_get_depth_of_field", "blurs", 0u, &target);
+        if (st != TR_OK) return st;
+    }
+    if (s->z_fb_cleared) {
+        // a logically cleared frame is black and nothing in it is drawn: zeros out of place, itself in place
+        if (!target) return TR_OK;
+        st = submit_pending(s);
+        if (st != TR_OK) return st;
+        HIP_TRY(hipMemsetAsync(target, 0, bytes, s->stream));
+        s->quiescent = false;
+        s->observed_seq = s->pass_seq;
+        return TR_OK;
+    }
+    if (!target) {
+        if (!s->d_dof_fb && (st = dev_alloc(&s->d_dof_fb, bytes))) return st;
+        if (!s->d_dof_clean && (st = dev_alloc(&s->d_dof_clean, (size_t)s->n_tiles))) return st;
+    }
+    st = enqueue_dof(s, p, target ? (uint8_t *)target : s->d_dof_fb, target ? nullptr : s->d_dof_clean);
+    if (st != TR_OK) return st;
+    if (!target) {
+        // in stream order: the blurred colour over the current frame, its flags over the frame's colour-clean flags
+        // (a record of a page-locked host buffer (HostFlags) says what that host buffer holds, which this call does not
+        // change: the next read-back compares the two as always)
+        HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, bytes, hipMemcpyDeviceToDevice, s->stream));
+        if (s->d_fbclean)
+            HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
+    }
+    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
+    // overflow would undo a blur made in place, or change what one made elsewhere was made from
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_depth_of_field: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_depth_of_field: null argument");
+    int st = check_dof_params(p, "tr_scene_get_depth_of_field");
+    if (st == TR_OK) st = check_dof_scene(s, "tr_scene_get_depth_of_field");
+    if (st != TR_OK) return st;
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
+        s->resolved_bytes = 0;
+        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
+        s->resolved_bytes = bytes;
+    }
+    if (s->z_fb_cleared) {
+        HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    } else {
+        st = enqueue_dof(s, p, s->d_resolved, nullptr);
+        if (st != TR_OK) return st;
+    }
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// The rule of tr_dof.h over caller's arrays, on the host.  Needs no GPU.
+int tr_dof_host(uint32_t width, uint32_t height, const float *z, const uint8_t *rgb, uint8_t *out, const tr_dof_params *p)
+{
+    int st = check_dof_params(p, "tr_dof_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!z || !rgb || !out) return tr::fail(TR_E_INVALID, "tr_dof_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_dof_host: out is rgb (the rule reads neighbours: not in place)");
+    dof_host(width, height, z, rgb, out, dof_rule(p), (p->flags & TR_DOF_SHOW_COC) != 0u);
+    return TR_OK;
+}
+
+int tr_dof_coc(const tr_dof_params *p, uint32_t n, const float *z, uint8_t *coc)
+{
+    int st = check_dof_params(p, "tr_dof_coc");
+    if (st != TR_OK) return st;
+    if (n == 0u) return TR_OK;
+    if (!z || !coc) return tr::fail(TR_E_INVALID, "tr_dof_coc: null argument");
+    dof_coc_host(dof_rule(p), n, z, coc);
     return TR_OK;
 }
 

@@ -261,6 +261,65 @@ def accumulate_host(frames, weights=None):
     return out
 
 
+DOF_MAX_RADIUS, DOF_SHOW_COC = 8, 1   # (TR_DOF_MAX_RADIUS, TR_DOF_SHOW_COC)
+
+
+class DofParams(C.Structure):
+    """tr_dof_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_radius", C.c_uint32), ("background_radius", C.c_uint32), ("flags", C.c_uint32),
+                ("focus", C.c_float), ("range", C.c_float), ("scale", C.c_float)]
+
+
+def dof_params(focus, scale, max_radius=4, background_radius=0, flags=0, range=0.0):
+    """tr_dof_params for Scene.depth_of_field / depth_of_field_host / dof_coc: the circle of confusion of a drawn pixel is
+    min(max_radius, ((|z - focus| - range) * scale) as u32) pixels, that of a pixel not drawn background_radius; flags:
+    DOF_SHOW_COC or 0.  ValueError for what the library would refuse (include/tiny_renderer.h)."""
+    for name, v in (("max_radius", max_radius), ("background_radius", background_radius), ("flags", flags)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("depth of field: %s must be an integer" % name)
+    if not 1 <= max_radius <= DOF_MAX_RADIUS:
+        raise ValueError("depth of field: max_radius must be 1..%d pixels" % DOF_MAX_RADIUS)
+    if not 0 <= background_radius <= max_radius:
+        raise ValueError("depth of field: background_radius must be 0..max_radius")
+    if flags & ~DOF_SHOW_COC:
+        raise ValueError("depth of field: unknown flags")
+    focus, range, scale = float(focus), float(range), float(scale)
+    with np.errstate(over="ignore"):   # (as f32: what the library gets)
+        f32, r32, s32 = np.float32(focus), np.float32(range), np.float32(scale)
+    if not np.isfinite(f32):
+        raise ValueError("depth of field: focus must be finite")
+    if not np.isfinite(r32) or r32 < 0.0:
+        raise ValueError("depth of field: range must be finite and >= 0")
+    if not np.isfinite(s32) or not s32 > 0.0:
+        raise ValueError("depth of field: scale must be finite and > 0")
+    return DofParams(C.sizeof(DofParams), int(max_radius), int(background_radius), int(flags), focus, range, scale)
+
+
+def depth_of_field_host(z, rgb, params):
+    """tr_dof_host: the rule of Scene.depth_of_field on the host (no GPU needed), by the inline functions k_dof calls.
+    z [H, W] float32 with row 0 = bottom (read_z_f32), rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params
+    from dof_params.  Returns the blurred frame and leaves its arguments alone."""
+    if not isinstance(params, DofParams):
+        raise ValueError("depth_of_field_host: params must come from dof_params")
+    zz = np.ascontiguousarray(z, np.float32)
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if zz.ndim != 2 or src.shape != zz.shape + (3,):
+        raise ValueError("depth_of_field_host: z [H, W] and rgb [H, W, 3]")
+    out = np.empty_like(src)
+    check(load_library().tr_dof_host(zz.shape[1], zz.shape[0], zz.ctypes.data, src.ctypes.data, out.ctypes.data, C.addressof(params)))
+    return out
+
+
+def dof_coc(params, z):
+    """tr_dof_coc: the circles of confusion (uint8, z's shape) of the depths z under params (dof_params)."""
+    if not isinstance(params, DofParams):
+        raise ValueError("dof_coc: params must come from dof_params")
+    zz = np.ascontiguousarray(z, np.float32)
+    out = np.empty(zz.shape, np.uint8)
+    check(load_library().tr_dof_coc(C.addressof(params), zz.size, zz.ctypes.data, out.ctypes.data))
+    return out
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -642,6 +701,39 @@ class Scene:
         kept frames, z, winner words and the shadow buffer stay.  Asynchronous; calling it twice averages twice."""
         n, w = accumulate_weights(n_frames, weights)
         check(load_library().tr_scene_accumulate(self._h, n, w.ctypes.data if w is not None else None, None))
+
+    # --- depth of field (tr_scene_depth_of_field / tr_scene_get_depth_of_field) ----------------------
+    def depth_of_field(self, params, out=None):
+        """tr_scene_depth_of_field: blurs the current frame by its own z buffer on the device (params from dof_params).
+        out=None: in place -- every later consumer (the getters, resolve, the sparse read-back, composite) sees the
+        blurred frame, z, winner words and the shadow buffer stay, calling it twice blurs twice.  Otherwise `out` is a
+        device pointer (int) to 3 * W * H bytes that overlaps no frame buffer of the scene, or an array from
+        pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().  Band
+        scenes are refused.  store_depth=True avoids the depth-only repeat of the frame's pass."""
+        if not isinstance(params, DofParams):
+            raise ValueError("depth_of_field: params must come from dof_params")
+        if out is None:
+            ptr = None
+        elif isinstance(out, np.ndarray):
+            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
+            ptr = out.ctypes.data
+        else:
+            ptr = int(out)
+        check(load_library().tr_scene_depth_of_field(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_depth_of_field(self, params, strict=True):
+        """tr_scene_get_depth_of_field: the current frame blurred on the device, as an [H, W, 3] uint8 array.
+        Synchronizes; the scene's frame stays unblurred."""
+        if not isinstance(params, DofParams):
+            raise ValueError("get_depth_of_field: params must come from dof_params")
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        code = load_library().tr_scene_get_depth_of_field(self._h, C.addressof(params), out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return out
 
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
