@@ -376,20 +376,40 @@ def device_buffer(n, fill=0x5A):
     return t
 
 
+# where the model stands at the shapes with partial tiles: over the corner of the partial tile column and row
+PLACE = {(208, 40): np.array([[0.3, 0.5, 0.0, 0.7]], np.float32), (144, 24): np.array([[0.6, 0.4, 0.0, 0.6]], np.float32)}
+RADII = ((1, 0), (3, 3), (8, 0), (8, 2))
+
+
+def partial_tiles_are_blurred(f, p, want):
+    """The drawn pixels with a circle > 0 whose output differs from the input, in the partial tile column and in the
+    partial tile row of the frame (z's orientation): both must exist."""
+    import tiny_renderer_amd as T
+    Hh, W = f["z"].shape
+    hit = (bits(f["z"]) != F32_MIN_BITS) & (T.dof_coc(p, f["z"]) > 0) & (want != f["fb"]).any(-1)[::-1]
+    assert W % 128 and Hh % 16
+    assert hit[:, W // 128 * 128:].any(), "no drawn, blurred pixel changes in the partial tile column"
+    assert hit[Hh // 16 * 16:].any(), "no drawn, blurred pixel changes in the partial tile row"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("store_depth", [False, True], ids=["transient", "stored"])
 @pytest.mark.parametrize("pipe", ["phong", "shadow"])
-@pytest.mark.parametrize("W,Hh", [(256, 48), (384, 48), (128, 16), (200, 40)])
+@pytest.mark.parametrize("W,Hh", [(256, 48), (384, 48), (128, 16), (200, 40), (208, 40), (144, 24)])
 def test_blurred_frame_equals_the_host_rule(small_synthetic, W, Hh, pipe, store_depth):
     """2 x 3 tiles, none with eight neighbours; 3 x 3 with a middle tile; one tile whose halo is all outside the frame;
-    the guarded path with a partial last tile column and row.  In place, for radii 1, 3 and 8."""
-    s = scene(W, Hh, small_synthetic, pipe, AT, tap=True, store_depth=store_depth)
+    the guarded path with a partial last tile column and row; the wide form with partial tiles in x and y (208 x 40), and
+    with a 16-pixel tile column over a half tile row (144 x 24) -- there the model stands over the partial tiles.  In
+    place, for radii 1, 3 and 8."""
+    s = scene(W, Hh, small_synthetic, pipe, PLACE.get((W, Hh), AT), tap=True, store_depth=store_depth)
     drive(s)
     f, before = snap(s), state(s)
-    for R, bg in ((1, 0), (3, 3), (8, 0), (8, 2)):
+    for R, bg in RADII:
         p = params_for(f, R, bg)
         want = host(f, p)
         assert not np.array_equal(want, f["fb"]), "the expectation is the unblurred frame"
+        if (W, Hh) in PLACE:
+            partial_tiles_are_blurred(f, p, want)
         drive(s)                                          # a fresh frame: depth and flags as a render leaves them
         s.depth_of_field(p)
         assert s.sync() == 0
@@ -616,6 +636,321 @@ def test_a_cleared_scene_held_back_frames_and_errors(small_synthetic):
     s.depth_of_field(p)
     assert not s.get_frame_buffer().any() and (bits(s.read_z_f32()) == F32_MIN_BITS).all()
     s.close(), band.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Paths of k_dof and of the in-place call that the cases above do not reach; each case asserts that it reaches its own
+# ------------------------------------------------------------------------------------------------------------------
+
+def device_bytes(ptr, n):
+    """A torch view of n bytes of device memory at ptr."""
+    import torch
+
+    class View:
+        __cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+
+    return torch.as_tensor(View(), device="cuda")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("place", ["out", "in"])
+def test_state_out_and_a_callers_frame_buffer_aligned_and_not(small_synthetic, place):
+    """256 x 48 takes the wide form unless an address says otherwise: `out`, and a caller's frame buffer blurred in place
+    (where the two stream-ordered copies write it), at 0, 4 and 16 bytes past a guard.  Every byte of the frame is the
+    rule's and no byte of the guards on either side changes."""
+    import torch
+    W, Hh = 256, 48
+    n = W * Hh * 3
+    ref = scene(W, Hh, small_synthetic, "phong", AT)
+    drive(ref)
+    f = snap(ref)
+    ref.close()
+    p = params_for(f, 8, 2)
+    want = host(f, p)
+    assert not np.array_equal(want, f["fb"])
+    guard = 48
+    buf = torch.full((guard + n + guard,), 0xAA, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    assert buf.data_ptr() % 16 == 0
+    for off in (0, 4, 16):      # (ascending: the bytes behind a frame have not held an earlier one)
+        at = buf.data_ptr() + guard + off
+        if place == "out":
+            d = scene(W, Hh, small_synthetic, "phong", AT)
+            drive(d)
+            d.depth_of_field(p, out=at)
+        elif off % 16 == 0:
+            d = scene(W, Hh, small_synthetic, "phong", AT, frame_buffer_device=at)
+            drive(d)
+            d.depth_of_field(p)
+        else:
+            # the scene's own kernels store whole 16-byte pieces, so it renders into its own buffer; the frame is copied
+            # to the odd address and handed over: the launcher must see the alignment and take the guarded form
+            d = scene(W, Hh, small_synthetic, "phong", AT)
+            drive(d)
+            assert d.sync() == 0
+            buf[guard + off:guard + off + n] = device_bytes(d.frame_buffer_device(), n)
+            torch.cuda.synchronize()
+            d.set_frame_buffer_device(at)
+            d.depth_of_field(p)
+        assert d.sync() == 0
+        torch.cuda.synchronize()
+        raw = buf.cpu().numpy()
+        assert np.array_equal(raw[guard + off:guard + off + n].reshape(Hh, W, 3), want), "offset %d" % off
+        assert (raw[:guard] == 0xAA).all() and (raw[guard + off + n:] == 0xAA).all(), "offset %d: a guard byte changed" % off
+        got = d.get_frame_buffer()
+        assert np.array_equal(got, f["fb"] if place == "out" else want)
+        d.close()
+
+
+VOTE_W, VOTE_H, VOTE_R = 512, 64, 8
+VOTE_AT = np.array([[-0.5, 0.0, 0.0, 2.0]], np.float32)    # larger than the frame: its flat middle fills whole tiles
+
+
+def vote_params(f):
+    """Focus on the nearest depth of the snapshot with a range of three tenths of it: the model's middle is sharp, its
+    rim partly blurred."""
+    z = f["z"][bits(f["z"]) != F32_MIN_BITS]
+    near = float(z.max())
+    return P(near, 6.0 / (0.3 * near), R=VOTE_R, rng=0.3 * near)
+
+
+def vote_tiles(f, p, want):
+    """[tiles_y, tiles_x] bool each, from the snapshot: (a) every circle of the tile itself is 0, a circle >= 2 lies in
+    its halo and a pixel of it changes; (b) the largest circle k_dof stages for it -- the tile and max_radius pixels
+    around, inside the frame -- lies strictly between 0 and max_radius; (c) drawn, nothing staged above 0, unchanged."""
+    import tiny_renderer_amd as T
+    coc = T.dof_coc(p, f["z"]).astype(np.int64)
+    R = int(p.max_radius)
+    changed = tiles_any((want != f["fb"]).any(-1)[::-1])
+    drawn = tiles_any(bits(f["z"]) != F32_MIN_BITS)
+    own, staged = np.zeros_like(changed, np.int64), np.zeros_like(changed, np.int64)
+    for j, i in np.ndindex(*changed.shape):
+        own[j, i] = coc[j * 16:j * 16 + 16, i * 128:i * 128 + 128].max()
+        staged[j, i] = coc[max(j * 16 - R, 0):j * 16 + 16 + R, max(i * 128 - R, 0):i * 128 + 128 + R].max()
+    return (own == 0) & (staged >= 2) & changed, (staged > 0) & (staged < R), drawn & (staged == 0) & ~changed
+
+
+def assert_vote_tiles(f, p, want):
+    a, b, c = vote_tiles(f, p, want)
+    assert a.any(), "no tile with circles of 0 alone takes colour from a circle >= 2 in its halo"
+    assert b.any(), "no tile whose tap loops stop between 0 and max_radius"
+    assert c.any(), "no drawn tile that is a plain copy"
+    return a, b, c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("store_depth", [False, True], ids=["transient", "stored"])
+def test_the_vote_counts_the_halo(small_synthetic, store_depth):
+    """4 x 4 tiles of the three kinds of vote_tiles: a vote over the tile's own pixels alone would copy the tiles of
+    kind (a)."""
+    s = scene(VOTE_W, VOTE_H, small_synthetic, "phong", VOTE_AT, store_depth=store_depth)
+    drive(s)
+    f = snap(s)
+    p = vote_params(f)
+    want = host(f, p)
+    a, b, c = assert_vote_tiles(f, p, want)
+    drive(s)
+    got = s.get_depth_of_field(p)
+    assert np.array_equal(got, want), "out of place: tiles %r differ" % (np.argwhere(tiles_any((got != want).any(-1)[::-1])).tolist(),)
+    s.depth_of_field(p)
+    got = s.get_frame_buffer()
+    assert np.array_equal(got, want), "in place: tiles %r differ" % (np.argwhere(tiles_any((got != want).any(-1)[::-1])).tolist(),)
+    s.close()
+
+
+STALE_W, STALE_H = 512, 64
+STALE_FIRST = np.array([[0.0, 0.0, 0.3, 1.0]], np.float32)
+STALE_THEN = ((-0.5, 0.0), (0.45, -0.1))
+
+
+def stale_fields(first, then, flags):
+    """What a kernel that ignored the z flags, or the colour flags, of the tiles around its own would read: the first
+    frame's z, or colour, in the tiles `flags` calls clean, the second frame's elsewhere."""
+    flagged = np.repeat(np.repeat(flags, 16, 0), 128, 1)[:then["z"].shape[0], :then["z"].shape[1]]
+    return ({"z": np.where(flagged, first["z"], then["z"]), "fb": then["fb"]},
+            {"z": then["z"], "fb": np.where(flagged[::-1, :, None], first["fb"], then["fb"])})
+
+
+def assert_stale_halo(first, then, flags, p, want):
+    """A tile that is clean now and was drawn before lies next to a tile that is drawn now, and either stale field
+    would show in the result."""
+    was = tiles_any(bits(first["z"]) != F32_MIN_BITS)
+    old = flags & was
+    assert old.any(), "no tile is clean now and was drawn before"
+    reach = False
+    for j, i in zip(*np.nonzero(old)):
+        reach = reach or (~flags[max(j - 1, 0):j + 2, max(i - 1, 0):i + 2]).any()
+    assert reach, "no such tile lies next to a drawn one"
+    for name, field in zip(("z", "colour"), stale_fields(first, then, flags)):
+        assert not np.array_equal(host(field, p), want), "stale %s would not show" % name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("store_depth", [False, True], ids=["transient", "stored"])
+@pytest.mark.parametrize("x,y", STALE_THEN)
+def test_a_stale_halo_reads_as_not_drawn(small_synthetic, x, y, store_depth):
+    """A large frame first (its depth in memory: stored, or fetched by one read of THAT frame), then the model moved to a
+    small place and rendered again with nothing read in between: the tiles it leaves hold the large frame's z behind
+    raised flags when k_dof stages its halos.  (Their COLOUR is zeros in memory by then -- a render stores zeros over a
+    tile it leaves, measured on a caller's buffer -- so k_dof ignoring the colour flags of its neighbours passes here.)
+    The expectation comes from scenes that rendered one frame each."""
+    W, Hh = STALE_W, STALE_H
+    one = scene(W, Hh, small_synthetic, "phong", STALE_FIRST, store_depth=store_depth)
+    drive(one)
+    first = snap(one)
+    one.close()
+    twin = scene(W, Hh, small_synthetic, "phong", TC._small(x, y), store_depth=store_depth)
+    drive(twin)
+    flags = clean_flags(twin)
+    then = snap(twin)
+    twin.close()
+    p = params_for(then, 8, near=True)
+    want = host(then, p)
+    assert_stale_halo(first, then, flags, p, want)
+    s = scene(W, Hh, small_synthetic, "phong", STALE_FIRST, store_depth=store_depth)
+    drive(s)
+    if not store_depth:
+        assert np.array_equal(bits(s.read_z_f32()), bits(first["z"]))
+    assert s.sync() == 0
+    s.set_instances(TC._small(x, y))
+    drive(s)
+    assert np.array_equal(s.get_depth_of_field(p), want), "out of place"
+    s.depth_of_field(p)
+    assert np.array_equal(s.get_frame_buffer(), want), "in place"
+    assert np.array_equal(bits(s.read_z_f32()), bits(then["z"]))
+    s.close()
+
+
+@pytest.mark.gpu
+def test_colour_over_undrawn_z_after_an_average_in_place(small_synthetic):
+    """z flag up, colour flag down: accumulate_in_place leaves colour of older frames in tiles the newest frame did not
+    draw.  background_radius 0 keeps it, 3 spreads it."""
+    from tests import test_accumulate as TA
+    W, Hh, n = 384, 48, 4
+    par = TA.views(n)
+    ref = scene(W, Hh, small_synthetic, "phong", frames_per_launch=n)
+    ref.render_frames(par)
+    avg = TA.oracle(TA.kept(ref, n))
+    f = {"fb": avg, "z": ref.read_z_f32()}
+    ref.close()
+    s = scene(W, Hh, small_synthetic, "phong", frames_per_launch=n)
+    s.render_frames(par)
+    s.accumulate_in_place(n)
+    flags = clean_flags(s)
+    mixed = ~tiles_any(bits(f["z"]) != F32_MIN_BITS) & ~flags & tiles_any(avg[::-1].any(-1))
+    assert mixed.any(), "no tile holds colour over undrawn z behind a lowered colour flag"
+    px = np.repeat(np.repeat(mixed, 16, 0), 128, 1)[::-1]
+    want = {bg: host(f, params_for(f, 3, bg)) for bg in (0, 3)}
+    assert not np.array_equal(want[0], avg) and not np.array_equal(want[3][px], want[0][px]), "the background radius does not show"
+    assert np.array_equal(s.get_depth_of_field(params_for(f, 3, 0)), want[0])
+    s.depth_of_field(params_for(f, 3, 3))
+    assert np.array_equal(s.get_frame_buffer(), want[3])
+    assert not (clean_flags(s) & tiles_any(want[3][::-1].any(-1))).any(), "a tile with colour in it is flagged clean"
+    assert np.array_equal(bits(s.read_z_f32()), bits(f["z"]))
+    s.close()
+
+
+@pytest.mark.gpu
+def test_a_trusted_buffer_whose_flags_are_up_over_drawn_z(small_synthetic):
+    """z flag down, colour flag up (the setup of tests/test_ambient_occlusion.py): two trusted caller's buffers, the
+    model on the left rendered into the first, on the right into the second, the first handed over again.  Its colour
+    reads as zeros where its flags are up, under the circles of the second frame's z."""
+    import torch
+    W, Hh = 512, 64
+    bufs = [torch.zeros(W * Hh * 3, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    torch.cuda.synchronize()
+    s = scene(W, Hh, small_synthetic, "phong", TC._small(-0.5, 0.0), frame_buffer_device=bufs[0].data_ptr(),
+              trust_frame_buffers=True, auto_group=False)
+    drive(s)
+    left, flags = s.get_frame_buffer(), clean_flags(s)
+    s.set_frame_buffer_device(bufs[1].data_ptr())
+    s.set_instances(TC._small(0.5, 0.0))
+    drive(s)
+    z = s.read_z_f32()
+    s.set_frame_buffer_device(bufs[0].data_ptr())
+    assert np.array_equal(clean_flags(s), flags), "a trusted buffer keeps its flags"
+    assert (flags & tiles_any(bits(z) != F32_MIN_BITS)).any(), "no flag is up over a drawn tile: the case shows nothing"
+    f = {"z": z, "fb": left}
+    p = params_for(f, 8, bg=2)
+    want = host(f, p)
+    assert not np.array_equal(want, left)
+    s.depth_of_field(p)
+    assert np.array_equal(s.resolve(2), box(want, 2)), "a consumer that skips clean tiles lost blurred pixels"
+    assert not (clean_flags(s) & tiles_any(want[::-1].any(-1))).any()
+    assert np.array_equal(s.get_frame_buffer(), want)
+    s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("buffers", ["own", "callers"])
+@pytest.mark.parametrize("store_depth", [False, True], ids=["transient", "stored"])
+def test_state_kept_frames_blur_the_selected_frame_only(small_synthetic, store_depth, buffers):
+    """Five views at four frames a launch; frame 1 is blurred in place with ITS z (rebuilt from the slot's own
+    parameters when depth is transient), every other kept frame and every z stays."""
+    import torch
+    W, Hh, n = 208, 40, 5
+    par = TC._params(n)
+    kept, want, p = [], None, None
+    for twin in (True, False):
+        s = scene(W, Hh, small_synthetic, "phong", AT, frames_per_launch=4, store_depth=store_depth)
+        store = torch.zeros(n * (W * Hh * 3 + 64), dtype=torch.uint8, device="cuda") if buffers == "callers" else None
+        torch.cuda.synchronize()
+        s.render_frames(par, None if store is None else [store.data_ptr() + k * (W * Hh * 3 + 64) for k in range(n)])
+        assert s.frames_kept() >= 3
+        if twin:
+            for back in range(3):
+                s.select_frame(back)
+                kept.append(snap(s))
+            p = params_for(kept[1], 3)
+            want = host(kept[1], p)
+            assert not np.array_equal(want, kept[1]["fb"]) and not np.array_equal(want, host(dict(kept[1], z=kept[0]["z"]), p))
+        else:
+            s.select_frame(1)
+            s.depth_of_field(p)
+            assert np.array_equal(s.get_frame_buffer(), want)
+            for back in (0, 2):
+                s.select_frame(back)
+                TC.same(snap(s), kept[back])
+            s.select_frame(1)
+            assert np.array_equal(s.get_frame_buffer(), want) and np.array_equal(bits(s.read_z_f32()), bits(kept[1]["z"]))
+        s.close()
+
+
+@pytest.mark.gpu
+def test_what_follows_a_blur_in_place(small_synthetic):
+    """A render without a clear on top of the blurred frame depth-tests against the unchanged z; resolve after
+    TR_DOF_SHOW_COC in place with a background radius reads the undrawn tiles, which are grey now."""
+    W, Hh = 512, 64
+    mk = lambda: scene(W, Hh, small_synthetic, "phong", TC._small(-0.4, 0.1))
+    ref = mk()
+    drive(ref)
+    f, flags = snap(ref), None
+    drive(ref, cam=-0.6)
+    f2 = snap(ref)
+    ref.close()
+    p = params_for(f, 8, near=True)
+    blurred = dict(f, fb=host(f, p), win=None)
+    want, wins = TC.merge(blurred, dict(f2, win=None))
+    assert wins.any() and not wins.all() and not np.array_equal(blurred["fb"], f["fb"])
+    s = mk()
+    drive(s)
+    flags = clean_flags(s)
+    s.depth_of_field(p)
+    drive(s, cam=-0.6, clear=False)
+    TC.same(snap(s), want)
+    show = params_for(f, 8, bg=1, flags=1)
+    grey = host(f, show)
+    undrawn = flags & ~tiles_any(bits(f["z"]) != F32_MIN_BITS)
+    assert undrawn.any()
+    drive(s)
+    assert np.array_equal(clean_flags(s), flags)
+    s.depth_of_field(show)
+    half = s.resolve(2)
+    assert np.array_equal(half, box(grey, 2))
+    for j, i in zip(*np.nonzero(undrawn)):
+        assert half[::-1][j * 8:j * 8 + 8, i * 64:i * 64 + 64].all(), "the undrawn tile (%d, %d) is not grey in the resolved frame" % (j, i)
+    assert not clean_flags(s).any(), "a grey tile kept its flag"
+    s.close()
 
 
 @pytest.mark.gpu
