@@ -408,8 +408,10 @@ int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb);
  * read nothing but the polygon, the uniforms and the textures -- `default`, `phong`, `normal_map`, `specular`, `darboux` --
  * merging scene(B) into scene(A), same size, camera, light and textures, winner_base = A's polygon count, is bit for bit
  * what one scene of the concatenated mesh A ++ B renders: colour, z and winner index.  `shadow` and `occlusion` merge by
- * the same rule, but their closures read the scene's OWN shadow buffer: B casts no shadow on A, so the result is not that
- * of a concatenated scene.  The scenes may differ in mesh, textures, pipeline, instance table, pose and options.
+ * the same rule, but their closures read the scene's OWN shadow buffer: after a plain tr_scene_render of each, B casts no
+ * shadow on A and the result is not that of a concatenated scene.  For those two, render the passes separately and merge
+ * the shadow buffers in between (tr_scene_render_shadow_pass, tr_scene_shadow_merge, tr_scene_render_colour_pass, below):
+ * the claim then holds for them as well.  The scenes may differ in mesh, textures, pipeline, instance table, pose and options.
  * Current frame: on both sides what the getters mean -- the last render's, a frame chosen with tr_scene_select_frame, the
  * caller's buffer after tr_scene_set_frame_buffer_device.
  * Pending work: frames tr_scene_render holds back are submitted, on both scenes; a pending clear of dst is made real; the
@@ -435,6 +437,67 @@ int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base);
 int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t *win_dst /* or NULL */,
                       const float *z_src, const uint8_t *rgb_src, const uint32_t *win_src /* or NULL */,
                       uint32_t winner_base);
+
+/* Shared shadows (nothing of the kind upstream): the two passes of `shadow` and `occlusion` as calls of their own, and the
+ * merge of two scenes' shadow buffers between them, so that composited models shade each other.
+ * Why it is exact: the reference's light-space pass is a running maximum without culling,
+ *     if z_value >= shadow_buffer[index] { shadow_buffer[index] = z_value }          (shader.rs:703, 841)
+ * and its shadow matrix depends on the light, look_at, up and the frame size alone (shader.rs:234-255).  So the shadow
+ * buffer of the concatenated mesh A ++ B is A's merged with B's by that same test, per pixel of the whole frame, with zs
+ * and zd the values tr_scene_read_shadow_f32 would return for src and dst:
+ *     if (zs >= zd) zd = zs
+ * bit for bit, the sign of a zero included (>= passes between +0.0 and -0.0: src's zero replaces dst's, as B's last
+ * zero fragment decides in the concatenated pass); a NaN on either side compares false and dst keeps its value; f32::MIN
+ * -- a pixel src never drew -- replaces nothing but f32::MIN.  The colour passes of the two pipelines read nothing shared
+ * but that buffer.  Hence, for two scenes A and B on `shadow` or `occlusion` with the same size, light and camera:
+ *     tr_scene_clear(A); tr_scene_clear(B);
+ *     tr_scene_render_shadow_pass(A); tr_scene_render_shadow_pass(B);
+ *     tr_scene_shadow_merge(A, B); tr_scene_shadow_merge(B, A);          -- both now hold the merged buffer
+ *     tr_scene_render_colour_pass(A); tr_scene_render_colour_pass(B);
+ *     tr_scene_composite(A, B, n_tri(A));
+ * leaves in A, bit for bit, what one scene of A ++ B renders: colour, z, winner index and shadow buffer.
+ *
+ * tr_scene_render_shadow_pass runs pass 0 of the scene's pipeline -- the light-space depth pass -- into the current
+ * frame's shadow buffer, under the current light, look_at, up and instance table / pose / palette.  It consumes a pending
+ * shadow clear (tr_scene_clear); a pending clear of z and colour stays pending.  Without a pending clear it raises the
+ * buffer as it stands, as tr_scene_render without a clear does.
+ * tr_scene_render_colour_pass runs the last pass against the shadow buffer as it stands -- looked up under the shadow
+ * matrix the buffer was last rendered, or merged, under.  It consumes the pending clear of z and colour; without one it
+ * depth-tests against the frame so far, whose depth is made real first as tr_scene_render does (TR_OPT_STORE_DEPTH).
+ *     tr_scene_clear; tr_scene_render_shadow_pass; tr_scene_render_colour_pass
+ * is in every byte -- colour, z, winner words, shadow buffer -- what tr_scene_clear; tr_scene_render produces.
+ * Both calls are asynchronous, submit first whatever tr_scene_render holds back, and are never held back or fused
+ * themselves.  Their passes count as handed on, as after tr_scene_composite: a bin overflow in one is reported by
+ * tr_scene_sync (TR_E_BIN_OVERFLOW, the pools grown: issue the calls again), never repaired by rendering the scene's
+ * last tr_scene_render again, which would run the scene's own shadow pass over a merged buffer.  tr_scene_render itself
+ * is unchanged.  A scene on a one-pass pipeline: TR_E_INVALID, nothing changed.
+ *
+ * tr_scene_shadow_merge merges src's current shadow buffer into dst's by the rule above.  The shadow buffer is the whole
+ * frame on a band scene as well (lookups are in light space, shader.rs:774-778), so the scenes' bands need not match.
+ * A src whose shadow buffer is logically cleared (tr_scene_clear and no shadow pass since): TR_OK, nothing happens.  A
+ * pending shadow clear of dst is made real first: dst then takes src's buffer.  Asynchronous: k_shadow_merge is enqueued
+ * on dst's stream behind src's work (an event recorded on src's stream), and src's stream then waits for it, so a later
+ * render of src cannot overwrite what the merge reads; the result is there after tr_scene_sync(dst).  Both scenes' passes
+ * issued so far count as handed on.  src is never written; colour, z and winner words of both scenes are untouched.
+ * Tiles (128 x 16) whose src fast-clear flag is up are skipped without reading a pixel; a dst tile behind its flag takes
+ * src's values without its stale memory being read.
+ * Each scene remembers the 16 floats of the shadow matrix its shadow buffer was last rendered under (tr_scene_render and
+ * the frame-group calls set them too; a merge into a cleared buffer hands src's on).
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene, dst == src, different devices,
+ * different width or height, either scene on a one-pass pipeline, shadow matrices that differ in any bit -- buffers taken
+ * under different lights do not merge into anything meaningful.  The matrices are compared only when BOTH current shadow
+ * buffers have one: a buffer no shadow pass has filled (a new scene's zeros, a frame slot not rendered into yet) or a dst
+ * with a pending clear merges under any light and takes over src's matrix.
+ * Out of scope: shadow passes of their own for the frames of a tr_scene_render_frames* group (a group renders both passes
+ * of every frame; select a kept frame and merge into that); a one-pass-pipeline scene as a shadow caster -- give its mesh
+ * a second scene on `shadow` and use that scene's shadow pass; an oracle of split passes (the oracle renders whole
+ * frames: the split is checked against them). */
+int tr_scene_render_shadow_pass(tr_scene *s);
+int tr_scene_render_colour_pass(tr_scene *s);
+int tr_scene_shadow_merge(tr_scene *dst, tr_scene *src);
+/* The rule above on the host (no GPU needed), by the very inline function k_shadow_merge calls: n values, dst updated in
+ * place.  n == 0: TR_OK; a NULL array with n > 0: TR_E_INVALID. */
+int tr_shadow_merge_host(size_t n, float *dst, const float *src);
 
 /* Screen-space ambient occlusion (upstream has only the light-space `occlusion` pipeline, shader.rs:806-960, which
  * costs a second geometry pass and replaces the picture by a grey one): the scene's CURRENT frame is darkened in place,

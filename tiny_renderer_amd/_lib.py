@@ -130,6 +130,10 @@ SYMBOLS = {
     "tr_scene_get_resolved": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "tr_scene_composite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "tr_composite_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "tr_scene_render_shadow_pass": (C.c_int, [C.c_void_p]),
+    "tr_scene_render_colour_pass": (C.c_int, [C.c_void_p]),
+    "tr_scene_shadow_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tr_shadow_merge_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p]),
     "tr_scene_ambient_occlusion": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_ao_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_ao_offsets": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),

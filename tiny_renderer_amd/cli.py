@@ -56,6 +56,10 @@ def main(argv=None):
                          "and light -- and merged into the picture by depth on the GPU (Scene.composite)")
     ap.add_argument("--with-shader", default=None, metavar="PIPELINE", help="shader pipeline of the --with model (default: -s)")
     ap.add_argument("--with-offset", default="0,0,0", metavar="X,Y,Z", help="where the --with model stands (an instance offset)")
+    ap.add_argument("--shared-shadows", action="store_true",
+                    help="with --with, both models on `shadow` or `occlusion`: render the light-space passes first, merge the "
+                         "two shadow buffers on the GPU (Scene.shadow_merge), then the colour passes -- the models shade each "
+                         "other as one scene of both would (needs --frames 1)")
     ap.add_argument("--ao", type=int, default=0, metavar="RADIUS",
                     help="screen-space ambient occlusion: darken the picture from its own z buffer on the GPU, samples on "
                          "rings of up to RADIUS (1..16) pixels (Scene.ambient_occlusion; after --with, before --ssaa resolves)")
@@ -108,6 +112,16 @@ def main(argv=None):
             assert len(args.with_offset) == 3
         except (ValueError, AssertionError):
             ap.error("--with-offset takes three numbers: x,y,z")
+    if args.shared_shadows:
+        from .scene import TWO_PASS_PIPELINES
+        if not args.with_path:
+            ap.error("--shared-shadows goes with --with DIR")
+        if args.pipeline not in TWO_PASS_PIPELINES or (args.with_shader or args.pipeline) not in TWO_PASS_PIPELINES:
+            ap.error("--shared-shadows needs a shadow buffer on both sides: -s and --with-shader must be `shadow` or `occlusion`")
+        if args.frames != 1 or args.shutter or args.seconds > 0 or args.gpus > 1:
+            ap.error("--shared-shadows renders one frame of one GPU pass by pass: use --frames 1 and --gpus 1, without --shutter "
+                     "and --seconds")
+        # (--bend and --morph-to pose the first model as scene state: the one frame's passes draw that pose)
     if args.bend is not None and (args.gpus > 1 or args.seconds > 0 or args.morph_to):
         ap.error("--bend skins the scene of one GPU, by frame count, without --morph-to: use --gpus 1 and --frames")
     if args.morph_to and (args.gpus > 1 or args.seconds > 0):
@@ -298,12 +312,25 @@ def _run(args, T, scene, sharded, rank, say):
         else:
             scene.render_frames(p)
         angles = []
+    if args.shared_shadows:
+        # one frame, pass by pass: both light-space passes, the shadow buffers merged both ways (each scene then holds
+        # the buffer of both models), both colour passes; the composite below finishes the picture
+        other = args.with_scene
+        for s in (scene, other):
+            s.clear()
+            s.set_light_direction([float(np.sin(la)), 0.0, float(np.cos(la))])
+            s.set_camera([float(np.sin(angles[0])), 0.0, float(np.cos(angles[0]))], [0, 0, 0], [0, 1, 0])
+        scene.render_shadow_pass(), other.render_shadow_pass()
+        scene.shadow_merge(other), other.shadow_merge(scene)
+        scene.render_colour_pass(), other.render_colour_pass()
+        scene.composite(other)
+        angles = []
     for ca in angles:
         scene.clear()                                                        # app.rs:170
         scene.set_light_direction([float(np.sin(la)), 0.0, float(np.cos(la))])   # app.rs:203-208
         scene.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])  # app.rs:200-209
         scene.render()                                                       # app.rs:210
-    if args.with_scene is not None:
+    if args.with_scene is not None and not args.shared_shadows:
         # the second model under the last frame's camera and light, merged into the picture before it is read
         ca = np.float32(args.camera_angle + (2.0 * np.pi * (args.frames - 1) / args.frames if args.frames > 1 else 0.0))
         other = args.with_scene

@@ -10,6 +10,7 @@
 #include "tr_composite.h"
 #include "tr_dof.h"
 #include "tr_morph.h"
+#include "tr_shadow_merge.h"
 #include "tr_skin.h"
 #include "tr_types.h"
 
@@ -69,6 +70,10 @@ int launch_resolve(const uint8_t *fb, uint8_t *out, const uint32_t *fb_clean, co
 // Depth compositing: src's frame into dst's over the tiles of dst's band, by the rule of tr_composite.h and through both
 // scenes' fast-clear flags: k_composite.  The caller orders the launch behind the work that produced both frames.
 int launch_composite(const CompositeArgs &a, hipStream_t st);
+// Shared shadows: src's shadow buffer into dst's over the tiles of the whole frame, by the rule of tr_shadow_merge.h and
+// through both scenes' fast-clear flags: k_shadow_merge.  The caller orders the launch behind the work that produced
+// both buffers and has made a pending clear of dst real (every flag up).
+int launch_shadow_merge(const ShadowMergeArgs &a, hipStream_t st);
 // Ambient occlusion: the frame's colour shaded in place from its own z buffer by the rule of tr_ao.h, through the
 // scene's fast-clear flags: k_ao.  The whole frame only (no band); the caller has made the depth real.
 int launch_ao(const AoArgs &a, hipStream_t st);

@@ -1946,6 +1946,84 @@ __global__ __launch_bounds__(8 * TILE_H) void k_composite(CompositeArgs a)
     }
 }
 
+// Shared shadows (tr_scene_shadow_merge): scene src's shadow buffer merged into scene dst's by the reference's
+// light-space test (tr_shadow_merge.h has the rule).  One workgroup of 256 lanes per 128 x 16 tile of the WHOLE frame
+// (a shadow buffer is full-frame on a band scene too); a tile is 16 rows of 32 four-pixel pieces, a lane owns the piece
+// at column 4 * (lane % 32) of rows lane / 32 and lane / 32 + 8, lanes run along the row first: a wavefront's load is
+// two contiguous 512-byte row segments.  Decided on the two fast-clear flags:
+//   * src's flag up: every value of src's tile is f32::MIN, which replaces nothing -- the workgroup leaves having loaded
+//     one word, before any barrier;
+//   * src's down, dst's up: every zd is f32::MIN and dst's stale memory is not read; every pixel of the tile inside the
+//     frame is stored and the flag comes down.  The one barrier separates every lane's load of dst's flag from lane 0's
+//     store to it (the branch is workgroup-uniform: all lanes read the same word);
+//   * both down: elementwise; a piece is stored only where the merge changed a bit of it.
+// The stores and the lowered flag are ordered before the colour pass that follows on the stream by the kernel boundary.
+// WIDE: width % 4 == 0 and both buffers 16-byte aligned (the launcher checks): a piece is one 16-byte load per buffer
+// and one store, and lies wholly inside or outside the row; otherwise the same pieces through element loads and stores
+// guarded by the width.  Bytes per pixel of a tile that is read: 4 + 4 read, up to 4 written.  No LDS, no atomics.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_shadow_merge(ShadowMergeArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H == 16, "a tile is 16 rows of 32 four-pixel pieces, two pieces per lane");
+    const uint32_t t = blockIdx.x;
+    if (a.src_clean[t] != 0u) return;  // (workgroup-uniform, ahead of the barrier)
+    const bool d_clean = a.dst_clean[t] != 0u;
+    if (d_clean) {
+        __syncthreads();
+        if (threadIdx.x == 0u) a.dst_clean[t] = 0u;
+    }
+    const int32_t W = (int32_t)a.frame.width;
+    const int32_t x = (int32_t)(t % a.frame.ntx) * TILE_W + (int32_t)(threadIdx.x % 32u) * 4;
+    const int32_t y0 = (a.frame.ty_base + (int32_t)(t / a.frame.ntx)) * TILE_H + (int32_t)(threadIdx.x / 32u);
+    const float fmin = bits_f32(TR_F32_MIN_BITS);
+    float zs[2][4], zd[2][4];
+    size_t at[2];
+    int32_t n_px[2];  // pixels of the piece inside the frame (WIDE: 4 or none)
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const int32_t y = y0 + 8 * r;
+        const bool inside = x < W && y >= a.frame.band_y0 && y < a.frame.band_y1;
+        n_px[r] = inside ? min(4, W - x) : 0;
+        at[r] = inside ? (size_t)y * (size_t)W + (size_t)x : 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) zs[r][i] = zd[r][i] = fmin;
+        if (n_px[r] == 0) continue;
+        if (WIDE) {
+            const float4 s = *reinterpret_cast<const float4 *>(a.src + at[r]);
+            zs[r][0] = s.x, zs[r][1] = s.y, zs[r][2] = s.z, zs[r][3] = s.w;
+            if (!d_clean) {
+                const float4 d = *reinterpret_cast<const float4 *>(a.dst + at[r]);
+                zd[r][0] = d.x, zd[r][1] = d.y, zd[r][2] = d.z, zd[r][3] = d.w;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px[r]) {
+                    zs[r][i] = a.src[at[r] + i];
+                    if (!d_clean) zd[r][i] = a.dst[at[r] + i];
+                }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        if (n_px[r] == 0) continue;
+        float m[4];
+        uint32_t changed = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            m[i] = shadow_merge(zs[r][i], zd[r][i]);
+            if (f32_bits(m[i]) != f32_bits(zd[r][i])) changed |= 1u << i;
+        }
+        if (WIDE) {
+            if (d_clean || changed != 0u) *reinterpret_cast<float4 *>(a.dst + at[r]) = make_float4(m[0], m[1], m[2], m[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px[r] && (d_clean || ((changed >> i) & 1u))) a.dst[at[r] + i] = m[i];
+        }
+    }
+}
+
 // Screen-space ambient occlusion (tr_scene_ambient_occlusion): the frame's colour darkened in place from its own z
 // buffer (tr_ao.h has the rule).  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_composite.
 //   * the tile's own z flag up: nothing is drawn there -- the workgroup leaves having loaded one word, before any barrier;
@@ -2994,6 +3072,21 @@ int launch_composite(const CompositeArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_composite<true>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
     else
         hipLaunchKernelGGL((k_composite<false>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_shadow_merge(const ShadowMergeArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.dst || !a.dst_clean || !a.src || !a.src_clean) return (int)hipErrorInvalidValue;
+    // the wide path: every piece is one aligned 16-byte word of each buffer
+    const bool wide = a.frame.width % 4u == 0u && ((uintptr_t)a.dst | (uintptr_t)a.src) % 16u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_shadow_merge<true>), dim3(n_tiles), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_shadow_merge<false>), dim3(n_tiles), dim3(256), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

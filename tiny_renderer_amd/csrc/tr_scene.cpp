@@ -93,8 +93,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -323,6 +323,10 @@ struct tr_scene {
         bool z_deferred = false;
         tr_frame_params z_params = {};
         InstRef z_inst;  // ... and the instance table it was rendered with
+        // The shadow matrix (shader.rs:234-255) the slot's shadow buffer was last rendered under -- or took over with a
+        // merged buffer: what tr_scene_shadow_merge compares and tr_scene_render_colour_pass looks the buffer up with
+        float shadow_matrix[16] = {};
+        bool shadow_matrix_set = false;
     };
     std::vector<FrameSlot> slots;
     int cur_slot = 0;
@@ -1354,6 +1358,13 @@ static bool fused_single_launches()
     return on;
 }
 
+// A slot's shadow buffer is about to be rendered under shadow matrix `m` (16 floats).
+void note_shadow_matrix(tr_scene::FrameSlot &slot, const float *m)
+{
+    memcpy(slot.shadow_matrix, m, sizeof slot.shadow_matrix);
+    slot.shadow_matrix_set = true;
+}
+
 // depth_only: the repeat of a colour pass for its depth alone (ensure_depth): from cleared targets, nothing of the
 // scene's clear / colour state is consumed or changed.
 int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
@@ -1373,6 +1384,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
     if (depth_pass) {
         fresh = s->shadow_cleared ? 1u : 0u;
         s->shadow_cleared = false;
+        note_shadow_matrix(s->slots[(size_t)s->cur_slot], du.shadow_matrix);
     } else if (depth_only) {
         fresh = 1u;
     } else {
@@ -1880,6 +1892,7 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
             memset(&ta, 0, sizeof ta);
             st = pass_uniforms(s, pass, sa.u);
             if (st != TR_OK) break;
+            if (depth_pass) note_shadow_matrix(slot, sa.u.shadow_matrix);
             const DevFrame &frame = depth_pass ? s->frame_full : s->frame;
             sa.mesh = mesh;
             sa.frame = frame;
@@ -2945,6 +2958,8 @@ int tr_scene_render(tr_scene *s)
             return st;
         }
     }
+    // (the frame's shadow pass is still to come, into the current slot: its matrix is known now)
+    if (pd.n_passes == 2) note_shadow_matrix(s->slots[(size_t)s->cur_slot], s->uniforms.shadow_matrix);
     tr_scene::DeferredFrame f;
     memcpy(f.p.light, s->light, 12); memcpy(f.p.look_from, s->from, 12);
     memcpy(f.p.look_at, s->at, 12); memcpy(f.p.up, s->up, 12);
@@ -3554,6 +3569,108 @@ int tr_composite_host(size_t n_pixels, float *z_dst, uint8_t *rgb_dst, uint32_t 
         memcpy(rgb_dst + 3 * i, rgb_src + 3 * i, 3);
         if (win_dst) win_dst[i] = composite_winner(win_src[i], winner_base);
     }
+    return TR_OK;
+}
+
+namespace {
+
+// tr_scene_render_shadow_pass / tr_scene_render_colour_pass: one pass of a two-pass pipeline, through run_pass like a
+// frame of tr_scene_render's -- but submitted at once, never fused, and handed on: recover_from_overflow would replay
+// s->last, the scene's own shadow pass included, over a buffer that may since have been merged.
+int render_split_pass(tr_scene *s, bool colour, const char *who)
+{
+    if (!s) return tr::fail(TR_E_INVALID, std::string(who) + ": null scene");
+    const PipelineDesc &pd = kPipelines[s->pipeline];
+    if (pd.n_passes != 2)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": the scene's pipeline `" + pd.name + "` has one pass (shadow and occlusion have two)");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(s->device));
+    int st = submit_pending(s);  // what tr_scene_render holds back goes first
+    if (st != TR_OK) return st;
+    s->host_status = TR_OK;
+    if (colour) {
+        // without a clear the pass depth-tests against the frame so far: its depth must be in memory
+        if (!s->z_fb_cleared && (st = ensure_depth(s)) != TR_OK) return st;
+        // the buffer as it stands is looked up under the matrix it was rendered (or merged) under; the reference's
+        // second prepare leaves the first one's shadow matrix in place the same way (shader.rs:259-279)
+        const tr_scene::FrameSlot &slot = s->slots[(size_t)s->cur_slot];
+        if (slot.shadow_matrix_set) memcpy(s->uniforms.shadow_matrix, slot.shadow_matrix, sizeof slot.shadow_matrix);
+    }
+    st = run_pass(s, pd.pass[colour ? 1 : 0]);
+    if (st == TR_OK) st = submit_pending_tiles(s);
+    if (st != TR_OK) {
+        s->host_status = st;
+        return st;
+    }
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_render_shadow_pass(tr_scene *s) { return render_split_pass(s, false, "tr_scene_render_shadow_pass"); }
+
+int tr_scene_render_colour_pass(tr_scene *s) { return render_split_pass(s, true, "tr_scene_render_colour_pass"); }
+
+int tr_scene_shadow_merge(tr_scene *dst, tr_scene *src)
+{
+    if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: null scene");
+    if (dst == src) return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: dst and src are the same scene");
+    if (dst->device != src->device) return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: the scenes are on different devices");
+    if (dst->width != src->width || dst->height != src->height)
+        return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: the scenes' frames differ in width or height");
+    if (kPipelines[dst->pipeline].n_passes != 2 || kPipelines[src->pipeline].n_passes != 2)
+        return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: a scene's pipeline has one pass and no shadow buffer of its own "
+                                      "(shadow and occlusion have two)");
+    if (dst->broken || src->broken)
+        return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (src->shadow_cleared) return TR_OK;  // a logically cleared buffer holds f32::MIN alone: it replaces nothing
+    tr_scene::FrameSlot &ds = dst->slots[(size_t)dst->cur_slot];
+    const tr_scene::FrameSlot &ss = src->slots[(size_t)src->cur_slot];
+    // (a buffer no shadow pass has filled since the scene was created has no matrix: it holds the zeros of Buffer::new,
+    // shader.rs:46-47, which merge by the rule under any)
+    if (!dst->shadow_cleared && ds.shadow_matrix_set && ss.shadow_matrix_set &&
+        memcmp(ds.shadow_matrix, ss.shadow_matrix, sizeof ds.shadow_matrix) != 0)
+        return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: the shadow buffers were rendered under different shadow matrices "
+                                      "(light, look_at, up or frame size differ)");
+    HIP_TRY(hipSetDevice(dst->device));
+    // both buffers on their way; a pending clear of dst made real (every flag up)
+    int st = submit_pending(src);
+    if (st == TR_OK) st = submit_pending(dst);
+    if (st == TR_OK) st = flush_clear_shadow(dst);
+    if (st != TR_OK) return st;
+    if (!src->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&src->ev_comp_ready, hipEventDisableTiming));
+    if (!dst->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&dst->ev_comp_done, hipEventDisableTiming));
+    ShadowMergeArgs a = {};
+    a.dst = dst->d_shadow;
+    a.dst_clean = dst->d_sclean;
+    a.src = src->d_shadow;
+    a.src_clean = src->d_sclean;
+    a.frame = dst->frame_full;
+    // behind src's shadow pass on dst's stream; src's stream behind the merge: a later render of src does not overtake it
+    HIP_TRY(hipEventRecord(src->ev_comp_ready, src->stream));
+    HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_comp_ready, 0));
+    {
+        Timed t(dst, K_SHADOW_MERGE);
+        int rc = launch_shadow_merge(a, dst->stream);
+        if (rc) return launch_status(rc, "k_shadow_merge");
+    }
+    HIP_TRY(hipEventRecord(dst->ev_comp_done, dst->stream));
+    HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_comp_done, 0));
+    if (ss.shadow_matrix_set) note_shadow_matrix(ds, ss.shadow_matrix);  // (equal already, or dst's buffer had none)
+    dst->quiescent = src->quiescent = false;
+    // both scenes' passes are now in a consumer's hands (as in tr_scene_composite): replaying a frame after a bin
+    // overflow would run the scene's own shadow pass over the merged buffer, or change what the merge read
+    dst->observed_seq = dst->pass_seq;
+    src->observed_seq = src->pass_seq;
+    return TR_OK;
+}
+
+// The rule of tr_shadow_merge.h over caller's arrays, on the host.  Needs no GPU.
+int tr_shadow_merge_host(size_t n, float *dst, const float *src)
+{
+    if (n && (!dst || !src)) return tr::fail(TR_E_INVALID, "tr_shadow_merge_host: null argument");
+    for (size_t i = 0; i < n; i++) dst[i] = shadow_merge(src[i], dst[i]);
     return TR_OK;
 }
 

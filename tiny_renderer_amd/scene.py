@@ -174,6 +174,21 @@ def composite_host(z_dst, rgb_dst, z_src, rgb_src, win_dst=None, win_src=None, w
     return (z, rgb) if win is None else (z, rgb, win)
 
 
+def shadow_merge_host(dst, src):
+    """tr_shadow_merge_host: the rule of Scene.shadow_merge on the host (no GPU needed), by the inline function
+    k_shadow_merge calls -- per value `if (zs >= zd) zd = zs`, the reference's light-space test.  Two float32 arrays of
+    one shape; returns the merged array and leaves its arguments alone."""
+    z = np.array(dst, np.float32, order="C")
+    zs = np.ascontiguousarray(src, np.float32)
+    if zs.shape != z.shape:
+        raise ValueError("shadow_merge_host: the arrays must have one shape")
+    check(load_library().tr_shadow_merge_host(z.size, z.ctypes.data, zs.ctypes.data))
+    return z
+
+
+TWO_PASS_PIPELINES = ("shadow", "occlusion")   # the pipelines with a light-space depth pass and a shadow buffer of their own
+
+
 AO_MAX_RADIUS, AO_MAX_RINGS = 16, 4   # (TR_AO_MAX_RADIUS, TR_AO_MAX_RINGS)
 
 
@@ -656,6 +671,39 @@ class Scene:
         if (src.width, src.height) != (self.width, self.height):
             raise ValueError("composite: src is %d x %d, this scene %d x %d" % (src.width, src.height, self.width, self.height))
         check(load_library().tr_scene_composite(self._h, src._h, int(winner_base) & 0xFFFFFFFF))
+
+    # --- shared shadows (tr_scene_render_shadow_pass / _colour_pass, tr_scene_shadow_merge) ----------
+    def _two_pass(self, who):
+        if getattr(self, "pipeline", None) not in TWO_PASS_PIPELINES:
+            raise ValueError("%s: pipeline %r has one pass (shadow and occlusion have two)" % (who, getattr(self, "pipeline", None)))
+
+    def render_shadow_pass(self):
+        """tr_scene_render_shadow_pass: the light-space depth pass of `shadow` / `occlusion` alone, into the current
+        frame's shadow buffer; consumes a pending shadow clear, a pending clear of z and colour stays pending."""
+        self._two_pass("render_shadow_pass")
+        check(load_library().tr_scene_render_shadow_pass(self._h))
+
+    def render_colour_pass(self):
+        """tr_scene_render_colour_pass: the colour pass of `shadow` / `occlusion` alone, against the shadow buffer as it
+        stands (the scene's own, or one merged with another scene's).  clear(); render_shadow_pass(); render_colour_pass()
+        is render() after clear() in every byte."""
+        self._two_pass("render_colour_pass")
+        check(load_library().tr_scene_render_colour_pass(self._h))
+
+    def shadow_merge(self, src):
+        """tr_scene_shadow_merge: merges the shadow buffer of scene `src` into this scene's on the device, per pixel
+        `if (zs >= zd) zd = zs` -- the buffer of the two meshes concatenated, when both shadow passes ran under one
+        light and camera.  Asynchronous; both scenes on `shadow` or `occlusion`, of one size and on one device; bands
+        need not match.  src is not written."""
+        if src is self:
+            raise ValueError("shadow_merge: src is this scene")
+        if not isinstance(src, Scene):
+            raise ValueError("shadow_merge: src must be a Scene")
+        if (src.width, src.height) != (self.width, self.height):
+            raise ValueError("shadow_merge: src is %d x %d, this scene %d x %d" % (src.width, src.height, self.width, self.height))
+        self._two_pass("shadow_merge")
+        src._two_pass("shadow_merge (src)")
+        check(load_library().tr_scene_shadow_merge(self._h, src._h))
 
     def ambient_occlusion(self, radius=8, rings=1, threshold=1.0, falloff=20.0, grey=False):
         """tr_scene_ambient_occlusion: darkens the current frame in place on the device from its own z buffer -- `rings`
