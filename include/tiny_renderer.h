@@ -658,6 +658,55 @@ int tr_dof_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up
 /* The circles of confusion of n depths under the parameters (coc: n bytes). */
 int tr_dof_coc(const tr_dof_params *p, uint32_t n, const float *z, uint8_t *coc);
 
+/* Dynamic textures (nothing of the kind upstream, whose four images are moved into Scene::new and never change): one of a
+ * scene's images -- `which` = 0..3 in tr_scene_create's order: texture, normal_map, normal_map_tangent, specular_map --
+ * replaced on the device, from host memory, from device memory or from another scene's (or the scene's own) current
+ * frame: an animated or painted texture without a new scene, and render-to-texture without a read-back -- a screen inside
+ * a scene, an impostor, a picture of model A on model B, feedback of a scene's own last frame.
+ * The rule: the image is w x h tightly packed rgb8, row 0 = top -- image::RgbImage, and exactly what
+ * tr_scene_get_frame_buffer returns.  After the call texture `which` of the scene IS that image: every render issued
+ * later, in every pipeline and on every path (per-frame, held back and fused, tr_scene_render_frames*, the split
+ * shadow / colour passes), draws bit for bit what a scene created with tex[which] replaced by that image draws -- colour,
+ * z, winner words, shadow buffer and device status (TR_E_OOB_LOOKUP included).  w and h must equal the replaced image's
+ * own size (a texture is not resized: TR_E_INVALID), so whether the scene keeps a texel set, the set's layout and the
+ * choice of the lit path never change.
+ * Ordering: the three setters are asynchronous.  Frames tr_scene_render holds back on the scene are submitted first and
+ * keep the old texture, as do all frames issued earlier, a frame whose read-back is still queued included; k_pack_texels
+ * is enqueued on the scene's stream behind all of them.  The scene's passes issued so far count as handed on, as after
+ * tr_scene_composite: a bin overflow among them is reported (TR_E_BIN_OVERFLOW), never repaired by a re-render, which
+ * would draw the new texture.  Kept frames (tr_scene_select_frame) stay what they are.
+ * tr_scene_set_texture: host memory, copied before the call returns (through a device staging buffer on a stream of
+ * the library's: the copy does not queue behind the scene's renders; with more than eight such calls in flight the
+ * oldest is waited for).
+ * tr_scene_set_texture_device: rgb_device is 3 * w * h bytes of device memory, or memory from tr_host_alloc.  producer:
+ * the scene whose stream produced it (tr_scene_resolve, tr_scene_accumulate, tr_scene_depth_of_field with `out`): the
+ * kernel runs behind producer's work -- an event on its stream -- and producer's stream then waits for the kernel, the way
+ * tr_scene_composite orders dst behind src.  producer == NULL: the caller guarantees that rgb_device is complete with
+ * respect to the scene's stream, and keeps it unchanged until the kernel has run (tr_scene_sync).
+ * tr_scene_set_texture_from_frame: src's CURRENT frame as the getters mean it -- the last render's, a kept frame chosen
+ * with tr_scene_select_frame, a caller's buffer, a merged, shaded, averaged or blurred frame -- becomes dst's image;
+ * src's frame size must equal the texture's size; src == dst is allowed (feedback).  What src holds back is submitted
+ * first.  A logically cleared src (tr_scene_clear and nothing rendered since) gives an image of zeros.  Tiles (128 x 16)
+ * whose colour-clean flag is up in src are not read: their texels are zeros.  Ordered behind src like a producer.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene, image or pointer, which > 3,
+ * a size that is not the replaced image's, ordinary host memory as rgb_device, a producer or src on another device, a
+ * band scene (tr_options.band_row0/1) as src, rgb_device overlapping the scene's own texel arrays.
+ * tr_scene_read_texture: image `which` as the scene holds it now, 3 * w * h bytes; synchronizes. */
+int tr_scene_set_texture(tr_scene *s, uint32_t which, const tr_image_rgb8 *image);
+int tr_scene_set_texture_device(tr_scene *s, uint32_t which, const void *rgb_device, uint32_t w, uint32_t h,
+                                tr_scene *producer /* or NULL */);
+int tr_scene_set_texture_from_frame(tr_scene *dst, uint32_t which, tr_scene *src);
+int tr_scene_read_texture(tr_scene *s, uint32_t which, uint8_t *rgb /* 3*w*h */);
+/* Diagnostic: the scene's texel set (csrc/tr_texels.h: the images its colour closure reads, interleaved texel by texel
+ * and tiled into 128-byte blocks; a scene whose four images differ in size has none) copied to `words`; synchronizes.
+ * Returns the number of words, 0 when the scene has no set; cap_words smaller than the set: TR_E_INVALID. */
+int tr_scene_debug_texel_set(tr_scene *s, uint32_t *words, size_t cap_words);
+/* The set tr_scene_create builds for `pipeline_name` from four images of one size, on the host (no GPU needed), by the
+ * very function tr_scene_create calls; blocks_per_row (may be NULL) receives the blocks per row of blocks.  Returns the
+ * number of words; cap_words too small, images of different sizes: TR_E_INVALID. */
+int tr_texel_set_host(const char *pipeline_name, const tr_image_rgb8 tex[4], uint32_t *words, size_t cap_words,
+                      uint32_t *blocks_per_row);
+
 /* Device-resident access for callers that keep the frame on the GPU. */
 int tr_scene_sync(tr_scene *s);                 /* wait for queued work; returns frame status */
 int tr_scene_flush(tr_scene *s);                /* hand every render issued so far to the device (the library

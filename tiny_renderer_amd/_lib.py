@@ -144,6 +144,12 @@ SYMBOLS = {
     "tr_scene_get_depth_of_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_dof_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_dof_coc": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ImageRgb8)]),
+    "tr_scene_set_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "tr_scene_set_texture_from_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_read_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_debug_texel_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "tr_texel_set_host": (C.c_int, [C.c_char_p, C.POINTER(ImageRgb8), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "tr_host_alloc": (C.c_void_p, [C.c_size_t]),
     "tr_host_free": (None, [C.c_void_p]),
     "tr_scene_host_buffer_written": (C.c_int, [C.c_void_p, C.c_void_p]),

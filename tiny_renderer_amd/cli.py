@@ -56,6 +56,10 @@ def main(argv=None):
                          "and light -- and merged into the picture by depth on the GPU (Scene.composite)")
     ap.add_argument("--with-shader", default=None, metavar="PIPELINE", help="shader pipeline of the --with model (default: -s)")
     ap.add_argument("--with-offset", default="0,0,0", metavar="X,Y,Z", help="where the --with model stands (an instance offset)")
+    ap.add_argument("--paint-with", dest="paint_path", default=None, metavar="DIR",
+                    help="render the model of this asset folder at the size of the main model's diffuse texture and use that "
+                         "frame as the texture (on the device: tr_scene_set_texture_from_frame) before the main render")
+    ap.add_argument("--paint-shader", default=None, metavar="PIPELINE", help="shader pipeline of the --paint-with model (default: -s)")
     ap.add_argument("--shared-shadows", action="store_true",
                     help="with --with, both models on `shadow` or `occlusion`: render the light-space passes first, merge the "
                          "two shadow buffers on the GPU (Scene.shadow_merge), then the colour passes -- the models shade each "
@@ -206,6 +210,21 @@ def main(argv=None):
         say("two-bone rig: upper bone turned about z by %g degrees" % args.bend)
         scene.set_skin(*bend_rig(mesh), n_bones=2)
         scene.set_bone_palette(bend_palette(T, args.bend))
+    if args.paint_path:
+        if sharded:
+            raise SystemExit("--paint-with needs one scene of the whole frame (--gpus 1)")
+        th, tw = texs[0].shape[:2]
+        say("diffuse texture painted with: %s/model.obj ('%s' shader pipeline, %d x %d)"
+            % (args.paint_path, args.paint_shader or args.pipeline, tw, th))
+        mesh3, texs3 = T.load_assets(args.paint_path)
+        painter = T.Scene(tw, th, mesh3, texs3, args.paint_shader or args.pipeline, device=args.device)
+        painter.clear()
+        painter.set_light_direction([float(np.sin(args.light_angle)), 0.0, float(np.cos(args.light_angle))])
+        painter.set_camera([float(np.sin(args.camera_angle)), 0.0, float(np.cos(args.camera_angle))], [0.0, 0.0, 0.0], [0.0, 1.0, 0.0])
+        painter.render()
+        scene.set_texture_from(painter, 0)
+        scene.sync()       # (the texture is in place: the painter can go)
+        painter.close()
     args.with_scene = None
     if args.with_path:
         say("second model from: %s/model.obj ('%s' shader pipeline, at %s)" % (args.with_path, args.with_shader or args.pipeline,

@@ -10,6 +10,7 @@
 #include "tr_composite.h"
 #include "tr_dof.h"
 #include "tr_morph.h"
+#include "tr_pack.h"
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
 #include "tr_types.h"
@@ -85,6 +86,10 @@ int launch_accumulate(const AccumulateArgs &a, hipStream_t st);
 // fast-clear flags of z and of colour: k_dof.  The whole frame only (no band); the caller has made the depth real.
 // a.out_clean: null, or the flags of `out` the kernel writes.
 int launch_dof(const DofArgs &a, hipStream_t st);
+// Dynamic textures: image a.src into the plain array a.texel and the owned words of the texel set a.set (words per texel:
+// 1 or 4; a.set null: the plain array alone) by the rule of tr_pack.h, through the source's colour-clean flags when it
+// is a frame: k_pack_texels.  The caller orders the launch behind whatever reads the arrays and produced the source.
+int launch_pack_texels(const PackArgs &a, int words, hipStream_t st);
 // Morph targets: the posed rows of n_frames frames (<= MORPH_MAX_FRAMES) by one launch -- frame f blends the mesh's
 // gathered rows `base` (n_rows x TRI_FLOATS) with the gathered delta rows `delta` (n_targets x n_rows x TRI_FLOATS) under
 // the weights tab.f[f].w (device memory) into tab.f[f].dst: k_morph, tr_morph.h.

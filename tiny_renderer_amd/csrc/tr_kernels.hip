@@ -35,6 +35,7 @@
 #include "tr_dof.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
+#include "tr_pack.h"
 #include "tr_plan.h"
 #include "tr_resolve.h"
 #include "tr_shaders.h"
@@ -2485,6 +2486,63 @@ __global__ __launch_bounds__(DOF_THREADS) void k_dof(DofArgs a)
     dof_store_share<WIDE>(o, px, n_px);
 }
 
+// Dynamic textures (tr_scene_set_texture*): image `which` of a scene replaced by a w x h image of packed rgb8 rows, in
+// the plain array and in the texel set together; tr_pack.h has the rule (pack_quad, shared with the host).  The grid is
+// that of a frame of w x h pixels -- the image may BE one (tr_scene_set_texture_from_frame): a workgroup of 256 lanes
+// covers 128 x 8 texels, half of a 128 x 16 frame tile, so the source's colour-clean flag is ONE workgroup-uniform word,
+// read before any pixel: a tile whose flag is up is not loaded and packs as zeros (decode_normal(0) in the normal
+// words).  A lane owns four horizontally adjacent texels:
+//   * WIDE (width % 4 == 0, every base aligned: the launcher checks): their 12 source bytes are three dword loads, the
+//     other image's words (word 0 of a four-word set is completed from them) one 16-byte load, the plain array's
+//     words one 16-byte store; else bytes and words guarded by the width;
+//   * the set's words go where packed_index puts them: one 16-byte store into an 8 x 4 block (one-word sets), the owned
+//     words of 64 contiguous bytes of a 4 x 2 block (four-word sets: four word-0 stores, or words 1..3 of each texel).
+// Rows of a tile count from the bottom of the frame, rows of the image from the top.  No LDS, no atomics, no scratch.
+constexpr uint32_t PACK_ROWS = 8;
+template <int WORDS, bool WIDE>
+__global__ __launch_bounds__(256) void k_pack_texels(PackArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H % (int)PACK_ROWS == 0, "a workgroup is 32 quads x 8 rows of a tile");
+    constexpr uint32_t PARTS = (uint32_t)TILE_H / PACK_ROWS;
+    const uint32_t ntx = (a.w + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W;
+    const uint32_t tile = blockIdx.x / PARTS, part = blockIdx.x % PARTS;
+    const bool zeros = a.src_all_clean != 0u || (a.src_clean != nullptr && a.src_clean[tile] != 0u);  // (workgroup-uniform)
+    const uint32_t cx = (tile % ntx) * (uint32_t)TILE_W + (threadIdx.x % 32u) * PACK_QUAD;
+    const uint32_t y = (tile / ntx) * (uint32_t)TILE_H + part * PACK_ROWS + threadIdx.x / 32u;
+    if (cx >= a.w || y >= a.h) return;
+    const uint32_t cy = a.h - 1u - y;
+    const uint32_t n = min(PACK_QUAD, a.w - cx);  // (WIDE: 4)
+    const size_t i = (size_t)cy * a.w + cx;
+    uint32_t t[PACK_QUAD] = { 0u, 0u, 0u, 0u }, o[PACK_QUAD] = { 0u, 0u, 0u, 0u };
+    if (!zeros) {
+        const uint8_t *p = a.src + 3u * i;
+        if (WIDE) {
+            // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+            const uint32_t d0 = reinterpret_cast<const uint32_t *>(p)[0], d1 = reinterpret_cast<const uint32_t *>(p)[1],
+                           d2 = reinterpret_cast<const uint32_t *>(p)[2];
+            t[0] = d0 & 0xFFFFFFu;
+            t[1] = (d0 >> 24) | ((d1 & 0xFFFFu) << 8);
+            t[2] = (d1 >> 16) | ((d2 & 0xFFu) << 16);
+            t[3] = d2 >> 8;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < PACK_QUAD; k++)
+                if (k < n) t[k] = pack_rgb8(p[3u * k], p[3u * k + 1u], p[3u * k + 2u]);
+        }
+    }
+    if (a.other) {
+        if (WIDE) {
+            const Texel4 q = *reinterpret_cast<const Texel4 *>(a.other + i);
+            o[0] = q.x, o[1] = q.y, o[2] = q.z, o[3] = q.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < PACK_QUAD; k++)
+                if (k < n) o[k] = a.other[i + k];
+        }
+    }
+    pack_quad<WORDS, WIDE>(a, cx, cy, n, t, a.other ? o : nullptr);
+}
+
 // Morph targets (tr_scene_set_morph_weights): the posed rows of the frames of one launch.  Frame blockIdx.y blends the
 // mesh's gathered rows `base` with the targets' gathered delta rows (`delta`: target k's rows start at k * n_pieces
 // pieces, laid out like `base`, their uv floats unused) under its own weights into its own destination (tab.f[frame]);
@@ -3151,6 +3209,27 @@ int launch_accumulate(const AccumulateArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_accumulate<true>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
     else
         hipLaunchKernelGGL((k_accumulate<false>), dim3(n_tiles), dim3(8 * TILE_H), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_pack_texels(const PackArgs &a, int words, hipStream_t st)
+{
+    if (a.w == 0u || a.h == 0u) return 0;
+    if (!a.texel || (!a.src && !a.src_all_clean) || (a.set && words != 1 && words != 4)) return (int)hipErrorInvalidValue;
+    if (a.set && ((a.mode == PACK_SPEC && !a.other) || (a.mode != 0u && a.mode != PACK_COLOUR && words != 4))) return (int)hipErrorInvalidValue;
+    const uint32_t ntx = (a.w + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W, nty = (a.h + (uint32_t)TILE_H - 1u) / (uint32_t)TILE_H;
+    const dim3 grid(ntx * nty * ((uint32_t)TILE_H / PACK_ROWS)), block(256);
+    // the wide path: a quad is three aligned dwords of the source and one aligned 16-byte word of each plain array
+    const bool wide = a.w % PACK_QUAD == 0u && (uintptr_t)a.src % 4u == 0u && ((uintptr_t)a.texel | (uintptr_t)a.other) % 16u == 0u;
+    if ((uintptr_t)a.set % 16u) return (int)hipErrorInvalidValue;
+    if (a.set && words == 4) {
+        if (wide) hipLaunchKernelGGL((k_pack_texels<4, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pack_texels<4, false>), grid, block, 0, st, a);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_pack_texels<1, true>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_pack_texels<1, false>), grid, block, 0, st, a);
+    }
     TR_LAUNCH_CHECK();
     return 0;
 }

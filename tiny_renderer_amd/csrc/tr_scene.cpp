@@ -23,6 +23,7 @@
 #include "tr_error.h"
 #include "tr_kernels.h"
 #include "tr_math.h"
+#include "tr_pack.h"
 #include "tr_plan.h"
 #include "tr_powf.h"
 #include "tr_prepare.h"
@@ -93,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -239,6 +240,21 @@ struct tr_scene {
     float *d_tri = nullptr;
     uint32_t *d_texel[4] = { nullptr, nullptr, nullptr, nullptr };
     uint32_t *d_packed = nullptr;  // the colour closure's images as one interleaved, tiled array (tr_texels.h)
+    size_t packed_count = 0;       // its words
+    int set_fs = 0;                // the closure the set was packed for (the last pass's)
+    // Dynamic textures (tr_scene_set_texture*): k_pack_texels rewrites d_texel[which] and the set's words in place on the
+    // main stream, behind every tile kernel issued so far; `ev_tex` is recorded behind it and both setup streams wait
+    // for it, so that a later chain's k_lit reads the new set.  The host form's images wait in device staging buffers
+    // (uploaded on a stream of their own, so that the copy does not queue behind the renders); a buffer is used again
+    // when the event behind its launch has completed.
+    hipEvent_t ev_tex = nullptr;
+    hipStream_t upload_stream = nullptr;
+    struct TexStage {
+        uint8_t *d = nullptr;
+        size_t bytes = 0;
+        hipEvent_t done = nullptr;
+    };
+    std::vector<TexStage> tex_stage;
     // The frame's lit texel image (k_lit, tr_kernels.hip): the normal-map / specular closure once per texel and frame
     // instead of once per fragment, where a frame has many more pixels than the images have texels.
     bool lit = false;
@@ -2414,6 +2430,12 @@ void destroy(tr_scene *s)
         }
     for (int k = 0; k < 4; k++) dev_free(s->d_texel[k]);
     dev_free(s->d_packed);
+    for (tr_scene::TexStage &t : s->tex_stage) {
+        dev_free(t.d);
+        if (t.done) (void)hipEventDestroy(t.done);
+    }
+    if (s->ev_tex) (void)hipEventDestroy(s->ev_tex);
+    if (s->upload_stream) (void)hipStreamDestroy(s->upload_stream);
     for (int k = 0; k < LOOKAHEAD; k++) dev_free(s->d_lit[k]);
     if (s->setup_stream) (void)hipStreamSynchronize(s->setup_stream);
     if (s->setup_stream2) (void)hipStreamSynchronize(s->setup_stream2);
@@ -2593,6 +2615,8 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
         HIP_TRY(hipMemcpy(s->d_packed, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
         s->tex.packed = s->d_packed;
         s->tex.packed_bpr = bpr;
+        s->packed_count = packed.size();
+        s->set_fs = fs;
         // The lit path (k_lit): for the closures that are functions of the texel alone, when a frame has many more
         // pixels than the images have texels.  1 Mi texels cost 11 us (specular) / 8 us (normal map) per frame beside
         // the tile kernels; measured per frame, per-fragment -> lit: specular 4096^2 42.8 -> 34.5 us, x64 grid at 8192^2
@@ -3672,6 +3696,256 @@ int tr_shadow_merge_host(size_t n, float *dst, const float *src)
     if (n && (!dst || !src)) return tr::fail(TR_E_INVALID, "tr_shadow_merge_host: null argument");
     for (size_t i = 0; i < n; i++) dst[i] = shadow_merge(src[i], dst[i]);
     return TR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Dynamic textures
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// Does [p, p + bytes) meet one of the scene's own texel arrays?
+bool overlaps_texels(const tr_scene *s, const void *p, size_t bytes)
+{
+    auto meets = [&](const void *q, size_t n) {
+        return q && (const uint8_t *)p < (const uint8_t *)q + n && (const uint8_t *)q < (const uint8_t *)p + bytes;
+    };
+    bool hit = meets(s->d_packed, s->packed_count * 4u);
+    for (int k = 0; k < 4; k++) hit = hit || meets(s->d_texel[k], (size_t)s->tex.w[k] * s->tex.h[k] * 4u);
+    return hit;
+}
+
+// Enqueues the repack of image `which` from `src_device` (w x h rgb8 rows; src_clean / all_clean: the colour-clean flags
+// of the frame it is, PackArgs) on s's stream: behind everything s has been asked to render -- frames held back are
+// submitted first and keep the old texture, every tile kernel issued so far is on the stream -- and behind `producer`'s
+// work (an event on its stream; its stream then waits for the kernel, as in tr_scene_composite).  The setup streams
+// wait for it as well: a later chain's k_lit reads the set.  *done (may be null) is recorded behind the kernel.
+int enqueue_pack(tr_scene *s, uint32_t which, const uint8_t *src_device, const uint32_t *src_clean, bool all_clean, tr_scene *producer,
+                 hipEvent_t done)
+{
+    int st = submit_pending(s);
+    if (st == TR_OK && producer && producer != s) st = submit_pending(producer);
+    if (st != TR_OK) return st;
+    if (!s->ev_tex) HIP_TRY(hipEventCreateWithFlags(&s->ev_tex, hipEventDisableTiming));
+    const bool other_scene = producer && producer != s;
+    if (other_scene) {
+        if (!producer->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&producer->ev_comp_ready, hipEventDisableTiming));
+        if (!s->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_comp_done, hipEventDisableTiming));
+    }
+    PackArgs a = {};
+    a.src = src_device;
+    a.src_clean = src_clean;
+    a.src_all_clean = all_clean ? 1u : 0u;
+    a.texel = s->d_texel[which];
+    a.set = s->d_packed;
+    a.w = s->tex.w[which];
+    a.h = s->tex.h[which];
+    a.bpr = s->tex.packed_bpr;
+    a.fs = s->set_fs;
+    a.mode = s->d_packed ? pack_mode(s->set_fs, which) : 0u;
+    // word 0 of a four-word set is rebuilt from the new texel and the other image's plain array
+    if (a.mode == PACK_COLOUR && s->set_fs == FS_SPECULAR) a.other = s->d_texel[3];
+    if (a.mode == PACK_SPEC) a.other = s->d_texel[0];
+    if (other_scene) {
+        HIP_TRY(hipEventRecord(producer->ev_comp_ready, producer->stream));
+        HIP_TRY(hipStreamWaitEvent(s->stream, producer->ev_comp_ready, 0));
+    }
+    {
+        Timed t(s, K_PACK_TEXELS);
+        int rc = launch_pack_texels(a, s->d_packed ? packed_words(s->set_fs) : 1, s->stream);
+        if (rc) return launch_status(rc, "k_pack_texels");
+    }
+    HIP_TRY(hipEventRecord(s->ev_tex, s->stream));
+    HIP_TRY(hipStreamWaitEvent(s->setup_stream, s->ev_tex, 0));
+    HIP_TRY(hipStreamWaitEvent(s->setup_stream2, s->ev_tex, 0));
+    if (done) HIP_TRY(hipEventRecord(done, s->stream));
+    if (other_scene) {
+        HIP_TRY(hipEventRecord(s->ev_comp_done, s->stream));
+        HIP_TRY(hipStreamWaitEvent(producer->stream, s->ev_comp_done, 0));
+        producer->quiescent = false;
+        producer->observed_seq = producer->pass_seq;
+    }
+    s->quiescent = false;
+    // the scene's passes issued so far count as handed on (as after tr_scene_composite): rendering one of them again
+    // after a bin overflow would draw the new texture
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+// The checks the three setters share; `who` names the entry point in the error text.
+int check_set_texture(const tr_scene *s, uint32_t which, uint32_t w, uint32_t h, const char *who)
+{
+    const std::string t(who);
+    if (which > 3u) return tr::fail(TR_E_INVALID, t + ": `which` must be 0..3 (texture, normal_map, normal_map_tangent, specular_map)");
+    if (w != s->tex.w[which] || h != s->tex.h[which]) {
+        char buf[160];
+        snprintf(buf, sizeof buf, ": the image is %u x %u, the texture it replaces %u x %u (a texture keeps its size)", w, h,
+                 s->tex.w[which], s->tex.h[which]);
+        return tr::fail(TR_E_INVALID, t + buf);
+    }
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    return TR_OK;
+}
+
+// A staging buffer of at least `bytes` bytes that no queued launch reads any more (a new one while all are in flight,
+// up to eight; then the oldest is waited for).
+int take_tex_stage(tr_scene *s, size_t bytes, tr_scene::TexStage **out)
+{
+    tr_scene::TexStage *free_one = nullptr;
+    for (tr_scene::TexStage &t : s->tex_stage)
+        if (hipEventQuery(t.done) == hipSuccess && (!free_one || (free_one->bytes < bytes && t.bytes >= bytes))) free_one = &t;
+    if (!free_one && s->tex_stage.size() >= 8u) {
+        free_one = &s->tex_stage.front();
+        HIP_TRY(hipEventSynchronize(free_one->done));
+    }
+    if (!free_one) {
+        tr_scene::TexStage t;
+        HIP_TRY(hipEventCreateWithFlags(&t.done, hipEventDisableTiming));
+        s->tex_stage.push_back(t);
+        free_one = &s->tex_stage.back();
+    }
+    if (free_one->bytes < bytes) {
+        dev_free(free_one->d);  // (idle: its event has completed, or it is new)
+        free_one->bytes = 0;
+        int st = dev_alloc(&free_one->d, bytes);
+        if (st != TR_OK) return st;
+        free_one->bytes = bytes;
+    }
+    *out = free_one;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_set_texture(tr_scene *s, uint32_t which, const tr_image_rgb8 *image)
+{
+    if (!s || !image || !image->rgb) return tr::fail(TR_E_INVALID, "tr_scene_set_texture: null argument");
+    int st = check_set_texture(s, which, image->w, image->h, "tr_scene_set_texture");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)image->w * image->h * 3u;
+    if (!s->upload_stream) HIP_TRY(hipStreamCreateWithFlags(&s->upload_stream, hipStreamNonBlocking));
+    tr_scene::TexStage *stage = nullptr;
+    if ((st = take_tex_stage(s, bytes, &stage)) != TR_OK) return st;
+    // the copy: on a stream of its own, waited for here -- the caller's memory is free when the call returns, and the
+    // copy never queues behind the scene's renders
+    HIP_TRY(hipMemcpyAsync(stage->d, image->rgb, bytes, hipMemcpyHostToDevice, s->upload_stream));
+    HIP_TRY(hipStreamSynchronize(s->upload_stream));
+    return enqueue_pack(s, which, stage->d, nullptr, false, nullptr, stage->done);
+}
+
+int tr_scene_set_texture_device(tr_scene *s, uint32_t which, const void *rgb_device, uint32_t w, uint32_t h, tr_scene *producer)
+{
+    if (!s || !rgb_device) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: null argument");
+    int st = check_set_texture(s, which, w, h, "tr_scene_set_texture_device");
+    if (st != TR_OK) return st;
+    if (producer && producer->device != s->device)
+        return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: the producer is on another device");
+    if (producer && producer->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)w * h * 3u;
+    const void *source = nullptr;
+    {
+        // memory from tr_host_alloc: the kernel loads through its mapped address; else it must be device memory
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(const_cast<void *>(rgb_device));
+        if (it != g_host_allocs.end()) {
+            if (it->second.bytes < bytes) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: the host buffer is smaller than the image");
+            source = it->second.device;
+        }
+    }
+    if (!source) {
+        const char *text = "tr_scene_set_texture_device: `rgb_device` is neither device memory nor from tr_host_alloc "
+                           "(tr_scene_set_texture takes any host memory)";
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, rgb_device) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, text);
+        }
+        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
+        if (attr.device != s->device) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: `rgb_device` is on another device");
+        source = rgb_device;
+    }
+    if (overlaps_texels(s, source, bytes))
+        return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: `rgb_device` overlaps the scene's own texel arrays");
+    return enqueue_pack(s, which, (const uint8_t *)source, nullptr, false, producer, nullptr);
+}
+
+int tr_scene_set_texture_from_frame(tr_scene *dst, uint32_t which, tr_scene *src)
+{
+    if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: null scene");
+    if (src->device != dst->device) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: the scenes are on different devices");
+    if (src->frame.band_y0 != 0 || src->frame.band_y1 != (int32_t)src->height)
+        return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: src is a band scene (tr_options.band_row0/1): it holds "
+                                      "only its rows of the frame");
+    int st = check_set_texture(dst, which, src->width, src->height, "tr_scene_set_texture_from_frame");
+    if (st != TR_OK) return st;
+    if (src->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    HIP_TRY(hipSetDevice(dst->device));
+    // src's frame on its way (what it holds back keeps dst's old texture when src is dst); a logically cleared frame is
+    // an image of zeros whatever its memory holds
+    st = submit_pending(src);
+    if (st != TR_OK) return st;
+    return enqueue_pack(dst, which, src->d_fb, src->d_fbclean, src->z_fb_cleared, src, nullptr);
+}
+
+int tr_scene_read_texture(tr_scene *s, uint32_t which, uint8_t *rgb)
+{
+    if (!s || !rgb) return tr::fail(TR_E_INVALID, "tr_scene_read_texture: null argument");
+    if (which > 3u) return tr::fail(TR_E_INVALID, "tr_scene_read_texture: `which` must be 0..3");
+    HIP_TRY(hipSetDevice(s->device));
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)s->tex.w[which] * s->tex.h[which];
+    std::vector<uint32_t> words(n);
+    HIP_TRY(hipMemcpy(words.data(), s->d_texel[which], n * 4u, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) {
+        rgb[3 * i] = (uint8_t)words[i];
+        rgb[3 * i + 1] = (uint8_t)(words[i] >> 8);
+        rgb[3 * i + 2] = (uint8_t)(words[i] >> 16);
+    }
+    return TR_OK;
+}
+
+int tr_scene_debug_texel_set(tr_scene *s, uint32_t *words, size_t cap_words)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_texel_set: null scene");
+    if (!s->d_packed) return 0;
+    if (s->packed_count > 0x7FFFFFFFu) return tr::fail(TR_E_INVALID, "tr_scene_debug_texel_set: the set has more words than the return value holds");
+    if (!words || cap_words < s->packed_count) return tr::fail(TR_E_INVALID, "tr_scene_debug_texel_set: `words` is smaller than the set");
+    HIP_TRY(hipSetDevice(s->device));
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(words, s->d_packed, s->packed_count * 4u, hipMemcpyDeviceToHost));
+    return (int)s->packed_count;
+}
+
+// The texel set tr_scene_create builds for pipeline_name from four images of one size, on the host.  Needs no GPU.
+int tr_texel_set_host(const char *pipeline_name, const tr_image_rgb8 tex[4], uint32_t *words, size_t cap_words, uint32_t *blocks_per_row)
+{
+    if (!pipeline_name || !tex) return tr::fail(TR_E_INVALID, "tr_texel_set_host: null argument");
+    const int pipe = find_pipeline(pipeline_name);
+    if (pipe < 0) return tr::fail(TR_E_UNKNOWN_PIPELINE, "Provided pipeline name is not supported!");
+    std::vector<uint32_t> rgba[4];
+    for (int k = 0; k < 4; k++) {
+        if (!tex[k].rgb || tex[k].w == 0u || tex[k].h == 0u || tex[k].w > 65535u || tex[k].h > 65535u)
+            return tr::fail(TR_E_INVALID, "tr_texel_set_host: an image is missing or has a side outside 1..65535");
+        if (tex[k].w != tex[0].w || tex[k].h != tex[0].h)
+            return tr::fail(TR_E_INVALID, "tr_texel_set_host: the images differ in size (such a scene has no texel set)");
+        const size_t n = (size_t)tex[k].w * tex[k].h;
+        rgba[k].resize(n);
+        for (size_t i = 0; i < n; i++) rgba[k][i] = pack_rgb8(tex[k].rgb[3 * i], tex[k].rgb[3 * i + 1], tex[k].rgb[3 * i + 2]);
+    }
+    const int fs = kPipelines[pipe].pass[kPipelines[pipe].n_passes - 1].fs;
+    const uint32_t *const image[4] = { rgba[0].data(), rgba[1].data(), rgba[2].data(), rgba[3].data() };
+    uint32_t bpr = 0;
+    const std::vector<uint32_t> packed = pack_texels(fs, image, tex[0].w, tex[0].h, bpr);
+    if (packed.size() > 0x7FFFFFFFu) return tr::fail(TR_E_INVALID, "tr_texel_set_host: the set has more words than the return value holds");
+    if (!words || cap_words < packed.size()) return tr::fail(TR_E_INVALID, "tr_texel_set_host: `words` is smaller than the set");
+    memcpy(words, packed.data(), packed.size() * 4u);
+    if (blocks_per_row) *blocks_per_row = bpr;
+    return (int)packed.size();
 }
 
 namespace {

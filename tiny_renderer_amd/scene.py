@@ -335,6 +335,24 @@ def dof_coc(params, z):
     return out
 
 
+def texel_set_host(pipeline_name, textures):
+    """tr_texel_set_host: (words uint32 [n], blocks_per_row) -- the texel set tr_scene_create builds for the pipeline from
+    four uint8 [h, w, 3] images of one size (csrc/tr_texels.h), by the function the library itself calls, on the host (no
+    GPU needed)."""
+    if len(textures) != 4:
+        raise ValueError("four textures are required (texture, normal_map, normal_map_tangent, specular_map)")
+    keep = [np.ascontiguousarray(t, np.uint8) for t in textures]
+    if any(t.ndim != 3 or t.shape[2] != 3 for t in keep):
+        raise ValueError("texel_set_host: textures are uint8 [h, w, 3] arrays")
+    imgs = (_lib.ImageRgb8 * 4)(*[_lib.ImageRgb8(t.ctypes.data_as(C.POINTER(C.c_uint8)), t.shape[1], t.shape[0]) for t in keep])
+    h, w = keep[0].shape[:2]
+    cap = ((w + 3) // 4) * ((h + 1) // 2) * 32 + ((w + 7) // 8) * ((h + 3) // 4) * 32   # (either block shape fits)
+    words = np.zeros(cap, np.uint32)
+    bpr = C.c_uint32()
+    n = check(load_library().tr_texel_set_host(pipeline_name.encode(), imgs, words.ctypes.data, cap, C.byref(bpr)))
+    return words[:n].copy(), int(bpr.value)
+
+
 class Scene:
     """Scene::new(width, height, obj, texture, normal_map, normal_map_tangent, specular_map,
     shader_pipeline_name) -- scene.rs:47-56.
@@ -366,6 +384,7 @@ class Scene:
             t = np.ascontiguousarray(t, np.uint8)
             keep.append(t)
             imgs[k] = _lib.ImageRgb8(t.ctypes.data_as(C.POINTER(C.c_uint8)), t.shape[1], t.shape[0])
+        self._tex_shapes = [tuple(t.shape) for t in keep[-4:]]
         o = _lib.Options()
         o.struct_size = C.sizeof(_lib.Options)
         o.device = device
@@ -783,6 +802,55 @@ class Scene:
         self.last_status = code
         return out
 
+    # --- dynamic textures (tr_scene_set_texture*) ---------------------------------------------------
+    def _texture_shape(self, which):
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or not 0 <= which <= 3:
+            raise ValueError("which must be 0..3 (texture, normal_map, normal_map_tangent, specular_map)")
+        return self._tex_shapes[int(which)]
+
+    def set_texture(self, which, image):
+        """tr_scene_set_texture: image `which` (0..3 in the constructor's order) becomes the uint8 [h, w, 3] array `image`,
+        which must have the size of the image it replaces.  Renders issued from now on draw what a scene created with that
+        image draws; frames issued earlier (held-back ones too) keep the old one.  Asynchronous; the array is copied."""
+        shape = self._texture_shape(which)
+        a = np.ascontiguousarray(image, np.uint8)
+        if a.shape != shape:
+            raise ValueError("set_texture: the image is %r, texture %d is %r (a texture keeps its size)" % (a.shape, which, shape))
+        img = _lib.ImageRgb8(a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0])
+        check(load_library().tr_scene_set_texture(self._h, int(which), C.byref(img)))
+
+    def set_texture_device(self, which, ptr, w, h, producer=None):
+        """tr_scene_set_texture_device: the same from 3 * w * h bytes of device memory at `ptr` (int), e.g. the target of
+        resolve_into / accumulate_into / depth_of_field(out=...).  producer: the Scene whose stream wrote it (the repack is
+        ordered behind its work); None: the caller guarantees the memory is complete with respect to this scene's stream."""
+        self._texture_shape(which)
+        if producer is not None and not isinstance(producer, Scene):
+            raise ValueError("set_texture_device: producer must be a Scene or None")
+        check(load_library().tr_scene_set_texture_device(self._h, int(which), int(ptr) if ptr is not None else None, int(w), int(h),
+                                                         producer._h if producer is not None else None))
+
+    def set_texture_from(self, src, which=0):
+        """tr_scene_set_texture_from_frame: the current frame of scene `src` (this scene itself is allowed: feedback) becomes
+        image `which`; src's frame size must be the texture's size.  Nothing leaves the device."""
+        self._texture_shape(which)
+        if not isinstance(src, Scene):
+            raise ValueError("set_texture_from: src must be a Scene")
+        check(load_library().tr_scene_set_texture_from_frame(self._h, int(which), src._h))
+
+    def read_texture(self, which):
+        """tr_scene_read_texture: image `which` as the scene holds it now, uint8 [h, w, 3].  Synchronizes."""
+        out = np.empty(self._texture_shape(which), np.uint8)
+        check(load_library().tr_scene_read_texture(self._h, int(which), out.ctypes.data))
+        return out
+
+    def debug_texel_set(self):
+        """tr_scene_debug_texel_set: the scene's texel set as uint32 words (empty: the scene has none).  Synchronizes."""
+        h, w = self._tex_shapes[0][:2]
+        cap = ((w + 3) // 4) * ((h + 1) // 2) * 32 + ((w + 7) // 8) * ((h + 3) // 4) * 32
+        words = np.zeros(cap, np.uint32)
+        n = check(load_library().tr_scene_debug_texel_set(self._h, words.ctypes.data, cap))
+        return words[:n].copy()
+
     def host_buffer_written(self, out):
         """Tells the scene that the caller has written into a pinned_frame() array (it then assumes nothing about
         the array's content at the next get_frame_buffer_async)."""
@@ -844,8 +912,8 @@ class Scene:
         check(load_library().tr_scene_profile_enable(self._h, 1 if on else 0))
 
     def profile_read(self):
-        buf = (_lib.KernelTime * 16)()
-        n = check(load_library().tr_scene_profile_read(self._h, buf, 16))
+        buf = (_lib.KernelTime * 32)()
+        n = check(load_library().tr_scene_profile_read(self._h, buf, 32))
         return {buf[i].name.decode(): {"launches": int(buf[i].launches), "total_ms": float(buf[i].total_ms),
                                        "frames": int(buf[i].frames)}
                 for i in range(n)}
