@@ -658,6 +658,64 @@ int tr_dof_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up
 /* The circles of confusion of n depths under the parameters (coc: n bytes). */
 int tr_dof_coc(const tr_dof_params *p, uint32_t n, const float *z, uint8_t *coc);
 
+/* Bloom: the highlights of the scene's CURRENT frame keyed out, blurred by a fixed tent and added back, on the device --
+ * bright areas (the highlights of `specular` and `phong`) bleed light.  Keyed at threshold 0 and written alone
+ * (TR_BLOOM_GLOW_ONLY) the glow is the frame's plain fixed-radius tent blur: a frosted reflection, a soft impostor or a
+ * glow map for tr_scene_set_texture_from_frame without a read-back.  The rule, over the stored u8 values F of the frame
+ * (no gamma); a pixel outside the frame is black; R = radius:
+ *   key   : m = max(F_p[0], F_p[1], F_p[2]);  B_p[c] = (m > threshold) ? F_p[c] : 0
+ *   tent  : w(d) = R + 1 - |d| for |d| <= R;  S = (R + 1)^2 is the sum of the weights of one axis;  D = S^2
+ *   blur  : V_p[c] = sum over |dx| <= R, |dy| <= R of w(dx) * w(dy) * B_(x + dx, y + dy)[c]
+ *           (a product: a horizontal pass followed by a vertical one gives the same integers in any order; with R <= 15
+ *           a horizontal sum is at most 255 * 256 and fits a u16, V at most 255 * 65536 and fits a u32 -- which is why
+ *           the largest radius is 15)
+ *   glow  : G_p[c] = (V_p[c] + D / 2) / D                                (integer division, rounded once)
+ *   out   : min(255, F_p[c] + ((strength * G_p[c] + 128) >> 8));  TR_BLOOM_GLOW_ONLY: G_p[c], strength is not used
+ * z, the winner words and the shadow buffer are never written. */
+#define TR_BLOOM_MAX_RADIUS 15
+#define TR_BLOOM_GLOW_ONLY 0x1u
+typedef struct tr_bloom_params {
+    uint32_t struct_size;   /* = sizeof(tr_bloom_params) = 20 */
+    uint32_t radius;        /* 1..TR_BLOOM_MAX_RADIUS */
+    uint32_t threshold;     /* 0..255; 255: nothing passes the key */
+    uint32_t strength;      /* 0..1024, in 1/256 */
+    uint32_t flags;         /* TR_BLOOM_GLOW_ONLY or 0 */
+} tr_bloom_params;
+/* Blooms the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_depth_of_field: k_bloom
+ * is enqueued on the scene's stream behind the renders issued so far (frames held back are submitted, a pending clear is
+ * made real), a later render is ordered behind it, the result is there after tr_scene_sync.  No depth is read: a depth
+ * left on the chip (see TR_OPT_STORE_DEPTH) stays there, no depth-only repeat runs and no z buffer is allocated.  The
+ * scene's passes issued so far count as handed on, as after tr_scene_get_frame_buffer_async: a bin overflow among them is
+ * reported (TR_E_BIN_OVERFLOW), not repaired by rendering again.  Tiles (128 x 16) whose whole 3 x 3 neighbourhood holds
+ * the cleared colour are written as zeros on the fast-clear flags without reading a pixel; glow spreads into a cleared
+ * tile beside a drawn one.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses); every byte of `out` is written on every call, the
+ * scene's frame is not.
+ * out == NULL: in place.  The kernel writes a frame and a set of flags of the library's (those of
+ * tr_scene_depth_of_field), and two device-to-device copies in stream order put them over the current frame and its
+ * colour-clean flags: every later consumer -- the getters, tr_scene_resolve, the sparse read-back, tr_scene_composite in
+ * either role, tr_scene_band_tiles, tr_scene_set_texture_from_frame -- sees the bloomed frame; z, the winner words and
+ * the shadow buffer stay.  Calling it twice blooms twice.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since): out of place `out` becomes zeros
+ * (hipMemsetAsync, no kernel); in place TR_OK, nothing happens.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene or NULL params, a wrong
+ * struct_size, a radius outside 1..TR_BLOOM_MAX_RADIUS, a threshold above 255, a strength above 1024, unknown flag bits,
+ * ordinary host memory as `out`, a pinned buffer that is too small, an `out` that overlaps a frame buffer the scene has
+ * rendered into, and a BAND scene (tr_options.band_row0/1 set): the taps at a band's border lie in rows another rank
+ * owns. */
+int tr_scene_bloom(tr_scene *s, const tr_bloom_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first (an overflowed frame is rendered
+ * again before it is read), blooms into a buffer of the library's, copies out and returns the frame's sticky status,
+ * like tr_scene_get_resolved.  The scene's frame stays unbloomed. */
+int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_bloom calls.  rgb: the frame as
+ * tr_scene_get_frame_buffer returns it, row 0 = top; out: like rgb, and not rgb.  The same parameter checks; width or
+ * height 0: TR_OK, nothing to do. */
+int tr_bloom_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
+                  const tr_bloom_params *p);
+
 /* Dynamic textures (nothing of the kind upstream, whose four images are moved into Scene::new and never change): one of a
  * scene's images -- `which` = 0..3 in tr_scene_create's order: texture, normal_map, normal_map_tangent, specular_map --
  * replaced on the device, from host memory, from device memory or from another scene's (or the scene's own) current

@@ -144,6 +144,9 @@ SYMBOLS = {
     "tr_scene_get_depth_of_field": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_dof_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_dof_coc": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_bloom": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_bloom": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_bloom_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_set_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ImageRgb8)]),
     "tr_scene_set_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "tr_scene_set_texture_from_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),

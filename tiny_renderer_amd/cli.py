@@ -81,7 +81,25 @@ def main(argv=None):
     ap.add_argument("--dof-range", type=float, default=0.0, metavar="B", help="half-width of the band of z around Z that stays sharp (default 0)")
     ap.add_argument("--dof-background", type=int, default=0, metavar="R", help="blur radius of pixels that are not drawn (0..--dof-radius, default 0)")
     ap.add_argument("--dof-show-coc", action="store_true", help="with --dof-focus: the blur radius of every pixel as a grey picture")
+    ap.add_argument("--bloom", type=int, default=0, metavar="R",
+                    help="bloom: the picture's highlights blurred by a tent of R (1..15) pixels and added back on the GPU "
+                         "(Scene.bloom; after --with, --ao, --shutter and --dof-*, before --ssaa resolves)")
+    ap.add_argument("--bloom-threshold", type=int, default=200, metavar="T", help="pixels whose largest channel exceeds T (0..255, default 200) glow")
+    ap.add_argument("--bloom-strength", type=int, default=256, metavar="S", help="the glow is added scaled by S / 256 (0..1024, default 256)")
+    ap.add_argument("--bloom-glow-only", action="store_true", help="with --bloom: the blurred highlights alone (threshold 0: the tent blur of the picture)")
     args = ap.parse_args(argv)
+    args.bloom_params = None
+    if not args.bloom and (args.bloom_threshold != 200 or args.bloom_strength != 256 or args.bloom_glow_only):
+        ap.error("--bloom-threshold, --bloom-strength and --bloom-glow-only go with --bloom R")
+    if args.bloom:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--bloom works on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import bloom_params
+        try:
+            args.bloom_params = bloom_params(args.bloom, threshold=args.bloom_threshold, strength=args.bloom_strength,
+                                             flags=1 if args.bloom_glow_only else 0)
+        except ValueError as e:
+            ap.error(str(e))
     args.dof = None
     if (args.dof_focus is None) != (args.dof_scale is None):
         ap.error("--dof-focus Z and --dof-scale S go together")
@@ -364,6 +382,8 @@ def _run(args, T, scene, sharded, rank, say):
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
     if args.dof is not None:
         scene.depth_of_field(args.dof)
+    if args.bloom_params is not None:
+        scene.bloom(args.bloom_params)
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

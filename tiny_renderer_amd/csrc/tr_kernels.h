@@ -9,6 +9,7 @@
 #include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_dof.h"
+#include "tr_bloom.h"
 #include "tr_morph.h"
 #include "tr_pack.h"
 #include "tr_shadow_merge.h"
@@ -86,6 +87,10 @@ int launch_accumulate(const AccumulateArgs &a, hipStream_t st);
 // fast-clear flags of z and of colour: k_dof.  The whole frame only (no band); the caller has made the depth real.
 // a.out_clean: null, or the flags of `out` the kernel writes.
 int launch_dof(const DofArgs &a, hipStream_t st);
+// Bloom: a.fb keyed, blurred by the tent and added back into a.out (which does not overlap it) by the rule of tr_bloom.h,
+// through the scene's colour fast-clear flags: k_bloom.  The whole frame only (no band); no depth is read.
+// a.out_clean: null, or the flags of `out` the kernel writes.
+int launch_bloom(const BloomArgs &a, hipStream_t st);
 // Dynamic textures: image a.src into the plain array a.texel and the owned words of the texel set a.set (words per texel:
 // 1 or 4; a.set null: the plain array alone) by the rule of tr_pack.h, through the source's colour-clean flags when it
 // is a frame: k_pack_texels.  The caller orders the launch behind whatever reads the arrays and produced the source.

@@ -33,6 +33,7 @@
 #include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_dof.h"
+#include "tr_bloom.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
 #include "tr_pack.h"
@@ -2486,6 +2487,209 @@ __global__ __launch_bounds__(DOF_THREADS) void k_dof(DofArgs a)
     dof_store_share<WIDE>(o, px, n_px);
 }
 
+// Bloom (tr_scene_bloom): the frame's highlights keyed, blurred by a fixed tent and added back, into `out`, never in
+// place (a tap reads a neighbour's colour); tr_bloom.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile, the
+// tiles and colour shares of k_dof.  The tent is a product, so the blur is two passes of 2 R + 1 taps through LDS
+// instead of (2 R + 1)^2 taps:
+//   * the nine colour flags of the 3 x 3 neighbourhood are workgroup-uniform (a tile outside the grid counts as up).
+//     All nine up: the tile is zeros, stored without loading a pixel, ahead of any barrier;
+//   * staging: the KEYED tile and a halo of R pixels go to LDS as rows of 160 words (one packed pixel each) that start
+//     16 pixels left of the tile, so that a piece of four pixels -- twelve bytes, three aligned words of the frame --
+//     lies in ONE tile: a piece in a tile whose flag is up, or outside the frame, is zeros without a load.  16 + 2 R rows;
+//   * the vote: whether any staged pixel passed the key (a wave vote and four words of LDS behind the staging
+//     barrier).  None: no glow reaches the tile -- it is a copy of its own colour, or zeros under TR_BLOOM_GLOW_ONLY;
+//   * the horizontal pass, LDS to LDS: a lane owns one column and every other staged row.  Lanes run along the row, so a
+//     tap is 64 consecutive words (ds_read_b32: lane l on bank l % 32 of its half-wave, no conflict) and dx is a loop
+//     variable, the weight scalar.  r and b accumulate in the halves of one word (each sum <= 65280 < 2^16), g in a
+//     second: u16 sums, as a plane of words {r | b << 16} and a plane of u16 g, rows of 128 behind the staged rows;
+//   * the vertical pass, into registers: a lane owns one column and eight of its rows and reads the 8 + 2 R sums of its
+//     column once each (64 consecutive words, and 64 consecutive u16 -- two lanes to a word, the same word), adding
+//     each to the rows it reaches;
+//   * glow: a plain u32 division by D = (R + 1)^4 per channel (24 per lane);
+//   * the glow goes through the first 8 KB of the staged rows (nobody reads them after the horizontal pass) to the
+//     colour shares -- a lane owns 16 pixels of a row --, which load their own 16 pixels of the frame again (three
+//     16-byte loads; none under TR_BLOOM_GLOW_ONLY or behind a raised flag), add and store every byte of the tile;
+//   * out_clean, when given, gets the tile's flag: 1 where the tile was stored as zeros on the flags alone, else 0.
+// LDS: (16 + 2 R) * (640 + 512 + 256) bytes, dynamic: 25 KB at radius 1, 44 KB at 8, 63.25 KB at 15 (below 64 KB).
+// fb and every flag of the frame are only read.  WIDE: width % 16 == 0 and fb and out 16-byte aligned (the launcher
+// checks); otherwise the same through byte accesses guarded by the width.  No atomics, no scratch.
+constexpr int BLOOM_LDS_W = TILE_W + 32;
+constexpr int BLOOM_THREADS = 256, BLOOM_ROWS = TILE_W * TILE_H / BLOOM_THREADS;  // rows of its column a lane owns
+
+// The 16 pixels of a share of the frame (24 bits each) from `q`: three 16-byte pieces, or n_px * 3 guarded bytes.
+template <bool WIDE>
+__device__ __forceinline__ void bloom_load_share(const uint8_t *q, uint32_t (&px)[16], int32_t n_px)
+{
+    if (WIDE) {
+        uint32_t w[12];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const uint4 v = reinterpret_cast<const uint4 *>(q)[k];
+            w[4 * k + 0] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
+        }
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            px[4 * g + 0] = w[3 * g] & 0xFFFFFFu;
+            px[4 * g + 1] = (w[3 * g] >> 24) | ((w[3 * g + 1] & 0xFFFFu) << 8);
+            px[4 * g + 2] = (w[3 * g + 1] >> 16) | ((w[3 * g + 2] & 0xFFu) << 16);
+            px[4 * g + 3] = w[3 * g + 2] >> 8;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+            px[i] = i < n_px ? bloom_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]) : 0u;
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(BLOOM_THREADS) void k_bloom(BloomArgs a)
+{
+    static_assert(TILE_W == 128 && BLOOM_MAX_RADIUS <= 16 && BLOOM_MAX_RADIUS <= TILE_H, "the halo lies in the eight tiles around");
+    static_assert(BLOOM_THREADS == 4 * 64 && 8 * TILE_H <= BLOOM_THREADS && BLOOM_THREADS == 2 * TILE_W, "four waves vote; the shares are the first lanes");
+    static_assert((TILE_H + 2) * BLOOM_LDS_W >= TILE_H * TILE_W, "the glow of a tile fits the staged rows of radius 1");
+    // (TILE_H + 2 R) rows of BLOOM_LDS_W keyed pixels, then as many rows of TILE_W words {r | b << 16}, then of TILE_W u16 g
+    extern __shared__ __align__(16) uint32_t s_key[];
+    __shared__ uint32_t s_any[4];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, R = (int32_t)a.rule.radius;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    // block b takes the tile of its row ty = b / ntx that lies 5 * ty columns (cyclically) right of column b % ntx.
+    // Blocks are dealt round-robin to the XCDs and their shader engines, in order: with 32 tiles to a row (4096
+    // pixels) block b % 32 is always the same tile column, and a model in the middle columns loads half of the engines
+    // with all the blurred tiles while the rest run the tiles that leave at once (DESIGN 7k has the counters).  A rotation
+    // is a permutation of the row for every ntx; it mixes the columns over the engines where 5 and ntx share no factor
+    // (every power of two), and is the identity again only for ntx = 5 (and moves within 2 columns for ntx = 10).
+    const int32_t ty = (int32_t)blockIdx.x / ntx, tx = ((int32_t)blockIdx.x % ntx + 5 * ty) % ntx;
+    const uint32_t t = (uint32_t)(ty * ntx + tx);
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): its colour reads as zeros (no such tile, or its flag is up)
+    uint32_t czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) czero |= bit;
+            else if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+        }
+    const uint32_t own_bit = 1u << 4;
+    // the colour shares of k_composite
+    const int32_t sx = x0 + (int32_t)(threadIdx.x % 8u) * 16, srow = (int32_t)(threadIdx.x / 8u), sy = y0 + srow;
+    const bool share = threadIdx.x < 8u * TILE_H && sx < W && sy < H;
+    const int32_t n_px = share ? min(16, W - sx) : 0;  // (WIDE: 16 or none)
+    const size_t share_at = share ? ((size_t)(H - 1 - sy) * (size_t)W + (size_t)sx) * 3u : 0u;
+    uint8_t *o = a.out + share_at;
+    uint32_t px[16];
+    const bool all_zero = czero == 0x1FFu;
+    if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = all_zero ? 1u : 0u;
+    if (all_zero) {  // (workgroup-uniform, ahead of the barriers)
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = 0u;
+        dof_store_share<WIDE>(o, px, n_px);
+        return;
+    }
+    const int32_t rows = TILE_H + 2 * R;  // LDS row r is frame row y0 - R + r, LDS column c frame column x0 - 16 + c
+    const uint32_t thr = a.rule.threshold;
+    uint32_t passed = 0u;                 // the keyed pixels this lane staged, or-ed
+    if (WIDE) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (BLOOM_LDS_W / 4); p += BLOOM_THREADS) {
+            const int32_t r = p / (BLOOM_LDS_W / 4), j = p % (BLOOM_LDS_W / 4);
+            if (4 * j + 3 < 16 - R || 4 * j >= 16 + TILE_W + R) continue;  // (no tap reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - R + r;
+            const int32_t ax = j < 4 ? 0 : j < 4 + TILE_W / 4 ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            uint32_t c[4] = { 0u, 0u, 0u, 0u };
+            if ((czero & bit) == 0u && x < W && y < H) {  // (czero covers the tiles outside the grid: x >= 0 and y >= 0 here)
+                // four pixels are twelve bytes at a multiple of four: three aligned words
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(a.fb + ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u);
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
+                c[0] = bloom_key(w0 & 0xFFFFFFu, thr);
+                c[1] = bloom_key((w0 >> 24) | ((w1 & 0xFFFFu) << 8), thr);
+                c[2] = bloom_key((w1 >> 16) | ((w2 & 0xFFu) << 16), thr);
+                c[3] = bloom_key(w2 >> 8, thr);
+            }
+            passed |= c[0] | c[1] | c[2] | c[3];
+            *reinterpret_cast<uint4 *>(&s_key[r * BLOOM_LDS_W + 4 * j]) = make_uint4(c[0], c[1], c[2], c[3]);
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * BLOOM_LDS_W; p += BLOOM_THREADS) {
+            const int32_t r = p / BLOOM_LDS_W, c = p % BLOOM_LDS_W;
+            if (c < 16 - R || c >= 16 + TILE_W + R) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - R + r;
+            const int32_t ax = c < 16 ? 0 : c < 16 + TILE_W ? 1 : 2, ay = y < y0 ? 0 : y < y0 + TILE_H ? 1 : 2;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            uint32_t col = 0u;
+            if ((czero & bit) == 0u && x < W && y < H) {
+                const uint8_t *q = a.fb + ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+                col = bloom_key(bloom_pack(q[0], q[1], q[2]), thr);
+            }
+            passed |= col;
+            s_key[r * BLOOM_LDS_W + c] = col;
+        }
+    }
+    // (a pixel that passes the key has a channel above the threshold: its packed word is not zero)
+    const bool wave_any = __any(passed != 0u) != 0;
+    if (threadIdx.x % 64u == 0u) s_any[threadIdx.x / 64u] = wave_any ? 1u : 0u;
+    __syncthreads();
+    const bool any = __builtin_amdgcn_readfirstlane(s_any[0] | s_any[1] | s_any[2] | s_any[3]) != 0u;
+    const bool own_zero = (czero & own_bit) != 0u;
+    const bool glow_only = a.rule.glow_only != 0u;
+    if (!any) {  // (workgroup-uniform) no glow anywhere in the tile: its own colour, or zeros
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = 0u;
+        if (!glow_only && !own_zero) bloom_load_share<WIDE>(a.fb + share_at, px, n_px);
+        dof_store_share<WIDE>(o, px, n_px);
+        return;
+    }
+    // the horizontal pass: column `col`, staged rows half, half + 2, ...
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, half = (int32_t)threadIdx.x / TILE_W;
+    uint32_t *s_rb = s_key + rows * BLOOM_LDS_W;
+    uint16_t *s_g = reinterpret_cast<uint16_t *>(s_rb + rows * TILE_W);
+    for (int32_t r = half; r < rows; r += BLOOM_THREADS / TILE_W) {
+        const uint32_t *src = s_key + r * BLOOM_LDS_W + 16 + col;
+        BloomH h = { 0u, 0u };
+        for (int32_t dx = -R; dx <= R; dx++) bloom_h_tap(h, src[dx], bloom_weight(R, dx));
+        s_rb[r * TILE_W + col] = h.rb;
+        s_g[r * TILE_W + col] = (uint16_t)h.g;
+    }
+    __syncthreads();
+    // the vertical pass: column `col`, rows row0 .. row0 + BLOOM_ROWS - 1 of the tile; staged row row0 + j is dy = j - R - k
+    // away from the lane's row k
+    const int32_t row0 = half * BLOOM_ROWS;
+    BloomV v[BLOOM_ROWS];
+#pragma unroll
+    for (int k = 0; k < BLOOM_ROWS; k++) v[k].r = v[k].g = v[k].b = 0u;
+    for (int32_t j = 0; j < BLOOM_ROWS + 2 * R; j++) {
+        const BloomH h = { s_rb[(row0 + j) * TILE_W + col], (uint32_t)s_g[(row0 + j) * TILE_W + col] };
+#pragma unroll
+        for (int k = 0; k < BLOOM_ROWS; k++) {
+            const int32_t w = R + 1 - abs(j - R - k);  // (scalar: j, R and k are)
+            bloom_v_tap(v[k], h, (uint32_t)max(w, 0));
+        }
+    }
+    const uint32_t D = bloom_divisor(a.rule.radius);
+    uint32_t *s_out = s_key;  // (the staged rows were last read before the barrier above)
+#pragma unroll
+    for (int k = 0; k < BLOOM_ROWS; k++) s_out[(row0 + k) * TILE_W + col] = bloom_glow_px(v[k], D);
+    __syncthreads();
+    if (!share) return;
+    uint32_t f[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) f[i] = 0u;
+    if (!glow_only && !own_zero) bloom_load_share<WIDE>(a.fb + share_at, f, n_px);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 g = *reinterpret_cast<const uint4 *>(&s_out[srow * TILE_W + (sx - x0) + 4 * k]);
+        px[4 * k + 0] = bloom_out_px(f[4 * k + 0], g.x, a.rule);
+        px[4 * k + 1] = bloom_out_px(f[4 * k + 1], g.y, a.rule);
+        px[4 * k + 2] = bloom_out_px(f[4 * k + 2], g.z, a.rule);
+        px[4 * k + 3] = bloom_out_px(f[4 * k + 3], g.w, a.rule);
+    }
+    dof_store_share<WIDE>(o, px, n_px);
+}
+
 // Dynamic textures (tr_scene_set_texture*): image `which` of a scene replaced by a w x h image of packed rgb8 rows, in
 // the plain array and in the texel set together; tr_pack.h has the rule (pack_quad, shared with the host).  The grid is
 // that of a frame of w x h pixels -- the image may BE one (tr_scene_set_texture_from_frame): a workgroup of 256 lanes
@@ -3189,6 +3393,30 @@ int launch_dof(const DofArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_dof<true>), dim3(n_tiles), dim3(DOF_THREADS), lds, st, a);
     else
         hipLaunchKernelGGL((k_dof<false>), dim3(n_tiles), dim3(DOF_THREADS), lds, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_bloom(const BloomArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo, sums that fit
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.rule.radius == 0u || a.rule.radius > (uint32_t)BLOOM_MAX_RADIUS || a.rule.threshold > 255u || a.rule.strength > BLOOM_MAX_STRENGTH)
+        return (int)hipErrorInvalidValue;
+    // `out` is never the frame that is read
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // the wide path: every share and every staged piece is whole aligned words of colour
+    const bool wide = a.frame.width % 16u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 16u == 0u;
+    // keyed pixels (a word each), the words {r | b << 16} and the u16 g of the horizontal sums
+    const size_t lds = (size_t)(TILE_H + 2 * (int)a.rule.radius) * ((size_t)BLOOM_LDS_W * 4u + (size_t)TILE_W * 6u);
+    if (wide)
+        hipLaunchKernelGGL((k_bloom<true>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
+    else
+        hipLaunchKernelGGL((k_bloom<false>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

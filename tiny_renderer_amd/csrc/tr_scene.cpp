@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -398,7 +398,7 @@ struct tr_scene {
     uint8_t *d_view = nullptr;  // scratch for get_z_buffer / get_shadow_buffer
     uint8_t *d_resolved = nullptr;  // tr_scene_get_resolved's / tr_scene_get_accumulated's device buffer, of the largest size asked for so far
     size_t resolved_bytes = 0;
-    // tr_scene_depth_of_field in place: the frame and the flags k_dof writes before both are copied over the current
+    // tr_scene_depth_of_field and tr_scene_bloom in place: the frame and the flags k_dof / k_bloom write before both are copied over the current
     // frame's (3 * W * H bytes, n_tiles words; allocated at the first such call)
     uint8_t *d_dof_fb = nullptr;
     uint32_t *d_dof_clean = nullptr;
@@ -4367,6 +4367,147 @@ int tr_dof_coc(const tr_dof_params *p, uint32_t n, const float *z, uint8_t *coc)
     if (n == 0u) return TR_OK;
     if (!z || !coc) return tr::fail(TR_E_INVALID, "tr_dof_coc: null argument");
     dof_coc_host(dof_rule(p), n, z, coc);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_BLOOM_MAX_RADIUS == BLOOM_MAX_RADIUS && TR_BLOOM_GLOW_ONLY == BLOOM_GLOW_ONLY && sizeof(tr_bloom_params) == 20,
+              "tr_bloom.h restates the header");
+
+// tr_bloom_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_bloom_params(const tr_bloom_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_bloom_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_bloom_params)");
+    if (p->radius < 1u || p->radius > (uint32_t)TR_BLOOM_MAX_RADIUS) return tr::fail(TR_E_INVALID, w + ": radius must be 1..TR_BLOOM_MAX_RADIUS");
+    if (p->threshold > 255u) return tr::fail(TR_E_INVALID, w + ": threshold must be 0..255");
+    if (p->strength > BLOOM_MAX_STRENGTH) return tr::fail(TR_E_INVALID, w + ": strength must be 0..1024");
+    if (p->flags & ~TR_BLOOM_GLOW_ONLY) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    return TR_OK;
+}
+
+BloomRule bloom_rule(const tr_bloom_params *p)
+{
+    BloomRule r;
+    r.radius = p->radius;
+    r.threshold = p->threshold;
+    r.strength = p->strength;
+    r.glow_only = (p->flags & TR_BLOOM_GLOW_ONLY) ? 1u : 0u;
+    return r;
+}
+
+int check_bloom_scene(const tr_scene *s, const char *who)
+{
+    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be bloomed: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    return TR_OK;
+}
+
+// Enqueues the bloom of the current frame into `out_device` (which overlaps no frame of the scene) behind everything
+// issued so far; out_clean: null, or where k_bloom writes the flags of `out_device`.  The scene is not logically cleared.
+// No depth is read: a depth left on the chip stays there.
+int enqueue_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *out_device, uint32_t *out_clean)
+{
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    BloomArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+    a.rule = bloom_rule(p);
+    {
+        Timed t(s, K_BLOOM);
+        int rc = launch_bloom(a, s->stream);
+        if (rc) return launch_status(rc, "k_bloom");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_bloom(tr_scene *s, const tr_bloom_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_bloom: null scene");
+    int st = check_bloom_params(p, "tr_scene_bloom");
+    if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_bloom");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    void *target = nullptr;
+    if (out) {
+        st = classify_out(s, out, bytes, "tr_scene_bloom", "tr_scene_get_bloom", "blooms", 0u, &target);
+        if (st != TR_OK) return st;
+    }
+    if (s->z_fb_cleared) {
+        // a logically cleared frame is black, and so is its glow: zeros out of place, itself in place
+        if (!target) return TR_OK;
+        st = submit_pending(s);
+        if (st != TR_OK) return st;
+        HIP_TRY(hipMemsetAsync(target, 0, bytes, s->stream));
+        s->quiescent = false;
+        s->observed_seq = s->pass_seq;
+        return TR_OK;
+    }
+    if (!target) {
+        // (the scratch frame and flag set of depth of field: each call leaves them free behind its two copies)
+        if (!s->d_dof_fb && (st = dev_alloc(&s->d_dof_fb, bytes))) return st;
+        if (!s->d_dof_clean && (st = dev_alloc(&s->d_dof_clean, (size_t)s->n_tiles))) return st;
+    }
+    st = enqueue_bloom(s, p, target ? (uint8_t *)target : s->d_dof_fb, target ? nullptr : s->d_dof_clean);
+    if (st != TR_OK) return st;
+    if (!target) {
+        // in stream order: the bloomed colour over the current frame, its flags over the frame's colour-clean flags
+        HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, bytes, hipMemcpyDeviceToDevice, s->stream));
+        if (s->d_fbclean)
+            HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
+    }
+    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
+    // overflow would undo a bloom made in place, or change what one made elsewhere was made from
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_bloom: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_bloom: null argument");
+    int st = check_bloom_params(p, "tr_scene_get_bloom");
+    if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_get_bloom");
+    if (st != TR_OK) return st;
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
+        s->resolved_bytes = 0;
+        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
+        s->resolved_bytes = bytes;
+    }
+    if (s->z_fb_cleared) {
+        HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    } else {
+        st = enqueue_bloom(s, p, s->d_resolved, nullptr);
+        if (st != TR_OK) return st;
+    }
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// The rule of tr_bloom.h over a caller's array, on the host.  Needs no GPU.
+int tr_bloom_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out, const tr_bloom_params *p)
+{
+    int st = check_bloom_params(p, "tr_bloom_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_bloom_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_bloom_host: out is rgb (the rule reads neighbours: not in place)");
+    bloom_host(width, height, rgb, out, bloom_rule(p));
     return TR_OK;
 }
 

@@ -335,6 +335,48 @@ def dof_coc(params, z):
     return out
 
 
+BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
+
+
+class BloomParams(C.Structure):
+    """tr_bloom_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("threshold", C.c_uint32), ("strength", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+def bloom_params(radius, threshold=200, strength=256, flags=0):
+    """tr_bloom_params for Scene.bloom / Scene.get_bloom / bloom_host: pixels whose largest channel exceeds threshold
+    (0..255) are blurred by a tent of `radius` pixels (1..15) and added back scaled by strength / 256 (0..1024); flags:
+    BLOOM_GLOW_ONLY (the blurred highlights alone) or 0.  ValueError for what the library would refuse
+    (include/tiny_renderer.h)."""
+    for name, v in (("radius", radius), ("threshold", threshold), ("strength", strength), ("flags", flags)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("bloom: %s must be an integer" % name)
+    if not 1 <= radius <= BLOOM_MAX_RADIUS:
+        raise ValueError("bloom: radius must be 1..%d pixels" % BLOOM_MAX_RADIUS)
+    if not 0 <= threshold <= 255:
+        raise ValueError("bloom: threshold must be 0..255")
+    if not 0 <= strength <= BLOOM_MAX_STRENGTH:
+        raise ValueError("bloom: strength must be 0..%d" % BLOOM_MAX_STRENGTH)
+    if flags & ~BLOOM_GLOW_ONLY:
+        raise ValueError("bloom: unknown flags")
+    return BloomParams(C.sizeof(BloomParams), int(radius), int(threshold), int(strength), int(flags))
+
+
+def bloom_host(rgb, params):
+    """tr_bloom_host: the rule of Scene.bloom on the host (no GPU needed), by the inline functions k_bloom calls.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from bloom_params.  Returns the bloomed frame and leaves
+    its arguments alone."""
+    if not isinstance(params, BloomParams):
+        raise ValueError("bloom_host: params must come from bloom_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("bloom_host: rgb [H, W, 3]")
+    out = np.empty_like(src)
+    check(load_library().tr_bloom_host(src.shape[1], src.shape[0], src.ctypes.data, out.ctypes.data, C.addressof(params)))
+    return out
+
+
 def texel_set_host(pipeline_name, textures):
     """tr_texel_set_host: (words uint32 [n], blocks_per_row) -- the texel set tr_scene_create builds for the pipeline from
     four uint8 [h, w, 3] images of one size (csrc/tr_texels.h), by the function the library itself calls, on the host (no
@@ -797,6 +839,39 @@ class Scene:
             raise ValueError("get_depth_of_field: params must come from dof_params")
         out = np.empty((self.height, self.width, 3), np.uint8)
         code = load_library().tr_scene_get_depth_of_field(self._h, C.addressof(params), out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return out
+
+    # --- bloom (tr_scene_bloom / tr_scene_get_bloom) -------------------------------------------------
+    def bloom(self, params, out=None):
+        """tr_scene_bloom: keys the current frame's highlights, blurs them by a tent and adds them back on the device
+        (params from bloom_params).  out=None: in place -- every later consumer (the getters, resolve, the sparse
+        read-back, composite, set_texture_from_frame) sees the bloomed frame, z, winner words and the shadow buffer stay,
+        calling it twice blooms twice.  Otherwise `out` is a device pointer (int) to 3 * W * H bytes that overlaps no frame
+        buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the
+        result is there after sync().  Band scenes are refused.  No depth is needed."""
+        if not isinstance(params, BloomParams):
+            raise ValueError("bloom: params must come from bloom_params")
+        if out is None:
+            ptr = None
+        elif isinstance(out, np.ndarray):
+            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
+            ptr = out.ctypes.data
+        else:
+            ptr = int(out)
+        check(load_library().tr_scene_bloom(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_bloom(self, params, strict=True):
+        """tr_scene_get_bloom: the current frame bloomed on the device, as an [H, W, 3] uint8 array.  Synchronizes; the
+        scene's frame stays unbloomed."""
+        if not isinstance(params, BloomParams):
+            raise ValueError("get_bloom: params must come from bloom_params")
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        code = load_library().tr_scene_get_bloom(self._h, C.addressof(params), out.ctypes.data)
         if strict:
             check(code)
         self.last_status = code
