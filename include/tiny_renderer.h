@@ -716,6 +716,63 @@ int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb);
 int tr_bloom_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
                   const tr_bloom_params *p);
 
+/* Colour grading: the scene's CURRENT frame mapped through a 3-D colour lookup table on the device -- the last step of the
+ * chain, which turns the linear stored picture into the one to look at: gamma or sRGB encoding, a tone curve, contrast,
+ * saturation, tint, inversion, false colour, or a film grade that exists as a .cube file; one rule for every pointwise
+ * colour operation.  The table holds n^3 entries of rgb8, n = 2..TR_GRADE_MAX_N, red fastest (the order of a .cube
+ * file): the entry for (ir, ig, ib) is lut[((ib * n + ig) * n + ir) * 3 + c].  The rule, in integers, over the stored u8
+ * channels (vr, vg, vb) of a pixel:
+ *   split : per channel x: p = v_x * (n - 1);  i_x = p / 255;  f_x = p % 255   (v_x = 255: i_x = n - 1, f_x = 0)
+ *           j_x = min(i_x + 1, n - 1)
+ *   order : the channels by f, largest first: a, b, c   (f_a >= f_b >= f_c)
+ *   walk  : V0 = entry(i_r, i_g, i_b);  V1 = V0 with channel a's index stepped to j_a;  V2 = V1 with channel b's index
+ *           stepped to j_b;  V3 = entry(j_r, j_g, j_b)
+ *   out   : out[ch] = ((255 - f_a) * V0[ch] + (f_a - f_b) * V1[ch] + (f_b - f_c) * V2[ch] + f_c * V3[ch] + 127) / 255
+ * -- tetrahedral interpolation with weights in units of 1 / 255, which sum to 255.  There is no tie-break: where two
+ * fractions are equal the vertex between them has weight 0, so any order of tied channels gives the same bytes; a
+ * clamped j_x only ever carries weight 0.  (0, 0, 0) maps to entry 0 exactly ("c0" below).  An identity table
+ * E(i) = round(255 i / (n - 1)) gives every byte back where n - 1 divides 255 (n = 2, 4, 6, 16, 18, ...) and is within
+ * +-1 otherwise (17, 33).  z, the winner words and the shadow buffer are never written. */
+#define TR_GRADE_MAX_N 33
+/* The table is scene state: copied, and expanded to one word an entry on the device, once.  Synchronous: waits for the
+ * scene's queued work first (frames issued so far are graded by the table they were issued under), like
+ * tr_scene_set_morph_targets.  n == 0 drops the table (lut may then be NULL).  TR_E_INVALID with a tr_last_error text,
+ * nothing changed: a NULL scene, n == 1, n > TR_GRADE_MAX_N, NULL lut with n > 0. */
+int tr_scene_set_lut(tr_scene *s, uint32_t n, const uint8_t *lut /* 3*n*n*n, host */);
+/* Grades the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_bloom: k_grade is
+ * enqueued on the scene's stream behind the renders issued so far (frames held back are submitted), a later render is
+ * ordered behind it, the result is there after tr_scene_sync.  No depth is read: a depth left on the chip (see
+ * TR_OPT_STORE_DEPTH) stays there, no depth-only repeat runs and no z buffer is allocated.  The scene's passes issued so
+ * far count as handed on, as after tr_scene_get_frame_buffer_async: a bin overflow among them is reported
+ * (TR_E_BIN_OVERFLOW), not repaired by rendering again.
+ * Tiles (128 x 16) whose colour fast-clear flag is up are not read: they become c0.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses), apart from every frame buffer of the scene.  A
+ * whole-frame scene writes every byte of `out` on every call; a BAND scene (tr_options.band_row0/1) writes its band's
+ * rows and nothing else, as tr_scene_accumulate does.  The scene's frame is not written.
+ * out == NULL: in place, by the kernel itself -- a pixel depends on itself alone, so there is no scratch frame and no
+ * copy.  A flagged tile keeps its zeros and its flag where c0 is (0, 0, 0); otherwise it is stored as c0 and its flag
+ * comes down.  Every later consumer -- the getters, tr_scene_resolve, the sparse read-back, tr_scene_composite in either
+ * role, tr_scene_band_tiles, tr_scene_set_texture_from_frame -- sees the graded frame.  Calling it twice grades twice.
+ * Band scenes are accepted either way: rows outside the band are never touched.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since): with c0 = (0, 0, 0), out of place the
+ * scene's rows of `out` become zeros (hipMemsetAsync, no kernel) and in place nothing happens (TR_OK); with another c0
+ * the clear is made real and the kernel runs: the frame (or `out`) holds c0 in every pixel, and a following render
+ * without a clear draws over it as over a caller's backdrop.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene, a scene without a table,
+ * ordinary host memory as `out`, a pinned buffer that is too small, an `out` that overlaps a frame buffer the scene has
+ * rendered into. */
+int tr_scene_grade(tr_scene *s, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first (an overflowed frame is rendered
+ * again before it is read), grades into a buffer of the library's, copies out and returns the frame's sticky status,
+ * like tr_scene_get_bloom.  The scene's frame stays ungraded.  A band scene's rows outside its band read as zeros. */
+int tr_scene_get_graded(tr_scene *s, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_grade calls, over n_pixels packed rgb8
+ * pixels in any order.  out may be rgb: the rule works in place.  The same checks of n; n_pixels 0: TR_OK, nothing to
+ * do. */
+int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out /* may be rgb */, uint32_t n, const uint8_t *lut);
+
 /* Dynamic textures (nothing of the kind upstream, whose four images are moved into Scene::new and never change): one of a
  * scene's images -- `which` = 0..3 in tr_scene_create's order: texture, normal_map, normal_map_tangent, specular_map --
  * replaced on the device, from host memory, from device memory or from another scene's (or the scene's own) current

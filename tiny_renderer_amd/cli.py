@@ -87,7 +87,28 @@ def main(argv=None):
     ap.add_argument("--bloom-threshold", type=int, default=200, metavar="T", help="pixels whose largest channel exceeds T (0..255, default 200) glow")
     ap.add_argument("--bloom-strength", type=int, default=256, metavar="S", help="the glow is added scaled by S / 256 (0..1024, default 256)")
     ap.add_argument("--bloom-glow-only", action="store_true", help="with --bloom: the blurred highlights alone (threshold 0: the tent blur of the picture)")
+    ap.add_argument("--lut", default=None, metavar="FILE.cube",
+                    help="colour grading: the picture mapped through the 3-D lookup table of a .cube file (2..33 entries an axis, "
+                         "unit domain) on the GPU (Scene.grade; after --bloom, before --ssaa resolves)")
+    ap.add_argument("--gamma", type=float, default=None, metavar="G",
+                    help="colour grading by a 33^3 table of v^(1/G), e.g. 2.2 (Scene.grade; after --bloom, before --ssaa resolves)")
     args = ap.parse_args(argv)
+    args.grade_lut = None
+    if args.lut is not None and args.gamma is not None:
+        ap.error("--lut and --gamma are two tables for one stage: give one")
+    if args.lut is not None or args.gamma is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--lut and --gamma work on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import load_cube, lut_from_function
+        try:
+            if args.lut is not None:
+                args.grade_lut = load_cube(args.lut)
+            else:
+                if not args.gamma > 0.0:
+                    raise ValueError("--gamma must be positive")
+                args.grade_lut = lut_from_function(33, lambda v: v ** (1.0 / args.gamma))
+        except (OSError, ValueError) as e:
+            ap.error(str(e))
     args.bloom_params = None
     if not args.bloom and (args.bloom_threshold != 200 or args.bloom_strength != 256 or args.bloom_glow_only):
         ap.error("--bloom-threshold, --bloom-strength and --bloom-glow-only go with --bloom R")
@@ -384,6 +405,9 @@ def _run(args, T, scene, sharded, rank, say):
         scene.depth_of_field(args.dof)
     if args.bloom_params is not None:
         scene.bloom(args.bloom_params)
+    if args.grade_lut is not None:
+        scene.set_lut(args.grade_lut)
+        scene.grade()
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

@@ -10,6 +10,7 @@
 #include "tr_composite.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
+#include "tr_grade.h"
 #include "tr_morph.h"
 #include "tr_pack.h"
 #include "tr_shadow_merge.h"
@@ -91,6 +92,11 @@ int launch_dof(const DofArgs &a, hipStream_t st);
 // through the scene's colour fast-clear flags: k_bloom.  The whole frame only (no band); no depth is read.
 // a.out_clean: null, or the flags of `out` the kernel writes.
 int launch_bloom(const BloomArgs &a, hipStream_t st);
+// Colour grading: a.fb mapped through the table a.lut (n^3 packed entries, padded to whole 16-byte pieces, 16-byte
+// aligned) into a.out -- a.fb itself or a buffer apart from it -- by the rule of tr_grade.h, through the frame's colour
+// fast-clear flags: k_grade, persistent workgroups.  The scene's tile grid, a band's included; no depth is read.
+// a.lower_clean: null, or a.fbclean (in place, c0 != 0): the flags of the tiles stored as c0 come down.
+int launch_grade(const GradeArgs &a, hipStream_t st);
 // Dynamic textures: image a.src into the plain array a.texel and the owned words of the texel set a.set (words per texel:
 // 1 or 4; a.set null: the plain array alone) by the rule of tr_pack.h, through the source's colour-clean flags when it
 // is a frame: k_pack_texels.  The caller orders the launch behind whatever reads the arrays and produced the source.

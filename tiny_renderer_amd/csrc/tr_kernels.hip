@@ -27,6 +27,7 @@
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "tr_accumulate.h"
@@ -34,6 +35,7 @@
 #include "tr_composite.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
+#include "tr_grade.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
 #include "tr_pack.h"
@@ -2690,6 +2692,122 @@ __global__ __launch_bounds__(BLOOM_THREADS) void k_bloom(BloomArgs a)
     dof_store_share<WIDE>(o, px, n_px);
 }
 
+// Colour grading (tr_scene_grade): every pixel of the frame mapped through the scene's 3-D lookup table into `out`,
+// which may BE the frame (a pixel depends on itself alone); tr_grade.h has the rule.  The working set is the table, not
+// a neighbourhood, so the workgroups are PERSISTENT: the launcher starts as many as the machine holds at once (by the
+// table's LDS size, never more than there are tiles), each stages the table once and then walks the 128 x 16 tiles of
+// the scene's grid (a band scene's: its band's) with the stride of the grid, G.
+//   * LDS form (N <= 25, at most 62,512 bytes of dynamic LDS): the table is copied from global memory in 16-byte pieces
+//     at the first tile the workgroup has to read -- a workgroup whose tiles all leave on their flags never stages it;
+//     global form (N = 26..33, up to 144 KB): the four entries of a pixel are gathered from global memory (L2);
+//   * which tile: slot k = b, b + G, b + 2 G, ... is row ty = k / ntx of the grid and the column that lies
+//     5 * ty + 13 * (ty * ntx / G) columns (cyclically) right of k % ntx -- a function of ty alone, so a permutation of
+//     every row whatever G is.  The first term is k_bloom's: a model's tile columns spread over the shader engines.
+//     The second moves a workgroup to another column each time it comes round (G is usually a multiple of ntx, and
+//     then ty * ntx / G is the round), so every workgroup gets drawn and empty tiles alike;
+//   * a tile whose colour-clean flag is up is not read (the flag is workgroup-uniform, one scalar word): it holds
+//     zeros and becomes c0, the table's entry 0.  In place with c0 = 0 it is left alone, flag and all; otherwise the
+//     constant is stored, and in place lane 0 lowers the flag behind a barrier (every wave has read it by then);
+//   * a unit is four pixels of a row, twelve bytes; a lane takes two units of a tile, eight rows apart, and 32 lanes run
+//     along a row (384 consecutive bytes).  WORDS: width % 4 == 0 and fb and out 4-byte aligned (the launcher checks),
+//     so a unit is three aligned words, loaded and stored as one 12-byte piece; otherwise guarded bytes, which also serve
+//     rows whose byte offset is no multiple of 4 (width 130: 390-byte rows).  A lane has read its bytes before it
+//     writes them and no other lane touches them: in place is safe.  Rows outside the band are not touched;
+//   * four table reads a pixel.
+// z, winner words, the shadow buffer and every flag but the one lowered are left alone.  No atomics, no inline
+// assembly, no scratch; LDS is dynamic only (its base stays 16-byte aligned).
+constexpr int GRADE_THREADS = 256, GRADE_UNITS = TILE_W * TILE_H / 4 / GRADE_THREADS;  // units of a tile a lane owns
+constexpr int GRADE_MAX_PER_CU = 8;  // workgroups of 256 lanes a CU holds by its waves
+
+template <bool LDS, bool WORDS>
+__global__ __launch_bounds__(GRADE_THREADS) void k_grade(GradeArgs a)
+{
+    static_assert(TILE_W == 128 && GRADE_UNITS == 2 && TILE_H == 16, "32 units to a row of a tile, two rounds of eight rows");
+    extern __shared__ __align__(16) uint32_t s_lut[];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t ntx = a.frame.ntx, n_tiles = a.frame.ntx * a.frame.nty, G = gridDim.x;
+    const uint32_t n = a.rule.n, c0 = a.rule.c0;
+    const bool in_place = a.out == a.fb;
+    bool staged = !LDS;
+    for (uint32_t k = blockIdx.x; k < n_tiles; k += G) {
+        const uint32_t tyl = k / ntx, tx = (k % ntx + 5u * tyl + 13u * (tyl * ntx / G)) % ntx;
+        const uint32_t t = tyl * ntx + tx;
+        const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+        if (clean && in_place && c0 == 0u) continue;
+        if (!clean && !staged) {  // (workgroup-uniform: the barrier is reached by all or none)
+            const uint32_t pieces = (n * n * n + 3u) / 4u;  // (the device table is padded to whole pieces)
+            for (uint32_t i = threadIdx.x; i < pieces; i += GRADE_THREADS)
+                reinterpret_cast<uint4 *>(s_lut)[i] = reinterpret_cast<const uint4 *>(a.lut)[i];
+            __syncthreads();
+            staged = true;
+        }
+        const int32_t x = (int32_t)tx * TILE_W + 4 * (int32_t)(threadIdx.x % 32u);
+        const int32_t y_first = (a.frame.ty_base + (int32_t)tyl) * TILE_H + (int32_t)(threadIdx.x / 32u);
+        const int32_t n_px = min(4, W - x);  // (WORDS: 4, or the unit is outside)
+        bool inside[GRADE_UNITS];
+        size_t ci[GRADE_UNITS];
+        uint32_t px[GRADE_UNITS][4];
+#pragma unroll
+        for (int h = 0; h < GRADE_UNITS; h++) {
+            const int32_t y = y_first + 8 * h;
+            inside[h] = x < W && y >= a.frame.band_y0 && y < a.frame.band_y1;
+            ci[h] = inside[h] ? ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; i++) px[h][i] = c0;
+        }
+        if (!clean) {
+            // both units' loads first, then the arithmetic
+#pragma unroll
+            for (int h = 0; h < GRADE_UNITS; h++) {
+                if (!inside[h]) continue;
+                const uint8_t *q = a.fb + ci[h];
+                if (WORDS) {
+                    const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                    const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                    px[h][0] = w0 & 0xFFFFFFu;
+                    px[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                    px[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                    px[h][3] = w2 >> 8;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (i < n_px) px[h][i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < GRADE_UNITS; h++) {
+                if (!inside[h]) continue;
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (WORDS || i < n_px) px[h][i] = LDS ? grade_px(s_lut, n, px[h][i]) : grade_px(a.lut, n, px[h][i]);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < GRADE_UNITS; h++) {
+            if (!inside[h]) continue;
+            uint8_t *o = a.out + ci[h];
+            if (WORDS) {
+                uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+                ow[0] = px[h][0] | (px[h][1] << 24);
+                ow[1] = (px[h][1] >> 8) | (px[h][2] << 16);
+                ow[2] = (px[h][2] >> 16) | (px[h][3] << 8);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) {
+                        o[3 * i + 0] = (uint8_t)(px[h][i] & 0xFFu);
+                        o[3 * i + 1] = (uint8_t)((px[h][i] >> 8) & 0xFFu);
+                        o[3 * i + 2] = (uint8_t)((px[h][i] >> 16) & 0xFFu);
+                    }
+            }
+        }
+        if (clean && a.lower_clean != nullptr) {  // (workgroup-uniform) the tile holds c0 != 0 now
+            __syncthreads();
+            if (threadIdx.x == 0u) a.lower_clean[t] = 0u;
+        }
+    }
+}
+
 // Dynamic textures (tr_scene_set_texture*): image `which` of a scene replaced by a w x h image of packed rgb8 rows, in
 // the plain array and in the texel set together; tr_pack.h has the rule (pack_quad, shared with the host).  The grid is
 // that of a frame of w x h pixels -- the image may BE one (tr_scene_set_texture_from_frame): a workgroup of 256 lanes
@@ -3417,6 +3535,40 @@ int launch_bloom(const BloomArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_bloom<true>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
     else
         hipLaunchKernelGGL((k_bloom<false>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_grade(const GradeArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out || !a.lut || a.rule.n < 2u || a.rule.n > GRADE_MAX_N || (uintptr_t)a.lut % 16u != 0u) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower_clean != nullptr && (a.out != a.fb || a.lower_clean != a.fbclean || a.rule.c0 == 0u)) return (int)hipErrorInvalidValue;
+    // whole words: every unit of four pixels is three aligned words of either buffer
+    const bool words = a.frame.width % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u;
+    const bool lds = a.rule.n <= GRADE_LDS_MAX_N;
+    const size_t lds_bytes = lds ? (size_t)((a.rule.n * a.rule.n * a.rule.n + 3u) / 4u) * 16u : 0u;
+    // persistent workgroups: as many as the device holds at once -- per CU what its LDS admits beside the waves' limit
+    int dev = 0, cus = 0, lds_per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        return (int)hipErrorInvalidDevice;
+    if (hipDeviceGetAttribute(&lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || lds_per_cu < 65536)
+        lds_per_cu = 65536;
+    uint32_t per_cu = (uint32_t)GRADE_MAX_PER_CU;
+    if (lds) per_cu = std::min<uint32_t>(per_cu, (uint32_t)((size_t)lds_per_cu / lds_bytes));
+    const uint32_t grid = std::min<uint32_t>((uint32_t)cus * per_cu, n_tiles);
+    if (lds && words)
+        hipLaunchKernelGGL((k_grade<true, true>), dim3(grid), dim3(GRADE_THREADS), lds_bytes, st, a);
+    else if (lds)
+        hipLaunchKernelGGL((k_grade<true, false>), dim3(grid), dim3(GRADE_THREADS), lds_bytes, st, a);
+    else if (words)
+        hipLaunchKernelGGL((k_grade<false, true>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_grade<false, false>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -402,6 +402,10 @@ struct tr_scene {
     // frame's (3 * W * H bytes, n_tiles words; allocated at the first such call)
     uint8_t *d_dof_fb = nullptr;
     uint32_t *d_dof_clean = nullptr;
+    // tr_scene_set_lut: the colour lookup table as k_grade reads it -- lut_n^3 packed entries, padded to whole 16-byte
+    // pieces; lut_c0: its entry 0, what a cleared tile becomes.  lut_n == 0: no table
+    uint32_t *d_lut = nullptr;
+    uint32_t lut_n = 0, lut_c0 = 0;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
     // memory not written".  Raised by the tile kernel for the empty tiles of a cleared frame (and by
@@ -2484,6 +2488,7 @@ void destroy(tr_scene *s)
     dev_free(s->d_resolved);
     dev_free(s->d_dof_fb);
     dev_free(s->d_dof_clean);
+    dev_free(s->d_lut);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
     for (tr_scene::HostFlags &f : s->host_flags) dev_free(f.clean);
@@ -4508,6 +4513,165 @@ int tr_bloom_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_bloom_host: null argument");
     if (out == rgb) return tr::fail(TR_E_INVALID, "tr_bloom_host: out is rgb (the rule reads neighbours: not in place)");
     bloom_host(width, height, rgb, out, bloom_rule(p));
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_GRADE_MAX_N == GRADE_MAX_N, "tr_grade.h restates the header");
+
+int check_grade_n(uint32_t n, const char *who)
+{
+    if (n < 2u || n > GRADE_MAX_N) return tr::fail(TR_E_INVALID, std::string(who) + ": the table's edge n must be 2..TR_GRADE_MAX_N");
+    return TR_OK;
+}
+
+int check_grade_scene(const tr_scene *s, const char *who)
+{
+    if (s->lut_n == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no lookup table (tr_scene_set_lut)");
+    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    return TR_OK;
+}
+
+// The scene's rows of a frame-sized buffer: their first byte and their number of bytes.
+void band_bytes(const tr_scene *s, size_t *first, size_t *count)
+{
+    *first = (size_t)s->width * (size_t)(s->height - (uint32_t)s->frame.band_y1) * 3;
+    *count = (size_t)s->width * (size_t)(s->frame.band_y1 - s->frame.band_y0) * 3;
+}
+
+// Enqueues the grade of the current frame into `out_device` (null: in place) behind everything issued so far.  A
+// logically cleared scene whose c0 is zero is the caller's business; with another c0 the clear is made real here and the
+// kernel turns every (flagged) tile into c0.  No depth is read: a depth left on the chip stays there.
+int enqueue_grade(tr_scene *s, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st != TR_OK) return st;
+    GradeArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower_clean = (!out_device && s->lut_c0 != 0u) ? s->d_fbclean : nullptr;
+    a.lut = s->d_lut;
+    a.frame = s->frame;
+    a.rule.n = s->lut_n;
+    a.rule.c0 = s->lut_c0;
+    {
+        Timed t(s, K_GRADE);
+        int rc = launch_grade(a, s->stream);
+        if (rc) return launch_status(rc, "k_grade");
+    }
+    // (in place a colour-clean flag of the DEVICE buffer may come down; a record of a page-locked host buffer says what
+    // that host buffer holds, which this call does not change: see enqueue_accumulate)
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_set_lut(tr_scene *s, uint32_t n, const uint8_t *lut)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_set_lut: null scene");
+    if (n != 0u) {
+        int st = check_grade_n(n, "tr_scene_set_lut");
+        if (st != TR_OK) return st;
+        if (!lut) return tr::fail(TR_E_INVALID, "tr_scene_set_lut: null table");
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // one word an entry, padded to whole 16-byte pieces (k_grade stages the table by pieces)
+    const size_t entries = (size_t)n * n * n, padded = (entries + 3u) / 4u * 4u;
+    std::vector<uint32_t> words(padded, 0u);
+    if (n) grade_expand(n, lut, words.data());
+    uint32_t *d_new = nullptr;
+    int st = TR_OK;
+    if (n && (st = dev_alloc(&d_new, padded)) != TR_OK) return st;
+    // frames issued so far keep their table: everything queued runs before it changes
+    if ((st = submit_pending(s)) != TR_OK) {
+        dev_free(d_new);
+        return st;
+    }
+    hipError_t e = hipStreamSynchronize(s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
+    if (e == hipSuccess && n) e = hipMemcpy(d_new, words.data(), padded * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
+    if (e != hipSuccess) {
+        dev_free(d_new);
+        HIP_TRY(e);
+    }
+    dev_free(s->d_lut);
+    s->d_lut = d_new;
+    s->lut_n = n;
+    s->lut_c0 = n ? words[0] : 0u;
+    return TR_OK;
+}
+
+int tr_scene_grade(tr_scene *s, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_grade: null scene");
+    int st = check_grade_scene(s, "tr_scene_grade");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    void *target = nullptr;
+    if (out) {
+        st = classify_out(s, out, bytes, "tr_scene_grade", "tr_scene_get_graded", "grades", 0u, &target);
+        if (st != TR_OK) return st;
+    }
+    if (s->z_fb_cleared && s->lut_c0 == 0u) {
+        // a logically cleared frame is black and black maps to c0 = black: zeros out of place, itself in place
+        if (!target) return TR_OK;
+        st = submit_pending(s);
+        if (st != TR_OK) return st;
+        size_t first = 0, count = 0;
+        band_bytes(s, &first, &count);
+        HIP_TRY(hipMemsetAsync((uint8_t *)target + first, 0, count, s->stream));
+        s->quiescent = false;
+        s->observed_seq = s->pass_seq;
+        return TR_OK;
+    }
+    st = enqueue_grade(s, (uint8_t *)target);
+    if (st != TR_OK) return st;
+    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
+    // overflow would undo a grade made in place, or change what one made elsewhere was made from
+    s->observed_seq = s->pass_seq;
+    return TR_OK;
+}
+
+int tr_scene_get_graded(tr_scene *s, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_graded: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_graded: null argument");
+    int st = check_grade_scene(s, "tr_scene_get_graded");
+    if (st != TR_OK) return st;
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const size_t bytes = (size_t)s->width * s->height * 3;
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
+        s->resolved_bytes = 0;
+        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
+        s->resolved_bytes = bytes;
+    }
+    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
+    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
+    if (!whole_frame || (s->z_fb_cleared && s->lut_c0 == 0u)) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    if (!(s->z_fb_cleared && s->lut_c0 == 0u)) {
+        st = enqueue_grade(s, s->d_resolved);
+        if (st != TR_OK) return st;
+    }
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// The rule of tr_grade.h over a caller's pixels, on the host.  Needs no GPU.
+int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out, uint32_t n, const uint8_t *lut)
+{
+    int st = check_grade_n(n, "tr_grade_host");
+    if (st != TR_OK) return st;
+    if (!lut) return tr::fail(TR_E_INVALID, "tr_grade_host: null table");
+    if (n_pixels == 0u) return TR_OK;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_grade_host: null argument");
+    grade_host(n_pixels, rgb, out, n, lut);
     return TR_OK;
 }
 

@@ -377,6 +377,96 @@ def bloom_host(rgb, params):
     return out
 
 
+GRADE_MAX_N = 33   # (TR_GRADE_MAX_N)
+
+
+def _lut_array(lut, who):
+    """A colour lookup table as the library takes it: contiguous uint8 [n, n, n, 3] indexed [b][g][r], n = 2..33."""
+    if not isinstance(lut, np.ndarray) or lut.dtype != np.uint8:
+        raise ValueError("%s: the table must be a uint8 array [n, n, n, 3]" % who)
+    if lut.ndim != 4 or lut.shape[3] != 3 or not (lut.shape[0] == lut.shape[1] == lut.shape[2]):
+        raise ValueError("%s: the table must have the shape [n, n, n, 3] (indexed [b][g][r])" % who)
+    if not 2 <= lut.shape[0] <= GRADE_MAX_N:
+        raise ValueError("%s: the table's edge n must be 2..%d" % (who, GRADE_MAX_N))
+    return np.ascontiguousarray(lut)
+
+
+def grade_host(rgb, lut):
+    """tr_grade_host: the rule of Scene.grade on the host (no GPU needed), by the inline functions k_grade calls.  rgb
+    uint8 [..., 3] in any pixel order, lut uint8 [n, n, n, 3] indexed [b][g][r].  Returns the graded pixels and leaves its
+    arguments alone."""
+    table = _lut_array(lut, "grade_host")
+    if not isinstance(rgb, np.ndarray) or rgb.dtype != np.uint8 or rgb.ndim < 1 or rgb.shape[-1] != 3:
+        raise ValueError("grade_host: rgb must be a uint8 array [..., 3]")
+    src = np.ascontiguousarray(rgb)
+    out = np.empty_like(src)
+    check(load_library().tr_grade_host(src.size // 3, src.ctypes.data, out.ctypes.data, table.shape[0], table.ctypes.data))
+    return out
+
+
+def lut_from_function(n, f):
+    """The table [n, n, n, 3] (indexed [b][g][r]) of a colour function: f takes a float array [..., 3] of rgb in [0, 1] at
+    the table's grid points i / (n - 1) and returns one of the same shape in [0, 1] (clipped), rounded half up to u8."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= GRADE_MAX_N:
+        raise ValueError("lut_from_function: n must be an integer 2..%d" % GRADE_MAX_N)
+    axis = np.arange(n, dtype=np.float64) / (n - 1)
+    b, g, r = np.meshgrid(axis, axis, axis, indexing="ij")
+    out = np.asarray(f(np.stack([r, g, b], -1)), np.float64)
+    if out.shape != (n, n, n, 3):
+        raise ValueError("lut_from_function: f must return an array of its argument's shape")
+    return np.floor(np.clip(out, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
+def lut_identity(n):
+    """The identity table: E(i) = round(255 i / (n - 1)) in each channel (exact where n - 1 divides 255, else within 1)."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= GRADE_MAX_N:
+        raise ValueError("lut_identity: n must be an integer 2..%d" % GRADE_MAX_N)
+    e = ((2 * 255 * np.arange(n, dtype=np.int64) + (n - 1)) // (2 * (n - 1))).astype(np.uint8)
+    out = np.empty((n, n, n, 3), np.uint8)
+    out[..., 0], out[..., 1], out[..., 2] = e[None, None, :], e[None, :, None], e[:, None, None]
+    return out
+
+
+def load_cube(path):
+    """A 3-D table from a .cube text file: LUT_3D_SIZE n, an optional TITLE, DOMAIN_MIN 0 0 0 / DOMAIN_MAX 1 1 1 (the unit
+    domain, also the default), then n^3 lines of three floats, red fastest.  Returns uint8 [n, n, n, 3] indexed
+    [b][g][r], values clipped to [0, 1] and rounded half up.  ValueError for a 1-D table (LUT_1D_SIZE), another domain,
+    n outside 2..33 and a wrong number of entries."""
+    n, rows = None, []
+    with open(path) as fh:
+        for line in fh:
+            line = line.split("#", 1)[0].strip()
+            if not line:
+                continue
+            word = line.split()
+            key = word[0].upper()
+            if key == "TITLE":
+                continue
+            if key == "LUT_1D_SIZE" or key == "LUT_1D_INPUT_RANGE":
+                raise ValueError("load_cube: %s holds a 1-D table; a 3-D table expresses it" % path)
+            if key == "LUT_3D_SIZE":
+                n = int(word[1])
+                if not 2 <= n <= GRADE_MAX_N:
+                    raise ValueError("load_cube: LUT_3D_SIZE must be 2..%d, not %d" % (GRADE_MAX_N, n))
+                continue
+            if key in ("DOMAIN_MIN", "DOMAIN_MAX", "LUT_3D_INPUT_RANGE"):
+                want = {"DOMAIN_MIN": [0.0] * 3, "DOMAIN_MAX": [1.0] * 3, "LUT_3D_INPUT_RANGE": [0.0, 1.0]}[key]
+                if [float(v) for v in word[1:]] != want:
+                    raise ValueError("load_cube: only the unit domain is supported (%s)" % line)
+                continue
+            if key[0].isalpha():
+                raise ValueError("load_cube: unknown keyword %s" % word[0])
+            if len(word) != 3:
+                raise ValueError("load_cube: an entry is three numbers (%s)" % line)
+            rows.append([float(v) for v in word])
+    if n is None:
+        raise ValueError("load_cube: no LUT_3D_SIZE in %s" % path)
+    if len(rows) != n ** 3:
+        raise ValueError("load_cube: %d entries for LUT_3D_SIZE %d" % (len(rows), n))
+    vals = np.asarray(rows, np.float64).reshape(n, n, n, 3)
+    return np.floor(np.clip(vals, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
 def texel_set_host(pipeline_name, textures):
     """tr_texel_set_host: (words uint32 [n], blocks_per_row) -- the texel set tr_scene_create builds for the pipeline from
     four uint8 [h, w, 3] images of one size (csrc/tr_texels.h), by the function the library itself calls, on the host (no
@@ -872,6 +962,43 @@ class Scene:
             raise ValueError("get_bloom: params must come from bloom_params")
         out = np.empty((self.height, self.width, 3), np.uint8)
         code = load_library().tr_scene_get_bloom(self._h, C.addressof(params), out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return out
+
+    # --- colour grading (tr_scene_set_lut / tr_scene_grade / tr_scene_get_graded) ---------------------
+    def set_lut(self, lut):
+        """tr_scene_set_lut: the scene's colour lookup table, uint8 [n, n, n, 3] indexed [b][g][r], n = 2..33 (lut_identity,
+        lut_from_function, load_cube); None drops it.  Waits for the scene's queued work."""
+        if lut is None:
+            check(load_library().tr_scene_set_lut(self._h, 0, None))
+            return
+        table = _lut_array(lut, "set_lut")
+        check(load_library().tr_scene_set_lut(self._h, table.shape[0], table.ctypes.data))
+
+    def grade(self, out=None):
+        """tr_scene_grade: maps the current frame through the scene's table on the device.  out=None: in place -- every
+        later consumer sees the graded frame, z, winner words and the shadow buffer stay, calling it twice grades twice.
+        Otherwise `out` is a device pointer (int) to 3 * W * H bytes apart from every frame buffer of the scene, or an
+        array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().
+        Band scenes write their band's rows only.  No depth is needed."""
+        if out is None:
+            ptr = None
+        elif isinstance(out, np.ndarray):
+            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
+            ptr = out.ctypes.data
+        else:
+            ptr = int(out)
+        check(load_library().tr_scene_grade(self._h, ptr))
+        return out
+
+    def get_graded(self, strict=True):
+        """tr_scene_get_graded: the current frame graded on the device, as an [H, W, 3] uint8 array.  Synchronizes; the
+        scene's frame stays ungraded."""
+        out = np.empty((self.height, self.width, 3), np.uint8)
+        code = load_library().tr_scene_get_graded(self._h, out.ctypes.data)
         if strict:
             check(code)
         self.last_status = code
