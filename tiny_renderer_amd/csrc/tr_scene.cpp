@@ -2723,6 +2723,18 @@ int create(uint32_t width, uint32_t height, const tr_mesh *mesh, const tr_image_
 // the call.
 bool fatal(int st) { return st == TR_E_HIP || st == TR_E_NOMEM || st == TR_E_INVALID; }
 
+// Does the scene render the whole frame (no band, tr_options.band_row0/1)?
+bool whole_frame(const tr_scene *s) { return s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height; }
+
+// The refusal of every entry point that would queue work on a broken scene.
+int unusable() { return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain"); }
+
+// Every pass issued so far is now in a consumer's hands -- a copy, a stage or a merge has read the frame, or changed
+// it: a bin overflow among those passes can no longer be repaired by rendering again (that would undo what was made in
+// place, or change the frame that a result made elsewhere was made from), and tr_scene_sync will say so
+// (TR_E_BIN_OVERFLOW).
+void handed_on(tr_scene *s) { s->observed_seq = s->pass_seq; }
+
 // tr_scene_resolve / tr_scene_get_resolved: is `factor` one this scene's frame can be resolved by?  (A source block
 // of factor x factor pixels must not straddle a 128 x 16 tile or the scene's band.)
 int check_resolve(const tr_scene *s, uint32_t factor)
@@ -2734,6 +2746,8 @@ int check_resolve(const tr_scene *s, uint32_t factor)
         return tr::fail(TR_E_INVALID, "resolve: the band's rows (tr_options.band_row0/1) must be multiples of the factor");
     return TR_OK;
 }
+
+size_t resolved_bytes(const tr_scene *s, uint32_t factor) { return (size_t)(s->width / factor) * (s->height / factor) * 3; }
 
 // Enqueues the resolve of the current frame into `out_device` behind everything issued so far.
 int enqueue_resolve(tr_scene *s, uint32_t factor, uint8_t *out_device)
@@ -2756,6 +2770,190 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return frame_status;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
+// ---------------------------------------------------------------------------------------------
+// A stage (resolve, accumulate, depth of field, bloom, grade) derives an image from the current frame.  Its own code is
+// its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
+//   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
+//   for a non-null `out`, then refuse_overlap (resolve has none); the cleared-scene shortcut where the stage has one --
+//   cleared_out_of_place, while in place a cleared frame is its own result and NOTHING happens, handed_on included; the
+//   enqueue_* into the target, into the frame itself, or through the scratch frame (in_place_via_scratch); handed_on.
+//   tr_scene_get_<stage>: the same checks, then get_stage.
+// A refused call has queued nothing and changed nothing, but for the read-back record of a tr_host_alloc `out` that
+// classify_out accepted.  In place a colour-clean flag of the DEVICE buffer may change; a record of a page-locked host
+// buffer (HostFlags) says what that host buffer holds, which no in-place call changes: the next read-back compares the
+// two as always.  Each enqueue_* keeps its own choice among flush_clear_color, submit_pending and depth_in_memory: that
+// choice decides whether a depth left on the chip stays there.
+
+size_t frame_bytes(const tr_scene *s) { return (size_t)s->width * s->height * 3; }
+
+// The scene's rows of a frame-sized buffer: their first byte and their number of bytes (a whole frame: all of it).
+void band_bytes(const tr_scene *s, size_t *first, size_t *count)
+{
+    *first = (size_t)s->width * (size_t)(s->height - (uint32_t)s->frame.band_y1) * 3;
+    *count = (size_t)s->width * (size_t)(s->frame.band_y1 - s->frame.band_y0) * 3;
+}
+
+// The frame on its way, its depth in memory behind valid flags.
+int depth_in_memory(tr_scene *s)
+{
+    int st = submit_pending(s);
+    if (st == TR_OK) st = ensure_depth(s);
+    if (st == TR_OK) st = need_z(s, s->cur_slot);
+    return st;
+}
+
+// The colour buffer of the frame tr_scene_select_frame(s, back) would make current.
+uint8_t *kept_frame_buffer(const tr_scene *s, uint32_t back)
+{
+    const size_t k = s->tail.params.size() - 1u - back;
+    return s->tail.fbs.empty() ? s->slots[(size_t)s->tail.slot[k]].fb : (uint8_t *)s->tail.fbs[k];
+}
+
+// `out` of a stage: memory from tr_host_alloc of at least `bytes` bytes (the kernel stores through its mapped address,
+// and the buffer's sparse read-back record lapses) or device memory.  The address the kernel stores to goes to *target.
+// who / getter / frame: the entry point's words in the error texts.
+int classify_out(void *out, size_t bytes, const char *who, const char *getter, const char *frame, void **target_out)
+{
+    const std::string w(who);
+    void *target = nullptr;
+    bool known_host = false;
+    {
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(out);
+        if (it != g_host_allocs.end()) {
+            known_host = true;
+            if (it->second.bytes >= bytes) {
+                target = it->second.device;
+                // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
+                it->second.writer = 0u;
+                it->second.gen += 1u;
+            }
+        }
+    }
+    if (known_host && !target) return tr::fail(TR_E_INVALID, w + ": the host buffer is smaller than the " + frame);
+    if (!target) {
+        const std::string text = w + ": `out` is neither device memory nor from tr_host_alloc (" + getter + " takes any host memory)";
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, text);
+        }
+        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
+        target = out;
+    }
+    *target_out = target;
+    return TR_OK;
+}
+
+// `target` (from classify_out) must not be (part of) a frame the kernel may read, or another one the scene keeps flags
+// of: none of its slots, no frame buffer with a flag set, none of the last n_kept kept frames.
+int refuse_overlap(const tr_scene *s, const void *target, size_t bytes, const char *who, const char *verb, uint32_t n_kept)
+{
+    auto overlaps = [&](const uint8_t *fb) {
+        return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
+    };
+    bool hit = false;
+    for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
+    for (const tr_scene::FbFlags &f : s->fb_flags) hit = hit || overlaps(f.fb);
+    for (uint32_t k = 0; k < n_kept; k++) hit = hit || overlaps(kept_frame_buffer(s, k));
+    if (!hit) return TR_OK;
+    return tr::fail(TR_E_INVALID, std::string(who) + ": `out` overlaps a frame buffer of the scene (out == NULL " + verb + " in place)");
+}
+
+// A non-null `out` of a frame-sized stage through both steps; null (in place) leaves *target null.
+int frame_out(const tr_scene *s, void *out, const char *who, const char *getter, const char *verb, uint32_t n_kept, void **target)
+{
+    *target = nullptr;
+    if (!out) return TR_OK;
+    int st = classify_out(out, frame_bytes(s), who, getter, "frame", target);
+    return st != TR_OK ? st : refuse_overlap(s, *target, frame_bytes(s), who, verb, n_kept);
+}
+
+// The cleared-scene shortcut out of place: the stage's image of a logically cleared frame is black, so the scene's rows
+// of `target` become zeros behind everything issued so far, and no kernel runs.
+int cleared_out_of_place(tr_scene *s, void *target)
+{
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    size_t first = 0, count = 0;
+    band_bytes(s, &first, &count);
+    HIP_TRY(hipMemsetAsync((uint8_t *)target + first, 0, count, s->stream));
+    s->quiescent = false;
+    handed_on(s);
+    return TR_OK;
+}
+
+// In place for a stage that reads neighbours: enqueue(out_device, out_clean) into the scene's scratch frame and flag
+// set (one pair, shared: each call leaves them free behind its two copies), then, in stream order, the colour over the
+// current frame and the flags over the frame's colour-clean flags.
+template <typename Enqueue>
+int in_place_via_scratch(tr_scene *s, Enqueue enqueue)
+{
+    int st = TR_OK;
+    if (!s->d_dof_fb && (st = dev_alloc(&s->d_dof_fb, frame_bytes(s)))) return st;
+    if (!s->d_dof_clean && (st = dev_alloc(&s->d_dof_clean, (size_t)s->n_tiles))) return st;
+    if ((st = enqueue(s->d_dof_fb, s->d_dof_clean)) != TR_OK) return st;
+    HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, frame_bytes(s), hipMemcpyDeviceToDevice, s->stream));
+    if (s->d_fbclean) HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
+    return TR_OK;
+}
+
+// The library's read-back buffer, one per scene and shared by every getter: s->d_resolved of at least `bytes` bytes,
+// grown only while the stream is idle (sync_and_status has waited).  zero: the kernel will not cover all of it -- a band
+// scene's writes its own rows only, a stage that short-circuits on a cleared scene runs none -- and the rest reads as zeros.
+int read_back_buffer(tr_scene *s, size_t bytes, bool zero)
+{
+    if (s->resolved_bytes < bytes) {
+        dev_free(s->d_resolved);
+        s->resolved_bytes = 0;
+        int st = dev_alloc(&s->d_resolved, bytes);
+        if (st) return st;
+        s->resolved_bytes = bytes;
+    }
+    if (zero) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
+    return TR_OK;
+}
+
+// Does a stage whose image of a black frame is black short-circuit?  (depth of field, bloom; grade: cleared_to_black)
+bool cleared(const tr_scene *s) { return s->z_fb_cleared; }
+
+// tr_scene_get_<stage>, after the stage's checks, in the getters' order (above): wait for the frame and take its status;
+// enqueue(out_device) into the library's buffer -- unless the stage short-circuits on this scene (short_circuits, may be
+// null; asked after the wait, which may have rendered held-back frames) --; wait, copy `bytes` bytes to rgb.
+template <typename Enqueue>
+int get_stage(tr_scene *s, uint8_t *rgb, size_t bytes, bool (*short_circuits)(const tr_scene *), Enqueue enqueue)
+{
+    int fst = sync_and_status(s);
+    if (fatal(fst)) return fst;
+    const bool skip = short_circuits && short_circuits(s);
+    int st = read_back_buffer(s, bytes, skip || !whole_frame(s));
+    if (st == TR_OK && !skip) st = enqueue(s->d_resolved);
+    if (st != TR_OK) return st;
+    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// A launch on dst's stream that reads src's buffers and writes dst's: behind src's work, and src's stream behind the
+// launch, so that a later render of src does not overtake it.  Both scenes' passes are then handed on: rendering one of
+// them again after a bin overflow would undo the merge, or change what it read.
+template <typename Launch>
+int cross_scene_launch(tr_scene *dst, tr_scene *src, Launch launch)
+{
+    if (!src->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&src->ev_comp_ready, hipEventDisableTiming));
+    if (!dst->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&dst->ev_comp_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(src->ev_comp_ready, src->stream));
+    HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_comp_ready, 0));
+    int st = launch();
+    if (st != TR_OK) return st;
+    HIP_TRY(hipEventRecord(dst->ev_comp_done, dst->stream));
+    HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_comp_done, 0));
+    dst->quiescent = src->quiescent = false;
+    handed_on(dst);
+    handed_on(src);
+    return TR_OK;
 }
 
 int depth_view(tr_scene *s, int frame_status, const float *src, uint8_t *rgb)
@@ -2956,7 +3154,7 @@ int tr_scene_set_camera(tr_scene *s, const float look_from[3], const float look_
 int tr_scene_render(tr_scene *s)
 {
     if (!s) return tr::fail(TR_E_INVALID, "null scene");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
     memcpy(s->last.light, s->light, 12);
     memcpy(s->last.from, s->from, 12);
@@ -3008,7 +3206,7 @@ int tr_scene_render(tr_scene *s)
 int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, void *const *frame_buffers_device)
 {
     if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     if (n_frames == 0) return TR_OK;
     if (frame_buffers_device)
         for (uint32_t i = 0; i < n_frames; i++)
@@ -3037,7 +3235,7 @@ static int render_frames_tables(tr_scene *s, uint32_t n_frames, const tr_frame_p
                                 const float *tables, void *const *frame_buffers_device)
 {
     if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     int st = check_instances(s, n, tables);
     if (st != TR_OK) return st;
     if (n_frames == 0) return TR_OK;
@@ -3149,7 +3347,7 @@ int tr_scene_render_frames_morphed(tr_scene *s, uint32_t n_frames, const tr_fram
                                    const float *weights, void *const *frame_buffers_device)
 {
     if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
     if (n_weights && n_frames && !weights) return tr::fail(TR_E_INVALID, "null weights");
     if (n_frames == 0) return TR_OK;
@@ -3235,7 +3433,7 @@ int tr_scene_render_frames_skinned(tr_scene *s, uint32_t n_frames, const tr_fram
                                    const tr_instance_xform *palettes, void *const *frame_buffers_device)
 {
     if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     if (n_bones != 0u && n_bones != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
     if (n_bones && n_frames && !palettes) return tr::fail(TR_E_INVALID, "null palettes");
     if (n_frames == 0) return TR_OK;
@@ -3406,7 +3604,6 @@ int tr_scene_get_frame_buffer_async(tr_scene *s, uint8_t *rgb)
     // The sparse form needs a scene that renders the WHOLE frame: k_read_back writes the tiles of the scene's band only,
     // and "the buffer ends up holding the complete frame" must hold for a band scene too (whose other rows, in a
     // caller's all-gather buffer, come from other ranks): such a scene takes the copy engine.
-    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
     void *mapped = nullptr;
     uint64_t serial = 0, gen = 0;
     bool mine = false;  // this scene was the buffer's last writer
@@ -3414,7 +3611,7 @@ int tr_scene_get_frame_buffer_async(tr_scene *s, uint8_t *rgb)
         std::lock_guard<std::mutex> lock(g_host_mutex);
         auto it = g_host_allocs.find(rgb);
         if (it != g_host_allocs.end()) {
-            if (it->second.bytes >= bytes && whole_frame && s->width % 16u == 0u && s->d_fbclean) {
+            if (it->second.bytes >= bytes && whole_frame(s) && s->width % 16u == 0u && s->d_fbclean) {
                 mapped = it->second.device;
                 serial = it->second.serial;
                 mine = it->second.writer == s->id;
@@ -3456,9 +3653,7 @@ int tr_scene_get_frame_buffer_async(tr_scene *s, uint8_t *rgb)
         HIP_TRY(hipMemcpyAsync(rgb, s->d_fb, bytes, hipMemcpyDeviceToHost, s->stream));
     }
     s->quiescent = false;
-    // every pass issued so far is now in a consumer's hands: a bin overflow among them can no longer
-    // be repaired by rendering again, and tr_scene_sync will say so (TR_E_BIN_OVERFLOW)
-    s->observed_seq = s->pass_seq;
+    handed_on(s);
     return TR_OK;
 }
 
@@ -3468,39 +3663,11 @@ int tr_scene_resolve(tr_scene *s, uint32_t factor, void *out)
     int st = check_resolve(s, factor);
     if (st != TR_OK) return st;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)(s->width / factor) * (s->height / factor) * 3;
-    // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
     void *target = nullptr;
-    bool known_host = false;
-    {
-        std::lock_guard<std::mutex> lock(g_host_mutex);
-        auto it = g_host_allocs.find(out);
-        if (it != g_host_allocs.end()) {
-            known_host = true;
-            if (it->second.bytes >= bytes) {
-                target = it->second.device;
-                // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
-                it->second.writer = 0u;
-                it->second.gen += 1u;
-            }
-        }
-    }
-    if (known_host && !target) return tr::fail(TR_E_INVALID, "tr_scene_resolve: the host buffer is smaller than the resolved frame");
-    if (!target) {
-        hipPointerAttribute_t attr = {};
-        if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
-            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
-            return tr::fail(TR_E_INVALID, "tr_scene_resolve: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_resolved takes any host memory)");
-        }
-        if (attr.type != hipMemoryTypeDevice)
-            return tr::fail(TR_E_INVALID, "tr_scene_resolve: `out` is neither device memory nor from tr_host_alloc (tr_scene_get_resolved takes any host memory)");
-        target = out;
-    }
-    st = enqueue_resolve(s, factor, (uint8_t *)target);
-    if (st != TR_OK) return st;
-    // every pass issued so far is now in a consumer's hands (as in tr_scene_get_frame_buffer_async)
-    s->observed_seq = s->pass_seq;
-    return TR_OK;
+    st = classify_out(out, resolved_bytes(s, factor), "tr_scene_resolve", "tr_scene_get_resolved", "resolved frame", &target);
+    if (st == TR_OK) st = enqueue_resolve(s, factor, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb)
@@ -3508,21 +3675,7 @@ int tr_scene_get_resolved(tr_scene *s, uint32_t factor, uint8_t *rgb)
     if (!s || !rgb) return tr::fail(TR_E_INVALID, "null argument");
     int st = check_resolve(s, factor);
     if (st != TR_OK) return st;
-    int fst = sync_and_status(s);
-    if (fatal(fst)) return fst;
-    const size_t bytes = (size_t)(s->width / factor) * (s->height / factor) * 3;
-    if (s->resolved_bytes < bytes) {
-        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
-        s->resolved_bytes = 0;
-        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
-        s->resolved_bytes = bytes;
-    }
-    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
-    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
-    if (!whole_frame) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
-    st = enqueue_resolve(s, factor, s->d_resolved);
-    if (st != TR_OK) return st;
-    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+    return get_stage(s, rgb, resolved_bytes(s, factor), nullptr, [&](uint8_t *o) { return enqueue_resolve(s, factor, o); });
 }
 
 int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base)
@@ -3536,22 +3689,16 @@ int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base)
         return tr::fail(TR_E_INVALID, "tr_scene_composite: the scenes render different bands (tr_options.band_row0/1)");
     if (dst->d_winner && !src->d_winner)
         return tr::fail(TR_E_INVALID, "tr_scene_composite: dst has TR_OPT_WINNER_TAP and src has not");
-    if (dst->broken || src->broken)
-        return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (dst->broken || src->broken) return unusable();
     HIP_TRY(hipSetDevice(dst->device));
     if (src->z_fb_cleared) return TR_OK;  // a logically cleared frame covers no pixel
-    // src: the frame on its way, its depth in memory behind valid flags
-    int st = submit_pending(src);
-    if (st == TR_OK) st = ensure_depth(src);
-    if (st == TR_OK) st = need_z(src, src->cur_slot);
-    // dst: the same, and a pending clear made real (its z: every flag up)
+    int st = depth_in_memory(src);
+    // dst: its frame on its way and its depth in memory too, and a pending clear made real (its z: every flag up)
     if (st == TR_OK) st = submit_pending(dst);
     if (st == TR_OK && !dst->z_fb_cleared) st = ensure_depth(dst);
     if (st == TR_OK) st = flush_clear_color(dst);
     if (st == TR_OK) st = need_z(dst, dst->cur_slot);
     if (st != TR_OK) return st;
-    if (!src->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&src->ev_comp_ready, hipEventDisableTiming));
-    if (!dst->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&dst->ev_comp_done, hipEventDisableTiming));
     CompositeArgs a = {};
     a.dst_z = dst->d_z;
     a.dst_fb = dst->d_fb;
@@ -3567,23 +3714,13 @@ int tr_scene_composite(tr_scene *dst, tr_scene *src, uint32_t winner_base)
     a.src_zclean = src->d_zclean;
     a.frame = dst->frame;
     a.winner_base = winner_base;
-    // behind src's frame on dst's stream; src's stream behind the merge: a later render of src does not overtake it
-    HIP_TRY(hipEventRecord(src->ev_comp_ready, src->stream));
-    HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_comp_ready, 0));
-    {
+    st = cross_scene_launch(dst, src, [&] {
         Timed t(dst, K_COMPOSITE);
         int rc = launch_composite(a, dst->stream);
-        if (rc) return launch_status(rc, "k_composite");
-    }
-    HIP_TRY(hipEventRecord(dst->ev_comp_done, dst->stream));
-    HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_comp_done, 0));
-    dst->slots[(size_t)dst->cur_slot].z_deferred = false;  // (the merged depth is in memory)
-    dst->quiescent = src->quiescent = false;
-    // both frames are now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering one of them again
-    // after a bin overflow would undo the merge, or change what it read
-    dst->observed_seq = dst->pass_seq;
-    src->observed_seq = src->pass_seq;
-    return TR_OK;
+        return rc ? launch_status(rc, "k_composite") : TR_OK;
+    });
+    if (st == TR_OK) dst->slots[(size_t)dst->cur_slot].z_deferred = false;  // (the merged depth is in memory)
+    return st;
 }
 
 // The rule of tr_composite.h over caller's arrays, on the host.  Needs no GPU.
@@ -3612,7 +3749,7 @@ int render_split_pass(tr_scene *s, bool colour, const char *who)
     const PipelineDesc &pd = kPipelines[s->pipeline];
     if (pd.n_passes != 2)
         return tr::fail(TR_E_INVALID, std::string(who) + ": the scene's pipeline `" + pd.name + "` has one pass (shadow and occlusion have two)");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
     int st = submit_pending(s);  // what tr_scene_render holds back goes first
     if (st != TR_OK) return st;
@@ -3631,7 +3768,7 @@ int render_split_pass(tr_scene *s, bool colour, const char *who)
         s->host_status = st;
         return st;
     }
-    s->observed_seq = s->pass_seq;
+    handed_on(s);
     return TR_OK;
 }
 
@@ -3651,8 +3788,7 @@ int tr_scene_shadow_merge(tr_scene *dst, tr_scene *src)
     if (kPipelines[dst->pipeline].n_passes != 2 || kPipelines[src->pipeline].n_passes != 2)
         return tr::fail(TR_E_INVALID, "tr_scene_shadow_merge: a scene's pipeline has one pass and no shadow buffer of its own "
                                       "(shadow and occlusion have two)");
-    if (dst->broken || src->broken)
-        return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (dst->broken || src->broken) return unusable();
     if (src->shadow_cleared) return TR_OK;  // a logically cleared buffer holds f32::MIN alone: it replaces nothing
     tr_scene::FrameSlot &ds = dst->slots[(size_t)dst->cur_slot];
     const tr_scene::FrameSlot &ss = src->slots[(size_t)src->cur_slot];
@@ -3668,31 +3804,20 @@ int tr_scene_shadow_merge(tr_scene *dst, tr_scene *src)
     if (st == TR_OK) st = submit_pending(dst);
     if (st == TR_OK) st = flush_clear_shadow(dst);
     if (st != TR_OK) return st;
-    if (!src->ev_comp_ready) HIP_TRY(hipEventCreateWithFlags(&src->ev_comp_ready, hipEventDisableTiming));
-    if (!dst->ev_comp_done) HIP_TRY(hipEventCreateWithFlags(&dst->ev_comp_done, hipEventDisableTiming));
     ShadowMergeArgs a = {};
     a.dst = dst->d_shadow;
     a.dst_clean = dst->d_sclean;
     a.src = src->d_shadow;
     a.src_clean = src->d_sclean;
     a.frame = dst->frame_full;
-    // behind src's shadow pass on dst's stream; src's stream behind the merge: a later render of src does not overtake it
-    HIP_TRY(hipEventRecord(src->ev_comp_ready, src->stream));
-    HIP_TRY(hipStreamWaitEvent(dst->stream, src->ev_comp_ready, 0));
-    {
+    // (handed on: replaying a frame after a bin overflow would run the scene's own shadow pass over the merged buffer)
+    st = cross_scene_launch(dst, src, [&] {
         Timed t(dst, K_SHADOW_MERGE);
         int rc = launch_shadow_merge(a, dst->stream);
-        if (rc) return launch_status(rc, "k_shadow_merge");
-    }
-    HIP_TRY(hipEventRecord(dst->ev_comp_done, dst->stream));
-    HIP_TRY(hipStreamWaitEvent(src->stream, dst->ev_comp_done, 0));
-    if (ss.shadow_matrix_set) note_shadow_matrix(ds, ss.shadow_matrix);  // (equal already, or dst's buffer had none)
-    dst->quiescent = src->quiescent = false;
-    // both scenes' passes are now in a consumer's hands (as in tr_scene_composite): replaying a frame after a bin
-    // overflow would run the scene's own shadow pass over the merged buffer, or change what the merge read
-    dst->observed_seq = dst->pass_seq;
-    src->observed_seq = src->pass_seq;
-    return TR_OK;
+        return rc ? launch_status(rc, "k_shadow_merge") : TR_OK;
+    });
+    if (st == TR_OK && ss.shadow_matrix_set) note_shadow_matrix(ds, ss.shadow_matrix);  // (equal already, or dst's buffer had none)
+    return st;
 }
 
 // The rule of tr_shadow_merge.h over caller's arrays, on the host.  Needs no GPU.
@@ -3767,12 +3892,10 @@ int enqueue_pack(tr_scene *s, uint32_t which, const uint8_t *src_device, const u
         HIP_TRY(hipEventRecord(s->ev_comp_done, s->stream));
         HIP_TRY(hipStreamWaitEvent(producer->stream, s->ev_comp_done, 0));
         producer->quiescent = false;
-        producer->observed_seq = producer->pass_seq;
+        handed_on(producer);
     }
     s->quiescent = false;
-    // the scene's passes issued so far count as handed on (as after tr_scene_composite): rendering one of them again
-    // after a bin overflow would draw the new texture
-    s->observed_seq = s->pass_seq;
+    handed_on(s);  // (rendering one of its passes again after a bin overflow would draw the new texture)
     return TR_OK;
 }
 
@@ -3787,7 +3910,7 @@ int check_set_texture(const tr_scene *s, uint32_t which, uint32_t w, uint32_t h,
                  s->tex.w[which], s->tex.h[which]);
         return tr::fail(TR_E_INVALID, t + buf);
     }
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     return TR_OK;
 }
 
@@ -3845,7 +3968,7 @@ int tr_scene_set_texture_device(tr_scene *s, uint32_t which, const void *rgb_dev
     if (st != TR_OK) return st;
     if (producer && producer->device != s->device)
         return tr::fail(TR_E_INVALID, "tr_scene_set_texture_device: the producer is on another device");
-    if (producer && producer->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (producer && producer->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
     const size_t bytes = (size_t)w * h * 3u;
     const void *source = nullptr;
@@ -3879,12 +4002,12 @@ int tr_scene_set_texture_from_frame(tr_scene *dst, uint32_t which, tr_scene *src
 {
     if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: null scene");
     if (src->device != dst->device) return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: the scenes are on different devices");
-    if (src->frame.band_y0 != 0 || src->frame.band_y1 != (int32_t)src->height)
+    if (!whole_frame(src))
         return tr::fail(TR_E_INVALID, "tr_scene_set_texture_from_frame: src is a band scene (tr_options.band_row0/1): it holds "
                                       "only its rows of the frame");
     int st = check_set_texture(dst, which, src->width, src->height, "tr_scene_set_texture_from_frame");
     if (st != TR_OK) return st;
-    if (src->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (src->broken) return unusable();
     HIP_TRY(hipSetDevice(dst->device));
     // src's frame on its way (what it holds back keeps dst's old texture when src is dst); a logically cleared frame is
     // an image of zeros whatever its memory holds
@@ -3980,17 +4103,13 @@ int tr_scene_ambient_occlusion(tr_scene *s, const tr_ao_params *p)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_ambient_occlusion: null scene");
     int st = check_ao_params(p, "tr_scene_ambient_occlusion");
     if (st != TR_OK) return st;
-    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+    if (!whole_frame(s))
         return tr::fail(TR_E_INVALID, "tr_scene_ambient_occlusion: a band scene (tr_options.band_row0/1) cannot be shaded: "
                                       "its border samples lie in another rank's rows");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
     if (s->z_fb_cleared) return TR_OK;  // a logically cleared frame has no drawn pixel
-    // the frame on its way, its depth in memory behind valid flags
-    st = submit_pending(s);
-    if (st == TR_OK) st = ensure_depth(s);
-    if (st == TR_OK) st = need_z(s, s->cur_slot);
-    if (st != TR_OK) return st;
+    if ((st = depth_in_memory(s)) != TR_OK) return st;
     AoArgs a = {};
     a.z = s->d_z;
     a.zclean = s->d_zclean;
@@ -4010,9 +4129,7 @@ int tr_scene_ambient_occlusion(tr_scene *s, const tr_ao_params *p)
     // (TR_AO_GREY lowers colour-clean flags of the DEVICE buffer; a record of a page-locked host buffer (HostFlags) says
     // what that host buffer holds, which this call does not change: the next read-back compares the two as always)
     s->quiescent = false;
-    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
-    // overflow would undo the shading
-    s->observed_seq = s->pass_seq;
+    handed_on(s);
     return TR_OK;
 }
 
@@ -4062,60 +4179,8 @@ int check_accumulate(uint32_t n, uint32_t kept, const uint32_t *weights, const c
     return TR_OK;
 }
 
-// The colour buffer of the frame tr_scene_select_frame(s, back) would make current.
-uint8_t *kept_frame_buffer(const tr_scene *s, uint32_t back)
-{
-    const size_t k = s->tail.params.size() - 1u - back;
-    return s->tail.fbs.empty() ? s->slots[(size_t)s->tail.slot[k]].fb : (uint8_t *)s->tail.fbs[k];
-}
-
-// `out` of tr_scene_accumulate / tr_scene_depth_of_field: memory from tr_host_alloc of at least `bytes` bytes (the
-// kernel stores through its mapped address, and the buffer's sparse read-back record lapses) or device memory, which
-// overlaps no frame buffer the scene keeps flags of, none of its slots and none of the last n_kept kept frames.  The
-// address the kernel stores to goes to *target.  who / getter / verb: the entry point's words in the error texts.
-int classify_out(tr_scene *s, void *out, size_t bytes, const char *who, const char *getter, const char *verb, uint32_t n_kept,
-                 void **target_out)
-{
-    const std::string w(who);
-    void *target = nullptr;
-    // memory from tr_host_alloc: the kernel stores through its mapped address; else it must be device memory
-    bool known_host = false;
-    {
-        std::lock_guard<std::mutex> lock(g_host_mutex);
-        auto it = g_host_allocs.find(out);
-        if (it != g_host_allocs.end()) {
-            known_host = true;
-            if (it->second.bytes >= bytes) {
-                target = it->second.device;
-                // (whatever a scene remembered of the buffer's zero tiles from a sparse read-back has lapsed)
-                it->second.writer = 0u;
-                it->second.gen += 1u;
-            }
-        }
-    }
-    if (known_host && !target) return tr::fail(TR_E_INVALID, w + ": the host buffer is smaller than the frame");
-    if (!target) {
-        const std::string text = w + ": `out` is neither device memory nor from tr_host_alloc (" + getter + " takes any host memory)";
-        hipPointerAttribute_t attr = {};
-        if (hipPointerGetAttributes(&attr, out) != hipSuccess) {
-            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
-            return tr::fail(TR_E_INVALID, text);
-        }
-        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
-        target = out;
-    }
-    // `out` must not be (part of) a frame the kernel may read, or another one the scene keeps flags of
-    auto overlaps = [&](const uint8_t *fb) {
-        return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
-    };
-    bool hit = false;
-    for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
-    for (const tr_scene::FbFlags &f : s->fb_flags) hit = hit || overlaps(f.fb);
-    for (uint32_t k = 0; k < n_kept; k++) hit = hit || overlaps(kept_frame_buffer(s, k));
-    if (hit) return tr::fail(TR_E_INVALID, w + ": `out` overlaps a frame buffer of the scene (out == NULL " + verb + " in place)");
-    *target_out = target;
-    return TR_OK;
-}
+// The frames the last tr_scene_render_frames call left to choose from.
+uint32_t frames_kept(const tr_scene *s) { return s->last_was_group ? (uint32_t)s->tail.params.size() : 0u; }
 
 // Enqueues the average of the last n kept frames into `out_device` (null: in place, into the current frame) behind
 // everything issued so far.  n, weights and D have passed check_accumulate.
@@ -4147,8 +4212,6 @@ int enqueue_accumulate(tr_scene *s, uint32_t n, const uint32_t *weights, uint32_
         int rc = launch_accumulate(a, s->stream);
         if (rc) return launch_status(rc, "k_accumulate");
     }
-    // (in place a colour-clean flag of the DEVICE buffer may come down; a record of a page-locked host buffer (HostFlags)
-    // says what that host buffer holds, which this call does not change: the next read-back compares the two as always)
     s->quiescent = false;
     return TR_OK;
 }
@@ -4159,22 +4222,15 @@ int tr_scene_accumulate(tr_scene *s, uint32_t n_frames, const uint32_t *weights,
 {
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_accumulate: null scene");
     uint32_t D = 0;
-    int st = check_accumulate(n_frames, s->last_was_group ? (uint32_t)s->tail.params.size() : 0u, weights, "tr_scene_accumulate", &D);
+    int st = check_accumulate(n_frames, frames_kept(s), weights, "tr_scene_accumulate", &D);
     if (st != TR_OK) return st;
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)s->width * s->height * 3;
     void *target = nullptr;
-    if (out) {
-        st = classify_out(s, out, bytes, "tr_scene_accumulate", "tr_scene_get_accumulated", "accumulates", n_frames, &target);
-        if (st != TR_OK) return st;
-    }
-    st = enqueue_accumulate(s, n_frames, weights, D, (uint8_t *)target);
-    if (st != TR_OK) return st;
-    // every pass issued so far is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering a frame
-    // again after a bin overflow would undo an average made in place, or change what one made elsewhere was made from
-    s->observed_seq = s->pass_seq;
-    return TR_OK;
+    st = frame_out(s, out, "tr_scene_accumulate", "tr_scene_get_accumulated", "accumulates", n_frames, &target);
+    if (st == TR_OK) st = enqueue_accumulate(s, n_frames, weights, D, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 int tr_scene_get_accumulated(tr_scene *s, uint32_t n_frames, const uint32_t *weights, uint8_t *rgb)
@@ -4182,23 +4238,9 @@ int tr_scene_get_accumulated(tr_scene *s, uint32_t n_frames, const uint32_t *wei
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_accumulated: null scene");
     if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_accumulated: null argument");
     uint32_t D = 0;
-    int st = check_accumulate(n_frames, s->last_was_group ? (uint32_t)s->tail.params.size() : 0u, weights, "tr_scene_get_accumulated", &D);
+    int st = check_accumulate(n_frames, frames_kept(s), weights, "tr_scene_get_accumulated", &D);
     if (st != TR_OK) return st;
-    int fst = sync_and_status(s);
-    if (fatal(fst)) return fst;
-    const size_t bytes = (size_t)s->width * s->height * 3;
-    if (s->resolved_bytes < bytes) {
-        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
-        s->resolved_bytes = 0;
-        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
-        s->resolved_bytes = bytes;
-    }
-    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
-    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
-    if (!whole_frame) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
-    st = enqueue_accumulate(s, n_frames, weights, D, s->d_resolved);
-    if (st != TR_OK) return st;
-    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+    return get_stage(s, rgb, frame_bytes(s), nullptr, [&](uint8_t *o) { return enqueue_accumulate(s, n_frames, weights, D, o); });
 }
 
 // The rule of tr_accumulate.h over caller's arrays, on the host.  Needs no GPU.
@@ -4248,10 +4290,10 @@ DofRule dof_rule(const tr_dof_params *p)
 
 int check_dof_scene(const tr_scene *s, const char *who)
 {
-    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+    if (!whole_frame(s))
         return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be blurred: "
                                                          "its border taps lie in another rank's rows");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     return TR_OK;
 }
 
@@ -4259,10 +4301,7 @@ int check_dof_scene(const tr_scene *s, const char *who)
 // issued so far; out_clean: null, or where k_dof writes the flags of `out_device`.  The scene is not logically cleared.
 int enqueue_dof(tr_scene *s, const tr_dof_params *p, uint8_t *out_device, uint32_t *out_clean)
 {
-    // the frame on its way, its depth in memory behind valid flags
-    int st = submit_pending(s);
-    if (st == TR_OK) st = ensure_depth(s);
-    if (st == TR_OK) st = need_z(s, s->cur_slot);
+    int st = depth_in_memory(s);
     if (st != TR_OK) return st;
     DofArgs a = {};
     a.z = s->d_z;
@@ -4292,40 +4331,15 @@ int tr_scene_depth_of_field(tr_scene *s, const tr_dof_params *p, void *out)
     if (st == TR_OK) st = check_dof_scene(s, "tr_scene_depth_of_field");
     if (st != TR_OK) return st;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)s->width * s->height * 3;
     void *target = nullptr;
-    if (out) {
-        st = classify_out(s, out, bytes, "tr_scene_depth_of_field", "tr_scene_get_depth_of_field", "blurs", 0u, &target);
-        if (st != TR_OK) return st;
-    }
-    if (s->z_fb_cleared) {
-        // a logically cleared frame is black and nothing in it is drawn: zeros out of place, itself in place
-        if (!target) return TR_OK;
-        st = submit_pending(s);
-        if (st != TR_OK) return st;
-        HIP_TRY(hipMemsetAsync(target, 0, bytes, s->stream));
-        s->quiescent = false;
-        s->observed_seq = s->pass_seq;
-        return TR_OK;
-    }
-    if (!target) {
-        if (!s->d_dof_fb && (st = dev_alloc(&s->d_dof_fb, bytes))) return st;
-        if (!s->d_dof_clean && (st = dev_alloc(&s->d_dof_clean, (size_t)s->n_tiles))) return st;
-    }
-    st = enqueue_dof(s, p, target ? (uint8_t *)target : s->d_dof_fb, target ? nullptr : s->d_dof_clean);
+    st = frame_out(s, out, "tr_scene_depth_of_field", "tr_scene_get_depth_of_field", "blurs", 0u, &target);
     if (st != TR_OK) return st;
-    if (!target) {
-        // in stream order: the blurred colour over the current frame, its flags over the frame's colour-clean flags
-        // (a record of a page-locked host buffer (HostFlags) says what that host buffer holds, which this call does not
-        // change: the next read-back compares the two as always)
-        HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, bytes, hipMemcpyDeviceToDevice, s->stream));
-        if (s->d_fbclean)
-            HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
-    }
-    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
-    // overflow would undo a blur made in place, or change what one made elsewhere was made from
-    s->observed_seq = s->pass_seq;
-    return TR_OK;
+    // a logically cleared frame is black and nothing in it is drawn: zeros out of place, itself in place
+    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_dof(s, p, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rgb)
@@ -4335,22 +4349,7 @@ int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rg
     int st = check_dof_params(p, "tr_scene_get_depth_of_field");
     if (st == TR_OK) st = check_dof_scene(s, "tr_scene_get_depth_of_field");
     if (st != TR_OK) return st;
-    int fst = sync_and_status(s);
-    if (fatal(fst)) return fst;
-    const size_t bytes = (size_t)s->width * s->height * 3;
-    if (s->resolved_bytes < bytes) {
-        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
-        s->resolved_bytes = 0;
-        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
-        s->resolved_bytes = bytes;
-    }
-    if (s->z_fb_cleared) {
-        HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
-    } else {
-        st = enqueue_dof(s, p, s->d_resolved, nullptr);
-        if (st != TR_OK) return st;
-    }
-    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_dof(s, p, o, nullptr); });
 }
 
 // The rule of tr_dof.h over caller's arrays, on the host.  Needs no GPU.
@@ -4405,10 +4404,10 @@ BloomRule bloom_rule(const tr_bloom_params *p)
 
 int check_bloom_scene(const tr_scene *s, const char *who)
 {
-    if (s->frame.band_y0 != 0 || s->frame.band_y1 != (int32_t)s->height)
+    if (!whole_frame(s))
         return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be bloomed: "
                                                          "its border taps lie in another rank's rows");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     return TR_OK;
 }
 
@@ -4444,39 +4443,15 @@ int tr_scene_bloom(tr_scene *s, const tr_bloom_params *p, void *out)
     if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_bloom");
     if (st != TR_OK) return st;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)s->width * s->height * 3;
     void *target = nullptr;
-    if (out) {
-        st = classify_out(s, out, bytes, "tr_scene_bloom", "tr_scene_get_bloom", "blooms", 0u, &target);
-        if (st != TR_OK) return st;
-    }
-    if (s->z_fb_cleared) {
-        // a logically cleared frame is black, and so is its glow: zeros out of place, itself in place
-        if (!target) return TR_OK;
-        st = submit_pending(s);
-        if (st != TR_OK) return st;
-        HIP_TRY(hipMemsetAsync(target, 0, bytes, s->stream));
-        s->quiescent = false;
-        s->observed_seq = s->pass_seq;
-        return TR_OK;
-    }
-    if (!target) {
-        // (the scratch frame and flag set of depth of field: each call leaves them free behind its two copies)
-        if (!s->d_dof_fb && (st = dev_alloc(&s->d_dof_fb, bytes))) return st;
-        if (!s->d_dof_clean && (st = dev_alloc(&s->d_dof_clean, (size_t)s->n_tiles))) return st;
-    }
-    st = enqueue_bloom(s, p, target ? (uint8_t *)target : s->d_dof_fb, target ? nullptr : s->d_dof_clean);
+    st = frame_out(s, out, "tr_scene_bloom", "tr_scene_get_bloom", "blooms", 0u, &target);
     if (st != TR_OK) return st;
-    if (!target) {
-        // in stream order: the bloomed colour over the current frame, its flags over the frame's colour-clean flags
-        HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, bytes, hipMemcpyDeviceToDevice, s->stream));
-        if (s->d_fbclean)
-            HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
-    }
-    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
-    // overflow would undo a bloom made in place, or change what one made elsewhere was made from
-    s->observed_seq = s->pass_seq;
-    return TR_OK;
+    // a logically cleared frame is black, and so is its glow: zeros out of place, itself in place
+    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_bloom(s, p, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb)
@@ -4486,22 +4461,7 @@ int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb)
     int st = check_bloom_params(p, "tr_scene_get_bloom");
     if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_get_bloom");
     if (st != TR_OK) return st;
-    int fst = sync_and_status(s);
-    if (fatal(fst)) return fst;
-    const size_t bytes = (size_t)s->width * s->height * 3;
-    if (s->resolved_bytes < bytes) {
-        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
-        s->resolved_bytes = 0;
-        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
-        s->resolved_bytes = bytes;
-    }
-    if (s->z_fb_cleared) {
-        HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
-    } else {
-        st = enqueue_bloom(s, p, s->d_resolved, nullptr);
-        if (st != TR_OK) return st;
-    }
-    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_bloom(s, p, o, nullptr); });
 }
 
 // The rule of tr_bloom.h over a caller's array, on the host.  Needs no GPU.
@@ -4529,16 +4489,12 @@ int check_grade_n(uint32_t n, const char *who)
 int check_grade_scene(const tr_scene *s, const char *who)
 {
     if (s->lut_n == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no lookup table (tr_scene_set_lut)");
-    if (s->broken) return tr::fail(TR_E_HIP, "the scene is unusable: a tile kernel could not be launched behind its chain");
+    if (s->broken) return unusable();
     return TR_OK;
 }
 
-// The scene's rows of a frame-sized buffer: their first byte and their number of bytes.
-void band_bytes(const tr_scene *s, size_t *first, size_t *count)
-{
-    *first = (size_t)s->width * (size_t)(s->height - (uint32_t)s->frame.band_y1) * 3;
-    *count = (size_t)s->width * (size_t)(s->frame.band_y1 - s->frame.band_y0) * 3;
-}
+// Does the stage short-circuit?  A logically cleared frame is black, and black maps to c0: to black where c0 is black.
+bool cleared_to_black(const tr_scene *s) { return s->z_fb_cleared && s->lut_c0 == 0u; }
 
 // Enqueues the grade of the current frame into `out_device` (null: in place) behind everything issued so far.  A
 // logically cleared scene whose c0 is zero is the caller's business; with another c0 the clear is made real here and the
@@ -4561,8 +4517,6 @@ int enqueue_grade(tr_scene *s, uint8_t *out_device)
         int rc = launch_grade(a, s->stream);
         if (rc) return launch_status(rc, "k_grade");
     }
-    // (in place a colour-clean flag of the DEVICE buffer may come down; a record of a page-locked host buffer says what
-    // that host buffer holds, which this call does not change: see enqueue_accumulate)
     s->quiescent = false;
     return TR_OK;
 }
@@ -4612,30 +4566,14 @@ int tr_scene_grade(tr_scene *s, void *out)
     int st = check_grade_scene(s, "tr_scene_grade");
     if (st != TR_OK) return st;
     HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)s->width * s->height * 3;
     void *target = nullptr;
-    if (out) {
-        st = classify_out(s, out, bytes, "tr_scene_grade", "tr_scene_get_graded", "grades", 0u, &target);
-        if (st != TR_OK) return st;
-    }
-    if (s->z_fb_cleared && s->lut_c0 == 0u) {
-        // a logically cleared frame is black and black maps to c0 = black: zeros out of place, itself in place
-        if (!target) return TR_OK;
-        st = submit_pending(s);
-        if (st != TR_OK) return st;
-        size_t first = 0, count = 0;
-        band_bytes(s, &first, &count);
-        HIP_TRY(hipMemsetAsync((uint8_t *)target + first, 0, count, s->stream));
-        s->quiescent = false;
-        s->observed_seq = s->pass_seq;
-        return TR_OK;
-    }
-    st = enqueue_grade(s, (uint8_t *)target);
+    st = frame_out(s, out, "tr_scene_grade", "tr_scene_get_graded", "grades", 0u, &target);
     if (st != TR_OK) return st;
-    // the frame is now in a consumer's hands (as in tr_scene_get_frame_buffer_async): rendering it again after a bin
-    // overflow would undo a grade made in place, or change what one made elsewhere was made from
-    s->observed_seq = s->pass_seq;
-    return TR_OK;
+    // zeros in the band's rows out of place, itself in place
+    if (cleared_to_black(s)) return target ? cleared_out_of_place(s, target) : TR_OK;
+    st = enqueue_grade(s, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 int tr_scene_get_graded(tr_scene *s, uint8_t *rgb)
@@ -4644,23 +4582,7 @@ int tr_scene_get_graded(tr_scene *s, uint8_t *rgb)
     if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_graded: null argument");
     int st = check_grade_scene(s, "tr_scene_get_graded");
     if (st != TR_OK) return st;
-    int fst = sync_and_status(s);
-    if (fatal(fst)) return fst;
-    const size_t bytes = (size_t)s->width * s->height * 3;
-    if (s->resolved_bytes < bytes) {
-        dev_free(s->d_resolved);  // (the stream is idle: sync_and_status waited)
-        s->resolved_bytes = 0;
-        if ((st = dev_alloc(&s->d_resolved, bytes))) return st;
-        s->resolved_bytes = bytes;
-    }
-    // a band scene's kernel writes its own rows only: the rest of the library's buffer reads as zeros
-    const bool whole_frame = s->frame.band_y0 == 0 && s->frame.band_y1 == (int32_t)s->height;
-    if (!whole_frame || (s->z_fb_cleared && s->lut_c0 == 0u)) HIP_TRY(hipMemsetAsync(s->d_resolved, 0, bytes, s->stream));
-    if (!(s->z_fb_cleared && s->lut_c0 == 0u)) {
-        st = enqueue_grade(s, s->d_resolved);
-        if (st != TR_OK) return st;
-    }
-    return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+    return get_stage(s, rgb, frame_bytes(s), cleared_to_black, [&](uint8_t *o) { return enqueue_grade(s, o); });
 }
 
 // The rule of tr_grade.h over a caller's pixels, on the host.  Needs no GPU.
@@ -4697,8 +4619,7 @@ int tr_scene_band_tiles(tr_scene *s, const void *frame_buffer_device, tr_band_ti
     out->first_tile_row = s->frame.ty_base;
     out->band_y0 = s->frame.band_y0;
     out->band_y1 = s->frame.band_y1;
-    // the flags now count as read by a consumer: a pass that overflowed its pool can no longer be repaired unseen
-    s->observed_seq = s->pass_seq;
+    handed_on(s);  // (the flags count as read by a consumer)
     s->quiescent = false;
     return TR_OK;
 }

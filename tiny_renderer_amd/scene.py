@@ -733,26 +733,45 @@ class Scene:
         """Makes the frame `back` frames before the last one of the last render_frames call current."""
         check(load_library().tr_scene_select_frame(self._h, int(back)))
 
-    def _image(self, fn, strict):
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        code = getattr(load_library(), fn)(self._h, out.ctypes.data)
+    def _image(self, fn, strict, *args, out=None):
+        """What getter `fn`(scene, *args, rgb) delivers, in `out` (default: a new [H, W, 3] uint8 array); its status goes to
+        last_status, and through check() when strict."""
+        if out is None:
+            out = np.empty((self.height, self.width, 3), np.uint8)
+        code = getattr(load_library(), fn)(self._h, *args, out.ctypes.data)
         if strict:
             check(code)
         self.last_status = code
         return out
+
+    def _pinned_array(self, shape):
+        """A page-locked uint8 array of `shape` from tr_host_alloc (freed with the scene)."""
+        n = int(np.prod(shape))
+        p = load_library().tr_host_alloc(n)
+        if not p:
+            raise MemoryError("tr_host_alloc(%d)" % n)
+        self._pinned.append(p)
+        return np.ctypeslib.as_array((C.c_uint8 * n).from_address(p)).reshape(shape)
+
+    def _out_pointer(self, out, name="out", shape="[H, W, 3]", source="pinned_frame", nbytes=None):
+        """`out` of a stage as the library takes it: None stays None (in place), an array of `nbytes` (default: a frame's)
+        contiguous bytes gives its address, any other array a ValueError in the caller's words; anything else is a device
+        pointer (int)."""
+        if out is None:
+            return None
+        if isinstance(out, np.ndarray):
+            if out.nbytes != (self.width * self.height * 3 if nbytes is None else nbytes) or not out.flags["C_CONTIGUOUS"]:
+                text = "%s must be a contiguous %s uint8 array (%s)" % (name, shape, source)
+                raise ValueError(text)
+            return out.ctypes.data
+        return int(out)
 
     def get_frame_buffer(self, strict=True):
         return self._image("tr_scene_get_frame_buffer", strict)
 
     def pinned_frame(self):
         """A page-locked [H, W, 3] uint8 array for get_frame_buffer_async (freed with the scene)."""
-        L = load_library()
-        n = self.width * self.height * 3
-        p = L.tr_host_alloc(n)
-        if not p:
-            raise MemoryError("tr_host_alloc(%d)" % n)
-        self._pinned.append(p)
-        return np.ctypeslib.as_array((C.c_uint8 * n).from_address(p)).reshape(self.height, self.width, 3)
+        return self._pinned_array((self.height, self.width, 3))
 
     def get_frame_buffer_async(self, out):
         """Enqueue the read-back of the frame into `out` (see pinned_frame); valid after sync()."""
@@ -780,33 +799,18 @@ class Scene:
             out = np.empty(shape, np.uint8)
         elif out.dtype != np.uint8 or out.nbytes != shape[0] * shape[1] * 3 or not out.flags["C_CONTIGUOUS"]:
             raise ValueError("out must be a contiguous [H / f, W / f, 3] uint8 array")
-        code = load_library().tr_scene_get_resolved(self._h, int(factor), out.ctypes.data)
-        if strict:
-            check(code)
-        self.last_status = code
-        return out
+        return self._image("tr_scene_get_resolved", strict, int(factor), out=out)
 
     def pinned_resolved(self, factor):
         """A page-locked [H / f, W / f, 3] uint8 array for resolve_into (freed with the scene)."""
-        shape = self._resolved_shape(factor)
-        n = shape[0] * shape[1] * 3
-        p = load_library().tr_host_alloc(n)
-        if not p:
-            raise MemoryError("tr_host_alloc(%d)" % n)
-        self._pinned.append(p)
-        return np.ctypeslib.as_array((C.c_uint8 * n).from_address(p)).reshape(shape)
+        return self._pinned_array(self._resolved_shape(factor))
 
     def resolve_into(self, factor, target):
         """Enqueue the resolve of the current frame behind the renders issued so far (tr_scene_resolve); the result is
         there after sync().  `target`: a device pointer (int) to 3 * (W / f) * (H / f) bytes, or an array from
         pinned_resolved.  A band scene writes output rows [band_row0 / f, band_row1 / f) only."""
         shape = self._resolved_shape(factor)
-        if isinstance(target, np.ndarray):
-            if target.nbytes != shape[0] * shape[1] * 3 or not target.flags["C_CONTIGUOUS"]:
-                raise ValueError("target must be a contiguous [H / f, W / f, 3] uint8 array (pinned_resolved)")
-            ptr = target.ctypes.data
-        else:
-            ptr = int(target) if target is not None else None
+        ptr = self._out_pointer(target, "target", "[H / f, W / f, 3]", "pinned_resolved", shape[0] * shape[1] * 3)
         check(load_library().tr_scene_resolve(self._h, int(factor), ptr))
         return target
 
@@ -871,12 +875,7 @@ class Scene:
         averaged on the device under integer weights (0..255, None: all 1): an [H, W, 3] uint8 array,
         (sum of w_k * F_k + D // 2) // D on the stored bytes with D = sum of w_k.  Synchronizes; no frame is changed."""
         n, w = accumulate_weights(n_frames, weights)
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        code = load_library().tr_scene_get_accumulated(self._h, n, w.ctypes.data if w is not None else None, out.ctypes.data)
-        if strict:
-            check(code)
-        self.last_status = code
-        return out
+        return self._image("tr_scene_get_accumulated", strict, n, w.ctypes.data if w is not None else None)
 
     def accumulate_into(self, n_frames, target, weights=None):
         """Enqueue the average behind the renders issued so far (tr_scene_accumulate); the result is there after sync().
@@ -885,12 +884,7 @@ class Scene:
         n, w = accumulate_weights(n_frames, weights)
         if target is None:
             raise ValueError("accumulate_into: no target (accumulate_in_place averages into the current frame)")
-        if isinstance(target, np.ndarray):
-            if target.nbytes != self.width * self.height * 3 or not target.flags["C_CONTIGUOUS"]:
-                raise ValueError("target must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
-            ptr = target.ctypes.data
-        else:
-            ptr = int(target)
+        ptr = self._out_pointer(target, "target")
         check(load_library().tr_scene_accumulate(self._h, n, w.ctypes.data if w is not None else None, ptr))
         return target
 
@@ -911,14 +905,7 @@ class Scene:
         scenes are refused.  store_depth=True avoids the depth-only repeat of the frame's pass."""
         if not isinstance(params, DofParams):
             raise ValueError("depth_of_field: params must come from dof_params")
-        if out is None:
-            ptr = None
-        elif isinstance(out, np.ndarray):
-            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
-            ptr = out.ctypes.data
-        else:
-            ptr = int(out)
+        ptr = self._out_pointer(out)
         check(load_library().tr_scene_depth_of_field(self._h, C.addressof(params), ptr))
         return out
 
@@ -927,12 +914,7 @@ class Scene:
         Synchronizes; the scene's frame stays unblurred."""
         if not isinstance(params, DofParams):
             raise ValueError("get_depth_of_field: params must come from dof_params")
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        code = load_library().tr_scene_get_depth_of_field(self._h, C.addressof(params), out.ctypes.data)
-        if strict:
-            check(code)
-        self.last_status = code
-        return out
+        return self._image("tr_scene_get_depth_of_field", strict, C.addressof(params))
 
     # --- bloom (tr_scene_bloom / tr_scene_get_bloom) -------------------------------------------------
     def bloom(self, params, out=None):
@@ -944,14 +926,7 @@ class Scene:
         result is there after sync().  Band scenes are refused.  No depth is needed."""
         if not isinstance(params, BloomParams):
             raise ValueError("bloom: params must come from bloom_params")
-        if out is None:
-            ptr = None
-        elif isinstance(out, np.ndarray):
-            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
-            ptr = out.ctypes.data
-        else:
-            ptr = int(out)
+        ptr = self._out_pointer(out)
         check(load_library().tr_scene_bloom(self._h, C.addressof(params), ptr))
         return out
 
@@ -960,12 +935,7 @@ class Scene:
         scene's frame stays unbloomed."""
         if not isinstance(params, BloomParams):
             raise ValueError("get_bloom: params must come from bloom_params")
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        code = load_library().tr_scene_get_bloom(self._h, C.addressof(params), out.ctypes.data)
-        if strict:
-            check(code)
-        self.last_status = code
-        return out
+        return self._image("tr_scene_get_bloom", strict, C.addressof(params))
 
     # --- colour grading (tr_scene_set_lut / tr_scene_grade / tr_scene_get_graded) ---------------------
     def set_lut(self, lut):
@@ -983,26 +953,14 @@ class Scene:
         Otherwise `out` is a device pointer (int) to 3 * W * H bytes apart from every frame buffer of the scene, or an
         array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().
         Band scenes write their band's rows only.  No depth is needed."""
-        if out is None:
-            ptr = None
-        elif isinstance(out, np.ndarray):
-            if out.nbytes != self.width * self.height * 3 or not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("out must be a contiguous [H, W, 3] uint8 array (pinned_frame)")
-            ptr = out.ctypes.data
-        else:
-            ptr = int(out)
+        ptr = self._out_pointer(out)
         check(load_library().tr_scene_grade(self._h, ptr))
         return out
 
     def get_graded(self, strict=True):
         """tr_scene_get_graded: the current frame graded on the device, as an [H, W, 3] uint8 array.  Synchronizes; the
         scene's frame stays ungraded."""
-        out = np.empty((self.height, self.width, 3), np.uint8)
-        code = load_library().tr_scene_get_graded(self._h, out.ctypes.data)
-        if strict:
-            check(code)
-        self.last_status = code
-        return out
+        return self._image("tr_scene_get_graded", strict)
 
     # --- dynamic textures (tr_scene_set_texture*) ---------------------------------------------------
     def _texture_shape(self, which):
