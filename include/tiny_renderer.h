@@ -772,6 +772,13 @@ int tr_scene_get_graded(tr_scene *s, uint8_t *rgb);
  * pixels in any order.  out may be rgb: the rule works in place.  The same checks of n; n_pixels 0: TR_OK, nothing to
  * do. */
 int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out /* may be rgb */, uint32_t n, const uint8_t *lut);
+/* Diagnostic: k_grade's workgroups are persistent -- the launcher starts as many as the device holds at once, never
+ * more than there are tiles, and each walks the tiles with the stride of the grid.  `cap` is stored on the scene: every
+ * later k_grade launch of that scene starts min(cap, that number) workgroups, so that a small frame takes several rounds
+ * of the walk; nothing else of the launch changes, and neither does a byte of the result.  cap == 0: no cap, the
+ * default.  Returns the number of workgroups of the scene's most recent k_grade launch (0: there has been none; a call
+ * that short-circuits on a logically cleared scene launches nothing), or TR_E_INVALID for a NULL scene. */
+int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap);
 
 /* Dynamic textures (nothing of the kind upstream, whose four images are moved into Scene::new and never change): one of a
  * scene's images -- `which` = 0..3 in tr_scene_create's order: texture, normal_map, normal_map_tangent, specular_map --

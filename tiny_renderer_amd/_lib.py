@@ -151,6 +151,7 @@ SYMBOLS = {
     "tr_scene_grade": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_scene_get_graded": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_grade_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_debug_grade_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tr_scene_set_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ImageRgb8)]),
     "tr_scene_set_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "tr_scene_set_texture_from_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -96,7 +96,8 @@ int launch_bloom(const BloomArgs &a, hipStream_t st);
 // aligned) into a.out -- a.fb itself or a buffer apart from it -- by the rule of tr_grade.h, through the frame's colour
 // fast-clear flags: k_grade, persistent workgroups.  The scene's tile grid, a band's included; no depth is read.
 // a.lower_clean: null, or a.fbclean (in place, c0 != 0): the flags of the tiles stored as c0 come down.
-int launch_grade(const GradeArgs &a, hipStream_t st);
+// cap: 0, or the most workgroups to start (tr_scene_debug_grade_grid); *grid: the number started (0: nothing launched).
+int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
 // Dynamic textures: image a.src into the plain array a.texel and the owned words of the texel set a.set (words per texel:
 // 1 or 4; a.set null: the plain array alone) by the rule of tr_pack.h, through the source's colour-clean flags when it
 // is a frame: k_pack_texels.  The caller orders the launch behind whatever reads the arrays and produced the source.

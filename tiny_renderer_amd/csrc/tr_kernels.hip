@@ -3539,8 +3539,9 @@ int launch_bloom(const BloomArgs &a, hipStream_t st)
     return 0;
 }
 
-int launch_grade(const GradeArgs &a, hipStream_t st)
+int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid_out)
 {
+    *grid_out = 0u;
     const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
     if (n_tiles == 0) return 0;
     if (!a.fb || !a.out || !a.lut || a.rule.n < 2u || a.rule.n > GRADE_MAX_N || (uintptr_t)a.lut % 16u != 0u) return (int)hipErrorInvalidValue;
@@ -3560,7 +3561,9 @@ int launch_grade(const GradeArgs &a, hipStream_t st)
         lds_per_cu = 65536;
     uint32_t per_cu = (uint32_t)GRADE_MAX_PER_CU;
     if (lds) per_cu = std::min<uint32_t>(per_cu, (uint32_t)((size_t)lds_per_cu / lds_bytes));
-    const uint32_t grid = std::min<uint32_t>((uint32_t)cus * per_cu, n_tiles);
+    uint32_t grid = std::min<uint32_t>((uint32_t)cus * per_cu, n_tiles);
+    if (cap != 0u) grid = std::min<uint32_t>(grid, cap);  // (the diagnostic: fewer workgroups, more rounds each)
+    *grid_out = grid;
     if (lds && words)
         hipLaunchKernelGGL((k_grade<true, true>), dim3(grid), dim3(GRADE_THREADS), lds_bytes, st, a);
     else if (lds)

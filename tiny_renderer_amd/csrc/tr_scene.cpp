@@ -406,6 +406,8 @@ struct tr_scene {
     // pieces; lut_c0: its entry 0, what a cleared tile becomes.  lut_n == 0: no table
     uint32_t *d_lut = nullptr;
     uint32_t lut_n = 0, lut_c0 = 0;
+    // tr_scene_debug_grade_grid: the most workgroups a k_grade launch may start (0: no cap) and what the last one started
+    uint32_t grade_cap = 0, grade_grid = 0;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
     // memory not written".  Raised by the tile kernel for the empty tiles of a cleared frame (and by
@@ -4514,7 +4516,7 @@ int enqueue_grade(tr_scene *s, uint8_t *out_device)
     a.rule.c0 = s->lut_c0;
     {
         Timed t(s, K_GRADE);
-        int rc = launch_grade(a, s->stream);
+        int rc = launch_grade(a, s->stream, s->grade_cap, &s->grade_grid);
         if (rc) return launch_status(rc, "k_grade");
     }
     s->quiescent = false;
@@ -4595,6 +4597,13 @@ int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out, uint32_t n,
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_grade_host: null argument");
     grade_host(n_pixels, rgb, out, n, lut);
     return TR_OK;
+}
+
+int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_grade_grid: null scene");
+    s->grade_cap = cap;
+    return (int)s->grade_grid;
 }
 
 int tr_scene_band_tiles(tr_scene *s, const void *frame_buffer_device, tr_band_tiles *out)

@@ -962,6 +962,14 @@ class Scene:
         scene's frame stays ungraded."""
         return self._image("tr_scene_get_graded", strict)
 
+    def debug_grade_grid(self, cap=0):
+        """tr_scene_debug_grade_grid: every later k_grade launch of the scene starts at most `cap` workgroups (0: no cap, the
+        default), so that each walks more tiles; the result does not change.  Returns the number of workgroups of the
+        scene's most recent k_grade launch, 0 if there has been none."""
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
+            raise ValueError("debug_grade_grid: cap must be an integer 0..2^32 - 1")
+        return check(load_library().tr_scene_debug_grade_grid(self._h, int(cap)))
+
     # --- dynamic textures (tr_scene_set_texture*) ---------------------------------------------------
     def _texture_shape(self, which):
         if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or not 0 <= which <= 3:
