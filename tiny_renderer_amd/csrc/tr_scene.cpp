@@ -157,11 +157,8 @@ struct tr_scene {
     hipStream_t stream = nullptr;
     bool own_stream = false;
 
-    // Scene::new defaults, scene.rs:66-69
-    float light[3] = { 0.0f, 0.0f, -1.0f };
-    float from[3] = { 0.0f, 0.0f, 1.0f };
-    float at[3] = { 0.0f, 0.0f, 0.0f };
-    float up[3] = { 0.0f, 1.0f, 0.0f };
+    // The view the next render draws under: light direction and camera (Scene::new defaults, scene.rs:66-69)
+    tr_frame_params view = { { 0.0f, 0.0f, -1.0f }, { 0.0f, 0.0f, 1.0f }, { 0.0f, 0.0f, 0.0f }, { 0.0f, 1.0f, 0.0f } };
 
     DevMesh mesh = {};         // what a pass rendered now draws: the mesh under the current instance table
     DevTextures tex = {};
@@ -452,7 +449,7 @@ struct tr_scene {
     // What the last render() started from, so that a frame whose bins overflowed can be
     // rendered again after the bins have grown.
     struct {
-        float light[3], from[3], at[3], up[3];
+        tr_frame_params view;
         bool z_fb_cleared, shadow_cleared;
         bool valid;
         InstRef inst;
@@ -624,6 +621,23 @@ void use_inst(tr_scene *s, const tr_scene::InstRef &r)
     s->inst = r;
     s->mesh = mesh_of(s, r);
 }
+
+// What the scene draws now -- the view and the table / pose -- held while the library renders a frame of its own accord
+// under that frame's state (a replay, a depth-only repeat, a frame held back, a group), and put back when the scope
+// ends, whichever way it ends.  Allocates nothing: tr_scene_render -> flush_deferred runs every step of a loop.
+struct DrawState {
+    tr_scene *const s;
+    const tr_frame_params view;
+    const tr_scene::InstRef inst;
+    explicit DrawState(tr_scene *scene) : s(scene), view(scene->view), inst(scene->inst) {}
+    ~DrawState()
+    {
+        s->view = view;
+        use_inst(s, inst);
+    }
+    DrawState(const DrawState &) = delete;
+    DrawState &operator=(const DrawState &) = delete;
+};
 
 // A chain that reads table `m` (a DevMesh of mesh_of) has been queued on `st`: the block may not be written or freed
 // until what is queued there now has run.  (No table: nothing to do -- the scene without instances queues nothing more.)
@@ -1215,21 +1229,16 @@ int recover_from_overflow(tr_scene *s, unsigned long long first_bad_seq)
     case plan::OverflowAction::REPLAY_LAST:
         break;
     }
-    float keep[12];
-    memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
-    memcpy(s->light, s->last.light, 12); memcpy(s->from, s->last.from, 12);
-    memcpy(s->at, s->last.at, 12); memcpy(s->up, s->last.up, 12);
-    const tr_scene::InstRef inst_now = s->inst;
+    const DrawState now(s);
+    s->view = s->last.view;
     use_inst(s, s->last.inst);
     const bool z_now = s->z_fb_cleared, sh_now = s->shadow_cleared;
     s->z_fb_cleared = true;
     s->shadow_cleared = s->last.shadow_cleared;
     st = render_frame(s);
-    use_inst(s, inst_now);
     // a clear() issued after the overflowing render stays pending
     s->z_fb_cleared = s->z_fb_cleared || z_now;
     s->shadow_cleared = s->shadow_cleared || sh_now;
-    memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
     return st;
 }
 
@@ -1312,7 +1321,8 @@ void fill_dev_uniforms(const tr_scene *s, DevUniforms &d)
 // The frame constants of one pass (shader.rs:183-279 prepares) for the light and camera the scene holds.
 int pass_uniforms(tr_scene *s, const PassDesc &p, DevUniforms &du)
 {
-    int st = prepare_uniforms(p.prepare_kind, &s->uniforms, s->width, s->height, s->light, s->from, s->at, s->up);
+    const tr_frame_params &v = s->view;
+    int st = prepare_uniforms(p.prepare_kind, &s->uniforms, s->width, s->height, v.light, v.look_from, v.look_at, v.up);
     if (st != TR_OK) return tr::fail(st, "prepare: singular matrix (try_inverse().unwrap() would panic)");
     fill_dev_uniforms(s, du);
     if (p.fs == FS_SHADOW2 || p.fs == FS_OCCLUSION2) shadow_times_inverse(&s->uniforms, du.sm_ivpmv);
@@ -1477,8 +1487,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
             // a group's frames it leaves its depth on the chip; whoever wants the z buffer gets it from ensure_depth
             ta.store = TR_STORE_COLOR;
             slot.z_deferred = true;
-            memcpy(slot.z_params.light, s->light, 12); memcpy(slot.z_params.look_from, s->from, 12);
-            memcpy(slot.z_params.look_at, s->at, 12); memcpy(slot.z_params.up, s->up, 12);
+            slot.z_params = s->view;
             slot.z_inst = s->inst;
         } else {
             // (an accumulating render has had the slot's depth made real before it came here: ensure_depth, tr_scene_render)
@@ -1616,19 +1625,14 @@ int ensure_depth(tr_scene *s)
     int st = submit_pending(s);   // (the frame itself, should it still be held back)
     if (st != TR_OK) return st;
     if (!slot.z_deferred) return TR_OK;
-    float keep[12];
-    memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
-    const tr_frame_params &q = slot.z_params;
-    memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
-    const tr_scene::InstRef inst_now = s->inst;
+    const DrawState now(s);
+    s->view = slot.z_params;
     use_inst(s, slot.z_inst);
     const PipelineDesc &pd = kPipelines[s->pipeline];
     const int host_status = s->host_status;
     st = run_pass(s, pd.pass[pd.n_passes - 1], true);
     if (st == TR_OK) st = submit_pending_tiles(s);
     s->host_status = host_status;
-    use_inst(s, inst_now);
-    memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
     return st;
 }
 
@@ -1882,11 +1886,9 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
         const DevFrame &fr = pd.pass[pi].fs == FS_DEPTH ? s->frame_full : s->frame;
         tile_layout(s, (uint64_t)fr.ntx * fr.nty * g, fr.ntx * fr.nty, n_poly, gs.tile_waves[pi], gs.shared[pi]);
     }
-    float keep[12];
-    memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
+    const DrawState now(s);  // (every frame's view passes through s->view, which pass_uniforms reads; nothing below the loop does)
     for (uint32_t j = 0; j < g && st == TR_OK; j++) {
-        memcpy(s->light, p[j].light, 12); memcpy(s->from, p[j].look_from, 12);
-        memcpy(s->at, p[j].look_at, 12); memcpy(s->up, p[j].up, 12);
+        s->view = p[j];
         if (!defer_depth(s)) st = need_z(s, slot_of[j]);   // (the frames store their depth)
         if (st != TR_OK) break;
         tr_scene::FrameSlot &slot = s->slots[(size_t)slot_of[j]];
@@ -1956,7 +1958,6 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
             if (tile_fs(s, pass.fs) == (int)FS_LIT) lit_args(s, gs.lit + e * (size_t)s->lit_words, sa, ta);
         }
     }
-    memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
     if (st != TR_OK) return st;
 
     // tables to the device, then per pass: vertex stage + binning of all frames, their work lists
@@ -2147,13 +2148,10 @@ int flush_deferred(tr_scene *s, bool hold_back)
     int st = TR_OK;
     if (g == 1u) {
         // alone: the ordinary path, from the state the frame was recorded in
-        float keep[12];
-        memcpy(keep, s->light, 12); memcpy(keep + 3, s->from, 12); memcpy(keep + 6, s->at, 12); memcpy(keep + 9, s->up, 12);
+        const DrawState now(s);
         const bool z_now = s->z_fb_cleared, sh_now = s->shadow_cleared;
         uint8_t *fb_now = s->d_fb;
-        const tr_frame_params &q = fr[0].p;
-        memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
-        const tr_scene::InstRef inst_now = s->inst;
+        s->view = fr[0].p;
         use_inst(s, fr[0].inst);
         s->z_fb_cleared = s->shadow_cleared = true;
         if (fr[0].fb != fb_now) st = use_slot(s, s->cur_slot, fr[0].fb == s->slots[(size_t)s->cur_slot].fb ? nullptr : fr[0].fb);
@@ -2165,8 +2163,6 @@ int flush_deferred(tr_scene *s, bool hold_back)
         // a clear() issued after that render stays pending
         s->z_fb_cleared = s->z_fb_cleared || z_now;
         s->shadow_cleared = s->shadow_cleared || sh_now;
-        memcpy(s->light, keep, 12); memcpy(s->from, keep + 3, 12); memcpy(s->at, keep + 6, 12); memcpy(s->up, keep + 9, 12);
-        use_inst(s, inst_now);
         return st;
     }
     // per-frame tile kernels issued before these frames go first (same targets)
@@ -2247,8 +2243,7 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_sc
         // the winner tap is a single buffer: frame by frame through the ordinary path, slots all the same
         for (uint32_t i = 0; i < n; i++) {
             if ((st = use_slot(s, (int)(i % G), fbs ? (uint8_t *)fbs[i] : nullptr, fbs != nullptr)) != TR_OK) return st;
-            memcpy(s->light, p[i].light, 12); memcpy(s->from, p[i].look_from, 12);
-            memcpy(s->at, p[i].look_at, 12); memcpy(s->up, p[i].up, 12);
+            s->view = p[i];
             if (per_frame) use_inst(s, ref_of(i));
             s->z_fb_cleared = s->shadow_cleared = true;
             if ((st = render_frame(s)) != TR_OK) return st;
@@ -2280,8 +2275,7 @@ int render_frames(tr_scene *s, uint32_t n, const tr_frame_params *p, const tr_sc
         }
         if ((st = finish_groups(s)) != TR_OK) return st;
         // the scene now stands where the per-frame calls would have left it
-        const tr_frame_params &l = p[n - 1];
-        memcpy(s->light, l.light, 12); memcpy(s->from, l.look_from, 12); memcpy(s->at, l.look_at, 12); memcpy(s->up, l.up, 12);
+        s->view = p[n - 1];
         if (per_frame) use_inst(s, kept_refs.back());
         s->z_fb_cleared = s->shadow_cleared = false;
         if ((st = use_slot(s, (int)((n - 1) % S), fbs ? (uint8_t *)fbs[n - 1] : nullptr)) != TR_OK) return st;
@@ -2308,13 +2302,12 @@ int replay_tail(tr_scene *s)
     if (kept == 0) return TR_OK;
     const int cur = s->cur_slot;
     uint8_t *cur_fb = s->d_fb;
-    const tr_scene::InstRef inst_now = s->inst;
+    const DrawState now(s);
     int st = TR_OK;
     if (s->d_winner) {
         for (uint32_t k = 0; k < kept && st == TR_OK; k++) {
             st = use_slot(s, s->tail.slot[k], s->tail.fbs.empty() ? nullptr : (uint8_t *)s->tail.fbs[k]);
-            const tr_frame_params &q = s->tail.params[k];
-            memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+            s->view = s->tail.params[k];
             use_inst(s, s->tail.inst[k]);
             s->z_fb_cleared = s->shadow_cleared = true;
             if (st == TR_OK) st = render_frame(s);
@@ -2324,7 +2317,6 @@ int replay_tail(tr_scene *s)
                        s->tail.slot.data(), kept);
         if (st == TR_OK) st = finish_groups(s);
     }
-    use_inst(s, inst_now);
     if (st != TR_OK) return st;
     return use_slot(s, cur, cur_fb == s->slots[(size_t)cur].fb ? nullptr : cur_fb);  // the selection the caller had
 }
@@ -2359,6 +2351,43 @@ uint32_t pool_cap_for(uint32_t width, uint32_t height, uint64_t n_poly, uint64_t
     return (uint32_t)cap;
 }
 
+// Everything the scene has been asked to render goes to the device and runs: afterwards nothing queued reads an array
+// of the scene's, which may then be freed or replaced.
+int drain(tr_scene *s)
+{
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipStreamSynchronize(s->setup_stream));
+    HIP_TRY(hipStreamSynchronize(s->setup_stream2));
+    return TR_OK;
+}
+
+// Replaces the device array `d` by the `count` elements at `h` (`present` false: drops it).  The new array is allocated
+// first; frames issued so far keep the old one -- everything queued runs (drain) before the scene changes hands.  A
+// failure frees the new array and leaves the old one in place.
+template <typename T>
+int swap_device_array(tr_scene *s, T *&d, bool present, const T *h, size_t count)
+{
+    T *d_new = nullptr;
+    int st = TR_OK;
+    if (present && (st = dev_alloc(&d_new, count)) != TR_OK) return st;
+    st = [&]() -> int {
+        int rc = drain(s);
+        if (rc != TR_OK) return rc;
+        if (present) HIP_TRY(hipMemcpy(d_new, h, count * sizeof(T), hipMemcpyHostToDevice));
+        HIP_TRY(hipStreamSynchronize(nullptr));  // (the scene's streams do not wait for the null stream)
+        return TR_OK;
+    }();
+    if (st != TR_OK) {
+        dev_free(d_new);
+        return st;
+    }
+    dev_free(d);
+    d = d_new;
+    return TR_OK;
+}
+
 // A table of n instances is about to be drawn: the per-pass record arrays and (automatic bin capacity) the pools grow to
 // what tr_scene_create gives the mesh replicated n times.  Never shrinks.  Waits for the scene's queued work when
 // something grows (a new, larger table: not the steady state).
@@ -2367,11 +2396,8 @@ int grow_for_instances(tr_scene *s, uint32_t n)
     const uint64_t polys = (uint64_t)s->n_rows * (n ? n : 1u);
     const uint32_t cap = s->auto_bin_cap ? pool_cap_for(s->width, s->height, polys, 0) : s->pool_cap;
     if (polys <= s->poly_cap && cap <= s->pool_cap) return TR_OK;
-    int st = submit_pending(s);
+    int st = drain(s);
     if (st != TR_OK) return st;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipStreamSynchronize(s->setup_stream));
-    HIP_TRY(hipStreamSynchronize(s->setup_stream2));
     for (tr_scene::GroupSet &gs : s->grp) gs.in_flight = false;  // (their tile kernels have run)
     if (polys > s->poly_cap) {
         s->poly_cap = polys;
@@ -2397,6 +2423,19 @@ int check_instances(const tr_scene *s, uint32_t n, const void *inst)
 {
     if (n && !inst) return tr::fail(TR_E_INVALID, "null instance table");
     if ((uint64_t)s->n_rows * n >= 0xFFFFFFF0ull) return tr::fail(TR_E_INVALID, "too many polygons (mesh polygons x instances)");
+    return TR_OK;
+}
+
+// The posed calls' counts (tr_scene_set_morph_weights / _bone_palette and their render_frames forms): 0 is "none".
+int check_weight_count(const tr_scene *s, uint32_t n)
+{
+    if (n != 0u && n != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
+    return TR_OK;
+}
+
+int check_bone_count(const tr_scene *s, uint32_t n)
+{
+    if (n != 0u && n != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
     return TR_OK;
 }
 
@@ -3140,16 +3179,16 @@ int tr_scene_clear(tr_scene *s)
 int tr_scene_set_light_direction(tr_scene *s, const float v[3])
 {
     if (!s || !v) return tr::fail(TR_E_INVALID, "null argument");
-    memcpy(s->light, v, sizeof s->light);
+    memcpy(s->view.light, v, sizeof s->view.light);
     return TR_OK;
 }
 
 int tr_scene_set_camera(tr_scene *s, const float look_from[3], const float look_at[3], const float up[3])
 {
     if (!s || !look_from || !look_at || !up) return tr::fail(TR_E_INVALID, "null argument");
-    memcpy(s->from, look_from, sizeof s->from);
-    memcpy(s->at, look_at, sizeof s->at);
-    memcpy(s->up, up, sizeof s->up);
+    memcpy(s->view.look_from, look_from, sizeof s->view.look_from);
+    memcpy(s->view.look_at, look_at, sizeof s->view.look_at);
+    memcpy(s->view.up, up, sizeof s->view.up);
     return TR_OK;
 }
 
@@ -3158,10 +3197,7 @@ int tr_scene_render(tr_scene *s)
     if (!s) return tr::fail(TR_E_INVALID, "null scene");
     if (s->broken) return unusable();
     HIP_TRY(hipSetDevice(s->device));
-    memcpy(s->last.light, s->light, 12);
-    memcpy(s->last.from, s->from, 12);
-    memcpy(s->last.at, s->at, 12);
-    memcpy(s->last.up, s->up, 12);
+    s->last.view = s->view;
     s->last.z_fb_cleared = s->z_fb_cleared;
     s->last.shadow_cleared = s->shadow_cleared;
     s->last.valid = true;
@@ -3190,8 +3226,7 @@ int tr_scene_render(tr_scene *s)
     // (the frame's shadow pass is still to come, into the current slot: its matrix is known now)
     if (pd.n_passes == 2) note_shadow_matrix(s->slots[(size_t)s->cur_slot], s->uniforms.shadow_matrix);
     tr_scene::DeferredFrame f;
-    memcpy(f.p.light, s->light, 12); memcpy(f.p.look_from, s->from, 12);
-    memcpy(f.p.look_at, s->at, 12); memcpy(f.p.up, s->up, 12);
+    f.p = s->view;
     f.fb = s->d_fb;
     f.inst = s->inst;
     s->deferred.push_back(f);
@@ -3205,15 +3240,32 @@ int tr_scene_render(tr_scene *s)
     return TR_OK;
 }
 
-int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, void *const *frame_buffers_device)
+// The argument protocol of the tr_scene_render_frames family: frames_head, the call's own refusals, frames_tail, then
+// render_frames.  The head: the arguments every form takes, and a scene that can still render.
+static int frames_head(const tr_scene *s, uint32_t n_frames, const tr_frame_params *frames)
 {
     if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return unusable();
-    if (n_frames == 0) return TR_OK;
+    return s->broken ? unusable() : TR_OK;
+}
+
+// The tail: no frames are TR_OK without a look at the list or the device (`none`: the call is over); else every colour
+// target of the list must be one, and the scene's device becomes the current one.
+static int frames_tail(const tr_scene *s, uint32_t n_frames, void *const *frame_buffers_device, bool &none)
+{
+    none = n_frames == 0;
+    if (none) return TR_OK;
     if (frame_buffers_device)
         for (uint32_t i = 0; i < n_frames; i++)
             if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
     HIP_TRY(hipSetDevice(s->device));
+    return TR_OK;
+}
+
+int tr_scene_render_frames(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, void *const *frame_buffers_device)
+{
+    bool none = false;
+    int st = frames_head(s, n_frames, frames);
+    if (st != TR_OK || (st = frames_tail(s, n_frames, frame_buffers_device, none)) != TR_OK || none) return st;
     return render_frames(s, n_frames, frames, nullptr, frame_buffers_device);
 }
 
@@ -3236,16 +3288,12 @@ static int set_table(tr_scene *s, uint32_t n, uint32_t stride, const float *tabl
 static int render_frames_tables(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n, uint32_t stride,
                                 const float *tables, void *const *frame_buffers_device)
 {
-    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return unusable();
-    int st = check_instances(s, n, tables);
-    if (st != TR_OK) return st;
-    if (n_frames == 0) return TR_OK;
+    bool none = false;
+    int st = frames_head(s, n_frames, frames);
+    if (st != TR_OK || (st = check_instances(s, n, tables)) != TR_OK) return st;
+    // (no frames: no entries, so this never comes before the tail's TR_OK)
     if ((uint64_t)n_frames * n > 0xFFFFFFFFull) return tr::fail(TR_E_INVALID, "instance tables too large");
-    if (frame_buffers_device)
-        for (uint32_t i = 0; i < n_frames; i++)
-            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
-    HIP_TRY(hipSetDevice(s->device));
+    if ((st = frames_tail(s, n_frames, frame_buffers_device, none)) != TR_OK || none) return st;
     if ((st = grow_for_instances(s, n)) != TR_OK) return st;
     // all the frames' tables as one block: frame i draws entries [i n, (i + 1) n)
     std::vector<tr_scene::InstRef> insts(n_frames);
@@ -3305,25 +3353,9 @@ int tr_scene_set_morph_targets(tr_scene *s, uint32_t n_targets, const float *dpo
             gather_polygon(dpos + (size_t)k * s->n_pos * 3u, no_tex.data(), dnrm + (size_t)k * s->n_nrm * 3u, ix,
                            &rows[((size_t)k * s->n_rows + t) * TRI_FLOATS]);
         }
-    float *d_new = nullptr;
-    int st = TR_OK;
-    if (n_targets && (st = dev_alloc(&d_new, rows.size())) != TR_OK) return st;
-    // frames issued so far keep their poses: they go to the device, and everything queued runs, before the deltas change
-    if ((st = submit_pending(s)) != TR_OK) {
-        dev_free(d_new);
-        return st;
-    }
-    hipError_t e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
-    if (e == hipSuccess && n_targets) e = hipMemcpy(d_new, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
-    if (e != hipSuccess) {
-        dev_free(d_new);
-        HIP_TRY(e);
-    }
-    dev_free(s->d_delta);
-    s->d_delta = d_new;
+    // (frames issued so far keep their poses: their rows are blended before the deltas change)
+    int st = swap_device_array(s, s->d_delta, n_targets != 0u, rows.data(), rows.size());
+    if (st != TR_OK) return st;
     s->n_targets = n_targets;
     trim_pose_pool(s, 0);  // (everything queued has run: the free rows go back to the device)
     // no weights of the old targets stay current (frames already rendered keep their rows); the palette does: the skin
@@ -3337,7 +3369,8 @@ int tr_scene_set_morph_targets(tr_scene *s, uint32_t n_targets, const float *dpo
 int tr_scene_set_morph_weights(tr_scene *s, uint32_t n_weights, const float *w)
 {
     if (!s) return tr::fail(TR_E_INVALID, "null scene");
-    if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
+    int st = check_weight_count(s, n_weights);
+    if (st != TR_OK) return st;
     if (n_weights && !w) return tr::fail(TR_E_INVALID, "null weights");
     tr_scene::InstRef r = s->inst;
     r.pose = make_pose(s, n_weights ? w : nullptr, pose_palette(s, s->inst.pose));  // (the palette stays)
@@ -3348,15 +3381,11 @@ int tr_scene_set_morph_weights(tr_scene *s, uint32_t n_weights, const float *w)
 int tr_scene_render_frames_morphed(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_weights,
                                    const float *weights, void *const *frame_buffers_device)
 {
-    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return unusable();
-    if (n_weights != 0u && n_weights != s->n_targets) return tr::fail(TR_E_INVALID, "n_weights must be 0 or the scene's number of morph targets");
+    bool none = false;
+    int st = frames_head(s, n_frames, frames);
+    if (st != TR_OK || (st = check_weight_count(s, n_weights)) != TR_OK) return st;
     if (n_weights && n_frames && !weights) return tr::fail(TR_E_INVALID, "null weights");
-    if (n_frames == 0) return TR_OK;
-    if (frame_buffers_device)
-        for (uint32_t i = 0; i < n_frames; i++)
-            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
-    HIP_TRY(hipSetDevice(s->device));
+    if ((st = frames_tail(s, n_frames, frame_buffers_device, none)) != TR_OK || none) return st;
     // the current table under a pose per frame
     return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, POSED_WEIGHTS, n_weights ? weights : nullptr);
 }
@@ -3392,25 +3421,9 @@ int tr_scene_set_skin(tr_scene *s, uint32_t n_bones, const uint32_t *bone, const
     // the influences gathered per polygon like the mesh's rows
     std::vector<uint32_t> rows(n_bones ? (size_t)s->n_rows * tr::SKIN_ROW_WORDS : 0u);
     if (n_bones) tr::gather_skin_rows(s->mesh_idx.data(), s->n_rows, bone, weight, rows.data());
-    uint32_t *d_new = nullptr;
-    int st = TR_OK;
-    if (n_bones && (st = dev_alloc(&d_new, rows.size())) != TR_OK) return st;
-    // frames issued so far keep their palettes: they go to the device, and everything queued runs, before the skin changes
-    if ((st = submit_pending(s)) != TR_OK) {
-        dev_free(d_new);
-        return st;
-    }
-    hipError_t e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
-    if (e == hipSuccess && n_bones) e = hipMemcpy(d_new, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
-    if (e != hipSuccess) {
-        dev_free(d_new);
-        HIP_TRY(e);
-    }
-    dev_free(s->d_skin);
-    s->d_skin = d_new;
+    // (frames issued so far keep their palettes: their rows are skinned before the skin changes)
+    int st = swap_device_array(s, s->d_skin, n_bones != 0u, rows.data(), rows.size());
+    if (st != TR_OK) return st;
     s->n_bones = n_bones;
     trim_pose_pool(s, 0);  // (everything queued has run: the free rows go back to the device)
     // no palette of the old skin stays current (frames already rendered keep their rows); the morph weights do
@@ -3423,7 +3436,8 @@ int tr_scene_set_skin(tr_scene *s, uint32_t n_bones, const uint32_t *bone, const
 int tr_scene_set_bone_palette(tr_scene *s, uint32_t n_bones, const tr_instance_xform *palette)
 {
     if (!s) return tr::fail(TR_E_INVALID, "null scene");
-    if (n_bones != 0u && n_bones != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
+    int st = check_bone_count(s, n_bones);
+    if (st != TR_OK) return st;
     if (n_bones && !palette) return tr::fail(TR_E_INVALID, "null palette");
     tr_scene::InstRef r = s->inst;
     r.pose = make_pose(s, pose_weights(s, s->inst.pose), n_bones ? reinterpret_cast<const float *>(palette) : nullptr);  // (the weights stay)
@@ -3434,15 +3448,11 @@ int tr_scene_set_bone_palette(tr_scene *s, uint32_t n_bones, const tr_instance_x
 int tr_scene_render_frames_skinned(tr_scene *s, uint32_t n_frames, const tr_frame_params *frames, uint32_t n_bones,
                                    const tr_instance_xform *palettes, void *const *frame_buffers_device)
 {
-    if (!s || (n_frames && !frames)) return tr::fail(TR_E_INVALID, "null argument");
-    if (s->broken) return unusable();
-    if (n_bones != 0u && n_bones != s->n_bones) return tr::fail(TR_E_INVALID, "n_bones must be 0 or the bone count of the scene's skin");
+    bool none = false;
+    int st = frames_head(s, n_frames, frames);
+    if (st != TR_OK || (st = check_bone_count(s, n_bones)) != TR_OK) return st;
     if (n_bones && n_frames && !palettes) return tr::fail(TR_E_INVALID, "null palettes");
-    if (n_frames == 0) return TR_OK;
-    if (frame_buffers_device)
-        for (uint32_t i = 0; i < n_frames; i++)
-            if (!frame_buffers_device[i]) return tr::fail(TR_E_INVALID, "null frame buffer in the list");
-    HIP_TRY(hipSetDevice(s->device));
+    if ((st = frames_tail(s, n_frames, frame_buffers_device, none)) != TR_OK || none) return st;
     // the current table and morph weights under a palette per frame
     return render_frames(s, n_frames, frames, nullptr, frame_buffers_device, POSED_PALETTES,
                          n_bones ? reinterpret_cast<const float *>(palettes) : nullptr);
@@ -3515,8 +3525,7 @@ int tr_scene_select_frame(tr_scene *s, uint32_t back)
         return tr::fail(TR_E_INVALID, "tr_scene_select_frame: no such frame (tr_scene_frames_kept tells how many the last tr_scene_render_frames left)");
     HIP_TRY(hipSetDevice(s->device));
     const size_t k = s->tail.params.size() - 1u - back;
-    const tr_frame_params &q = s->tail.params[k];
-    memcpy(s->light, q.light, 12); memcpy(s->from, q.look_from, 12); memcpy(s->at, q.look_at, 12); memcpy(s->up, q.up, 12);
+    s->view = s->tail.params[k];   // (for good: the selection is the scene's state from here on)
     use_inst(s, s->tail.inst[k]);
     return use_slot(s, s->tail.slot[k], s->tail.fbs.empty() ? nullptr : (uint8_t *)s->tail.fbs[k]);
 }
@@ -4538,25 +4547,8 @@ int tr_scene_set_lut(tr_scene *s, uint32_t n, const uint8_t *lut)
     const size_t entries = (size_t)n * n * n, padded = (entries + 3u) / 4u * 4u;
     std::vector<uint32_t> words(padded, 0u);
     if (n) grade_expand(n, lut, words.data());
-    uint32_t *d_new = nullptr;
-    int st = TR_OK;
-    if (n && (st = dev_alloc(&d_new, padded)) != TR_OK) return st;
-    // frames issued so far keep their table: everything queued runs before it changes
-    if ((st = submit_pending(s)) != TR_OK) {
-        dev_free(d_new);
-        return st;
-    }
-    hipError_t e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->setup_stream2);
-    if (e == hipSuccess && n) e = hipMemcpy(d_new, words.data(), padded * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the scene's streams do not wait for the null stream)
-    if (e != hipSuccess) {
-        dev_free(d_new);
-        HIP_TRY(e);
-    }
-    dev_free(s->d_lut);
-    s->d_lut = d_new;
+    int st = swap_device_array(s, s->d_lut, n != 0u, words.data(), padded);
+    if (st != TR_OK) return st;
     s->lut_n = n;
     s->lut_c0 = n ? words[0] : 0u;
     return TR_OK;

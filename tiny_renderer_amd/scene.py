@@ -579,49 +579,48 @@ class Scene:
         """Whether render() may hold cleared frames back to fuse them (default on; tr_scene_set_auto_group)."""
         check(load_library().tr_scene_set_auto_group(self._h, 1 if on else 0))
 
+    def _dropped(self, fn, value, n_arrays=1):
+        """The setters' opening: None or an empty `value` calls setter `fn` with a count of zero and null arrays; was it so?"""
+        if value is None or len(value) == 0:
+            check(getattr(load_library(), fn)(self._h, 0, *[None] * n_arrays))
+            return True
+        return False
+
     def set_instances(self, instances):
         """tr_scene_set_instances: draw the mesh once per row of the [n, 4] float32 table (offset x, y, z, scale),
         positions p * scale + offset, instance-major polygon order; None or an empty table: the mesh itself."""
-        L = load_library()
-        if instances is None or len(instances) == 0:
-            check(L.tr_scene_set_instances(self._h, 0, None))
+        if self._dropped("tr_scene_set_instances", instances):
             return
         a = _instance_table(instances)
-        check(L.tr_scene_set_instances(self._h, a.shape[0], a.ctypes.data))
+        check(load_library().tr_scene_set_instances(self._h, a.shape[0], a.ctypes.data))
 
     def set_instance_transforms(self, table):
         """tr_scene_set_instance_transforms: draw the mesh once per row of the [n, 24] float32 table (instance_transforms
         builds one: a 3 x 4 for positions, a 3 x 3 for vertex normals), replacing a table of either kind; None or an
         empty table: the mesh itself."""
-        L = load_library()
-        if table is None or len(table) == 0:
-            check(L.tr_scene_set_instance_transforms(self._h, 0, None))
+        if self._dropped("tr_scene_set_instance_transforms", table):
             return
         a = _transform_table(table)
-        check(L.tr_scene_set_instance_transforms(self._h, a.shape[0], a.ctypes.data))
+        check(load_library().tr_scene_set_instance_transforms(self._h, a.shape[0], a.ctypes.data))
 
     def set_morph_targets(self, dpos, dnrm=None):
         """tr_scene_set_morph_targets: T morph targets as deltas dpos [T, n_pos, 3] and dnrm [T, n_nrm, 3] float32
         (morph_deltas builds one from a second mesh); None or no targets: drops them.  Leaves the scene without a pose."""
-        L = load_library()
-        if dpos is None or len(dpos) == 0:
-            check(L.tr_scene_set_morph_targets(self._h, 0, None, None))
+        if self._dropped("tr_scene_set_morph_targets", dpos, 2):
             self.n_morph_targets = 0
             return
         if dnrm is None:
             raise ValueError("morph targets need dnrm beside dpos")
         dp, dn = _morph_deltas(self._mesh_shape, dpos, dnrm)
-        check(L.tr_scene_set_morph_targets(self._h, dp.shape[0], dp.ctypes.data, dn.ctypes.data))
+        check(load_library().tr_scene_set_morph_targets(self._h, dp.shape[0], dp.ctypes.data, dn.ctypes.data))
         self.n_morph_targets = dp.shape[0]
 
     def set_morph_weights(self, weights):
         """tr_scene_set_morph_weights: the pose drawn from now on, [T] float32; None or empty: the mesh itself."""
-        L = load_library()
-        if weights is None or len(weights) == 0:
-            check(L.tr_scene_set_morph_weights(self._h, 0, None))
+        if self._dropped("tr_scene_set_morph_weights", weights):
             return
         w = _morph_weights(weights, self.n_morph_targets)
-        check(L.tr_scene_set_morph_weights(self._h, w.shape[0], w.ctypes.data))
+        check(load_library().tr_scene_set_morph_weights(self._h, w.shape[0], w.ctypes.data))
 
     def set_skin(self, bones, weights=None, n_bones=None):
         """tr_scene_set_skin: four influences per position index -- bones [n_pos, 4] uint32, weights [n_pos, 4] float32;
@@ -646,12 +645,10 @@ class Scene:
     def set_bone_palette(self, palette):
         """tr_scene_set_bone_palette: the palette drawn from now on, [n_bones, 24] float32 (instance_transforms builds
         one); None or empty: no palette -- the morph pose's rows or the mesh's own."""
-        L = load_library()
-        if palette is None or len(palette) == 0:
-            check(L.tr_scene_set_bone_palette(self._h, 0, None))
+        if self._dropped("tr_scene_set_bone_palette", palette):
             return
         a = _palette(palette, self.n_bones)
-        check(L.tr_scene_set_bone_palette(self._h, a.shape[0], a.ctypes.data))
+        check(load_library().tr_scene_set_bone_palette(self._h, a.shape[0], a.ctypes.data))
 
     def debug_morph_rows(self):
         """tr_scene_debug_morph_rows: sets of posed rows the scene has on the device now (held and free)."""
@@ -688,35 +685,21 @@ class Scene:
             if len(frame_buffers_device) != len(frames):
                 raise ValueError("one frame buffer per frame")
             fbs = (C.c_void_p * len(frames))(*[int(q) for q in frame_buffers_device])
-        if bone_palettes is not None:
-            pal = _palette(bone_palettes, self.n_bones, per_frame=True)
-            if pal.shape[0] != len(frames):
-                raise ValueError("one palette per frame")
-            check(load_library().tr_scene_render_frames_skinned(self._h, len(frames), frames.ctypes.data, pal.shape[1],
-                                                                pal.ctypes.data, fbs))
-            return
-        if morph_weights is not None:
-            w = _morph_weights(morph_weights, self.n_morph_targets, per_frame=True)
-            if w.shape[0] != len(frames):
-                raise ValueError("one pose per frame")
-            check(load_library().tr_scene_render_frames_morphed(self._h, len(frames), frames.ctypes.data, w.shape[1],
-                                                                w.ctypes.data if w.size else None, fbs))
-            return
-        if instance_transforms is not None:
-            xf = _transform_table(instance_transforms, per_frame=True)
-            if xf.shape[0] != len(frames):
-                raise ValueError("one instance transform table per frame")
-            check(load_library().tr_scene_render_frames_transformed(self._h, len(frames), frames.ctypes.data, xf.shape[1],
-                                                                    xf.ctypes.data if xf.size else None, fbs))
-            return
-        if instances is None:
-            check(load_library().tr_scene_render_frames(self._h, len(frames), frames.ctypes.data, fbs))
-            return
-        inst = _instance_table(instances, per_frame=True)
-        if inst.shape[0] != len(frames):
-            raise ValueError("one instance table per frame")
-        check(load_library().tr_scene_render_frames_instanced(self._h, len(frames), frames.ctypes.data, inst.shape[1],
-                                                              inst.ctypes.data if inst.size else None, fbs))
+        # The per-frame input, at most one (above): its converter and what that takes beside the array, the call, what the
+        # ValueError for a wrong number of frames calls it, whether an array without elements still goes as a pointer
+        kinds = ((bone_palettes, _palette, (self.n_bones,), "tr_scene_render_frames_skinned", "palette", True),
+                 (morph_weights, _morph_weights, (self.n_morph_targets,), "tr_scene_render_frames_morphed", "pose", False),
+                 (instance_transforms, _transform_table, (), "tr_scene_render_frames_transformed", "instance transform table", False),
+                 (instances, _instance_table, (), "tr_scene_render_frames_instanced", "instance table", False))
+        for value, convert, args, fn, what, always_pointer in kinds:
+            if value is not None:
+                a = convert(value, *args, per_frame=True)
+                if a.shape[0] != len(frames):
+                    raise ValueError("one %s per frame" % what)
+                check(getattr(load_library(), fn)(self._h, len(frames), frames.ctypes.data, a.shape[1],
+                                                  a.ctypes.data if a.size or always_pointer else None, fbs))
+                return
+        check(load_library().tr_scene_render_frames(self._h, len(frames), frames.ctypes.data, fbs))
 
     @property
     def frames_per_launch(self):
