@@ -4,11 +4,11 @@
 // bbox-y, depth-testing and shading each covered pixel in polygon order.  Here a render pass is
 // four kernels:
 //
-//   k_setup        one lane per polygon: vertex closure, clamped bounding box; then the wavefront
-//                  spreads its (polygon, tile) pairs over all 64 lanes and appends the polygon's
-//                  complete record to the fixed-capacity bin of every tile it touches
-//   k_order_count, k_order_place
-//                  one thread per tile: the tile kernel's work list, tiles sorted by polygon count
+//   k_setup        one lane per polygon: vertex closure, clamped bounding box, the polygon's record;
+//                  the wavefront then counts, per tile, the polygons whose box meets it
+//   k_order        one thread per tile: the tile kernel's work lists, tiles by polygon count, and
+//                  every tile's range of exactly that many records in the pass's pool
+//   k_bin          copies the records into the tiles' ranges (exact binning: see k_setup below)
 //   k_tile         one workgroup (4, 8 or 16 waves) per 128x16 screen tile, heaviest tiles first:
 //                  the bin is copied into LDS in one coalesced pass, each wave resolves coverage +
 //                  depth for its column of the tile against LDS keys, then the survivors are shaded

@@ -271,7 +271,7 @@ struct tr_scene {
     WorkItem *d_order[LOOKAHEAD] = {};  // the tile kernel's work list (k_order)
     Piece *d_bins[LOOKAHEAD] = {};      // the passes' pools: pool_cap records of rec_pieces x 16 B each
     Piece *d_recs[LOOKAHEAD] = {};      // every polygon's record, once per pass (k_setup -> k_bin)
-    // Pass pipelining: k_setup and k_order_* of pass p run on `setup_stream`, ordered after the tile
+    // Pass pipelining: the chain of pass p (launch_chain: k_lit, k_setup, k_order, k_bin) runs on `setup_stream`, ordered after the tile
     // kernel of pass p - LOOKAHEAD (which freed its bins and zeroed its counters) and before the tile
     // kernel of pass p on the main stream.  They need only frame constants, so they overlap the tile
     // kernels of earlier passes: consecutive frames are in flight together, like any renderer's.
@@ -494,8 +494,6 @@ void dev_free(T *&p)
     p = nullptr;
 }
 
-// Points d_fbclean at the flag set of the current frame buffer (allocated zeroed = "content unknown"
-// the first time a buffer is seen; at most a handful of buffers are remembered).
 // The flag set of frame buffer `fb` (allocated zeroed = "content unknown" the first time a buffer is seen;
 // a few dozen buffers are remembered: a caller's double-buffered groups of frames, the scene's own slots).
 int fb_flags_for(tr_scene *s, uint8_t *fb, uint32_t **out, bool forget = false)
@@ -949,6 +947,18 @@ hipEvent_t take_event(tr_scene *s)
     return e;
 }
 
+// A launch's profile record: with its two timing events while the scene is profiling, else with none (the launchers
+// take null events); whoever launched pushes it onto s->events when it has events.
+EventPair timing_pair(tr_scene *s, int kernel, uint32_t frames)
+{
+    EventPair ep = { nullptr, nullptr, kernel, frames };
+    if (s->profiling) {
+        ep.a = take_event(s);
+        ep.b = take_event(s);
+    }
+    return ep;
+}
+
 struct Timed {
     tr_scene *s;
     hipStream_t st;
@@ -1007,19 +1017,16 @@ int launch_status(int rc, const char *what)
 int launch_pending_tile(tr_scene *s, const tr_scene::PendingTile &t)
 {
     int status = TR_OK;
-    if (!s->profiling) {
-        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, nullptr, 0, s->stream, nullptr, s->ev_tile[t.p_seq % RING], 0u,
-                             t.fused_single);
-        if (rc) status = launch_status(rc, "k_tile");
-        if (rc) s->broken = true;  // (its chain has run: the set's counters were not zeroed, the pass's ranges never consumed)
-    } else {
-        EventPair ep = { take_event(s), take_event(s), t.kernel_id, 1u };
-        int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, nullptr, 0, s->stream, ep.a, ep.b, 0u, t.fused_single);
-        if (rc) status = launch_status(rc, "k_tile");
-        if (rc) s->broken = true;
+    // (the pass's "tile done" event rides on the kernel's own completion signal; profiling: recorded behind its timing events)
+    const EventPair ep = timing_pair(s, t.kernel_id, 1u);
+    hipEvent_t tile_done = s->ev_tile[t.p_seq % RING];
+    int rc = launch_tile(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, nullptr, 0, s->stream, ep.a, s->profiling ? ep.b : tile_done, 0u,
+                         t.fused_single);
+    if (rc) status = launch_status(rc, "k_tile");
+    if (rc) s->broken = true;  // (its chain has run: the set's counters were not zeroed, the pass's ranges never consumed)
+    if (s->profiling) {
         s->events.push_back(ep);
-        if (hipEventRecord(s->ev_tile[t.p_seq % RING], s->stream) != hipSuccess && status == TR_OK)
-            status = tr::fail(TR_E_HIP, "hipEventRecord");
+        if (hipEventRecord(tile_done, s->stream) != hipSuccess && status == TR_OK) status = tr::fail(TR_E_HIP, "hipEventRecord");
     }
     if (t.fused_single) s->fused_interior = tile_launch_is_interior(t.fs, t.args, t.tile_waves, t.shared, t.n_poly, true) ? 1 : 0;
     s->tiles_submitted += 1;
@@ -1337,19 +1344,6 @@ int pass_uniforms(tr_scene *s, const PassDesc &p, DevUniforms &du)
 // and specular closures have run per texel, and the fragment stage fetches their result.
 int tile_fs(const tr_scene *s, int fs) { return (s->lit && (fs == FS_NORMAL_MAP || fs == FS_SPECULAR)) ? (int)FS_LIT : fs; }
 
-// ... and what the pass's chain needs for it: where the frame's lit image goes, and the tile kernel's view of it.
-void lit_args(const tr_scene *s, uint32_t *lit, SetupArgs &sa, TileArgs &ta)
-{
-    sa.lit = lit;
-    sa.texel_set = s->tex.packed;
-    sa.tex_w = s->tex.w[0];
-    sa.tex_h = s->tex.h[0];
-    sa.set_bpr = s->set_bpr;
-    sa.lit_bpr = s->lit_bpr;
-    ta.tex.packed = lit;        // (one word per texel, 8x4 blocks: what fetch_texels<FS_LIT> reads)
-    ta.tex.packed_bpr = s->lit_bpr;
-}
-
 // How a tile's work is divided is a launch-time choice (speed only; tr_options.tile_waves / tile_mode
 // pin it).  Few tiles cannot fill the GPU with four waves each: more waves per tile shorten every
 // wave's serial chain, and sharing the bin between them (instead of giving each a column of the
@@ -1397,12 +1391,132 @@ void note_shadow_matrix(tr_scene::FrameSlot &slot, const float *m)
     slot.shadow_matrix_set = true;
 }
 
+// One frame's render targets, as fill_pass_args takes them: run_pass passes the scene's current aliases (s->d_*),
+// run_group a frame slot's buffers with the colour target and flags it has resolved for the frame.
+struct PassTargets {
+    float *z, *shadow;
+    uint8_t *fb;
+    uint32_t *zclean, *sclean, *fbclean;
+    uint32_t *winner;
+    uint64_t *stamps;
+};
+
+// The storage of one pass's chain: run_pass passes its share of the LOOKAHEAD rings and the BinState's counter set,
+// run_group slice e of the GroupSet.  lit: where the frame's lit image goes (scenes on the lit path).  len_src / len_host:
+// SetupArgs' -- a fused launch reports its list lengths to the host; null on the per-frame path.
+struct ChainStore {
+    uint32_t *tile_count;
+    Piece *recs, *bins;
+    WorkItem *order;
+    uint32_t *lit;
+    const uint32_t *len_src;
+    uint32_t *len_host;
+};
+
+// The arguments of one pass of one frame: every member of `sa` but sa.u, which the caller has filled in place
+// (pass_uniforms: the constants are copied once, into ta.u), and every member of `ta`.  Decides nothing: whether the
+// targets are cleared (fresh), what the pass writes (store), the tile kernel's form (shared) and which targets and
+// storage are the callers'.  depth_only (ensure_depth's repeat): no winner words, no stamps, and the pass's own closure
+// -- no lit arguments -- even on a scene whose lit path is on.  Allocates nothing.
+void fill_pass_args(const tr_scene *s, const PassDesc &p, const PassTargets &t, const ChainStore &c, const DevMesh &mesh, int shared,
+                    uint32_t fresh, uint32_t store, uint64_t pass_seq, bool depth_only, SetupArgs &sa, TileArgs &ta)
+{
+    const bool depth_pass = p.fs == FS_DEPTH;
+    const bool looks_up_shadow = p.fs == FS_SHADOW2 || p.fs == FS_OCCLUSION2;
+    const bool lit = !depth_only && tile_fs(s, p.fs) == (int)FS_LIT;   // k_lit runs the closure per texel, the tiles fetch its result
+    const DevFrame &frame = depth_pass ? s->frame_full : s->frame;      // (a depth pass fills the whole shadow buffer)
+    sa.mesh = mesh;
+    sa.frame = frame;
+    sa.tile_count = c.tile_count;
+    sa.recs = c.recs;
+    sa.bins = c.bins;
+    sa.pool_cap = s->pool_cap;
+    sa.rec_pieces = s->rec_pieces;
+    sa.err = s->d_err;
+    sa.alarm = s->d_alarm;
+    sa.cells = shared ? 1u : 0u;
+    sa.lit = lit ? c.lit : nullptr;
+    sa.texel_set = lit ? s->tex.packed : nullptr;
+    sa.tex_w = lit ? s->tex.w[0] : 0u;
+    sa.tex_h = lit ? s->tex.h[0] : 0u;
+    sa.set_bpr = lit ? s->set_bpr : 0u;
+    sa.lit_bpr = lit ? s->lit_bpr : 0u;
+    sa.len_src = c.len_src;
+    sa.len_host = c.len_host;
+    memset(&ta, 0, sizeof ta);   // (list_len: zeroed by the host, filled by k_order)
+    ta.bins = c.bins;
+    ta.pool_cap = s->pool_cap;
+    ta.rec_pieces = s->rec_pieces;
+    ta.order = c.order;
+    ta.tile_count = c.tile_count;
+    ta.bin_need = s->d_bin_need;
+    ta.overflow_seq = s->d_overflow_seq;
+    ta.pass_seq = pass_seq;
+    ta.frame = frame;
+    ta.u = sa.u;
+    ta.tex = s->tex;
+    if (lit) {
+        ta.tex.packed = c.lit;   // (one word per texel, 8x4 blocks: what fetch_texels<FS_LIT> reads)
+        ta.tex.packed_bpr = s->lit_bpr;
+    }
+    ta.zbuf = t.z;
+    ta.shadow = t.shadow;
+    ta.fb = t.fb;
+    ta.winner = depth_only ? nullptr : t.winner;
+    ta.err = s->d_err;
+    ta.alarm = s->d_alarm;
+    ta.fresh = fresh;
+    ta.store = store;
+    ta.aligned16 = (s->width % 16u == 0u) ? 1u : 0u;
+    ta.aligned4 = (s->width % 4u == 0u) ? 1u : 0u;
+    ta.stamps = (depth_pass || depth_only) ? nullptr : t.stamps;
+    ta.zclean = depth_pass ? t.sclean : t.zclean;   // (the depth pass's z is the shadow buffer)
+    ta.fbclean = depth_pass ? nullptr : t.fbclean;
+    ta.sclean = looks_up_shadow ? t.sclean : nullptr;
+}
+
+// Queues one pass's chain on `chain`: k_lit first where the pass is lit (sa0.lit: it needs nothing but the frame's
+// constants), then vertex stage + counting, work lists + pool ranges, records into the ranges.  d_setup / d_tile: the
+// device tables of a fused launch over g frames -- sa0 / ta0 then say what the frames share, n_poly is the largest
+// frame's and xform whether any frame draws a transform table -- or null: the one frame sa0 / ta0 describe (g = 1).
+// `done` (may be null) completes with the chain.  Without profiling it rides on the last kernel's own completion signal
+// -- k_bin's, or k_order's when there are no polygons and k_bin is not launched; with profiling the kernels carry their
+// timing events and `done` is recorded behind them.
+int launch_chain(tr_scene *s, const PassDesc &p, const SetupArgs &sa0, const TileArgs &ta0, const SetupArgs *d_setup, const TileArgs *d_tile,
+                 uint32_t g, uint32_t n_tiles_pass, uint32_t n_poly, bool xform, bool chain_on_main, hipStream_t chain, hipEvent_t done)
+{
+    const uint32_t nf = d_setup ? g : 0u;   // (the launchers' n_frames: 0 = an ordinary launch)
+    const bool prof = s->profiling;
+    if (sa0.lit) {
+        const EventPair el = timing_pair(s, K_LIT, g);
+        int rc = launch_lit(p.fs, sa0, d_setup, nf, chain, el.a, el.b);
+        if (rc) return launch_status(rc, "k_lit");
+        if (prof) s->events.push_back(el);
+    }
+    const EventPair ep = timing_pair(s, K_SETUP, g);
+    int rc = launch_setup(p.vs, sa0, d_setup, nf, xform, chain_on_main, chain, ep.a, ep.b);
+    if (rc) return launch_status(rc, "k_setup");
+    if (prof) s->events.push_back(ep);
+    const EventPair eo = timing_pair(s, K_ORDER, g);
+    rc = launch_order(ta0, n_tiles_pass, d_tile, nf, chain, eo.a, (prof || n_poly) ? eo.b : done);
+    if (rc) return launch_status(rc, "k_order");
+    if (prof) s->events.push_back(eo);
+    if (n_poly) {
+        const EventPair eb = timing_pair(s, K_BIN, g);
+        rc = launch_bin(sa0, d_setup, nf, chain_on_main, chain, eb.a, prof ? eb.b : done);
+        if (rc) return launch_status(rc, "k_bin");
+        if (prof) s->events.push_back(eb);
+    }
+    if (prof && done) HIP_TRY(hipEventRecord(done, chain));
+    return TR_OK;
+}
+
 // depth_only: the repeat of a colour pass for its depth alone (ensure_depth): from cleared targets, nothing of the
 // scene's clear / colour state is consumed or changed.
 int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
 {
-    DevUniforms du;
-    int st = pass_uniforms(s, p, du);
+    SetupArgs sa = {};   // (every byte defined: the kernels take the struct by value)
+    int st = pass_uniforms(s, p, sa.u);
     if (st != TR_OK) return st;
     // a per-frame pass after frame groups: their tile kernels first (it may render onto their targets)
     if (s->group_submitted < s->group_seq || s->groups_unfenced) {
@@ -1416,7 +1530,7 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
     if (depth_pass) {
         fresh = s->shadow_cleared ? 1u : 0u;
         s->shadow_cleared = false;
-        note_shadow_matrix(s->slots[(size_t)s->cur_slot], du.shadow_matrix);
+        note_shadow_matrix(s->slots[(size_t)s->cur_slot], sa.u.shadow_matrix);
     } else if (depth_only) {
         fresh = 1u;
     } else {
@@ -1436,56 +1550,17 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
     tile_layout(s, n_tiles_pass, n_tiles_pass, s->mesh.n_tri, pt.tile_waves, pt.shared);
     pt.n_poly = s->mesh.n_tri;
 
-    SetupArgs sa = {};   // (every member defined: the kernels take the struct by value)
-    sa.mesh = s->mesh;
-    sa.frame = frame;
-    sa.u = du;
-    sa.cells = pt.shared ? 1u : 0u;
-    tr_scene::BinState &bs = depth_pass ? s->bin_depth : s->bin_color;
-    const int set_cur = (int)(bs.seq % SETS);
-    const uint64_t p_seq = s->pass_seq;
-    Piece *bins = s->d_bins[p_seq % LOOKAHEAD];
-    sa.tile_count = bs.count[set_cur];
-    sa.recs = s->d_recs[p_seq % LOOKAHEAD];
-    sa.bins = bins;
-    sa.pool_cap = s->pool_cap;
-    sa.rec_pieces = s->rec_pieces;
-    sa.err = s->d_err;
-    sa.alarm = s->d_alarm;
-    TileArgs ta = {};
-    ta.bins = bins;
-    ta.pool_cap = s->pool_cap;
-    ta.rec_pieces = s->rec_pieces;
-    ta.order = s->d_order[p_seq % LOOKAHEAD];
-    ta.tile_count = bs.count[set_cur];
-    ta.bin_need = s->d_bin_need;
-    ta.overflow_seq = s->d_overflow_seq;
-    ta.pass_seq = p_seq;
-    ta.frame = frame;
-    ta.u = du;
-    ta.tex = s->tex;
-    ta.zbuf = s->d_z;
-    ta.shadow = s->d_shadow;
-    ta.fb = s->d_fb;
-    ta.winner = s->d_winner;
-    ta.zclean = depth_pass ? s->d_sclean : s->d_zclean;
-    ta.fbclean = depth_pass ? nullptr : s->d_fbclean;
-    ta.sclean = (p.fs == FS_SHADOW2 || p.fs == FS_OCCLUSION2) ? s->d_sclean : nullptr;
-    ta.err = s->d_err;
-    ta.alarm = s->d_alarm;
-    ta.fresh = fresh;
-    ta.store = TR_STORE_DEPTH | TR_STORE_COLOR;
+    // What the pass writes to memory (TileArgs::store)
+    uint32_t store = TR_STORE_DEPTH | TR_STORE_COLOR;
     if (!depth_pass) {
         tr_scene::FrameSlot &slot = s->slots[(size_t)s->cur_slot];
         if (depth_only) {
-            ta.store = TR_STORE_DEPTH;
-            ta.winner = nullptr;
-            ta.stamps = nullptr;
+            store = TR_STORE_DEPTH;
             slot.z_deferred = false;
         } else if (fresh && !s->d_winner && defer_depth(s) && fused_single_launches()) {
             // a cleared frame on its own: the fused launches' kernel for one frame (launch_tile, fused_single), and like
             // a group's frames it leaves its depth on the chip; whoever wants the z buffer gets it from ensure_depth
-            ta.store = TR_STORE_COLOR;
+            store = TR_STORE_COLOR;
             slot.z_deferred = true;
             slot.z_params = s->view;
             slot.z_inst = s->inst;
@@ -1495,16 +1570,18 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
         }
     }
     pt.fused_single = !depth_only && fresh != 0u && !s->d_winner && fused_single_launches();
-    if (!depth_pass && ((ta.store & TR_STORE_DEPTH) || fresh == 0u)) {   // the pass reads or writes z memory
+    if (!depth_pass && ((store & TR_STORE_DEPTH) || fresh == 0u)) {   // the pass reads or writes z memory
         st = need_z(s, s->cur_slot);
         if (st != TR_OK) return st;
-        ta.zbuf = s->d_z;
     }
-    ta.aligned16 = (s->width % 16u == 0u) ? 1u : 0u;
-    ta.aligned4 = (s->width % 4u == 0u) ? 1u : 0u;
-    if (!depth_only) ta.stamps = depth_pass ? nullptr : s->d_stamps;
-    const bool lit_pass = !depth_only && tile_fs(s, p.fs) == (int)FS_LIT;
-    if (lit_pass) lit_args(s, s->d_lit[p_seq % LOOKAHEAD], sa, ta);
+    tr_scene::BinState &bs = depth_pass ? s->bin_depth : s->bin_color;
+    const uint64_t p_seq = s->pass_seq;
+    const size_t ring = (size_t)(p_seq % LOOKAHEAD);
+    // (the current aliases, read after need_z: it may have given the slot its z buffer and pointed d_z at it)
+    const PassTargets targets = { s->d_z, s->d_shadow, s->d_fb, s->d_zclean, s->d_sclean, s->d_fbclean, s->d_winner, s->d_stamps };
+    const ChainStore cs = { bs.count[bs.seq % SETS], s->d_recs[ring], s->d_bins[ring], s->d_order[ring], s->d_lit[ring], nullptr, nullptr };
+    TileArgs &ta = pt.args;
+    fill_pass_args(s, p, targets, cs, s->mesh, pt.shared, fresh, store, p_seq, depth_only, sa, ta);
     // setup on its own stream: after the tile kernel of pass p - LOOKAHEAD, before the tile kernel of pass p.
     // With NOTHING in flight (a frame rendered and read, rendered and read: the interactive loop) the chain has
     // nothing to overlap with, and the hop between the streams -- event, wait packet, dispatch: 13-17 us -- is
@@ -1522,45 +1599,14 @@ int run_pass(tr_scene *s, const PassDesc &p, bool depth_only = false)
         sa.mesh.tri = s->mesh.tri = s->inst.pose->rows.d;
     }
     if (!sa.mesh.tri && sa.mesh.n_tri) return tr::fail(TR_E_INVALID, "no rows to draw");
-    // the chain: vertex stage + counting, work lists + pool ranges, records into the ranges
-    if (lit_pass) {  // (first in the chain: it needs nothing but the frame's constants)
-        EventPair el = { nullptr, nullptr, K_LIT, 1u };
-        if (s->profiling) { el.a = take_event(s); el.b = take_event(s); }
-        int rc = launch_lit(p.fs, sa, nullptr, 0, chain, el.a, el.b);
-        if (rc) return launch_status(rc, "k_lit");
-        if (s->profiling) s->events.push_back(el);
-    }
-    if (!s->profiling) {
-        int rc = launch_setup(p.vs, sa, nullptr, 0, sa.mesh.inst_xform != 0u, chain_on_main, chain, nullptr, nullptr);
-        if (rc) return launch_status(rc, "k_setup");
-        rc = launch_order(ta, n_tiles_pass, nullptr, 0, chain, nullptr, s->mesh.n_tri ? nullptr : s->ev_setup[p_seq % RING]);
-        if (rc) return launch_status(rc, "k_order");
-        rc = launch_bin(sa, nullptr, 0, chain_on_main, chain, nullptr, s->ev_setup[p_seq % RING]);
-        if (rc) return launch_status(rc, "k_bin");
-    } else {
-        // profiling: timing events on the dispatches themselves, then the pipeline's event separately
-        EventPair ep = { take_event(s), take_event(s), K_SETUP, 1u };
-        int rc = launch_setup(p.vs, sa, nullptr, 0, sa.mesh.inst_xform != 0u, chain_on_main, chain, ep.a, ep.b);
-        if (rc) return launch_status(rc, "k_setup");
-        s->events.push_back(ep);
-        EventPair eo = { take_event(s), take_event(s), K_ORDER, 1u };
-        rc = launch_order(ta, n_tiles_pass, nullptr, 0, chain, eo.a, eo.b);
-        if (rc) return launch_status(rc, "k_order");
-        s->events.push_back(eo);
-        if (s->mesh.n_tri) {
-            EventPair eb = { take_event(s), take_event(s), K_BIN, 1u };
-            rc = launch_bin(sa, nullptr, 0, chain_on_main, chain, eb.a, eb.b);
-            if (rc) return launch_status(rc, "k_bin");
-            s->events.push_back(eb);
-        }
-        HIP_TRY(hipEventRecord(s->ev_setup[p_seq % RING], chain));
-    }
+    st = launch_chain(s, p, sa, ta, nullptr, nullptr, 1u, n_tiles_pass, sa.mesh.n_tri, sa.mesh.inst_xform != 0u, chain_on_main, chain,
+                      s->ev_setup[p_seq % RING]);
+    if (st != TR_OK) return st;
     if ((st = note_inst_use(s, sa.mesh, chain)) != TR_OK) return st;
     if ((st = note_pose_use(s, &s->inst.pose, 1u, chain)) != TR_OK) return st;
     pt.fs = depth_only ? p.fs : tile_fs(s, p.fs);
     pt.kernel_id = depth_pass ? K_TILE_DEPTH : K_TILE;
     pt.p_seq = p_seq;
-    pt.args = ta;
     s->pending.push_back(pt);
     bs.seq++;
     s->pass_seq++;
@@ -1906,56 +1952,23 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
         if (!fb) st = slot_own_fb(s, slot_of[j], &fb);
         uint32_t *fbclean = nullptr;
         if (st == TR_OK) st = fb_flags_for(s, fb, &fbclean, callers && forget_callers_buffers);
+        // (the slot's z after need_z.  The winner tap is null on every way here: with it render_frames and replay_tail go
+        // frame by frame through run_pass, and frame_is_groupable holds no frame back)
+        const PassTargets targets = { slot.z, slot.shadow, fb, slot.zclean, slot.sclean, fbclean, s->d_winner, s->d_stamps };
         for (uint32_t pi = 0; pi < np && st == TR_OK; pi++) {
             const PassDesc &pass = pd.pass[pi];
-            const bool depth_pass = (pass.fs == FS_DEPTH);
             const size_t e = (size_t)pi * G + j;  // this frame-pass's share of the set
             SetupArgs &sa = h_setup[e];
-            TileArgs &ta = h_tile[e];
-            memset(&sa, 0, sizeof sa);
-            memset(&ta, 0, sizeof ta);
             st = pass_uniforms(s, pass, sa.u);
             if (st != TR_OK) break;
-            if (depth_pass) note_shadow_matrix(slot, sa.u.shadow_matrix);
-            const DevFrame &frame = depth_pass ? s->frame_full : s->frame;
-            sa.mesh = mesh;
-            sa.frame = frame;
-            sa.tile_count = gs.count + e * group_counts_per_frame(s);
-            sa.recs = gs.recs + e * group_recs_per_frame(s);
-            sa.bins = gs.bins + e * group_bins_per_frame(s);
-            sa.pool_cap = s->pool_cap;
-            sa.rec_pieces = s->rec_pieces;
-            sa.err = s->d_err;
-            sa.alarm = s->d_alarm;
-            sa.cells = gs.shared[pi] ? 1u : 0u;
-            sa.len_src = d_tile[e].list_len;
-            sa.len_host = gs.d_lens + e * LEN_WORDS;
-            ta.bins = sa.bins;
-            ta.pool_cap = s->pool_cap;
-            ta.rec_pieces = s->rec_pieces;
-            ta.order = gs.order + e * (size_t)s->n_tiles_full * ORDER_LISTS;
-            ta.tile_count = sa.tile_count;
-            ta.bin_need = s->d_bin_need;
-            ta.overflow_seq = s->d_overflow_seq;
-            ta.pass_seq = s->pass_seq + (uint64_t)j * np + pi;  // frame by frame, as the per-frame path numbers them
-            ta.frame = frame;
-            ta.u = sa.u;
-            ta.tex = s->tex;
-            ta.zbuf = slot.z;
-            ta.shadow = slot.shadow;
-            ta.fb = fb;
-            ta.winner = nullptr;
-            ta.zclean = depth_pass ? slot.sclean : slot.zclean;
-            ta.fbclean = depth_pass ? nullptr : fbclean;
-            ta.sclean = (pass.fs == FS_SHADOW2 || pass.fs == FS_OCCLUSION2) ? slot.sclean : nullptr;
-            ta.err = s->d_err;
-            ta.alarm = s->d_alarm;
-            ta.fresh = 1u;  // every frame of a group starts from cleared targets
-            ta.store = (!depth_pass && defer_depth(s)) ? TR_STORE_COLOR : (TR_STORE_DEPTH | TR_STORE_COLOR);
-            ta.aligned16 = (s->width % 16u == 0u) ? 1u : 0u;
-            ta.aligned4 = (s->width % 4u == 0u) ? 1u : 0u;
-            ta.stamps = depth_pass ? nullptr : s->d_stamps;
-            if (tile_fs(s, pass.fs) == (int)FS_LIT) lit_args(s, gs.lit + e * (size_t)s->lit_words, sa, ta);
+            if (pass.fs == FS_DEPTH) note_shadow_matrix(slot, sa.u.shadow_matrix);
+            const ChainStore cs = { gs.count + e * group_counts_per_frame(s), gs.recs + e * group_recs_per_frame(s),
+                                    gs.bins + e * group_bins_per_frame(s), gs.order + e * (size_t)s->n_tiles_full * ORDER_LISTS,
+                                    gs.lit ? gs.lit + e * (size_t)s->lit_words : nullptr, d_tile[e].list_len, gs.d_lens + e * LEN_WORDS };
+            // every frame of a group starts from cleared targets; its colour pass leaves the depth on the chip where it may;
+            // passes are numbered frame by frame, as the per-frame path numbers them
+            const uint32_t store = (pass.fs != FS_DEPTH && defer_depth(s)) ? TR_STORE_COLOR : (TR_STORE_DEPTH | TR_STORE_COLOR);
+            fill_pass_args(s, pass, targets, cs, mesh, gs.shared[pi], 1u, store, s->pass_seq + (uint64_t)j * np + pi, false, sa, h_tile[e]);
         }
     }
     if (st != TR_OK) return st;
@@ -1974,35 +1987,12 @@ int run_group(tr_scene *s, const tr_frame_params *p, const tr_scene::InstRef *in
         // kernels read their own entry of the table)
         SetupArgs sa0 = h_setup[(size_t)pi * G];
         sa0.mesh.n_tri = n_poly;
-        const uint32_t n_tiles_pass = sa0.frame.ntx * sa0.frame.nty;
-        EventPair ep = { nullptr, nullptr, K_SETUP, g }, eo = { nullptr, nullptr, K_ORDER, g }, eb = { nullptr, nullptr, K_BIN, g };
-        if (s->profiling) {
-            ep.a = take_event(s); ep.b = take_event(s);
-            eo.a = take_event(s); eo.b = take_event(s);
-            eb.a = take_event(s); eb.b = take_event(s);
-        }
-        int rc = 0;
-        if (tile_fs(s, pass.fs) == (int)FS_LIT) {
-            EventPair el = { nullptr, nullptr, K_LIT, g };
-            if (s->profiling) { el.a = take_event(s); el.b = take_event(s); }
-            rc = launch_lit(pass.fs, sa0, d_setup + (size_t)pi * G, g, chain, el.a, el.b);
-            if (rc) return launch_status(rc, "k_lit");
-            if (s->profiling) s->events.push_back(el);
-        }
         bool xform = false;  // does any frame of the group draw a transform table?
         for (uint32_t j = 0; j < g; j++) xform = xform || h_setup[(size_t)pi * G + j].mesh.inst_xform != 0u;
-        rc = launch_setup(pass.vs, sa0, d_setup + (size_t)pi * G, g, xform, chain_on_main, chain, ep.a, ep.b);
-        if (rc) return launch_status(rc, "k_setup");
-        rc = launch_order(h_tile[(size_t)pi * G], n_tiles_pass, d_tile + (size_t)pi * G, g, chain, eo.a, eo.b);
-        if (rc) return launch_status(rc, "k_order");
-        rc = launch_bin(sa0, d_setup + (size_t)pi * G, g, chain_on_main, chain, eb.a, eb.b);
-        if (rc) return launch_status(rc, "k_bin");
-        if (s->profiling) {
-            s->events.push_back(ep);
-            s->events.push_back(eo);
-            if (n_poly) s->events.push_back(eb);
-            else { s->event_pool.push_back(eb.a); s->event_pool.push_back(eb.b); }
-        }
+        // (no `done`: one record behind all the passes' chains, below)
+        st = launch_chain(s, pass, sa0, h_tile[(size_t)pi * G], d_setup + (size_t)pi * G, d_tile + (size_t)pi * G, g,
+                          sa0.frame.ntx * sa0.frame.nty, n_poly, xform, chain_on_main, chain, nullptr);
+        if (st != TR_OK) return st;
     }
     HIP_TRY(hipEventRecord(gs.ev_setup, chain));
     for (uint32_t j = 0; j < g; j++)
@@ -2037,11 +2027,7 @@ int submit_group_tiles(tr_scene *s, bool wait_for_setup)
         const PassDesc &pass = pd.pass[pi];
         const TileArgs &ta0 = h_tile[(size_t)pi * G];
         const int tile_waves = gs.tile_waves[pi], shared = gs.shared[pi];
-        EventPair ep = { nullptr, nullptr, pass.fs == FS_DEPTH ? K_TILE_DEPTH : K_TILE, g };
-        if (s->profiling) {
-            ep.a = take_event(s);
-            ep.b = take_event(s);
-        }
+        const EventPair ep = timing_pair(s, pass.fs == FS_DEPTH ? K_TILE_DEPTH : K_TILE, g);
         // (the group's "tiles done" event rides on its last tile kernel's own completion signal: a separate record
         // is one more packet between this group's tile kernel and the next one's)
         const bool last = pi + 1u == np;
