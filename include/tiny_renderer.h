@@ -780,6 +780,81 @@ int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out /* may be rg
  * that short-circuits on a logically cleared scene launches nothing), or TR_E_INVALID for a NULL scene. */
 int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap);
 
+/* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
+ * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
+ * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as
+ * tr_scene_read_z_f32 returns it.  A pixel TAKES PART when it lies in the window, the scene's band and the frame; the
+ * window is x0, y0, w, h in output-image coordinates, w == 0 && h == 0 the whole frame, otherwise w, h >= 1 and wholly
+ * inside the frame.
+ *   colour (always), per pixel that takes part, over its stored u8 channels (R, G, B):
+ *       hist[0][R]++   hist[1][G]++   hist[2][B]++
+ *       hist[3][Y]++ with Y = (54 R + 183 G + 19 B + 128) >> 8      (integer BT.709: the weights sum to 256, Y <= 255)
+ *       hist[4][max(R, G, B)]++                                      (the key tr_scene_bloom thresholds)
+ *       n_pixels++
+ *   depth (TR_STATS_DEPTH), per pixel that takes part and is DRAWN -- bits(z) != bits(f32::MIN), as tr_scene_composite
+ *   has it:
+ *       n_drawn++, and the box of drawn pixels grows: box_x0, box_y0 inclusive, box_x1, box_y1 exclusive, output-image
+ *       coordinates; all four 0 when nothing is drawn
+ *       a NaN z counts in n_nan and nowhere else
+ *       any other z enters z_min / z_max under the total order of the key k = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000)
+ *       (-0.0 < +0.0), and zhist[min(255, ((z - z_lo) * z_scale) as u32)]++ -- f32, each operation rounded once, `as u32`
+ *       the truncating, saturating cast of tr_dof_coc (negatives and -inf: bin 0; +inf: bin 255)
+ *       where no drawn pixel that is not NaN exists, z_min and z_max hold f32::MIN
+ *   Without the flag every depth field is zero and no depth is touched.
+ * Everything is a count or an order statistic, so the record does not depend on the order of visits: the device equals
+ * tr_frame_stats_host in every byte.  Every histogram sums to n_pixels, zhist to n_drawn - n_nan. */
+#define TR_STATS_DEPTH 0x1u
+typedef struct tr_stats_params {   /* 32 bytes */
+    uint32_t struct_size, flags;
+    uint32_t x0, y0, w, h;         /* window; w == h == 0: the whole frame */
+    float z_lo, z_scale;           /* depth histogram; read only with TR_STATS_DEPTH: z_lo finite, z_scale finite and > 0 */
+} tr_stats_params;
+typedef struct tr_frame_stats {    /* 6192 bytes */
+    uint32_t hist[5][256];         /* r, g, b, luma, max channel */
+    uint32_t zhist[256];
+    uint32_t n_pixels, n_drawn, n_nan;
+    float z_min, z_max;
+    uint32_t box_x0, box_y0, box_x1, box_y1;
+    uint32_t reserved[3];          /* zeros */
+} tr_frame_stats;
+/* The record of the current frame -- what the getters mean: the last render's, a frame chosen with
+ * tr_scene_select_frame, the caller's buffer after tr_scene_set_frame_buffer_device, a merged, shaded, averaged, blurred,
+ * bloomed or graded frame -- into `out`: sizeof(tr_frame_stats) bytes of device memory, or of memory from tr_host_alloc
+ * (the kernel stores through its mapped address).  Asynchronous and ordered like tr_scene_resolve: frames held back are
+ * submitted, k_stats and k_stats_finish are enqueued on the scene's stream behind everything issued so far, a later render
+ * is ordered behind them, the result is there after tr_scene_sync.  The scene's frame, z, flags and winner words are
+ * never written.  The scene's passes issued so far count as handed on, as after tr_scene_resolve.
+ * Tiles (128 x 16) whose colour fast-clear flag is up are not read: their pixels count in bin 0.  Tiles whose depth
+ * fast-clear flag is up hold no drawn pixel and are not read either.
+ * Without TR_STATS_DEPTH no depth is read: a depth left on the chip (see TR_OPT_STORE_DEPTH) stays there, no depth-only
+ * repeat runs and no z buffer is allocated.  With it the depth is made real first, as by tr_scene_depth_of_field.
+ * A BAND scene (tr_options.band_row0/1) is served: only its band's rows take part, and tr_frame_stats_merge over the
+ * ranks' records gives the whole frame's.  A scene that is logically cleared (tr_scene_clear and nothing rendered since)
+ * gives the record of a black frame in which nothing is drawn, and its pending clear stays pending.
+ * TR_E_INVALID with a tr_last_error text, nothing queued: a NULL scene, NULL params or a NULL `out`, a wrong struct_size,
+ * unknown flags, a window with exactly one of w, h zero or one that reaches outside the frame, with TR_STATS_DEPTH a z_lo
+ * that is not finite or a z_scale that is not finite and positive, ordinary host memory as `out`, a pinned buffer that is
+ * too small. */
+int tr_scene_frame_stats(tr_scene *s, const tr_stats_params *p, void *out);
+/* The same into any host memory: waits for the scene first (an overflowed frame is rendered again before it is read),
+ * runs into a buffer of the library's, copies out and returns the frame's sticky status, like tr_scene_get_resolved. */
+int tr_scene_get_frame_stats(tr_scene *s, const tr_stats_params *p, tr_frame_stats *host);
+/* The rule above on the host (no GPU needed), by the very inline functions the kernels call.  rgb: 3 * width * height
+ * bytes, row 0 = top; z: width * height floats, index x + y * width with y up (tr_scene_read_z_f32), read only with
+ * TR_STATS_DEPTH and may be NULL without it.  The same checks of the parameters against width and height. */
+int tr_frame_stats_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z /* or NULL without the flag */,
+                        const tr_stats_params *p, tr_frame_stats *out);
+/* The record of the union of two DISJOINT pixel sets from their two records, into dst: counts add, z_min / z_max merge
+ * under the key's order (a side without a drawn non-NaN pixel does not take part), the boxes unite (a side with nothing
+ * drawn does not take part).  Both records come from calls with the same z_lo and z_scale.  Host only. */
+int tr_frame_stats_merge(tr_frame_stats *dst, const tr_frame_stats *src);   /* host: the record of the union of two disjoint pixel sets */
+/* Diagnostic, as tr_scene_debug_grade_grid: k_stats' workgroups are persistent -- at most one a compute unit and never
+ * more than there are tiles.  `cap` is stored on the scene: every later k_stats launch of that scene starts
+ * min(cap, that number) workgroups, each of which then walks more tiles, and k_stats_finish sums that many partial
+ * records; not a byte of the result changes.  cap == 0: no cap, the default.  Returns the number of workgroups of the
+ * scene's most recent k_stats launch (0: there has been none), or TR_E_INVALID for a NULL scene. */
+int tr_scene_debug_stats_grid(tr_scene *s, uint32_t cap);                   /* as tr_scene_debug_grade_grid */
+
 /* Dynamic textures (nothing of the kind upstream, whose four images are moved into Scene::new and never change): one of a
  * scene's images -- `which` = 0..3 in tr_scene_create's order: texture, normal_map, normal_map_tangent, specular_map --
  * replaced on the device, from host memory, from device memory or from another scene's (or the scene's own) current

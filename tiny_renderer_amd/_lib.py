@@ -152,6 +152,11 @@ SYMBOLS = {
     "tr_scene_get_graded": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_grade_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "tr_scene_debug_grade_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_frame_stats_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "tr_scene_debug_stats_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tr_scene_set_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ImageRgb8)]),
     "tr_scene_set_texture_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "tr_scene_set_texture_from_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -92,10 +92,32 @@ def main(argv=None):
                          "unit domain) on the GPU (Scene.grade; after --bloom, before --ssaa resolves)")
     ap.add_argument("--gamma", type=float, default=None, metavar="G",
                     help="colour grading by a 33^3 table of v^(1/G), e.g. 2.2 (Scene.grade; after --bloom, before --ssaa resolves)")
+    ap.add_argument("--auto-levels", default=None, metavar="LOW,HIGH",
+                    help="colour grading by a table made from the picture itself: its luma percentiles LOW and HIGH (e.g. 0.01,0.99), "
+                         "found on the GPU (Scene.get_frame_stats), stretched to black and white (lut_auto_levels; in the place of "
+                         "--lut / --gamma)")
+    ap.add_argument("--dof-autofocus", action="store_true",
+                    help="depth of field focused on the median depth of what is drawn in the central quarter of the picture "
+                         "(depth_median; in the place of --dof-focus Z, with --dof-scale S)")
+    ap.add_argument("--stats", action="store_true",
+                    help="print the finished picture's statistics (Scene.get_frame_stats): pixels, drawn pixels, depth range, the "
+                         "box of what is drawn and the luma bins at 1, 50 and 99 %%")
     args = ap.parse_args(argv)
     args.grade_lut = None
-    if args.lut is not None and args.gamma is not None:
-        ap.error("--lut and --gamma are two tables for one stage: give one")
+    args.levels = None
+    if sum(v is not None for v in (args.lut, args.gamma, args.auto_levels)) > 1:
+        ap.error("--lut, --gamma and --auto-levels are tables for one stage: give one")
+    if args.auto_levels is not None or args.stats or args.dof_autofocus:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--auto-levels, --dof-autofocus and --stats work on the frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+    if args.auto_levels is not None:
+        try:
+            low, high = (float(v) for v in args.auto_levels.split(","))
+            if not 0.0 <= low < high <= 1.0:
+                raise ValueError
+        except ValueError:
+            ap.error("--auto-levels takes LOW,HIGH with 0 <= LOW < HIGH <= 1")
+        args.levels = (low, high)
     if args.lut is not None or args.gamma is not None:
         if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
             ap.error("--lut and --gamma work on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
@@ -122,10 +144,21 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
     args.dof = None
-    if (args.dof_focus is None) != (args.dof_scale is None):
+    if args.dof_autofocus and args.dof_focus is not None:
+        ap.error("--dof-autofocus finds the focus that --dof-focus Z states: give one")
+    if args.dof_autofocus and args.dof_scale is None:
+        ap.error("--dof-autofocus goes with --dof-scale S")
+    if not args.dof_autofocus and (args.dof_focus is None) != (args.dof_scale is None):
         ap.error("--dof-focus Z and --dof-scale S go together")
-    if args.dof_focus is None and (args.dof_radius != 4 or args.dof_range != 0.0 or args.dof_background != 0 or args.dof_show_coc):
+    if args.dof_focus is None and not args.dof_autofocus and (args.dof_radius != 4 or args.dof_range != 0.0 or args.dof_background != 0 or args.dof_show_coc):
         ap.error("--dof-radius, --dof-range, --dof-background and --dof-show-coc go with --dof-focus Z --dof-scale S")
+    if args.dof_autofocus:
+        from .scene import dof_params
+        try:   # (the focus is found at run time; everything else is checked now)
+            dof_params(0.0, args.dof_scale, max_radius=args.dof_radius, background_radius=args.dof_background,
+                       flags=1 if args.dof_show_coc else 0, range=args.dof_range)
+        except ValueError as e:
+            ap.error(str(e))
     if args.dof_focus is not None:
         if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
             ap.error("--dof-focus blurs the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
@@ -401,13 +434,30 @@ def _run(args, T, scene, sharded, rank, say):
         scene.accumulate_in_place(args.shutter)
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
+    if args.dof_autofocus:
+        # the median depth of what is drawn in the central quarter; a picture with nothing there stays sharp
+        w, h = scene.width, scene.height
+        focus = T.depth_median(scene, (w // 4, h // 4, max(1, w // 2), max(1, h // 2)))
+        if focus is None:
+            say("autofocus --- nothing drawn in the central quarter: no depth of field")
+        else:
+            say("autofocus --- z %r" % focus)
+            args.dof = T.dof_params(focus, args.dof_scale, max_radius=args.dof_radius, background_radius=args.dof_background,
+                                    flags=1 if args.dof_show_coc else 0, range=args.dof_range)
     if args.dof is not None:
         scene.depth_of_field(args.dof)
     if args.bloom_params is not None:
         scene.bloom(args.bloom_params)
+    if args.levels is not None:
+        args.grade_lut = T.lut_auto_levels(scene.get_frame_stats(), args.levels[0], args.levels[1])
     if args.grade_lut is not None:
         scene.set_lut(args.grade_lut)
         scene.grade()
+    if args.stats:
+        st = scene.get_frame_stats(depth=True)
+        say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
+            % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
+               T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
     img = _view(scene, args.view, args.ssaa)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238

@@ -15,6 +15,7 @@
 #include "tr_pack.h"
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
+#include "tr_stats.h"
 #include "tr_types.h"
 
 namespace tr {
@@ -98,6 +99,15 @@ int launch_bloom(const BloomArgs &a, hipStream_t st);
 // a.lower_clean: null, or a.fbclean (in place, c0 != 0): the flags of the tiles stored as c0 come down.
 // cap: 0, or the most workgroups to start (tr_scene_debug_grade_grid); *grid: the number started (0: nothing launched).
 int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
+// Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
+// frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
+// k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped
+// host memory).  The scene's tile grid, a band's included; nothing of the scene is written.  a.partials holds at least
+// stats_max_grid(a.frame) slots.  cap: 0, or the most workgroups to start (tr_scene_debug_stats_grid); *grid: the number
+// started.
+int launch_stats(const StatsArgs &a, uint32_t *out, hipStream_t st, uint32_t cap, uint32_t *grid);
+// The most workgroups a k_stats launch over `frame` starts on the current device (0: the device cannot be asked).
+uint32_t stats_max_grid(const DevFrame &frame);
 // Dynamic textures: image a.src into the plain array a.texel and the owned words of the texel set a.set (words per texel:
 // 1 or 4; a.set null: the plain array alone) by the rule of tr_pack.h, through the source's colour-clean flags when it
 // is a frame: k_pack_texels.  The caller orders the launch behind whatever reads the arrays and produced the source.

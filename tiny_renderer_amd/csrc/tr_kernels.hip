@@ -36,6 +36,7 @@
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_grade.h"
+#include "tr_stats.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
 #include "tr_pack.h"
@@ -2808,6 +2809,245 @@ __global__ __launch_bounds__(GRADE_THREADS) void k_grade(GradeArgs a)
     }
 }
 
+// Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
+// partial record.  The project's one reduction, in two launches:
+//   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
+//     caps it).  A workgroup is four TEAMS of 256 lanes, four waves each; team number v = 4 * block + team of V = 4 * G
+//     walks the tiles v, v + V, v + 2 V, ... of the scene's 128 x 16 tile grid (a band scene's: its band's) under k_grade's
+//     permutation of a row's columns, and owns a tile the way a k_grade workgroup does: a unit is four pixels of a row,
+//     twelve bytes, a lane takes two units eight rows apart.  There is no barrier inside the walk, so everything that
+//     steers it need only be wave-uniform.
+//       * a tile that does not meet the window is left after the comparison of its rectangle with the window's;
+//       * the flags are read before any pixel.  A tile whose colour-clean flag is up holds zeros: the lane that keeps
+//         the team's count adds the area of tile and window to `flat`, which goes to bin 0 of the five histograms at the
+//         end; nothing is loaded.  A tile whose z-clean flag is up holds no drawn pixel: no depth is loaded.  A logically
+//         cleared scene (a.cleared) is all such tiles.  The two flags are looked at independently;
+//       * n_pixels is the sum of those areas whatever the path;
+//       * WORDS (width % 4 == 0, fb 4-byte and z 16-byte aligned: the launcher checks): a unit's colour is three aligned
+//         words, its depth one 16-byte load; otherwise guarded bytes and floats;
+//       * counts go to ONE partial record in LDS (6192 bytes) by LDS atomics -- no global atomic anywhere.  Rendered
+//         frames are flat: a drawn tile is mostly backdrop, a graded frame may be one colour, and 64 lanes adding to one
+//         LDS word are served one after the other.  So every add is AGGREGATED over the wave (stats_add_*): the value of
+//         the first lane that has one is broadcast, the lanes that hold the same value are counted by a ballot, and that
+//         first lane alone adds the count; only lanes with another value add for themselves.  A wave of one colour costs
+//         five adds of one lane.  Copies of the histograms per wave would not help: LDS serves one instruction of a CU at
+//         a time whichever wave it comes from, and what is slow is the lanes of ONE instruction meeting on a word;
+//       * a lane keeps its depth scalars (drawn, NaN, keyed min / max, box) in registers, a wave folds them by shuffles
+//         at the end and its first lane adds them to the partial;
+//       * behind a barrier the 1024 lanes store the partial to the workgroup's slot as 16-byte pieces, plain stores.
+//   k_stats_finish -- 7 workgroups of 256 lanes, a lane a word: it sums (maxes) that word over the G slots, the last
+//     workgroup turns the keyed words back (stats_publish), and every lane stores its word of the record to `out`, device
+//     memory or the device address of page-locked host memory.  The launch boundary is the only ordering between the two.
+// The frame, z, winner words and every flag are read only.  No inline assembly, no scratch.
+constexpr int STATS_THREADS = 1024, STATS_TEAM = 256, STATS_TEAMS = STATS_THREADS / STATS_TEAM;
+constexpr int STATS_FINISH_THREADS = 256;
+constexpr uint32_t STATS_FINISH_BLOCKS = (STATS_WORDS + (uint32_t)STATS_FINISH_THREADS - 1u) / (uint32_t)STATS_FINISH_THREADS;
+static_assert((STATS_FINISH_BLOCKS - 1u) * (uint32_t)STATS_FINISH_THREADS == SW_N_PIXELS && STATS_TAIL <= 64u,
+              "the last finishing workgroup holds exactly the tail, in its first wave");
+
+// `count` into s[bin] for every lane with act set, aggregated: the wave's first such lane adds for all that share its bin.
+__device__ __forceinline__ void stats_add_bin(uint32_t *s, bool act, uint32_t bin, uint32_t lane)
+{
+    const unsigned long long m = __ballot(act);
+    if (m == 0ull) return;  // (wave-uniform)
+    const uint32_t first = (uint32_t)__ffsll((long long)m) - 1u;
+    const uint32_t v0 = (uint32_t)__builtin_amdgcn_readlane((int)bin, (int)first);
+    const bool same = act && bin == v0;
+    const uint32_t n = (uint32_t)__popcll(__ballot(same));
+    if (lane == first) atomicAdd(&s[v0], n);
+    else if (act && !same) atomicAdd(&s[bin], 1u);
+}
+
+// A packed pixel (r lowest) into the five colour histograms, aggregated likewise on the whole pixel.
+__device__ __forceinline__ void stats_add_colour(uint32_t *s, bool act, uint32_t px, uint32_t lane)
+{
+    const unsigned long long m = __ballot(act);
+    if (m == 0ull) return;  // (wave-uniform)
+    const uint32_t first = (uint32_t)__ffsll((long long)m) - 1u;
+    const uint32_t v0 = (uint32_t)__builtin_amdgcn_readlane((int)px, (int)first);
+    const bool same = act && px == v0;
+    const uint32_t n = (uint32_t)__popcll(__ballot(same));
+    if (lane == first || (act && !same)) {
+        const uint32_t add = lane == first ? n : 1u;
+        const uint32_t r = px & 0xFFu, g = (px >> 8) & 0xFFu, b = (px >> 16) & 0xFFu;
+        atomicAdd(&s[0u * STATS_BINS + r], add);
+        atomicAdd(&s[1u * STATS_BINS + g], add);
+        atomicAdd(&s[2u * STATS_BINS + b], add);
+        atomicAdd(&s[3u * STATS_BINS + stats_luma(r, g, b)], add);
+        atomicAdd(&s[4u * STATS_BINS + stats_max3(r, g, b)], add);
+    }
+}
+
+template <bool DEPTH, bool WORDS>
+__global__ __launch_bounds__(STATS_THREADS) void k_stats(StatsArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H == 16 && STATS_TEAM == 256, "32 units to a row of a tile, two rounds of eight rows");
+    __shared__ __align__(16) uint32_t s_rec[STATS_WORDS];
+    for (uint32_t i = threadIdx.x; i < STATS_WORDS; i += STATS_THREADS) s_rec[i] = 0u;
+    __syncthreads();
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t ntx = a.frame.ntx, n_tiles = a.frame.ntx * a.frame.nty;
+    const uint32_t team = threadIdx.x / (uint32_t)STATS_TEAM, tid = threadIdx.x % (uint32_t)STATS_TEAM, lane = threadIdx.x % 64u;
+    const uint32_t V = gridDim.x * (uint32_t)STATS_TEAMS;
+    const StatsWindow win = a.rule.win;
+    const bool cleared = a.cleared != 0u;
+    uint32_t flat = 0u, n_pixels = 0u;  // (the same in every lane of a team; its lane 0 adds them)
+    uint32_t n_drawn = 0u, n_nan = 0u, zmax = 0u, zminc = 0u, bx0c = 0u, by0c = 0u, bx1 = 0u, by1 = 0u;
+    for (uint32_t k = blockIdx.x * (uint32_t)STATS_TEAMS + team; k < n_tiles; k += V) {
+        const uint32_t tyl = k / ntx, tx = (k % ntx + 5u * tyl + 13u * (tyl * ntx / V)) % ntx;
+        const uint32_t t = tyl * ntx + tx;
+        const int32_t tx0 = (int32_t)tx * TILE_W, ty0 = (a.frame.ty_base + (int32_t)tyl) * TILE_H;
+        // the tile's part of the window (which is cut to the frame and the band already)
+        const int32_t cx0 = max(win.x0, tx0), cx1 = min(win.x1, tx0 + TILE_W), cy0 = max(win.y0, ty0), cy1 = min(win.y1, ty0 + TILE_H);
+        if (cx0 >= cx1 || cy0 >= cy1) continue;
+        const uint32_t area = (uint32_t)(cx1 - cx0) * (uint32_t)(cy1 - cy0);
+        const bool c_clean = cleared || (a.fbclean != nullptr && a.fbclean[t] != 0u);
+        const bool z_clean = !DEPTH || cleared || a.zclean[t] != 0u;
+        n_pixels += area;
+        if (c_clean) flat += area;
+        if (c_clean && z_clean) continue;
+        const int32_t x = tx0 + 4 * (int32_t)(tid % 32u);
+        const int32_t y_first = ty0 + (int32_t)(tid / 32u);
+        bool in_x[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) in_x[i] = x + i >= cx0 && x + i < cx1;
+        bool row_in[2];
+        uint32_t px[2][4];
+        float zz[2][4];
+        // both units' loads first, then the counting
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int32_t y = y_first + 8 * h;
+            // (a unit of the WORDS form lies wholly inside the frame or wholly outside: width % 4 == 0)
+            row_in[h] = y >= cy0 && y < cy1 && (WORDS ? x < W : true) && (in_x[0] || in_x[1] || in_x[2] || in_x[3]);
+#pragma unroll
+            for (int i = 0; i < 4; i++) px[h][i] = 0u, zz[h][i] = 0.0f;
+            if (!row_in[h]) continue;
+            if (!c_clean) {
+                const uint8_t *q = a.fb + ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+                if (WORDS) {
+                    const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                    const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                    px[h][0] = w0 & 0xFFFFFFu;
+                    px[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                    px[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                    px[h][3] = w2 >> 8;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (in_x[i]) px[h][i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+                }
+            }
+            if (DEPTH && !z_clean) {
+                const float *q = a.z + (size_t)y * (size_t)W + (size_t)x;
+                if (WORDS) {
+                    const float4 v = *reinterpret_cast<const float4 *>(q);
+                    zz[h][0] = v.x, zz[h][1] = v.y, zz[h][2] = v.z, zz[h][3] = v.w;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (in_x[i]) zz[h][i] = q[i];
+                }
+            }
+        }
+        if (!c_clean) {
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) stats_add_colour(s_rec, row_in[h] && in_x[i], px[h][i], lane);
+        }
+        if (DEPTH && !z_clean) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const uint32_t row = (uint32_t)(H - 1 - (y_first + 8 * h));
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t zb = f32_bits(zz[h][i]);
+                    const bool drawn = row_in[h] && in_x[i] && zb != TR_F32_MIN_BITS;
+                    const bool nan = stats_is_nan(zb);
+                    if (drawn) {
+                        const uint32_t xi = (uint32_t)(x + i);
+                        n_drawn += 1u;
+                        bx0c = max(bx0c, ~xi), by0c = max(by0c, ~row), bx1 = max(bx1, xi + 1u), by1 = max(by1, row + 1u);
+                        if (nan) {
+                            n_nan += 1u;
+                        } else {
+                            const uint32_t key = stats_zkey(zb);
+                            zmax = max(zmax, key), zminc = max(zminc, ~key);
+                        }
+                    }
+                    stats_add_bin(s_rec + SW_ZHIST, drawn && !nan, stats_zbin(zz[h][i], a.rule.z_lo, a.rule.z_scale), lane);
+                }
+            }
+        }
+    }
+    if (tid == 0u) {
+        if (n_pixels) atomicAdd(&s_rec[SW_N_PIXELS], n_pixels);
+        if (flat) {
+#pragma unroll
+            for (uint32_t c = 0; c < STATS_HISTS; c++) atomicAdd(&s_rec[c * STATS_BINS], flat);
+        }
+    }
+    if (DEPTH) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            n_drawn += (uint32_t)__shfl_xor((int)n_drawn, d, 64);
+            n_nan += (uint32_t)__shfl_xor((int)n_nan, d, 64);
+            zmax = max(zmax, (uint32_t)__shfl_xor((int)zmax, d, 64));
+            zminc = max(zminc, (uint32_t)__shfl_xor((int)zminc, d, 64));
+            bx0c = max(bx0c, (uint32_t)__shfl_xor((int)bx0c, d, 64));
+            by0c = max(by0c, (uint32_t)__shfl_xor((int)by0c, d, 64));
+            bx1 = max(bx1, (uint32_t)__shfl_xor((int)bx1, d, 64));
+            by1 = max(by1, (uint32_t)__shfl_xor((int)by1, d, 64));
+        }
+        if (lane == 0u && n_drawn != 0u) {
+            atomicAdd(&s_rec[SW_N_DRAWN], n_drawn);
+            atomicAdd(&s_rec[SW_N_NAN], n_nan);
+            atomicMax(&s_rec[SW_ZMAX], zmax);
+            atomicMax(&s_rec[SW_ZMINC], zminc);
+            atomicMax(&s_rec[SW_BX0C], bx0c);
+            atomicMax(&s_rec[SW_BY0C], by0c);
+            atomicMax(&s_rec[SW_BX1], bx1);
+            atomicMax(&s_rec[SW_BY1], by1);
+        }
+    }
+    __syncthreads();
+    uint4 *slot = reinterpret_cast<uint4 *>(a.partials + (size_t)blockIdx.x * STATS_WORDS);
+    for (uint32_t i = threadIdx.x; i < STATS_WORDS / 4u; i += STATS_THREADS) slot[i] = reinterpret_cast<const uint4 *>(s_rec)[i];
+}
+
+// partials: n_slots slots of STATS_WORDS words (k_stats' grid); depth: TR_STATS_DEPTH was given; out: STATS_WORDS words.
+__global__ __launch_bounds__(STATS_FINISH_THREADS) void k_stats_finish(const uint32_t *partials, uint32_t n_slots, uint32_t depth, uint32_t *out)
+{
+    __shared__ uint32_t s_tail[64];
+    const uint32_t i = blockIdx.x * (uint32_t)STATS_FINISH_THREADS + threadIdx.x;
+    uint32_t v = 0u;
+    if (i < STATS_WORDS) {
+        const bool sum = i < STATS_SUMS;
+        for (uint32_t g = 0; g < n_slots; g++) {
+            const uint32_t p = partials[(size_t)g * STATS_WORDS + i];
+            v = sum ? v + p : max(v, p);
+        }
+    }
+    if (blockIdx.x != STATS_FINISH_BLOCKS - 1u) {
+        out[i] = v;  // (i < STATS_SUMS <= STATS_WORDS here)
+        return;
+    }
+    // words STATS_SUMS - 3 .. STATS_WORDS - 1: the counts stats_publish reads, the maxima and the reserved words
+    constexpr uint32_t first = (STATS_FINISH_BLOCKS - 1u) * (uint32_t)STATS_FINISH_THREADS;
+    static_assert(first == SW_N_PIXELS, "the last workgroup starts at n_pixels");
+    if (threadIdx.x < STATS_TAIL) s_tail[threadIdx.x] = v;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        StatsTail t;
+#pragma unroll
+        for (uint32_t j = 0; j < STATS_TAIL; j++) t.w[j] = s_tail[j];
+        stats_publish(t, depth != 0u);
+#pragma unroll
+        for (uint32_t j = 0; j < STATS_TAIL; j++) out[first + j] = t.w[j];
+    }
+}
+
 // Dynamic textures (tr_scene_set_texture*): image `which` of a scene replaced by a w x h image of packed rgb8 rows, in
 // the plain array and in the texel set together; tr_pack.h has the rule (pack_quad, shared with the host).  The grid is
 // that of a frame of w x h pixels -- the image may BE one (tr_scene_set_texture_from_frame): a workgroup of 256 lanes
@@ -3572,6 +3812,46 @@ int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *gri
         hipLaunchKernelGGL((k_grade<false, true>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_grade<false, false>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+uint32_t stats_max_grid(const DevFrame &frame)
+{
+    const uint32_t n_tiles = frame.ntx * frame.nty;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        return 0u;
+    // one workgroup of 1024 lanes a CU, and no more workgroups than tiles
+    return std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)cus, n_tiles));
+}
+
+int launch_stats(const StatsArgs &a, uint32_t *out, hipStream_t st, uint32_t cap, uint32_t *grid_out)
+{
+    *grid_out = 0u;
+    if (!a.fb || !a.partials || !out || (uintptr_t)a.partials % 16u != 0u || (uintptr_t)out % 4u != 0u) return (int)hipErrorInvalidValue;
+    const bool depth = a.rule.depth != 0u;
+    if (depth && a.cleared == 0u && (!a.z || !a.zclean)) return (int)hipErrorInvalidValue;
+    // the window lies inside the frame and the band (an empty one is served: every workgroup stores zeros)
+    const StatsWindow &w = a.rule.win;
+    if (w.x0 < 0 || w.x1 > (int32_t)a.frame.width || w.y0 < a.frame.band_y0 || w.y1 > a.frame.band_y1) return (int)hipErrorInvalidValue;
+    if (a.frame.band_y0 < 0 || a.frame.band_y1 > (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    uint32_t grid = stats_max_grid(a.frame);
+    if (grid == 0u) return (int)hipErrorInvalidDevice;
+    if (cap != 0u) grid = std::min<uint32_t>(grid, cap);  // (the diagnostic: fewer workgroups, more rounds each)
+    *grid_out = grid;
+    // whole words: every unit of four pixels is three aligned words of colour and one aligned 16-byte piece of depth
+    const bool words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u && (!depth || a.cleared != 0u || (uintptr_t)a.z % 16u == 0u);
+    if (depth && words)
+        hipLaunchKernelGGL((k_stats<true, true>), dim3(grid), dim3(STATS_THREADS), 0, st, a);
+    else if (depth)
+        hipLaunchKernelGGL((k_stats<true, false>), dim3(grid), dim3(STATS_THREADS), 0, st, a);
+    else if (words)
+        hipLaunchKernelGGL((k_stats<false, true>), dim3(grid), dim3(STATS_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_stats<false, false>), dim3(grid), dim3(STATS_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_stats_finish, dim3(STATS_FINISH_BLOCKS), dim3(STATS_FINISH_THREADS), 0, st, (const uint32_t *)a.partials, grid, a.rule.depth, out);
     TR_LAUNCH_CHECK();
     return 0;
 }

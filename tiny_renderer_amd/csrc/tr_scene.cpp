@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -405,6 +405,10 @@ struct tr_scene {
     uint32_t lut_n = 0, lut_c0 = 0;
     // tr_scene_debug_grade_grid: the most workgroups a k_grade launch may start (0: no cap) and what the last one started
     uint32_t grade_cap = 0, grade_grid = 0;
+    // tr_scene_frame_stats: the slots k_stats' workgroups store their partial records to (stats_slots of them, allocated
+    // at the first call), and tr_scene_debug_stats_grid's cap and last grid, as for k_grade
+    uint32_t *d_stats_partials = nullptr;
+    uint32_t stats_slots = 0, stats_cap = 0, stats_grid = 0;
     uint32_t *d_winner = nullptr;
     // Fast depth clear: one word per colour-pass tile, non-zero = "every z of the tile is f32::MIN,
     // memory not written".  Raised by the tile kernel for the empty tiles of a cleared frame (and by
@@ -2516,6 +2520,7 @@ void destroy(tr_scene *s)
     dev_free(s->d_dof_fb);
     dev_free(s->d_dof_clean);
     dev_free(s->d_lut);
+    dev_free(s->d_stats_partials);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
     for (tr_scene::HostFlags &f : s->host_flags) dev_free(f.clean);
@@ -4582,6 +4587,139 @@ int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_grade_grid: null scene");
     s->grade_cap = cap;
     return (int)s->grade_grid;
+}
+
+namespace {
+
+static_assert(TR_STATS_DEPTH == STATS_DEPTH && sizeof(tr_stats_params) == 32 && sizeof(tr_frame_stats) == sizeof(StatsRecord) &&
+                  offsetof(tr_frame_stats, zhist) == offsetof(StatsRecord, zhist) && offsetof(tr_frame_stats, n_pixels) == offsetof(StatsRecord, n_pixels) &&
+                  offsetof(tr_frame_stats, z_min) == offsetof(StatsRecord, z_min) && offsetof(tr_frame_stats, box_x0) == offsetof(StatsRecord, box_x0) &&
+                  offsetof(tr_frame_stats, reserved) == offsetof(StatsRecord, reserved),
+              "tr_stats.h restates the header");
+
+// tr_stats_params as every entry point accepts them for a frame of width x height (`who` names the entry point in the
+// error text).
+int check_stats_params(const tr_stats_params *p, uint32_t width, uint32_t height, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_stats_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_stats_params)");
+    if (p->flags & ~TR_STATS_DEPTH) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if ((p->w == 0u) != (p->h == 0u)) return tr::fail(TR_E_INVALID, w + ": a window has w and h >= 1, or both 0 for the whole frame");
+    if (p->w != 0u && ((uint64_t)p->x0 + p->w > width || (uint64_t)p->y0 + p->h > height))
+        return tr::fail(TR_E_INVALID, w + ": the window reaches outside the frame");
+    if (p->flags & TR_STATS_DEPTH) {
+        if (!std::isfinite(p->z_lo)) return tr::fail(TR_E_INVALID, w + ": z_lo must be finite");
+        if (!std::isfinite(p->z_scale) || !(p->z_scale > 0.0f)) return tr::fail(TR_E_INVALID, w + ": z_scale must be finite and > 0");
+    }
+    return TR_OK;
+}
+
+StatsRule stats_rule(const tr_stats_params *p, uint32_t width, uint32_t height, int32_t band_y0, int32_t band_y1)
+{
+    StatsRule r;
+    r.win = stats_window(width, height, p->x0, p->y0, p->w, p->h, band_y0, band_y1);
+    r.depth = (p->flags & TR_STATS_DEPTH) ? 1u : 0u;
+    r.z_lo = r.depth ? p->z_lo : 0.0f;
+    r.z_scale = r.depth ? p->z_scale : 1.0f;
+    return r;
+}
+
+// Enqueues the statistics of the current frame into `out_device` behind everything issued so far.  Nothing of the scene
+// is written: a logically cleared scene stays so (the kernel is told, and treats every tile as flagged).  Without
+// TR_STATS_DEPTH no depth is read and a depth left on the chip stays there; with it the depth is made real first.
+int enqueue_stats(tr_scene *s, const tr_stats_params *p, uint8_t *out_device)
+{
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    const bool depth = (p->flags & TR_STATS_DEPTH) != 0u;
+    const bool cleared = s->z_fb_cleared;
+    if (depth && !cleared && (st = depth_in_memory(s)) != TR_OK) return st;
+    if (!s->d_stats_partials) {
+        const uint32_t slots = stats_max_grid(s->frame);
+        if (slots == 0u) return tr::fail(TR_E_HIP, "tr_scene_frame_stats: the device does not tell its compute units");
+        if ((st = dev_alloc(&s->d_stats_partials, (size_t)slots * STATS_WORDS)) != TR_OK) return st;
+        s->stats_slots = slots;
+    }
+    StatsArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.z = depth && !cleared ? s->d_z : nullptr;
+    a.zclean = depth && !cleared ? s->d_zclean : nullptr;
+    a.partials = s->d_stats_partials;
+    a.frame = s->frame;
+    a.rule = stats_rule(p, s->width, s->height, s->frame.band_y0, s->frame.band_y1);
+    a.cleared = cleared ? 1u : 0u;
+    {
+        Timed t(s, K_STATS);
+        // (never more workgroups than slots: the device's count of compute units does not change)
+        const uint32_t cap = s->stats_cap ? std::min(s->stats_cap, s->stats_slots) : s->stats_slots;
+        int rc = launch_stats(a, (uint32_t *)out_device, s->stream, cap, &s->stats_grid);
+        if (rc) return launch_status(rc, "k_stats");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+int check_stats_scene(const tr_scene *s)
+{
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_frame_stats(tr_scene *s, const tr_stats_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_frame_stats: null scene");
+    int st = check_stats_params(p, s->width, s->height, "tr_scene_frame_stats");
+    if (st != TR_OK) return st;
+    if (!out) return tr::fail(TR_E_INVALID, "tr_scene_frame_stats: null argument");
+    if ((st = check_stats_scene(s)) != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = classify_out(out, sizeof(tr_frame_stats), "tr_scene_frame_stats", "tr_scene_get_frame_stats", "record", &target);
+    if (st == TR_OK && (uintptr_t)target % 4u != 0u) st = tr::fail(TR_E_INVALID, "tr_scene_frame_stats: `out` is not aligned to 4 bytes");
+    if (st == TR_OK) st = enqueue_stats(s, p, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_frame_stats(tr_scene *s, const tr_stats_params *p, tr_frame_stats *host)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_frame_stats: null scene");
+    int st = check_stats_params(p, s->width, s->height, "tr_scene_get_frame_stats");
+    if (st != TR_OK) return st;
+    if (!host) return tr::fail(TR_E_INVALID, "tr_scene_get_frame_stats: null argument");
+    if ((st = check_stats_scene(s)) != TR_OK) return st;
+    return get_stage(s, (uint8_t *)host, sizeof(tr_frame_stats), nullptr, [&](uint8_t *o) { return enqueue_stats(s, p, o); });
+}
+
+// The rule of tr_stats.h over a caller's arrays, on the host.  Needs no GPU.
+int tr_frame_stats_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_stats_params *p, tr_frame_stats *out)
+{
+    int st = check_stats_params(p, width, height, "tr_frame_stats_host");
+    if (st != TR_OK) return st;
+    if (!out) return tr::fail(TR_E_INVALID, "tr_frame_stats_host: null argument");
+    const bool empty = width == 0u || height == 0u;
+    if (!empty && (!rgb || ((p->flags & TR_STATS_DEPTH) && !z))) return tr::fail(TR_E_INVALID, "tr_frame_stats_host: null argument");
+    stats_host(width, height, rgb, z, stats_rule(p, width, height, 0, (int32_t)height), reinterpret_cast<StatsRecord *>(out));
+    return TR_OK;
+}
+
+int tr_frame_stats_merge(tr_frame_stats *dst, const tr_frame_stats *src)
+{
+    if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_frame_stats_merge: null argument");
+    if (dst == src) return tr::fail(TR_E_INVALID, "tr_frame_stats_merge: dst is src (the two pixel sets are disjoint)");
+    stats_merge(reinterpret_cast<StatsRecord *>(dst), reinterpret_cast<const StatsRecord *>(src));
+    return TR_OK;
+}
+
+int tr_scene_debug_stats_grid(tr_scene *s, uint32_t cap)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_stats_grid: null scene");
+    s->stats_cap = cap;
+    return (int)s->stats_grid;
 }
 
 int tr_scene_band_tiles(tr_scene *s, const void *frame_buffer_device, tr_band_tiles *out)

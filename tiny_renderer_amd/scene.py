@@ -467,6 +467,171 @@ def load_cube(path):
     return np.floor(np.clip(vals, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
 
 
+STATS_DEPTH = 1   # (TR_STATS_DEPTH)
+
+
+class StatsParams(C.Structure):
+    """tr_stats_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("x0", C.c_uint32), ("y0", C.c_uint32), ("w", C.c_uint32),
+                ("h", C.c_uint32), ("z_lo", C.c_float), ("z_scale", C.c_float)]
+
+
+class FrameStatsRecord(C.Structure):
+    """tr_frame_stats"""
+    _fields_ = [("hist", (C.c_uint32 * 256) * 5), ("zhist", C.c_uint32 * 256), ("n_pixels", C.c_uint32), ("n_drawn", C.c_uint32),
+                ("n_nan", C.c_uint32), ("z_min", C.c_float), ("z_max", C.c_float), ("box_x0", C.c_uint32), ("box_y0", C.c_uint32),
+                ("box_x1", C.c_uint32), ("box_y1", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+FRAME_STATS_BYTES = C.sizeof(FrameStatsRecord)   # 6192
+
+
+def stats_params(window=None, depth=False, z_lo=0.0, z_scale=1.0):
+    """tr_stats_params for Scene.frame_stats / Scene.get_frame_stats / frame_stats_host.  window: None (the whole frame) or
+    (x0, y0, w, h) in output-image coordinates with w, h >= 1; depth: also coverage, the depth range, the box of drawn
+    pixels and a depth histogram whose bin is min(255, ((z - z_lo) * z_scale) as u32).  ValueError for what the library
+    would refuse (include/tiny_renderer.h) as far as it can be told without the frame's size."""
+    x0 = y0 = w = h = 0
+    if window is not None:
+        try:
+            x0, y0, w, h = window
+        except (TypeError, ValueError):
+            raise ValueError("frame statistics: window must be None or (x0, y0, w, h)")
+        for v in (x0, y0, w, h):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError("frame statistics: window must hold four integers 0..2^32 - 1")
+        if w < 1 or h < 1:
+            raise ValueError("frame statistics: a window has w and h >= 1 (None: the whole frame)")
+    z_lo, z_scale = float(z_lo), float(z_scale)
+    if depth:
+        with np.errstate(over="ignore"):   # (as f32: what the library gets)
+            l32, s32 = np.float32(z_lo), np.float32(z_scale)
+        if not np.isfinite(l32):
+            raise ValueError("frame statistics: z_lo must be finite")
+        if not np.isfinite(s32) or not s32 > 0.0:
+            raise ValueError("frame statistics: z_scale must be finite and > 0")
+    return StatsParams(C.sizeof(StatsParams), STATS_DEPTH if depth else 0, int(x0), int(y0), int(w), int(h), z_lo, z_scale)
+
+
+class FrameStats:
+    """A tr_frame_stats record as numpy arrays and scalars: hist uint32 [5, 256] (r, g, b, luma, max channel), zhist uint32
+    [256], n_pixels, n_drawn, n_nan (int), z_min, z_max (np.float32), box = (x0, y0, x1, y1) in output-image coordinates,
+    x1 and y1 exclusive.  `raw` is the record's 6192 bytes as a uint8 array; two records are equal when those are."""
+
+    def __init__(self, raw):
+        raw = np.array(np.asarray(raw).reshape(-1).view(np.uint8), copy=True)
+        if raw.nbytes != FRAME_STATS_BYTES:
+            raise ValueError("a tr_frame_stats record has %d bytes, not %d" % (FRAME_STATS_BYTES, raw.nbytes))
+        self.raw = raw
+        w = raw.view(np.uint32)
+        self.hist = w[:1280].reshape(5, 256)
+        self.zhist = w[1280:1536]
+        self.n_pixels, self.n_drawn, self.n_nan = int(w[1536]), int(w[1537]), int(w[1538])
+        self.z_min, self.z_max = w[1539:1541].view(np.float32)
+        self.box = tuple(int(v) for v in w[1541:1545])
+        self.reserved = w[1545:1548]
+
+    luma = property(lambda self: self.hist[3])
+    max_channel = property(lambda self: self.hist[4])
+
+    def __eq__(self, other):
+        return isinstance(other, FrameStats) and np.array_equal(self.raw, other.raw)
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "FrameStats(n_pixels=%d, n_drawn=%d, n_nan=%d, z_min=%r, z_max=%r, box=%r)" % (
+            self.n_pixels, self.n_drawn, self.n_nan, float(self.z_min), float(self.z_max), self.box)
+
+
+def frame_stats_host(rgb, z=None, window=None, depth=None, z_lo=0.0, z_scale=1.0):
+    """tr_frame_stats_host: the rule of Scene.frame_stats on the host (no GPU needed), by the inline functions k_stats calls.
+    rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer); z None or [H, W] float32 with row 0 = bottom (read_z_f32);
+    depth: None means "when z is given".  Returns a FrameStats and leaves its arguments alone."""
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("frame_stats_host: rgb [H, W, 3]")
+    if depth is None:
+        depth = z is not None
+    zz = None
+    if depth:
+        if z is None:
+            raise ValueError("frame_stats_host: depth statistics need z")
+        zz = np.ascontiguousarray(z, np.float32)
+        if zz.shape != src.shape[:2]:
+            raise ValueError("frame_stats_host: z [H, W] beside rgb [H, W, 3]")
+    p = stats_params(window, depth, z_lo, z_scale)
+    out = np.zeros(FRAME_STATS_BYTES, np.uint8)
+    check(load_library().tr_frame_stats_host(src.shape[1], src.shape[0], src.ctypes.data, zz.ctypes.data if zz is not None else None,
+                                             C.addressof(p), out.ctypes.data))
+    return FrameStats(out)
+
+
+def frame_stats_merge(a, b):
+    """tr_frame_stats_merge: the record (a new FrameStats) of the union of the two disjoint pixel sets whose records are a
+    and b -- two bands of a frame, two windows that do not overlap."""
+    if not isinstance(a, FrameStats) or not isinstance(b, FrameStats):
+        raise ValueError("frame_stats_merge: two FrameStats records")
+    dst, src = a.raw.copy(), np.ascontiguousarray(b.raw)
+    check(load_library().tr_frame_stats_merge(dst.ctypes.data, src.ctypes.data))
+    return FrameStats(dst)
+
+
+def hist_percentile(hist, q):
+    """The smallest bin whose cumulative count reaches q (0..1) of the histogram's total -- at least one count, so q = 0 gives
+    the lowest occupied bin and q = 1 the highest.  An empty histogram gives 0."""
+    h = np.asarray(hist)
+    if h.ndim != 1 or h.dtype.kind not in "iu" or h.size == 0:
+        raise ValueError("hist_percentile: a 1-D array of counts")
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("hist_percentile: q must be 0..1")
+    cum = np.cumsum(h.astype(np.uint64))
+    total = int(cum[-1])
+    if total == 0:
+        return 0
+    need = max(1, int(np.ceil(q * total)))
+    return int(np.searchsorted(cum, need, side="left"))
+
+
+def lut_auto_levels(stats, low=0.01, high=0.99, n=17):
+    """A table [n, n, n, 3] for Scene.set_lut that stretches the picture's tones: the luma bins at the `low` and `high`
+    percentiles of `stats` (a FrameStats) go to 0 and 255, every channel by the same line, clipped (lut_from_function).  A
+    picture whose two bins coincide gets the step at that bin."""
+    if not isinstance(stats, FrameStats):
+        raise ValueError("lut_auto_levels: stats must be a FrameStats")
+    low, high = float(low), float(high)
+    if not 0.0 <= low < high <= 1.0:
+        raise ValueError("lut_auto_levels: 0 <= low < high <= 1")
+    lo, hi = hist_percentile(stats.luma, low), hist_percentile(stats.luma, high)
+    hi = max(hi, lo + 1)
+    return lut_from_function(n, lambda v: (v * 255.0 - lo) / float(hi - lo))
+
+
+def depth_median(scene, window=None):
+    """The median depth of the drawn pixels of `scene`'s current frame inside `window` (None: the whole frame), by two
+    get_frame_stats calls: the depth range first, then a depth histogram of 256 bins over exactly that range; returns the
+    centre of the bin the median lies in (within (z_max - z_min) / 512 of it), z_min itself where all depths are equal, and
+    None where no pixel with a number for a depth is drawn.  Infinite depths are left to the outermost bins."""
+    first = scene.get_frame_stats(window=window, depth=True)
+    if first.n_drawn - first.n_nan <= 0:
+        return None
+    lo, hi = np.float32(first.z_min), np.float32(first.z_max)
+    if not np.isfinite(lo) or not np.isfinite(hi):
+        fin = np.float32(np.finfo(np.float32).max)
+        lo, hi = np.clip(lo, -fin, fin), np.clip(hi, -fin, fin)
+    with np.errstate(over="ignore", divide="ignore"):
+        scale = np.float32(256.0) / (hi - lo)
+    if not hi > lo or not np.isfinite(scale) or not scale > 0.0:
+        return float(lo)
+    second = scene.get_frame_stats(window=window, depth=True, z_lo=float(lo), z_scale=float(scale))
+    b = hist_percentile(second.zhist, 0.5)
+    return float(lo) + (b + 0.5) / float(scale)
+
+
 def texel_set_host(pipeline_name, textures):
     """tr_texel_set_host: (words uint32 [n], blocks_per_row) -- the texel set tr_scene_create builds for the pipeline from
     four uint8 [h, w, 3] images of one size (csrc/tr_texels.h), by the function the library itself calls, on the host (no
@@ -952,6 +1117,45 @@ class Scene:
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
             raise ValueError("debug_grade_grid: cap must be an integer 0..2^32 - 1")
         return check(load_library().tr_scene_debug_grade_grid(self._h, int(cap)))
+
+    # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
+    def pinned_stats(self):
+        """A page-locked uint8 array of one tr_frame_stats record for frame_stats (freed with the scene); FrameStats(array)
+        reads it after sync()."""
+        return self._pinned_array((FRAME_STATS_BYTES,))
+
+    def frame_stats(self, window=None, depth=False, z_lo=0.0, z_scale=1.0, out=None):
+        """tr_scene_frame_stats: enqueue the reduction of the current frame to one record behind everything issued so far;
+        the result is there after sync().  window, depth, z_lo, z_scale: stats_params.  `out`: a device pointer (int) to
+        6192 bytes, or an array from pinned_stats; None takes a page-locked array of the scene's own (one, reused by every
+        such call).  Returns `out` -- FrameStats(out) after sync() for an array.  Nothing of the scene is written; without
+        depth no depth is read.  Band scenes give the record of their band's rows (frame_stats_merge joins them)."""
+        p = stats_params(window, depth, z_lo, z_scale)
+        if out is None:
+            if getattr(self, "_stats_out", None) is None:
+                self._stats_out = self.pinned_stats()
+            out = self._stats_out
+        ptr = self._out_pointer(out, "out", "6192-byte", "pinned_stats", FRAME_STATS_BYTES)
+        check(load_library().tr_scene_frame_stats(self._h, C.addressof(p), ptr))
+        return out
+
+    def get_frame_stats(self, window=None, depth=False, z_lo=0.0, z_scale=1.0, strict=True):
+        """tr_scene_get_frame_stats: the record of the current frame as a FrameStats.  Synchronizes."""
+        p = stats_params(window, depth, z_lo, z_scale)
+        out = np.zeros(FRAME_STATS_BYTES, np.uint8)
+        code = load_library().tr_scene_get_frame_stats(self._h, C.addressof(p), out.ctypes.data)
+        if strict:
+            check(code)
+        self.last_status = code
+        return FrameStats(out)
+
+    def debug_stats_grid(self, cap=0):
+        """tr_scene_debug_stats_grid: every later k_stats launch of the scene starts at most `cap` workgroups (0: no cap, the
+        default), so that each walks more tiles and k_stats_finish sums fewer slots; the record does not change.  Returns
+        the number of workgroups of the scene's most recent k_stats launch, 0 if there has been none."""
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
+            raise ValueError("debug_stats_grid: cap must be an integer 0..2^32 - 1")
+        return check(load_library().tr_scene_debug_stats_grid(self._h, int(cap)))
 
     # --- dynamic textures (tr_scene_set_texture*) ---------------------------------------------------
     def _texture_shape(self, which):
