@@ -780,6 +780,80 @@ int tr_grade_host(size_t n_pixels, const uint8_t *rgb, uint8_t *out /* may be rg
  * that short-circuits on a logically cleared scene launches nothing), or TR_E_INVALID for a NULL scene. */
 int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap);
 
+/* Outlines: ink laid over the scene's CURRENT frame where its own z buffer has a silhouette, a depth step or a fold, on
+ * the device -- a line around each model, a line where one model passes in front of another (tr_scene_composite), a line
+ * along a sharp fold.  With tr_scene_grade through a posterising table it is a cel or technical-illustration look for a
+ * frame of any pipeline, merged or posed, with no geometry work.  The rule, with z as tr_scene_read_z_f32 returns it
+ * (index x + y * width, y up; a pixel is drawn when bits(z) != bits(f32::MIN); a larger z is nearer) and F the frame as
+ * tr_scene_get_frame_buffer returns it:
+ *   neighbours : the 4-neighbours of p are (x +- 1, y) and (x, y +- 1).  A neighbour outside the frame does not exist
+ *             and contributes nothing: a model cut by the frame's border gets no ink there.
+ *   kinds   : of a drawn pixel p with depth z0 (a pixel that is not drawn has kind 0), in f32, every operation rounded
+ *             once, nothing fused, a comparison with a NaN false:
+ *                 SIL = 1    : some existing neighbour is not drawn
+ *                 STEP = 2   : some existing drawn neighbour q has (z0 - zq) > depth_step -- the ink sits on the nearer
+ *                              side of a depth step only
+ *                 CREASE = 4 : only with TR_OUTLINE_CREASES, on an axis (horizontal or vertical) whose two neighbours a
+ *                              and b both exist and are drawn: |z0 - za| > depth_step is false, |z0 - zb| > depth_step is
+ *                              false, and |(za + zb) - (z0 + z0)| > crease.  A plane at any tilt has second difference 0
+ *                              up to rounding and gets no ink, a fold does, a depth step is left to STEP.
+ *   seed    : p is a seed when its kinds are not 0.
+ *   ink     : p is inked when some q inside the frame with max(|dx|, |dy|) <= radius is a seed.  Ink spreads onto pixels
+ *             that are not drawn.
+ *   output  : base = paper under TR_OUTLINE_ONLY, else F_p.  An inked pixel gets, per channel c,
+ *                 out[c] = (ink[c] * opacity + base[c] * (256 - opacity) + 128) >> 8
+ *             and any other pixel gets base.
+ * z, the winner words and the shadow buffer are never written. */
+#define TR_OUTLINE_MAX_RADIUS 3
+#define TR_OUTLINE_CREASES 0x1u   /* also ink folds (second difference of depth) */
+#define TR_OUTLINE_ONLY    0x2u   /* the base colour is `paper`, not the frame: a line drawing */
+typedef struct tr_outline_params {
+    uint32_t struct_size;  /* = sizeof(tr_outline_params) = 32 */
+    uint32_t radius;       /* 0..TR_OUTLINE_MAX_RADIUS: ink reaches this far (Chebyshev) from a seed pixel */
+    uint32_t flags;
+    uint32_t opacity;      /* 0..256 */
+    uint8_t  ink[4];       /* r, g, b, 0 */
+    uint8_t  paper[4];     /* r, g, b, 0; read only under TR_OUTLINE_ONLY */
+    float depth_step;      /* finite, >= 0, units of tr_scene_read_z_f32 */
+    float crease;          /* finite, >= 0; read only under TR_OUTLINE_CREASES */
+} tr_outline_params;
+/* Outlines the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_depth_of_field:
+ * k_outline is enqueued on the scene's stream behind the renders issued so far (frames held back are submitted, a depth
+ * left on the chip -- see TR_OPT_STORE_DEPTH -- is fetched by the depth-only repeat of the frame's pass), a later render
+ * is ordered behind it, the result is there after tr_scene_sync.  The scene's passes issued so far count as handed on.
+ * Tiles (128 x 16) whose whole 3 x 3 neighbourhood has its z fast-clear flag up hold no ink and are handled on the flags.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses), apart from every frame buffer of the scene; every byte
+ * of `out` is written on every call, the scene's frame is not.
+ * out == NULL: in place, by the kernel itself -- a pixel's output depends on the depths around it and on its own colour
+ * alone, so there is no scratch frame and no copy.  A tile whose colour fast-clear flag is up and that receives no ink
+ * keeps its flag and is not touched (under TR_OUTLINE_ONLY: where paper is (0, 0, 0)); ink that spreads into such a
+ * tile, or a paper that is not black, stores the whole tile and lowers its flag.  Every later consumer -- the getters,
+ * tr_scene_resolve, the sparse read-back, tr_scene_composite in either role, tr_scene_set_texture_from_frame -- sees
+ * the outlined frame.  Calling it twice outlines twice.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since): out of place `out` becomes zeros
+ * (hipMemsetAsync, no kernel), or `paper` in every pixel under TR_OUTLINE_ONLY (the clear is made real and the kernel
+ * runs); in place TR_OK, nothing happens.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene or NULL params, a wrong
+ * struct_size, radius > TR_OUTLINE_MAX_RADIUS, unknown flag bits, opacity > 256, a non-zero fourth byte of ink or paper,
+ * a depth_step or crease that is not finite or is negative, ordinary host memory as `out`, a pinned buffer that is too
+ * small, an `out` that overlaps a frame buffer the scene has rendered into, and a BAND scene (tr_options.band_row0/1
+ * set): the neighbours at a band's border lie in rows another rank owns. */
+int tr_scene_outline(tr_scene *s, const tr_outline_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first (an overflowed frame is rendered
+ * again before it is read), outlines into a buffer of the library's, copies out and returns the frame's sticky status,
+ * like tr_scene_get_depth_of_field.  The scene's frame stays as it is. */
+int tr_scene_get_outlined(tr_scene *s, const tr_outline_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_outline calls.  z: width * height floats,
+ * index x + y * width, y up; rgb: row 0 = top; out: like rgb, and may be rgb.  The same parameter checks; width or height
+ * 0: TR_OK, nothing to do. */
+int tr_outline_host(uint32_t width, uint32_t height, const float *z /* x + y*W, y up */, const uint8_t *rgb /* row 0 = top */,
+                    uint8_t *out /* may be rgb */, const tr_outline_params *p);
+/* The kind bits (SIL 1, STEP 2, CREASE 4) of every pixel under the parameters, in z's orientation (kinds: width * height
+ * bytes) -- for choosing depth_step and crease. */
+int tr_outline_kinds(uint32_t width, uint32_t height, const float *z, const tr_outline_params *p, uint8_t *kinds);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -152,6 +152,10 @@ SYMBOLS = {
     "tr_scene_get_graded": (C.c_int, [C.c_void_p, C.c_void_p]),
     "tr_grade_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "tr_scene_debug_grade_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tr_scene_outline": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_outlined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_outline_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_outline_kinds": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -92,6 +92,17 @@ def main(argv=None):
                          "unit domain) on the GPU (Scene.grade; after --bloom, before --ssaa resolves)")
     ap.add_argument("--gamma", type=float, default=None, metavar="G",
                     help="colour grading by a 33^3 table of v^(1/G), e.g. 2.2 (Scene.grade; after --bloom, before --ssaa resolves)")
+    ap.add_argument("--outline", type=int, default=None, metavar="R",
+                    help="outlines: ink on the picture's silhouettes and depth steps, found in its own z buffer on the GPU, reaching "
+                         "R (0..3) pixels from the edge (Scene.outline; after --lut / --gamma / --auto-levels, so the table does not "
+                         "recolour the ink, and before --ssaa resolves, so supersampling smooths the lines)")
+    ap.add_argument("--outline-depth", type=float, default=4.0, metavar="T",
+                    help="a drawn neighbour more than T units of z farther away makes a depth step (default 4)")
+    ap.add_argument("--outline-crease", type=float, default=None, metavar="T",
+                    help="also ink folds: pixels whose second difference of z along a row or a column exceeds T")
+    ap.add_argument("--outline-colour", default="0,0,0", metavar="r,g,b", help="the ink (default 0,0,0)")
+    ap.add_argument("--outline-opacity", type=int, default=256, metavar="N", help="the ink covers N / 256 of the picture (0..256, default 256)")
+    ap.add_argument("--outline-only", action="store_true", help="with --outline: the lines alone, on white paper")
     ap.add_argument("--auto-levels", default=None, metavar="LOW,HIGH",
                     help="colour grading by a table made from the picture itself: its luma percentiles LOW and HIGH (e.g. 0.01,0.99), "
                          "found on the GPU (Scene.get_frame_stats), stretched to black and white (lut_auto_levels; in the place of "
@@ -130,6 +141,20 @@ def main(argv=None):
                     raise ValueError("--gamma must be positive")
                 args.grade_lut = lut_from_function(33, lambda v: v ** (1.0 / args.gamma))
         except (OSError, ValueError) as e:
+            ap.error(str(e))
+    args.outline_params = None
+    if args.outline is None and (args.outline_depth != 4.0 or args.outline_crease is not None or args.outline_colour != "0,0,0"
+                                 or args.outline_opacity != 256 or args.outline_only):
+        ap.error("--outline-depth, --outline-crease, --outline-colour, --outline-opacity and --outline-only go with --outline R")
+    if args.outline is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--outline works on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import outline_params
+        try:
+            ink = [int(v) for v in args.outline_colour.split(",")]
+            args.outline_params = outline_params(args.outline, depth_step=args.outline_depth, crease=args.outline_crease, ink=ink,
+                                                 opacity=args.outline_opacity, only=args.outline_only)
+        except ValueError as e:
             ap.error(str(e))
     args.bloom_params = None
     if not args.bloom and (args.bloom_threshold != 200 or args.bloom_strength != 256 or args.bloom_glow_only):
@@ -453,6 +478,8 @@ def _run(args, T, scene, sharded, rank, say):
     if args.grade_lut is not None:
         scene.set_lut(args.grade_lut)
         scene.grade()
+    if args.outline_params is not None:
+        scene.outline(args.outline_params)
     if args.stats:
         st = scene.get_frame_stats(depth=True)
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"

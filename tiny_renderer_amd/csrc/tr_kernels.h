@@ -12,6 +12,7 @@
 #include "tr_bloom.h"
 #include "tr_grade.h"
 #include "tr_morph.h"
+#include "tr_outline.h"
 #include "tr_pack.h"
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
@@ -99,6 +100,11 @@ int launch_bloom(const BloomArgs &a, hipStream_t st);
 // a.lower_clean: null, or a.fbclean (in place, c0 != 0): the flags of the tiles stored as c0 come down.
 // cap: 0, or the most workgroups to start (tr_scene_debug_grade_grid); *grid: the number started (0: nothing launched).
 int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
+// Outlines: ink laid over a.fb where a.z has a silhouette, a depth step or a fold, into a.out -- a.fb itself or a buffer
+// apart from it -- by the rule of tr_outline.h, through the scene's fast-clear flags of z and of colour: k_outline.  The
+// whole frame only (no band); the caller has made the depth real.  In place the colour flag of a flagged tile the kernel
+// writes comes down.
+int launch_outline(const OutlineArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

@@ -39,6 +39,7 @@
 #include "tr_stats.h"
 #include "tr_kernels.h"
 #include "tr_morph.h"
+#include "tr_outline.h"
 #include "tr_pack.h"
 #include "tr_plan.h"
 #include "tr_resolve.h"
@@ -2809,6 +2810,190 @@ __global__ __launch_bounds__(GRADE_THREADS) void k_grade(GradeArgs a)
     }
 }
 
+// Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
+// a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
+// alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
+//   * the nine z flags of the 3 x 3 neighbourhood and the tile's own colour flag are workgroup-uniform (scalar loads; a
+//     tile outside the grid counts as raised).  All nine raised: nothing is drawn within radius + 1 pixels, so the tile
+//     has no ink -- no staging, no barrier, the colour phase below with empty masks;
+//   * staging: z of the tile and a halo of radius + 1 pixels go to LDS as rows of 136 floats that start 4 pixels left of
+//     the tile, so that a 16-byte piece is aligned in memory and lies in ONE tile: a piece in a tile whose z flag is up,
+//     or outside the frame, is filled with f32::MIN without a load.  At most 24 rows: 13 KB.  "Outside the frame" is
+//     not "not drawn": whether a neighbour EXISTS comes from the pixel's coordinates (outline_exist), never from LDS;
+//   * seeds: for the tile and a halo of `radius` pixels, as bit rows -- a wave takes 64 consecutive pixels of a row,
+//     every lane evaluates outline_kinds of its pixel from five LDS words, one ballot makes a 64-bit word, lane 0 stores
+//     it.  At most 22 rows of three words;
+//   * ink: a unit is four pixels of a row (k_grade's); a lane takes two units, eight rows apart.  It ORs the 2 r + 1 seed
+//     rows around its row, shifted so that the unit's window of 4 + 2 r bits starts at bit 0 (one or two 64-bit words a
+//     row, mostly the same words for a whole wave), and a pixel is inked when its 2 r + 1 bits of the window are not all
+//     zero.  A vote (one barrier) says whether the tile has any ink;
+//   * colour: base is paper under TR_OUTLINE_ONLY, zeros behind a raised colour flag (no load), else the unit's twelve
+//     bytes.  Out of place every unit of the tile is stored.  In place without ONLY only units with ink are loaded and
+//     stored, and a tile without ink is not touched -- but ink that reaches a FLAGGED tile stores the whole tile (zeros
+//     and ink) and lane 0 lowers the flag behind a barrier: a flag that stays up still means "cleared colour, memory
+//     not read".  In place under ONLY the whole tile is stored (flag lowered) unless it is flagged, paper is black and
+//     no ink reaches it.
+// WIDE: width % 4 == 0, z 16-byte and fb / out 4-byte aligned (the launcher checks): z in 16-byte pieces, a unit as three
+// aligned words; otherwise the same through element accesses guarded by the width.  z, its flags, the winner words and
+// the shadow buffer are only read.  No atomics, no inline assembly, no scratch.
+constexpr int OUTLINE_LDS_W = TILE_W + 8, OUTLINE_LDS_H = TILE_H + 2 * (OUTLINE_MAX_RADIUS + 1);
+constexpr int OUTLINE_SEED_H = TILE_H + 2 * OUTLINE_MAX_RADIUS, OUTLINE_SEED_WORDS = 3;  // rows of 192 bits, bit c = LDS column c
+constexpr int OUTLINE_THREADS = 256, OUTLINE_UNITS = TILE_W * TILE_H / 4 / OUTLINE_THREADS;
+
+template <bool WIDE>
+__global__ __launch_bounds__(OUTLINE_THREADS) void k_outline(OutlineArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H == 16 && OUTLINE_UNITS == 2, "32 units to a row of a tile, two rounds of eight rows");
+    static_assert(OUTLINE_MAX_RADIUS + 1 <= 4 && OUTLINE_MAX_RADIUS + 1 <= TILE_H, "the halo lies in the eight tiles around, within 4 columns");
+    static_assert(OUTLINE_LDS_W <= 64 * OUTLINE_SEED_WORDS && OUTLINE_THREADS == 4 * 64, "three ballots cover a row; four waves");
+    __shared__ float s_z[OUTLINE_LDS_H * OUTLINE_LDS_W];
+    __shared__ unsigned long long s_seed[OUTLINE_SEED_H * OUTLINE_SEED_WORDS];
+    const uint32_t t = blockIdx.x;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, R = (int32_t)a.rule.radius;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t tx = (int32_t)t % ntx, ty = (int32_t)t / ntx;
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    const bool only = (a.rule.flags & OUTLINE_ONLY) != 0u, in_place = a.out == a.fb;
+    const bool clean = a.fbclean[t] != 0u;  // (workgroup-uniform)
+    // bit 3 * ay + ax: the tile at (tx + ax - 1, ty + ay - 1) reads as f32::MIN -- flag up, or no such tile
+    uint32_t stale = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            bool up = nx < 0 || nx >= ntx || ny < 0 || ny >= nty;
+            if (!up) up = a.zclean[ny * ntx + nx] != 0u;
+            if (up) stale |= 1u << (3 * ay + ax);
+        }
+    // the units of k_grade
+    const int32_t ux = 4 * (int32_t)(threadIdx.x % 32u), x = x0 + ux, row_first = (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = min(4, W - x);  // (WIDE: 4, or the unit is outside)
+    uint32_t inked[OUTLINE_UNITS];       // bit i: pixel i of the unit is inked
+#pragma unroll
+    for (int h = 0; h < OUTLINE_UNITS; h++) inked[h] = 0u;
+    bool any_ink = false;
+    if (stale != 0x1FFu) {  // (workgroup-uniform: the barriers are reached by all or none)
+        const int32_t rows = TILE_H + 2 * (R + 1);  // LDS row r is frame row y0 - (R + 1) + r, LDS column c frame column x0 - 4 + c
+        const float z_min = bits_f32(TR_F32_MIN_BITS);
+        if (WIDE) {
+            for (int32_t p = (int32_t)threadIdx.x; p < rows * (OUTLINE_LDS_W / 4); p += OUTLINE_THREADS) {
+                const int32_t r = p / (OUTLINE_LDS_W / 4), j = p % (OUTLINE_LDS_W / 4);
+                const int32_t px = x0 - 4 + 4 * j, py = y0 - (R + 1) + r;
+                const int32_t ax = j < 1 ? 0 : j < 1 + TILE_W / 4 ? 1 : 2, ay = py < y0 ? 0 : py < y0 + TILE_H ? 1 : 2;
+                float4 v = make_float4(z_min, z_min, z_min, z_min);
+                if (((stale >> (3 * ay + ax)) & 1u) == 0u && px < W && py < H)
+                    v = *reinterpret_cast<const float4 *>(a.z + (size_t)py * (size_t)W + (size_t)px);
+                *reinterpret_cast<float4 *>(&s_z[r * OUTLINE_LDS_W + 4 * j]) = v;
+            }
+        } else {
+            for (int32_t p = (int32_t)threadIdx.x; p < rows * OUTLINE_LDS_W; p += OUTLINE_THREADS) {
+                const int32_t r = p / OUTLINE_LDS_W, c = p % OUTLINE_LDS_W;
+                if (c < 3 - R || c > 4 + TILE_W + R) continue;  // (no pixel of the seed region looks at it)
+                const int32_t px = x0 - 4 + c, py = y0 - (R + 1) + r;
+                const int32_t ax = c < 4 ? 0 : c < 4 + TILE_W ? 1 : 2, ay = py < y0 ? 0 : py < y0 + TILE_H ? 1 : 2;
+                float v = z_min;
+                if (((stale >> (3 * ay + ax)) & 1u) == 0u && px < W && py < H) v = a.z[(size_t)py * (size_t)W + (size_t)px];
+                s_z[r * OUTLINE_LDS_W + c] = v;
+            }
+        }
+        __syncthreads();
+        // seeds: seed row sr is frame row y0 - R + sr, LDS row sr + 1; bit c of a row is LDS column c
+        const int32_t wave = (int32_t)(threadIdx.x / 64u), lane = (int32_t)(threadIdx.x % 64u);
+        const int32_t seed_rows = TILE_H + 2 * R;
+        for (int32_t task = wave; task < seed_rows * OUTLINE_SEED_WORDS; task += OUTLINE_THREADS / 64) {
+            const int32_t sr = task / OUTLINE_SEED_WORDS, j = task % OUTLINE_SEED_WORDS;
+            const int32_t c = 64 * j + lane, px = x0 - 4 + c, py = y0 - R + sr;
+            bool seed = false;
+            if (c >= 4 - R && c < 4 + TILE_W + R && px >= 0 && px < W && py >= 0 && py < H) {
+                const float *q = s_z + (sr + 1) * OUTLINE_LDS_W + c;
+                seed = outline_kinds(q[0], q[-1], q[1], q[-OUTLINE_LDS_W], q[OUTLINE_LDS_W], outline_exist(px, py, W, H), a.rule) != 0u;
+            }
+            const unsigned long long word = __ballot(seed ? 1 : 0);
+            if (lane == 0) s_seed[sr * OUTLINE_SEED_WORDS + j] = word;
+        }
+        __syncthreads();
+        // ink: the unit's window starts R bits left of its first pixel
+        const int32_t first = 4 + ux - R, j = first >> 6, off = first & 63;
+        const uint32_t span = (1u << (2 * R + 1)) - 1u;
+        uint32_t mine = 0u;
+#pragma unroll
+        for (int h = 0; h < OUTLINE_UNITS; h++) {
+            const int32_t row = row_first + 8 * h;  // seed rows row .. row + 2 R lie around it
+            unsigned long long acc = 0ull;
+            for (int32_t dy = 0; dy <= 2 * R; dy++) {
+                const unsigned long long *w = s_seed + (row + dy) * OUTLINE_SEED_WORDS + j;
+                acc |= w[0] >> off;
+                if (off != 0 && j + 1 < OUTLINE_SEED_WORDS) acc |= w[1] << (64 - off);
+            }
+            const uint32_t window = (uint32_t)acc;
+            const bool inside = x < W && y0 + row < H;
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (inside && i < n_px && ((window >> i) & span) != 0u) inked[h] |= 1u << i;
+            mine |= inked[h];
+        }
+        any_ink = __syncthreads_or((int)mine) != 0;
+    }
+    // what the tile needs (all workgroup-uniform)
+    bool store_all = true, load = !only && !clean;
+    if (in_place) {
+        if (only) {
+            if (clean && a.rule.paper == 0u && !any_ink) return;  // stays the cleared colour behind its flag
+            load = false;
+        } else {
+            if (!any_ink) return;
+            store_all = clean;  // zeros and ink over stale memory: every byte
+        }
+    }
+    const uint32_t blank = only ? a.rule.paper : 0u;
+#pragma unroll
+    for (int h = 0; h < OUTLINE_UNITS; h++) {
+        const int32_t y = y0 + row_first + 8 * h;
+        if (x >= W || y >= H) continue;
+        if (!store_all && inked[h] == 0u) continue;
+        const size_t ci = ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u;
+        uint32_t px[4] = { blank, blank, blank, blank };
+        if (load) {
+            const uint8_t *q = a.fb + ci;
+            if (WIDE) {
+                const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                px[0] = w0 & 0xFFFFFFu;
+                px[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                px[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                px[3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) px[i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if ((inked[h] >> i) & 1u) px[i] = outline_px(px[i], a.rule);
+        uint8_t *o = a.out + ci;
+        if (WIDE) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = px[0] | (px[1] << 24);
+            ow[1] = (px[1] >> 8) | (px[2] << 16);
+            ow[2] = (px[2] >> 16) | (px[3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(px[i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((px[i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((px[i] >> 16) & 0xFFu);
+                }
+        }
+    }
+    if (in_place && clean) {  // (workgroup-uniform) the tile's memory is its colour now
+        __syncthreads();  // (every wave has read the flag)
+        if (threadIdx.x == 0u) a.fbclean[t] = 0u;
+    }
+}
+
 // Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
 // partial record.  The project's one reduction, in two launches:
 //   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
@@ -3812,6 +3997,28 @@ int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *gri
         hipLaunchKernelGGL((k_grade<false, true>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_grade<false, false>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_outline(const OutlineArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.z || !a.zclean || !a.fb || !a.fbclean || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), seeds inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.rule.radius > (uint32_t)OUTLINE_MAX_RADIUS || a.rule.opacity > 256u || (a.rule.flags & ~(OUTLINE_CREASES | OUTLINE_ONLY)) != 0u)
+        return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // the wide path: z in aligned 16-byte pieces, every unit of four pixels three aligned words of either buffer
+    const bool wide = a.frame.width % 4u == 0u && (uintptr_t)a.z % 16u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_outline<true>), dim3(n_tiles), dim3(OUTLINE_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_outline<false>), dim3(n_tiles), dim3(OUTLINE_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2807,7 +2807,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve has none); the cleared-scene shortcut where the stage has one --
@@ -4587,6 +4587,131 @@ int tr_scene_debug_grade_grid(tr_scene *s, uint32_t cap)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_grade_grid: null scene");
     s->grade_cap = cap;
     return (int)s->grade_grid;
+}
+
+namespace {
+
+static_assert(TR_OUTLINE_MAX_RADIUS == OUTLINE_MAX_RADIUS && TR_OUTLINE_CREASES == OUTLINE_CREASES && TR_OUTLINE_ONLY == OUTLINE_ONLY &&
+                  sizeof(tr_outline_params) == 32,
+              "tr_outline.h restates the header");
+
+// tr_outline_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_outline_params(const tr_outline_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_outline_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_outline_params)");
+    if (p->radius > (uint32_t)TR_OUTLINE_MAX_RADIUS) return tr::fail(TR_E_INVALID, w + ": radius must be 0..TR_OUTLINE_MAX_RADIUS");
+    if (p->flags & ~(TR_OUTLINE_CREASES | TR_OUTLINE_ONLY)) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if (p->ink[3] != 0u || p->paper[3] != 0u) return tr::fail(TR_E_INVALID, w + ": the fourth byte of ink and of paper must be 0");
+    if (!std::isfinite(p->depth_step) || p->depth_step < 0.0f) return tr::fail(TR_E_INVALID, w + ": depth_step must be finite and >= 0");
+    if (!std::isfinite(p->crease) || p->crease < 0.0f) return tr::fail(TR_E_INVALID, w + ": crease must be finite and >= 0");
+    return TR_OK;
+}
+
+OutlineRule outline_rule(const tr_outline_params *p)
+{
+    OutlineRule r;
+    r.radius = p->radius;
+    r.flags = p->flags;
+    r.opacity = p->opacity;
+    r.ink = grade_pack(p->ink[0], p->ink[1], p->ink[2]);
+    r.paper = grade_pack(p->paper[0], p->paper[1], p->paper[2]);
+    r.depth_step = p->depth_step;
+    r.crease = p->crease;
+    return r;
+}
+
+int check_outline_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be outlined: "
+                                                         "its border neighbours lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// Is the stage's image of a logically cleared frame zeros?  (Under TR_OUTLINE_ONLY it is `paper`.)
+bool outline_of_cleared_is_zeros(const tr_outline_params *p) { return !(p->flags & TR_OUTLINE_ONLY) || outline_rule(p).paper == 0u; }
+
+// Enqueues the outlines of the current frame into `out_device` (null: in place) behind everything issued so far.  A
+// logically cleared scene is the caller's business where its image is zeros; where it is `paper` the clear is made real
+// here and the kernel turns every (flagged) tile into paper.
+int enqueue_outline(tr_scene *s, const tr_outline_params *p, uint8_t *out_device)
+{
+    int st = s->z_fb_cleared ? flush_clear_color(s) : TR_OK;
+    if (st == TR_OK) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    OutlineArgs a = {};
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.frame = s->frame;
+    a.rule = outline_rule(p);
+    {
+        Timed t(s, K_OUTLINE);
+        int rc = launch_outline(a, s->stream);
+        if (rc) return launch_status(rc, "k_outline");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_outline(tr_scene *s, const tr_outline_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_outline: null scene");
+    int st = check_outline_params(p, "tr_scene_outline");
+    if (st == TR_OK) st = check_outline_scene(s, "tr_scene_outline");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_outline", "tr_scene_get_outlined", "outlines", 0u, &target);
+    if (st != TR_OK) return st;
+    // a logically cleared frame has no drawn pixel, so no ink: itself in place; zeros, or paper, out of place
+    if (s->z_fb_cleared) {
+        if (!target) return TR_OK;
+        if (outline_of_cleared_is_zeros(p)) return cleared_out_of_place(s, target);
+    }
+    st = enqueue_outline(s, p, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_outlined(tr_scene *s, const tr_outline_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_outlined: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_outlined: null argument");
+    int st = check_outline_params(p, "tr_scene_get_outlined");
+    if (st == TR_OK) st = check_outline_scene(s, "tr_scene_get_outlined");
+    if (st != TR_OK) return st;
+    return get_stage(s, rgb, frame_bytes(s), outline_of_cleared_is_zeros(p) ? cleared : nullptr,
+                     [&](uint8_t *o) { return enqueue_outline(s, p, o); });
+}
+
+// The rule of tr_outline.h over caller's arrays, on the host.  Needs no GPU.
+int tr_outline_host(uint32_t width, uint32_t height, const float *z, const uint8_t *rgb, uint8_t *out, const tr_outline_params *p)
+{
+    int st = check_outline_params(p, "tr_outline_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!z || !rgb || !out) return tr::fail(TR_E_INVALID, "tr_outline_host: null argument");
+    outline_host(width, height, z, rgb, out, outline_rule(p));
+    return TR_OK;
+}
+
+int tr_outline_kinds(uint32_t width, uint32_t height, const float *z, const tr_outline_params *p, uint8_t *kinds)
+{
+    int st = check_outline_params(p, "tr_outline_kinds");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!z || !kinds) return tr::fail(TR_E_INVALID, "tr_outline_kinds: null argument");
+    outline_kinds_host(width, height, z, outline_rule(p), kinds);
+    return TR_OK;
 }
 
 namespace {

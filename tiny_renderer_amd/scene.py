@@ -335,6 +335,76 @@ def dof_coc(params, z):
     return out
 
 
+OUTLINE_MAX_RADIUS, OUTLINE_CREASES, OUTLINE_ONLY = 3, 1, 2   # (TR_OUTLINE_MAX_RADIUS, TR_OUTLINE_CREASES, TR_OUTLINE_ONLY)
+OUTLINE_SIL, OUTLINE_STEP, OUTLINE_CREASE = 1, 2, 4           # the kind bits of outline_kinds
+
+
+class OutlineParams(C.Structure):
+    """tr_outline_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("opacity", C.c_uint32),
+                ("ink", C.c_uint8 * 4), ("paper", C.c_uint8 * 4), ("depth_step", C.c_float), ("crease", C.c_float)]
+
+
+def _rgb0(colour, name):
+    c = [int(v) for v in colour]
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise ValueError("outline: %s must be three values 0..255" % name)
+    return (C.c_uint8 * 4)(c[0], c[1], c[2], 0)
+
+
+def outline_params(radius=1, depth_step=1.0, crease=None, ink=(0, 0, 0), opacity=256, only=False, paper=(255, 255, 255)):
+    """tr_outline_params for Scene.outline / outline_host / outline_kinds: ink reaches `radius` pixels (0..3, Chebyshev)
+    from a seed -- a drawn pixel beside one not drawn, on the nearer side of a depth step larger than depth_step, or, with
+    crease given (which sets OUTLINE_CREASES), on a fold whose second difference of depth exceeds it.  opacity 0..256;
+    only=True draws on `paper` instead of the frame (OUTLINE_ONLY).  ValueError for what the library would refuse
+    (include/tiny_renderer.h)."""
+    for name, v in (("radius", radius), ("opacity", opacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("outline: %s must be an integer" % name)
+    if not 0 <= radius <= OUTLINE_MAX_RADIUS:
+        raise ValueError("outline: radius must be 0..%d pixels" % OUTLINE_MAX_RADIUS)
+    if not 0 <= opacity <= 256:
+        raise ValueError("outline: opacity must be 0..256")
+    flags = (OUTLINE_CREASES if crease is not None else 0) | (OUTLINE_ONLY if only else 0)
+    for name, v in (("depth_step", depth_step), ("crease", 0.0 if crease is None else crease)):
+        with np.errstate(over="ignore"):   # (as f32: what the library gets)
+            v32 = np.float32(float(v))
+        if not np.isfinite(v32) or v32 < 0.0:
+            raise ValueError("outline: %s must be finite and >= 0" % name)
+    return OutlineParams(C.sizeof(OutlineParams), int(radius), flags, int(opacity), _rgb0(ink, "ink"), _rgb0(paper, "paper"),
+                         float(depth_step), 0.0 if crease is None else float(crease))
+
+
+def outline_host(z, rgb, params, in_place=False):
+    """tr_outline_host: the rule of Scene.outline on the host (no GPU needed), by the inline functions k_outline calls.
+    z [H, W] float32 with row 0 = bottom (read_z_f32), rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params
+    from outline_params.  Returns the outlined frame and leaves its arguments alone; in_place=True hands the library
+    one buffer as rgb and out (a copy of rgb), which the rule allows."""
+    if not isinstance(params, OutlineParams):
+        raise ValueError("outline_host: params must come from outline_params")
+    zz = np.ascontiguousarray(z, np.float32)
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if zz.ndim != 2 or src.shape != zz.shape + (3,):
+        raise ValueError("outline_host: z [H, W] and rgb [H, W, 3]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_outline_host(zz.shape[1], zz.shape[0], zz.ctypes.data, out.ctypes.data if in_place else src.ctypes.data,
+                                         out.ctypes.data, C.addressof(params)))
+    return out
+
+
+def outline_kinds(z, params):
+    """tr_outline_kinds: the kind bits (OUTLINE_SIL 1, OUTLINE_STEP 2, OUTLINE_CREASE 4; uint8, z's shape and orientation)
+    of every pixel of the depths z [H, W] under params (outline_params) -- for choosing depth_step and crease."""
+    if not isinstance(params, OutlineParams):
+        raise ValueError("outline_kinds: params must come from outline_params")
+    zz = np.ascontiguousarray(z, np.float32)
+    if zz.ndim != 2:
+        raise ValueError("outline_kinds: z [H, W]")
+    out = np.zeros(zz.shape, np.uint8)
+    check(load_library().tr_outline_kinds(zz.shape[1], zz.shape[0], zz.ctypes.data, C.addressof(params), out.ctypes.data))
+    return out
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1117,6 +1187,28 @@ class Scene:
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
             raise ValueError("debug_grade_grid: cap must be an integer 0..2^32 - 1")
         return check(load_library().tr_scene_debug_grade_grid(self._h, int(cap)))
+
+    # --- outlines (tr_scene_outline / tr_scene_get_outlined) ------------------------------------------
+    def outline(self, params, out=None):
+        """tr_scene_outline: inks the current frame's silhouettes, depth steps and folds from its own z buffer on the
+        device (params from outline_params).  out=None: in place, by the kernel itself -- every later consumer (the
+        getters, resolve, the sparse read-back, composite) sees the outlined frame, z, winner words and the shadow buffer
+        stay, calling it twice outlines twice.  Otherwise `out` is a device pointer (int) to 3 * W * H bytes apart from
+        every frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.
+        Asynchronous: the result is there after sync().  Band scenes are refused.  store_depth=True avoids the
+        depth-only repeat of the frame's pass."""
+        if not isinstance(params, OutlineParams):
+            raise ValueError("outline: params must come from outline_params")
+        ptr = self._out_pointer(out)
+        check(load_library().tr_scene_outline(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_outlined(self, params, strict=True):
+        """tr_scene_get_outlined: the current frame outlined on the device, as an [H, W, 3] uint8 array.  Synchronizes;
+        the scene's frame stays as it is."""
+        if not isinstance(params, OutlineParams):
+            raise ValueError("get_outlined: params must come from outline_params")
+        return self._image("tr_scene_get_outlined", strict, C.addressof(params))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
