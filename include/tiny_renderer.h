@@ -854,6 +854,72 @@ int tr_outline_host(uint32_t width, uint32_t height, const float *z /* x + y*W, 
  * bytes) -- for choosing depth_step and crease. */
 int tr_outline_kinds(uint32_t width, uint32_t height, const float *z, const tr_outline_params *p, uint8_t *kinds);
 
+/* Edge anti-aliasing: the stair-steps of the scene's CURRENT frame smoothed on the device, at the frame's own size and
+ * without geometry -- a luma-driven edge filter of the FXAA family, in integers on the stored bytes.  It works on any
+ * frame: rendered, composited, graded, inked by tr_scene_outline.  The rule, in the orientation of
+ * tr_scene_get_frame_buffer (row 0 = top, y grows downwards; N is (x, y - 1), S (x, y + 1), W (x - 1, y), E (x + 1, y)):
+ * F(x, y) is the stored rgb8 and L(x, y) = (54 R + 183 G + 19 B + 128) >> 8 its luma, the Y of tr_frame_stats.  A
+ * coordinate outside the frame is clamped to it, x and y each on its own: the border pixel repeats.  For every pixel p:
+ *   1 contrast : M, N, S, W, E the lumas of p and its four neighbours, lo / hi their min / max, range = hi - lo.
+ *                range < max(contrast_min, (hi * contrast_rel + 128) >> 8), or range == 0: off = 0, p is kept.
+ *   2 direction: EH = |NW + SW - 2 W| + 2 |N + S - 2 M| + |NE + SE - 2 E|
+ *                EV = |NW + NE - 2 N| + 2 |W + E - 2 M| + |SW + SE - 2 S|;  the edge is horizontal when EH >= EV.
+ *   3 sides    : horizontal: A = N, B = S, t = (1, 0); vertical: A = W, B = E, t = (0, 1).  gA = |A - M|, gB = |B - M|;
+ *                the side is A when gA >= gB, else B; g = max(gA, gB); C the chosen neighbour's luma, n the unit step
+ *                from p to it; mid2 = M + C.
+ *   4 search   : for s in {-1, +1}, each on its own: k = 1 .. search, q = p + s k t, d2 = L(q) + L(q + n) - mid2, stop at
+ *                the first k with 2 |d2| >= g.  dist_s = that k, or `search` when none stopped; end_s = the last d2
+ *                evaluated.
+ *   5 edge     : span = dist_- + dist_+; the near end is the - end when dist_- < dist_+, else the + end, with `near` its
+ *                distance and `end` its d2.  good = (end < 0) != (2 M - mid2 < 0).
+ *                off_e = good ? ((span - 2 near) * 128 + span / 2) / span : 0            (floor divisions; 0..128)
+ *   6 sub-pixel: a = |2 (N + S + W + E) + NW + NE + SW + SE - 12 M|;  tq = min(256, (a * 256) / (12 * range))
+ *                sm = (tq * tq * (768 - 2 tq)) >> 16;  off_s = (((sm * sm) >> 8) * subpixel) >> 8          (0..256)
+ *   7 output   : off = max(off_e, off_s); out[c] = (F_p[c] * (256 - off) + F_(p + n)[c] * off + 128) >> 8, p + n clamped
+ *                like every coordinate.  Under TR_AA_SHOW_BLEND all three channels are min(255, off) instead (0 for a
+ *                kept pixel): what the filter found, a diagnostic like TR_DOF_SHOW_COC.
+ * z, the winner words and the shadow buffer are neither read nor written. */
+#define TR_AA_MAX_SEARCH 8
+#define TR_AA_SHOW_BLEND 0x1u
+typedef struct tr_aa_params {
+    uint32_t struct_size;   /* = sizeof(tr_aa_params) = 24 */
+    uint32_t contrast_min;  /* 0..255: a pixel whose local luma range is below it is kept */
+    uint32_t contrast_rel;  /* 0..256: ... or below this many 256ths of the brightest of the five lumas */
+    uint32_t search;        /* 1..TR_AA_MAX_SEARCH: how far along the edge its ends are looked for */
+    uint32_t subpixel;      /* 0..256: the weight of the sub-pixel term (0: edges only) */
+    uint32_t flags;
+} tr_aa_params;
+/* Filters the current frame -- what the getters mean.  Asynchronous and ordered like tr_scene_bloom: k_aa is enqueued on
+ * the scene's stream behind the renders issued so far (frames held back are submitted; no depth is read, so a depth left
+ * on the chip stays there), a later render is ordered behind it, the result is there after tr_scene_sync.  The scene's
+ * passes issued so far count as handed on.  Tiles (128 x 16) whose whole 3 x 3 neighbourhood has its colour fast-clear
+ * flag up are black, stay black and are handled on the flags.
+ * out != NULL: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses), apart from every frame buffer of the scene; every byte
+ * of `out` is written on every call, the scene's frame is not.
+ * out == NULL: in place -- through a scratch frame of the scene's and a device-to-device copy, because a pixel reads its
+ * neighbours.  A tile whose colour flag is up keeps it unless colour came in from a neighbour's edge (some byte of its
+ * output is not zero): then its flag is lowered.  Every later consumer sees the filtered frame; calling it twice
+ * filters twice.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since) is black and stays black: out of place
+ * `out` becomes zeros (hipMemsetAsync, no kernel); in place TR_OK, nothing happens.
+ * TR_E_INVALID with a tr_last_error text, nothing changed and nothing queued: a NULL scene or NULL params, a wrong
+ * struct_size, contrast_min > 255, contrast_rel > 256, search outside 1..TR_AA_MAX_SEARCH, subpixel > 256, unknown flag
+ * bits, ordinary host memory as `out`, a pinned buffer that is too small, an `out` that overlaps a frame buffer the
+ * scene has rendered into, and a BAND scene (tr_options.band_row0/1 set): the taps at a band's border lie in rows
+ * another rank owns. */
+int tr_scene_antialias(tr_scene *s, const tr_aa_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * width * height bytes): waits for the scene first, filters into a buffer of the
+ * library's, copies out and returns the frame's sticky status, like tr_scene_get_bloom.  The scene's frame stays. */
+int tr_scene_get_antialiased(tr_scene *s, const tr_aa_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_aa calls.  rgb and out: 3 * width * height
+ * bytes, row 0 = top; out must not be rgb.  The same parameter checks; width or height 0: TR_OK, nothing to do. */
+int tr_aa_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out /* != rgb */, const tr_aa_params *p);
+/* The rule's two floor divisions as device and host compute them, for checking them exhaustively: out[i] = the edge
+ * term of span a[i] (2..16) and near b[i] (1..a[i] / 2) when which == 0, tq of a = a[i] (0..3060) and range b[i] (1..255)
+ * when which == 1.  TR_E_INVALID for another `which`, a NULL pointer with n > 0, or a pair outside those ranges. */
+int tr_aa_quotients(uint32_t which, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -103,6 +103,14 @@ def main(argv=None):
     ap.add_argument("--outline-colour", default="0,0,0", metavar="r,g,b", help="the ink (default 0,0,0)")
     ap.add_argument("--outline-opacity", type=int, default=256, metavar="N", help="the ink covers N / 256 of the picture (0..256, default 256)")
     ap.add_argument("--outline-only", action="store_true", help="with --outline: the lines alone, on white paper")
+    ap.add_argument("--aa", action="store_true",
+                    help="edge anti-aliasing: smooth the picture's stair-steps at its own size by a luma-driven edge filter on the GPU "
+                         "(Scene.antialias; after --outline, so the ink's edges are smoothed too, and before --ssaa resolves)")
+    ap.add_argument("--aa-contrast", default="8,32", metavar="MIN,REL",
+                    help="filter a pixel whose local luma range reaches MIN (0..255) and REL / 256 (0..256) of the brightest luma (default 8,32)")
+    ap.add_argument("--aa-search", type=int, default=8, metavar="N", help="look for an edge's ends up to N pixels away (1..8, default 8)")
+    ap.add_argument("--aa-subpixel", type=int, default=192, metavar="N", help="the weight of the sub-pixel term (0..256, default 192; 0: edges only)")
+    ap.add_argument("--aa-show-blend", action="store_true", help="with --aa: the blend weight the filter found instead of the picture")
     ap.add_argument("--auto-levels", default=None, metavar="LOW,HIGH",
                     help="colour grading by a table made from the picture itself: its luma percentiles LOW and HIGH (e.g. 0.01,0.99), "
                          "found on the GPU (Scene.get_frame_stats), stretched to black and white (lut_auto_levels; in the place of "
@@ -154,6 +162,19 @@ def main(argv=None):
             ink = [int(v) for v in args.outline_colour.split(",")]
             args.outline_params = outline_params(args.outline, depth_step=args.outline_depth, crease=args.outline_crease, ink=ink,
                                                  opacity=args.outline_opacity, only=args.outline_only)
+        except ValueError as e:
+            ap.error(str(e))
+    args.aa_params = None
+    if not args.aa and (args.aa_contrast != "8,32" or args.aa_search != 8 or args.aa_subpixel != 192 or args.aa_show_blend):
+        ap.error("--aa-contrast, --aa-search, --aa-subpixel and --aa-show-blend go with --aa")
+    if args.aa:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--aa works on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import aa_params
+        try:
+            lo, rel = (int(v) for v in args.aa_contrast.split(","))
+            args.aa_params = aa_params(contrast_min=lo, contrast_rel=rel, search=args.aa_search, subpixel=args.aa_subpixel,
+                                       show_blend=args.aa_show_blend)
         except ValueError as e:
             ap.error(str(e))
     args.bloom_params = None
@@ -480,6 +501,8 @@ def _run(args, T, scene, sharded, rank, say):
         scene.grade()
     if args.outline_params is not None:
         scene.outline(args.outline_params)
+    if args.aa_params is not None:
+        scene.antialias(args.aa_params)
     if args.stats:
         st = scene.get_frame_stats(depth=True)
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
+#include "tr_aa.h"
 #include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
@@ -105,6 +106,10 @@ int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *gri
 // whole frame only (no band); the caller has made the depth real.  In place the colour flag of a flagged tile the kernel
 // writes comes down.
 int launch_outline(const OutlineArgs &a, hipStream_t st);
+// Edge anti-aliasing: a.fb filtered by the rule of tr_aa.h into a.out, which is apart from it (a pixel reads its
+// neighbours), through the scene's colour fast-clear flags: k_aa.  The whole frame only (no band).  a.out_clean: null, or
+// where each workgroup writes the flag of its tile of a.out -- a tile flagged there is zeros in every byte.
+int launch_aa(const AaArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

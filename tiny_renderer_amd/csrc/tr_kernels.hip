@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "tr_aa.h"
 #include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
@@ -2994,6 +2995,250 @@ __global__ __launch_bounds__(OUTLINE_THREADS) void k_outline(OutlineArgs a)
     }
 }
 
+// Edge anti-aliasing (tr_scene_antialias): the frame's stair-steps smoothed by a luma-driven edge filter into `out`,
+// never in place (a pixel reads lumas up to `search` pixels away and one neighbour's colour); tr_aa.h has the rule.  One
+// workgroup of 256 lanes per 128 x 16 tile, the grid of k_bloom and k_outline.  The rule speaks of BUFFER rows (row 0 =
+// top), so the kernel does too: tile row ty holds buffer rows by0 .. by0 + 15 with by0 = H - 16 - 16 ty (negative in a
+// partial top row: those rows do not exist), and the tile row ABOVE it in the buffer is ty + 1.
+//   * the nine colour flags of the 3 x 3 neighbourhood are workgroup-uniform (a tile outside the grid counts as up: what
+//     is clamped from it repeats a border pixel of a tile inside).  All nine up: the tile is black and stays black,
+//     nothing is read -- zeros are stored and, with out_clean, the output flag is raised (a raised colour flag says
+//     "zeros, no need to load", and the memory behind it IS zeros: tr_scene_get_frame_buffer copies it as it lies);
+//   * staging: the LUMA of the tile and a halo of `search` pixels goes to LDS as bytes, rows of 144 that start 8 pixels
+//     left of the tile, so that a piece of four pixels (twelve bytes of the frame, one word of LDS) lies in ONE tile: a
+//     piece behind a raised flag is zeros without a load.  What lies outside the frame is filled from LDS behind a
+//     barrier with the luma of the clamped coordinates (only tiles whose halo leaves the frame take that pass);
+//   * step 1 of the rule: a lane owns two units of four pixels, eight rows apart (k_outline's), and tests them from
+//     three aligned words and two bytes of LDS a unit.  A pixel that passes goes onto a list in LDS (one LDS atomic a
+//     lane for its place).  The list's length is the tile's vote: empty, and the tile is a copy of itself;
+//   * steps 2 to 6: the list is dealt out to the lanes, 256 survivors at a time, so that the walk of the search runs on
+//     full waves whatever the survivors' places are; a wave beyond the list's end does nothing.  The result (off and the
+//     neighbour, 11 bits) goes to a u16 plane of the tile in LDS;
+//   * output: a unit's twelve bytes are loaded (zeros behind the tile's own raised flag), a pixel with off > 0 fetches
+//     its neighbour's three bytes straight from memory (zeros behind that tile's flag, the coordinates clamped) and
+//     blends, every unit of the tile is stored;
+//   * with out_clean a tile whose OWN flag is up votes (one barrier) whether any byte of its output is not zero -- colour
+//     came in from a neighbour's edge: its output flag is 1 when none did (the zeros are stored all the same), else 0.
+// LDS: 4608 + 4096 + 4096 bytes.  WIDE: width % 4 == 0 and fb / out 4-byte aligned (the launcher checks): a unit as
+// three aligned words; otherwise the same through bytes guarded by the width.  fb and its flags are only read.  No
+// global atomics, no inline assembly, no scratch.
+constexpr int AA_LDS_W = TILE_W + 2 * AA_MAX_SEARCH, AA_LDS_H = TILE_H + 2 * AA_MAX_SEARCH;
+constexpr int AA_THREADS = 256, AA_UNITS = TILE_W * TILE_H / 4 / AA_THREADS;
+
+// L of the rule from the staged bytes: LDS row 0 is buffer row oy, LDS column 0 frame column ox.
+struct AaTileLuma {
+    const uint8_t *s;
+    int32_t ox, oy;
+    __device__ __forceinline__ int32_t operator()(int32_t x, int32_t y) const { return (int32_t)s[(y - oy) * AA_LDS_W + (x - ox)]; }
+};
+
+template <bool WIDE>
+__global__ __launch_bounds__(AA_THREADS) void k_aa(AaArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H == 16 && AA_UNITS == 2, "32 units to a row of a tile, two rounds of eight rows");
+    static_assert(AA_MAX_SEARCH % 4 == 0 && AA_MAX_SEARCH <= TILE_H && AA_LDS_W % 4 == 0, "the halo lies in the eight tiles around, in whole pieces");
+    static_assert(TILE_W * TILE_H <= 65536, "a pixel's place in the tile fits a u16");
+    __shared__ __align__(16) uint8_t s_l[AA_LDS_H * AA_LDS_W];
+    __shared__ __align__(8) uint16_t s_found[TILE_W * TILE_H];
+    __shared__ uint16_t s_list[TILE_W * TILE_H];
+    __shared__ uint32_t s_n;
+    const uint32_t t = blockIdx.x;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, S = (int32_t)a.rule.search;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t tx = (int32_t)t % ntx, ty = (int32_t)t / ntx;
+    const int32_t x0 = tx * TILE_W, by0 = H - TILE_H - ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): its colour reads as zeros (its flag is up), or no such tile
+    uint32_t czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) czero |= bit;
+            else if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+        }
+    const bool own_zero = (czero & (1u << 4)) != 0u;
+    // the units of k_outline, in buffer rows
+    const int32_t ux = 4 * (int32_t)(threadIdx.x % 32u), x = x0 + ux, row_first = (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = min(4, W - x);  // (WIDE: 4, or the unit is outside)
+    uint32_t px[AA_UNITS][4];
+    if (czero == 0x1FFu) {  // (workgroup-uniform, ahead of the barriers)
+        if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = 1u;
+#pragma unroll
+        for (int h = 0; h < AA_UNITS; h++) {
+            const int32_t by = by0 + row_first + 8 * h;
+            if (x >= W || by < 0) continue;
+            uint8_t *o = a.out + ((size_t)by * (size_t)W + (size_t)x) * 3u;
+            if (WIDE) {
+                uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+                ow[0] = 0u, ow[1] = 0u, ow[2] = 0u;
+            } else {
+                for (int32_t i = 0; i < 3 * n_px; i++) o[i] = 0u;
+            }
+        }
+        return;
+    }
+    if (threadIdx.x == 0u) s_n = 0u;
+    // staging, what lies in the frame: LDS row r is buffer row by0 - S + r, LDS column c frame column x0 - 8 + c
+    const int32_t rows = TILE_H + 2 * S, c_first = AA_MAX_SEARCH - S, c_end = AA_MAX_SEARCH + TILE_W + S;
+    if (WIDE) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (AA_LDS_W / 4); p += AA_THREADS) {
+            const int32_t r = p / (AA_LDS_W / 4), j = p % (AA_LDS_W / 4);
+            if (4 * j + 3 < c_first || 4 * j >= c_end) continue;  // (no pixel of the tile looks at it)
+            const int32_t qx = x0 - AA_MAX_SEARCH + 4 * j, qy = by0 - S + r;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;  // (the clamp, below)
+            const int32_t ax = j < AA_MAX_SEARCH / 4 ? 0 : j < (AA_MAX_SEARCH + TILE_W) / 4 ? 1 : 2;
+            const int32_t ay = qy >= by0 + TILE_H ? 0 : qy >= by0 ? 1 : 2;
+            uint32_t l4 = 0u;
+            if (((czero >> (3 * ay + ax)) & 1u) == 0u) {
+                // four pixels are twelve bytes at a multiple of four: three aligned words
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(a.fb + ((size_t)qy * (size_t)W + (size_t)qx) * 3u);
+                const uint32_t w0 = q[0], w1 = q[1], w2 = q[2];
+                l4 = aa_luma(w0 & 0xFFFFFFu) | (aa_luma((w0 >> 24) | ((w1 & 0xFFFFu) << 8)) << 8) |
+                     (aa_luma((w1 >> 16) | ((w2 & 0xFFu) << 16)) << 16) | (aa_luma(w2 >> 8) << 24);
+            }
+            *reinterpret_cast<uint32_t *>(&s_l[r * AA_LDS_W + 4 * j]) = l4;
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * AA_LDS_W; p += AA_THREADS) {
+            const int32_t r = p / AA_LDS_W, c = p % AA_LDS_W;
+            if (c < c_first || c >= c_end) continue;
+            const int32_t qx = x0 - AA_MAX_SEARCH + c, qy = by0 - S + r;
+            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const int32_t ax = c < AA_MAX_SEARCH ? 0 : c < AA_MAX_SEARCH + TILE_W ? 1 : 2;
+            const int32_t ay = qy >= by0 + TILE_H ? 0 : qy >= by0 ? 1 : 2;
+            uint32_t l = 0u;
+            if (((czero >> (3 * ay + ax)) & 1u) == 0u) {
+                const uint8_t *q = a.fb + ((size_t)qy * (size_t)W + (size_t)qx) * 3u;
+                l = stats_luma(q[0], q[1], q[2]);
+            }
+            s_l[r * AA_LDS_W + c] = (uint8_t)l;
+        }
+    }
+    // the clamp: what lies outside the frame repeats the border pixel, which the pass above has staged (the clamped
+    // coordinates lie in the frame and between the tile and the place they are asked for)
+    if (x0 - S < 0 || x0 + TILE_W + S > W || by0 - S < 0 || by0 + TILE_H + S > H) {  // (workgroup-uniform)
+        __syncthreads();
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * AA_LDS_W; p += AA_THREADS) {
+            const int32_t r = p / AA_LDS_W, c = p % AA_LDS_W;
+            if (c < c_first || c >= c_end) continue;
+            const int32_t qx = x0 - AA_MAX_SEARCH + c, qy = by0 - S + r;
+            if (qx >= 0 && qx < W && qy >= 0 && qy < H) continue;
+            const int32_t cx = aa_clamp(qx, W), cy = aa_clamp(qy, H);
+            s_l[r * AA_LDS_W + c] = s_l[(cy - by0 + S) * AA_LDS_W + (cx - x0 + AA_MAX_SEARCH)];
+        }
+    }
+    __syncthreads();
+    // step 1 on the lane's eight pixels; the survivors go onto the list
+    uint32_t passed = 0u;  // bit 4 * h + i: pixel i of unit h
+#pragma unroll
+    for (int h = 0; h < AA_UNITS; h++) {
+        const int32_t row = row_first + 8 * h;
+        if (x >= W || by0 + row < 0) continue;
+        const uint8_t *base = s_l + (row + S) * AA_LDS_W + AA_MAX_SEARCH + ux;
+        const uint32_t mid = *reinterpret_cast<const uint32_t *>(base);
+        const uint32_t up = *reinterpret_cast<const uint32_t *>(base - AA_LDS_W), dn = *reinterpret_cast<const uint32_t *>(base + AA_LDS_W);
+        // bytes 1..4 of `line` are the unit, byte 0 its left and byte 5 its right neighbour
+        const unsigned long long line = (unsigned long long)base[-1] | ((unsigned long long)mid << 8) | ((unsigned long long)base[4] << 40);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            int32_t range = 0;
+            const bool ok = aa_passes((int32_t)((mid >> (8 * i)) & 0xFFu), (int32_t)((up >> (8 * i)) & 0xFFu), (int32_t)((dn >> (8 * i)) & 0xFFu),
+                                      (int32_t)((line >> (8 * i)) & 0xFFull), (int32_t)((line >> (8 * i + 16)) & 0xFFull), a.rule, &range);
+            if (ok && i < n_px) passed |= 1u << (4 * h + i);
+        }
+        *reinterpret_cast<uint2 *>(&s_found[row * TILE_W + ux]) = make_uint2(0u, 0u);
+    }
+    if (passed != 0u) {
+        uint32_t at = atomicAdd(&s_n, (uint32_t)__popc(passed));  // (LDS; the order of the list does not matter)
+#pragma unroll
+        for (int k = 0; k < 4 * AA_UNITS; k++)
+            if ((passed >> k) & 1u) s_list[at++] = (uint16_t)((row_first + 8 * (k / 4)) * TILE_W + ux + (k % 4));
+    }
+    __syncthreads();
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_n);
+    // steps 2 to 6 on the survivors, a lane each
+    if (n != 0u) {  // (workgroup-uniform)
+        const AaTileLuma L = { s_l, x0 - AA_MAX_SEARCH, by0 - S };
+        for (uint32_t k = threadIdx.x; k < n; k += AA_THREADS) {
+            const int32_t at = (int32_t)s_list[k], lx = at % TILE_W, lr = at / TILE_W;
+            const int32_t gx = x0 + lx, gy = by0 + lr;
+            int32_t range = 0;
+            (void)aa_passes(L(gx, gy), L(gx, gy - 1), L(gx, gy + 1), L(gx - 1, gy), L(gx + 1, gy), a.rule, &range);
+            s_found[at] = (uint16_t)aa_found(L, gx, gy, range, a.rule);
+        }
+        __syncthreads();
+    }
+    // output
+    uint32_t lit = 0u;  // the tile's output bytes, or-ed
+#pragma unroll
+    for (int h = 0; h < AA_UNITS; h++) {
+        const int32_t row = row_first + 8 * h, by = by0 + row;
+#pragma unroll
+        for (int i = 0; i < 4; i++) px[h][i] = 0u;
+        if (x >= W || by < 0) continue;
+        const size_t ci = ((size_t)by * (size_t)W + (size_t)x) * 3u;
+        if (!own_zero) {
+            const uint8_t *q = a.fb + ci;
+            if (WIDE) {
+                const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                px[h][0] = w0 & 0xFFFFFFu;
+                px[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                px[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                px[h][3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) px[h][i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+            }
+        }
+        const uint2 f2 = *reinterpret_cast<const uint2 *>(&s_found[row * TILE_W + ux]);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint32_t found = ((i < 2 ? f2.x : f2.y) >> (16 * (i % 2))) & 0xFFFFu;
+            const uint32_t off = found & AA_OFF_MASK, to = found >> 9;
+            uint32_t fn = 0u;
+            if (off != 0u && (a.rule.flags & AA_SHOW_BLEND) == 0u) {
+                // p + n clamped to the frame; its tile is one of the nine
+                const int32_t cx = aa_clamp(x + i + aa_dx(to), W), cy = aa_clamp(by + aa_dy(to), H);
+                const int32_t ax = cx / TILE_W - tx + 1, ay = (H - 1 - cy) / TILE_H - ty + 1;
+                if (((czero >> (3 * ay + ax)) & 1u) == 0u) {
+                    const uint8_t *q = a.fb + ((size_t)cy * (size_t)W + (size_t)cx) * 3u;
+                    fn = grade_pack(q[0], q[1], q[2]);
+                }
+            }
+            if (i < n_px) px[h][i] = aa_out_px(px[h][i], fn, off, a.rule);
+            lit |= px[h][i];
+        }
+    }
+    if (a.out_clean != nullptr) {  // (workgroup-uniform) behind its own flag: did colour come in from a neighbour's edge?
+        const bool any_lit = !own_zero || __syncthreads_or((int)lit) != 0;
+        if (threadIdx.x == 0u) a.out_clean[t] = any_lit ? 0u : 1u;
+    }
+#pragma unroll
+    for (int h = 0; h < AA_UNITS; h++) {
+        const int32_t by = by0 + row_first + 8 * h;
+        if (x >= W || by < 0) continue;
+        uint8_t *o = a.out + ((size_t)by * (size_t)W + (size_t)x) * 3u;
+        if (WIDE) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = px[h][0] | (px[h][1] << 24);
+            ow[1] = (px[h][1] >> 8) | (px[h][2] << 16);
+            ow[2] = (px[h][2] >> 16) | (px[h][3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(px[h][i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((px[h][i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((px[h][i] >> 16) & 0xFFu);
+                }
+        }
+    }
+}
+
 // Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
 // partial record.  The project's one reduction, in two launches:
 //   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
@@ -4019,6 +4264,30 @@ int launch_outline(const OutlineArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_outline<true>), dim3(n_tiles), dim3(OUTLINE_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_outline<false>), dim3(n_tiles), dim3(OUTLINE_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_aa(const AaArgs &a, hipStream_t st)
+{
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), the search inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (a.frame.width + TILE_W - 1) / TILE_W || a.frame.nty != (a.frame.height + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (a.rule.search < 1u || a.rule.search > (uint32_t)AA_MAX_SEARCH || a.rule.contrast_min > 255u || a.rule.contrast_rel > 256u ||
+        a.rule.subpixel > 256u || (a.rule.flags & ~AA_SHOW_BLEND) != 0u)
+        return (int)hipErrorInvalidValue;
+    // `out` is apart from the frame
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // the wide path: every unit of four pixels three aligned words of either buffer
+    const bool wide = a.frame.width % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_aa<true>), dim3(n_tiles), dim3(AA_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_aa<false>), dim3(n_tiles), dim3(AA_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2807,7 +2807,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve has none); the cleared-scene shortcut where the stage has one --
@@ -4711,6 +4711,123 @@ int tr_outline_kinds(uint32_t width, uint32_t height, const float *z, const tr_o
     if (width == 0u || height == 0u) return TR_OK;
     if (!z || !kinds) return tr::fail(TR_E_INVALID, "tr_outline_kinds: null argument");
     outline_kinds_host(width, height, z, outline_rule(p), kinds);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_AA_MAX_SEARCH == AA_MAX_SEARCH && TR_AA_SHOW_BLEND == AA_SHOW_BLEND && sizeof(tr_aa_params) == 24, "tr_aa.h restates the header");
+
+// tr_aa_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_aa_params(const tr_aa_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_aa_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_aa_params)");
+    if (p->contrast_min > 255u) return tr::fail(TR_E_INVALID, w + ": contrast_min must be 0..255");
+    if (p->contrast_rel > 256u) return tr::fail(TR_E_INVALID, w + ": contrast_rel must be 0..256");
+    if (p->search < 1u || p->search > (uint32_t)TR_AA_MAX_SEARCH) return tr::fail(TR_E_INVALID, w + ": search must be 1..TR_AA_MAX_SEARCH");
+    if (p->subpixel > 256u) return tr::fail(TR_E_INVALID, w + ": subpixel must be 0..256");
+    if (p->flags & ~TR_AA_SHOW_BLEND) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    return TR_OK;
+}
+
+AaRule aa_rule(const tr_aa_params *p)
+{
+    AaRule r;
+    r.contrast_min = p->contrast_min;
+    r.contrast_rel = p->contrast_rel;
+    r.search = p->search;
+    r.subpixel = p->subpixel;
+    r.flags = p->flags;
+    return r;
+}
+
+int check_aa_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be anti-aliased: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// Enqueues the filtered current frame into `out_device` (which overlaps no frame of the scene) behind everything issued
+// so far; out_clean: null, or where k_aa writes the flags of `out_device`.  The scene is not logically cleared.  No depth
+// is read: a depth left on the chip stays there.
+int enqueue_aa(tr_scene *s, const tr_aa_params *p, uint8_t *out_device, uint32_t *out_clean)
+{
+    int st = submit_pending(s);
+    if (st != TR_OK) return st;
+    AaArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+    a.rule = aa_rule(p);
+    {
+        Timed t(s, K_AA);
+        int rc = launch_aa(a, s->stream);
+        if (rc) return launch_status(rc, "k_aa");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_antialias(tr_scene *s, const tr_aa_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_antialias: null scene");
+    int st = check_aa_params(p, "tr_scene_antialias");
+    if (st == TR_OK) st = check_aa_scene(s, "tr_scene_antialias");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_antialias", "tr_scene_get_antialiased", "filters", 0u, &target);
+    if (st != TR_OK) return st;
+    // a logically cleared frame is black and has no edge: zeros out of place, itself in place
+    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_aa(s, p, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_antialiased(tr_scene *s, const tr_aa_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_antialiased: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_antialiased: null argument");
+    int st = check_aa_params(p, "tr_scene_get_antialiased");
+    if (st == TR_OK) st = check_aa_scene(s, "tr_scene_get_antialiased");
+    if (st != TR_OK) return st;
+    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_aa(s, p, o, nullptr); });
+}
+
+// The rule of tr_aa.h over a caller's array, on the host.  Needs no GPU.
+int tr_aa_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out, const tr_aa_params *p)
+{
+    int st = check_aa_params(p, "tr_aa_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_aa_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_aa_host: out is rgb (the rule reads neighbours: not in place)");
+    aa_host(width, height, rgb, out, aa_rule(p));
+    return TR_OK;
+}
+
+// The rule's two divisions by the inline functions of tr_aa.h, for an exhaustive check.
+int tr_aa_quotients(uint32_t which, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out)
+{
+    if (which > 1u) return tr::fail(TR_E_INVALID, "tr_aa_quotients: which must be 0 (edge term) or 1 (tq)");
+    if (n == 0u) return TR_OK;
+    if (!a || !b || !out) return tr::fail(TR_E_INVALID, "tr_aa_quotients: null argument");
+    for (uint32_t i = 0; i < n; i++) {
+        const bool ok = which == 0u ? (a[i] >= 2u && a[i] <= 2u * AA_MAX_SEARCH && b[i] >= 1u && b[i] <= a[i] / 2u) : (a[i] <= 3060u && b[i] >= 1u && b[i] <= 255u);
+        if (!ok) return tr::fail(TR_E_INVALID, "tr_aa_quotients: a pair outside the rule's ranges");
+    }
+    for (uint32_t i = 0; i < n; i++) out[i] = which == 0u ? aa_edge_offset(a[i], b[i]) : aa_tq(a[i], b[i]);
     return TR_OK;
 }
 

@@ -405,6 +405,49 @@ def outline_kinds(z, params):
     return out
 
 
+AA_MAX_SEARCH, AA_SHOW_BLEND = 8, 1   # (TR_AA_MAX_SEARCH, TR_AA_SHOW_BLEND)
+
+
+class AaParams(C.Structure):
+    """tr_aa_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("contrast_min", C.c_uint32), ("contrast_rel", C.c_uint32), ("search", C.c_uint32),
+                ("subpixel", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def aa_params(contrast_min=8, contrast_rel=32, search=8, subpixel=192, show_blend=False):
+    """tr_aa_params for Scene.antialias / Scene.get_antialiased / aa_host: a pixel is filtered when the luma range of
+    itself and its four neighbours reaches contrast_min (0..255) and contrast_rel / 256 (0..256) of their brightest; the
+    edge's ends are looked for up to `search` pixels away (1..8); subpixel (0..256) weighs the term that pulls a lone
+    pixel towards its surroundings; show_blend=True shows the blend weight instead of the picture (AA_SHOW_BLEND).
+    ValueError for what the library would refuse (include/tiny_renderer.h)."""
+    for name, v in (("contrast_min", contrast_min), ("contrast_rel", contrast_rel), ("search", search), ("subpixel", subpixel)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("antialias: %s must be an integer" % name)
+    if not 0 <= contrast_min <= 255:
+        raise ValueError("antialias: contrast_min must be 0..255")
+    if not 0 <= contrast_rel <= 256:
+        raise ValueError("antialias: contrast_rel must be 0..256")
+    if not 1 <= search <= AA_MAX_SEARCH:
+        raise ValueError("antialias: search must be 1..%d pixels" % AA_MAX_SEARCH)
+    if not 0 <= subpixel <= 256:
+        raise ValueError("antialias: subpixel must be 0..256")
+    return AaParams(C.sizeof(AaParams), int(contrast_min), int(contrast_rel), int(search), int(subpixel), AA_SHOW_BLEND if show_blend else 0)
+
+
+def aa_host(rgb, params):
+    """tr_aa_host: the rule of Scene.antialias on the host (no GPU needed), by the inline functions k_aa calls.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from aa_params.  Returns the filtered frame and leaves its
+    arguments alone."""
+    if not isinstance(params, AaParams):
+        raise ValueError("aa_host: params must come from aa_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("aa_host: rgb [H, W, 3]")
+    out = np.empty_like(src)
+    check(load_library().tr_aa_host(src.shape[1], src.shape[0], src.ctypes.data, out.ctypes.data, C.addressof(params)))
+    return out
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1209,6 +1252,27 @@ class Scene:
         if not isinstance(params, OutlineParams):
             raise ValueError("get_outlined: params must come from outline_params")
         return self._image("tr_scene_get_outlined", strict, C.addressof(params))
+
+    # --- edge anti-aliasing (tr_scene_antialias / tr_scene_get_antialiased) ---------------------------
+    def antialias(self, params, out=None):
+        """tr_scene_antialias: smooths the current frame's stair-steps on the device by a luma-driven edge filter (params
+        from aa_params), at the frame's own size.  out=None: in place (through a scratch frame of the scene's) -- every
+        later consumer sees the filtered frame, z, winner words and the shadow buffer stay, calling it twice filters
+        twice.  Otherwise `out` is a device pointer (int) to 3 * W * H bytes apart from every frame buffer of the scene,
+        or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after
+        sync().  Band scenes are refused.  No depth is read."""
+        if not isinstance(params, AaParams):
+            raise ValueError("antialias: params must come from aa_params")
+        ptr = self._out_pointer(out)
+        check(load_library().tr_scene_antialias(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_antialiased(self, params, strict=True):
+        """tr_scene_get_antialiased: the current frame filtered on the device, as an [H, W, 3] uint8 array.  Synchronizes;
+        the scene's frame stays as it is."""
+        if not isinstance(params, AaParams):
+            raise ValueError("get_antialiased: params must come from aa_params")
+        return self._image("tr_scene_get_antialiased", strict, C.addressof(params))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
