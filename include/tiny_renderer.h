@@ -920,6 +920,65 @@ int tr_aa_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out
  * when which == 1.  TR_E_INVALID for another `which`, a NULL pointer with n > 0, or a pair outside those ranges. */
 int tr_aa_quotients(uint32_t which, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);
 
+/* Resize: the scene's CURRENT frame, W x H, scaled on the device to any width x height -- 1920 x 1080 from 4096^2, a
+ * thumbnail, a x 1.5 preview, a half-size render shown at full size -- by a separable filter with integer weights, the
+ * last step of the chain (render, composite, ..., antialias, RESIZE, read back or tr_scene_set_texture_device).  F is
+ * the image tr_scene_get_frame_buffer would return and `out` has its orientation (row 0 = top), tightly packed rgb8.
+ * The axes are independent (the two ratios may differ).  For ONE axis with N source and M output samples, output index X
+ * gets raw integer taps o[x] over the source indices x in [0, N):
+ *   TR_RESIZE_AREA      o[x] = max(0, min((x + 1) M, (X + 1) N) - max(x M, X N)): the overlap of the two pixels'
+ *                       intervals in units of 1 / (N M);
+ *   TR_RESIZE_BILINEAR  a triangle whose support grows with the ratio when minifying: S = 2 max(M, N), C = (2 X + 1) N,
+ *                       o[x] = max(0, S - |(2 x + 1) M - C|); taps that would fall outside [0, N) are dropped, not
+ *                       clamped, and the normalisation makes up for them.
+ * The taps with o[x] > 0 form one run x0 .. x0 + n - 1 and their weights sum to exactly 4096 by cumulative rounding:
+ * O = sum of o, cum_k = o[x0] + .. + o[x0 + k], c_k = (4096 cum_k + O / 2) / O (integer division), w_k = c_k - c_(k-1)
+ * with c_(-1) = 0; a weight may come out 0 and is kept.  Then
+ *     out[Y][X][c] = ( sum_j wy[Y][j] * ( sum_k wx[X][k] * F[y0(Y) + j][x0(X) + k][c] ) + 2^23 ) >> 24
+ * with the inner sum unrounded; everything fits 32 bits.  So: the same size is a copy, a constant frame stays constant,
+ * and TR_RESIZE_AREA at W / f x H / f, f = 2, 4, 8, equals tr_scene_resolve(f) in every byte.  No gamma.
+ * Limits: ceil(N / 8) <= M <= 8192 on each axis -- a minification beyond 8 is refused, a magnification is bounded by the
+ * size alone --, within which a run has at most TR_RESIZE_MAX_TAPS taps; filter is one of the two; flags must be 0. */
+#define TR_RESIZE_AREA 0u
+#define TR_RESIZE_BILINEAR 1u
+#define TR_RESIZE_MAX_TAPS 16
+typedef struct tr_resize_params {
+    uint32_t width, height; /* of the output, each 1..8192 and at least an eighth of the frame's, rounded up */
+    uint32_t filter;        /* TR_RESIZE_AREA or TR_RESIZE_BILINEAR */
+    uint32_t flags;         /* 0 */
+} tr_resize_params;
+/* Resizes the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_resolve: frames held
+ * back are submitted, a pending clear is made real, k_resize is enqueued on the scene's stream behind the renders issued
+ * so far (no depth is read, so a depth left on the chip stays there), a later render is ordered behind it, the result is
+ * there after tr_scene_sync.  The scene's passes issued so far count as handed on.  The weights are computed on the
+ * host; their tables are kept on the scene for the last (width, height, filter) and uploaded again, in stream order,
+ * only when that changes.  An output tile whose whole source footprint has its colour fast-clear flags up is stored as
+ * zeros without a load.
+ * out: 3 * width * height bytes of device memory, or memory from tr_host_alloc (the kernel stores through its mapped
+ * address; the buffer's sparse read-back record lapses); every byte of it is written on every call.  The output is no
+ * frame of the scene: there is no in-place form and out == NULL is refused.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since) is black at every size: `out` becomes
+ * zeros (hipMemsetAsync, no kernel).
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene, params
+ * or out, flags != 0, an unknown filter, a width or height outside the limits above, ordinary host memory as `out`, a
+ * pinned buffer that is too small, and a BAND scene (tr_options.band_row0/1 set): the taps at a band's border lie in
+ * rows another rank owns. */
+int tr_scene_resize(tr_scene *s, const tr_resize_params *p, void *out);
+/* The same into any host memory (3 * p->width * p->height bytes): waits for the scene first, resizes into a buffer of
+ * the library's, copies out and returns the frame's sticky status, like tr_scene_get_resolved.  A cleared scene gives
+ * zeros. */
+int tr_scene_get_resized(tr_scene *s, const tr_resize_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), through the tables k_resize is fed.  rgb: 3 * width * height bytes, out:
+ * 3 * p->width * p->height bytes, both row 0 = top; out must not be rgb.  The same parameter checks, with width and
+ * height (each >= 1) in the frame's place. */
+int tr_resize_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr_resize_params *p, uint8_t *out /* != rgb */);
+/* The tables of one axis as the kernel is fed them, for checking them against the rule: for every output index X the
+ * first source index of its run, the run's length (1..TR_RESIZE_MAX_TAPS) and its weights, zeros beyond the length.
+ * TR_E_INVALID for an unknown filter, an n_dst outside ceil(n_src / 8)..8192, n_src == 0 or a NULL pointer. */
+int tr_resize_taps(uint32_t filter, uint32_t n_src, uint32_t n_dst, uint16_t *first /* n_dst */, uint16_t *count /* n_dst */,
+                   uint16_t *weights /* n_dst * TR_RESIZE_MAX_TAPS, zero-padded */);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -111,6 +111,11 @@ def main(argv=None):
     ap.add_argument("--aa-search", type=int, default=8, metavar="N", help="look for an edge's ends up to N pixels away (1..8, default 8)")
     ap.add_argument("--aa-subpixel", type=int, default=192, metavar="N", help="the weight of the sub-pixel term (0..256, default 192; 0: edges only)")
     ap.add_argument("--aa-show-blend", action="store_true", help="with --aa: the blend weight the filter found instead of the picture")
+    ap.add_argument("--out-size", default=None, metavar="WxH",
+                    help="resize: write the picture scaled to W x H (each 1..8192 and at least an eighth of the rendered side) on "
+                         "the GPU (Scene.resize; applied last, after --aa, in the place of the --ssaa resolve)")
+    ap.add_argument("--resize-filter", default="area", choices=("area", "bilinear"),
+                    help="the filter of --out-size: area (pixel overlap; default) or bilinear (a triangle that widens when shrinking)")
     ap.add_argument("--auto-levels", default=None, metavar="LOW,HIGH",
                     help="colour grading by a table made from the picture itself: its luma percentiles LOW and HIGH (e.g. 0.01,0.99), "
                          "found on the GPU (Scene.get_frame_stats), stretched to black and white (lut_auto_levels; in the place of "
@@ -250,6 +255,22 @@ def main(argv=None):
         ap.error("--morph-to poses the scene of one GPU, by frame count: use --gpus 1 and --frames")
     if args.ssaa > 1 and (args.gpus > 1 or args.view != "frame"):
         ap.error("--ssaa resolves the colour frame of one GPU: use --gpus 1 and --view frame")
+    args.resize = None
+    if args.out_size is not None:
+        try:
+            w, h = (int(v) for v in args.out_size.lower().split("x"))
+        except ValueError:
+            ap.error("--out-size takes two integers: WxH")
+        if args.ssaa > 1:
+            ap.error("--out-size does not go with --ssaa: render large (-W, -H) and resize with --resize-filter area instead")
+        if args.gpus > 1 or args.view != "frame":
+            ap.error("--out-size resizes the colour frame of one GPU: use --gpus 1 and --view frame")
+        from .scene import resize_params
+        try:
+            resize_params(args.width, args.height, w, h, args.resize_filter, "--out-size")
+        except ValueError as e:
+            ap.error(str(e))
+        args.resize = (w, h, args.resize_filter)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.instances < 1:
@@ -417,7 +438,7 @@ def _run(args, T, scene, sharded, rank, say):
             scene.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
             scene.render()
             if not args.no_readback:
-                img = _view(scene, args.view, args.ssaa)
+                img = _view(scene, args.view, args.ssaa, args.resize)
             elif fps_counter % 64 == 63:
                 scene.sync()  # keep the queue bounded
             fps_counter += 1
@@ -426,7 +447,7 @@ def _run(args, T, scene, sharded, rank, say):
                 fps_counter, fps_t = 0, now
         scene.sync()
         if args.out:
-            img = _view(scene, args.view, args.ssaa)
+            img = _view(scene, args.view, args.ssaa, args.resize)
             if rank == 0:
                 write_frame(T, args.out, img)
         return 0
@@ -508,7 +529,7 @@ def _run(args, T, scene, sharded, rank, say):
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
             % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
                T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
-    img = _view(scene, args.view, args.ssaa)
+    img = _view(scene, args.view, args.ssaa, args.resize)
     dt = time.perf_counter() - t0
     say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238
     if args.out and rank == 0:
@@ -516,7 +537,9 @@ def _run(args, T, scene, sharded, rank, say):
     return 0
 
 
-def _view(scene, view, ssaa=1):
+def _view(scene, view, ssaa=1, resize=None):
+    if resize is not None:   # (--view frame, --ssaa 1: main() has seen to it)
+        return scene.resize(*resize)
     if view == "frame":
         return scene.resolve(ssaa) if ssaa > 1 else scene.get_frame_buffer()
     return {"z": scene.get_z_buffer, "shadow": scene.get_shadow_buffer}[view]()

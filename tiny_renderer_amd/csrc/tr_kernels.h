@@ -15,6 +15,7 @@
 #include "tr_morph.h"
 #include "tr_outline.h"
 #include "tr_pack.h"
+#include "tr_resize.h"
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
 #include "tr_stats.h"
@@ -110,6 +111,10 @@ int launch_outline(const OutlineArgs &a, hipStream_t st);
 // neighbours), through the scene's colour fast-clear flags: k_aa.  The whole frame only (no band).  a.out_clean: null, or
 // where each workgroup writes the flag of its tile of a.out -- a tile flagged there is zeros in every byte.
 int launch_aa(const AaArgs &a, hipStream_t st);
+// Resize: a.fb scaled to a.out (a.out_w x a.out_h, apart from it) by the rule of tr_resize.h through the tables a.x and a.y
+// (device memory, built by resize_axis on the host) and the scene's colour fast-clear flags: k_resize, in the shape
+// a.shape of kResizeShapes, which the vertical table must fit (a.y_span).  The whole frame only (no band); no depth is read.
+int launch_resize(const ResizeArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

@@ -3239,6 +3239,122 @@ __global__ __launch_bounds__(AA_THREADS) void k_aa(AaArgs a)
     }
 }
 
+// Resize (tr_scene_resize): the frame scaled to out_w x out_h by the separable integer filter of tr_resize.h.  The rule's
+// divisions were done on the host; the kernel gets, per axis, first index | count << 16 and RESIZE_MAX_TAPS u16 weights
+// to an output index, and multiplies and adds in u32.  One workgroup of 256 lanes per tile of OTW x OTH OUTPUT pixels
+// (kResizeShapes: the launcher's caller chose the shape so that the source rows a tile's OTH rows reach over are at most
+// ROWS).  Everything is in BUFFER rows (row 0 = top); source tile row ty is buffer rows H - 16 - 16 ty onwards.
+//   * footprint: the tile's source columns and rows from the tables' first and last entries (the runs move monotonically),
+//     the colour flags of the 128 x 16 source tiles it touches to LDS -- at most 6 x 5 of them -- and one vote: all up,
+//     and the tile is stored as zeros without a load;
+//   * phase 1: a lane owns ONE output column of the tile -- its run's weights stay in registers, two 16-byte loads --
+//     and walks the footprint's source rows 256 / OTW apart: the run's pixels from memory as bytes, the part of the run
+//     behind a raised flag contributing zeros without a load (a run of at most 16 pixels lies in at most two source
+//     tiles), three unrounded u32 sums to LDS, row-major, 3 OTW words a row;
+//   * phase 2: a lane per output BYTE (row, 3 x + c): consecutive lanes read consecutive words of LDS, the row's
+//     weights come from LDS; round, shift, and the byte goes to a staging tile in LDS;
+//   * stores from the staging tile: 12-byte units of four pixels as three aligned words where WIDE (out_w % 4 == 0 and
+//     `out` 4-byte aligned: the launcher checks), otherwise bytes, consecutive lanes consecutive bytes, guarded by the
+//     output's width and height.  Every byte of `out` is written.
+// LDS: ROWS * OTW * 12 + OTW * OTH * 3 + OTH * (32 + 4) + 128 bytes.  No global atomics, no inline assembly, no scratch.
+constexpr int RESIZE_THREADS = 256, RESIZE_FLAGS_W = 6, RESIZE_FLAGS_H = 5;
+
+template <int OTW, int OTH, int ROWS, bool WIDE>
+__global__ __launch_bounds__(RESIZE_THREADS) void k_resize(ResizeArgs a)
+{
+    static_assert(RESIZE_THREADS % OTW == 0 && OTW % 4 == 0 && OTW * OTH / 4 <= RESIZE_THREADS, "a lane keeps its column; a unit a lane at most");
+    static_assert((OTW - 1) * 8 + 1 + RESIZE_MAX_TAPS <= (RESIZE_FLAGS_W - 1) * TILE_W + 1 && ROWS <= (RESIZE_FLAGS_H - 1) * TILE_H + 1,
+                  "the footprint's source tiles fit the flag array");
+    static_assert(OTH * RESIZE_MAX_TAPS <= RESIZE_THREADS && RESIZE_FLAGS_W * RESIZE_FLAGS_H <= RESIZE_THREADS, "one lane a weight, one a flag");
+    __shared__ uint32_t s_sum[ROWS * OTW * 3];
+    __shared__ __align__(4) uint8_t s_out[OTH * OTW * 3];
+    __shared__ uint16_t s_wy[OTH * RESIZE_MAX_TAPS];
+    __shared__ uint32_t s_fcy[OTH];
+    __shared__ uint32_t s_zero[RESIZE_FLAGS_W * RESIZE_FLAGS_H];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, ntx = (int32_t)a.frame.ntx;
+    const int32_t Wd = (int32_t)a.out_w, Hd = (int32_t)a.out_h;
+    const int32_t X0 = (int32_t)blockIdx.x * OTW, Y0 = (int32_t)blockIdx.y * OTH;
+    const int32_t n_x = min(OTW, Wd - X0), n_y = min(OTH, Hd - Y0);  // the tile's columns and rows inside the output (>= 1)
+    // the footprint (workgroup-uniform): source columns [sx0, sx1], buffer rows [sy0, sy1]
+    const uint32_t fx_a = a.x.fc[X0], fx_b = a.x.fc[X0 + n_x - 1], fy_a = a.y.fc[Y0], fy_b = a.y.fc[Y0 + n_y - 1];
+    const int32_t sx0 = (int32_t)(fx_a & 0xFFFFu), sx1 = (int32_t)(fx_b & 0xFFFFu) + (int32_t)(fx_b >> 16) - 1;
+    const int32_t sy0 = (int32_t)(fy_a & 0xFFFFu), sy1 = (int32_t)(fy_b & 0xFFFFu) + (int32_t)(fy_b >> 16) - 1;
+    const int32_t n_rows = min(sy1 - sy0 + 1, ROWS);  // (the shape was chosen so that the min changes nothing)
+    // its source tiles: columns ftx0 .. ftx1, tile rows fty0 (of buffer row sy1, the lowest) .. fty1
+    const int32_t ftx0 = sx0 / TILE_W, ftx1 = sx1 / TILE_W, fty0 = (H - 1 - sy1) / TILE_H, fty1 = (H - 1 - sy0) / TILE_H;
+    const int32_t fw = ftx1 - ftx0 + 1, fh = fty1 - fty0 + 1;
+    bool up = true;
+    if ((int32_t)threadIdx.x < fw * fh) {  // (fw <= RESIZE_FLAGS_W, fh <= RESIZE_FLAGS_H: the launcher checks the spans)
+        const int32_t fx = (int32_t)threadIdx.x % fw, fy = (int32_t)threadIdx.x / fw;
+        up = a.fbclean != nullptr && a.fbclean[(fty0 + fy) * ntx + ftx0 + fx] != 0u;
+        s_zero[fy * RESIZE_FLAGS_W + fx] = up ? 1u : 0u;
+    }
+    if ((int32_t)threadIdx.x < n_y * RESIZE_MAX_TAPS)
+        s_wy[threadIdx.x] = a.y.w[(size_t)Y0 * RESIZE_MAX_TAPS + threadIdx.x];
+    if ((int32_t)threadIdx.x < n_y) s_fcy[threadIdx.x] = a.y.fc[Y0 + (int32_t)threadIdx.x];
+    const bool zeros = __syncthreads_and((int)up) != 0;  // (also the barrier behind the three arrays)
+    if (!zeros) {  // (workgroup-uniform)
+        // phase 1
+        const int32_t lx = (int32_t)threadIdx.x % OTW;
+        if (lx < n_x) {
+            const uint32_t fc = a.x.fc[X0 + lx];
+            const int32_t x0 = (int32_t)(fc & 0xFFFFu), n = (int32_t)(fc >> 16);
+            const uint4 *wp = reinterpret_cast<const uint4 *>(a.x.w + (size_t)(X0 + lx) * RESIZE_MAX_TAPS);
+            const uint4 wa = wp[0], wb = wp[1];
+            const uint32_t w2[RESIZE_MAX_TAPS / 2] = { wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w };
+            // the run lies in source tile column x0 / 128 up to `split`, in the next one from there
+            const int32_t fc0 = x0 / TILE_W - ftx0, split = (x0 / TILE_W + 1) * TILE_W;
+            const int32_t fc1 = (x0 + n - 1) / TILE_W - ftx0;
+            for (int32_t r = (int32_t)threadIdx.x / OTW; r < n_rows; r += RESIZE_THREADS / OTW) {
+                const int32_t sy = sy0 + r, fr = ((H - 1 - sy) / TILE_H - fty0) * RESIZE_FLAGS_W;
+                const bool z0 = s_zero[fr + fc0] != 0u, z1 = s_zero[fr + fc1] != 0u;
+                uint32_t acc0 = 0u, acc1 = 0u, acc2 = 0u;
+                if (!(z0 && z1)) {
+                    const uint8_t *p = a.fb + ((size_t)sy * (size_t)W + (size_t)x0) * 3u;
+#pragma unroll
+                    for (int k = 0; k < RESIZE_MAX_TAPS; k++) {
+                        if (k >= n) break;
+                        const uint32_t w = (w2[k / 2] >> (16 * (k % 2))) & 0xFFFFu;
+                        if (x0 + k < split ? z0 : z1) continue;
+                        acc0 += w * (uint32_t)p[3 * k + 0];
+                        acc1 += w * (uint32_t)p[3 * k + 1];
+                        acc2 += w * (uint32_t)p[3 * k + 2];
+                    }
+                }
+                uint32_t *d = &s_sum[(r * OTW + lx) * 3];
+                d[0] = acc0, d[1] = acc1, d[2] = acc2;
+            }
+        }
+        __syncthreads();
+        // phase 2
+        for (int32_t v = (int32_t)threadIdx.x; v < n_y * OTW * 3; v += RESIZE_THREADS) {
+            const int32_t ly = v / (OTW * 3), j = v % (OTW * 3);
+            if (j >= n_x * 3) continue;
+            const uint32_t fc = s_fcy[ly];
+            const int32_t r0 = (int32_t)(fc & 0xFFFFu) - sy0, n = (int32_t)(fc >> 16);
+            uint32_t acc = 1u << 23;
+            for (int32_t k = 0; k < n; k++) acc += (uint32_t)s_wy[ly * RESIZE_MAX_TAPS + k] * s_sum[min(r0 + k, n_rows - 1) * (OTW * 3) + j];
+            s_out[ly * (OTW * 3) + j] = (uint8_t)(acc >> 24);
+        }
+        __syncthreads();
+    }
+    // stores
+    if (WIDE) {
+        const int32_t u = (int32_t)threadIdx.x, ly = u / (OTW / 4), ux = 4 * (u % (OTW / 4));
+        if (ly < n_y && ux < n_x) {  // (out_w % 4 == 0: a unit lies inside the output or outside it)
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(&s_out[ly * (OTW * 3) + ux * 3]);
+            uint32_t *o = reinterpret_cast<uint32_t *>(a.out + ((size_t)(Y0 + ly) * (size_t)Wd + (size_t)(X0 + ux)) * 3u);
+            o[0] = zeros ? 0u : q[0], o[1] = zeros ? 0u : q[1], o[2] = zeros ? 0u : q[2];
+        }
+    } else {
+        for (int32_t v = (int32_t)threadIdx.x; v < n_y * OTW * 3; v += RESIZE_THREADS) {
+            const int32_t ly = v / (OTW * 3), j = v % (OTW * 3);
+            if (j >= n_x * 3) continue;
+            a.out[((size_t)(Y0 + ly) * (size_t)Wd + (size_t)X0) * 3u + (size_t)j] = zeros ? (uint8_t)0u : s_out[ly * (OTW * 3) + j];
+        }
+    }
+}
+
 // Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
 // partial record.  The project's one reduction, in two launches:
 //   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
@@ -4288,6 +4404,38 @@ int launch_aa(const AaArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_aa<true>), dim3(n_tiles), dim3(AA_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_aa<false>), dim3(n_tiles), dim3(AA_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int I>
+static void launch_resize_shape(const ResizeArgs &a, bool wide, hipStream_t st)
+{
+    constexpr ResizeShape S = kResizeShapes[I];
+    const dim3 grid((a.out_w + S.w - 1) / S.w, (a.out_h + S.h - 1) / S.h);
+    if (wide)
+        hipLaunchKernelGGL((k_resize<S.w, S.h, S.rows, true>), grid, dim3(RESIZE_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_resize<S.w, S.h, S.rows, false>), grid, dim3(RESIZE_THREADS), 0, st, a);
+}
+
+int launch_resize(const ResizeArgs &a, hipStream_t st)
+{
+    if (!a.fb || !a.out || !a.x.fc || !a.x.w || !a.y.fc || !a.y.w) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (the flags are indexed by it), the rule's limits, a shape the tables fit
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (a.frame.width + TILE_W - 1) / TILE_W || a.frame.nty != (a.frame.height + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (!resize_side_ok(a.frame.width, a.out_w) || !resize_side_ok(a.frame.height, a.out_h)) return (int)hipErrorInvalidValue;
+    if (a.shape < 0 || a.shape >= RESIZE_SHAPES || a.y_span > (uint32_t)kResizeShapes[a.shape].rows) return (int)hipErrorInvalidValue;
+    if (a.x_span > (uint32_t)(RESIZE_FLAGS_W - 1) * TILE_W + 1u || (uintptr_t)a.x.w % 16u != 0u) return (int)hipErrorInvalidValue;
+    // `out` is apart from the frame
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u, out_bytes = (size_t)a.out_w * a.out_h * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + out_bytes) return (int)hipErrorInvalidValue;
+    // the wide path: every unit of four output pixels three aligned words
+    const bool wide = a.out_w % 4u == 0u && (uintptr_t)a.out % 4u == 0u;
+    if (a.shape == 0) launch_resize_shape<0>(a, wide, st);
+    else if (a.shape == 1) launch_resize_shape<1>(a, wide, st);
+    else launch_resize_shape<2>(a, wide, st);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -403,6 +403,17 @@ struct tr_scene {
     // pieces; lut_c0: its entry 0, what a cleared tile becomes.  lut_n == 0: no table
     uint32_t *d_lut = nullptr;
     uint32_t lut_n = 0, lut_c0 = 0;
+    // tr_scene_resize: the two axes' tables of the last (width, height, filter) asked for (width == 0: none) in one device
+    // block `d`, the page-locked block `h` they are uploaded from and the event behind the last upload (resize_tables);
+    // shape, y_span and x_span: what launch_resize wants to know of them
+    struct ResizeTables {
+        uint8_t *d = nullptr, *h = nullptr;
+        hipEvent_t uploaded = nullptr;
+        uint32_t width = 0, height = 0, filter = 0;
+        ResizeTable x = {}, y = {};
+        int shape = -1;
+        uint32_t y_span = 0, x_span = 0;
+    } resize;
     // tr_scene_debug_grade_grid: the most workgroups a k_grade launch may start (0: no cap) and what the last one started
     uint32_t grade_cap = 0, grade_grid = 0;
     // tr_scene_frame_stats: the slots k_stats' workgroups store their partial records to (stats_slots of them, allocated
@@ -2520,6 +2531,9 @@ void destroy(tr_scene *s)
     dev_free(s->d_dof_fb);
     dev_free(s->d_dof_clean);
     dev_free(s->d_lut);
+    dev_free(s->resize.d);
+    if (s->resize.h) (void)hipHostFree(s->resize.h);
+    if (s->resize.uploaded) (void)hipEventDestroy(s->resize.uploaded);
     dev_free(s->d_stats_partials);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
@@ -2807,10 +2821,10 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, resize) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
-//   for a non-null `out`, then refuse_overlap (resolve has none); the cleared-scene shortcut where the stage has one --
+//   for a non-null `out`, then refuse_overlap (resolve and resize have none); the cleared-scene shortcut where the stage has one --
 //   cleared_out_of_place, while in place a cleared frame is its own result and NOTHING happens, handed_on included; the
 //   enqueue_* into the target, into the frame itself, or through the scratch frame (in_place_via_scratch); handed_on.
 //   tr_scene_get_<stage>: the same checks, then get_stage.
@@ -4828,6 +4842,169 @@ int tr_aa_quotients(uint32_t which, uint32_t n, const uint32_t *a, const uint32_
         if (!ok) return tr::fail(TR_E_INVALID, "tr_aa_quotients: a pair outside the rule's ranges");
     }
     for (uint32_t i = 0; i < n; i++) out[i] = which == 0u ? aa_edge_offset(a[i], b[i]) : aa_tq(a[i], b[i]);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_RESIZE_AREA == RESIZE_AREA && TR_RESIZE_BILINEAR == RESIZE_BILINEAR && TR_RESIZE_MAX_TAPS == RESIZE_MAX_TAPS &&
+                  sizeof(tr_resize_params) == 16,
+              "tr_resize.h restates the header");
+
+// tr_resize_params as every entry point accepts them for a source of src_w x src_h pixels (`who` names the entry point
+// in the error text).
+int check_resize_params(const tr_resize_params *p, uint32_t src_w, uint32_t src_h, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->flags != 0u) return tr::fail(TR_E_INVALID, w + ": flags must be 0");
+    if (p->filter != TR_RESIZE_AREA && p->filter != TR_RESIZE_BILINEAR)
+        return tr::fail(TR_E_INVALID, w + ": filter must be TR_RESIZE_AREA or TR_RESIZE_BILINEAR");
+    if (p->width < 1u || p->width > RESIZE_MAX_SIDE || p->height < 1u || p->height > RESIZE_MAX_SIDE)
+        return tr::fail(TR_E_INVALID, w + ": width and height must be 1..8192");
+    if (src_w < 1u || src_h < 1u) return tr::fail(TR_E_INVALID, w + ": the source is empty");
+    if (!resize_side_ok(src_w, p->width) || !resize_side_ok(src_h, p->height))
+        return tr::fail(TR_E_INVALID, w + ": a side shrinks by more than 8 (width and height must be at least an eighth of the source's, rounded up)");
+    return TR_OK;
+}
+
+int check_resize_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be resized: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+size_t resized_bytes(const tr_resize_params *p) { return (size_t)p->width * p->height * 3; }
+
+// The device tables of (p->width, p->height, p->filter): the scene keeps those of its last call and builds and uploads
+// others only when the key changes -- through one page-locked block, on the scene's stream, so behind every k_resize
+// that still reads the old ones; the host waits for the previous upload alone before it writes the block again.
+int resize_tables(tr_scene *s, const tr_resize_params *p)
+{
+    tr_scene::ResizeTables &t = s->resize;
+    if (t.d && t.width == p->width && t.height == p->height && t.filter == p->filter) return TR_OK;
+    ResizeAxis ax, ay;
+    if (!ax.build(p->filter, s->width, p->width) || !ay.build(p->filter, s->height, p->height))
+        return tr::fail(TR_E_INVALID, "resize: a run of taps longer than TR_RESIZE_MAX_TAPS");
+    const int shape = resize_shape(ay);
+    if (shape < 0) return tr::fail(TR_E_INVALID, "resize: the vertical table fits no shape of k_resize");
+    // one block for every size: the weights of x, of y, then first | count << 16 of x, of y
+    const size_t cap = (size_t)2 * RESIZE_MAX_SIDE * (RESIZE_MAX_TAPS * sizeof(uint16_t) + sizeof(uint32_t));
+    if (!t.d) {
+        int st = dev_alloc(&t.d, cap);
+        if (st != TR_OK) return st;
+    }
+    if (!t.h) HIP_TRY(hipHostMalloc((void **)&t.h, cap, hipHostMallocDefault));
+    if (!t.uploaded) HIP_TRY(hipEventCreateWithFlags(&t.uploaded, hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(t.uploaded));
+    t.width = 0u;  // (no key while the block is being rewritten: a failure below leaves no tables)
+    const size_t wx = 0, wy = wx + ax.weights.size() * sizeof(uint16_t), fx = wy + ay.weights.size() * sizeof(uint16_t);
+    const size_t fy = fx + (size_t)p->width * sizeof(uint32_t), bytes = fy + (size_t)p->height * sizeof(uint32_t);
+    memcpy(t.h + wx, ax.weights.data(), wy - wx);
+    memcpy(t.h + wy, ay.weights.data(), fx - wy);
+    uint32_t *fcx = (uint32_t *)(t.h + fx), *fcy = (uint32_t *)(t.h + fy);
+    for (uint32_t i = 0; i < p->width; i++) fcx[i] = (uint32_t)ax.first[i] | ((uint32_t)ax.count[i] << 16);
+    for (uint32_t i = 0; i < p->height; i++) fcy[i] = (uint32_t)ay.first[i] | ((uint32_t)ay.count[i] << 16);
+    HIP_TRY(hipMemcpyAsync(t.d, t.h, bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipEventRecord(t.uploaded, s->stream));
+    s->quiescent = false;
+    t.x = { (const uint32_t *)(t.d + fx), (const uint16_t *)(t.d + wx) };
+    t.y = { (const uint32_t *)(t.d + fy), (const uint16_t *)(t.d + wy) };
+    t.shape = shape;
+    t.y_span = ay.span((uint32_t)kResizeShapes[shape].h);
+    t.x_span = ax.span((uint32_t)kResizeShapes[shape].w);
+    t.width = p->width, t.height = p->height, t.filter = p->filter;
+    return TR_OK;
+}
+
+// Enqueues the current frame, resized, into `out_device` (which is no frame of the scene) behind everything issued so
+// far.  No depth is read: a depth left on the chip stays there.
+int enqueue_resize(tr_scene *s, const tr_resize_params *p, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st == TR_OK) st = resize_tables(s, p);
+    if (st != TR_OK) return st;
+    ResizeArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_w = p->width;
+    a.out_h = p->height;
+    a.x = s->resize.x;
+    a.y = s->resize.y;
+    a.shape = s->resize.shape;
+    a.y_span = s->resize.y_span;
+    a.x_span = s->resize.x_span;
+    a.frame = s->frame;
+    {
+        Timed t(s, K_RESIZE);
+        int rc = launch_resize(a, s->stream);
+        if (rc) return launch_status(rc, "k_resize");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_resize(tr_scene *s, const tr_resize_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_resize: null scene");
+    int st = check_resize_params(p, s->width, s->height, "tr_scene_resize");
+    if (st == TR_OK) st = check_resize_scene(s, "tr_scene_resize");
+    if (st != TR_OK) return st;
+    if (!out) return tr::fail(TR_E_INVALID, "tr_scene_resize: out == NULL (the output is no frame of the scene: there is no in-place form)");
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = classify_out(out, resized_bytes(p), "tr_scene_resize", "tr_scene_get_resized", "resized frame", &target);
+    if (st != TR_OK) return st;
+    if (s->z_fb_cleared) {  // a logically cleared frame is black at every size: zeros, no kernel
+        if ((st = submit_pending(s)) != TR_OK) return st;
+        HIP_TRY(hipMemsetAsync(target, 0, resized_bytes(p), s->stream));
+        s->quiescent = false;
+    } else if ((st = enqueue_resize(s, p, (uint8_t *)target)) != TR_OK) {
+        return st;
+    }
+    handed_on(s);
+    return TR_OK;
+}
+
+int tr_scene_get_resized(tr_scene *s, const tr_resize_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_resized: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_resized: null argument");
+    int st = check_resize_params(p, s->width, s->height, "tr_scene_get_resized");
+    if (st == TR_OK) st = check_resize_scene(s, "tr_scene_get_resized");
+    if (st != TR_OK) return st;
+    return get_stage(s, rgb, resized_bytes(p), cleared, [&](uint8_t *o) { return enqueue_resize(s, p, o); });
+}
+
+// The rule of tr_resize.h over a caller's array, on the host.  Needs no GPU.
+int tr_resize_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr_resize_params *p, uint8_t *out)
+{
+    int st = check_resize_params(p, width, height, "tr_resize_host");
+    if (st != TR_OK) return st;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_resize_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_resize_host: out is rgb (the sizes differ and a pixel reads its neighbours: not in place)");
+    if (!resize_host(width, height, rgb, p->filter, p->width, p->height, out))
+        return tr::fail(TR_E_INVALID, "tr_resize_host: a run of taps longer than TR_RESIZE_MAX_TAPS");
+    return TR_OK;
+}
+
+// The tables k_resize is fed for one axis, as resize_axis builds them.
+int tr_resize_taps(uint32_t filter, uint32_t n_src, uint32_t n_dst, uint16_t *first, uint16_t *count, uint16_t *weights)
+{
+    if (filter != TR_RESIZE_AREA && filter != TR_RESIZE_BILINEAR)
+        return tr::fail(TR_E_INVALID, "tr_resize_taps: filter must be TR_RESIZE_AREA or TR_RESIZE_BILINEAR");
+    if (!resize_side_ok(n_src, n_dst))
+        return tr::fail(TR_E_INVALID, "tr_resize_taps: n_dst must be 1..8192 and at least an eighth of n_src, rounded up");
+    if (!first || !count || !weights) return tr::fail(TR_E_INVALID, "tr_resize_taps: null argument");
+    if (!resize_axis(filter, n_src, n_dst, first, count, weights, nullptr))
+        return tr::fail(TR_E_INVALID, "tr_resize_taps: a run of taps longer than TR_RESIZE_MAX_TAPS");
     return TR_OK;
 }
 

@@ -448,6 +448,64 @@ def aa_host(rgb, params):
     return out
 
 
+RESIZE_AREA, RESIZE_BILINEAR, RESIZE_MAX_TAPS, RESIZE_MAX_SIDE = 0, 1, 16, 8192   # (TR_RESIZE_AREA, TR_RESIZE_BILINEAR, TR_RESIZE_MAX_TAPS)
+RESIZE_FILTERS = {"area": RESIZE_AREA, "bilinear": RESIZE_BILINEAR}
+
+
+class ResizeParams(C.Structure):
+    """tr_resize_params"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("filter", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def _resize_filter(filter, who):
+    if filter in RESIZE_FILTERS:
+        return RESIZE_FILTERS[filter]
+    if not isinstance(filter, (bool, str)) and filter in RESIZE_FILTERS.values():
+        return int(filter)
+    raise ValueError("%s: filter must be TR_RESIZE_AREA or TR_RESIZE_BILINEAR" % who)
+
+
+def resize_params(src_width, src_height, width, height, filter="area", who="resize"):
+    """tr_resize_params for a source of src_width x src_height pixels: the output's width x height, each 1..8192 and at
+    least an eighth of the source's (rounded up), and the filter, "area" or "bilinear" (or RESIZE_AREA / RESIZE_BILINEAR).
+    ValueError, in the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    f = _resize_filter(filter, who)
+    for v in (width, height):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= RESIZE_MAX_SIDE:
+            raise ValueError("%s: width and height must be 1..8192" % who)
+    if src_width < 1 or src_height < 1:
+        raise ValueError("%s: the source is empty" % who)
+    if 8 * width < src_width or 8 * height < src_height:
+        raise ValueError("%s: a side shrinks by more than 8 (width and height must be at least an eighth of the source's, rounded up)" % who)
+    return ResizeParams(int(width), int(height), f, 0)
+
+
+def resize_host(rgb, width, height, filter="area"):
+    """tr_resize_host: the rule of Scene.resize on the host (no GPU needed), through the tables k_resize is fed.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer).  Returns the [height, width, 3] frame and leaves its argument
+    alone."""
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("tr_resize_host: rgb [H, W, 3]")
+    p = resize_params(src.shape[1], src.shape[0], width, height, filter, "tr_resize_host")
+    out = np.empty((p.height, p.width, 3), np.uint8)
+    check(load_library().tr_resize_host(src.shape[1], src.shape[0], src.ctypes.data, C.addressof(p), out.ctypes.data))
+    return out
+
+
+def resize_taps(filter, n_src, n_dst):
+    """tr_resize_taps: the tables of one axis as k_resize is fed them -- (first [n_dst], count [n_dst], weights
+    [n_dst, 16]) uint16: output index X sums count[X] source samples from first[X] on under weights[X, :count[X]], which
+    add up to 4096; zeros beyond."""
+    f = _resize_filter(filter, "tr_resize_taps")
+    if isinstance(n_dst, bool) or not isinstance(n_dst, (int, np.integer)) or not 1 <= n_dst <= RESIZE_MAX_SIDE or n_src < 1 or 8 * n_dst < n_src:
+        raise ValueError("tr_resize_taps: n_dst must be 1..8192 and at least an eighth of n_src, rounded up")
+    first, count = np.empty(n_dst, np.uint16), np.empty(n_dst, np.uint16)
+    weights = np.empty((n_dst, RESIZE_MAX_TAPS), np.uint16)
+    check(load_library().tr_resize_taps(f, int(n_src), int(n_dst), first.ctypes.data, count.ctypes.data, weights.ctypes.data))
+    return first, count, weights
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1273,6 +1331,33 @@ class Scene:
         if not isinstance(params, AaParams):
             raise ValueError("get_antialiased: params must come from aa_params")
         return self._image("tr_scene_get_antialiased", strict, C.addressof(params))
+
+    # --- resize (tr_scene_resize / tr_scene_get_resized) -----------------------------------------------
+    def resize(self, width, height, filter="area", strict=True):
+        """tr_scene_get_resized: the current frame scaled on the device to width x height (each 1..8192 and at least an
+        eighth of the frame's) by the "area" or the "bilinear" filter: a [height, width, 3] uint8 array, equal to
+        resize_host(get_frame_buffer(), width, height, filter) in every byte.  Synchronizes; the scene's frame stays."""
+        p = resize_params(self.width, self.height, width, height, filter, "tr_scene_get_resized")
+        return self._image("tr_scene_get_resized", strict, C.addressof(p), out=np.empty((p.height, p.width, 3), np.uint8))
+
+    def pinned_resized(self, width, height):
+        """A page-locked [height, width, 3] uint8 array for resize_into (freed with the scene)."""
+        return self._pinned_array((int(height), int(width), 3))
+
+    def resize_into(self, out, width, height, filter="area"):
+        """tr_scene_resize: enqueue the resize of the current frame behind the renders issued so far; the result is there
+        after sync().  `out`: a torch tensor on the scene's device or a device pointer (int) to 3 * width * height bytes,
+        or an array from pinned_resized; every byte of it is written.  Band scenes are refused; there is no in-place
+        form.  No depth is read."""
+        p = resize_params(self.width, self.height, width, height, filter, "tr_scene_resize")
+        if out is None:
+            raise ValueError("tr_scene_resize: out == NULL (the output is no frame of the scene: there is no in-place form)")
+        target = out.data_ptr() if hasattr(out, "data_ptr") else out
+        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < p.width * p.height * 3 or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
+        ptr = self._out_pointer(target, "out", "[height, width, 3]", "pinned_resized", p.width * p.height * 3)
+        check(load_library().tr_scene_resize(self._h, C.addressof(p), ptr))
+        return out
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
