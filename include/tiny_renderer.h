@@ -979,6 +979,71 @@ int tr_resize_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr
 int tr_resize_taps(uint32_t filter, uint32_t n_src, uint32_t n_dst, uint16_t *first /* n_dst */, uint16_t *count /* n_dst */,
                    uint16_t *weights /* n_dst * TR_RESIZE_MAX_TAPS, zero-padded */);
 
+/* Warp: the scene's CURRENT frame, W x H, resampled on the device through a coarse grid of source coordinates -- one
+ * grid and one kernel for every geometric operation: rotation, flip, lens distortion (Brown-Conrady), keystone, crop and
+ * zoom, stabilisation, separated colour channels; each is a different grid built on the host.  In the chain it stands
+ * after antialias and before resize.  F is the image tr_scene_get_frame_buffer would return; the output is W' x H', each
+ * 1..8192, with F's orientation (row 0 = top), tightly packed rgb8.
+ * Grid.  Nodes are TR_WARP_CELL = 16 output pixels apart: gw = (W' + 15) / 16 + 1 by gh = (H' + 15) / 16 + 1 nodes,
+ * row-major, each a pair of int32_t (sx, sy) in units of 1/256 source pixel.  256 * x means exactly source sample x (a
+ * sample-index convention, no half-pixel offset).  Every node value lies in [-2^22, 2^22]; others are refused.
+ * Per output pixel (X, Y): gx = X >> 4, fx = X & 15, gy = Y >> 4, fy = Y & 15, and for both coordinates
+ *     s = ((16-fx)(16-fy) n00 + fx (16-fy) n10 + (16-fx) fy n01 + fx fy n11 + 128) >> 8    (arithmetic shift: floor; i32)
+ * over the cell's nodes n00 = (gx, gy), n10 = (gx + 1, gy), n01 = (gx, gy + 1), n11 = (gx + 1, gy + 1).
+ * Sample.  ix = sx >> 8 (floor), ax = sx & 255, likewise iy, ay;
+ *     out[c] = ((256-ax)(256-ay) T(ix,iy) + ax (256-ay) T(ix+1,iy) + (256-ax) ay T(ix,iy+1) + ax ay T(ix+1,iy+1) + 2^15) >> 16
+ * in u32.  Edge: under TR_WARP_BORDER T is border[c] for a texel outside [0, W) x [0, H); under TR_WARP_CLAMP each texel
+ * index is clamped to the image.  A texel of weight 0 contributes nothing either way.
+ * TR_WARP_PER_CHANNEL (flags): the scene's grid must be three grids -- r, g, b, gw * gh nodes apart -- and each channel is
+ * sampled at its own coordinate; without the flag it must be one.
+ * So: the identity grid (node = 256 * 16 * (gx, gy)) at W' x H' = W x H is a copy, sx = 256 * (W - 1 - 16 gx) is a
+ * horizontal flip, a quarter turn is exact, a whole-pixel translation is a shifted copy with border, sx = 128 X doubles
+ * the width with (a + b + 1) >> 1 midpoints, and a constant frame stays constant under TR_WARP_CLAMP.
+ * The filter is 2 x 2 and no wider: a grid that minifies strongly ALIASES -- shrink with tr_scene_resize. */
+#define TR_WARP_CELL 16
+#define TR_WARP_BORDER 0u
+#define TR_WARP_CLAMP 1u
+#define TR_WARP_PER_CHANNEL 1u
+typedef struct tr_warp_params {
+    uint32_t edge;     /* TR_WARP_BORDER or TR_WARP_CLAMP */
+    uint8_t border[3]; /* r, g, b of a texel outside the image under TR_WARP_BORDER */
+    uint8_t pad;       /* 0 */
+    uint32_t flags;    /* 0 or TR_WARP_PER_CHANNEL */
+} tr_warp_params;
+/* The scene's grid: the output is width x height (each 1..8192) and `grid` holds n_grids (1, or 3 for
+ * TR_WARP_PER_CHANNEL) grids of gw * gh node pairs.  The nodes are checked and copied before the call returns, then
+ * uploaded in stream order and kept on the scene until the next call: work already issued keeps the old grid.
+ * TR_E_INVALID with a text that names the call, nothing changed: a NULL scene or grid, a size outside 1..8192, n_grids
+ * not 1 or 3, a node value outside [-2^22, 2^22]. */
+int tr_scene_set_warp(tr_scene *s, uint32_t width, uint32_t height, uint32_t n_grids, const int32_t *grid);
+/* Warps the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device -- through the scene's grid.  Asynchronous and ordered like
+ * tr_scene_bloom: frames held back are submitted, a pending clear is made real, k_warp is enqueued on the scene's stream
+ * behind the renders issued so far (no depth is read, so a depth left on the chip stays there), a later render is ordered
+ * behind it, the result is there after tr_scene_sync.  The scene's passes issued so far count as handed on.
+ * out: 3 * W' * H' bytes (the grid's size) of device memory, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses); every byte of it is written; it must not overlap a frame
+ * buffer of the scene.  out == NULL: IN PLACE, allowed only when the grid's size is the frame's: the warped frame
+ * replaces the current one (through a scratch frame of the scene's) with its colour fast-clear flags, and every later
+ * consumer sees it.  An output tile whose whole source footprint has its colour fast-clear flags up is stored as zeros
+ * without a load where the rule gives black there; a texel behind a raised flag is never loaded.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since) maps to black under TR_WARP_CLAMP or a
+ * border of 0: `out` becomes zeros (hipMemsetAsync, no kernel), and in place nothing happens.  With another border the
+ * clear is made real and the kernel runs.
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene or
+ * params, an unknown edge, pad != 0, unknown flags; no grid set (tr_scene_set_warp), a grid count that does not match
+ * TR_WARP_PER_CHANNEL, a BAND scene (tr_options.band_row0/1 set); ordinary host memory as `out`, a pinned buffer that
+ * is too small, an `out` that overlaps a frame, out == NULL with a grid of another size than the frame's. */
+int tr_scene_warp(tr_scene *s, const tr_warp_params *p, void *out);
+/* The same into any host memory (3 * W' * H' bytes): waits for the scene first, warps into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_bloom. */
+int tr_scene_get_warped(tr_scene *s, const tr_warp_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed).  rgb: 3 * width * height bytes, out: 3 * out_width * out_height bytes,
+ * both row 0 = top; out must not be rgb.  The same parameter and grid checks, with width and height (each >= 1) in the
+ * frame's place. */
+int tr_warp_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint32_t out_width, uint32_t out_height, uint32_t n_grids,
+                 const int32_t *grid, const tr_warp_params *p, uint8_t *out /* != rgb */);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

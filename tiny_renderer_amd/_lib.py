@@ -164,6 +164,10 @@ SYMBOLS = {
     "tr_scene_get_resized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_resize_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_resize_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_warp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "tr_scene_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_warped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_warp_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

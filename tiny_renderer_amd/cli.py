@@ -111,6 +111,17 @@ def main(argv=None):
     ap.add_argument("--aa-search", type=int, default=8, metavar="N", help="look for an edge's ends up to N pixels away (1..8, default 8)")
     ap.add_argument("--aa-subpixel", type=int, default=192, metavar="N", help="the weight of the sub-pixel term (0..256, default 192; 0: edges only)")
     ap.add_argument("--aa-show-blend", action="store_true", help="with --aa: the blend weight the filter found instead of the picture")
+    ap.add_argument("--rotate", type=float, default=None, metavar="DEG",
+                    help="warp: turn the picture counter-clockwise by DEG degrees about its centre on the GPU (Scene.warp through "
+                         "warp_grid_rotate; after --aa and before --out-size)")
+    ap.add_argument("--lens", default=None, metavar="K1[,K2]",
+                    help="warp: a Brown-Conrady radial lens, r -> r (1 + K1 r^2 + K2 r^4) with r = 1 at the corner (warp_grid_lens; "
+                         "K1 < 0 barrel, K1 > 0 pincushion); applied after --rotate")
+    ap.add_argument("--chromatic", type=float, default=None, metavar="PX",
+                    help="warp: scale red and blue apart radially, PX pixels at the corner (warp_grid_chromatic: a grid a channel); "
+                         "applied after --lens")
+    ap.add_argument("--warp-edge", default=None, choices=("border", "clamp"),
+                    help="what --rotate, --lens and --chromatic show outside the picture: black (border; default) or its nearest pixel (clamp)")
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="resize: write the picture scaled to W x H (each 1..8192 and at least an eighth of the rendered side) on "
                          "the GPU (Scene.resize; applied last, after --aa, in the place of the --ssaa resolve)")
@@ -255,6 +266,26 @@ def main(argv=None):
         ap.error("--morph-to poses the scene of one GPU, by frame count: use --gpus 1 and --frames")
     if args.ssaa > 1 and (args.gpus > 1 or args.view != "frame"):
         ap.error("--ssaa resolves the colour frame of one GPU: use --gpus 1 and --view frame")
+    args.warps = []
+    if args.rotate is not None or args.lens is not None or args.chromatic is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--rotate, --lens and --chromatic work on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        from .scene import warp_grid_rotate, warp_grid_lens, warp_grid_chromatic, warp_params
+        edge = args.warp_edge or "border"
+        if args.rotate is not None:
+            args.warps.append((warp_grid_rotate(args.rotate, args.width, args.height), warp_params(edge)))
+        if args.lens is not None:
+            try:
+                k = [float(v) for v in args.lens.split(",")]
+                if not 1 <= len(k) <= 2:
+                    raise ValueError
+            except ValueError:
+                ap.error("--lens takes one or two numbers: K1[,K2]")
+            args.warps.append((warp_grid_lens(k[0], k[1] if len(k) > 1 else 0.0, args.width, args.height), warp_params(edge)))
+        if args.chromatic is not None:
+            args.warps.append((warp_grid_chromatic(args.chromatic, args.width, args.height), warp_params(edge, per_channel=True)))
+    elif args.warp_edge is not None:
+        ap.error("--warp-edge goes with --rotate, --lens or --chromatic")
     args.resize = None
     if args.out_size is not None:
         try:
@@ -524,6 +555,9 @@ def _run(args, T, scene, sharded, rank, say):
         scene.outline(args.outline_params)
     if args.aa_params is not None:
         scene.antialias(args.aa_params)
+    for grid, wp in args.warps:   # in place: --stats, --ssaa and --out-size see the warped frame
+        scene.set_warp(grid, args.width, args.height)
+        scene.warp(wp)
     if args.stats:
         st = scene.get_frame_stats(depth=True)
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"

@@ -19,6 +19,7 @@
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
 #include "tr_stats.h"
+#include "tr_warp.h"
 #include "tr_types.h"
 
 namespace tr {
@@ -115,6 +116,11 @@ int launch_aa(const AaArgs &a, hipStream_t st);
 // (device memory, built by resize_axis on the host) and the scene's colour fast-clear flags: k_resize, in the shape
 // a.shape of kResizeShapes, which the vertical table must fit (a.y_span).  The whole frame only (no band); no depth is read.
 int launch_resize(const ResizeArgs &a, hipStream_t st);
+// Warp: a.fb resampled to a.out (a.out_w x a.out_h, apart from it) by the rule of tr_warp.h through the node grid a.grid
+// (device memory; one grid, or three with a.rule.per_channel) and the scene's colour fast-clear flags: k_warp.  The whole
+// frame only (no band); no depth is read.  a.out_clean: null, or -- the output has the frame's size and its height is a
+// multiple of 16 -- where each workgroup writes the flag of its tile of a.out: a tile flagged there is zeros in every byte.
+int launch_warp(const WarpArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

@@ -3355,6 +3355,169 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_resize(ResizeArgs a)
     }
 }
 
+// Warp (tr_scene_warp): the frame resampled to out_w x out_h through a grid of source coordinates; tr_warp.h has the
+// rule.  One workgroup of 256 lanes per tile of 128 x 16 OUTPUT pixels: eight grid cells in a row, so a tile owns whole
+// cells and, where the output has the frame's size and a height that is a multiple of 16, is a tile of the frame's
+// grid.  Everything is in BUFFER rows (row 0 = top); source tile row ty is buffer rows H - 16 - 16 ty onwards.
+//   * nodes: the tile's 9 x 2 nodes of each grid to LDS (a partial tile repeats the last node of its last cell);
+//   * footprint (workgroup-uniform): a pixel's coordinate is a convex combination of its cell's nodes, so the tile's
+//     texels lie in [min >> 8, (max >> 8) + 1] per axis over those nodes.  Wholly outside the image under WARP_BORDER:
+//     the tile is the border colour.  Otherwise the colour flags of the 128 x 16 source tiles under the footprint,
+//     clamped to the image -- a lane every 256th, up to WARP_FLAG_TILES of them, beyond which nothing is concluded --
+//     and two votes: ALL up and the rule gives black there (WARP_CLAMP, a border of 0, or a footprint wholly inside):
+//     the tile is stored as zeros without a load; NONE up: no texel asks for its flag;
+//   * gather: a lane owns one column of the tile and every other row, eight pixels: coordinates from the nodes in LDS,
+//     four texels straight from memory through L1 / L2 as bytes -- a texel of weight 0 is skipped, one outside the image is
+//     the border or clamped, one behind a raised flag is zero WITHOUT a load (its memory is stale) --, the rounded bytes
+//     to a staging tile in LDS.  PC (WARP_PER_CHANNEL): three coordinates a pixel, one byte a texel;
+//   * stores from the staging tile (or the constant): 12-byte units of four pixels as three aligned words where WIDE
+//     (out_w % 4 == 0 and `out` 4-byte aligned: the launcher checks), otherwise bytes, consecutive lanes consecutive
+//     bytes, guarded by the output's width and height.  Every byte of `out` is written;
+//   * out_clean, when given, gets the tile's flag: 1 where the tile was stored as zeros without a load, else 0.
+// LDS: 6144 bytes of staging and 144 (PC: 432) of nodes.  No atomics, no inline assembly, no scratch.
+constexpr int WARP_THREADS = 256, WARP_TW = TILE_W, WARP_TH = WARP_CELL, WARP_NODES_X = WARP_TW / WARP_CELL + 1;
+constexpr int WARP_ROWS = WARP_TW * WARP_TH / WARP_THREADS;  // pixels of its column a lane owns
+constexpr int32_t WARP_FLAG_TILES = 1024;  // (four flags a lane)
+
+// One sample of the rule at (sx, sy): all three channels into o, or (PC) channel ch alone.
+template <bool PC>
+__device__ __forceinline__ void warp_sample(const WarpArgs &a, int32_t W, int32_t H, int32_t ntx, bool any_up, int32_t sx, int32_t sy,
+                                            int ch, uint32_t (&o)[3])
+{
+    const int32_t ix = sx >> 8, iy = sy >> 8;
+    const WarpWeights w = warp_weights((uint32_t)(sx & 255), (uint32_t)(sy & 255));
+    const uint32_t wt[4] = { w.w00, w.w10, w.w01, w.w11 };
+    uint32_t sum[3] = { 0u, 0u, 0u };
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+        if (wt[t] == 0u) continue;
+        int32_t x = ix + (t & 1), y = iy + (t >> 1);
+        bool in = x >= 0 && x < W && y >= 0 && y < H;
+        if (a.rule.edge == WARP_CLAMP) {
+            x = min(max(x, 0), W - 1), y = min(max(y, 0), H - 1);
+            in = true;
+        }
+        uint32_t v[3] = { a.rule.border[0], a.rule.border[1], a.rule.border[2] };
+        if (in) {  // (x, y) lies in the image from here on
+            if (any_up && a.fbclean[((H - 1 - y) / TILE_H) * ntx + x / TILE_W] != 0u) {
+                v[0] = v[1] = v[2] = 0u;
+            } else {
+                const uint8_t *p = a.fb + ((size_t)y * (size_t)W + (size_t)x) * 3u;
+                if (PC) v[ch] = p[ch];
+                else v[0] = p[0], v[1] = p[1], v[2] = p[2];
+            }
+        }
+        if (PC) sum[ch] += wt[t] * v[ch];
+        else sum[0] += wt[t] * v[0], sum[1] += wt[t] * v[1], sum[2] += wt[t] * v[2];
+    }
+    if (PC) o[ch] = warp_round(sum[ch]);
+    else o[0] = warp_round(sum[0]), o[1] = warp_round(sum[1]), o[2] = warp_round(sum[2]);
+}
+
+template <bool PC, bool WIDE>
+__global__ __launch_bounds__(WARP_THREADS) void k_warp(WarpArgs a)
+{
+    constexpr int NG = PC ? 3 : 1, NODES = NG * 2 * WARP_NODES_X;
+    static_assert(WARP_TW == 128 && WARP_TH == 16 && WARP_TH == TILE_H && NODES <= WARP_THREADS, "a tile of the frame's grid, one cell tall; a lane a node");
+    static_assert(WARP_THREADS % WARP_TW == 0 && WARP_TW * WARP_TH / 4 == 2 * WARP_THREADS, "a lane keeps its column; two units a lane");
+    __shared__ int32_t s_node[NODES * 2];
+    __shared__ __align__(4) uint8_t s_out[WARP_TH * WARP_TW * 3];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height, ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t Wd = (int32_t)a.out_w, Hd = (int32_t)a.out_h;
+    const int32_t gw = (int32_t)warp_grid_side(a.out_w), gh = (int32_t)warp_grid_side(a.out_h);
+    const int32_t bx = (int32_t)blockIdx.x, by = (int32_t)blockIdx.y;
+    const int32_t X0 = bx * WARP_TW, Y0 = by * WARP_TH;
+    const int32_t n_x = min(WARP_TW, Wd - X0), n_y = min(WARP_TH, Hd - Y0);  // the tile's columns and rows inside the output (>= 1)
+    const int32_t n_cx = (n_x + WARP_CELL - 1) / WARP_CELL;                   // its cells inside the output: nodes 0 .. n_cx
+    if ((int32_t)threadIdx.x < NODES) {
+        const int32_t g = (int32_t)threadIdx.x / (2 * WARP_NODES_X), r = (int32_t)threadIdx.x / WARP_NODES_X % 2;
+        const int32_t c = min((int32_t)threadIdx.x % WARP_NODES_X, n_cx);
+        // (column bx * 8 + n_cx <= gw - 1 and row by + 1 <= gh - 1: the grid has a node behind the last cell)
+        const size_t at = (size_t)g * (size_t)(gw * gh) + (size_t)(by + r) * (size_t)gw + (size_t)(bx * (WARP_NODES_X - 1) + c);
+        const int2 v = reinterpret_cast<const int2 *>(a.grid)[at];
+        s_node[2 * threadIdx.x] = v.x, s_node[2 * threadIdx.x + 1] = v.y;
+    }
+    __syncthreads();
+    // the footprint (workgroup-uniform): source columns [fx0, fx1], buffer rows [fy0, fy1], maybe outside the image
+    int32_t lo_x = s_node[0], hi_x = lo_x, lo_y = s_node[1], hi_y = lo_y;
+    for (int i = 1; i < NODES; i++) {
+        const int32_t x = s_node[2 * i], y = s_node[2 * i + 1];
+        lo_x = min(lo_x, x), hi_x = max(hi_x, x), lo_y = min(lo_y, y), hi_y = max(hi_y, y);
+    }
+    const int32_t fx0 = lo_x >> 8, fx1 = (hi_x >> 8) + 1, fy0 = lo_y >> 8, fy1 = (hi_y >> 8) + 1;
+    const bool outside = fx1 < 0 || fx0 >= W || fy1 < 0 || fy0 >= H;
+    const bool inside = fx0 >= 0 && fx1 < W && fy0 >= 0 && fy1 < H;
+    const bool border_mode = a.rule.edge != WARP_CLAMP;
+    const uint32_t br = a.rule.border[0], bg = a.rule.border[1], bb = a.rule.border[2];
+    bool constant = false, any_up = false;
+    uint32_t cr = 0u, cg = 0u, cb = 0u;  // the constant tile's colour
+    if (border_mode && outside) {
+        constant = true, cr = br, cg = bg, cb = bb;
+    } else if (a.fbclean != nullptr) {
+        // the source tiles under the footprint clamped to the image: columns ftx0 .. ftx1, tile rows fty0 .. fty1
+        const int32_t cx0 = min(max(fx0, 0), W - 1), cx1 = min(max(fx1, 0), W - 1), cy0 = min(max(fy0, 0), H - 1), cy1 = min(max(fy1, 0), H - 1);
+        const int32_t ftx0 = cx0 / TILE_W, ftx1 = cx1 / TILE_W, fty0 = (H - 1 - cy1) / TILE_H, fty1 = (H - 1 - cy0) / TILE_H;
+        const int32_t fw = ftx1 - ftx0 + 1, n_ft = fw * (fty1 - fty0 + 1);
+        if (n_ft <= WARP_FLAG_TILES) {
+            bool up = true, down = true;
+            for (int32_t i = (int32_t)threadIdx.x; i < n_ft; i += WARP_THREADS) {
+                const bool f = a.fbclean[(fty0 + i / fw) * ntx + ftx0 + i % fw] != 0u;
+                up = up && f, down = down && !f;
+            }
+            const bool all_up = __syncthreads_and((int)up) != 0;
+            any_up = __syncthreads_and((int)down) == 0;
+            if (all_up && (!border_mode || (br | bg | bb) == 0u || inside)) constant = true;
+        } else {
+            any_up = true;
+        }
+    }
+    if (a.out_clean != nullptr && threadIdx.x == 0u)  // (the launcher: the output's tiles are the frame's)
+        a.out_clean[(nty - 1 - by) * ntx + bx] = (constant && (cr | cg | cb) == 0u) ? 1u : 0u;
+    if (!constant) {  // (workgroup-uniform)
+        const int32_t lx = (int32_t)threadIdx.x % WARP_TW, cell = lx / WARP_CELL, fx = lx % WARP_CELL;
+        if (lx < n_x) {
+#pragma unroll 2
+            for (int k = 0; k < WARP_ROWS; k++) {
+                const int32_t ly = (int32_t)threadIdx.x / WARP_TW + (WARP_THREADS / WARP_TW) * k;  // (= Y & 15: the tile is one cell tall)
+                if (ly >= n_y) break;
+                uint32_t o[3];
+#pragma unroll
+                for (int g = 0; g < NG; g++) {
+                    const int32_t *n0 = &s_node[(g * 2 * WARP_NODES_X + cell) * 2], *n1 = n0 + WARP_NODES_X * 2;
+                    const int32_t sx = warp_coord(n0[0], n0[2], n1[0], n1[2], fx, ly);
+                    const int32_t sy = warp_coord(n0[1], n0[3], n1[1], n1[3], fx, ly);
+                    warp_sample<PC>(a, W, H, ntx, any_up, sx, sy, g, o);
+                }
+                uint8_t *d = &s_out[(ly * WARP_TW + lx) * 3];
+                d[0] = (uint8_t)o[0], d[1] = (uint8_t)o[1], d[2] = (uint8_t)o[2];
+            }
+        }
+        __syncthreads();
+    }
+    // stores
+    if (WIDE) {
+        // four pixels of the constant colour as three words: r g b r | g b r g | b r g b
+        const uint32_t k0 = cr | (cg << 8) | (cb << 16) | (cr << 24), k1 = cg | (cb << 8) | (cr << 16) | (cg << 24);
+        const uint32_t k2 = cb | (cr << 8) | (cg << 16) | (cb << 24);
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            const int32_t u = (int32_t)threadIdx.x + WARP_THREADS * j, ly = u / (WARP_TW / 4), ux = 4 * (u % (WARP_TW / 4));
+            if (ly < n_y && ux < n_x) {  // (out_w % 4 == 0: a unit lies inside the output or outside it)
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(&s_out[(ly * WARP_TW + ux) * 3]);
+                uint32_t *o = reinterpret_cast<uint32_t *>(a.out + ((size_t)(Y0 + ly) * (size_t)Wd + (size_t)(X0 + ux)) * 3u);
+                o[0] = constant ? k0 : q[0], o[1] = constant ? k1 : q[1], o[2] = constant ? k2 : q[2];
+            }
+        }
+    } else {
+        for (int32_t v = (int32_t)threadIdx.x; v < n_y * WARP_TW * 3; v += WARP_THREADS) {
+            const int32_t ly = v / (WARP_TW * 3), j = v % (WARP_TW * 3);
+            if (j >= n_x * 3) continue;
+            const uint32_t k = j % 3 == 0 ? cr : (j % 3 == 1 ? cg : cb);
+            a.out[((size_t)(Y0 + ly) * (size_t)Wd + (size_t)X0) * 3u + (size_t)j] = constant ? (uint8_t)k : s_out[ly * (WARP_TW * 3) + j];
+        }
+    }
+}
+
 // Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
 // partial record.  The project's one reduction, in two launches:
 //   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
@@ -4436,6 +4599,33 @@ int launch_resize(const ResizeArgs &a, hipStream_t st)
     if (a.shape == 0) launch_resize_shape<0>(a, wide, st);
     else if (a.shape == 1) launch_resize_shape<1>(a, wide, st);
     else launch_resize_shape<2>(a, wide, st);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_warp(const WarpArgs &a, hipStream_t st)
+{
+    if (!a.fb || !a.out || !a.grid || (uintptr_t)a.grid % 8u != 0u) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (the flags are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (a.frame.width + TILE_W - 1) / TILE_W || a.frame.nty != (a.frame.height + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (a.frame.width < 1u || a.frame.height < 1u) return (int)hipErrorInvalidValue;
+    if (a.out_w < 1u || a.out_w > WARP_MAX_SIDE || a.out_h < 1u || a.out_h > WARP_MAX_SIDE) return (int)hipErrorInvalidValue;
+    if (a.rule.edge > WARP_CLAMP || a.rule.border[0] > 255u || a.rule.border[1] > 255u || a.rule.border[2] > 255u) return (int)hipErrorInvalidValue;
+    // `out` is apart from the frame; flags of `out` only where its tiles are the frame's
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u, out_bytes = (size_t)a.out_w * a.out_h * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + out_bytes) return (int)hipErrorInvalidValue;
+    if (a.out_clean && (a.out_w != a.frame.width || a.out_h != a.frame.height || a.frame.height % TILE_H != 0u)) return (int)hipErrorInvalidValue;
+    // the wide path: every unit of four output pixels three aligned words
+    const bool wide = a.out_w % 4u == 0u && (uintptr_t)a.out % 4u == 0u;
+    const dim3 grid((a.out_w + WARP_TW - 1) / WARP_TW, (a.out_h + WARP_TH - 1) / WARP_TH);
+    if (a.rule.per_channel) {
+        if (wide) hipLaunchKernelGGL((k_warp<true, true>), grid, dim3(WARP_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((k_warp<true, false>), grid, dim3(WARP_THREADS), 0, st, a);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_warp<false, true>), grid, dim3(WARP_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((k_warp<false, false>), grid, dim3(WARP_THREADS), 0, st, a);
+    }
     TR_LAUNCH_CHECK();
     return 0;
 }

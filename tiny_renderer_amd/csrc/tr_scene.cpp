@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -414,6 +414,14 @@ struct tr_scene {
         int shape = -1;
         uint32_t y_span = 0, x_span = 0;
     } resize;
+    // tr_scene_set_warp: the node grids of the last call (width == 0: none) in the device block `d`, the page-locked block
+    // `h` they are uploaded from -- both grown on demand, `cap` int32 each -- and the event behind the last upload
+    struct WarpGrid {
+        int32_t *d = nullptr, *h = nullptr;
+        size_t cap = 0;
+        hipEvent_t uploaded = nullptr;
+        uint32_t width = 0, height = 0, n_grids = 0;
+    } warp;
     // tr_scene_debug_grade_grid: the most workgroups a k_grade launch may start (0: no cap) and what the last one started
     uint32_t grade_cap = 0, grade_grid = 0;
     // tr_scene_frame_stats: the slots k_stats' workgroups store their partial records to (stats_slots of them, allocated
@@ -2534,6 +2542,9 @@ void destroy(tr_scene *s)
     dev_free(s->resize.d);
     if (s->resize.h) (void)hipHostFree(s->resize.h);
     if (s->resize.uploaded) (void)hipEventDestroy(s->resize.uploaded);
+    dev_free(s->warp.d);
+    if (s->warp.h) (void)hipHostFree(s->warp.h);
+    if (s->warp.uploaded) (void)hipEventDestroy(s->warp.uploaded);
     dev_free(s->d_stats_partials);
     dev_free(s->d_winner);
     for (tr_scene::FbFlags &f : s->fb_flags) dev_free(f.clean);
@@ -2821,7 +2832,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, resize) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, resize) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none); the cleared-scene shortcut where the stage has one --
@@ -2896,11 +2907,14 @@ int classify_out(void *out, size_t bytes, const char *who, const char *getter, c
 }
 
 // `target` (from classify_out) must not be (part of) a frame the kernel may read, or another one the scene keeps flags
-// of: none of its slots, no frame buffer with a flag set, none of the last n_kept kept frames.
-int refuse_overlap(const tr_scene *s, const void *target, size_t bytes, const char *who, const char *verb, uint32_t n_kept)
+// of: none of its slots, no frame buffer with a flag set, none of the last n_kept kept frames.  bytes: a frame's;
+// target_bytes: the target's where it differs (0: the same).
+int refuse_overlap(const tr_scene *s, const void *target, size_t bytes, const char *who, const char *verb, uint32_t n_kept,
+                   size_t target_bytes = 0)
 {
+    if (target_bytes == 0u) target_bytes = bytes;
     auto overlaps = [&](const uint8_t *fb) {
-        return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + bytes;
+        return fb && (const uint8_t *)target < fb + bytes && fb < (const uint8_t *)target + target_bytes;
     };
     bool hit = false;
     for (const tr_scene::FrameSlot &fs : s->slots) hit = hit || overlaps(fs.fb);
@@ -5005,6 +5019,208 @@ int tr_resize_taps(uint32_t filter, uint32_t n_src, uint32_t n_dst, uint16_t *fi
     if (!first || !count || !weights) return tr::fail(TR_E_INVALID, "tr_resize_taps: null argument");
     if (!resize_axis(filter, n_src, n_dst, first, count, weights, nullptr))
         return tr::fail(TR_E_INVALID, "tr_resize_taps: a run of taps longer than TR_RESIZE_MAX_TAPS");
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_WARP_CELL == WARP_CELL && TR_WARP_BORDER == WARP_BORDER && TR_WARP_CLAMP == WARP_CLAMP &&
+                  TR_WARP_PER_CHANNEL == WARP_PER_CHANNEL && sizeof(tr_warp_params) == 12,
+              "tr_warp.h restates the header");
+
+// tr_warp_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_warp_params(const tr_warp_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->edge != TR_WARP_BORDER && p->edge != TR_WARP_CLAMP) return tr::fail(TR_E_INVALID, w + ": edge must be TR_WARP_BORDER or TR_WARP_CLAMP");
+    if (p->pad != 0u) return tr::fail(TR_E_INVALID, w + ": pad must be 0");
+    if (p->flags & ~TR_WARP_PER_CHANNEL) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    return TR_OK;
+}
+
+// A grid as tr_scene_set_warp and tr_warp_host accept it: the output's size, the number of grids, every node in range.
+int check_warp_grid(uint32_t width, uint32_t height, uint32_t n_grids, const int32_t *grid, const char *who)
+{
+    const std::string w(who);
+    if (!grid) return tr::fail(TR_E_INVALID, w + ": null grid");
+    if (width < 1u || width > WARP_MAX_SIDE || height < 1u || height > WARP_MAX_SIDE)
+        return tr::fail(TR_E_INVALID, w + ": width and height must be 1..8192");
+    if (n_grids != 1u && n_grids != 3u) return tr::fail(TR_E_INVALID, w + ": n_grids must be 1 or 3 (TR_WARP_PER_CHANNEL)");
+    const size_t n = (size_t)warp_grid_side(width) * warp_grid_side(height) * 2u * n_grids;
+    for (size_t i = 0; i < n; i++)
+        if (grid[i] < -WARP_NODE_MAX || grid[i] > WARP_NODE_MAX)
+            return tr::fail(TR_E_INVALID, w + ": a node value outside [-2^22, 2^22]");
+    return TR_OK;
+}
+
+// Do the flags of a call go with the number of grids?
+int check_warp_count(const tr_warp_params *p, uint32_t n_grids, const char *who)
+{
+    if ((p->flags & TR_WARP_PER_CHANNEL) && n_grids != 3u)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": TR_WARP_PER_CHANNEL needs three grids and there is one");
+    if (!(p->flags & TR_WARP_PER_CHANNEL) && n_grids != 1u)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": three grids need TR_WARP_PER_CHANNEL");
+    return TR_OK;
+}
+
+int check_warp_scene(const tr_scene *s, const tr_warp_params *p, const char *who)
+{
+    if (s->warp.width == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no grid (tr_scene_set_warp)");
+    int st = check_warp_count(p, s->warp.n_grids, who);
+    if (st != TR_OK) return st;
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be warped: "
+                                                         "a pixel's source may lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+WarpRule warp_rule(const tr_warp_params *p)
+{
+    WarpRule r;
+    r.edge = p->edge;
+    for (int c = 0; c < 3; c++) r.border[c] = p->border[c];
+    r.per_channel = (p->flags & TR_WARP_PER_CHANNEL) ? 1u : 0u;
+    return r;
+}
+
+size_t warped_bytes(const tr_scene *s) { return (size_t)s->warp.width * s->warp.height * 3; }
+
+// Does the stage short-circuit?  A logically cleared frame is black, and black maps to black where no border colour
+// comes in: under TR_WARP_CLAMP, or with a border of 0.
+bool warp_of_cleared_is_zeros(const tr_warp_params *p) { return p->edge == TR_WARP_CLAMP || (p->border[0] | p->border[1] | p->border[2]) == 0u; }
+
+// Enqueues the current frame, warped through the scene's grid, into `out_device` (which overlaps no frame of the
+// scene) behind everything issued so far; out_clean: null, or a flag set of the frame's tile grid that is to say what
+// `out_device` holds (in place: the output has the frame's size).  With another border than black a pending clear is
+// made real first.  No depth is read: a depth left on the chip stays there.
+int enqueue_warp(tr_scene *s, const tr_warp_params *p, uint8_t *out_device, uint32_t *out_clean)
+{
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st != TR_OK) return st;
+    // k_warp's tiles lie 16 rows apart from the TOP, the frame's from the bottom: they are the same tiles where the
+    // height is a multiple of 16, and the kernel writes the flags; otherwise every flag goes down (nothing is claimed)
+    const bool same_tiles = s->height % 16u == 0u;
+    if (out_clean && !same_tiles) HIP_TRY(hipMemsetAsync(out_clean, 0, (size_t)s->n_tiles * 4, s->stream));
+    WarpArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = same_tiles ? out_clean : nullptr;
+    a.grid = s->warp.d;
+    a.out_w = s->warp.width;
+    a.out_h = s->warp.height;
+    a.rule = warp_rule(p);
+    a.frame = s->frame;
+    {
+        Timed t(s, K_WARP);
+        int rc = launch_warp(a, s->stream);
+        if (rc) return launch_status(rc, "k_warp");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_set_warp(tr_scene *s, uint32_t width, uint32_t height, uint32_t n_grids, const int32_t *grid)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_set_warp: null scene");
+    int st = check_warp_grid(width, height, n_grids, grid, "tr_scene_set_warp");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    tr_scene::WarpGrid &g = s->warp;
+    const size_t n = (size_t)warp_grid_side(width) * warp_grid_side(height) * 2u * n_grids;
+    if (!g.uploaded) HIP_TRY(hipEventCreateWithFlags(&g.uploaded, hipEventDisableTiming));
+    if (g.cap < n) {
+        // larger blocks: a k_warp issued earlier may still read the old device block, so the stream runs empty first
+        int32_t *d_new = nullptr, *h_new = nullptr;
+        if ((st = dev_alloc(&d_new, n)) != TR_OK) return st;
+        if (hipHostMalloc((void **)&h_new, n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            dev_free(d_new);
+            return tr::fail(TR_E_NOMEM, "tr_scene_set_warp: no page-locked memory for the grid");
+        }
+        hipError_t e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) {
+            dev_free(d_new);
+            (void)hipHostFree(h_new);
+            HIP_TRY(e);
+        }
+        dev_free(g.d);
+        if (g.h) (void)hipHostFree(g.h);
+        g.d = d_new, g.h = h_new, g.cap = n;
+        g.width = 0u;
+    } else {
+        HIP_TRY(hipEventSynchronize(g.uploaded));  // (the previous upload has left the page-locked block)
+    }
+    g.width = 0u;  // (no grid while the block is being rewritten: a failure below leaves none)
+    memcpy(g.h, grid, n * sizeof(int32_t));
+    // in stream order: behind every k_warp that still reads the old nodes
+    HIP_TRY(hipMemcpyAsync(g.d, g.h, n * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipEventRecord(g.uploaded, s->stream));
+    s->quiescent = false;
+    g.width = width, g.height = height, g.n_grids = n_grids;
+    return TR_OK;
+}
+
+int tr_scene_warp(tr_scene *s, const tr_warp_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_warp: null scene");
+    int st = check_warp_params(p, "tr_scene_warp");
+    if (st == TR_OK) st = check_warp_scene(s, p, "tr_scene_warp");
+    if (st != TR_OK) return st;
+    if (!out && (s->warp.width != s->width || s->warp.height != s->height))
+        return tr::fail(TR_E_INVALID, "tr_scene_warp: out == NULL warps in place, and the grid's size is not the frame's");
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    if (out) {
+        st = classify_out(out, warped_bytes(s), "tr_scene_warp", "tr_scene_get_warped", "warped frame", &target);
+        if (st == TR_OK) st = refuse_overlap(s, target, frame_bytes(s), "tr_scene_warp", "warps", 0u, warped_bytes(s));
+        if (st != TR_OK) return st;
+    }
+    // a logically cleared frame is black, and so is its warp where no border colour comes in: zeros out of place,
+    // itself in place
+    if (s->z_fb_cleared && warp_of_cleared_is_zeros(p)) {
+        if (!target) return TR_OK;
+        if ((st = submit_pending(s)) != TR_OK) return st;
+        HIP_TRY(hipMemsetAsync(target, 0, warped_bytes(s), s->stream));
+        s->quiescent = false;
+        handed_on(s);
+        return TR_OK;
+    }
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_warp(s, p, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_warped(tr_scene *s, const tr_warp_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_warped: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_warped: null argument");
+    int st = check_warp_params(p, "tr_scene_get_warped");
+    if (st == TR_OK) st = check_warp_scene(s, p, "tr_scene_get_warped");
+    if (st != TR_OK) return st;
+    // (the predicate takes the scene alone: the parameters decide here which one is asked)
+    return get_stage(s, rgb, warped_bytes(s), warp_of_cleared_is_zeros(p) ? cleared : nullptr,
+                     [&](uint8_t *o) { return enqueue_warp(s, p, o, nullptr); });
+}
+
+// The rule of tr_warp.h over a caller's array, on the host.  Needs no GPU.
+int tr_warp_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint32_t out_width, uint32_t out_height, uint32_t n_grids,
+                 const int32_t *grid, const tr_warp_params *p, uint8_t *out)
+{
+    int st = check_warp_params(p, "tr_warp_host");
+    if (st == TR_OK) st = check_warp_grid(out_width, out_height, n_grids, grid, "tr_warp_host");
+    if (st == TR_OK) st = check_warp_count(p, n_grids, "tr_warp_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || height < 1u) return tr::fail(TR_E_INVALID, "tr_warp_host: the source is empty");
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_warp_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_warp_host: out is rgb (a pixel reads other pixels: not in place)");
+    warp_host(width, height, rgb, out_width, out_height, grid, warp_rule(p), out);
     return TR_OK;
 }
 

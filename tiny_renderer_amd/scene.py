@@ -506,6 +506,148 @@ def resize_taps(filter, n_src, n_dst):
     return first, count, weights
 
 
+WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
+WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
+
+
+class WarpParams(C.Structure):
+    """tr_warp_params"""
+    _fields_ = [("edge", C.c_uint32), ("border", C.c_uint8 * 3), ("pad", C.c_uint8), ("flags", C.c_uint32)]
+
+
+def warp_params(edge="border", border=(0, 0, 0), per_channel=False, who="warp"):
+    """tr_warp_params: the edge mode, "border" (a texel outside the image is `border`, r g b) or "clamp" (texel indices
+    are clamped to the image), and whether the scene's grid is three grids, one a channel.  ValueError, in the library's
+    words, for what it would refuse."""
+    if edge in WARP_EDGES:
+        e = WARP_EDGES[edge]
+    elif not isinstance(edge, (bool, str)) and edge in WARP_EDGES.values():
+        e = int(edge)
+    else:
+        raise ValueError("%s: edge must be TR_WARP_BORDER or TR_WARP_CLAMP" % who)
+    b = [int(v) for v in border]
+    if len(b) != 3 or any(not 0 <= v <= 255 for v in b):
+        raise ValueError("%s: border is three values 0..255" % who)
+    return WarpParams(e, (C.c_uint8 * 3)(*b), 0, WARP_PER_CHANNEL if per_channel else 0)
+
+
+def warp_grid_shape(width, height):
+    """(gh, gw): the nodes of a grid for an output of width x height -- one every 16 pixels and one behind the last cell."""
+    return (int(height) + WARP_CELL - 1) // WARP_CELL + 1, (int(width) + WARP_CELL - 1) // WARP_CELL + 1
+
+
+def _warp_grid(grid, width, height, who):
+    """`grid` as the library takes it: int32 [n, gh, gw, 2] with n = 1 or 3 ([gh, gw, 2] is one grid), its size and every
+    node checked in the library's words."""
+    for v in (width, height):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= WARP_MAX_SIDE:
+            raise ValueError("%s: width and height must be 1..8192" % who)
+    if grid is None:
+        raise ValueError("%s: null grid" % who)
+    g = np.asarray(grid)
+    if g.dtype.kind not in "iu":
+        raise ValueError("%s: the grid is an integer array (units of 1/256 source pixel)" % who)
+    if g.ndim == 3:
+        g = g[None]
+    gh, gw = warp_grid_shape(width, height)
+    if g.ndim != 4 or g.shape[0] not in (1, 3):
+        raise ValueError("%s: n_grids must be 1 or 3 (TR_WARP_PER_CHANNEL)" % who)
+    if g.shape[1:] != (gh, gw, 2):
+        raise ValueError("%s: a grid for %d x %d is [%d, %d, 2] (gh, gw, (sx, sy))" % (who, width, height, gh, gw))
+    if g.size and (int(g.min()) < -WARP_NODE_MAX or int(g.max()) > WARP_NODE_MAX):
+        raise ValueError("%s: a node value outside [-2^22, 2^22]" % who)
+    return np.ascontiguousarray(g, np.int32)
+
+
+def warp_host(rgb, grid, width, height, params):
+    """tr_warp_host: the rule of Scene.warp on the host (no GPU needed).  rgb [H, W, 3] uint8 with row 0 = top
+    (get_frame_buffer), grid as for Scene.set_warp for an output of width x height, params from warp_params.  Returns the
+    [height, width, 3] frame and leaves its arguments alone."""
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("tr_warp_host: rgb [H, W, 3]")
+    if not isinstance(params, WarpParams):
+        raise ValueError("tr_warp_host: params must come from warp_params")
+    g = _warp_grid(grid, width, height, "tr_warp_host")
+    out = np.empty((int(height), int(width), 3), np.uint8)
+    check(load_library().tr_warp_host(src.shape[1], src.shape[0], src.ctypes.data, int(width), int(height), g.shape[0], g.ctypes.data,
+                                      C.addressof(params), out.ctypes.data))
+    return out
+
+
+def warp_grid_from_function(f, width, height):
+    """A grid for an output of width x height from f(X, Y) -> (sx, sy): X and Y are float64 arrays [gh, gw] of the nodes'
+    OUTPUT pixel indices (0, 16, 32, ... -- the last column and row may lie outside the output), sx and sy the SOURCE
+    sample each should show, in pixels (sample indices: 0 is the first sample's centre).  Evaluated in floating point;
+    a node is floor(256 v + 0.5), clipped to [-2^22, 2^22].  int32 [gh, gw, 2].  Between the nodes the device
+    interpolates linearly: a grid follows a smooth function to within its curvature over 16 pixels."""
+    gh, gw = warp_grid_shape(width, height)
+    Y, X = np.meshgrid(np.arange(gh, dtype=np.float64) * WARP_CELL, np.arange(gw, dtype=np.float64) * WARP_CELL, indexing="ij")
+    sx, sy = f(X, Y)
+    g = np.stack([np.broadcast_to(np.asarray(sx, np.float64), X.shape), np.broadcast_to(np.asarray(sy, np.float64), X.shape)], axis=-1)
+    g = np.nan_to_num(np.floor(256.0 * g + 0.5), nan=0.0, posinf=float(WARP_NODE_MAX), neginf=-float(WARP_NODE_MAX))
+    return np.clip(g, -WARP_NODE_MAX, WARP_NODE_MAX).astype(np.int32)
+
+
+def warp_grid_identity(width, height):
+    """The grid that shows every source sample where it is: at the frame's own size Scene.warp is then a copy."""
+    return warp_grid_from_function(lambda X, Y: (X, Y), width, height)
+
+
+def warp_grid_rotate(deg, width, height, src_width=None, src_height=None, zoom=1.0):
+    """The picture turned counter-clockwise by `deg` degrees (and magnified by `zoom`) about its centre: the centre of
+    the width x height output shows the centre of the src_width x src_height source (default: the same size).
+    Multiples of 90 degrees take exact sines, so a quarter turn with the sides exchanged is np.rot90 in every byte."""
+    sw = width if src_width is None else src_width
+    sh = height if src_height is None else src_height
+    q = float(deg) / 90.0
+    if q == int(q):
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q) % 4]
+    else:
+        c, s = float(np.cos(np.radians(deg))), float(np.sin(np.radians(deg)))
+    c, s = c / zoom, s / zoom
+    cxo, cyo, cxs, cys = (width - 1) / 2.0, (height - 1) / 2.0, (sw - 1) / 2.0, (sh - 1) / 2.0
+    return warp_grid_from_function(lambda X, Y: (cxs + c * (X - cxo) - s * (Y - cyo), cys + s * (X - cxo) + c * (Y - cyo)), width, height)
+
+
+def warp_grid_lens(k1, k2=0.0, width=None, height=None, scale=1.0):
+    """A Brown-Conrady radial lens: the output pixel at distance r from the centre (r = 1 at the corner) shows the source
+    at distance r (1 + k1 r^2 + k2 r^4) * scale along the same ray.  k1 < 0 gives a barrel, k1 > 0 a pincushion; apply
+    the model's own coefficients to distort a rendered frame like the lens, their inverse fit to undistort one."""
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    R2 = max(cx * cx + cy * cy, 1.0)
+
+    def f(X, Y):
+        dx, dy = X - cx, Y - cy
+        r2 = (dx * dx + dy * dy) / R2
+        m = (1.0 + k1 * r2 + k2 * r2 * r2) * scale
+        return cx + dx * m, cy + dy * m
+    return warp_grid_from_function(f, width, height)
+
+
+def warp_grid_homography(M, width, height):
+    """A projective map (keystone, perspective correction): M, 3 x 3, takes an output pixel (X, Y, 1) to the source's
+    homogeneous (x, y, w); the node is (x / w, y / w).  A node whose w is not positive is thrown far outside."""
+    M = np.asarray(M, np.float64).reshape(3, 3)
+
+    def f(X, Y):
+        x, y, w = (M[i, 0] * X + M[i, 1] * Y + M[i, 2] for i in range(3))
+        ok = w > 1e-12
+        w = np.where(ok, w, 1.0)
+        far = float(WARP_NODE_MAX)
+        return np.where(ok, x / w, -far), np.where(ok, y / w, -far)
+    return warp_grid_from_function(f, width, height)
+
+
+def warp_grid_chromatic(px, width, height):
+    """Three grids [3, gh, gw, 2] for TR_WARP_PER_CHANNEL: red is scaled up and blue down about the centre so that at the
+    corner they lie `px` source pixels to either side of green, which stays (lateral chromatic aberration)."""
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    e = float(px) / max(float(np.hypot(cx, cy)), 1.0)
+    return np.stack([warp_grid_from_function(lambda X, Y, m=m: (cx + (X - cx) * m, cy + (Y - cy) * m), width, height)
+                     for m in (1.0 - e, 1.0, 1.0 + e)])
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1358,6 +1500,46 @@ class Scene:
         ptr = self._out_pointer(target, "out", "[height, width, 3]", "pinned_resized", p.width * p.height * 3)
         check(load_library().tr_scene_resize(self._h, C.addressof(p), ptr))
         return out
+
+    # --- warp (tr_scene_set_warp / tr_scene_warp / tr_scene_get_warped) -------------------------------
+    def set_warp(self, grid, width, height):
+        """tr_scene_set_warp: the scene's grid of source coordinates for an output of width x height (each 1..8192): int32
+        [gh, gw, 2], or [3, gh, gw, 2] for a grid a channel (warp_params(per_channel=True)), (gh, gw) = warp_grid_shape,
+        nodes (sx, sy) in 1/256 source pixel (warp_grid_identity, warp_grid_from_function, warp_grid_rotate, warp_grid_lens,
+        warp_grid_homography, warp_grid_chromatic).  Uploaded in stream order: work already issued keeps the old grid."""
+        g = _warp_grid(grid, width, height, "tr_scene_set_warp")
+        check(load_library().tr_scene_set_warp(self._h, int(width), int(height), g.shape[0], g.ctypes.data))
+        self._warp_size = (int(width), int(height))
+
+    def pinned_warped(self, width, height):
+        """A page-locked [height, width, 3] uint8 array for warp (freed with the scene)."""
+        return self._pinned_array((int(height), int(width), 3))
+
+    def warp(self, params, out=None):
+        """tr_scene_warp: resamples the current frame through the scene's grid on the device (params from warp_params).
+        out=None: in place, allowed where the grid's size is the frame's -- every later consumer (the getters, resize,
+        resolve, the sparse read-back) sees the warped frame, z and the shadow buffer stay.  Otherwise `out` is a torch
+        tensor on the scene's device or a device pointer (int) to 3 * width * height bytes (the grid's size) apart from
+        every frame buffer of the scene, or an array from pinned_warped; every byte of it is written and the scene's frame
+        stays.  Asynchronous: the result is there after sync().  Band scenes are refused.  No depth is needed."""
+        if not isinstance(params, WarpParams):
+            raise ValueError("warp: params must come from warp_params")
+        w, h = getattr(self, "_warp_size", (self.width, self.height))
+        target = out.data_ptr() if hasattr(out, "data_ptr") else out
+        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < w * h * 3 or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
+        ptr = self._out_pointer(target, "out", "[height, width, 3]", "pinned_warped", w * h * 3)
+        check(load_library().tr_scene_warp(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_warped(self, params, strict=True):
+        """tr_scene_get_warped: the current frame warped on the device, as a [height, width, 3] uint8 array of the grid's
+        size, equal to warp_host(get_frame_buffer(), grid, width, height, params) in every byte.  Synchronizes; the scene's
+        frame stays."""
+        if not isinstance(params, WarpParams):
+            raise ValueError("get_warped: params must come from warp_params")
+        w, h = getattr(self, "_warp_size", (self.width, self.height))
+        return self._image("tr_scene_get_warped", strict, C.addressof(params), out=np.empty((h, w, 3), np.uint8))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
