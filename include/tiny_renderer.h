@@ -1044,6 +1044,68 @@ int tr_scene_get_warped(tr_scene *s, const tr_warp_params *p, uint8_t *rgb);
 int tr_warp_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint32_t out_width, uint32_t out_height, uint32_t n_grids,
                  const int32_t *grid, const tr_warp_params *p, uint8_t *out /* != rgb */);
 
+/* Convolve: the scene's CURRENT frame filtered on the device through a kernel of integer weights -- one kernel
+ * (k_convolve) for every linear neighbourhood filter: Gaussian and box blur, sharpen and unsharp mask, emboss, Laplacian,
+ * Sobel, directional blur.  F is the frame as tr_scene_get_frame_buffer returns it: rgb8, row 0 = top, y grows downward.
+ * kw x kh taps, both odd; w(i, j) is the weight of column i from the left, row j from the top:
+ *   general   : w(i, j) = weights[j * kw + i], kw and kh 1..9
+ *   separable : row = weights[0 .. kw), col = weights[kw .. kw + kh), w(i, j) = row[i] * col[j], kw and kh 1..31
+ *   sum   : acc[c] = sum over j < kh, i < kw of w(i, j) * F(x + i - kw / 2, y + j - kh / 2)[c]    (correlation: no flip)
+ *           a tap outside the image is border[c] under TR_CONVOLVE_BORDER; under TR_CONVOLVE_CLAMP its index is clamped
+ *           per axis
+ *   scale : v = (acc + rnd) >> shift, an arithmetic shift, rnd = shift ? 1 << (shift - 1) : 0;  TR_CONVOLVE_ABS: v = |v|
+ *   out   : clamp(v + bias, 0, 255)
+ *           TR_CONVOLVE_UNSHARP: v = clamp(v, 0, 255), out = clamp(F + ((amount * (F - v) + 128) >> 8), 0, 255) with an
+ *           arithmetic shift; bias must be 0 and TR_CONVOLVE_ABS is refused: sharpening at any radius up to 15 is one
+ *           separable call
+ * Bounds: A = sum |w| (general) or sum |row| * sum |col| (separable) must not exceed 2^22 -- then 255 A + 2^21 < 2^31 and an
+ * int32 holds every sum; no int16 kernel of the general form is refused on it (81 * 32767 < 2^22).  Separable: sum |row|
+ * must not exceed 2^15 either.  The separable form is DEFINED as the 2-D sum of the outer product; everything is integer,
+ * so the device equals tr_convolve_host in every byte.  1 x 1 with w = 1 and shift 0 is a copy; a single tap of 1 off
+ * centre is a shifted copy; a separable kernel of at most 9 x 9 equals its outer product through the general form; the
+ * tent row = col = [1 .. R + 1 .. 1] with shift = 4 log2(R + 1) and a border of 0 is tr_scene_bloom's glow at threshold 0
+ * for R = 1, 3, 7, 15. */
+#define TR_CONVOLVE_SEPARABLE 1u
+#define TR_CONVOLVE_ABS 2u
+#define TR_CONVOLVE_UNSHARP 4u
+#define TR_CONVOLVE_BORDER 0u
+#define TR_CONVOLVE_CLAMP 1u
+typedef struct tr_convolve_params {
+    uint32_t struct_size;   /* = sizeof(tr_convolve_params) = 200 */
+    uint32_t kw, kh;        /* odd; general form 1..9 each, TR_CONVOLVE_SEPARABLE 1..31 each */
+    uint32_t flags;         /* TR_CONVOLVE_SEPARABLE | TR_CONVOLVE_ABS | TR_CONVOLVE_UNSHARP */
+    uint32_t shift;         /* 0..22 */
+    int32_t bias;           /* -255..255 */
+    uint32_t amount;        /* 0..1024 in 1/256; read under TR_CONVOLVE_UNSHARP only, else must be 0 */
+    uint32_t edge;          /* TR_CONVOLVE_BORDER or TR_CONVOLVE_CLAMP */
+    uint8_t border[3];      /* r, g, b of a tap outside the image under TR_CONVOLVE_BORDER */
+    uint8_t pad;            /* 0 */
+    int16_t weights[82];    /* see above; entries behind the last one used are not read */
+} tr_convolve_params;
+/* Filters the current frame -- what the getters mean.  Asynchronous and ordered like tr_scene_bloom: frames held back are
+ * submitted, a pending clear is made real, k_convolve is enqueued on the scene's stream.  No depth is read, so a depth
+ * left on the chip stays there.  out: 3 * W * H bytes of device memory or of memory from tr_host_alloc, apart from every
+ * frame buffer of the scene; every byte is written and the scene's frame stays.  out == NULL: IN PLACE -- every later
+ * consumer sees the filtered frame, the colour fast-clear flags follow (a tile is flagged only where it is zeros in
+ * every byte), z, the winner words and the shadow buffer stay; calling it twice filters twice.  A tile whose 3 x 3
+ * neighbourhood is flagged clean is not read: it becomes clamp(bias) (0 under TR_CONVOLVE_UNSHARP) where no border
+ * colour reaches it.  A scene that is logically cleared maps to black where the rule gives black -- clamp(bias) == 0 and
+ * (TR_CONVOLVE_CLAMP or a border of 0): zeros out of place, nothing in place, no kernel; otherwise the clear is made real
+ * and the kernel runs.
+ * TR_E_INVALID, each text opening with the call's name: a null scene or params, a wrong struct_size, unknown flags, an
+ * even or out-of-range kw or kh, a shift above 22, a bias outside -255..255, an amount above 1024 or non-zero without
+ * TR_CONVOLVE_UNSHARP, an unknown edge, pad != 0, weights beyond either bound, TR_CONVOLVE_UNSHARP with TR_CONVOLVE_ABS or
+ * a bias; a BAND scene (tr_options.band_row0/1 set: the taps at a band's border lie in another rank's rows); ordinary
+ * host memory as `out`, a pinned buffer that is too small, an `out` that overlaps a frame buffer of the scene. */
+int tr_scene_convolve(tr_scene *s, const tr_convolve_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * W * H bytes): waits for the scene first, filters into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_bloom.  The scene's frame stays. */
+int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_convolve calls.  rgb and out: 3 * width *
+ * height bytes, row 0 = top; out must not be rgb.  The same parameter checks; a width or height of 0 returns TR_OK. */
+int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
+                     const tr_convolve_params *p);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -122,6 +122,19 @@ def main(argv=None):
                          "applied after --lens")
     ap.add_argument("--warp-edge", default=None, choices=("border", "clamp"),
                     help="what --rotate, --lens and --chromatic show outside the picture: black (border; default) or its nearest pixel (clamp)")
+    ap.add_argument("--blur", type=float, default=None, metavar="SIGMA",
+                    help="convolve: a separable Gaussian blur of SIGMA pixels, clamped at the edge, on the GPU (Scene.convolve "
+                         "through kernel_gaussian; after the warp options and before --out-size)")
+    ap.add_argument("--sharpen", default=None, metavar="AMOUNT[,SIGMA]",
+                    help="convolve: an unsharp mask, picture + AMOUNT * (picture - its Gaussian blur of SIGMA pixels, default 1.5); "
+                         "AMOUNT 0..4; applied after --blur")
+    ap.add_argument("--emboss", action="store_true", help="convolve: a 3 x 3 emboss around mid grey (kernel_emboss, bias 128); applied after --sharpen")
+    ap.add_argument("--edges", action="store_true", help="convolve: the absolute 3 x 3 Laplacian (kernel_laplacian); applied after --emboss")
+    ap.add_argument("--convolve", default=None, metavar="ROWS",
+                    help='convolve: a kernel of integer weights, rows from the top separated by ";", weights by ",": '
+                         '"0,-1,0;-1,5,-1;0,-1,0" (odd sides up to 9; black outside the picture); applied after --edges')
+    ap.add_argument("--convolve-shift", type=int, default=0, metavar="N", help="with --convolve: shift the sum right by N bits, rounded (0..22)")
+    ap.add_argument("--convolve-bias", type=int, default=0, metavar="N", help="with --convolve: add N afterwards (-255..255)")
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="resize: write the picture scaled to W x H (each 1..8192 and at least an eighth of the rendered side) on "
                          "the GPU (Scene.resize; applied last, after --aa, in the place of the --ssaa resolve)")
@@ -286,6 +299,35 @@ def main(argv=None):
             args.warps.append((warp_grid_chromatic(args.chromatic, args.width, args.height), warp_params(edge, per_channel=True)))
     elif args.warp_edge is not None:
         ap.error("--warp-edge goes with --rotate, --lens or --chromatic")
+    args.convolves = []
+    if args.convolve is None and (args.convolve_shift or args.convolve_bias):
+        ap.error("--convolve-shift and --convolve-bias go with --convolve")
+    if args.blur is not None or args.sharpen is not None or args.emboss or args.edges or args.convolve is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--blur, --sharpen, --emboss, --edges and --convolve work on the colour frame of one GPU, by frame count: "
+                     "use --gpus 1, --frames and --view frame")
+        from .scene import convolve_params, kernel_gaussian, kernel_laplacian, kernel_emboss
+        try:
+            if args.blur is not None:
+                k, shift = kernel_gaussian(args.blur)
+                args.convolves.append(convolve_params(k, shift=shift, edge="clamp"))
+            if args.sharpen is not None:
+                v = [float(x) for x in args.sharpen.split(",")]
+                if not 1 <= len(v) <= 2:
+                    raise ValueError("--sharpen takes one or two numbers: AMOUNT[,SIGMA]")
+                k, shift = kernel_gaussian(v[1] if len(v) > 1 else 1.5)
+                args.convolves.append(convolve_params(k, shift=shift, edge="clamp", unsharp=int(round(256.0 * v[0]))))
+            if args.emboss:
+                args.convolves.append(convolve_params(kernel_emboss()[0], bias=128, edge="clamp"))
+            if args.edges:
+                args.convolves.append(convolve_params(kernel_laplacian()[0], edge="clamp", absolute=True))
+            if args.convolve is not None:
+                rows = [[int(x) for x in r.split(",")] for r in args.convolve.split(";")]
+                if len(set(len(r) for r in rows)) != 1:
+                    raise ValueError("--convolve: every row has the same number of weights")
+                args.convolves.append(convolve_params(np.array(rows, np.int32), shift=args.convolve_shift, bias=args.convolve_bias))
+        except ValueError as e:
+            ap.error(str(e))
     args.resize = None
     if args.out_size is not None:
         try:
@@ -558,6 +600,8 @@ def _run(args, T, scene, sharded, rank, say):
     for grid, wp in args.warps:   # in place: --stats, --ssaa and --out-size see the warped frame
         scene.set_warp(grid, args.width, args.height)
         scene.warp(wp)
+    for cp in args.convolves:     # in place, after the warps: --stats, --ssaa and --out-size see the filtered frame
+        scene.convolve(cp)
     if args.stats:
         st = scene.get_frame_stats(depth=True)
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"

@@ -9,6 +9,7 @@
 #include "tr_accumulate.h"
 #include "tr_ao.h"
 #include "tr_composite.h"
+#include "tr_convolve.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_grade.h"
@@ -121,6 +122,11 @@ int launch_resize(const ResizeArgs &a, hipStream_t st);
 // frame only (no band); no depth is read.  a.out_clean: null, or -- the output has the frame's size and its height is a
 // multiple of 16 -- where each workgroup writes the flag of its tile of a.out: a tile flagged there is zeros in every byte.
 int launch_warp(const WarpArgs &a, hipStream_t st);
+// Convolve: a.fb filtered through the integer kernel a.rule into a.out (which does not overlap it) by the rule of
+// tr_convolve.h, through the scene's colour fast-clear flags: k_convolve.  The whole frame only (no band); no depth is
+// read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile
+// of a.out -- a tile flagged there is zeros in every byte.
+int launch_convolve(const ConvolveArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

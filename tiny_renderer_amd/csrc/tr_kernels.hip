@@ -36,6 +36,7 @@
 #include "tr_composite.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
+#include "tr_convolve.h"
 #include "tr_grade.h"
 #include "tr_stats.h"
 #include "tr_kernels.h"
@@ -2695,6 +2696,234 @@ __global__ __launch_bounds__(BLOOM_THREADS) void k_bloom(BloomArgs a)
     dof_store_share<WIDE>(o, px, n_px);
 }
 
+// Convolve (tr_scene_convolve): the frame filtered through a kernel of integer weights into `out`, never in place (a tap
+// reads a neighbour's colour); tr_convolve.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile, the tiles,
+// colour shares and rotated block-to-tile mapping of k_bloom.  The kernel's rows are the buffer's (row 0 = bottom): the
+// rule's row j from the top lies ry - j rows ABOVE the pixel, so staged row r feeds the lane's row k with j = k + 2 ry - r.
+//   * the nine colour flags of the 3 x 3 neighbourhood are workgroup-uniform.  Every neighbour that exists up, and no
+//     border colour in reach (CLAMP, a border of 0, or the halo inside the image): the tile is the constant
+//     convolve_of_zeros, stored without a load, ahead of any barrier; out_clean gets 1 only where that constant is 0;
+//   * staging: the tile and its halo of rx columns and ry rows go to LDS as rows of 160 words (one packed pixel each)
+//     that start 16 pixels left of the tile.  A texel outside the image is the border colour, or under CLAMP the texel at
+//     the clamped index (which lies in one of the nine tiles); a texel behind a raised flag is zeros WITHOUT a load --
+//     that memory is stale.  a.words: four pixels are twelve bytes, three aligned words of the frame, in one tile;
+//   * SEP, the separable form, runs the VERTICAL pass first, LDS to LDS, and the horizontal pass into registers: the
+//     tile is 128 x 16, so the vertical sums are 16 rows of 128 + 2 rx columns (30 KB as three int32 planes), where
+//     horizontal sums would be 16 + 2 ry rows of 128 (69 KB at 31 taps, beyond the 64 KB a workgroup may ask for).
+//     The integers are the same in either order.  A vertical sum is below 255 * sum |col|; M24: that is below 2^23 and
+//     the horizontal pass multiplies in 24 bits, otherwise in 32.  A lane owns a column and eight rows in both passes;
+//     the eight weights a staged row feeds are a window that slides by one a row: one scalar load a row or a tap;
+//   * the general form takes its kw * kh taps from the staged tile, column by column of the kernel, by the same window;
+//   * a weight of 0 is skipped by a uniform branch (horizontal pass) or costs its multiply-adds (the windows);
+//   * the results go through the first 8 KB of the staged rows to the colour shares -- a lane owns 16 pixels of a row.
+// LDS, dynamic: (16 + 2 ry) * 640 bytes, and 30,720 more for SEP: 10 KB at 1 x 1 general, 15 KB at 9 x 9, 58.75 KB at
+// 31 x 31.  fb and every flag of the frame are only read.  STORE (the launcher checks): 2 -- width % 16 == 0 and out
+// 16-byte aligned, a share is three 16-byte stores; 1 -- width % 4 == 0 and out 4-byte aligned, a share is up to four
+// 12-byte pieces; 0 -- guarded bytes.  No atomics, no scratch, no inline assembly.
+constexpr int CONV_LDS_W = TILE_W + 32, CONV_THREADS = 256, CONV_ROWS = TILE_W * TILE_H / CONV_THREADS;
+static_assert((TILE_H + 2 * (CONVOLVE_MAX_SEPARABLE / 2)) * CONV_LDS_W * 4 + 3 * TILE_H * CONV_LDS_W * 4 < 65536, "the largest kernel's LDS is below 64 KB");
+static_assert(CONVOLVE_MAX_SEPARABLE / 2 <= 15 && CONVOLVE_MAX_SEPARABLE / 2 < TILE_H, "the halo lies in the eight tiles around, 16 columns left of the tile included");
+
+// The window of a lane's eight rows over one staged column: `src` is the lane's first staged row (row stride
+// CONV_LDS_W), n_rows = CONV_ROWS + 2 ry staged rows feed it, staged row jj feeds row k with the weight
+// weights[w0 + (k + 2 ry - jj) * w_stride] where that index is a row of the kernel.
+#define CONV_WINDOW(acc, src, w0, w_stride)                                                                          \
+    {                                                                                                                \
+        int32_t wk[CONV_ROWS];                                                                                       \
+        _Pragma("unroll") for (int k = 0; k < CONV_ROWS; k++) wk[k] = 0;                                             \
+        wk[0] = a.rule.weights[(w0) + 2 * ry * (w_stride)];                                                          \
+        for (int32_t jj = 0; jj < CONV_ROWS + 2 * ry; jj++) {                                                        \
+            const int32_t jn = 2 * ry - jj - 1;                                                                      \
+            const int32_t w_next = jn >= 0 ? a.rule.weights[(w0) + jn * (w_stride)] : 0;                             \
+            const uint32_t px = (src)[jj * CONV_LDS_W];                                                              \
+            const int32_t pr = (int32_t)(px & 0xFFu), pg = (int32_t)((px >> 8) & 0xFFu), pb = (int32_t)(px >> 16);   \
+            _Pragma("unroll") for (int k = 0; k < CONV_ROWS; k++) {                                                  \
+                acc[k][0] += convolve_mul24(wk[k], pr);                                                              \
+                acc[k][1] += convolve_mul24(wk[k], pg);                                                              \
+                acc[k][2] += convolve_mul24(wk[k], pb);                                                              \
+            }                                                                                                        \
+            _Pragma("unroll") for (int k = CONV_ROWS - 1; k > 0; k--) wk[k] = wk[k - 1];                             \
+            wk[0] = w_next;                                                                                          \
+        }                                                                                                            \
+    }
+
+// The 16 finished pixels of a share (24 bits each) into `o`.  STORE 2: three 16-byte pieces (k_dof's wide form); 1: a
+// piece of four pixels is twelve bytes at a multiple of four -- three words stored together --, n_px / 4 pieces (the
+// width is a multiple of 4, so n_px is); 0: n_px * 3 guarded bytes.
+template <int STORE>
+__device__ __forceinline__ void conv_store_share(uint8_t *o, const uint32_t (&px)[16], int32_t n_px)
+{
+    if (STORE == 1) {
+        struct alignas(4) Piece {
+            uint32_t w0, w1, w2;
+        };
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+            if (4 * g < n_px) {
+                Piece q;
+                q.w0 = px[4 * g] | (px[4 * g + 1] << 24);
+                q.w1 = (px[4 * g + 1] >> 8) | (px[4 * g + 2] << 16);
+                q.w2 = (px[4 * g + 2] >> 16) | (px[4 * g + 3] << 8);
+                reinterpret_cast<Piece *>(o)[g] = q;
+            }
+    } else {
+        dof_store_share<STORE == 2>(o, px, n_px);
+    }
+}
+
+template <bool SEP, int STORE, bool M24>
+__global__ __launch_bounds__(CONV_THREADS) void k_convolve(ConvolveArgs a)
+{
+    static_assert(TILE_W == 128 && CONV_THREADS == 2 * TILE_W && 8 * TILE_H <= CONV_THREADS && CONV_ROWS == 8, "a lane owns a column and eight rows; the shares are the first lanes");
+    // (TILE_H + 2 ry) rows of CONV_LDS_W packed pixels; SEP: then three planes of TILE_H rows of CONV_LDS_W int32 sums
+    extern __shared__ __align__(16) uint32_t s_cv[];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t kw = (int32_t)a.rule.kw, kh = (int32_t)a.rule.kh, rx = kw / 2, ry = kh / 2;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    // (k_bloom's mapping: the tile of row ty that lies 5 * ty columns right of column b % ntx)
+    const int32_t ty = (int32_t)blockIdx.x / ntx, tx = ((int32_t)blockIdx.x % ntx + 5 * ty) % ntx;
+    const uint32_t t = (uint32_t)(ty * ntx + tx);
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): exists -- it is part of the grid; czero -- and its flag is up
+    uint32_t exists = 0u, czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) continue;
+            exists |= bit;
+            if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+        }
+    const bool clamp = a.rule.edge == CONVOLVE_CLAMP;
+    const bool halo_inside = x0 - rx >= 0 && x0 + TILE_W + rx <= W && y0 - ry >= 0 && y0 + TILE_H + ry <= H;
+    const bool constant = czero == exists && (clamp || a.rule.border == 0u || halo_inside);
+    // the colour shares of k_composite
+    const int32_t sx = x0 + (int32_t)(threadIdx.x % 8u) * 16, srow = (int32_t)(threadIdx.x / 8u), sy = y0 + srow;
+    const bool share = threadIdx.x < 8u * TILE_H && sx < W && sy < H;
+    const int32_t n_px = share ? min(16, W - sx) : 0;  // (STORE 2: 16 or none; 1: a multiple of 4)
+    const size_t share_at = share ? ((size_t)(H - 1 - sy) * (size_t)W + (size_t)sx) * 3u : 0u;
+    uint8_t *o = a.out + share_at;
+    uint32_t px[16];
+    const uint32_t c0 = convolve_of_zeros(a.rule) * 0x010101u;
+    if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = constant && c0 == 0u ? 1u : 0u;
+    if (constant) {  // (workgroup-uniform, ahead of the barriers)
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = c0;
+        conv_store_share<STORE>(o, px, n_px);
+        return;
+    }
+    // LDS row r is the kernel's row y0 - ry + r, LDS column c the frame's column x0 - 16 + c; columns c_lo .. c_hi - 1 are read
+    const int32_t rows = TILE_H + 2 * ry, c_lo = 16 - rx, c_hi = 16 + TILE_W + rx;
+    if (a.words != 0u) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (CONV_LDS_W / 4); p += CONV_THREADS) {
+            const int32_t r = p / (CONV_LDS_W / 4), j = p % (CONV_LDS_W / 4);
+            if (4 * j + 3 < c_lo || 4 * j >= c_hi) continue;  // (no tap reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - ry + r;
+            // (x and the width are multiples of 4: the four pixels lie inside the image's columns or outside together)
+            const bool x_out = x < 0 || x >= W, y_out = y < 0 || y >= H;
+            uint32_t c[4] = { a.rule.border, a.rule.border, a.rule.border, a.rule.border };
+            if (clamp || !(x_out || y_out)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                c[0] = c[1] = c[2] = c[3] = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = a.fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    if (!x_out) {
+                        const uint32_t *q4 = reinterpret_cast<const uint32_t *>(q);
+                        const uint32_t w0 = q4[0], w1 = q4[1], w2 = q4[2];
+                        c[0] = w0 & 0xFFFFFFu;
+                        c[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                        c[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                        c[3] = w2 >> 8;
+                    } else {
+                        c[0] = c[1] = c[2] = c[3] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+                    }
+                }
+            }
+            *reinterpret_cast<uint4 *>(&s_cv[r * CONV_LDS_W + 4 * j]) = make_uint4(c[0], c[1], c[2], c[3]);
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * CONV_LDS_W; p += CONV_THREADS) {
+            const int32_t r = p / CONV_LDS_W, c = p % CONV_LDS_W;
+            if (c < c_lo || c >= c_hi) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - ry + r;
+            uint32_t col = a.rule.border;
+            if (clamp || !(x < 0 || x >= W || y < 0 || y >= H)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                col = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = a.fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    col = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+                }
+            }
+            s_cv[r * CONV_LDS_W + c] = col;
+        }
+    }
+    __syncthreads();
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, row0 = (int32_t)threadIdx.x / TILE_W * CONV_ROWS;
+    int32_t acc[CONV_ROWS][3];
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++) acc[k][0] = acc[k][1] = acc[k][2] = 0;
+    if (SEP) {
+        // the vertical pass: staged column c, rows 8 h .. 8 h + 7 of the tile, into the planes
+        int32_t *s_v = reinterpret_cast<int32_t *>(s_cv + rows * CONV_LDS_W);
+        const int32_t n_cols = c_hi - c_lo;
+        for (int32_t item = (int32_t)threadIdx.x; item < 2 * n_cols; item += CONV_THREADS) {
+            const int32_t h = item >= n_cols ? 1 : 0, c = item - h * n_cols + c_lo;
+            int32_t v[CONV_ROWS][3];
+#pragma unroll
+            for (int k = 0; k < CONV_ROWS; k++) v[k][0] = v[k][1] = v[k][2] = 0;
+            const uint32_t *src = s_cv + h * CONV_ROWS * CONV_LDS_W + c;
+            CONV_WINDOW(v, src, kw, 1)
+#pragma unroll
+            for (int k = 0; k < CONV_ROWS; k++)
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) s_v[(ch * TILE_H + h * CONV_ROWS + k) * CONV_LDS_W + c] = v[k][ch];
+        }
+        __syncthreads();
+        // the horizontal pass: column `col`, rows row0 .. row0 + 7 of the tile
+        for (int32_t i = 0; i < kw; i++) {
+            const int32_t w = a.rule.weights[i];
+            if (w == 0) continue;  // (scalar)
+            const int32_t *src = s_v + row0 * CONV_LDS_W + 16 + col + i - rx;
+#pragma unroll
+            for (int k = 0; k < CONV_ROWS; k++)
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) {
+                    const int32_t v = src[(ch * TILE_H + k) * CONV_LDS_W];
+                    acc[k][ch] += M24 ? convolve_mul24(w, v) : w * v;
+                }
+        }
+    } else {
+        for (int32_t i = 0; i < kw; i++) {
+            const uint32_t *src = s_cv + row0 * CONV_LDS_W + 16 + col + i - rx;
+            CONV_WINDOW(acc, src, i, kw)
+        }
+    }
+    // the frame's own pixels, staged: row k of the tile is staged row ry + k
+    uint32_t res[CONV_ROWS];
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++)
+        res[k] = convolve_finish_px(acc[k][0], acc[k][1], acc[k][2], s_cv[(ry + row0 + k) * CONV_LDS_W + 16 + col], a.rule);
+    __syncthreads();  // every staged pixel has been read: the results take the place of the first rows
+    uint32_t *s_out = s_cv;
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++) s_out[(row0 + k) * TILE_W + col] = res[k];
+    __syncthreads();
+    if (!share) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&s_out[srow * TILE_W + (sx - x0) + 4 * k]);
+        px[4 * k + 0] = v.x, px[4 * k + 1] = v.y, px[4 * k + 2] = v.z, px[4 * k + 3] = v.w;
+    }
+    conv_store_share<STORE>(o, px, n_px);
+}
+#undef CONV_WINDOW
+
 // Colour grading (tr_scene_grade): every pixel of the frame mapped through the scene's 3-D lookup table into `out`,
 // which may BE the frame (a pixel depends on itself alone); tr_grade.h has the rule.  The working set is the table, not
 // a neighbourhood, so the workgroups are PERSISTENT: the launcher starts as many as the machine holds at once (by the
@@ -4484,6 +4713,45 @@ int launch_bloom(const BloomArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_bloom<true>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
     else
         hipLaunchKernelGGL((k_bloom<false>), dim3(n_tiles), dim3(BLOOM_THREADS), lds, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_convolve(const ConvolveArgs &a0, hipStream_t st)
+{
+    ConvolveArgs a = a0;
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    const bool sep = (a.rule.flags & CONVOLVE_SEPARABLE) != 0u;
+    const uint32_t k_max = sep ? (uint32_t)CONVOLVE_MAX_SEPARABLE : (uint32_t)CONVOLVE_MAX_GENERAL;
+    if (a.rule.kw % 2u == 0u || a.rule.kh % 2u == 0u || a.rule.kw > k_max || a.rule.kh > k_max || a.rule.shift > CONVOLVE_MAX_SHIFT ||
+        a.rule.edge > CONVOLVE_CLAMP || a.rule.amount > CONVOLVE_MAX_AMOUNT)
+        return (int)hipErrorInvalidValue;
+    // `out` is never the frame that is read
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // staging by words: four pixels at a multiple of four are three aligned words of the frame
+    a.words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u ? 1u : 0u;
+    // the stores: every share three whole 16-byte pieces of `out`, else whole 12-byte pieces at multiples of 4, else bytes
+    const int store = a.frame.width % 16u == 0u && (uintptr_t)a.out % 16u == 0u ? 2 : a.frame.width % 4u == 0u && (uintptr_t)a.out % 4u == 0u ? 1 : 0;
+    int64_t col_sum = 0;
+    for (uint32_t j = 0; sep && j < a.rule.kh; j++) col_sum += std::abs((int64_t)a.rule.weights[a.rule.kw + j]);
+    a.rule.mul24 = sep && col_sum <= CONVOLVE_MAX_ROW ? 1 : 0;
+    const size_t lds = (size_t)(TILE_H + 2 * (int)(a.rule.kh / 2u)) * CONV_LDS_W * 4u + (sep ? (size_t)3 * TILE_H * CONV_LDS_W * 4u : 0u);
+    const dim3 grid(n_tiles), block(CONV_THREADS);
+#define CONV_LAUNCH(SEP_, M24_)                                                                                  \
+    {                                                                                                            \
+        if (store == 2) hipLaunchKernelGGL((k_convolve<SEP_, 2, M24_>), grid, block, lds, st, a);                \
+        else if (store == 1) hipLaunchKernelGGL((k_convolve<SEP_, 1, M24_>), grid, block, lds, st, a);           \
+        else hipLaunchKernelGGL((k_convolve<SEP_, 0, M24_>), grid, block, lds, st, a);                           \
+    }
+    if (!sep) CONV_LAUNCH(false, true)
+    else if (a.rule.mul24) CONV_LAUNCH(true, true)
+    else CONV_LAUNCH(true, false)
+#undef CONV_LAUNCH
     TR_LAUNCH_CHECK();
     return 0;
 }

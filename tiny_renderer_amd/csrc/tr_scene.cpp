@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2832,7 +2832,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, resize) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none); the cleared-scene shortcut where the stage has one --
@@ -5221,6 +5221,138 @@ int tr_warp_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint32_t o
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_warp_host: null argument");
     if (out == rgb) return tr::fail(TR_E_INVALID, "tr_warp_host: out is rgb (a pixel reads other pixels: not in place)");
     warp_host(width, height, rgb, out_width, out_height, grid, warp_rule(p), out);
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_CONVOLVE_SEPARABLE == CONVOLVE_SEPARABLE && TR_CONVOLVE_ABS == CONVOLVE_ABS && TR_CONVOLVE_UNSHARP == CONVOLVE_UNSHARP &&
+                  TR_CONVOLVE_BORDER == CONVOLVE_BORDER && TR_CONVOLVE_CLAMP == CONVOLVE_CLAMP && sizeof(tr_convolve_params) == 200 &&
+                  sizeof(((tr_convolve_params *)nullptr)->weights) == CONVOLVE_MAX_WEIGHTS * sizeof(int16_t),
+              "tr_convolve.h restates the header");
+
+// tr_convolve_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_convolve_params(const tr_convolve_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->struct_size != sizeof(tr_convolve_params)) return tr::fail(TR_E_INVALID, w + ": struct_size is not sizeof(tr_convolve_params)");
+    if (p->flags & ~(TR_CONVOLVE_SEPARABLE | TR_CONVOLVE_ABS | TR_CONVOLVE_UNSHARP)) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    const bool sep = (p->flags & TR_CONVOLVE_SEPARABLE) != 0u, unsharp = (p->flags & TR_CONVOLVE_UNSHARP) != 0u;
+    const uint32_t k_max = sep ? (uint32_t)CONVOLVE_MAX_SEPARABLE : (uint32_t)CONVOLVE_MAX_GENERAL;
+    if (p->kw % 2u == 0u || p->kh % 2u == 0u || p->kw > k_max || p->kh > k_max)
+        return tr::fail(TR_E_INVALID, w + (sep ? ": kw and kh must be odd and 1..31 (TR_CONVOLVE_SEPARABLE)" : ": kw and kh must be odd and 1..9 (1..31 with TR_CONVOLVE_SEPARABLE)"));
+    if (p->shift > CONVOLVE_MAX_SHIFT) return tr::fail(TR_E_INVALID, w + ": shift must be 0..22");
+    if (p->bias < -CONVOLVE_MAX_BIAS || p->bias > CONVOLVE_MAX_BIAS) return tr::fail(TR_E_INVALID, w + ": bias must be -255..255");
+    if (p->amount > CONVOLVE_MAX_AMOUNT) return tr::fail(TR_E_INVALID, w + ": amount must be 0..1024");
+    if (!unsharp && p->amount != 0u) return tr::fail(TR_E_INVALID, w + ": amount must be 0 without TR_CONVOLVE_UNSHARP");
+    if (p->edge != TR_CONVOLVE_BORDER && p->edge != TR_CONVOLVE_CLAMP) return tr::fail(TR_E_INVALID, w + ": edge must be TR_CONVOLVE_BORDER or TR_CONVOLVE_CLAMP");
+    if (p->pad != 0u) return tr::fail(TR_E_INVALID, w + ": pad must be 0");
+    auto sum_abs = [&](uint32_t first, uint32_t n) {
+        int64_t a = 0;
+        for (uint32_t i = 0; i < n; i++) a += std::abs((int64_t)p->weights[first + i]);
+        return a;
+    };
+    const int64_t row = sep ? sum_abs(0u, p->kw) : 0;
+    const int64_t A = sep ? row * sum_abs(p->kw, p->kh) : sum_abs(0u, p->kw * p->kh);
+    if (A > CONVOLVE_MAX_A) return tr::fail(TR_E_INVALID, w + ": the weights' absolute sum exceeds 2^22 (separable: the product of the row's and the column's)");
+    if (row > CONVOLVE_MAX_ROW) return tr::fail(TR_E_INVALID, w + ": the row's absolute sum exceeds 2^15");
+    if (unsharp && (p->flags & TR_CONVOLVE_ABS)) return tr::fail(TR_E_INVALID, w + ": TR_CONVOLVE_UNSHARP does not go with TR_CONVOLVE_ABS");
+    if (unsharp && p->bias != 0) return tr::fail(TR_E_INVALID, w + ": TR_CONVOLVE_UNSHARP needs a bias of 0");
+    return TR_OK;
+}
+
+ConvolveRule convolve_rule(const tr_convolve_params *p)
+{
+    ConvolveRule r = {};
+    r.kw = p->kw, r.kh = p->kh, r.flags = p->flags, r.shift = p->shift, r.bias = p->bias, r.amount = p->amount, r.edge = p->edge;
+    r.border = (uint32_t)p->border[0] | ((uint32_t)p->border[1] << 8) | ((uint32_t)p->border[2] << 16);
+    const uint32_t n = (p->flags & TR_CONVOLVE_SEPARABLE) ? p->kw + p->kh : p->kw * p->kh;
+    for (uint32_t i = 0; i < n; i++) r.weights[i] = p->weights[i];  // (entries behind the last one used are not read)
+    return r;
+}
+
+int check_convolve_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be convolved: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// Is the rule's image of a black frame black?  The constant of a neighbourhood of zeros is 0, and no border colour
+// comes in: TR_CONVOLVE_CLAMP, or a border of 0.
+bool convolve_of_black_is_black(const tr_convolve_params *p)
+{
+    return convolve_of_zeros(convolve_rule(p)) == 0u && (p->edge == TR_CONVOLVE_CLAMP || (p->border[0] | p->border[1] | p->border[2]) == 0u);
+}
+
+// Enqueues the current frame, filtered, into `out_device` (which overlaps no frame of the scene) behind everything
+// issued so far; out_clean: null, or where k_convolve writes the flags of `out_device`.  A pending clear is made real
+// first.  No depth is read: a depth left on the chip stays there.
+int enqueue_convolve(tr_scene *s, const tr_convolve_params *p, uint8_t *out_device, uint32_t *out_clean)
+{
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st != TR_OK) return st;
+    ConvolveArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+    a.rule = convolve_rule(p);
+    {
+        Timed t(s, K_CONVOLVE);
+        int rc = launch_convolve(a, s->stream);
+        if (rc) return launch_status(rc, "k_convolve");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_convolve(tr_scene *s, const tr_convolve_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_convolve: null scene");
+    int st = check_convolve_params(p, "tr_scene_convolve");
+    if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_convolve");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_convolve", "tr_scene_get_convolved", "convolves", 0u, &target);
+    if (st != TR_OK) return st;
+    // a logically cleared frame is black, and so is its image where the rule gives black: zeros out of place, itself in place
+    if (s->z_fb_cleared && convolve_of_black_is_black(p)) return target ? cleared_out_of_place(s, target) : TR_OK;
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_convolved: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_convolved: null argument");
+    int st = check_convolve_params(p, "tr_scene_get_convolved");
+    if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_get_convolved");
+    if (st != TR_OK) return st;
+    // (the predicate takes the scene alone: the parameters decide here which one is asked)
+    return get_stage(s, rgb, frame_bytes(s), convolve_of_black_is_black(p) ? cleared : nullptr,
+                     [&](uint8_t *o) { return enqueue_convolve(s, p, o, nullptr); });
+}
+
+// The rule of tr_convolve.h over a caller's array, on the host.  Needs no GPU.
+int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out, const tr_convolve_params *p)
+{
+    int st = check_convolve_params(p, "tr_convolve_host");
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_convolve_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_convolve_host: out is rgb (the rule reads neighbours: not in place)");
+    convolve_host(width, height, rgb, out, convolve_rule(p));
     return TR_OK;
 }
 

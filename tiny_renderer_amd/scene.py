@@ -648,6 +648,158 @@ def warp_grid_chromatic(px, width, height):
                      for m in (1.0 - e, 1.0, 1.0 + e)])
 
 
+CONVOLVE_SEPARABLE, CONVOLVE_ABS, CONVOLVE_UNSHARP, CONVOLVE_BORDER, CONVOLVE_CLAMP = 1, 2, 4, 0, 1   # (TR_CONVOLVE_*)
+CONVOLVE_EDGES = {"border": CONVOLVE_BORDER, "clamp": CONVOLVE_CLAMP}
+CONVOLVE_AXIS_SHIFT = 11   # the builders' normalised rows sum to 2^11: a row and a column make A = 2^22, the largest allowed
+
+
+class ConvolveParams(C.Structure):
+    """tr_convolve_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("kw", C.c_uint32), ("kh", C.c_uint32), ("flags", C.c_uint32), ("shift", C.c_uint32),
+                ("bias", C.c_int32), ("amount", C.c_uint32), ("edge", C.c_uint32), ("border", C.c_uint8 * 3), ("pad", C.c_uint8),
+                ("weights", C.c_int16 * 82)]
+
+
+def convolve_params(kernel, shift=0, bias=0, edge="border", border=(0, 0, 0), absolute=False, unsharp=None):
+    """tr_convolve_params for Scene.convolve / Scene.get_convolved / convolve_host.  kernel: an integer array [kh, kw]
+    (the general form, kw and kh odd and 1..9; kernel[j][i] is the weight of row j from the top, column i from the left)
+    or a pair (row, col) of 1-D integer arrays (the separable form, 1..31 taps each, w(i, j) = row[i] * col[j]).  The sum
+    of the weighted neighbours is shifted right by `shift` (0..22, rounded), made absolute with absolute=True, and `bias`
+    (-255..255) is added; unsharp=AMOUNT (0..1024 in 1/256) sharpens instead: F + AMOUNT / 256 * (F - filtered).  edge:
+    "border" (a tap outside the image is `border`, r g b) or "clamp".  ValueError, in the library's words, for what it
+    would refuse (include/tiny_renderer.h)."""
+    if edge in CONVOLVE_EDGES:
+        e = CONVOLVE_EDGES[edge]
+    elif not isinstance(edge, (bool, str)) and edge in CONVOLVE_EDGES.values():
+        e = int(edge)
+    else:
+        raise ValueError("convolve: edge must be TR_CONVOLVE_BORDER or TR_CONVOLVE_CLAMP")
+    b = [int(v) for v in border]
+    if len(b) != 3 or any(not 0 <= v <= 255 for v in b):
+        raise ValueError("convolve: border is three values 0..255")
+    for name, v in (("shift", shift), ("bias", bias)) + ((("unsharp", unsharp),) if unsharp is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("convolve: %s must be an integer" % name)
+    if not 0 <= shift <= 22:
+        raise ValueError("convolve: shift must be 0..22")
+    if not -255 <= bias <= 255:
+        raise ValueError("convolve: bias must be -255..255")
+    if unsharp is not None and not 0 <= unsharp <= 1024:
+        raise ValueError("convolve: amount must be 0..1024")
+    flags = (CONVOLVE_ABS if absolute else 0) | (CONVOLVE_UNSHARP if unsharp is not None else 0)
+    if isinstance(kernel, tuple) and len(kernel) == 2:
+        flags |= CONVOLVE_SEPARABLE
+        parts = [np.asarray(v) for v in kernel]
+        if any(v.ndim != 1 or v.dtype.kind not in "iu" for v in parts):
+            raise ValueError("convolve: (row, col) are two 1-D integer arrays")
+        kw, kh = parts[0].size, parts[1].size
+        if kw % 2 == 0 or kh % 2 == 0 or kw > 31 or kh > 31:
+            raise ValueError("convolve: kw and kh must be odd and 1..31 (TR_CONVOLVE_SEPARABLE)")
+        taps = np.concatenate(parts)
+    else:
+        k = np.asarray(kernel)
+        if k.ndim != 2 or k.dtype.kind not in "iu":
+            raise ValueError("convolve: the kernel is a 2-D integer array [kh, kw], or a pair (row, col)")
+        kh, kw = k.shape
+        if kw % 2 == 0 or kh % 2 == 0 or kw > 9 or kh > 9:
+            raise ValueError("convolve: kw and kh must be odd and 1..9 (1..31 with TR_CONVOLVE_SEPARABLE)")
+        taps = k.reshape(-1)
+    if taps.size and (int(taps.min()) < -32768 or int(taps.max()) > 32767):
+        raise ValueError("convolve: a weight does not fit an int16")
+    p = ConvolveParams(C.sizeof(ConvolveParams), kw, kh, flags, int(shift), int(bias), int(unsharp or 0), e, (C.c_uint8 * 3)(*b), 0)
+    for i, v in enumerate(taps):
+        p.weights[i] = int(v)
+    L = load_library()
+    if L.tr_convolve_host(0, 0, None, None, C.addressof(p)) != 0:   # (an empty image: the parameter checks alone)
+        raise ValueError(L.tr_last_error().decode().replace("tr_convolve_host", "convolve", 1))
+    return p
+
+
+def convolve_host(rgb, params):
+    """tr_convolve_host: the rule of Scene.convolve on the host (no GPU needed), by the inline functions k_convolve calls.
+    rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from convolve_params.  Returns the filtered frame and
+    leaves its arguments alone."""
+    if not isinstance(params, ConvolveParams):
+        raise ValueError("convolve_host: params must come from convolve_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("convolve_host: rgb [H, W, 3]")
+    out = np.empty_like(src)
+    check(load_library().tr_convolve_host(src.shape[1], src.shape[0], src.ctypes.data, out.ctypes.data, C.addressof(params)))
+    return out
+
+
+def _convolve_normalise(w, shift=CONVOLVE_AXIS_SHIFT):
+    """The symmetric positive taps `w` (odd length) as integers that sum to exactly 2^shift and stay symmetric: the left
+    half by cumulative rounding (each tap is the difference of two rounded running sums), mirrored, the centre takes the
+    rest -- the way the resize tables reach 4096."""
+    w = np.asarray(w, np.float64)
+    r = w.size // 2
+    run = np.floor(np.cumsum(w[:r]) / w.sum() * (1 << shift) + 0.5).astype(np.int64)
+    left = np.diff(np.concatenate([[0], run]))
+    return np.concatenate([left, [(1 << shift) - 2 * int(left.sum())], left[::-1]]).astype(np.int32)
+
+
+def kernel_gaussian(sigma, radius=None):
+    """((row, col), shift): a separable Gaussian of standard deviation `sigma` pixels, cut at `radius` (default
+    ceil(3 sigma), at most 15).  Each axis sums to 2^11, shift is 22: a flat colour stays."""
+    r = int(min(15, max(1, np.ceil(3.0 * float(sigma))))) if radius is None else int(radius)
+    if not 0 <= r <= 15 or not float(sigma) > 0.0:
+        raise ValueError("kernel_gaussian: sigma above 0, radius 0..15")
+    d = np.arange(-r, r + 1, dtype=np.float64)
+    g = _convolve_normalise(np.exp(-0.5 * (d / float(sigma)) ** 2))
+    return (g, g.copy()), 2 * CONVOLVE_AXIS_SHIFT
+
+
+def kernel_box(rx, ry):
+    """((row, col), shift): the mean over (2 rx + 1) x (2 ry + 1) pixels, rx and ry 0..15; each axis sums to 2^11."""
+    if not (0 <= int(rx) <= 15 and 0 <= int(ry) <= 15):
+        raise ValueError("kernel_box: rx and ry 0..15")
+    return (_convolve_normalise(np.ones(2 * int(rx) + 1)), _convolve_normalise(np.ones(2 * int(ry) + 1))), 2 * CONVOLVE_AXIS_SHIFT
+
+
+def kernel_tent(R):
+    """((row, col), shift): the tent of radius R (0..15) on both axes.  Where R + 1 is a power of two the taps are the
+    plain [1 .. R + 1 .. 1] and shift = 4 log2(R + 1) -- under a border of 0 tr_scene_bloom's glow at threshold 0;
+    otherwise each axis is normalised to 2^11."""
+    R = int(R)
+    if not 0 <= R <= 15:
+        raise ValueError("kernel_tent: R 0..15")
+    t = (R + 1 - np.abs(np.arange(-R, R + 1))).astype(np.int32)
+    if (R + 1) & R == 0:
+        return (t, t.copy()), 4 * int(R + 1).bit_length() - 4
+    t = _convolve_normalise(t)
+    return (t, t.copy()), 2 * CONVOLVE_AXIS_SHIFT
+
+
+def kernel_sobel(axis):
+    """(kernel, 0): the 3 x 3 Sobel derivative along "x" (left to right) or "y" (top to bottom); use absolute=True or a
+    bias of 128 to see both signs."""
+    if axis not in ("x", "y"):
+        raise ValueError('kernel_sobel: axis "x" or "y"')
+    k = np.array([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]], np.int32)
+    return (k if axis == "x" else np.ascontiguousarray(k.T)), 0
+
+
+def kernel_laplacian():
+    """(kernel, 0): the 3 x 3 four-neighbour Laplacian; with absolute=True an edge detector."""
+    return np.array([[0, 1, 0], [1, -4, 1], [0, 1, 0]], np.int32), 0
+
+
+def kernel_emboss():
+    """(kernel, 0): a 3 x 3 emboss lit from the top left; its weights sum to 0, so use a bias of 128."""
+    return np.array([[-1, -1, 0], [-1, 0, 1], [0, 1, 1]], np.int32), 0
+
+
+def kernel_motion(length, horizontal=True):
+    """((row, col), shift): a directional blur over `length` pixels (odd, 1..31) along x or along y; sums to 2^11."""
+    n = int(length)
+    if n % 2 == 0 or not 1 <= n <= 31:
+        raise ValueError("kernel_motion: length odd and 1..31")
+    line, one = _convolve_normalise(np.ones(n)), np.array([1], np.int32)
+    return ((line, one) if horizontal else (one, line)), CONVOLVE_AXIS_SHIFT
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1540,6 +1692,31 @@ class Scene:
             raise ValueError("get_warped: params must come from warp_params")
         w, h = getattr(self, "_warp_size", (self.width, self.height))
         return self._image("tr_scene_get_warped", strict, C.addressof(params), out=np.empty((h, w, 3), np.uint8))
+
+    # --- convolve (tr_scene_convolve / tr_scene_get_convolved) -----------------------------------------
+    def convolve(self, params, out=None):
+        """tr_scene_convolve: filters the current frame through a kernel of integer weights on the device (params from
+        convolve_params; kernel_gaussian, kernel_box, kernel_tent, kernel_sobel, kernel_laplacian, kernel_emboss and
+        kernel_motion build the usual ones).  out=None: in place -- every later consumer (the getters, resize, resolve,
+        the sparse read-back) sees the filtered frame, z, winner words and the shadow buffer stay, calling it twice
+        filters twice.  Otherwise `out` is a torch tensor on the scene's device or a device pointer (int) to 3 * W * H
+        bytes that overlaps no frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it
+        is.  Asynchronous: the result is there after sync().  Band scenes are refused.  No depth is needed."""
+        if not isinstance(params, ConvolveParams):
+            raise ValueError("convolve: params must come from convolve_params")
+        target = out.data_ptr() if hasattr(out, "data_ptr") else out
+        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < self.width * self.height * 3 or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
+        ptr = self._out_pointer(target)
+        check(load_library().tr_scene_convolve(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_convolved(self, params, strict=True):
+        """tr_scene_get_convolved: the current frame filtered on the device, as an [H, W, 3] uint8 array equal to
+        convolve_host(get_frame_buffer(), params) in every byte.  Synchronizes; the scene's frame stays."""
+        if not isinstance(params, ConvolveParams):
+            raise ValueError("get_convolved: params must come from convolve_params")
+        return self._image("tr_scene_get_convolved", strict, C.addressof(params))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
