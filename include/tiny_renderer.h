@@ -1106,6 +1106,82 @@ int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rg
 int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
                      const tr_convolve_params *p);
 
+/* YUV output: the scene's CURRENT frame, or any rgb8 image on the device, converted on the device to 8-bit YCbCr planes --
+ * the form encoders and video files take, 1.5 bytes a pixel in 4:2:0 where rgb8 has 3 -- as the chain's very last step
+ * (render, composite, ..., resize, TO_YUV, read back).  The source F is the image tr_scene_get_frame_buffer would return:
+ * W x H, row 0 = top, rgb8; the output has its orientation and is tightly packed (no pitch).  cw = (W + 1) / 2, ch =
+ * (H + 1) / 2.
+ *   TR_YUV_I420  Y (W x H), U (cw x ch), V (cw x ch), in this order                        W H + 2 cw ch bytes
+ *   TR_YUV_NV12  Y (W x H), then ONE plane of cw x ch interleaved (U, V) byte pairs        W H + 2 cw ch bytes
+ *   TR_YUV_I444  Y, U, V, each W x H                                                       3 W H bytes
+ * Coefficients, in units of 1 / 65536, rows (r, g, b): the nearest integers to the real matrix (Kr, Kb = 0.299, 0.114 for
+ * TR_YUV_BT601 and 0.2126, 0.0722 for TR_YUV_BT709; TR_YUV_LIMITED scales Y by 219 / 255 and chroma by 224 / 255), the
+ * green entry adjusted so that a Y row sums to the rounded scale and a chroma row to exactly 0:
+ *   601 full     Y 19595 38470 7471   U -11058 -21710 32768   V 32768 -27439 -5329   y0 0
+ *   601 limited  Y 16829 33039 6416   U  -9714 -19070 28784   V 28784 -24103 -4681   y0 16
+ *   709 full     Y 13933 46871 4732   U  -7509 -25259 32768   V 32768 -29763 -3005   y0 0
+ *   709 limited  Y 11966 40254 4064   U  -6596 -22188 28784   V 28784 -26145 -2639   y0 16
+ * Per pixel, in i32 with arithmetic shifts:  Y = (yr R + yg G + yb B + (y0 << 16) + 32768) >> 16.  For TR_YUV_I444, U and
+ * V have the same form with their own rows and 128 in the place of y0.  For 4:2:0, chroma sample (i, j) covers columns 2i
+ * and min(2i + 1, W - 1) and rows 2j and min(2j + 1, H - 1) -- at an odd edge the last column or row counts twice --, Rs,
+ * Gs, Bs are the sums of those four pixels (0..1020) and the result is rounded once:
+ *     U = (ur Rs + ug Gs + ub Bs + (128 << 18) + (1 << 17)) >> 18, V alike with the V row.
+ * Every result is then clamped to 0..255.  It follows: the clamp only acts at the top (full range: pure blue gives U = 256
+ * and pure red V = 256 before it; limited range stays within 16..235 / 16..240; nothing goes negative); a grey v gives
+ * Y = v in full range and U = V = 128 in every table; black gives (y0, 128, 128); every accumulator stays below 2^27.  The
+ * 4:2:0 siting is the centred one (C420jpeg in a Y4M header).  This Y is NOT tr_frame_stats' 8-bit luma (54, 183, 19).
+ * No gamma: the bytes are converted as stored. */
+#define TR_YUV_I420 0u
+#define TR_YUV_NV12 1u
+#define TR_YUV_I444 2u
+#define TR_YUV_BT601 0u
+#define TR_YUV_BT709 1u
+#define TR_YUV_FULL 0u
+#define TR_YUV_LIMITED 1u
+typedef struct tr_yuv_params {
+    uint32_t layout; /* TR_YUV_I420, TR_YUV_NV12 or TR_YUV_I444 */
+    uint32_t matrix; /* TR_YUV_BT601 or TR_YUV_BT709 */
+    uint32_t range;  /* TR_YUV_FULL or TR_YUV_LIMITED */
+    uint32_t flags;  /* 0 */
+} tr_yuv_params;
+/* The bytes of all planes of a width x height image (each 1..8192); 0, with a tr_last_error text, for an unknown layout
+ * or such a size. */
+size_t tr_yuv_bytes(uint32_t width, uint32_t height, uint32_t layout);
+/* Plane `plane` (0: Y; I420 and I444: 1 U, 2 V; NV12: 1 the pairs): the offset of its first byte, its width and height in
+ * samples and the bytes from one sample to the next of its kind (NV12's pairs: cw x ch, step 2; else 1).  TR_E_INVALID
+ * for a null pointer, an unknown layout, a size outside 1..8192 or a plane the layout has not. */
+int tr_yuv_plane(uint32_t width, uint32_t height, uint32_t layout, uint32_t plane, size_t *offset, uint32_t *w, uint32_t *h, uint32_t *step);
+/* The table above as the library holds it: out10 = Y row, U row, V row, y0.  TR_E_INVALID for an unknown matrix or range. */
+int tr_yuv_coefficients(uint32_t matrix, uint32_t range, int32_t *out10);
+/* Converts the current frame -- what the getters mean: the last render's, a frame chosen with tr_scene_select_frame, the
+ * caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like tr_scene_resize: frames held
+ * back are submitted, a pending clear is made real, k_yuv is enqueued on the scene's stream behind the renders issued so
+ * far (no depth is read, so a depth left on the chip stays there), a later render is ordered behind it, the result is
+ * there after tr_scene_sync.  The scene's passes issued so far count as handed on.  A 128 x 16 tile whose colour
+ * fast-clear flag is up is not loaded: its Y is y0 and its chroma 128; where an odd H puts the two rows of a chroma
+ * sample into two tiles, the flagged one counts as zeros and is still not read.
+ * out: tr_yuv_bytes bytes of device memory at ANY address, or memory from tr_host_alloc (the kernel stores through its
+ * mapped address; the buffer's sparse read-back record lapses); every byte of it is written on every call.  The planes
+ * are no frame of the scene: there is no in-place form and out == NULL is refused.
+ * A scene that is logically cleared (tr_scene_clear and nothing rendered since) gives the planes of black by fills
+ * (hipMemsetAsync, no kernel).
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene, params
+ * or out, flags != 0, an unknown layout, matrix or range, ordinary host memory as `out`, a pinned buffer that is too
+ * small, an `out` that overlaps a frame buffer of the scene, and a BAND scene (tr_options.band_row0/1 set): a chroma
+ * sample's pair of rows straddles a band's border. */
+int tr_scene_to_yuv(tr_scene *s, const tr_yuv_params *p, void *out);
+/* The same for ANY tightly packed rgb8 image of width x height pixels (each 1..8192, row 0 = top) in device memory or in
+ * memory from tr_host_alloc -- the output of tr_scene_resize, tr_scene_resolve or tr_scene_warp --, enqueued on the scene's
+ * stream behind everything issued so far.  No flags are used: every pixel is read.  Also refused: an `rgb` that is
+ * ordinary host memory or a pinned block that is too small, and an `rgb` that overlaps `out`.  Band scenes may call it. */
+int tr_scene_to_yuv_from(tr_scene *s, const void *rgb, uint32_t width, uint32_t height, const tr_yuv_params *p, void *out);
+/* The current frame's planes into any host memory (tr_yuv_bytes bytes): waits for the scene first, converts into a buffer
+ * of the library's, copies out and returns the frame's sticky status, like tr_scene_get_resized. */
+int tr_scene_get_yuv(tr_scene *s, const tr_yuv_params *p, uint8_t *planes);
+/* The rule above on the host (no GPU needed), by the very inline functions k_yuv calls.  rgb: 3 * width * height bytes,
+ * out: tr_yuv_bytes bytes, both row 0 = top; out must not be rgb.  The same parameter checks. */
+int tr_yuv_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr_yuv_params *p, uint8_t *out /* != rgb */);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -171,6 +171,13 @@ SYMBOLS = {
     "tr_scene_convolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_convolved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_convolve_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_to_yuv_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_yuv_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_yuv_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "tr_yuv_plane": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_yuv_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

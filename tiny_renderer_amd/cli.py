@@ -27,7 +27,13 @@ def main(argv=None):
                          "camera turns at CAMERA_SPEED = 3 rad/s as if a key were held, `FPS --- n` every second")
     ap.add_argument("--no-readback", action="store_true",
                     help="with --seconds: leave the frames on the GPU (the reference hands every frame to its window)")
-    ap.add_argument("--out", default=None, help="write the last frame: .png, .tga (24-bit) or binary PPM otherwise")
+    ap.add_argument("--out", default=None, help="write the last frame: .png, .tga (24-bit) or binary PPM otherwise; NAME.y4m: write "
+                                                "EVERY frame of a --frames N run, in order, as YCbCr planes converted on the GPU (Scene.to_yuv_into; "
+                                                "after every other stage option, behind --out-size or --ssaa)")
+    ap.add_argument("--fps", type=int, default=30, metavar="N", help="the frame rate written into a .y4m file (default 30)")
+    ap.add_argument("--yuv-matrix", default="bt709", choices=("bt601", "bt709"), help="the matrix of a .y4m file (default bt709)")
+    ap.add_argument("--yuv-range", default="limited", choices=("full", "limited"), help="the range of a .y4m file (default limited)")
+    ap.add_argument("--yuv-layout", default="i420", choices=("i420", "i444"), help="the planes of a .y4m file: i420 (C420jpeg; default) or i444 (C444)")
     ap.add_argument("--view", choices=("frame", "z", "shadow"), default="frame")  # app.rs:213-215
     ap.add_argument("--device", type=int, default=-1)
     ap.add_argument("--synthetic", action="store_true", help="procedural scene instead of -p")
@@ -344,6 +350,14 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         args.resize = (w, h, args.resize_filter)
+    args.y4m = bool(args.out) and args.out.lower().endswith(".y4m")
+    if args.y4m:
+        if args.gpus > 1 or args.view != "frame" or args.seconds > 0:
+            ap.error("--out NAME.y4m converts the colour frames of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        if args.shutter or args.shared_shadows:
+            ap.error("--out NAME.y4m writes every frame of the run: not with --shutter (one average of the run's last frames) or --shared-shadows (one frame)")
+        if args.fps < 1:
+            ap.error("--fps must be >= 1")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     if args.instances < 1:
@@ -529,6 +543,8 @@ def _run(args, T, scene, sharded, rank, say):
     angles = [np.float32(args.camera_angle + (2.0 * np.pi * f / args.frames if args.frames > 1 else 0.0))
               for f in range(args.frames)]
     la = np.float32(args.light_angle)
+    if args.y4m:
+        return _run_y4m(args, T, scene, angles, la, say, t0)
     if args.frames > 1 or args.shutter:
         # many frames: the library's throughput path (the same frames, several per kernel launch; with --gpus every
         # rank renders its band of a group, and the bands are exchanged frame by frame)
@@ -572,6 +588,17 @@ def _run(args, T, scene, sharded, rank, say):
         scene.composite(other)
     if args.shutter:
         scene.accumulate_in_place(args.shutter)
+    _post(args, T, scene, say)
+    img = _view(scene, args.view, args.ssaa, args.resize)
+    dt = time.perf_counter() - t0
+    say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238
+    if args.out and rank == 0:
+        write_frame(T, args.out, img)
+    return 0
+
+
+def _post(args, T, scene, say):
+    """The stage options on the scene's current frame, in their order (after --with and --shutter)."""
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
     if args.dof_autofocus:
@@ -607,11 +634,58 @@ def _run(args, T, scene, sharded, rank, say):
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
             % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
                T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
-    img = _view(scene, args.view, args.ssaa, args.resize)
+
+
+def _run_y4m(args, T, scene, angles, la, say, t0):
+    """--out NAME.y4m: every frame of the run rendered, sent through the stage options and converted on the GPU into one
+    of TWO page-locked blocks, so that frame f + 1 is rendered and converted while frame f is written to the file.  With
+    --out-size or --ssaa the resized or resolved image stays on the device and is converted from there."""
+    light = [float(np.sin(la)), 0.0, float(np.cos(la))]
+    w, h = scene.width, scene.height
+    small = None
+    if args.resize is not None or args.ssaa > 1:
+        import torch
+        w, h = (args.resize[0], args.resize[1]) if args.resize is not None else (scene.width // args.ssaa, scene.height // args.ssaa)
+        small = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    blocks = [scene.pinned_yuv(args.yuv_layout, w, h) for _ in range(2)]
+    yuv = dict(layout=args.yuv_layout, matrix=args.yuv_matrix, range=args.yuv_range)
+    weights = morph_wave(args.frames, args.morph_weight) if args.morph_to else None
+    bends = bend_palette(T, args.bend * np.arange(1, args.frames + 1) / args.frames) if args.bend is not None else None
+    with T.Y4MWriter(args.out, w, h, args.fps, args.yuv_layout, args.yuv_range) as out:
+        for f, ca in enumerate(angles):
+            p = np.zeros((1, 12), np.float32)
+            p[0, 0:3], p[0, 3:6], p[0, 6:9], p[0, 9:12] = light, [float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0]
+            if weights is not None:
+                scene.render_frames(p, morph_weights=weights[f:f + 1])
+            elif bends is not None:
+                scene.render_frames(p, bone_palettes=bends[f:f + 1])
+            else:
+                scene.render_frames(p)
+            if args.with_scene is not None:
+                other = args.with_scene
+                other.clear()
+                other.set_light_direction(light)
+                other.set_camera([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0, 0, 0], [0, 1, 0])
+                other.render()
+                scene.composite(other)
+            _post(args, T, scene, say)
+            block = blocks[f % 2]
+            if small is None:
+                scene.to_yuv_into(block, **yuv)
+            else:
+                if args.resize is not None:
+                    scene.resize_into(small, *args.resize)
+                else:
+                    scene.resolve_into(args.ssaa, small.data_ptr())
+                scene.to_yuv_from(small, target=block, **yuv)
+            scene.flush()
+            if f > 0:   # (frame f is on its way: write frame f - 1, whose block the sync below has made whole)
+                out.write(blocks[(f - 1) % 2])
+            scene.sync()
+        out.write(blocks[(len(angles) - 1) % 2])
     dt = time.perf_counter() - t0
-    say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))              # app.rs:238
-    if args.out and rank == 0:
-        write_frame(T, args.out, img)
+    say("FPS --- %d" % int(args.frames / dt if dt > 0 else 0))
+    print("wrote %s (%d frames)" % (args.out, len(angles)))
     return 0
 
 

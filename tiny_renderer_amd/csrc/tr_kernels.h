@@ -21,6 +21,7 @@
 #include "tr_skin.h"
 #include "tr_stats.h"
 #include "tr_warp.h"
+#include "tr_yuv.h"
 #include "tr_types.h"
 
 namespace tr {
@@ -122,6 +123,10 @@ int launch_resize(const ResizeArgs &a, hipStream_t st);
 // frame only (no band); no depth is read.  a.out_clean: null, or -- the output has the frame's size and its height is a
 // multiple of 16 -- where each workgroup writes the flag of its tile of a.out: a tile flagged there is zeros in every byte.
 int launch_warp(const WarpArgs &a, hipStream_t st);
+// YUV output: the rgb8 image a.src (a.width x a.height, each 1..8192) converted to the planes of a.rule.layout in a.out
+// (yuv_bytes, apart from it, any address) by the rule of tr_yuv.h: k_yuv.  a.clean: null, or the image's colour
+// fast-clear flags over its whole 128 x 16 tile grid (a.ntx a row).  No depth is read.
+int launch_yuv(const YuvArgs &a, hipStream_t st);
 // Convolve: a.fb filtered through the integer kernel a.rule into a.out (which does not overlap it) by the rule of
 // tr_convolve.h, through the scene's colour fast-clear flags: k_convolve.  The whole frame only (no band); no depth is
 // read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile

@@ -3747,6 +3747,162 @@ __global__ __launch_bounds__(WARP_THREADS) void k_warp(WarpArgs a)
     }
 }
 
+// YUV output (tr_scene_to_yuv, tr_scene_to_yuv_from): an rgb8 image converted to YCbCr planes by the rule of tr_yuv.h.
+// Pointwise and memory-bound: 3 bytes a pixel in, 1.5 (4:2:0) or 3 (4:4:4) out, no LDS, no barrier, no atomics.  One
+// workgroup per block of 128 columns x 16 BUFFER rows counted from the TOP (rows 16 by .. 16 by + 15), not per tile of the
+// flag grid, which counts from the bottom: a chroma sample's two rows 2j and 2j + 1 then always lie in one workgroup, at
+// every height.  One workgroup a block and no persistent walk: a workgroup has no table to stage and no setup to spread
+// over several tiles (k_grade's reason), so a walk would only add its loop.
+//   * unit: a lane converts N columns x 2 rows, N / 2 chroma samples of 4:2:0: N = 8 where width % 8 == 0 and src and out
+//     are 8-byte aligned (three 8-byte loads a row; 8-byte stores of Y, of NV12's pairs and of I444's chroma, 4-byte
+//     stores of I420's chroma), N = 4 where width % 4 == 0 and both are 4-byte aligned (three 4-byte loads a row; 4-byte
+//     stores, 2-byte stores of I420's chroma), N = 2 with byte loads and byte stores otherwise -- any width, any address:
+//     the chroma planes begin at out + W H, odd whenever W H is.  In the two wide forms every plane's offset and row
+//     length is a multiple of the store's size (W H, cw = W / 2 and cw ch are); a unit lies inside the image or outside.
+//   * flags: a workgroup's columns are those of ONE column of flag tiles; its rows lie in at most TWO tile rows, ty_top =
+//     (H - 1 - 16 by) / 16 and the one below it, whose border is buffer row H - 16 ty_top.  With an even H that border is
+//     even and a chroma pair (2j, 2j + 1) has both rows in one tile.  With an odd H EVERY border falls between the two
+//     rows of a pair: row 2j is the last of the upper tile, 2j + 1 the first of the lower.  So the flag is taken per ROW:
+//     a row behind a raised flag is not loaded and counts as zeros -- its Y is y0, and it adds nothing to the pair's sums.
+//     Both rows flagged: Y = y0 and chroma 128 without a load.  clean == null: every row is read.
+//   * odd edges (N = 2 only for columns, every N for rows): column min(x + 1, W - 1) and row min(y + 1, H - 1) are counted
+//     twice from the values already loaded; their Y is not stored.
+// Every byte of `out` is written, none outside.  No depth is read.
+constexpr int YUV_BW = 128, YUV_BH = 16;
+
+template <int N>
+__device__ __forceinline__ void yuv_load_row(const uint8_t *p, bool second_column, uint32_t (&w)[6])
+{
+    if (N == 8) {
+        const uint2 *q = reinterpret_cast<const uint2 *>(p);
+        const uint2 a = q[0], b = q[1], c = q[2];
+        w[0] = a.x, w[1] = a.y, w[2] = b.x, w[3] = b.y, w[4] = c.x, w[5] = c.y;
+    } else if (N == 4) {
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+        w[0] = q[0], w[1] = q[1], w[2] = q[2];
+    } else {
+        const uint8_t *s = second_column ? p + 3 : p;  // (the last column twice at an odd width)
+        w[0] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)s[0] << 24);
+        w[1] = (uint32_t)s[1] | ((uint32_t)s[2] << 8);
+    }
+}
+
+// Byte k of a row's words (k is a constant after unrolling).
+__device__ __forceinline__ int32_t yuv_byte(const uint32_t (&w)[6], int k) { return (int32_t)((w[k >> 2] >> (8 * (k & 3))) & 0xFFu); }
+
+// n bytes (n = 8, 4, 2: one aligned store; the caller has seen to the alignment) from lo and hi.
+template <int BYTES>
+__device__ __forceinline__ void yuv_store(uint8_t *p, uint32_t lo, uint32_t hi)
+{
+    if (BYTES == 8) *reinterpret_cast<uint2 *>(p) = make_uint2(lo, hi);
+    else if (BYTES == 4) *reinterpret_cast<uint32_t *>(p) = lo;
+    else *reinterpret_cast<uint16_t *>(p) = (uint16_t)lo;
+}
+
+template <int N, uint32_t LAYOUT>
+__global__ __launch_bounds__(256) void k_yuv(YuvArgs a)
+{
+    static_assert(N == 8 || N == 4 || N == 2, "a unit is 8, 4 or 2 columns");
+    constexpr int UNITS_X = YUV_BW / N, UNITS = UNITS_X * (YUV_BH / 2);
+    const int32_t W = (int32_t)a.width, H = (int32_t)a.height;
+    const int32_t cw = (W + 1) / 2, ch = (H + 1) / 2;
+    const size_t wh = (size_t)W * (size_t)H;
+    const YuvRule k = a.rule;
+    // the two flags this workgroup's rows can lie behind (workgroup-uniform)
+    const int32_t ty_top = (H - 1 - (int32_t)blockIdx.y * YUV_BH) / TILE_H;
+    bool up_top = false, up_low = false;
+    if (a.clean != nullptr) {
+        up_top = a.clean[(size_t)ty_top * a.ntx + blockIdx.x] != 0u;
+        up_low = ty_top >= 1 ? a.clean[(size_t)(ty_top - 1) * a.ntx + blockIdx.x] != 0u : up_top;
+    }
+    for (int32_t u = (int32_t)threadIdx.x; u < UNITS; u += (int32_t)blockDim.x) {
+        const int32_t x = (int32_t)blockIdx.x * YUV_BW + (u % UNITS_X) * N;
+        const int32_t y0 = (int32_t)blockIdx.y * YUV_BH + (u / UNITS_X) * 2;
+        if (x >= W || y0 >= H) continue;
+        const bool row1 = y0 + 1 < H, col1 = x + 1 < W;  // (col1 matters where N == 2)
+        const int32_t y1 = row1 ? y0 + 1 : y0;
+        const bool z0 = (H - 1 - y0) / TILE_H == ty_top ? up_top : up_low;
+        const bool z1 = (H - 1 - y1) / TILE_H == ty_top ? up_top : up_low;
+        uint32_t w0[6] = { 0u, 0u, 0u, 0u, 0u, 0u }, w1[6] = { 0u, 0u, 0u, 0u, 0u, 0u };
+        if (!z0) yuv_load_row<N>(a.src + ((size_t)y0 * (size_t)W + (size_t)x) * 3u, col1, w0);
+        if (row1) {
+            if (!z1) yuv_load_row<N>(a.src + ((size_t)y1 * (size_t)W + (size_t)x) * 3u, col1, w1);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 6; i++) w1[i] = w0[i];  // (the last row twice at an odd height)
+        }
+        // Y, and I444's chroma, a byte a pixel: packed four to a word
+        uint32_t py[2][2] = { { 0u, 0u }, { 0u, 0u } }, pu[2][2] = { { 0u, 0u }, { 0u, 0u } }, pv[2][2] = { { 0u, 0u }, { 0u, 0u } };
+        uint32_t c_lo = 0u, c_hi = 0u, d_lo = 0u;  // 4:2:0: NV12's pairs in c_lo, c_hi; I420's U in c_lo, V in d_lo
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const uint32_t(&w)[6] = r ? w1 : w0;
+                const int32_t R = yuv_byte(w, 3 * i), G = yuv_byte(w, 3 * i + 1), B = yuv_byte(w, 3 * i + 2);
+                py[r][i >> 2] |= yuv_luma(k, R, G, B) << (8 * (i & 3));
+                if (LAYOUT == YUV_I444) {
+                    pu[r][i >> 2] |= yuv_chroma1(k.u, R, G, B) << (8 * (i & 3));
+                    pv[r][i >> 2] |= yuv_chroma1(k.v, R, G, B) << (8 * (i & 3));
+                }
+            }
+            if (LAYOUT != YUV_I444 && (i & 1)) {
+                int32_t s[3];
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+                    s[c] = yuv_byte(w0, 3 * (i - 1) + c) + yuv_byte(w0, 3 * i + c) + yuv_byte(w1, 3 * (i - 1) + c) + yuv_byte(w1, 3 * i + c);
+                const uint32_t U = yuv_chroma4(k.u, s[0], s[1], s[2]), V = yuv_chroma4(k.v, s[0], s[1], s[2]);
+                const int j = i >> 1;  // the unit's chroma sample
+                if (LAYOUT == YUV_NV12) {
+                    const uint32_t pair = (U | (V << 8)) << (16 * (j & 1));
+                    if (j < 2) c_lo |= pair;
+                    else c_hi |= pair;
+                } else {
+                    c_lo |= U << (8 * j), d_lo |= V << (8 * j);
+                }
+            }
+        }
+        // stores
+        uint8_t *oy0 = a.out + (size_t)y0 * (size_t)W + (size_t)x, *oy1 = a.out + (size_t)y1 * (size_t)W + (size_t)x;
+        if (N == 2) {
+            oy0[0] = (uint8_t)py[0][0];
+            if (col1) oy0[1] = (uint8_t)(py[0][0] >> 8);
+            if (row1) {
+                oy1[0] = (uint8_t)py[1][0];
+                if (col1) oy1[1] = (uint8_t)(py[1][0] >> 8);
+            }
+        } else {
+            yuv_store<N>(oy0, py[0][0], py[0][1]);
+            if (row1) yuv_store<N>(oy1, py[1][0], py[1][1]);
+        }
+        if (LAYOUT == YUV_I444) {
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                if (r == 1 && !row1) break;
+                uint8_t *ou = (r ? oy1 : oy0) + wh, *ov = ou + wh;
+                if (N == 2) {
+                    ou[0] = (uint8_t)pu[r][0], ov[0] = (uint8_t)pv[r][0];
+                    if (col1) ou[1] = (uint8_t)(pu[r][0] >> 8), ov[1] = (uint8_t)(pv[r][0] >> 8);
+                } else {
+                    yuv_store<N>(ou, pu[r][0], pu[r][1]);
+                    yuv_store<N>(ov, pv[r][0], pv[r][1]);
+                }
+            }
+        } else {
+            const size_t at = (size_t)(y0 >> 1) * (size_t)cw + (size_t)(x >> 1);  // (y0 / 2 < ch, x / 2 + N / 2 <= cw)
+            if (LAYOUT == YUV_NV12) {
+                uint8_t *oc = a.out + wh + 2u * at;
+                if (N == 2) oc[0] = (uint8_t)c_lo, oc[1] = (uint8_t)(c_lo >> 8);
+                else yuv_store<N>(oc, c_lo, c_hi);
+            } else {
+                uint8_t *ou = a.out + wh + at, *ov = ou + (size_t)cw * (size_t)ch;
+                if (N == 2) ou[0] = (uint8_t)c_lo, ov[0] = (uint8_t)d_lo;
+                else yuv_store<N / 2>(ou, c_lo, 0u), yuv_store<N / 2>(ov, d_lo, 0u);
+            }
+        }
+    }
+}
+
 // Frame statistics (tr_scene_frame_stats): the frame reduced to one record; tr_stats.h has the rule and the form of a
 // partial record.  The project's one reduction, in two launches:
 //   k_stats -- PERSISTENT workgroups of 1024 lanes, at most one a CU and at most one a tile (the launcher; the diagnostic
@@ -4867,6 +5023,34 @@ int launch_resize(const ResizeArgs &a, hipStream_t st)
     if (a.shape == 0) launch_resize_shape<0>(a, wide, st);
     else if (a.shape == 1) launch_resize_shape<1>(a, wide, st);
     else launch_resize_shape<2>(a, wide, st);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+template <uint32_t LAYOUT>
+static void launch_yuv_layout(const YuvArgs &a, int n, hipStream_t st)
+{
+    const dim3 grid((a.width + YUV_BW - 1) / YUV_BW, (a.height + YUV_BH - 1) / YUV_BH);
+    if (n == 8) hipLaunchKernelGGL((k_yuv<8, LAYOUT>), grid, dim3(128), 0, st, a);
+    else if (n == 4) hipLaunchKernelGGL((k_yuv<4, LAYOUT>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_yuv<2, LAYOUT>), grid, dim3(256), 0, st, a);
+}
+
+int launch_yuv(const YuvArgs &a, hipStream_t st)
+{
+    if (!a.src || !a.out) return (int)hipErrorInvalidValue;
+    if (a.width < 1u || a.width > YUV_MAX_SIDE || a.height < 1u || a.height > YUV_MAX_SIDE || !yuv_layout_ok(a.rule.layout)) return (int)hipErrorInvalidValue;
+    // flags are indexed by the whole image's tile grid
+    if (a.clean && a.ntx != (a.width + TILE_W - 1) / TILE_W) return (int)hipErrorInvalidValue;
+    // `out` is apart from the source
+    const size_t bytes = (size_t)a.width * a.height * 3u, out_bytes = yuv_bytes(a.width, a.height, a.rule.layout);
+    if ((const uint8_t *)a.out < a.src + bytes && a.src < (const uint8_t *)a.out + out_bytes) return (int)hipErrorInvalidValue;
+    // the unit: 8 or 4 columns where every load and store of that form is aligned, else 2 columns by bytes
+    const uintptr_t both = (uintptr_t)a.src | (uintptr_t)a.out;
+    const int n = a.width % 8u == 0u && both % 8u == 0u ? 8 : a.width % 4u == 0u && both % 4u == 0u ? 4 : 2;
+    if (a.rule.layout == YUV_I420) launch_yuv_layout<YUV_I420>(a, n, st);
+    else if (a.rule.layout == YUV_NV12) launch_yuv_layout<YUV_NV12>(a, n, st);
+    else launch_yuv_layout<YUV_I444>(a, n, st);
     TR_LAUNCH_CHECK();
     return 0;
 }

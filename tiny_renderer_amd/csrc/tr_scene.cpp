@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2832,10 +2832,10 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize, to_yuv) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
-//   for a non-null `out`, then refuse_overlap (resolve and resize have none); the cleared-scene shortcut where the stage has one --
+//   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
 //   cleared_out_of_place, while in place a cleared frame is its own result and NOTHING happens, handed_on included; the
 //   enqueue_* into the target, into the frame itself, or through the scratch frame (in_place_via_scratch); handed_on.
 //   tr_scene_get_<stage>: the same checks, then get_stage.
@@ -5353,6 +5353,207 @@ int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_convolve_host: null argument");
     if (out == rgb) return tr::fail(TR_E_INVALID, "tr_convolve_host: out is rgb (the rule reads neighbours: not in place)");
     convolve_host(width, height, rgb, out, convolve_rule(p));
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_YUV_I420 == YUV_I420 && TR_YUV_NV12 == YUV_NV12 && TR_YUV_I444 == YUV_I444 && TR_YUV_BT601 == YUV_BT601 &&
+                  TR_YUV_BT709 == YUV_BT709 && TR_YUV_FULL == YUV_FULL && TR_YUV_LIMITED == YUV_LIMITED && sizeof(tr_yuv_params) == 16,
+              "tr_yuv.h restates the header");
+
+// tr_yuv_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_yuv_params(const tr_yuv_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->flags != 0u) return tr::fail(TR_E_INVALID, w + ": flags must be 0");
+    if (!yuv_layout_ok(p->layout)) return tr::fail(TR_E_INVALID, w + ": layout must be TR_YUV_I420, TR_YUV_NV12 or TR_YUV_I444");
+    if (p->matrix != TR_YUV_BT601 && p->matrix != TR_YUV_BT709) return tr::fail(TR_E_INVALID, w + ": matrix must be TR_YUV_BT601 or TR_YUV_BT709");
+    if (p->range != TR_YUV_FULL && p->range != TR_YUV_LIMITED) return tr::fail(TR_E_INVALID, w + ": range must be TR_YUV_FULL or TR_YUV_LIMITED");
+    return TR_OK;
+}
+
+int check_yuv_size(uint32_t width, uint32_t height, const char *who)
+{
+    if (width < 1u || width > YUV_MAX_SIDE || height < 1u || height > YUV_MAX_SIDE)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": width and height must be 1..8192");
+    return TR_OK;
+}
+
+int check_yuv_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be converted: "
+                                                         "a chroma sample's pair of rows straddles a band's border, and its planes are not the frame's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+YuvRule yuv_rule(const tr_yuv_params *p)
+{
+    YuvRule k = kYuvTables[p->matrix][p->range];
+    k.layout = p->layout;
+    return k;
+}
+
+// The planes of black -- Y = y0, chroma 128 -- into `out_device` by fills behind everything issued so far: no kernel.
+int fill_yuv_black(tr_scene *s, uint32_t width, uint32_t height, const tr_yuv_params *p, uint8_t *out_device)
+{
+    const size_t wh = (size_t)width * height, all = yuv_bytes(width, height, p->layout);
+    HIP_TRY(hipMemsetAsync(out_device, kYuvTables[p->matrix][p->range].y0, wh, s->stream));
+    HIP_TRY(hipMemsetAsync(out_device + wh, 128, all - wh, s->stream));
+    s->quiescent = false;
+    return TR_OK;
+}
+
+// Enqueues the conversion of src (width x height, with its flags or null) into `out_device` on the scene's stream.
+int launch_yuv_on(tr_scene *s, const uint8_t *src, const uint32_t *clean, uint32_t width, uint32_t height, const tr_yuv_params *p, uint8_t *out_device)
+{
+    YuvArgs a = {};
+    a.src = src;
+    a.clean = clean;
+    a.out = out_device;
+    a.width = width;
+    a.height = height;
+    a.ntx = (width + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W;
+    a.rule = yuv_rule(p);
+    {
+        Timed t(s, K_YUV);
+        int rc = launch_yuv(a, s->stream);
+        if (rc) return launch_status(rc, "k_yuv");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+// Enqueues the current frame's planes into `out_device` (which is no frame of the scene) behind everything issued so
+// far; a logically cleared scene gives the black planes by fills.  No depth is read: a depth left on the chip stays there.
+int enqueue_yuv(tr_scene *s, const tr_yuv_params *p, uint8_t *out_device)
+{
+    if (s->z_fb_cleared) {
+        int st = submit_pending(s);
+        return st != TR_OK ? st : fill_yuv_black(s, s->width, s->height, p, out_device);
+    }
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st != TR_OK) return st;
+    return launch_yuv_on(s, s->d_fb, s->d_fbclean, s->width, s->height, p, out_device);
+}
+
+}  // namespace
+
+int tr_scene_to_yuv(tr_scene *s, const tr_yuv_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv: null scene");
+    int st = check_yuv_params(p, "tr_scene_to_yuv");
+    if (st == TR_OK) st = check_yuv_size(s->width, s->height, "tr_scene_to_yuv");
+    if (st == TR_OK) st = check_yuv_scene(s, "tr_scene_to_yuv");
+    if (st != TR_OK) return st;
+    if (!out) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv: out == NULL (the planes are no frame of the scene: there is no in-place form)");
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    const size_t bytes = yuv_bytes(s->width, s->height, p->layout);
+    st = classify_out(out, bytes, "tr_scene_to_yuv", "tr_scene_get_yuv", "planes", &target);
+    if (st != TR_OK) return st;
+    if (refuse_overlap(s, target, frame_bytes(s), "tr_scene_to_yuv", "converts", 0u, bytes) != TR_OK)
+        return tr::fail(TR_E_INVALID, "tr_scene_to_yuv: `out` overlaps a frame buffer of the scene (there is no in-place form)");
+    if ((st = enqueue_yuv(s, p, (uint8_t *)target)) != TR_OK) return st;
+    handed_on(s);
+    return TR_OK;
+}
+
+int tr_scene_to_yuv_from(tr_scene *s, const void *rgb, uint32_t width, uint32_t height, const tr_yuv_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv_from: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv_from: null argument");
+    int st = check_yuv_params(p, "tr_scene_to_yuv_from");
+    if (st == TR_OK) st = check_yuv_size(width, height, "tr_scene_to_yuv_from");
+    if (st != TR_OK) return st;
+    if (s->broken) return unusable();
+    if (!out) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv_from: out == NULL (there is no in-place form)");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t in_bytes = (size_t)width * height * 3u, bytes = yuv_bytes(width, height, p->layout);
+    const void *source = nullptr;
+    {
+        // memory from tr_host_alloc: the kernel loads through its mapped address; else it must be device memory
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(const_cast<void *>(rgb));
+        if (it != g_host_allocs.end()) {
+            if (it->second.bytes < in_bytes) return tr::fail(TR_E_INVALID, "tr_scene_to_yuv_from: the host buffer `rgb` is smaller than the image");
+            source = it->second.device;
+        }
+    }
+    if (!source) {
+        const char *text = "tr_scene_to_yuv_from: `rgb` is neither device memory nor from tr_host_alloc (tr_yuv_host takes any host memory)";
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, rgb) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, text);
+        }
+        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
+        source = rgb;
+    }
+    void *target = nullptr;
+    st = classify_out(out, bytes, "tr_scene_to_yuv_from", "tr_yuv_host", "planes", &target);
+    if (st != TR_OK) return st;
+    if ((const uint8_t *)target < (const uint8_t *)source + in_bytes && (const uint8_t *)source < (const uint8_t *)target + bytes)
+        return tr::fail(TR_E_INVALID, "tr_scene_to_yuv_from: `rgb` overlaps `out` (there is no in-place form)");
+    // behind everything issued so far, held-back frames included: the image may be a stage's output of this scene
+    if ((st = submit_pending(s)) != TR_OK) return st;
+    return launch_yuv_on(s, (const uint8_t *)source, nullptr, width, height, p, (uint8_t *)target);
+}
+
+int tr_scene_get_yuv(tr_scene *s, const tr_yuv_params *p, uint8_t *planes)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_yuv: null scene");
+    if (!planes) return tr::fail(TR_E_INVALID, "tr_scene_get_yuv: null argument");
+    int st = check_yuv_params(p, "tr_scene_get_yuv");
+    if (st == TR_OK) st = check_yuv_size(s->width, s->height, "tr_scene_get_yuv");
+    if (st == TR_OK) st = check_yuv_scene(s, "tr_scene_get_yuv");
+    if (st != TR_OK) return st;
+    // (no short circuit: a cleared scene's planes are not zeros; enqueue_yuv fills them)
+    return get_stage(s, planes, yuv_bytes(s->width, s->height, p->layout), nullptr, [&](uint8_t *o) { return enqueue_yuv(s, p, o); });
+}
+
+// The rule of tr_yuv.h over a caller's array, on the host.  Needs no GPU.
+int tr_yuv_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr_yuv_params *p, uint8_t *out)
+{
+    int st = check_yuv_params(p, "tr_yuv_host");
+    if (st == TR_OK) st = check_yuv_size(width, height, "tr_yuv_host");
+    if (st != TR_OK) return st;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_yuv_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_yuv_host: out is rgb (the sizes differ: not in place)");
+    yuv_host(width, height, rgb, yuv_rule(p), out);
+    return TR_OK;
+}
+
+size_t tr_yuv_bytes(uint32_t width, uint32_t height, uint32_t layout)
+{
+    if (!yuv_layout_ok(layout) || width < 1u || width > YUV_MAX_SIDE || height < 1u || height > YUV_MAX_SIDE) {
+        (void)tr::fail(TR_E_INVALID, "tr_yuv_bytes: an unknown layout, or width and height not 1..8192");
+        return 0u;
+    }
+    return yuv_bytes(width, height, layout);
+}
+
+int tr_yuv_plane(uint32_t width, uint32_t height, uint32_t layout, uint32_t plane, size_t *offset, uint32_t *w, uint32_t *h, uint32_t *step)
+{
+    if (!offset || !w || !h || !step) return tr::fail(TR_E_INVALID, "tr_yuv_plane: null argument");
+    if (!yuv_layout_ok(layout)) return tr::fail(TR_E_INVALID, "tr_yuv_plane: layout must be TR_YUV_I420, TR_YUV_NV12 or TR_YUV_I444");
+    int st = check_yuv_size(width, height, "tr_yuv_plane");
+    if (st != TR_OK) return st;
+    if (!yuv_plane(width, height, layout, plane, offset, w, h, step)) return tr::fail(TR_E_INVALID, "tr_yuv_plane: the layout has no such plane");
+    return TR_OK;
+}
+
+int tr_yuv_coefficients(uint32_t matrix, uint32_t range, int32_t *out10)
+{
+    if (!out10) return tr::fail(TR_E_INVALID, "tr_yuv_coefficients: null argument");
+    if (matrix > TR_YUV_BT709 || range > TR_YUV_LIMITED) return tr::fail(TR_E_INVALID, "tr_yuv_coefficients: an unknown matrix or range");
+    const YuvRule &k = kYuvTables[matrix][range];
+    for (int c = 0; c < 3; c++) out10[c] = k.y[c], out10[3 + c] = k.u[c], out10[6 + c] = k.v[c];
+    out10[9] = k.y0;
     return TR_OK;
 }
 

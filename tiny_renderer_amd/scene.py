@@ -506,6 +506,130 @@ def resize_taps(filter, n_src, n_dst):
     return first, count, weights
 
 
+YUV_I420, YUV_NV12, YUV_I444, YUV_BT601, YUV_BT709, YUV_FULL, YUV_LIMITED, YUV_MAX_SIDE = 0, 1, 2, 0, 1, 0, 1, 8192   # (TR_YUV_*)
+YUV_LAYOUTS = {"i420": YUV_I420, "nv12": YUV_NV12, "i444": YUV_I444}
+YUV_MATRICES = {"bt601": YUV_BT601, "bt709": YUV_BT709}
+YUV_RANGES = {"full": YUV_FULL, "limited": YUV_LIMITED}
+
+
+class YuvParams(C.Structure):
+    """tr_yuv_params"""
+    _fields_ = [("layout", C.c_uint32), ("matrix", C.c_uint32), ("range", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def _yuv_choice(value, names, text):
+    if isinstance(value, str) and value in names:
+        return names[value]
+    if not isinstance(value, (bool, str)) and value in names.values():
+        return int(value)
+    raise ValueError(text)
+
+
+def yuv_params(layout="i420", matrix="bt709", range="limited", who="to_yuv"):
+    """tr_yuv_params: layout "i420", "nv12" or "i444", matrix "bt601" or "bt709", range "full" or "limited" (or the
+    YUV_* numbers).  ValueError, in the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    return YuvParams(_yuv_choice(layout, YUV_LAYOUTS, "%s: layout must be TR_YUV_I420, TR_YUV_NV12 or TR_YUV_I444" % who),
+                     _yuv_choice(matrix, YUV_MATRICES, "%s: matrix must be TR_YUV_BT601 or TR_YUV_BT709" % who),
+                     _yuv_choice(range, YUV_RANGES, "%s: range must be TR_YUV_FULL or TR_YUV_LIMITED" % who), 0)
+
+
+def _yuv_size(width, height, who):
+    for v in (width, height):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= YUV_MAX_SIDE:
+            raise ValueError("%s: width and height must be 1..8192" % who)
+    return int(width), int(height)
+
+
+def yuv_bytes(width, height, layout="i420"):
+    """tr_yuv_bytes: the bytes of all planes of a width x height image (each 1..8192)."""
+    w, h = _yuv_size(width, height, "tr_yuv_bytes")
+    return int(load_library().tr_yuv_bytes(w, h, yuv_params(layout, who="tr_yuv_bytes").layout))
+
+
+def yuv_planes(flat, width, height, layout="i420"):
+    """The planes of one flat uint8 array of yuv_bytes bytes, as views into it (tr_yuv_plane): (Y [H, W], U [ch, cw],
+    V [ch, cw]) for "i420", (Y [H, W], UV [ch, cw, 2]) for "nv12", (Y, U, V), each [H, W], for "i444"."""
+    w, h = _yuv_size(width, height, "tr_yuv_plane")
+    lay = yuv_params(layout, who="tr_yuv_plane").layout
+    flat = np.asarray(flat)
+    if flat.dtype != np.uint8 or flat.ndim != 1 or flat.size != yuv_bytes(w, h, lay):
+        raise ValueError("tr_yuv_plane: flat must be a uint8 array of yuv_bytes(width, height, layout) bytes")
+    planes = []
+    for k in (0, 1) if lay == YUV_NV12 else (0, 1, 2):
+        off, pw, ph, step = C.c_size_t(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(load_library().tr_yuv_plane(w, h, lay, k, C.addressof(off), C.addressof(pw), C.addressof(ph), C.addressof(step)))
+        shape = (ph.value, pw.value) if step.value == 1 else (ph.value, pw.value, step.value)
+        planes.append(flat[off.value:off.value + ph.value * pw.value * step.value].reshape(shape))
+    return tuple(planes)
+
+
+def yuv_coefficients(matrix="bt709", range="limited"):
+    """tr_yuv_coefficients: (Y row, U row, V row, y0) of a table as the library holds it, in units of 1 / 65536."""
+    p = yuv_params("i420", matrix, range, "tr_yuv_coefficients")
+    out = np.empty(10, np.int32)
+    check(load_library().tr_yuv_coefficients(p.matrix, p.range, out.ctypes.data))
+    return tuple(int(v) for v in out[0:3]), tuple(int(v) for v in out[3:6]), tuple(int(v) for v in out[6:9]), int(out[9])
+
+
+def yuv_host(rgb, layout="i420", matrix="bt709", range="limited", flat=False):
+    """tr_yuv_host: the rule of Scene.to_yuv on the host (no GPU needed).  rgb [H, W, 3] uint8 with row 0 = top
+    (get_frame_buffer).  Returns the planes as yuv_planes gives them -- views into one flat array --, or that array
+    with flat=True; leaves its argument alone."""
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("tr_yuv_host: rgb [H, W, 3]")
+    p = yuv_params(layout, matrix, range, "tr_yuv_host")
+    w, h = _yuv_size(src.shape[1], src.shape[0], "tr_yuv_host")
+    out = np.empty(yuv_bytes(w, h, p.layout), np.uint8)
+    check(load_library().tr_yuv_host(w, h, src.ctypes.data, C.addressof(p), out.ctypes.data))
+    return out if flat else yuv_planes(out, w, h, p.layout)
+
+
+class Y4MWriter:
+    """A YUV4MPEG2 file of width x height frames at `fps` frames a second (an integer, or (numerator, denominator)):
+    write(frame) appends one frame, a flat array of yuv_bytes bytes or the tuple of planes yuv_planes gives.  "i420" is
+    written as C420jpeg (the centred siting of the rule), "i444" as C444; the range goes into XCOLORRANGE=FULL or
+    LIMITED.  "nv12" is refused: the format has no interleaved chroma."""
+
+    def __init__(self, path, width, height, fps=30, layout="i420", range="limited"):
+        lay = yuv_params(layout, who="Y4MWriter").layout
+        if lay == YUV_NV12:
+            raise ValueError("Y4MWriter: YUV4MPEG2 has no NV12 (interleaved chroma): use i420 or i444")
+        rng = _yuv_choice(range, YUV_RANGES, "Y4MWriter: range must be TR_YUV_FULL or TR_YUV_LIMITED")
+        self.width, self.height = _yuv_size(width, height, "Y4MWriter")
+        num, den = (fps if isinstance(fps, (tuple, list)) else (fps, 1))
+        if isinstance(num, bool) or int(num) != num or int(den) != den or num < 1 or den < 1:
+            raise ValueError("Y4MWriter: fps must be a positive integer or a pair of them")
+        self.layout, self.frames = lay, 0
+        self.frame_bytes = yuv_bytes(self.width, self.height, lay)
+        self._f = open(path, "wb")
+        self._f.write(("YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s\n"
+                       % (self.width, self.height, int(num), int(den), "C420jpeg" if lay == YUV_I420 else "C444",
+                          "FULL" if rng == YUV_FULL else "LIMITED")).encode("ascii"))
+
+    def write(self, frame):
+        if isinstance(frame, (tuple, list)):
+            frame = np.concatenate([np.ascontiguousarray(p, np.uint8).reshape(-1) for p in frame])
+        frame = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+        if frame.size != self.frame_bytes:
+            raise ValueError("Y4MWriter: a frame is %d bytes, not %d" % (self.frame_bytes, frame.size))
+        self._f.write(b"FRAME\n")
+        self._f.write(frame.tobytes())
+        self.frames += 1
+
+    def close(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
 WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
 
@@ -1717,6 +1841,70 @@ class Scene:
         if not isinstance(params, ConvolveParams):
             raise ValueError("get_convolved: params must come from convolve_params")
         return self._image("tr_scene_get_convolved", strict, C.addressof(params))
+
+    # --- YUV output (tr_scene_to_yuv / tr_scene_to_yuv_from / tr_scene_get_yuv) ------------------------
+    def to_yuv(self, layout="i420", matrix="bt709", range="limited", strict=True):
+        """tr_scene_get_yuv: the current frame as YCbCr planes, converted on the device: the tuple yuv_planes gives (NV12's
+        second plane [ch, cw, 2]), equal to yuv_host(get_frame_buffer(), ...) in every byte.  Synchronizes."""
+        p = yuv_params(layout, matrix, range, "tr_scene_get_yuv")
+        flat = self._image("tr_scene_get_yuv", strict, C.addressof(p), out=np.empty(yuv_bytes(self.width, self.height, p.layout), np.uint8))
+        return yuv_planes(flat, self.width, self.height, p.layout)
+
+    def pinned_yuv(self, layout="i420", width=None, height=None):
+        """A page-locked flat uint8 array of yuv_bytes bytes for to_yuv_into / to_yuv_from (freed with the scene); of the
+        frame's size, or of width x height."""
+        w, h = (self.width if width is None else width), (self.height if height is None else height)
+        return self._pinned_array((yuv_bytes(w, h, layout),))
+
+    def _yuv_target(self, target, nbytes, who):
+        if target is None:
+            raise ValueError("%s: out == NULL (there is no in-place form)" % who)
+        if hasattr(target, "data_ptr"):
+            if target.numel() * target.element_size() < nbytes or not target.is_contiguous():
+                raise ValueError("%s: target must be a contiguous tensor of at least yuv_bytes bytes" % who)
+            return target.data_ptr()
+        return self._out_pointer(target, "target", "flat yuv_bytes", "pinned_yuv", nbytes)
+
+    def to_yuv_into(self, target, layout="i420", matrix="bt709", range="limited"):
+        """tr_scene_to_yuv: enqueue the conversion of the current frame behind the renders issued so far; the planes are
+        there after sync() (yuv_planes splits them).  `target`: a torch uint8 tensor on the scene's device, a device
+        address (int, any alignment) of yuv_bytes bytes, or an array from pinned_yuv; every byte of it is written.  Band
+        scenes are refused; there is no in-place form.  No depth is read."""
+        p = yuv_params(layout, matrix, range, "tr_scene_to_yuv")
+        ptr = self._yuv_target(target, yuv_bytes(self.width, self.height, p.layout), "tr_scene_to_yuv")
+        check(load_library().tr_scene_to_yuv(self._h, C.addressof(p), ptr))
+        return target
+
+    def to_yuv_from(self, image, layout="i420", matrix="bt709", range="limited", target=None, width=None, height=None):
+        """tr_scene_to_yuv_from: the planes of any tightly packed rgb8 image on the device -- what resize_into,
+        resolve_into or warp wrote --, enqueued on the scene's stream behind everything issued so far.  `image`: a
+        torch uint8 tensor [h, w, 3] on the scene's device, a page-locked [h, w, 3] array of the scene's, or a device
+        address (int) with width and height.  `target` as for to_yuv_into, and the call is asynchronous; without one
+        the call synchronizes and returns the tuple of planes."""
+        p = yuv_params(layout, matrix, range, "tr_scene_to_yuv_from")
+        if hasattr(image, "data_ptr") or isinstance(image, np.ndarray):
+            shape = tuple(image.shape)
+            contiguous = image.is_contiguous() if hasattr(image, "data_ptr") else image.flags["C_CONTIGUOUS"]
+            if len(shape) != 3 or shape[2] != 3 or not contiguous or (image.element_size() if hasattr(image, "data_ptr") else image.itemsize) != 1:
+                raise ValueError("tr_scene_to_yuv_from: image must be a contiguous [h, w, 3] uint8 tensor or page-locked array")
+            h, w = shape[0], shape[1]
+            src = image.data_ptr() if hasattr(image, "data_ptr") else image.ctypes.data
+        else:
+            w, h, src = width, height, int(image)
+        w, h = _yuv_size(w, h, "tr_scene_to_yuv_from")
+        nbytes = yuv_bytes(w, h, p.layout)
+        own = target is None
+        if own:
+            cache = self.__dict__.setdefault("_yuv_blocks", {})
+            target = cache.get(nbytes)
+            if target is None:
+                target = cache[nbytes] = self._pinned_array((nbytes,))
+        ptr = self._yuv_target(target, nbytes, "tr_scene_to_yuv_from")
+        check(load_library().tr_scene_to_yuv_from(self._h, src, w, h, C.addressof(p), ptr))
+        if not own:
+            return target
+        self.sync()
+        return yuv_planes(target.copy(), w, h, p.layout)
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
