@@ -35,6 +35,7 @@ def host(fb, **kw):
 def four_forms(s, f, before, kws):
     """Every parameter set of kws into device memory, into tr_host_alloc memory, through the getter and in place, each on
     a fresh render of the frame f was taken from.  Returns the number of pixels the host rule changes."""
+    import torch
     W, Hh = s.width, s.height
     dev, pinned = device_buffer(W * Hh * 3), s.pinned_frame()
     changed = 0
@@ -44,6 +45,7 @@ def four_forms(s, f, before, kws):
         p = params(**kw)
         drive(s)
         dev[:] = 0x5A
+        torch.cuda.synchronize()                          # (torch fills on its own stream: not behind the scene's kernel)
         s.antialias(p, out=dev.data_ptr())
         assert s.sync() == 0
         got = dev.cpu().numpy().reshape(Hh, W, 3)

@@ -41,12 +41,13 @@ def guarded(frame_bytes, extra=0):
     return buf
 
 
-def dense_scene(ms, W, Hh, kind):
+def dense_scene(ms, W, Hh, kind, table=DC.table, draws=True):
     """A scene that has drawn its model over the backdrop in a caller's guarded buffer, that buffer, and the snapshot
-    {"fb", "z"} of the frame."""
+    {"fb", "z"} of the frame.  table(W, Hh): where the model stands; draws=False: a size at which no model leaves a pixel
+    (tests/extreme_cases.py), where the frame is asserted to be the backdrop."""
     back = DC.backdrop(kind, W, Hh)
     buf = guarded(back)
-    s = scene(W, Hh, ms, DC.PIPE, DC.table(W, Hh))
+    s = scene(W, Hh, ms, DC.PIPE, table(W, Hh))
     # A new scene's z is memory nobody has written, and a clear that is still pending when the frame is rendered would
     # make the pass start from cleared COLOUR too: the backdrop would read as zeros.  So the clear is made real on the
     # scene's own buffer first (a getter does that); from here on z reads as f32::MIN, and the caller's buffer, which is
@@ -57,6 +58,9 @@ def dense_scene(ms, W, Hh, kind):
     TC.drive(s, DC.CAM, DC.LIGHT, clear=False)
     f = {"fb": s.get_frame_buffer(), "z": s.read_z_f32()}
     drawn = (bits(f["z"]) != F32_MIN_BITS)[::-1]
+    if not draws:
+        assert not drawn.any() and np.array_equal(f["fb"], back), "something was drawn, or the backdrop did not stay"
+        return s, buf, f
     assert drawn.any() and not drawn.all() and not np.array_equal(f["fb"], back), "nothing was drawn over the backdrop"
     assert np.array_equal(f["fb"][~drawn], back[~drawn]), "the backdrop did not stay where nothing was drawn"
     if kind == "noise":
@@ -74,41 +78,52 @@ def in_buffer(buf, want, off=0):
     return raw
 
 
-def sets(stage, s, f):
-    """[(label, the host rule's frame, call(out): the stage into `out` or with None in place, get(): the getter)]"""
+def default_params(stage, s, f):
+    """The stage's parameter sets of tests/dense_cases.py."""
+    W, Hh = s.width, s.height
+    if stage == "resolve":
+        assert DC.resolve_factors(W, Hh) == [2, 4]
+    return {"aa": DC.aa_sets, "bloom": lambda: DC.BLOOM_SETS, "dof": lambda: DC.dof_sets(f), "outline": DC.outline_sets,
+            "grade": lambda: DC.grade_luts(W), "ao": lambda: DC.AO_SETS, "resolve": lambda: DC.resolve_factors(W, Hh)}[stage]()
+
+
+def sets(stage, s, f, params=None, changes=True):
+    """[(label, the host rule's frame, call(out): the stage into `out` or with None in place, get(): the getter)]
+    params: the stage's parameter sets (None: those of tests/dense_cases.py); changes=False: a frame that no set of the
+    stage changes is fine."""
     import tiny_renderer_amd as T
     from tests import test_bloom as TB
-    W, Hh = s.width, s.height
+    if params is None:
+        params = default_params(stage, s, f)
     out = []
     if stage == "aa":
-        for kw in DC.aa_sets():
+        for kw in params:
             p = T.aa_params(**kw)
             out.append((kw, T.aa_host(f["fb"], p), lambda o, p=p: s.antialias(p, out=o), lambda p=p: s.get_antialiased(p)))
     elif stage == "bloom":
-        for q in DC.BLOOM_SETS:
+        for q in params:
             p = TB.P(*q)
             out.append((q, T.bloom_host(f["fb"], p), lambda o, p=p: s.bloom(p, out=o), lambda p=p: s.get_bloom(p)))
     elif stage == "dof":
-        for p in DC.dof_sets(f):
+        for p in params:
             label = (int(p.background_radius), float(p.scale))
             out.append((label, T.depth_of_field_host(f["z"], f["fb"], p), lambda o, p=p: s.depth_of_field(p, out=o),
                         lambda p=p: s.get_depth_of_field(p)))
     elif stage == "outline":
-        for kw in DC.outline_sets():
+        for kw in params:
             p = T.outline_params(**kw)
             out.append((kw, T.outline_host(f["z"], f["fb"], p), lambda o, p=p: s.outline(p, out=o), lambda p=p: s.get_outlined(p)))
     elif stage == "grade":
-        for lut in DC.grade_luts(W):
+        for lut in params:
             out.append((lut.shape[0], T.grade_host(f["fb"], lut), lambda o, lut=lut: (s.set_lut(lut), s.grade(out=o)),
                         lambda lut=lut: (s.set_lut(lut), s.get_graded())[1]))
     elif stage == "ao":
-        for kw in DC.AO_SETS:
+        for kw in params:
             out.append((kw, T.ambient_occlusion_host(f["z"], f["fb"], **kw), lambda o, kw=kw: s.ambient_occlusion(**kw), None))
     elif stage == "resolve":
-        assert DC.resolve_factors(W, Hh) == [2, 4]
-        for k in DC.resolve_factors(W, Hh):
+        for k in params:
             out.append((k, box(f["fb"], k), lambda o, k=k: s.resolve_into(k, o), lambda k=k: s.resolve(k)))
-    assert out and any(not np.array_equal(want, f["fb"]) for _, want, _, _ in out), "every expectation is the input"
+    assert out and (not changes or any(not np.array_equal(want, f["fb"]) for _, want, _, _ in out)), "every expectation is the input"
     return out
 
 
@@ -125,12 +140,14 @@ def reaches(stage, kind, f):
 def test_out_of_place(small_synthetic, stage, W, Hh, kind):
     """Every parameter set of the stage into device memory filled with 0x5A and through the getter: the host rule in
     every byte, and the caller's frame, its guards and z as they were."""
+    import torch
     s, buf, f = dense_scene(small_synthetic, W, Hh, kind)
     reaches(stage, kind, f)
     zb = bits(f["z"])
     dev = TO.device_buffer(W * Hh * 3)
     for label, want, call, get in sets(stage, s, f):
         dev[:] = 0x5A
+        torch.cuda.synchronize()                          # (torch fills on its own stream: not behind the scene's kernel)
         call(dev.data_ptr())
         assert s.sync() == 0
         raw = dev.cpu().numpy()

@@ -63,6 +63,7 @@ def box(img, f):
 def test_outlined_frame_equals_the_host_rule_in_all_four_forms(small_synthetic, W, Hh, pipe, store_depth):
     """Radius 0, 1 and 3, creases off and on, ONLY with black and with another paper, opacity 256 and 100; into device
     memory, into tr_host_alloc memory, through the getter and in place."""
+    import torch
     s = scene(W, Hh, small_synthetic, pipe, OC.table(W, Hh), tap=True, store_depth=store_depth)
     drive(s)
     f, before = snap(s), state(s)
@@ -75,6 +76,7 @@ def test_outlined_frame_equals_the_host_rule_in_all_four_forms(small_synthetic, 
         p = params(**kw)
         drive(s)                                          # a fresh frame: depth and flags as a render leaves them
         dev[:] = 0x5A
+        torch.cuda.synchronize()                          # (torch fills on its own stream: not behind the scene's kernel)
         s.outline(p, out=dev.data_ptr())
         assert s.sync() == 0
         got = dev.cpu().numpy().reshape(Hh, W, 3)
