@@ -1182,6 +1182,88 @@ int tr_scene_get_yuv(tr_scene *s, const tr_yuv_params *p, uint8_t *planes);
  * out: tr_yuv_bytes bytes, both row 0 = top; out must not be rgb.  The same parameter checks. */
 int tr_yuv_host(uint32_t width, uint32_t height, const uint8_t *rgb, const tr_yuv_params *p, uint8_t *out /* != rgb */);
 
+/* Layers: a SECOND image blended into the scene's CURRENT frame on the device -- a backdrop under the render, a
+ * watermark, title or picture-in-picture over it, a vignette or grain (a mask multiplied or added), a cross-fade, the
+ * difference of two frames -- by one exact rule.  The frame F is W x H, row 0 = top, as tr_scene_get_frame_buffer
+ * returns it.  The layer L is width x height pixels (each 1..8192) of TR_LAYER_RGB8 (3 bytes a pixel) or TR_LAYER_RGBA8
+ * (4, alpha last), row 0 = top, rows `stride` bytes apart (0: tightly packed; else at least width * bytes per pixel).
+ * Its top-left pixel lands on frame pixel (x, y); x and y are signed, the layer may hang over any edge or miss the
+ * frame.  For a frame pixel P inside the layer's rectangle, s is the layer's pixel there and d the frame's; per channel:
+ *   coverage  a = A * opacity, A the layer's alpha byte (255 for RGB8), opacity 0..256: a is 0..65280.
+ *             TR_LAYER_KEY: a layer pixel whose rgb equals key[0..2] has a = 0 (allowed with RGBA8: the rgb is compared).
+ *             TR_LAYER_WHERE_DRAWN: a = 0 where the frame's own depth at P says nothing is drawn (bits(z) ==
+ *             bits(f32::MIN)) -- the layer tints the model only.  TR_LAYER_WHERE_UNDRAWN: a = 0 where something is
+ *             drawn -- a backdrop under the render.  The two exclude each other.
+ *   blend     b = s (TR_LAYER_NORMAL), min(255, s + d) (ADD), (s d + 127) / 255 (MULTIPLY), 255 - ((255 - s)(255 - d) +
+ *             127) / 255 (SCREEN), max(s, d) (LIGHTEN), min(s, d) (DARKEN), |s - d| (DIFFERENCE).
+ *   output    (b a + d (65280 - a) + 32640) / 65280, rounded once.
+ * A frame pixel outside the rectangle is unchanged.  It follows: opacity 0 or A = 0 leaves d; A = 255 at opacity 256
+ * gives exactly b; NORMAL with an opaque layer of the frame's size at (0, 0) copies the layer; MULTIPLY by 255 and ADD of
+ * 0 are identities; DIFFERENCE of a frame with itself is black.  ONLY COLOUR CHANGES: z, winner words and the shadow
+ * buffer stay, so a backdrop pixel is still "not drawn" to a later tr_scene_composite, tr_scene_outline, depth of field
+ * or another WHERE layer.  A pixel depends on itself and on the layer alone: the rule works in place. */
+#define TR_LAYER_NORMAL 0u
+#define TR_LAYER_ADD 1u
+#define TR_LAYER_MULTIPLY 2u
+#define TR_LAYER_SCREEN 3u
+#define TR_LAYER_LIGHTEN 4u
+#define TR_LAYER_DARKEN 5u
+#define TR_LAYER_DIFFERENCE 6u
+#define TR_LAYER_RGB8 0u
+#define TR_LAYER_RGBA8 1u
+#define TR_LAYER_KEY 0x1u
+#define TR_LAYER_WHERE_DRAWN 0x2u
+#define TR_LAYER_WHERE_UNDRAWN 0x4u
+#define TR_LAYER_MAX_SIDE 8192
+typedef struct tr_layer_params {
+    uint32_t mode;     /* TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE */
+    uint32_t format;   /* TR_LAYER_RGB8 or TR_LAYER_RGBA8 */
+    uint32_t flags;    /* TR_LAYER_KEY, and at most one of TR_LAYER_WHERE_DRAWN / TR_LAYER_WHERE_UNDRAWN */
+    uint32_t opacity;  /* 0..256 */
+    int32_t x, y;      /* where the layer's top-left pixel lands in the frame (row 0 = top) */
+    uint32_t width, height; /* the layer's size in pixels, each 1..TR_LAYER_MAX_SIDE */
+    uint32_t stride;   /* bytes from one row of the layer to the next; 0: width * bytes per pixel */
+    uint8_t key[4];    /* r, g, b of TR_LAYER_KEY; key[3] is not looked at */
+} tr_layer_params;
+/* Blends `image` into the current frame -- what the getters mean: the last render's, a frame chosen with
+ * tr_scene_select_frame, the caller's buffer after tr_scene_set_frame_buffer_device.  Asynchronous and ordered like
+ * tr_scene_grade: frames held back are submitted, a pending clear is made real, k_layer is enqueued on the scene's stream
+ * behind the renders issued so far, a later render is ordered behind it, the result is there after tr_scene_sync; the
+ * scene's passes issued so far count as handed on.  Depth is read only with a WHERE flag (then a depth left on the chip
+ * is made real first, as for tr_scene_outline); without one it stays where it is.
+ * image: the layer in device memory at ANY byte address, or memory from tr_host_alloc (the kernel loads through its
+ * mapped address); stride * (height - 1) + width * bytes per pixel bytes of it are read and no byte outside them.
+ * out == NULL: in place, by the kernel itself -- no scratch frame, no copy.  Only tiles the rectangle touches are
+ * visited; a 128 x 16 tile whose colour fast-clear flag is up counts as zeros without a load and, where the result can
+ * differ from zeros, is stored whole with its flag lowered (MULTIPLY and DARKEN leave it black behind its flag).  Every
+ * later consumer sees the layered frame; calling it twice blends twice.  A layer that misses the frame, or opacity 0,
+ * queues nothing.
+ * Otherwise out: 3 W H bytes of device memory or memory from tr_host_alloc, apart from every frame buffer of the scene;
+ * every byte of it is written, the blended rectangle and a copy of the rest, and the scene's frame stays as it is.  A
+ * logically cleared scene gives the layer over black.
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene, params
+ * or image; an unknown mode, format or flag; both WHERE flags; opacity > 256; width or height 0 or above 8192; a
+ * non-zero stride below the row's bytes; a BAND scene (tr_options.band_row0/1); `image` or `out` that is ordinary host
+ * memory or a pinned block that is too small; `out` overlapping a frame buffer of the scene; `image` overlapping `out`
+ * or a frame buffer of the scene. */
+int tr_scene_layer(tr_scene *s, const tr_layer_params *p, const void *image, void *out /* or NULL */);
+/* The same with src's CURRENT frame as the layer (rgb8, of src's size, which may differ from dst's): p->format must be
+ * TR_LAYER_RGB8 and p->width, p->height and p->stride 0 -- they are taken from src.  A tile of src behind a raised colour
+ * flag is taken as zeros and never loaded; a logically cleared src is a layer of zeros.  Stream ordering between the
+ * two scenes as in tr_scene_composite: the launch is behind src's work issued so far, a later render of src behind the
+ * launch, and both scenes' passes count as handed on.  src's frame, depth and flags are only read.  Also refused:
+ * src == dst, scenes on different devices, a band scene on either side, a src wider or higher than 8192, an `out` that
+ * overlaps a frame buffer of src. */
+int tr_scene_layer_from_scene(tr_scene *dst, const tr_layer_params *p, tr_scene *src, void *out /* or NULL */);
+/* The layered frame into any host memory (3 W H bytes): waits for the scene first, blends into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_graded.  The scene's frame stays as it is. */
+int tr_scene_get_layered(tr_scene *s, const tr_layer_params *p, const void *image, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_layer calls.  rgb and out: 3 * width * height
+ * bytes, row 0 = top; out may be rgb.  z: width * height floats, index x + y * width with y UP (tr_scene_read_z_f32); NULL
+ * without a WHERE flag.  image: any host memory.  The same parameter checks; width and height are the FRAME's, at least 1. */
+int tr_layer_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z /* NULL without a WHERE flag */,
+                  const tr_layer_params *p, const uint8_t *image, uint8_t *out /* may be rgb */);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

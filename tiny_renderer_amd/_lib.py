@@ -178,6 +178,10 @@ SYMBOLS = {
     "tr_yuv_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "tr_yuv_plane": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_yuv_coefficients": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p]),
+    "tr_scene_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_layer_from_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_layered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_layer_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

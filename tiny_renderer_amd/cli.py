@@ -141,6 +141,19 @@ def main(argv=None):
                          '"0,-1,0;-1,5,-1;0,-1,0" (odd sides up to 9; black outside the picture); applied after --edges')
     ap.add_argument("--convolve-shift", type=int, default=0, metavar="N", help="with --convolve: shift the sum right by N bits, rounded (0..22)")
     ap.add_argument("--convolve-bias", type=int, default=0, metavar="N", help="with --convolve: add N afterwards (-255..255)")
+    ap.add_argument("--backdrop", default=None, metavar="FILE.tga|R,G,B[:R,G,B]",
+                    help="layer: a picture, a colour or a gradient from the top colour to the bottom one behind the model, blended "
+                         "on the GPU where nothing is drawn (Scene.layer, where=\"undrawn\"; after --with and --ao, before the "
+                         "depth-of-field and bloom options)")
+    ap.add_argument("--overlay", default=None, metavar="FILE.tga",
+                    help="layer: a picture blended over the finished frame on the GPU (Scene.layer; after the convolve options, "
+                         "before --vignette, --out-size and y4m output)")
+    ap.add_argument("--overlay-at", default="0,0", metavar="X,Y", help="with --overlay: where its top-left pixel lands (signed; default 0,0)")
+    ap.add_argument("--overlay-opacity", type=int, default=256, metavar="N", help="with --overlay: 0..256 (default 256, opaque)")
+    ap.add_argument("--overlay-mode", default="normal", choices=("normal", "add", "multiply", "screen", "lighten", "darken", "difference"),
+                    help="with --overlay: the blend (default normal)")
+    ap.add_argument("--vignette", type=int, default=None, metavar="N",
+                    help="layer: darken the picture towards its corners by up to N of 255 (layer_vignette multiplied in; after --overlay)")
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="resize: write the picture scaled to W x H (each 1..8192 and at least an eighth of the rendered side) on "
                          "the GPU (Scene.resize; applied last, after --aa, in the place of the --ssaa resolve)")
@@ -184,6 +197,30 @@ def main(argv=None):
                     raise ValueError("--gamma must be positive")
                 args.grade_lut = lut_from_function(33, lambda v: v ** (1.0 / args.gamma))
         except (OSError, ValueError) as e:
+            ap.error(str(e))
+    args.backdrop_spec = None
+    if args.overlay is None and (args.overlay_at != "0,0" or args.overlay_opacity != 256 or args.overlay_mode != "normal"):
+        ap.error("--overlay-at, --overlay-opacity and --overlay-mode go with --overlay FILE.tga")
+    if args.backdrop is not None or args.overlay is not None or args.vignette is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--backdrop, --overlay and --vignette work on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        try:
+            if args.backdrop is not None:
+                if args.backdrop.lower().endswith(".tga"):
+                    args.backdrop_spec = args.backdrop
+                else:
+                    ends = [tuple(int(v) for v in c.split(",")) for c in args.backdrop.split(":")]
+                    if not 1 <= len(ends) <= 2 or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in ends):
+                        raise ValueError("--backdrop takes FILE.tga, R,G,B or R,G,B:R,G,B with values 0..255")
+                    args.backdrop_spec = (ends[0], ends[-1])
+            if args.overlay is not None:
+                at = [int(v) for v in args.overlay_at.split(",")]
+                if len(at) != 2 or not 0 <= args.overlay_opacity <= 256:
+                    raise ValueError("--overlay-at takes X,Y and --overlay-opacity 0..256")
+                args.overlay_at = at
+            if args.vignette is not None and not 0 <= args.vignette <= 255:
+                raise ValueError("--vignette takes 0..255")
+        except ValueError as e:
             ap.error(str(e))
     args.outline_params = None
     if args.outline is None and (args.outline_depth != 4.0 or args.outline_crease is not None or args.outline_colour != "0,0,0"
@@ -601,6 +638,11 @@ def _post(args, T, scene, say):
     """The stage options on the scene's current frame, in their order (after --with and --shutter)."""
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
+    if args.backdrop_spec is not None:
+        # in place, where nothing is drawn: depth of field, bloom and everything later see the backdrop
+        spec = args.backdrop_spec
+        back = _pinned_layer(scene, "backdrop", lambda: T.load_tga(spec) if isinstance(spec, str) else T.layer_gradient(scene.width, scene.height, spec[0], spec[1]))
+        scene.layer(back, where="undrawn")
     if args.dof_autofocus:
         # the median depth of what is drawn in the central quarter; a picture with nothing there stays sharp
         w, h = scene.width, scene.height
@@ -629,11 +671,27 @@ def _post(args, T, scene, say):
         scene.warp(wp)
     for cp in args.convolves:     # in place, after the warps: --stats, --ssaa and --out-size see the filtered frame
         scene.convolve(cp)
+    if args.overlay is not None:   # in place, after the convolves: --stats, --ssaa, --out-size and y4m output see the layered frame
+        scene.layer(_pinned_layer(scene, "overlay", lambda: T.load_tga(args.overlay)), args.overlay_at[0], args.overlay_at[1], args.overlay_mode,
+                    args.overlay_opacity)
+    if args.vignette is not None:
+        scene.layer(_pinned_layer(scene, "vignette", lambda: T.layer_vignette(scene.width, scene.height, args.vignette)), mode="multiply")
     if args.stats:
         st = scene.get_frame_stats(depth=True)
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
             % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
                T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
+
+
+def _pinned_layer(scene, name, make):
+    """The layer `name` -- make() gives it, [h, w, 3 | 4] uint8 -- in a page-locked array of the scene's, which k_layer reads
+    through its mapped address; made once and kept with the scene: a y4m run blends the same layers into every frame."""
+    cache = scene.__dict__.setdefault("_cli_layers", {})
+    if name not in cache:
+        image = make()
+        cache[name] = scene.pinned_layer(image.shape[1], image.shape[0], image.shape[2])
+        cache[name][...] = image
+    return cache[name]
 
 
 def _run_y4m(args, T, scene, angles, la, say, t0):

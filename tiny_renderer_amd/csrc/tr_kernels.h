@@ -13,6 +13,7 @@
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_grade.h"
+#include "tr_layer.h"
 #include "tr_morph.h"
 #include "tr_outline.h"
 #include "tr_pack.h"
@@ -127,6 +128,12 @@ int launch_warp(const WarpArgs &a, hipStream_t st);
 // (yuv_bytes, apart from it, any address) by the rule of tr_yuv.h: k_yuv.  a.clean: null, or the image's colour
 // fast-clear flags over its whole 128 x 16 tile grid (a.ntx a row).  No depth is read.
 int launch_yuv(const YuvArgs &a, hipStream_t st);
+// Layers: a.image (a.rule's size, format and stride; from_scene: another scene's rgb8 frame behind a.src_clean /
+// a.src_all_clean) blended into a.fb at (a.rule.x, a.rule.y) by the rule of tr_layer.h, into a.out -- a.fb itself (in
+// place: only the tiles the rectangle touches are launched, none where it misses) or apart from it (every tile: the
+// rest is copied, a flagged tile as zeros): k_layer.  The whole frame only (no band); z and a.zclean are read only with
+// a WHERE flag.  a.total, a.c* and a.g* are set here.
+int launch_layer(const LayerArgs &a, bool from_scene, hipStream_t st);
 // Convolve: a.fb filtered through the integer kernel a.rule into a.out (which does not overlap it) by the rule of
 // tr_convolve.h, through the scene's colour fast-clear flags: k_convolve.  The whole frame only (no band); no depth is
 // read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile

@@ -3040,6 +3040,161 @@ __global__ __launch_bounds__(GRADE_THREADS) void k_grade(GradeArgs a)
     }
 }
 
+// Layers (tr_scene_layer, tr_scene_layer_from_scene): a second image blended into the frame, into `out`, which may BE the
+// frame (a pixel depends on itself and on the layer alone); tr_layer.h has the rule.  One workgroup of 256 lanes per
+// 128 x 16 tile, over the tiles the clipped rectangle touches -- out of place over every tile: the rest is copied.
+//   * units as in k_grade: four pixels of a row, twelve bytes, two units a lane eight rows apart.  WORDS: width % 4 == 0
+//     and fb and out 4-byte aligned (z 16-byte with a WHERE flag; the launcher checks): a unit is three aligned words;
+//     otherwise guarded bytes.  A unit the rectangle only partly covers blends its covered pixels and keeps the others;
+//   * the layer's bytes for a unit start at any byte: the aligned words that cover the unit's COVERED bytes are loaded
+//     and funnel-shifted into pixels (layer_fetch: four words for rgb8, five for an unaligned rgba8); a word that does
+//     not overlap them is never loaded, the block's first and last word are put together from bytes where they reach
+//     outside it.  FORMAT 2 is another scene's rgb8 frame behind its colour flags: a unit lies in one source tile row
+//     and at most two source tile columns, and its pixels behind a raised flag are zeros without a load;
+//   * the tile's own colour flag is workgroup-uniform (one scalar word): raised, d = 0 without a load.  In place a tile
+//     the rectangle misses is not touched; a flagged tile under MULTIPLY or DARKEN stays black behind its flag; any other
+//     flagged tile is stored whole (zeros and the blend) and lane 0 lowers the flag behind a barrier; an unflagged tile
+//     loads and stores only the units the rectangle covers;
+//   * WHERE: the tile's z flag is workgroup-uniform too.  Raised, nothing is drawn in the tile: WHERE_DRAWN takes the
+//     tile as missed, WHERE_UNDRAWN covers it without reading z; otherwise z is read per covered unit (z is indexed y
+//     up, the frame's rows top down).  It is the z flag that says "not drawn", never the colour flag;
+//   * the mode is workgroup-uniform: one scalar switch a unit around the arithmetic of its four pixels.
+// z, winner words, the shadow buffer and every flag but the one lowered are left alone.  No LDS, no atomics, no inline
+// assembly, no scratch.
+constexpr int LAYER_THREADS = 256, LAYER_UNITS = TILE_W * TILE_H / 4 / LAYER_THREADS;
+constexpr int LAYER_FROM_SCENE = 2;  // (FORMAT beside LAYER_RGB8 and LAYER_RGBA8)
+
+template <uint32_t MODE>
+__device__ __forceinline__ void layer_unit(uint32_t d[4], const uint32_t s[4], const uint32_t cov[4], uint32_t m)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if ((m >> i) & 1u) d[i] = layer_px<MODE>(s[i], d[i], cov[i]);
+}
+
+template <bool WORDS, int FORMAT, bool WHERE>
+__global__ __launch_bounds__(LAYER_THREADS) void k_layer(LayerArgs a)
+{
+    static_assert(TILE_W == 128 && LAYER_UNITS == 2 && TILE_H == 16, "32 units to a row of a tile, two rounds of eight rows");
+    constexpr int BPP = FORMAT == (int)LAYER_RGBA8 ? 4 : 3;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t tx = a.gx0 + blockIdx.x % a.gnx, ty = a.gy0 + blockIdx.x / a.gnx, t = ty * a.frame.ntx + tx;
+    const bool in_place = a.out == a.fb;
+    const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+    const uint32_t mode = a.rule.mode;
+    // does the clipped rectangle touch the tile?  (tile rows counted up, the rectangle's from the top)
+    const int32_t tx0 = (int32_t)tx * TILE_W, tx1 = min(W, tx0 + TILE_W), yu0 = (int32_t)ty * TILE_H, yu1 = min(H, yu0 + TILE_H);
+    bool hit = a.cx0 < tx1 && tx0 < a.cx1 && a.cr0 < H - yu0 && H - yu1 < a.cr1 && a.rule.opacity != 0u;
+    bool read_z = false;
+    if (WHERE) {
+        const bool z_clean = a.zclean[t] != 0u;  // (workgroup-uniform) nothing is drawn in the tile
+        if (z_clean && (a.rule.flags & LAYER_WHERE_DRAWN)) hit = false;
+        read_z = hit && !z_clean;
+    }
+    if (in_place) {
+        if (!hit) return;
+        if (clean && (mode == LAYER_MULTIPLY || mode == LAYER_DARKEN)) return;  // black stays black behind its flag
+    }
+    const bool store_all = !in_place || clean;
+    const int32_t x = tx0 + 4 * (int32_t)(threadIdx.x % 32u), row_first = yu0 + (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = min(4, W - x);  // (WORDS: 4, or the unit is outside)
+#pragma unroll
+    for (int h = 0; h < LAYER_UNITS; h++) {
+        const int32_t y = row_first + 8 * h, r = H - 1 - y;
+        if (x >= W || y >= H) continue;
+        // the unit's covered pixels: i0 .. i1 - 1
+        int32_t i0 = 0, i1 = 0;
+        if (hit && r >= a.cr0 && r < a.cr1) i0 = max(0, a.cx0 - x), i1 = min(n_px, a.cx1 - x);
+        uint32_t m = i0 < i1 ? ((1u << i1) - 1u) & ~((1u << i0) - 1u) : 0u;
+        if (!store_all && m == 0u) continue;
+        const size_t ci = ((size_t)r * (size_t)W + (size_t)x) * 3u;
+        uint32_t d[4] = { 0u, 0u, 0u, 0u };
+        if (!clean) {
+            const uint8_t *q = a.fb + ci;
+            if (WORDS) {
+                const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                d[0] = w0 & 0xFFFFFFu;
+                d[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                d[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                d[3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) d[i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+            }
+        }
+        if (m != 0u) {
+            // the layer's pixels under the unit: pixel i of the unit is column lc + i of layer row lr
+            const int32_t lc = x - a.rule.x, lr = r - a.rule.y;
+            int32_t j0 = i0, j1 = i1;  // the pixels to load: the covered ones not behind a source flag
+            if (FORMAT == LAYER_FROM_SCENE) {
+                if (a.src_all_clean != 0u) j1 = j0;
+                else if (a.src_clean != nullptr) {
+                    const uint32_t *row = a.src_clean + (size_t)(((int32_t)a.rule.height - 1 - lr) / TILE_H) * a.src_ntx;
+                    const int32_t ta = (lc + i0) / TILE_W, tb = (lc + i1 - 1) / TILE_W, ib = tb * TILE_W - lc;  // pixel ib begins tile tb
+                    const bool fa = row[ta] != 0u, fb = ta == tb ? fa : row[tb] != 0u;
+                    if (fa) j0 = ta == tb ? i1 : ib;
+                    if (fb) j1 = ta == tb ? j0 : (fa ? j0 : ib);
+                }
+            }
+            uint32_t s[4] = { 0xFF000000u, 0xFF000000u, 0xFF000000u, 0xFF000000u };
+            if (j0 < j1) {
+                const int64_t u0 = (int64_t)lr * (int64_t)a.rule.stride + (int64_t)lc * BPP;
+                layer_fetch<BPP>(a.image, a.total, u0, u0 + j0 * BPP, u0 + j1 * BPP, s);
+            }
+            if (FORMAT == LAYER_FROM_SCENE) {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < j0 || i >= j1) s[i] = 0xFF000000u;
+            }
+            uint32_t drawn = 0u;  // bit i: pixel i of the unit is drawn
+            if (WHERE && read_z) {
+                const float *zq = a.z + (size_t)y * (size_t)W + (size_t)x;
+                if (WORDS) {
+                    const float4 v = *reinterpret_cast<const float4 *>(zq);
+                    drawn = (layer_drawn(v.x) ? 1u : 0u) | (layer_drawn(v.y) ? 2u : 0u) | (layer_drawn(v.z) ? 4u : 0u) | (layer_drawn(v.w) ? 8u : 0u);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (((m >> i) & 1u) && layer_drawn(zq[i])) drawn |= 1u << i;
+                }
+            }
+            uint32_t cov[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) cov[i] = layer_coverage(a.rule, s[i], ((drawn >> i) & 1u) != 0u);
+            switch (mode) {  // (scalar)
+            case LAYER_ADD: layer_unit<LAYER_ADD>(d, s, cov, m); break;
+            case LAYER_MULTIPLY: layer_unit<LAYER_MULTIPLY>(d, s, cov, m); break;
+            case LAYER_SCREEN: layer_unit<LAYER_SCREEN>(d, s, cov, m); break;
+            case LAYER_LIGHTEN: layer_unit<LAYER_LIGHTEN>(d, s, cov, m); break;
+            case LAYER_DARKEN: layer_unit<LAYER_DARKEN>(d, s, cov, m); break;
+            case LAYER_DIFFERENCE: layer_unit<LAYER_DIFFERENCE>(d, s, cov, m); break;
+            default: layer_unit<LAYER_NORMAL>(d, s, cov, m); break;
+            }
+        }
+        uint8_t *o = a.out + ci;
+        if (WORDS) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = d[0] | (d[1] << 24);
+            ow[1] = (d[1] >> 8) | (d[2] << 16);
+            ow[2] = (d[2] >> 16) | (d[3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(d[i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((d[i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((d[i] >> 16) & 0xFFu);
+                }
+        }
+    }
+    if (in_place && clean && a.lower != nullptr) {  // (workgroup-uniform) the tile holds the blend over zeros now
+        __syncthreads();
+        if (threadIdx.x == 0u) a.lower[t] = 0u;
+    }
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -4945,6 +5100,71 @@ int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *gri
         hipLaunchKernelGGL((k_grade<false, true>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_grade<false, false>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool WORDS, int FORMAT>
+static void launch_layer_form(const LayerArgs &a, bool where, hipStream_t st)
+{
+    const dim3 grid(a.gnx * a.gny), block(LAYER_THREADS);
+    if (where)
+        hipLaunchKernelGGL((k_layer<WORDS, FORMAT, true>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((k_layer<WORDS, FORMAT, false>), grid, block, 0, st, a);
+}
+
+int launch_layer(const LayerArgs &a_in, bool from_scene, hipStream_t st)
+{
+    LayerArgs a = a_in;
+    const uint32_t W = a.frame.width, H = a.frame.height;
+    if (a.frame.ntx * a.frame.nty == 0) return 0;
+    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (the flags are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    const LayerRule &q = a.rule;
+    const uint32_t where_flags = q.flags & (LAYER_WHERE_DRAWN | LAYER_WHERE_UNDRAWN);
+    if (q.mode >= LAYER_MODES || q.format > LAYER_RGBA8 || (q.flags & ~(LAYER_KEY | LAYER_WHERE_DRAWN | LAYER_WHERE_UNDRAWN)) != 0u ||
+        where_flags == (LAYER_WHERE_DRAWN | LAYER_WHERE_UNDRAWN) || q.opacity > 256u || q.width < 1u || q.width > LAYER_MAX_SIDE ||
+        q.height < 1u || q.height > LAYER_MAX_SIDE || q.stride < q.width * layer_bpp(q.format))
+        return (int)hipErrorInvalidValue;
+    if (from_scene && (q.format != LAYER_RGB8 || (a.src_clean && a.src_ntx != (q.width + TILE_W - 1) / TILE_W))) return (int)hipErrorInvalidValue;
+    if (!from_scene && (a.src_clean || a.src_all_clean)) return (int)hipErrorInvalidValue;
+    if (where_flags != 0u && (!a.z || !a.zclean)) return (int)hipErrorInvalidValue;
+    if (!a.image && !a.src_all_clean) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only; the layer is apart from both
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    a.total = layer_block_bytes(q.width, q.height, q.stride, q.format);
+    if (a.image && a.image < (const uint8_t *)a.out + bytes && (const uint8_t *)a.out < a.image + a.total) return (int)hipErrorInvalidValue;
+    // the rectangle clipped to the frame, in 64 bits: x + width may pass 2^31
+    const int64_t cx0 = std::max<int64_t>(0, q.x), cx1 = std::min<int64_t>(W, (int64_t)q.x + q.width);
+    const int64_t cr0 = std::max<int64_t>(0, q.y), cr1 = std::min<int64_t>(H, (int64_t)q.y + q.height);
+    const bool miss = cx0 >= cx1 || cr0 >= cr1;
+    a.cx0 = miss ? 0 : (int32_t)cx0, a.cx1 = miss ? 0 : (int32_t)cx1, a.cr0 = miss ? 0 : (int32_t)cr0, a.cr1 = miss ? 0 : (int32_t)cr1;
+    if (miss) a.rule.x = a.rule.y = 0;  // (never looked at; keeps the kernel's 32-bit differences small)
+    if (a.out == a.fb) {
+        // in place: the tiles the rectangle touches (tile rows count from the bottom)
+        if (miss || q.opacity == 0u) return 0;
+        a.gx0 = (uint32_t)cx0 / TILE_W, a.gnx = (uint32_t)(cx1 - 1) / TILE_W - a.gx0 + 1u;
+        a.gy0 = (H - (uint32_t)cr1) / TILE_H, a.gny = (H - 1u - (uint32_t)cr0) / TILE_H - a.gy0 + 1u;
+    } else {
+        a.gx0 = a.gy0 = 0u, a.gnx = a.frame.ntx, a.gny = a.frame.nty;
+    }
+    // whole words: every unit of four pixels is three aligned words of either buffer, its depths one 16-byte piece
+    const bool words = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u && (where_flags == 0u || (uintptr_t)a.z % 16u == 0u);
+    const bool where = where_flags != 0u;
+#define LAYER_LAUNCH(FORMAT_)                                        \
+    {                                                                \
+        if (words) launch_layer_form<true, FORMAT_>(a, where, st);   \
+        else launch_layer_form<false, FORMAT_>(a, where, st);        \
+    }
+    if (from_scene) LAYER_LAUNCH(LAYER_FROM_SCENE)
+    else if (q.format == LAYER_RGBA8) LAYER_LAUNCH((int)LAYER_RGBA8)
+    else LAYER_LAUNCH((int)LAYER_RGB8)
+#undef LAYER_LAUNCH
     TR_LAUNCH_CHECK();
     return 0;
 }

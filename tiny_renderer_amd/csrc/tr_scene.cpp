@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2832,7 +2832,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize, to_yuv) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize, to_yuv, layer) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -5554,6 +5554,223 @@ int tr_yuv_coefficients(uint32_t matrix, uint32_t range, int32_t *out10)
     const YuvRule &k = kYuvTables[matrix][range];
     for (int c = 0; c < 3; c++) out10[c] = k.y[c], out10[3 + c] = k.u[c], out10[6 + c] = k.v[c];
     out10[9] = k.y0;
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_LAYER_NORMAL == LAYER_NORMAL && TR_LAYER_ADD == LAYER_ADD && TR_LAYER_MULTIPLY == LAYER_MULTIPLY && TR_LAYER_SCREEN == LAYER_SCREEN &&
+                  TR_LAYER_LIGHTEN == LAYER_LIGHTEN && TR_LAYER_DARKEN == LAYER_DARKEN && TR_LAYER_DIFFERENCE == LAYER_DIFFERENCE &&
+                  TR_LAYER_RGB8 == LAYER_RGB8 && TR_LAYER_RGBA8 == LAYER_RGBA8 && TR_LAYER_KEY == LAYER_KEY && TR_LAYER_WHERE_DRAWN == LAYER_WHERE_DRAWN &&
+                  TR_LAYER_WHERE_UNDRAWN == LAYER_WHERE_UNDRAWN && TR_LAYER_MAX_SIDE == LAYER_MAX_SIDE && sizeof(tr_layer_params) == 40,
+              "tr_layer.h restates the header");
+
+constexpr uint32_t kLayerWhere = TR_LAYER_WHERE_DRAWN | TR_LAYER_WHERE_UNDRAWN;
+
+// tr_layer_params as every entry point accepts them (`who` names the entry point in the error text).  from_scene: the
+// layer is another scene's frame, and its size and stride are that scene's.
+int check_layer_params(const tr_layer_params *p, bool from_scene, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->mode > TR_LAYER_DIFFERENCE) return tr::fail(TR_E_INVALID, w + ": mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE");
+    if (p->format != TR_LAYER_RGB8 && p->format != TR_LAYER_RGBA8) return tr::fail(TR_E_INVALID, w + ": format must be TR_LAYER_RGB8 or TR_LAYER_RGBA8");
+    if ((p->flags & ~(TR_LAYER_KEY | kLayerWhere)) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if ((p->flags & kLayerWhere) == kLayerWhere)
+        return tr::fail(TR_E_INVALID, w + ": TR_LAYER_WHERE_DRAWN and TR_LAYER_WHERE_UNDRAWN exclude each other");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if (from_scene) {
+        if (p->format != TR_LAYER_RGB8) return tr::fail(TR_E_INVALID, w + ": format must be TR_LAYER_RGB8 (a scene's frame is rgb8)");
+        if (p->width != 0u || p->height != 0u || p->stride != 0u)
+            return tr::fail(TR_E_INVALID, w + ": width, height and stride must be 0 (they are taken from src)");
+        return TR_OK;
+    }
+    if (p->width < 1u || p->width > LAYER_MAX_SIDE || p->height < 1u || p->height > LAYER_MAX_SIDE)
+        return tr::fail(TR_E_INVALID, w + ": width and height must be 1..8192");
+    if (p->stride != 0u && p->stride < p->width * layer_bpp(p->format))
+        return tr::fail(TR_E_INVALID, w + ": stride must be 0 or at least the bytes of a row");
+    return TR_OK;
+}
+
+int check_layer_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be layered: "
+                                                         "the layer's rows would have to be split among the ranks");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// The rule of checked parameters for a layer of width x height pixels.
+LayerRule layer_rule(const tr_layer_params *p, uint32_t width, uint32_t height)
+{
+    LayerRule r;
+    r.mode = p->mode, r.format = p->format, r.flags = p->flags, r.opacity = p->opacity;
+    r.x = p->x, r.y = p->y;
+    r.width = width, r.height = height;
+    r.stride = p->stride ? p->stride : width * layer_bpp(p->format);
+    r.key = grade_pack(p->key[0], p->key[1], p->key[2]);
+    return r;
+}
+
+// Does the layer's rectangle miss a W x H frame (or cover nothing: opacity 0)?
+bool layer_misses(const LayerRule &r, uint32_t W, uint32_t H)
+{
+    return r.opacity == 0u || r.x >= (int64_t)W || r.y >= (int64_t)H || (int64_t)r.x + r.width <= 0 || (int64_t)r.y + r.height <= 0;
+}
+
+// `image` of a layer: memory from tr_host_alloc of at least `bytes` bytes (its mapped address) or device memory.
+int classify_layer_image(const void *image, size_t bytes, const char *who, const void **source_out)
+{
+    const std::string w(who);
+    const void *source = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_host_mutex);
+        auto it = g_host_allocs.find(const_cast<void *>(image));
+        if (it != g_host_allocs.end()) {
+            if (it->second.bytes < bytes) return tr::fail(TR_E_INVALID, w + ": the host buffer `image` is smaller than the layer");
+            source = it->second.device;
+        }
+    }
+    if (!source) {
+        const std::string text = w + ": `image` is neither device memory nor from tr_host_alloc (tr_layer_host takes any host memory)";
+        hipPointerAttribute_t attr = {};
+        if (hipPointerGetAttributes(&attr, image) != hipSuccess) {
+            (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
+            return tr::fail(TR_E_INVALID, text);
+        }
+        if (attr.type != hipMemoryTypeDevice) return tr::fail(TR_E_INVALID, text);
+        source = image;
+    }
+    *source_out = source;
+    return TR_OK;
+}
+
+// Enqueues the blend of the layer `image` (r's; src: the scene whose current frame it is, or null) into `out_device`
+// (null: in place) behind everything issued so far.  A pending clear is made real: in place the kernel then runs on the
+// raised flags, out of place it writes the layer over zeros.  Depth is needed only with a WHERE flag; without one a
+// depth left on the chip stays there.
+int enqueue_layer(tr_scene *s, const LayerRule &r, const uint8_t *image, tr_scene *src, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK && (r.flags & kLayerWhere)) st = depth_in_memory(s);
+    // src's frame on its way; a logically cleared frame is a layer of zeros whatever its memory holds
+    if (st == TR_OK && src) st = submit_pending(src);
+    if (st != TR_OK) return st;
+    LayerArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    if (r.flags & kLayerWhere) a.z = s->d_z, a.zclean = s->d_zclean;
+    a.image = image;
+    if (src) {
+        a.src_clean = src->d_fbclean;
+        a.src_ntx = (src->width + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W;
+        a.src_all_clean = src->z_fb_cleared ? 1u : 0u;
+    }
+    a.frame = s->frame;
+    a.rule = r;
+    auto launch = [&] {
+        Timed t(s, K_LAYER);
+        int rc = launch_layer(a, src != nullptr, s->stream);
+        return rc ? launch_status(rc, "k_layer") : TR_OK;
+    };
+    if (src) return cross_scene_launch(s, src, launch);
+    if ((st = launch()) != TR_OK) return st;
+    s->quiescent = false;
+    return TR_OK;
+}
+
+// What tr_scene_layer and tr_scene_layer_from_scene share once the layer is known: `out`, the overlaps, the shortcuts.
+int layer_into(tr_scene *s, const LayerRule &r, const uint8_t *image, tr_scene *src, void *out, const char *who)
+{
+    void *target = nullptr;
+    int st = frame_out(s, out, who, "tr_scene_get_layered", "layers", 0u, &target);
+    if (st != TR_OK) return st;
+    const size_t image_bytes = (size_t)layer_block_bytes(r.width, r.height, r.stride, r.format);
+    if (target && (const uint8_t *)target < image + image_bytes && image < (const uint8_t *)target + frame_bytes(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + (src ? ": `out` overlaps a frame buffer of src" : ": `image` overlaps `out`"));
+    if (!src && refuse_overlap(s, image, frame_bytes(s), who, "layers", 0u, image_bytes) != TR_OK)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": `image` overlaps a frame buffer of the scene");
+    if (target && src && refuse_overlap(src, target, frame_bytes(src), who, "layers", 0u, frame_bytes(s)) != TR_OK)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": `out` overlaps a frame buffer of src");
+    if (layer_misses(r, s->width, s->height)) {
+        // nothing is blended: in place nothing happens, out of place a copy -- of black without a kernel
+        if (!target) return TR_OK;
+        if (s->z_fb_cleared) return cleared_out_of_place(s, target);
+    }
+    st = enqueue_layer(s, r, image, src, (uint8_t *)target);
+    if (st == TR_OK && !src) handed_on(s);
+    return st;
+}
+
+}  // namespace
+
+int tr_scene_layer(tr_scene *s, const tr_layer_params *p, const void *image, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_layer: null scene");
+    int st = check_layer_params(p, false, "tr_scene_layer");
+    if (st == TR_OK && !image) st = tr::fail(TR_E_INVALID, "tr_scene_layer: null argument");
+    if (st == TR_OK) st = check_layer_scene(s, "tr_scene_layer");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const LayerRule r = layer_rule(p, p->width, p->height);
+    const void *source = nullptr;
+    st = classify_layer_image(image, (size_t)layer_block_bytes(r.width, r.height, r.stride, r.format), "tr_scene_layer", &source);
+    if (st != TR_OK) return st;
+    return layer_into(s, r, (const uint8_t *)source, nullptr, out, "tr_scene_layer");
+}
+
+int tr_scene_layer_from_scene(tr_scene *dst, const tr_layer_params *p, tr_scene *src, void *out)
+{
+    if (!dst || !src) return tr::fail(TR_E_INVALID, "tr_scene_layer_from_scene: null scene");
+    int st = check_layer_params(p, true, "tr_scene_layer_from_scene");
+    if (st != TR_OK) return st;
+    if (dst == src) return tr::fail(TR_E_INVALID, "tr_scene_layer_from_scene: dst and src are the same scene");
+    if (dst->device != src->device) return tr::fail(TR_E_INVALID, "tr_scene_layer_from_scene: the scenes are on different devices");
+    if (src->width > LAYER_MAX_SIDE || src->height > LAYER_MAX_SIDE)
+        return tr::fail(TR_E_INVALID, "tr_scene_layer_from_scene: src is wider or higher than 8192 (a layer's width and height must be 1..8192)");
+    if (!whole_frame(src))
+        return tr::fail(TR_E_INVALID, "tr_scene_layer_from_scene: src is a band scene (tr_options.band_row0/1): it holds only its rows of the frame");
+    st = check_layer_scene(dst, "tr_scene_layer_from_scene");
+    if (st != TR_OK) return st;
+    if (src->broken) return unusable();
+    HIP_TRY(hipSetDevice(dst->device));
+    // what src holds back goes first, as in tr_scene_set_texture_from_frame: its current frame buffer is known after it
+    if ((st = submit_pending(src)) != TR_OK) return st;
+    return layer_into(dst, layer_rule(p, src->width, src->height), src->d_fb, src, out, "tr_scene_layer_from_scene");
+}
+
+int tr_scene_get_layered(tr_scene *s, const tr_layer_params *p, const void *image, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_layered: null scene");
+    int st = check_layer_params(p, false, "tr_scene_get_layered");
+    if (st == TR_OK && (!image || !rgb)) st = tr::fail(TR_E_INVALID, "tr_scene_get_layered: null argument");
+    if (st == TR_OK) st = check_layer_scene(s, "tr_scene_get_layered");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const LayerRule r = layer_rule(p, p->width, p->height);
+    const size_t image_bytes = (size_t)layer_block_bytes(r.width, r.height, r.stride, r.format);
+    const void *source = nullptr;
+    st = classify_layer_image(image, image_bytes, "tr_scene_get_layered", &source);
+    if (st != TR_OK) return st;
+    if (refuse_overlap(s, source, frame_bytes(s), "tr_scene_get_layered", "layers", 0u, image_bytes) != TR_OK)
+        return tr::fail(TR_E_INVALID, "tr_scene_get_layered: `image` overlaps a frame buffer of the scene");
+    // (a cleared scene is zeros only where nothing is blended)
+    return get_stage(s, rgb, frame_bytes(s), layer_misses(r, s->width, s->height) ? cleared : nullptr,
+                     [&](uint8_t *o) { return enqueue_layer(s, r, (const uint8_t *)source, nullptr, o); });
+}
+
+// The rule of tr_layer.h over caller's arrays, on the host.  Needs no GPU.
+int tr_layer_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_layer_params *p, const uint8_t *image, uint8_t *out)
+{
+    int st = check_layer_params(p, false, "tr_layer_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || height < 1u) return tr::fail(TR_E_INVALID, "tr_layer_host: the frame's width and height must be at least 1");
+    if (!rgb || !image || !out) return tr::fail(TR_E_INVALID, "tr_layer_host: null argument");
+    if ((p->flags & kLayerWhere) && !z) return tr::fail(TR_E_INVALID, "tr_layer_host: a WHERE flag needs z");
+    layer_host(width, height, rgb, z, layer_rule(p, p->width, p->height), image, out);
     return TR_OK;
 }
 

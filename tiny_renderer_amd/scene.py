@@ -630,6 +630,147 @@ class Y4MWriter:
         return False
 
 
+LAYER_MODES = {"normal": 0, "add": 1, "multiply": 2, "screen": 3, "lighten": 4, "darken": 5, "difference": 6}   # (TR_LAYER_*)
+LAYER_RGB8, LAYER_RGBA8, LAYER_KEY, LAYER_WHERE_DRAWN, LAYER_WHERE_UNDRAWN, LAYER_MAX_SIDE = 0, 1, 1, 2, 4, 8192
+LAYER_WHERE = {None: 0, "drawn": LAYER_WHERE_DRAWN, "undrawn": LAYER_WHERE_UNDRAWN}
+
+
+class LayerParams(C.Structure):
+    """tr_layer_params"""
+    _fields_ = [("mode", C.c_uint32), ("format", C.c_uint32), ("flags", C.c_uint32), ("opacity", C.c_uint32), ("x", C.c_int32), ("y", C.c_int32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("stride", C.c_uint32), ("key", C.c_uint8 * 4)]
+
+
+def layer_params(width, height, x=0, y=0, mode="normal", format="rgb8", opacity=256, where=None, key=None, stride=0, who="layer"):
+    """tr_layer_params: a layer of width x height pixels (each 1..8192; both 0 for Scene.layer_from) of format "rgb8" or
+    "rgba8", rows `stride` bytes apart (0: tightly packed), its top-left pixel on frame pixel (x, y) -- signed, row 0 =
+    top.  mode: "normal", "add", "multiply", "screen", "lighten", "darken" or "difference"; opacity 0..256; where: None,
+    "drawn" (the model only) or "undrawn" (a backdrop); key: None or (r, g, b), the layer colour that covers nothing.
+    ValueError, in the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    for v in (width, height, x, y, opacity, stride):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: width, height, x, y, opacity and stride must be integers" % who)
+    if mode not in LAYER_MODES:
+        raise ValueError("%s: mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE" % who)
+    if format not in ("rgb8", "rgba8"):
+        raise ValueError("%s: format must be TR_LAYER_RGB8 or TR_LAYER_RGBA8" % who)
+    if where not in LAYER_WHERE:
+        raise ValueError("%s: where must be None, \"drawn\" or \"undrawn\"" % who)
+    if not 0 <= opacity <= 256:
+        raise ValueError("%s: opacity must be 0..256" % who)
+    if not -2 ** 31 <= x < 2 ** 31 or not -2 ** 31 <= y < 2 ** 31:
+        raise ValueError("%s: x and y must fit 32 bits" % who)
+    bpp = 4 if format == "rgba8" else 3
+    if (width, height, stride) != (0, 0, 0):
+        if not 1 <= width <= LAYER_MAX_SIDE or not 1 <= height <= LAYER_MAX_SIDE:
+            raise ValueError("%s: width and height must be 1..8192" % who)
+        if stride != 0 and not width * bpp <= stride < 2 ** 32:
+            raise ValueError("%s: stride must be 0 or at least the bytes of a row" % who)
+    flags = LAYER_WHERE[where] | (LAYER_KEY if key is not None else 0)
+    k = (C.c_uint8 * 4)(0, 0, 0, 0)
+    if key is not None:
+        c = [int(v) for v in key]
+        if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+            raise ValueError("%s: key must be three values 0..255" % who)
+        k = (C.c_uint8 * 4)(c[0], c[1], c[2], 0)
+    return LayerParams(LAYER_MODES[mode], LAYER_RGBA8 if bpp == 4 else LAYER_RGB8, flags, int(opacity), int(x), int(y), int(width), int(height),
+                       int(stride), k)
+
+
+def _layer_array(image, who):
+    """(format, width, height, stride) of a layer held in a uint8 array or tensor [h, w, 3 | 4] whose pixels are packed
+    and whose rows lie `stride` bytes apart."""
+    shape = tuple(image.shape)
+    strides = tuple(image.stride()) if hasattr(image, "data_ptr") else tuple(image.strides)
+    item = image.element_size() if hasattr(image, "data_ptr") else image.itemsize
+    if len(shape) != 3 or shape[2] not in (3, 4) or item != 1 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("%s: image must be a uint8 [h, w, 3] or [h, w, 4] array" % who)
+    if strides[2] != 1 or strides[1] != shape[2] or (shape[0] > 1 and strides[0] < shape[1] * shape[2]):
+        raise ValueError("%s: image must have packed pixels and rows at a non-negative stride" % who)
+    return ("rgba8" if shape[2] == 4 else "rgb8"), shape[1], shape[0], (strides[0] if shape[0] > 1 else shape[1] * shape[2])
+
+
+def layer_host(rgb, image, x=0, y=0, mode="normal", opacity=256, where=None, key=None, z=None, in_place=False):
+    """tr_layer_host: the rule of Scene.layer on the host (no GPU needed), by the inline functions k_layer calls.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer); image [h, w, 3 | 4] uint8, its rows at any stride; z [H, W]
+    float32 with row 0 = bottom (read_z_f32), needed with `where`.  Returns the layered frame and leaves its arguments
+    alone; in_place=True hands the library one buffer as rgb and out (a copy of rgb), which the rule allows."""
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError("tr_layer_host: rgb [H, W, 3]")
+    img = np.asarray(image)
+    fmt, w, h, stride = _layer_array(img, "tr_layer_host")
+    p = layer_params(w, h, x, y, mode, fmt, opacity, where, key, stride, "tr_layer_host")
+    zz = None
+    if where is not None:
+        zz = np.ascontiguousarray(z, np.float32)
+        if zz.shape != src.shape[:2]:
+            raise ValueError("tr_layer_host: a WHERE flag needs z [H, W]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_layer_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data,
+                                       None if zz is None else zz.ctypes.data, C.addressof(p), img.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _layer_size(w, h, who):
+    for v in (w, h):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= LAYER_MAX_SIDE:
+            raise ValueError("%s: width and height must be 1..8192" % who)
+    return int(w), int(h)
+
+
+def layer_gradient(w, h, top, bottom):
+    """An rgb8 layer [h, w, 3] that runs from the colour `top` in row 0 to `bottom` in the last row -- a sky behind the
+    model (where="undrawn").  Row r is round(top + (bottom - top) r / (h - 1)) per channel, halves up."""
+    w, h = _layer_size(w, h, "layer_gradient")
+    a, b = np.asarray(top, np.int64).reshape(3), np.asarray(bottom, np.int64).reshape(3)
+    if a.min() < 0 or a.max() > 255 or b.min() < 0 or b.max() > 255:
+        raise ValueError("layer_gradient: colours must be three values 0..255")
+    r, n = np.arange(h, dtype=np.int64)[:, None], max(h - 1, 1)
+    rows = (2 * (a * (n - r) + b * r) + n) // (2 * n)
+    return np.ascontiguousarray(np.broadcast_to(rows[:, None, :], (h, w, 3)).astype(np.uint8))
+
+
+def layer_vignette(w, h, strength):
+    """A grey rgb8 mask [h, w, 3] for mode="multiply": 255 at the centre, falling with the square of the distance to
+    255 - strength (0..255) in the corners."""
+    w, h = _layer_size(w, h, "layer_vignette")
+    if isinstance(strength, bool) or not isinstance(strength, (int, np.integer)) or not 0 <= strength <= 255:
+        raise ValueError("layer_vignette: strength must be an integer 0..255")
+    # in integers: the squared distance of pixel centres from the centre, in units of half pixels
+    dx, dy = (2 * np.arange(w, dtype=np.int64) + 1 - w) ** 2, (2 * np.arange(h, dtype=np.int64) + 1 - h) ** 2
+    d2, most = dy[:, None] * (w * w) + dx[None, :] * (h * h), 2 * (w * w) * (h * h)   # (scaled so both axes reach 1 at the edge)
+    grey = 255 - (2 * int(strength) * d2 + most) // (2 * most)
+    return np.ascontiguousarray(np.repeat(np.clip(grey, 0, 255).astype(np.uint8)[:, :, None], 3, axis=2))
+
+
+def layer_checker(w, h, cell=8, a=(255, 255, 255), b=(0, 0, 0)):
+    """An rgb8 layer [h, w, 3] of cell x cell squares that alternate between the colours a (top left) and b."""
+    w, h = _layer_size(w, h, "layer_checker")
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or cell < 1:
+        raise ValueError("layer_checker: cell must be a positive integer")
+    ca, cb = np.asarray(a, np.int64).reshape(3), np.asarray(b, np.int64).reshape(3)
+    if min(ca.min(), cb.min()) < 0 or max(ca.max(), cb.max()) > 255:
+        raise ValueError("layer_checker: colours must be three values 0..255")
+    odd = ((np.arange(h)[:, None] // cell + np.arange(w)[None, :] // cell) % 2).astype(bool)
+    return np.where(odd[:, :, None], cb.astype(np.uint8), ca.astype(np.uint8))
+
+
+def layer_letterbox(w, h, bar, colour=(0, 0, 0)):
+    """An rgba8 layer [h, w, 4]: `bar` rows of opaque `colour` at the top and at the bottom, transparent between."""
+    w, h = _layer_size(w, h, "layer_letterbox")
+    if isinstance(bar, bool) or not isinstance(bar, (int, np.integer)) or not 0 <= 2 * bar <= h:
+        raise ValueError("layer_letterbox: bar must be an integer with 0 <= 2 bar <= h")
+    c = np.asarray(colour, np.int64).reshape(3)
+    if c.min() < 0 or c.max() > 255:
+        raise ValueError("layer_letterbox: colour must be three values 0..255")
+    out = np.zeros((h, w, 4), np.uint8)
+    out[:, :, :3] = c.astype(np.uint8)
+    out[:bar, :, 3] = 255
+    out[h - bar:, :, 3] = 255
+    return out
+
+
 WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
 WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
 
@@ -1905,6 +2046,58 @@ class Scene:
             return target
         self.sync()
         return yuv_planes(target.copy(), w, h, p.layout)
+
+    # --- layers (tr_scene_layer / tr_scene_layer_from_scene / tr_scene_get_layered) ------------------
+    def _layer_source(self, image, who, width, height, format, stride):
+        """(address, format, width, height, stride, keep-alive) of `image`: a torch uint8 tensor [h, w, 3 | 4] on the scene's
+        device or a page-locked array of the scene's (rows at any stride), or a device address (int) with width,
+        height, format and stride."""
+        if hasattr(image, "data_ptr") or isinstance(image, np.ndarray):
+            fmt, w, h, st = _layer_array(image, who)
+            return (image.data_ptr() if hasattr(image, "data_ptr") else image.ctypes.data), fmt, w, h, st
+        if width is None or height is None:
+            raise ValueError("%s: a device address needs width and height" % who)
+        return int(image), format, width, height, stride
+
+    def layer(self, image, x=0, y=0, mode="normal", opacity=256, where=None, key=None, out=None, width=None, height=None, format="rgb8", stride=0):
+        """tr_scene_layer: blends a second image into the current frame on the device with its top-left pixel on frame
+        pixel (x, y) (signed; row 0 = top; it may hang over any edge): a backdrop (where="undrawn"), a tint of the
+        model (where="drawn"), a watermark or picture-in-picture, a vignette (mode="multiply"), a cross-fade (opacity).
+        `image`: a torch uint8 tensor [h, w, 3] or [h, w, 4] on the scene's device -- a non-contiguous row stride is
+        passed on as the stride --, a page-locked array of the scene's (pinned_layer), or a device address (int) with
+        width, height, format and stride.  out=None: in place, by the kernel itself -- every later consumer sees the
+        layered frame, z, winner words and the shadow buffer stay, calling it twice blends twice.  Otherwise `out` is a
+        device pointer (int) to 3 * W * H bytes apart from every frame buffer of the scene, or an array from
+        pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync() -- keep
+        `image` alive until then.  Band scenes are refused.  Depth is read only with `where`.  layer_host is the rule."""
+        src, fmt, w, h, st = self._layer_source(image, "tr_scene_layer", width, height, format, stride)
+        p = layer_params(w, h, x, y, mode, fmt, opacity, where, key, st, "tr_scene_layer")
+        check(load_library().tr_scene_layer(self._h, C.addressof(p), src, self._out_pointer(out)))
+        return out
+
+    def layer_from(self, other, x=0, y=0, mode="normal", opacity=256, where=None, key=None, out=None):
+        """tr_scene_layer_from_scene: the same with the CURRENT frame of the scene `other` (any size) as the layer, read
+        on the device behind its fast-clear flags; ordered behind other's renders issued so far.  other is only read."""
+        if not isinstance(other, Scene):
+            raise ValueError("tr_scene_layer_from_scene: other must be a Scene")
+        p = layer_params(0, 0, x, y, mode, "rgb8", opacity, where, key, 0, "tr_scene_layer_from_scene")
+        check(load_library().tr_scene_layer_from_scene(self._h, C.addressof(p), other._h, self._out_pointer(out)))
+        return out
+
+    def get_layered(self, image, x=0, y=0, mode="normal", opacity=256, where=None, key=None, strict=True, width=None, height=None,
+                    format="rgb8", stride=0):
+        """tr_scene_get_layered: the current frame with `image` blended in on the device (arguments as for layer), as an
+        [H, W, 3] uint8 array.  Synchronizes; the scene's frame stays as it is."""
+        src, fmt, w, h, st = self._layer_source(image, "tr_scene_get_layered", width, height, format, stride)
+        p = layer_params(w, h, x, y, mode, fmt, opacity, where, key, st, "tr_scene_get_layered")
+        return self._image("tr_scene_get_layered", strict, C.addressof(p), src)
+
+    def pinned_layer(self, width, height, channels=3):
+        """A page-locked [height, width, channels] uint8 array for layer / get_layered (freed with the scene)."""
+        if channels not in (3, 4):
+            raise ValueError("pinned_layer: channels must be 3 or 4")
+        w, h = _layer_size(width, height, "pinned_layer")
+        return self._pinned_array((h, w, channels))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
