@@ -1106,6 +1106,71 @@ int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rg
 int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
                      const tr_convolve_params *p);
 
+/* Rank: the scene's CURRENT frame through an order-statistic neighbourhood filter on the device -- one kernel (k_rank)
+ * for median, minimum (erode), maximum (dilate) and what is built from them: open, close, morphological gradient,
+ * despeckle.  No stack of convolutions expresses these.
+ * Input.  F is the frame as tr_scene_get_frame_buffer returns it: rgb8, row 0 at the top.
+ * Footprint.  A set of taps inside a kw x kh box; kw and kh are odd and each is 1..15.  It is given as rows[15] of
+ * uint16_t: bit i of rows[j] set means that column i from the left, row j from the TOP, is a tap.  Bits at or beyond kw,
+ * and rows at or beyond kh, must be 0.  n, the number of taps, must be at least 1.  Rows or columns inside the box may be
+ * empty, and the centre need not be a tap.  Tap (i, j) of pixel (x, y) reads F(x + i - kw / 2, y + j - kh / 2).
+ * Edge handling.  Under TR_RANK_BORDER a tap outside the image is border[c]; under TR_RANK_CLAMP its index is clamped
+ * per axis.
+ * Ranking.  For each channel independently, sort the n tap values in ascending order; v(k) is element k, 0-based.
+ * Operations (op):
+ *   TR_RANK_VALUE         v(rank).  Rank 0 is erode, rank n - 1 is dilate, and the middle rank is the median.
+ *   TR_RANK_RANGE         v(rank2) - v(rank).  The morphological gradient is this at ranks 0 and n - 1.
+ *   TR_RANK_MID           (v(rank) + v(rank2) + 1) >> 1
+ *   TR_RANK_CLAMP_CENTRE  min(max(F(x, y), v(rank)), v(rank2)): conservative despeckle -- a pixel is changed only if it
+ *                         lies outside the rank interval of its neighbourhood.
+ * rank <= rank2 <= n - 1; under TR_RANK_VALUE rank2 must be 0.
+ * Order statistics are exact, so the device equals tr_rank_host in every byte.  What follows from the rule: a one-tap
+ * footprint under TR_RANK_VALUE is a copy -- off centre a shifted copy, with the border colour entering; a constant frame
+ * under TR_RANK_CLAMP stays constant, and its TR_RANK_RANGE is 0; rank k of F equals 255 - rank (n - 1 - k) of (255 - F)
+ * with the border complemented; TR_RANK_VALUE at rank 0 or n - 1 over a full kw x kh rectangle equals the kw x 1 call
+ * followed by the 1 x kh call, under either edge mode. */
+#define TR_RANK_VALUE 0u
+#define TR_RANK_RANGE 1u
+#define TR_RANK_MID 2u
+#define TR_RANK_CLAMP_CENTRE 3u
+#define TR_RANK_BORDER 0u
+#define TR_RANK_CLAMP 1u
+typedef struct tr_rank_params {
+    uint32_t struct_size;   /* = sizeof(tr_rank_params) = 64 */
+    uint32_t kw, kh;        /* odd, 1..15 each */
+    uint32_t op;            /* TR_RANK_VALUE, TR_RANK_RANGE, TR_RANK_MID or TR_RANK_CLAMP_CENTRE */
+    uint32_t rank, rank2;   /* 0-based; rank2 is 0 under TR_RANK_VALUE, else rank <= rank2 <= n - 1 */
+    uint32_t edge;          /* TR_RANK_BORDER or TR_RANK_CLAMP */
+    uint8_t border[3];      /* r, g, b of a tap outside the image under TR_RANK_BORDER */
+    uint8_t pad;            /* 0 */
+    uint16_t rows[15];      /* bit i of rows[j]: column i from the left, row j from the top is a tap */
+    uint16_t pad2;          /* 0 */
+} tr_rank_params;
+/* Filters the current frame -- what the getters mean.  Asynchronous and ordered like tr_scene_convolve: frames held back
+ * are submitted, a pending clear is made real, k_rank is enqueued on the scene's stream.  No depth is read, so a depth
+ * left on the chip stays there.  out: 3 * W * H bytes of device memory or of memory from tr_host_alloc, apart from every
+ * frame buffer of the scene; every byte is written and the scene's frame stays.  out == NULL: IN PLACE, through the
+ * scene's scratch frame (a tap reads neighbours) -- every later consumer sees the filtered frame, the colour fast-clear
+ * flags follow (a tile is flagged only where it is zeros in every byte), z, the winner words and the shadow buffer stay;
+ * calling it twice filters twice, so open is erode then dilate.  A tile whose existing 3 x 3 neighbourhood is flagged
+ * clean, with no non-zero border colour in reach (TR_RANK_CLAMP, a border of 0, or a halo inside the image), is 0 under
+ * every op: it is stored without a load.  A texel behind a raised flag counts as zeros and is never loaded.  A scene that
+ * is logically cleared under TR_RANK_CLAMP or a border of 0: zeros out of place, nothing in place, no kernel; otherwise
+ * the clear is made real and the kernel runs.
+ * TR_E_INVALID, each text opening with the call's name: a null scene or params, a wrong struct_size, an even or
+ * out-of-range kw or kh, footprint bits outside the box, an empty footprint, an unknown op or edge, pad or pad2 != 0, a
+ * rank or rank2 >= n, rank > rank2, a non-zero rank2 under TR_RANK_VALUE; a BAND scene (tr_options.band_row0/1 set: the
+ * taps at a band's border lie in another rank's rows); ordinary host memory as `out`, a pinned buffer that is too small,
+ * an `out` that overlaps a frame buffer of the scene.  The parameters are checked first, then the band, then `out`. */
+int tr_scene_rank(tr_scene *s, const tr_rank_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * W * H bytes): waits for the scene first, filters into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_convolved.  The scene's frame stays. */
+int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the inline functions k_rank shares.  rgb and out: 3 * width * height
+ * bytes, row 0 = top; out must not be rgb.  The same parameter checks; a width or height of 0 returns TR_OK. */
+int tr_rank_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
+                 const tr_rank_params *p);
+
 /* YUV output: the scene's CURRENT frame, or any rgb8 image on the device, converted on the device to 8-bit YCbCr planes --
  * the form encoders and video files take, 1.5 bytes a pixel in 4:2:0 where rgb8 has 3 -- as the chain's very last step
  * (render, composite, ..., resize, TO_YUV, read back).  The source F is the image tr_scene_get_frame_buffer would return:

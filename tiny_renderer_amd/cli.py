@@ -13,6 +13,15 @@ import time
 import numpy as np
 
 
+class _Once(argparse.Action):
+    """An integer option that may be given at most once."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        if getattr(namespace, self.dest, None) is not None:
+            parser.error("%s may be given at most once" % option_string)
+        setattr(namespace, self.dest, values)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="tiny_renderer_amd", description=__doc__)
     ap.add_argument("-p", dest="asset_path", default="assets/diablo", help="asset folder (main.rs:12)")
@@ -141,6 +150,16 @@ def main(argv=None):
                          '"0,-1,0;-1,5,-1;0,-1,0" (odd sides up to 9; black outside the picture); applied after --edges')
     ap.add_argument("--convolve-shift", type=int, default=0, metavar="N", help="with --convolve: shift the sum right by N bits, rounded (0..22)")
     ap.add_argument("--convolve-bias", type=int, default=0, metavar="N", help="with --convolve: add N afterwards (-255..255)")
+    ap.add_argument("--erode", type=int, default=None, action=_Once, metavar="N",
+                    help="rank: the minimum over a footprint of radius N (1..7), clamped at the edge, on the GPU (Scene.rank; after "
+                         "the convolve options and before --overlay)")
+    ap.add_argument("--dilate", type=int, default=None, action=_Once, metavar="N", help="rank: the maximum over a footprint of radius N (1..7); applied after --erode")
+    ap.add_argument("--median", type=int, default=None, action=_Once, metavar="N", help="rank: the median over a footprint of radius N (1..7); applied after --dilate")
+    ap.add_argument("--despeckle", type=int, default=None, action=_Once, metavar="N",
+                    help="rank: every pixel clamped between the second lowest and the second highest value of its footprint of radius N "
+                         "(1..7); applied after --median")
+    ap.add_argument("--rank-shape", default=None, choices=("rect", "disc", "cross"),
+                    help="the footprint of --erode, --dilate, --median and --despeckle: the whole square (rect; default), a disc or a cross")
     ap.add_argument("--backdrop", default=None, metavar="FILE.tga|R,G,B[:R,G,B]",
                     help="layer: a picture, a colour or a gradient from the top colour to the bottom one behind the model, blended "
                          "on the GPU where nothing is drawn (Scene.layer, where=\"undrawn\"; after --with and --ao, before the "
@@ -371,6 +390,27 @@ def main(argv=None):
                 args.convolves.append(convolve_params(np.array(rows, np.int32), shift=args.convolve_shift, bias=args.convolve_bias))
         except ValueError as e:
             ap.error(str(e))
+    args.ranks = []
+    if all(v is None for v in (args.erode, args.dilate, args.median, args.despeckle)):
+        if args.rank_shape is not None:
+            ap.error("--rank-shape goes with --erode, --dilate, --median or --despeckle")
+    else:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--erode, --dilate, --median and --despeckle work on the colour frame of one GPU, by frame count: "
+                     "use --gpus 1, --frames and --view frame")
+        from .scene import rank_params, footprint_rect, footprint_disc, footprint_cross
+        shape = {"rect": lambda r: footprint_rect(2 * r + 1, 2 * r + 1), "disc": footprint_disc, "cross": footprint_cross}[args.rank_shape or "rect"]
+        for name, r in (("--erode", args.erode), ("--dilate", args.dilate), ("--median", args.median), ("--despeckle", args.despeckle)):
+            if r is None:
+                continue
+            if not 1 <= r <= 7:
+                ap.error(name + " takes a radius 1..7")
+            f = shape(r)
+            n = int(f.sum())
+            if name == "--despeckle":
+                args.ranks.append(rank_params(f, 1, n - 2, op="clamp_centre", edge="clamp"))
+            else:
+                args.ranks.append(rank_params(f, {"--erode": "min", "--dilate": "max", "--median": "median"}[name], edge="clamp"))
     args.resize = None
     if args.out_size is not None:
         try:
@@ -671,6 +711,8 @@ def _post(args, T, scene, say):
         scene.warp(wp)
     for cp in args.convolves:     # in place, after the warps: --stats, --ssaa and --out-size see the filtered frame
         scene.convolve(cp)
+    for rp in args.ranks:         # in place, after the convolves: erode, dilate, median, despeckle
+        scene.rank(rp)
     if args.overlay is not None:   # in place, after the convolves: --stats, --ssaa, --out-size and y4m output see the layered frame
         scene.layer(_pinned_layer(scene, "overlay", lambda: T.load_tga(args.overlay)), args.overlay_at[0], args.overlay_at[1], args.overlay_mode,
                     args.overlay_opacity)

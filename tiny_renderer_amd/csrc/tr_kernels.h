@@ -10,6 +10,7 @@
 #include "tr_ao.h"
 #include "tr_composite.h"
 #include "tr_convolve.h"
+#include "tr_rank.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_grade.h"
@@ -139,6 +140,11 @@ int launch_layer(const LayerArgs &a, bool from_scene, hipStream_t st);
 // read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile
 // of a.out -- a tile flagged there is zeros in every byte.
 int launch_convolve(const ConvolveArgs &a, hipStream_t st);
+// Rank: a.fb through the order-statistic filter a.rule into a.out (which does not overlap it) by the rule of tr_rank.h,
+// through the scene's colour fast-clear flags: k_rank, in its extremes form where every rank asked for is the first or
+// the last, else the general one.  The whole frame only (no band); no depth is read.  a.words is set here.  a.out_clean
+// as for launch_convolve.
+int launch_rank(const RankArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

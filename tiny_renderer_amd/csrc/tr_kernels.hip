@@ -37,6 +37,7 @@
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_convolve.h"
+#include "tr_rank.h"
 #include "tr_grade.h"
 #include "tr_stats.h"
 #include "tr_kernels.h"
@@ -2924,6 +2925,225 @@ __global__ __launch_bounds__(CONV_THREADS) void k_convolve(ConvolveArgs a)
 }
 #undef CONV_WINDOW
 
+// Rank (tr_scene_rank): the frame through an order-statistic filter over a footprint of taps into `out`, never in place;
+// tr_rank.h has the rule.  The tile, the workgroup, the rotated block-to-tile mapping, the nine-flag test, the staged
+// rows of 160 words that start 16 pixels left of the tile, the window of a lane's eight rows over a staged column and
+// the three store forms are k_convolve's.  What differs:
+//   * a neighbourhood of zeros is 0 under every op: the constant tile is zeros and out_clean gets 1;
+//   * a staged pixel is SPREAD, r | g << 10 | b << 20, so that one subtraction compares three channels at once: with
+//     bit 9 of every field set in p, field c of p - t is 512 + p_c - t_c, and its bit 9 says p_c >= t_c (no field
+//     borrows from its neighbour: 257 <= 512 + p_c - t_c <= 767);
+//   * SEL 0, any rank of any footprint: eight steps from bit 7 down build v(k) a channel -- the candidate t | bit stays
+//     where the number of taps below it is at most k, that is where ge, the number of taps at or above it, is at least
+//     n - k.  ge of three channels is one word of 10-bit fields (n <= 225), the test against n - k the same subtraction.
+//     A staged value feeds the eight windows of the lane; whether row j, column i of the box is a tap is a scalar, the
+//     window of eight such scalars slides by one a staged row; a column of the box without a tap is skipped.  An op of
+//     two ranks searches twice;
+//   * SEL 1, 2, 3, the extremes: every rank asked for is 0 or n - 1, so no selection -- the minimum (bit 0 of SEL)
+//     and/or the maximum (bit 1) over the taps, one pass; a pixel outside the footprint enters as 255 or as 0.
+// LDS, dynamic: (16 + 2 ry) * 640 bytes, 10 KB at a box one row high, 19.2 KB at fifteen.  fb and every flag of the
+// frame are only read.  No atomics, no scratch, no inline assembly.
+constexpr uint32_t RANK_ONES = 0x00100401u, RANK_HIGH = RANK_ONES << 9;
+static_assert(RANK_MAX_TAPS < 512u && RANK_MAX_SIDE / 2u <= 15u && (int)(RANK_MAX_SIDE / 2u) < TILE_H, "a count fits a 10-bit field; the halo lies in the eight tiles around");
+
+__device__ __forceinline__ uint32_t rank_spread(uint32_t px) { return (px & 0xFFu) | ((px & 0xFF00u) << 2) | ((px & 0xFF0000u) << 4); }
+__device__ __forceinline__ uint32_t rank_unspread(uint32_t v) { return (v & 0xFFu) | ((v >> 2) & 0xFF00u) | ((v >> 4) & 0xFF0000u); }
+
+// Is column i of row j (from the top) a tap, for a row index that may lie outside the box?  (scalar)
+__device__ __forceinline__ uint32_t rank_member(const RankArgs &a, int32_t i, int32_t j, int32_t kh)
+{
+    return j >= 0 && j < kh ? (a.rule.rows[j] >> i) & 1u : 0u;
+}
+
+// v(k) of the lane's eight windows, spread: `src` is the lane's first staged row at the column of the box's column 0.
+__device__ __forceinline__ void rank_search(const uint32_t *src, const RankArgs &a, uint32_t k, uint32_t col_mask, uint32_t (&t)[CONV_ROWS])
+{
+    const int32_t kw = (int32_t)a.rule.kw, kh = (int32_t)a.rule.kh, ry = kh / 2;
+    const uint32_t need = (a.rule.n - k) * RANK_ONES;
+#pragma unroll
+    for (int r = 0; r < CONV_ROWS; r++) t[r] = 0u;
+    for (int32_t b = 7; b >= 0; b--) {
+        uint32_t cand[CONV_ROWS], ge[CONV_ROWS];
+#pragma unroll
+        for (int r = 0; r < CONV_ROWS; r++) cand[r] = t[r] | (RANK_ONES << b), ge[r] = 0u;
+        for (int32_t i = 0; i < kw; i++) {
+            if (((col_mask >> i) & 1u) == 0u) continue;  // (scalar)
+            uint32_t wk[CONV_ROWS];
+#pragma unroll
+            for (int r = 0; r < CONV_ROWS; r++) wk[r] = 0u;
+            wk[0] = rank_member(a, i, 2 * ry, kh) * RANK_ONES;
+            for (int32_t jj = 0; jj < CONV_ROWS + 2 * ry; jj++) {
+                const uint32_t w_next = rank_member(a, i, 2 * ry - jj - 1, kh) * RANK_ONES;
+                const uint32_t p = src[jj * CONV_LDS_W + i] | RANK_HIGH;
+#pragma unroll
+                for (int r = 0; r < CONV_ROWS; r++) ge[r] += ((p - cand[r]) >> 9) & wk[r];
+#pragma unroll
+                for (int r = CONV_ROWS - 1; r > 0; r--) wk[r] = wk[r - 1];
+                wk[0] = w_next;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < CONV_ROWS; r++) t[r] |= ((((ge[r] | RANK_HIGH) - need) >> 9) & RANK_ONES) << b;
+    }
+}
+
+template <int SEL, int STORE>
+__global__ __launch_bounds__(CONV_THREADS) void k_rank(RankArgs a)
+{
+    static_assert(TILE_W == 128 && CONV_THREADS == 2 * TILE_W && 8 * TILE_H <= CONV_THREADS && CONV_ROWS == 8, "a lane owns a column and eight rows; the shares are the first lanes");
+    extern __shared__ __align__(16) uint32_t s_rk[];  // (TILE_H + 2 ry) rows of CONV_LDS_W spread pixels
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t kw = (int32_t)a.rule.kw, kh = (int32_t)a.rule.kh, rx = kw / 2, ry = kh / 2;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t ty = (int32_t)blockIdx.x / ntx, tx = ((int32_t)blockIdx.x % ntx + 5 * ty) % ntx;
+    const uint32_t t = (uint32_t)(ty * ntx + tx);
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): exists -- it is part of the grid; czero -- and its flag is up
+    uint32_t exists = 0u, czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) continue;
+            exists |= bit;
+            if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+        }
+    const bool clamp = a.rule.edge == RANK_CLAMP;
+    const bool halo_inside = x0 - rx >= 0 && x0 + TILE_W + rx <= W && y0 - ry >= 0 && y0 + TILE_H + ry <= H;
+    const bool constant = czero == exists && (clamp || a.rule.border == 0u || halo_inside);
+    const int32_t sx = x0 + (int32_t)(threadIdx.x % 8u) * 16, srow = (int32_t)(threadIdx.x / 8u), sy = y0 + srow;
+    const bool share = threadIdx.x < 8u * TILE_H && sx < W && sy < H;
+    const int32_t n_px = share ? min(16, W - sx) : 0;  // (STORE 2: 16 or none; 1: a multiple of 4)
+    const size_t share_at = share ? ((size_t)(H - 1 - sy) * (size_t)W + (size_t)sx) * 3u : 0u;
+    uint8_t *o = a.out + share_at;
+    uint32_t px[16];
+    if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = constant ? 1u : 0u;
+    if (constant) {  // (workgroup-uniform, ahead of the barriers)
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = 0u;
+        conv_store_share<STORE>(o, px, n_px);
+        return;
+    }
+    // LDS row r is the kernel's row y0 - ry + r, LDS column c the frame's column x0 - 16 + c; columns c_lo .. c_hi - 1 are read
+    const int32_t rows = TILE_H + 2 * ry, c_lo = 16 - rx, c_hi = 16 + TILE_W + rx;
+    const uint32_t border = rank_spread(a.rule.border);
+    if (a.words != 0u) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (CONV_LDS_W / 4); p += CONV_THREADS) {
+            const int32_t r = p / (CONV_LDS_W / 4), j = p % (CONV_LDS_W / 4);
+            if (4 * j + 3 < c_lo || 4 * j >= c_hi) continue;  // (no tap reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - ry + r;
+            // (x and the width are multiples of 4: the four pixels lie inside the image's columns or outside together)
+            const bool x_out = x < 0 || x >= W, y_out = y < 0 || y >= H;
+            uint32_t c[4] = { border, border, border, border };
+            if (clamp || !(x_out || y_out)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                c[0] = c[1] = c[2] = c[3] = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = a.fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    if (!x_out) {
+                        const uint32_t *q4 = reinterpret_cast<const uint32_t *>(q);
+                        const uint32_t w0 = q4[0], w1 = q4[1], w2 = q4[2];
+                        c[0] = rank_spread(w0 & 0xFFFFFFu);
+                        c[1] = rank_spread((w0 >> 24) | ((w1 & 0xFFFFu) << 8));
+                        c[2] = rank_spread((w1 >> 16) | ((w2 & 0xFFu) << 16));
+                        c[3] = rank_spread(w2 >> 8);
+                    } else {
+                        c[0] = c[1] = c[2] = c[3] = (uint32_t)q[0] | ((uint32_t)q[1] << 10) | ((uint32_t)q[2] << 20);
+                    }
+                }
+            }
+            *reinterpret_cast<uint4 *>(&s_rk[r * CONV_LDS_W + 4 * j]) = make_uint4(c[0], c[1], c[2], c[3]);
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * CONV_LDS_W; p += CONV_THREADS) {
+            const int32_t r = p / CONV_LDS_W, c = p % CONV_LDS_W;
+            if (c < c_lo || c >= c_hi) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - ry + r;
+            uint32_t col = border;
+            if (clamp || !(x < 0 || x >= W || y < 0 || y >= H)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                col = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = a.fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    col = (uint32_t)q[0] | ((uint32_t)q[1] << 10) | ((uint32_t)q[2] << 20);
+                }
+            }
+            s_rk[r * CONV_LDS_W + c] = col;
+        }
+    }
+    __syncthreads();
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, row0 = (int32_t)threadIdx.x / TILE_W * CONV_ROWS;
+    // the lane's first staged row at the column of the box's column 0
+    const uint32_t *src = s_rk + row0 * CONV_LDS_W + 16 + col - rx;
+    uint32_t col_mask = 0u;  // the columns of the box that hold a tap
+    for (int32_t j = 0; j < kh; j++) col_mask |= a.rule.rows[j];
+    uint32_t lo[CONV_ROWS], hi[CONV_ROWS];  // v(rank), v(rank2), spread
+    if (SEL == 0) {
+        rank_search(src, a, a.rule.rank, col_mask, lo);
+        if (a.rule.rank2 != a.rule.rank) {  // (scalar)
+            rank_search(src, a, a.rule.rank2, col_mask, hi);
+        } else {
+#pragma unroll
+            for (int r = 0; r < CONV_ROWS; r++) hi[r] = lo[r];
+        }
+    } else {
+        uint32_t mn[CONV_ROWS][3], mx[CONV_ROWS][3];
+#pragma unroll
+        for (int r = 0; r < CONV_ROWS; r++) mn[r][0] = mn[r][1] = mn[r][2] = 255u, mx[r][0] = mx[r][1] = mx[r][2] = 0u;
+        for (int32_t i = 0; i < kw; i++) {
+            if (((col_mask >> i) & 1u) == 0u) continue;  // (scalar)
+            uint32_t wk[CONV_ROWS];  // 255 where the staged row is a tap of the lane's row r
+#pragma unroll
+            for (int r = 0; r < CONV_ROWS; r++) wk[r] = 0u;
+            wk[0] = rank_member(a, i, 2 * ry, kh) * 255u;
+            for (int32_t jj = 0; jj < CONV_ROWS + 2 * ry; jj++) {
+                const uint32_t w_next = rank_member(a, i, 2 * ry - jj - 1, kh) * 255u;
+                const uint32_t p = src[jj * CONV_LDS_W + i];
+                const uint32_t pc[3] = { p & 0xFFu, (p >> 10) & 0xFFu, p >> 20 };
+#pragma unroll
+                for (int r = 0; r < CONV_ROWS; r++)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        if ((SEL & 1) != 0) mn[r][ch] = min(mn[r][ch], pc[ch] | (wk[r] ^ 255u));
+                        if ((SEL & 2) != 0) mx[r][ch] = max(mx[r][ch], pc[ch] & wk[r]);
+                    }
+#pragma unroll
+                for (int r = CONV_ROWS - 1; r > 0; r--) wk[r] = wk[r - 1];
+                wk[0] = w_next;
+            }
+        }
+        const bool lo_min = a.rule.rank == 0u, hi_min = a.rule.rank2 == 0u;  // (n = 1: rank 0 is n - 1 too, and the minimum is it)
+#pragma unroll
+        for (int r = 0; r < CONV_ROWS; r++) {
+            const uint32_t vmin = mn[r][0] | (mn[r][1] << 10) | (mn[r][2] << 20), vmax = mx[r][0] | (mx[r][1] << 10) | (mx[r][2] << 20);
+            lo[r] = (SEL & 2) == 0 || ((SEL & 1) != 0 && lo_min) ? vmin : vmax;
+            hi[r] = (SEL & 2) == 0 || ((SEL & 1) != 0 && hi_min) ? vmin : vmax;
+        }
+    }
+    // the frame's own pixels, staged: row r of the tile is staged row ry + r
+    uint32_t res[CONV_ROWS];
+#pragma unroll
+    for (int r = 0; r < CONV_ROWS; r++)
+        res[r] = rank_finish_px(a.rule.op, rank_unspread(lo[r]), rank_unspread(hi[r]), rank_unspread(s_rk[(ry + row0 + r) * CONV_LDS_W + 16 + col]));
+    __syncthreads();  // every staged pixel has been read: the results take the place of the first rows
+    uint32_t *s_out = s_rk;
+#pragma unroll
+    for (int r = 0; r < CONV_ROWS; r++) s_out[(row0 + r) * TILE_W + col] = res[r];
+    __syncthreads();
+    if (!share) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&s_out[srow * TILE_W + (sx - x0) + 4 * k]);
+        px[4 * k + 0] = v.x, px[4 * k + 1] = v.y, px[4 * k + 2] = v.z, px[4 * k + 3] = v.w;
+    }
+    conv_store_share<STORE>(o, px, n_px);
+}
+
 // Colour grading (tr_scene_grade): every pixel of the frame mapped through the scene's 3-D lookup table into `out`,
 // which may BE the frame (a pixel depends on itself alone); tr_grade.h has the rule.  The working set is the table, not
 // a neighbourhood, so the workgroups are PERSISTENT: the launcher starts as many as the machine holds at once (by the
@@ -5063,6 +5283,45 @@ int launch_convolve(const ConvolveArgs &a0, hipStream_t st)
     else if (a.rule.mul24) CONV_LAUNCH(true, true)
     else CONV_LAUNCH(true, false)
 #undef CONV_LAUNCH
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_rank(const RankArgs &a0, hipStream_t st)
+{
+    RankArgs a = a0;
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    const RankRule &q = a.rule;
+    if (q.kw % 2u == 0u || q.kh % 2u == 0u || q.kw > RANK_MAX_SIDE || q.kh > RANK_MAX_SIDE || q.op > RANK_CLAMP_CENTRE || q.edge > RANK_CLAMP || q.n == 0u ||
+        q.n > q.kw * q.kh || q.rank > q.rank2 || q.rank2 >= q.n)
+        return (int)hipErrorInvalidValue;
+    // `out` is never the frame that is read
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    // staging by words: four pixels at a multiple of four are three aligned words of the frame
+    a.words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u ? 1u : 0u;
+    // the stores: every share three whole 16-byte pieces of `out`, else whole 12-byte pieces at multiples of 4, else bytes
+    const int store = a.frame.width % 16u == 0u && (uintptr_t)a.out % 16u == 0u ? 2 : a.frame.width % 4u == 0u && (uintptr_t)a.out % 4u == 0u ? 1 : 0;
+    // the extremes need no selection: every rank asked for is the first or the last; bit 0 -- the minimum, bit 1 -- the maximum
+    const bool extremes = (q.rank == 0u || q.rank == q.n - 1u) && (q.rank2 == 0u || q.rank2 == q.n - 1u);
+    const int sel = !extremes ? 0 : ((q.rank == 0u || q.rank2 == 0u) ? 1 : 0) | ((q.rank != 0u || q.rank2 != 0u) ? 2 : 0);
+    const size_t lds = (size_t)(TILE_H + 2 * (int)(q.kh / 2u)) * CONV_LDS_W * 4u;
+    const dim3 grid(n_tiles), block(CONV_THREADS);
+#define RANK_LAUNCH(SEL_)                                                                         \
+    {                                                                                             \
+        if (store == 2) hipLaunchKernelGGL((k_rank<SEL_, 2>), grid, block, lds, st, a);           \
+        else if (store == 1) hipLaunchKernelGGL((k_rank<SEL_, 1>), grid, block, lds, st, a);      \
+        else hipLaunchKernelGGL((k_rank<SEL_, 0>), grid, block, lds, st, a);                      \
+    }
+    if (sel == 0) RANK_LAUNCH(0)
+    else if (sel == 1) RANK_LAUNCH(1)
+    else if (sel == 2) RANK_LAUNCH(2)
+    else RANK_LAUNCH(3)
+#undef RANK_LAUNCH
     TR_LAUNCH_CHECK();
     return 0;
 }

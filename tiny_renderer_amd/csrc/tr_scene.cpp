@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2832,7 +2832,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, resize, to_yuv, layer) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, resize, to_yuv, layer) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -5353,6 +5353,108 @@ int tr_convolve_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_convolve_host: null argument");
     if (out == rgb) return tr::fail(TR_E_INVALID, "tr_convolve_host: out is rgb (the rule reads neighbours: not in place)");
     convolve_host(width, height, rgb, out, convolve_rule(p));
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_RANK_VALUE == RANK_VALUE && TR_RANK_RANGE == RANK_RANGE && TR_RANK_MID == RANK_MID && TR_RANK_CLAMP_CENTRE == RANK_CLAMP_CENTRE &&
+                  TR_RANK_BORDER == RANK_BORDER && TR_RANK_CLAMP == RANK_CLAMP && sizeof(tr_rank_params) == 64 && sizeof(RankParams) == sizeof(tr_rank_params) &&
+                  offsetof(tr_rank_params, edge) == offsetof(RankParams, edge) && offsetof(tr_rank_params, border) == offsetof(RankParams, border) &&
+                  offsetof(tr_rank_params, pad) == offsetof(RankParams, pad) && offsetof(tr_rank_params, rows) == offsetof(RankParams, rows) &&
+                  offsetof(tr_rank_params, pad2) == offsetof(RankParams, pad2),
+              "tr_rank.h restates the header");
+
+// tr_rank_params as every entry point accepts them (`who` names the entry point in the error text); *q: tr_rank.h's copy.
+int check_rank_params(const tr_rank_params *p, const char *who, RankParams *q)
+{
+    if (!p) return tr::fail(TR_E_INVALID, std::string(who) + ": null argument");
+    memcpy(q, p, sizeof(RankParams));
+    const char *why = rank_refusal(*q);
+    return why ? tr::fail(TR_E_INVALID, std::string(who) + why) : TR_OK;
+}
+
+int check_rank_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be ranked: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// Is the rule's image of a black frame black?  A neighbourhood of zeros is 0 under every op, so: no border colour comes
+// in -- TR_RANK_CLAMP, or a border of 0.
+bool rank_of_black_is_black(const RankParams &q) { return q.edge == RANK_CLAMP || (q.border[0] | q.border[1] | q.border[2]) == 0u; }
+
+// Enqueues the current frame, filtered, into `out_device` (which overlaps no frame of the scene) behind everything
+// issued so far; out_clean: null, or where k_rank writes the flags of `out_device`.  A pending clear is made real
+// first.  No depth is read: a depth left on the chip stays there.
+int enqueue_rank(tr_scene *s, const RankParams &q, uint8_t *out_device, uint32_t *out_clean)
+{
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st != TR_OK) return st;
+    RankArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+    a.rule = rank_rule(q);
+    {
+        Timed t(s, K_RANK);
+        int rc = launch_rank(a, s->stream);
+        if (rc) return launch_status(rc, "k_rank");
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_rank(tr_scene *s, const tr_rank_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_rank: null scene");
+    RankParams q;
+    int st = check_rank_params(p, "tr_scene_rank", &q);
+    if (st == TR_OK) st = check_rank_scene(s, "tr_scene_rank");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_rank", "tr_scene_get_ranked", "ranks", 0u, &target);
+    if (st != TR_OK) return st;
+    // a logically cleared frame is black, and so is its image where no border colour comes in: zeros out of place, itself in place
+    if (s->z_fb_cleared && rank_of_black_is_black(q)) return target ? cleared_out_of_place(s, target) : TR_OK;
+    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); };
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_ranked: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_ranked: null argument");
+    RankParams q;
+    int st = check_rank_params(p, "tr_scene_get_ranked", &q);
+    if (st == TR_OK) st = check_rank_scene(s, "tr_scene_get_ranked");
+    if (st != TR_OK) return st;
+    // (the predicate takes the scene alone: the parameters decide here which one is asked)
+    return get_stage(s, rgb, frame_bytes(s), rank_of_black_is_black(q) ? cleared : nullptr,
+                     [&](uint8_t *o) { return enqueue_rank(s, q, o, nullptr); });
+}
+
+// The rule of tr_rank.h over a caller's array, on the host.  Needs no GPU.
+int tr_rank_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *out, const tr_rank_params *p)
+{
+    RankParams q;
+    int st = check_rank_params(p, "tr_rank_host", &q);
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_rank_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_rank_host: out is rgb (the rule reads neighbours: not in place)");
+    rank_host(width, height, rgb, out, rank_rule(q));
     return TR_OK;
 }
 

@@ -1065,6 +1065,126 @@ def kernel_motion(length, horizontal=True):
     return ((line, one) if horizontal else (one, line)), CONVOLVE_AXIS_SHIFT
 
 
+RANK_VALUE, RANK_RANGE, RANK_MID, RANK_CLAMP_CENTRE, RANK_BORDER, RANK_CLAMP = 0, 1, 2, 3, 0, 1   # (TR_RANK_*)
+RANK_OPS = {"value": RANK_VALUE, "range": RANK_RANGE, "mid": RANK_MID, "clamp_centre": RANK_CLAMP_CENTRE}
+RANK_EDGES = {"border": RANK_BORDER, "clamp": RANK_CLAMP}
+
+
+class RankParams(C.Structure):
+    """tr_rank_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("kw", C.c_uint32), ("kh", C.c_uint32), ("op", C.c_uint32), ("rank", C.c_uint32),
+                ("rank2", C.c_uint32), ("edge", C.c_uint32), ("border", C.c_uint8 * 3), ("pad", C.c_uint8), ("rows", C.c_uint16 * 15),
+                ("pad2", C.c_uint16)]
+
+
+def rank_params(footprint, rank="median", rank2=None, op="value", edge="border", border=(0, 0, 0)):
+    """tr_rank_params for Scene.rank / Scene.get_ranked / rank_host.  footprint: a 2-D array [kh, kw] (both odd, 1..15)
+    whose non-zero entries are the taps, footprint[j][i] being row j from the top, column i from the left
+    (footprint_rect, footprint_disc, footprint_cross and footprint_line build the usual ones).  rank: "median"
+    ((n - 1) // 2 of the n taps), "min" (0), "max" (n - 1) or an integer; rank2 likewise, for the ops of two ranks.  op:
+    "value" (v(rank)), "range" (v(rank2) - v(rank)), "mid" ((v(rank) + v(rank2) + 1) >> 1) or "clamp_centre" (the pixel
+    clamped to [v(rank), v(rank2)]).  edge: "border" (a tap outside the image is `border`, r g b) or "clamp".
+    ValueError, in the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    if edge in RANK_EDGES:
+        e = RANK_EDGES[edge]
+    elif not isinstance(edge, (bool, str)) and edge in RANK_EDGES.values():
+        e = int(edge)
+    else:
+        raise ValueError("rank: edge must be TR_RANK_BORDER or TR_RANK_CLAMP")
+    if op in RANK_OPS:
+        o = RANK_OPS[op]
+    elif not isinstance(op, (bool, str)) and op in RANK_OPS.values():
+        o = int(op)
+    else:
+        raise ValueError("rank: op must be TR_RANK_VALUE, TR_RANK_RANGE, TR_RANK_MID or TR_RANK_CLAMP_CENTRE")
+    b = [int(v) for v in border]
+    if len(b) != 3 or any(not 0 <= v <= 255 for v in b):
+        raise ValueError("rank: border is three values 0..255")
+    f = np.asarray(footprint)
+    if f.ndim != 2 or f.dtype.kind not in "biu":
+        raise ValueError("rank: the footprint is a 2-D boolean or integer array [kh, kw]")
+    kh, kw = f.shape
+    if kw % 2 == 0 or kh % 2 == 0 or kw > 15 or kh > 15:
+        raise ValueError("rank: kw and kh must be odd and 1..15")
+    taps = f != 0
+    n = int(taps.sum())
+
+    def which(r, name):
+        if isinstance(r, str):
+            if r not in ("median", "min", "max"):
+                raise ValueError('rank: %s is "median", "min", "max" or an integer' % name)
+            return {"median": max(n - 1, 0) // 2, "min": 0, "max": max(n - 1, 0)}[r]
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or r < 0 or r > 0xFFFFFFFF:
+            raise ValueError('rank: %s is "median", "min", "max" or an integer' % name)
+        return int(r)
+
+    p = RankParams(C.sizeof(RankParams), kw, kh, o, which(rank, "rank"), 0 if rank2 is None else which(rank2, "rank2"), e, (C.c_uint8 * 3)(*b), 0)
+    for j in range(kh):
+        p.rows[j] = sum(1 << i for i in range(kw) if taps[j, i])
+    L = load_library()
+    if L.tr_rank_host(0, 0, None, None, C.addressof(p)) != 0:   # (an empty image: the parameter checks alone)
+        raise ValueError(L.tr_last_error().decode().replace("tr_rank_host", "rank", 1))
+    return p
+
+
+def rank_host(rgb, params):
+    """tr_rank_host: the rule of Scene.rank on the host (no GPU needed), by the inline functions k_rank shares.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from rank_params.  Returns the filtered frame and leaves
+    its arguments alone."""
+    if not isinstance(params, RankParams):
+        raise ValueError("rank_host: params must come from rank_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("rank_host: rgb [H, W, 3]")
+    out = np.empty_like(src)
+    check(load_library().tr_rank_host(src.shape[1], src.shape[0], src.ctypes.data, out.ctypes.data, C.addressof(params)))
+    return out
+
+
+def footprint_rect(kw, kh):
+    """[kh, kw] of True: every pixel of the box (kw and kh odd, 1..15)."""
+    kw, kh = int(kw), int(kh)
+    if kw % 2 == 0 or kh % 2 == 0 or not 1 <= kw <= 15 or not 1 <= kh <= 15:
+        raise ValueError("footprint_rect: kw and kh odd and 1..15")
+    return np.ones((kh, kw), bool)
+
+
+def footprint_disc(r):
+    """[2 r + 1, 2 r + 1]: the taps with dx^2 + dy^2 <= r^2 + r (r 0..7): 9 taps at r = 1, 21 at 2, 37 at 3."""
+    r = int(r)
+    if not 0 <= r <= 7:
+        raise ValueError("footprint_disc: r 0..7")
+    d = np.arange(-r, r + 1)
+    return np.add.outer(d * d, d * d) <= r * r + r
+
+
+def footprint_cross(r):
+    """[2 r + 1, 2 r + 1]: the centre row and the centre column (r 0..7), 4 r + 1 taps."""
+    r = int(r)
+    if not 0 <= r <= 7:
+        raise ValueError("footprint_cross: r 0..7")
+    f = np.zeros((2 * r + 1, 2 * r + 1), bool)
+    f[r, :] = f[:, r] = True
+    return f
+
+
+def footprint_line(length, degrees):
+    """A line of `length` pixels (odd, 1..15) through the centre at `degrees` counter-clockwise from the x axis as the
+    picture is seen: step t = -(length - 1) / 2 .. (length - 1) / 2 is the tap at dx = round(t cos), dy = -round(t sin)
+    (halves away from zero), in the smallest box that holds them."""
+    n = int(length)
+    if n % 2 == 0 or not 1 <= n <= 15:
+        raise ValueError("footprint_line: length odd and 1..15")
+    t = np.arange(-(n // 2), n // 2 + 1, dtype=np.float64)
+    a = np.deg2rad(float(degrees))
+    away = lambda v: (np.sign(v) * np.floor(np.abs(v) + 0.5)).astype(np.int64)
+    dx, dy = away(t * np.cos(a)), -away(t * np.sin(a))
+    rx, ry = int(np.abs(dx).max()), int(np.abs(dy).max())
+    f = np.zeros((2 * ry + 1, 2 * rx + 1), bool)
+    f[dy + ry, dx + rx] = True
+    return f
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -1982,6 +2102,32 @@ class Scene:
         if not isinstance(params, ConvolveParams):
             raise ValueError("get_convolved: params must come from convolve_params")
         return self._image("tr_scene_get_convolved", strict, C.addressof(params))
+
+    # --- rank (tr_scene_rank / tr_scene_get_ranked) ----------------------------------------------------
+    def rank(self, params, out=None):
+        """tr_scene_rank: the current frame through an order-statistic filter on the device -- median, erode, dilate,
+        morphological gradient, despeckle (params from rank_params; footprint_rect, footprint_disc, footprint_cross and
+        footprint_line build the usual footprints).  out=None: in place -- every later consumer (the getters, resize,
+        resolve, the sparse read-back) sees the filtered frame, z, winner words and the shadow buffer stay, calling it
+        twice filters twice (open is erode then dilate).  Otherwise `out` is a torch tensor on the scene's device or a
+        device pointer (int) to 3 * W * H bytes that overlaps no frame buffer of the scene, or an array from
+        pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().  Band scenes
+        are refused.  No depth is needed."""
+        if not isinstance(params, RankParams):
+            raise ValueError("rank: params must come from rank_params")
+        target = out.data_ptr() if hasattr(out, "data_ptr") else out
+        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < self.width * self.height * 3 or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
+        ptr = self._out_pointer(target)
+        check(load_library().tr_scene_rank(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_ranked(self, params, strict=True):
+        """tr_scene_get_ranked: the current frame filtered on the device, as an [H, W, 3] uint8 array equal to
+        rank_host(get_frame_buffer(), params) in every byte.  Synchronizes; the scene's frame stays."""
+        if not isinstance(params, RankParams):
+            raise ValueError("get_ranked: params must come from rank_params")
+        return self._image("tr_scene_get_ranked", strict, C.addressof(params))
 
     # --- YUV output (tr_scene_to_yuv / tr_scene_to_yuv_from / tr_scene_get_yuv) ------------------------
     def to_yuv(self, layout="i420", matrix="bt709", range="limited", strict=True):
