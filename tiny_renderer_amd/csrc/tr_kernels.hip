@@ -5248,41 +5248,54 @@ int launch_bloom(const BloomArgs &a, hipStream_t st)
     return 0;
 }
 
+// What launch_convolve and launch_rank share: the refusals of a stage that reads neighbours (ok), a.words, the store
+// form (k_convolve's STORE) and the LDS of the staged rows.
+struct NeighPlan {
+    bool ok;
+    int store;
+    size_t lds;
+};
+
+template <typename Args>
+static NeighPlan neigh_plan(Args &a)
+{
+    NeighPlan plan = { false, 0, (size_t)(TILE_H + 2 * (int)(a.rule.kh / 2u)) * CONV_LDS_W * 4u };
+    if (!a.fb || !a.out) return plan;
+    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return plan;
+    // `out` is never the frame that is read
+    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
+    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return plan;
+    // staging by words: four pixels at a multiple of four are three aligned words of the frame
+    a.words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u ? 1u : 0u;
+    // the stores: every share three whole 16-byte pieces of `out`, else whole 12-byte pieces at multiples of 4, else bytes
+    plan.store = a.frame.width % 16u == 0u && (uintptr_t)a.out % 16u == 0u ? 2 : a.frame.width % 4u == 0u && (uintptr_t)a.out % 4u == 0u ? 1 : 0;
+    plan.ok = true;
+    return plan;
+}
+
 int launch_convolve(const ConvolveArgs &a0, hipStream_t st)
 {
     ConvolveArgs a = a0;
     const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
     if (n_tiles == 0) return 0;
-    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
-    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
-    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    const NeighPlan plan = neigh_plan(a);
     const bool sep = (a.rule.flags & CONVOLVE_SEPARABLE) != 0u;
     const uint32_t k_max = sep ? (uint32_t)CONVOLVE_MAX_SEPARABLE : (uint32_t)CONVOLVE_MAX_GENERAL;
-    if (a.rule.kw % 2u == 0u || a.rule.kh % 2u == 0u || a.rule.kw > k_max || a.rule.kh > k_max || a.rule.shift > CONVOLVE_MAX_SHIFT ||
+    if (!plan.ok || a.rule.kw % 2u == 0u || a.rule.kh % 2u == 0u || a.rule.kw > k_max || a.rule.kh > k_max || a.rule.shift > CONVOLVE_MAX_SHIFT ||
         a.rule.edge > CONVOLVE_CLAMP || a.rule.amount > CONVOLVE_MAX_AMOUNT)
         return (int)hipErrorInvalidValue;
-    // `out` is never the frame that is read
-    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
-    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
-    // staging by words: four pixels at a multiple of four are three aligned words of the frame
-    a.words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u ? 1u : 0u;
-    // the stores: every share three whole 16-byte pieces of `out`, else whole 12-byte pieces at multiples of 4, else bytes
-    const int store = a.frame.width % 16u == 0u && (uintptr_t)a.out % 16u == 0u ? 2 : a.frame.width % 4u == 0u && (uintptr_t)a.out % 4u == 0u ? 1 : 0;
     int64_t col_sum = 0;
     for (uint32_t j = 0; sep && j < a.rule.kh; j++) col_sum += std::abs((int64_t)a.rule.weights[a.rule.kw + j]);
     a.rule.mul24 = sep && col_sum <= CONVOLVE_MAX_ROW ? 1 : 0;
-    const size_t lds = (size_t)(TILE_H + 2 * (int)(a.rule.kh / 2u)) * CONV_LDS_W * 4u + (sep ? (size_t)3 * TILE_H * CONV_LDS_W * 4u : 0u);
-    const dim3 grid(n_tiles), block(CONV_THREADS);
-#define CONV_LAUNCH(SEP_, M24_)                                                                                  \
-    {                                                                                                            \
-        if (store == 2) hipLaunchKernelGGL((k_convolve<SEP_, 2, M24_>), grid, block, lds, st, a);                \
-        else if (store == 1) hipLaunchKernelGGL((k_convolve<SEP_, 1, M24_>), grid, block, lds, st, a);           \
-        else hipLaunchKernelGGL((k_convolve<SEP_, 0, M24_>), grid, block, lds, st, a);                           \
-    }
-    if (!sep) CONV_LAUNCH(false, true)
-    else if (a.rule.mul24) CONV_LAUNCH(true, true)
-    else CONV_LAUNCH(true, false)
-#undef CONV_LAUNCH
+    const size_t lds = plan.lds + (sep ? (size_t)3 * TILE_H * CONV_LDS_W * 4u : 0u);
+    // [general, separable in 24 bits, separable in 32][STORE]
+    static constexpr void (*kernels[3][3])(ConvolveArgs) = {
+        { k_convolve<false, 0, true>, k_convolve<false, 1, true>, k_convolve<false, 2, true> },
+        { k_convolve<true, 0, true>, k_convolve<true, 1, true>, k_convolve<true, 2, true> },
+        { k_convolve<true, 0, false>, k_convolve<true, 1, false>, k_convolve<true, 2, false> },
+    };
+    hipLaunchKernelGGL(kernels[!sep ? 0 : a.rule.mul24 ? 1 : 2][plan.store], dim3(n_tiles), dim3(CONV_THREADS), lds, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }
@@ -5292,36 +5305,22 @@ int launch_rank(const RankArgs &a0, hipStream_t st)
     RankArgs a = a0;
     const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
     if (n_tiles == 0) return 0;
-    if (!a.fb || !a.out) return (int)hipErrorInvalidValue;
-    // the whole frame's tile grid (a band's halo would lie on another rank), taps inside the staged halo
-    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)a.frame.height) return (int)hipErrorInvalidValue;
+    const NeighPlan plan = neigh_plan(a);
     const RankRule &q = a.rule;
-    if (q.kw % 2u == 0u || q.kh % 2u == 0u || q.kw > RANK_MAX_SIDE || q.kh > RANK_MAX_SIDE || q.op > RANK_CLAMP_CENTRE || q.edge > RANK_CLAMP || q.n == 0u ||
-        q.n > q.kw * q.kh || q.rank > q.rank2 || q.rank2 >= q.n)
+    if (!plan.ok || q.kw % 2u == 0u || q.kh % 2u == 0u || q.kw > RANK_MAX_SIDE || q.kh > RANK_MAX_SIDE || q.op > RANK_CLAMP_CENTRE || q.edge > RANK_CLAMP ||
+        q.n == 0u || q.n > q.kw * q.kh || q.rank > q.rank2 || q.rank2 >= q.n)
         return (int)hipErrorInvalidValue;
-    // `out` is never the frame that is read
-    const size_t bytes = (size_t)a.frame.width * a.frame.height * 3u;
-    if ((const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
-    // staging by words: four pixels at a multiple of four are three aligned words of the frame
-    a.words = a.frame.width % 4u == 0u && (uintptr_t)a.fb % 4u == 0u ? 1u : 0u;
-    // the stores: every share three whole 16-byte pieces of `out`, else whole 12-byte pieces at multiples of 4, else bytes
-    const int store = a.frame.width % 16u == 0u && (uintptr_t)a.out % 16u == 0u ? 2 : a.frame.width % 4u == 0u && (uintptr_t)a.out % 4u == 0u ? 1 : 0;
     // the extremes need no selection: every rank asked for is the first or the last; bit 0 -- the minimum, bit 1 -- the maximum
     const bool extremes = (q.rank == 0u || q.rank == q.n - 1u) && (q.rank2 == 0u || q.rank2 == q.n - 1u);
     const int sel = !extremes ? 0 : ((q.rank == 0u || q.rank2 == 0u) ? 1 : 0) | ((q.rank != 0u || q.rank2 != 0u) ? 2 : 0);
-    const size_t lds = (size_t)(TILE_H + 2 * (int)(q.kh / 2u)) * CONV_LDS_W * 4u;
-    const dim3 grid(n_tiles), block(CONV_THREADS);
-#define RANK_LAUNCH(SEL_)                                                                         \
-    {                                                                                             \
-        if (store == 2) hipLaunchKernelGGL((k_rank<SEL_, 2>), grid, block, lds, st, a);           \
-        else if (store == 1) hipLaunchKernelGGL((k_rank<SEL_, 1>), grid, block, lds, st, a);      \
-        else hipLaunchKernelGGL((k_rank<SEL_, 0>), grid, block, lds, st, a);                      \
-    }
-    if (sel == 0) RANK_LAUNCH(0)
-    else if (sel == 1) RANK_LAUNCH(1)
-    else if (sel == 2) RANK_LAUNCH(2)
-    else RANK_LAUNCH(3)
-#undef RANK_LAUNCH
+    // [SEL][STORE]
+    static constexpr void (*kernels[4][3])(RankArgs) = {
+        { k_rank<0, 0>, k_rank<0, 1>, k_rank<0, 2> },
+        { k_rank<1, 0>, k_rank<1, 1>, k_rank<1, 2> },
+        { k_rank<2, 0>, k_rank<2, 1>, k_rank<2, 2> },
+        { k_rank<3, 0>, k_rank<3, 1>, k_rank<3, 2> },
+    };
+    hipLaunchKernelGGL(kernels[sel][plan.store], dim3(n_tiles), dim3(CONV_THREADS), plan.lds, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -2806,6 +2806,19 @@ int check_resolve(const tr_scene *s, uint32_t factor)
 
 size_t resolved_bytes(const tr_scene *s, uint32_t factor) { return (size_t)(s->width / factor) * (s->height / factor) * 3; }
 
+// The tail of an enqueue_*: the launch inside its timing scope, a refusal under the kernel's name, the stream no longer idle.
+template <typename Launch>
+int timed_launch(tr_scene *s, int kernel, const char *name, Launch launch)
+{
+    {
+        Timed t(s, kernel);
+        int rc = launch();
+        if (rc) return launch_status(rc, name);
+    }
+    s->quiescent = false;
+    return TR_OK;
+}
+
 // Enqueues the resolve of the current frame into `out_device` behind everything issued so far.
 int enqueue_resolve(tr_scene *s, uint32_t factor, uint8_t *out_device)
 {
@@ -2813,13 +2826,7 @@ int enqueue_resolve(tr_scene *s, uint32_t factor, uint8_t *out_device)
     if (st != TR_OK) return st;
     st = submit_pending(s);
     if (st != TR_OK) return st;
-    {
-        Timed t(s, K_RESOLVE);
-        int rc = launch_resolve(s->d_fb, out_device, s->d_fbclean, s->frame, factor, s->stream);
-        if (rc) return launch_status(rc, "k_resolve");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_RESOLVE, "k_resolve", [&] { return launch_resolve(s->d_fb, out_device, s->d_fbclean, s->frame, factor, s->stream); });
 }
 
 int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, size_t bytes)
@@ -2838,12 +2845,16 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
 //   cleared_out_of_place, while in place a cleared frame is its own result and NOTHING happens, handed_on included; the
 //   enqueue_* into the target, into the frame itself, or through the scratch frame (in_place_via_scratch); handed_on.
-//   tr_scene_get_<stage>: the same checks, then get_stage.
+//   The frame-sized stages that go through the scratch frame (depth of field, bloom, antialias, convolve, rank) call
+//   scratch_stage after their checks: it is that order from hipSetDevice on.
+//   tr_scene_get_<stage>: the same checks, then get_stage (those five: get_scratch_stage).
+//   enqueue_*: the stage's queue choice; its arguments (frame_stage_args: the five fields every such kernel takes);
+//   timed_launch -- the launch under Timed, launch_status under the kernel's name, quiescent = false.
 // A refused call has queued nothing and changed nothing, but for the read-back record of a tr_host_alloc `out` that
 // classify_out accepted.  In place a colour-clean flag of the DEVICE buffer may change; a record of a page-locked host
 // buffer (HostFlags) says what that host buffer holds, which no in-place call changes: the next read-back compares the
-// two as always.  Each enqueue_* keeps its own choice among flush_clear_color, submit_pending and depth_in_memory: that
-// choice decides whether a depth left on the chip stays there.
+// two as always.  Each enqueue_* keeps its own choice among flush_clear_color, submit_pending and depth_in_memory, written
+// out in its own function ahead of the shared calls: that choice decides whether a depth left on the chip stays there.
 
 size_t frame_bytes(const tr_scene *s) { return (size_t)s->width * s->height * 3; }
 
@@ -2947,6 +2958,18 @@ int cleared_out_of_place(tr_scene *s, void *target)
     return TR_OK;
 }
 
+// The frame, its flags and the output in a stage's kernel arguments (out_clean: null, or where the kernel writes the
+// flags of `out_device`).
+template <typename Args>
+void frame_stage_args(Args &a, const tr_scene *s, uint8_t *out_device, uint32_t *out_clean)
+{
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device;
+    a.out_clean = out_clean;
+    a.frame = s->frame;
+}
+
 // In place for a stage that reads neighbours: enqueue(out_device, out_clean) into the scene's scratch frame and flag
 // set (one pair, shared: each call leaves them free behind its two copies), then, in stream order, the colour over the
 // current frame and the flags over the frame's colour-clean flags.
@@ -2960,6 +2983,23 @@ int in_place_via_scratch(tr_scene *s, Enqueue enqueue)
     HIP_TRY(hipMemcpyAsync(s->d_fb, s->d_dof_fb, frame_bytes(s), hipMemcpyDeviceToDevice, s->stream));
     if (s->d_fbclean) HIP_TRY(hipMemcpyAsync(s->d_fbclean, s->d_dof_clean, (size_t)s->n_tiles * 4, hipMemcpyDeviceToDevice, s->stream));
     return TR_OK;
+}
+
+// tr_scene_<stage>(s, .., out) of a frame-sized stage that goes in place through the scratch frame, after the stage's
+// checks.  who / getter / verb: the entry point's words in the error texts; black_stays_black: the stage's image of a
+// black frame is black, so a logically cleared frame gives zeros out of place and is its own result in place;
+// enqueue(out_device, out_clean): the stage's enqueue_*.
+template <typename Enqueue>
+int scratch_stage(tr_scene *s, void *out, const char *who, const char *getter, const char *verb, bool black_stays_black, Enqueue enqueue)
+{
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    int st = frame_out(s, out, who, getter, verb, 0u, &target);
+    if (st != TR_OK) return st;
+    if (s->z_fb_cleared && black_stays_black) return target ? cleared_out_of_place(s, target) : TR_OK;
+    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
+    if (st == TR_OK) handed_on(s);
+    return st;
 }
 
 // The library's read-back buffer, one per scene and shared by every getter: s->d_resolved of at least `bytes` bytes,
@@ -2994,6 +3034,13 @@ int get_stage(tr_scene *s, uint8_t *rgb, size_t bytes, bool (*short_circuits)(co
     if (st == TR_OK && !skip) st = enqueue(s->d_resolved);
     if (st != TR_OK) return st;
     return finish_read_back(s, fst, rgb, s->d_resolved, bytes);
+}
+
+// tr_scene_get_<stage> of the stages of scratch_stage, after the stage's checks: the same black_stays_black and enqueue.
+template <typename Enqueue>
+int get_scratch_stage(tr_scene *s, uint8_t *rgb, bool black_stays_black, Enqueue enqueue)
+{
+    return get_stage(s, rgb, frame_bytes(s), black_stays_black ? cleared : nullptr, [&](uint8_t *o) { return enqueue(o, nullptr); });
 }
 
 // A launch on dst's stream that reads src's buffers and writes dst's: behind src's work, and src's stream behind the
@@ -4237,13 +4284,7 @@ int enqueue_accumulate(tr_scene *s, uint32_t n, const uint32_t *weights, uint32_
     a.frame = s->frame;
     a.n = n;
     a.div = accumulate_divisor(D);
-    {
-        Timed t(s, K_ACCUMULATE);
-        int rc = launch_accumulate(a, s->stream);
-        if (rc) return launch_status(rc, "k_accumulate");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_ACCUMULATE, "k_accumulate", [&] { return launch_accumulate(a, s->stream); });
 }
 
 }  // namespace
@@ -4336,20 +4377,10 @@ int enqueue_dof(tr_scene *s, const tr_dof_params *p, uint8_t *out_device, uint32
     DofArgs a = {};
     a.z = s->d_z;
     a.zclean = s->d_zclean;
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = out_clean;
-    a.frame = s->frame;
+    frame_stage_args(a, s, out_device, out_clean);
     a.show_coc = (p->flags & TR_DOF_SHOW_COC) ? 1u : 0u;
     a.rule = dof_rule(p);
-    {
-        Timed t(s, K_DOF);
-        int rc = launch_dof(a, s->stream);
-        if (rc) return launch_status(rc, "k_dof");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_DOF, "k_dof", [&] { return launch_dof(a, s->stream); });
 }
 
 }  // namespace
@@ -4360,16 +4391,8 @@ int tr_scene_depth_of_field(tr_scene *s, const tr_dof_params *p, void *out)
     int st = check_dof_params(p, "tr_scene_depth_of_field");
     if (st == TR_OK) st = check_dof_scene(s, "tr_scene_depth_of_field");
     if (st != TR_OK) return st;
-    HIP_TRY(hipSetDevice(s->device));
-    void *target = nullptr;
-    st = frame_out(s, out, "tr_scene_depth_of_field", "tr_scene_get_depth_of_field", "blurs", 0u, &target);
-    if (st != TR_OK) return st;
     // a logically cleared frame is black and nothing in it is drawn: zeros out of place, itself in place
-    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
-    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_dof(s, p, o, clean); };
-    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
-    if (st == TR_OK) handed_on(s);
-    return st;
+    return scratch_stage(s, out, "tr_scene_depth_of_field", "tr_scene_get_depth_of_field", "blurs", true, [&](uint8_t *o, uint32_t *clean) { return enqueue_dof(s, p, o, clean); });
 }
 
 int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rgb)
@@ -4379,7 +4402,7 @@ int tr_scene_get_depth_of_field(tr_scene *s, const tr_dof_params *p, uint8_t *rg
     int st = check_dof_params(p, "tr_scene_get_depth_of_field");
     if (st == TR_OK) st = check_dof_scene(s, "tr_scene_get_depth_of_field");
     if (st != TR_OK) return st;
-    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_dof(s, p, o, nullptr); });
+    return get_scratch_stage(s, rgb, true, [&](uint8_t *o, uint32_t *clean) { return enqueue_dof(s, p, o, clean); });
 }
 
 // The rule of tr_dof.h over caller's arrays, on the host.  Needs no GPU.
@@ -4449,19 +4472,9 @@ int enqueue_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *out_device, ui
     int st = submit_pending(s);
     if (st != TR_OK) return st;
     BloomArgs a = {};
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = out_clean;
-    a.frame = s->frame;
+    frame_stage_args(a, s, out_device, out_clean);
     a.rule = bloom_rule(p);
-    {
-        Timed t(s, K_BLOOM);
-        int rc = launch_bloom(a, s->stream);
-        if (rc) return launch_status(rc, "k_bloom");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_BLOOM, "k_bloom", [&] { return launch_bloom(a, s->stream); });
 }
 
 }  // namespace
@@ -4472,16 +4485,8 @@ int tr_scene_bloom(tr_scene *s, const tr_bloom_params *p, void *out)
     int st = check_bloom_params(p, "tr_scene_bloom");
     if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_bloom");
     if (st != TR_OK) return st;
-    HIP_TRY(hipSetDevice(s->device));
-    void *target = nullptr;
-    st = frame_out(s, out, "tr_scene_bloom", "tr_scene_get_bloom", "blooms", 0u, &target);
-    if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its glow: zeros out of place, itself in place
-    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
-    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_bloom(s, p, o, clean); };
-    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
-    if (st == TR_OK) handed_on(s);
-    return st;
+    return scratch_stage(s, out, "tr_scene_bloom", "tr_scene_get_bloom", "blooms", true, [&](uint8_t *o, uint32_t *clean) { return enqueue_bloom(s, p, o, clean); });
 }
 
 int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb)
@@ -4491,7 +4496,7 @@ int tr_scene_get_bloom(tr_scene *s, const tr_bloom_params *p, uint8_t *rgb)
     int st = check_bloom_params(p, "tr_scene_get_bloom");
     if (st == TR_OK) st = check_bloom_scene(s, "tr_scene_get_bloom");
     if (st != TR_OK) return st;
-    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_bloom(s, p, o, nullptr); });
+    return get_scratch_stage(s, rgb, true, [&](uint8_t *o, uint32_t *clean) { return enqueue_bloom(s, p, o, clean); });
 }
 
 // The rule of tr_bloom.h over a caller's array, on the host.  Needs no GPU.
@@ -4542,13 +4547,7 @@ int enqueue_grade(tr_scene *s, uint8_t *out_device)
     a.frame = s->frame;
     a.rule.n = s->lut_n;
     a.rule.c0 = s->lut_c0;
-    {
-        Timed t(s, K_GRADE);
-        int rc = launch_grade(a, s->stream, s->grade_cap, &s->grade_grid);
-        if (rc) return launch_status(rc, "k_grade");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_GRADE, "k_grade", [&] { return launch_grade(a, s->stream, s->grade_cap, &s->grade_grid); });
 }
 
 }  // namespace
@@ -4679,13 +4678,7 @@ int enqueue_outline(tr_scene *s, const tr_outline_params *p, uint8_t *out_device
     a.out = out_device ? out_device : s->d_fb;
     a.frame = s->frame;
     a.rule = outline_rule(p);
-    {
-        Timed t(s, K_OUTLINE);
-        int rc = launch_outline(a, s->stream);
-        if (rc) return launch_status(rc, "k_outline");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_OUTLINE, "k_outline", [&] { return launch_outline(a, s->stream); });
 }
 
 }  // namespace
@@ -4788,19 +4781,9 @@ int enqueue_aa(tr_scene *s, const tr_aa_params *p, uint8_t *out_device, uint32_t
     int st = submit_pending(s);
     if (st != TR_OK) return st;
     AaArgs a = {};
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = out_clean;
-    a.frame = s->frame;
+    frame_stage_args(a, s, out_device, out_clean);
     a.rule = aa_rule(p);
-    {
-        Timed t(s, K_AA);
-        int rc = launch_aa(a, s->stream);
-        if (rc) return launch_status(rc, "k_aa");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_AA, "k_aa", [&] { return launch_aa(a, s->stream); });
 }
 
 }  // namespace
@@ -4811,16 +4794,8 @@ int tr_scene_antialias(tr_scene *s, const tr_aa_params *p, void *out)
     int st = check_aa_params(p, "tr_scene_antialias");
     if (st == TR_OK) st = check_aa_scene(s, "tr_scene_antialias");
     if (st != TR_OK) return st;
-    HIP_TRY(hipSetDevice(s->device));
-    void *target = nullptr;
-    st = frame_out(s, out, "tr_scene_antialias", "tr_scene_get_antialiased", "filters", 0u, &target);
-    if (st != TR_OK) return st;
     // a logically cleared frame is black and has no edge: zeros out of place, itself in place
-    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
-    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_aa(s, p, o, clean); };
-    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
-    if (st == TR_OK) handed_on(s);
-    return st;
+    return scratch_stage(s, out, "tr_scene_antialias", "tr_scene_get_antialiased", "filters", true, [&](uint8_t *o, uint32_t *clean) { return enqueue_aa(s, p, o, clean); });
 }
 
 int tr_scene_get_antialiased(tr_scene *s, const tr_aa_params *p, uint8_t *rgb)
@@ -4830,7 +4805,7 @@ int tr_scene_get_antialiased(tr_scene *s, const tr_aa_params *p, uint8_t *rgb)
     int st = check_aa_params(p, "tr_scene_get_antialiased");
     if (st == TR_OK) st = check_aa_scene(s, "tr_scene_get_antialiased");
     if (st != TR_OK) return st;
-    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_aa(s, p, o, nullptr); });
+    return get_scratch_stage(s, rgb, true, [&](uint8_t *o, uint32_t *clean) { return enqueue_aa(s, p, o, clean); });
 }
 
 // The rule of tr_aa.h over a caller's array, on the host.  Needs no GPU.
@@ -4954,13 +4929,7 @@ int enqueue_resize(tr_scene *s, const tr_resize_params *p, uint8_t *out_device)
     a.y_span = s->resize.y_span;
     a.x_span = s->resize.x_span;
     a.frame = s->frame;
-    {
-        Timed t(s, K_RESIZE);
-        int rc = launch_resize(a, s->stream);
-        if (rc) return launch_status(rc, "k_resize");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_RESIZE, "k_resize", [&] { return launch_resize(a, s->stream); });
 }
 
 }  // namespace
@@ -5105,22 +5074,12 @@ int enqueue_warp(tr_scene *s, const tr_warp_params *p, uint8_t *out_device, uint
     const bool same_tiles = s->height % 16u == 0u;
     if (out_clean && !same_tiles) HIP_TRY(hipMemsetAsync(out_clean, 0, (size_t)s->n_tiles * 4, s->stream));
     WarpArgs a = {};
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = same_tiles ? out_clean : nullptr;
+    frame_stage_args(a, s, out_device, same_tiles ? out_clean : nullptr);
     a.grid = s->warp.d;
     a.out_w = s->warp.width;
     a.out_h = s->warp.height;
     a.rule = warp_rule(p);
-    a.frame = s->frame;
-    {
-        Timed t(s, K_WARP);
-        int rc = launch_warp(a, s->stream);
-        if (rc) return launch_status(rc, "k_warp");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_WARP, "k_warp", [&] { return launch_warp(a, s->stream); });
 }
 
 }  // namespace
@@ -5297,19 +5256,9 @@ int enqueue_convolve(tr_scene *s, const tr_convolve_params *p, uint8_t *out_devi
     if (st == TR_OK) st = submit_pending(s);
     if (st != TR_OK) return st;
     ConvolveArgs a = {};
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = out_clean;
-    a.frame = s->frame;
+    frame_stage_args(a, s, out_device, out_clean);
     a.rule = convolve_rule(p);
-    {
-        Timed t(s, K_CONVOLVE);
-        int rc = launch_convolve(a, s->stream);
-        if (rc) return launch_status(rc, "k_convolve");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_CONVOLVE, "k_convolve", [&] { return launch_convolve(a, s->stream); });
 }
 
 }  // namespace
@@ -5320,16 +5269,8 @@ int tr_scene_convolve(tr_scene *s, const tr_convolve_params *p, void *out)
     int st = check_convolve_params(p, "tr_scene_convolve");
     if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_convolve");
     if (st != TR_OK) return st;
-    HIP_TRY(hipSetDevice(s->device));
-    void *target = nullptr;
-    st = frame_out(s, out, "tr_scene_convolve", "tr_scene_get_convolved", "convolves", 0u, &target);
-    if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its image where the rule gives black: zeros out of place, itself in place
-    if (s->z_fb_cleared && convolve_of_black_is_black(p)) return target ? cleared_out_of_place(s, target) : TR_OK;
-    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); };
-    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
-    if (st == TR_OK) handed_on(s);
-    return st;
+    return scratch_stage(s, out, "tr_scene_convolve", "tr_scene_get_convolved", "convolves", convolve_of_black_is_black(p), [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); });
 }
 
 int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rgb)
@@ -5339,9 +5280,7 @@ int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rg
     int st = check_convolve_params(p, "tr_scene_get_convolved");
     if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_get_convolved");
     if (st != TR_OK) return st;
-    // (the predicate takes the scene alone: the parameters decide here which one is asked)
-    return get_stage(s, rgb, frame_bytes(s), convolve_of_black_is_black(p) ? cleared : nullptr,
-                     [&](uint8_t *o) { return enqueue_convolve(s, p, o, nullptr); });
+    return get_scratch_stage(s, rgb, convolve_of_black_is_black(p), [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); });
 }
 
 // The rule of tr_convolve.h over a caller's array, on the host.  Needs no GPU.
@@ -5396,19 +5335,9 @@ int enqueue_rank(tr_scene *s, const RankParams &q, uint8_t *out_device, uint32_t
     if (st == TR_OK) st = submit_pending(s);
     if (st != TR_OK) return st;
     RankArgs a = {};
-    a.fb = s->d_fb;
-    a.fbclean = s->d_fbclean;
-    a.out = out_device;
-    a.out_clean = out_clean;
-    a.frame = s->frame;
+    frame_stage_args(a, s, out_device, out_clean);
     a.rule = rank_rule(q);
-    {
-        Timed t(s, K_RANK);
-        int rc = launch_rank(a, s->stream);
-        if (rc) return launch_status(rc, "k_rank");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_RANK, "k_rank", [&] { return launch_rank(a, s->stream); });
 }
 
 }  // namespace
@@ -5420,16 +5349,8 @@ int tr_scene_rank(tr_scene *s, const tr_rank_params *p, void *out)
     int st = check_rank_params(p, "tr_scene_rank", &q);
     if (st == TR_OK) st = check_rank_scene(s, "tr_scene_rank");
     if (st != TR_OK) return st;
-    HIP_TRY(hipSetDevice(s->device));
-    void *target = nullptr;
-    st = frame_out(s, out, "tr_scene_rank", "tr_scene_get_ranked", "ranks", 0u, &target);
-    if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its image where no border colour comes in: zeros out of place, itself in place
-    if (s->z_fb_cleared && rank_of_black_is_black(q)) return target ? cleared_out_of_place(s, target) : TR_OK;
-    auto enqueue = [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); };
-    st = target ? enqueue((uint8_t *)target, nullptr) : in_place_via_scratch(s, enqueue);
-    if (st == TR_OK) handed_on(s);
-    return st;
+    return scratch_stage(s, out, "tr_scene_rank", "tr_scene_get_ranked", "ranks", rank_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); });
 }
 
 int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb)
@@ -5440,9 +5361,7 @@ int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb)
     int st = check_rank_params(p, "tr_scene_get_ranked", &q);
     if (st == TR_OK) st = check_rank_scene(s, "tr_scene_get_ranked");
     if (st != TR_OK) return st;
-    // (the predicate takes the scene alone: the parameters decide here which one is asked)
-    return get_stage(s, rgb, frame_bytes(s), rank_of_black_is_black(q) ? cleared : nullptr,
-                     [&](uint8_t *o) { return enqueue_rank(s, q, o, nullptr); });
+    return get_scratch_stage(s, rgb, rank_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); });
 }
 
 // The rule of tr_rank.h over a caller's array, on the host.  Needs no GPU.
@@ -5520,13 +5439,7 @@ int launch_yuv_on(tr_scene *s, const uint8_t *src, const uint32_t *clean, uint32
     a.height = height;
     a.ntx = (width + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W;
     a.rule = yuv_rule(p);
-    {
-        Timed t(s, K_YUV);
-        int rc = launch_yuv(a, s->stream);
-        if (rc) return launch_status(rc, "k_yuv");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    return timed_launch(s, K_YUV, "k_yuv", [&] { return launch_yuv(a, s->stream); });
 }
 
 // Enqueues the current frame's planes into `out_device` (which is no frame of the scene) behind everything issued so
@@ -5937,15 +5850,9 @@ int enqueue_stats(tr_scene *s, const tr_stats_params *p, uint8_t *out_device)
     a.frame = s->frame;
     a.rule = stats_rule(p, s->width, s->height, s->frame.band_y0, s->frame.band_y1);
     a.cleared = cleared ? 1u : 0u;
-    {
-        Timed t(s, K_STATS);
-        // (never more workgroups than slots: the device's count of compute units does not change)
-        const uint32_t cap = s->stats_cap ? std::min(s->stats_cap, s->stats_slots) : s->stats_slots;
-        int rc = launch_stats(a, (uint32_t *)out_device, s->stream, cap, &s->stats_grid);
-        if (rc) return launch_status(rc, "k_stats");
-    }
-    s->quiescent = false;
-    return TR_OK;
+    // (never more workgroups than slots: the device's count of compute units does not change)
+    const uint32_t cap = s->stats_cap ? std::min(s->stats_cap, s->stats_slots) : s->stats_slots;
+    return timed_launch(s, K_STATS, "k_stats", [&] { return launch_stats(a, (uint32_t *)out_device, s->stream, cap, &s->stats_grid); });
 }
 
 int check_stats_scene(const tr_scene *s)

@@ -310,12 +310,17 @@ def dof_params(focus, scale, max_radius=4, background_radius=0, flags=0, range=0
     return DofParams(C.sizeof(DofParams), int(max_radius), int(background_radius), int(flags), focus, range, scale)
 
 
+def _check_params(params, kind, who, maker):
+    """The refusal of `params` that `maker` did not build (who: the caller's name in the text)."""
+    if not isinstance(params, kind):
+        raise ValueError("%s: params must come from %s" % (who, maker))
+
+
 def depth_of_field_host(z, rgb, params):
     """tr_dof_host: the rule of Scene.depth_of_field on the host (no GPU needed), by the inline functions k_dof calls.
     z [H, W] float32 with row 0 = bottom (read_z_f32), rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params
     from dof_params.  Returns the blurred frame and leaves its arguments alone."""
-    if not isinstance(params, DofParams):
-        raise ValueError("depth_of_field_host: params must come from dof_params")
+    _check_params(params, DofParams, "depth_of_field_host", "dof_params")
     zz = np.ascontiguousarray(z, np.float32)
     src = np.ascontiguousarray(rgb, np.uint8)
     if zz.ndim != 2 or src.shape != zz.shape + (3,):
@@ -327,8 +332,7 @@ def depth_of_field_host(z, rgb, params):
 
 def dof_coc(params, z):
     """tr_dof_coc: the circles of confusion (uint8, z's shape) of the depths z under params (dof_params)."""
-    if not isinstance(params, DofParams):
-        raise ValueError("dof_coc: params must come from dof_params")
+    _check_params(params, DofParams, "dof_coc", "dof_params")
     zz = np.ascontiguousarray(z, np.float32)
     out = np.empty(zz.shape, np.uint8)
     check(load_library().tr_dof_coc(C.addressof(params), zz.size, zz.ctypes.data, out.ctypes.data))
@@ -380,8 +384,7 @@ def outline_host(z, rgb, params, in_place=False):
     z [H, W] float32 with row 0 = bottom (read_z_f32), rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params
     from outline_params.  Returns the outlined frame and leaves its arguments alone; in_place=True hands the library
     one buffer as rgb and out (a copy of rgb), which the rule allows."""
-    if not isinstance(params, OutlineParams):
-        raise ValueError("outline_host: params must come from outline_params")
+    _check_params(params, OutlineParams, "outline_host", "outline_params")
     zz = np.ascontiguousarray(z, np.float32)
     src = np.ascontiguousarray(rgb, np.uint8)
     if zz.ndim != 2 or src.shape != zz.shape + (3,):
@@ -395,8 +398,7 @@ def outline_host(z, rgb, params, in_place=False):
 def outline_kinds(z, params):
     """tr_outline_kinds: the kind bits (OUTLINE_SIL 1, OUTLINE_STEP 2, OUTLINE_CREASE 4; uint8, z's shape and orientation)
     of every pixel of the depths z [H, W] under params (outline_params) -- for choosing depth_step and crease."""
-    if not isinstance(params, OutlineParams):
-        raise ValueError("outline_kinds: params must come from outline_params")
+    _check_params(params, OutlineParams, "outline_kinds", "outline_params")
     zz = np.ascontiguousarray(z, np.float32)
     if zz.ndim != 2:
         raise ValueError("outline_kinds: z [H, W]")
@@ -438,8 +440,7 @@ def aa_host(rgb, params):
     """tr_aa_host: the rule of Scene.antialias on the host (no GPU needed), by the inline functions k_aa calls.  rgb
     [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from aa_params.  Returns the filtered frame and leaves its
     arguments alone."""
-    if not isinstance(params, AaParams):
-        raise ValueError("aa_host: params must come from aa_params")
+    _check_params(params, AaParams, "aa_host", "aa_params")
     src = np.ascontiguousarray(rgb, np.uint8)
     if src.ndim != 3 or src.shape[2] != 3:
         raise ValueError("aa_host: rgb [H, W, 3]")
@@ -831,8 +832,7 @@ def warp_host(rgb, grid, width, height, params):
     src = np.ascontiguousarray(rgb, np.uint8)
     if src.ndim != 3 or src.shape[2] != 3:
         raise ValueError("tr_warp_host: rgb [H, W, 3]")
-    if not isinstance(params, WarpParams):
-        raise ValueError("tr_warp_host: params must come from warp_params")
+    _check_params(params, WarpParams, "tr_warp_host", "warp_params")
     g = _warp_grid(grid, width, height, "tr_warp_host")
     out = np.empty((int(height), int(width), 3), np.uint8)
     check(load_library().tr_warp_host(src.shape[1], src.shape[0], src.ctypes.data, int(width), int(height), g.shape[0], g.ctypes.data,
@@ -984,8 +984,7 @@ def convolve_host(rgb, params):
     """tr_convolve_host: the rule of Scene.convolve on the host (no GPU needed), by the inline functions k_convolve calls.
     rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from convolve_params.  Returns the filtered frame and
     leaves its arguments alone."""
-    if not isinstance(params, ConvolveParams):
-        raise ValueError("convolve_host: params must come from convolve_params")
+    _check_params(params, ConvolveParams, "convolve_host", "convolve_params")
     src = np.ascontiguousarray(rgb, np.uint8)
     if src.ndim != 3 or src.shape[2] != 3:
         raise ValueError("convolve_host: rgb [H, W, 3]")
@@ -1131,8 +1130,7 @@ def rank_host(rgb, params):
     """tr_rank_host: the rule of Scene.rank on the host (no GPU needed), by the inline functions k_rank shares.  rgb
     [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from rank_params.  Returns the filtered frame and leaves
     its arguments alone."""
-    if not isinstance(params, RankParams):
-        raise ValueError("rank_host: params must come from rank_params")
+    _check_params(params, RankParams, "rank_host", "rank_params")
     src = np.ascontiguousarray(rgb, np.uint8)
     if src.ndim != 3 or src.shape[2] != 3:
         raise ValueError("rank_host: rgb [H, W, 3]")
@@ -1217,8 +1215,7 @@ def bloom_host(rgb, params):
     """tr_bloom_host: the rule of Scene.bloom on the host (no GPU needed), by the inline functions k_bloom calls.  rgb
     [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from bloom_params.  Returns the bloomed frame and leaves
     its arguments alone."""
-    if not isinstance(params, BloomParams):
-        raise ValueError("bloom_host: params must come from bloom_params")
+    _check_params(params, BloomParams, "bloom_host", "bloom_params")
     src = np.ascontiguousarray(rgb, np.uint8)
     if src.ndim != 3 or src.shape[2] != 3:
         raise ValueError("bloom_host: rgb [H, W, 3]")
@@ -1764,6 +1761,15 @@ class Scene:
             return out.ctypes.data
         return int(out)
 
+    def _target_pointer(self, out, tensor_text, name="out", shape="[H, W, 3]", source="pinned_frame", nbytes=None):
+        """_out_pointer of a stage that takes a torch tensor too: one of at least `nbytes` contiguous bytes gives its
+        address, any other tensor a ValueError of tensor_text."""
+        if hasattr(out, "data_ptr"):
+            if out.numel() * out.element_size() < (self.width * self.height * 3 if nbytes is None else nbytes) or not out.is_contiguous():
+                raise ValueError(tensor_text)
+            return out.data_ptr()
+        return self._out_pointer(out, name, shape, source, nbytes)
+
     def get_frame_buffer(self, strict=True):
         return self._image("tr_scene_get_frame_buffer", strict)
 
@@ -1901,8 +1907,7 @@ class Scene:
         device pointer (int) to 3 * W * H bytes that overlaps no frame buffer of the scene, or an array from
         pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().  Band
         scenes are refused.  store_depth=True avoids the depth-only repeat of the frame's pass."""
-        if not isinstance(params, DofParams):
-            raise ValueError("depth_of_field: params must come from dof_params")
+        _check_params(params, DofParams, "depth_of_field", "dof_params")
         ptr = self._out_pointer(out)
         check(load_library().tr_scene_depth_of_field(self._h, C.addressof(params), ptr))
         return out
@@ -1910,8 +1915,7 @@ class Scene:
     def get_depth_of_field(self, params, strict=True):
         """tr_scene_get_depth_of_field: the current frame blurred on the device, as an [H, W, 3] uint8 array.
         Synchronizes; the scene's frame stays unblurred."""
-        if not isinstance(params, DofParams):
-            raise ValueError("get_depth_of_field: params must come from dof_params")
+        _check_params(params, DofParams, "get_depth_of_field", "dof_params")
         return self._image("tr_scene_get_depth_of_field", strict, C.addressof(params))
 
     # --- bloom (tr_scene_bloom / tr_scene_get_bloom) -------------------------------------------------
@@ -1922,8 +1926,7 @@ class Scene:
         calling it twice blooms twice.  Otherwise `out` is a device pointer (int) to 3 * W * H bytes that overlaps no frame
         buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the
         result is there after sync().  Band scenes are refused.  No depth is needed."""
-        if not isinstance(params, BloomParams):
-            raise ValueError("bloom: params must come from bloom_params")
+        _check_params(params, BloomParams, "bloom", "bloom_params")
         ptr = self._out_pointer(out)
         check(load_library().tr_scene_bloom(self._h, C.addressof(params), ptr))
         return out
@@ -1931,8 +1934,7 @@ class Scene:
     def get_bloom(self, params, strict=True):
         """tr_scene_get_bloom: the current frame bloomed on the device, as an [H, W, 3] uint8 array.  Synchronizes; the
         scene's frame stays unbloomed."""
-        if not isinstance(params, BloomParams):
-            raise ValueError("get_bloom: params must come from bloom_params")
+        _check_params(params, BloomParams, "get_bloom", "bloom_params")
         return self._image("tr_scene_get_bloom", strict, C.addressof(params))
 
     # --- colour grading (tr_scene_set_lut / tr_scene_grade / tr_scene_get_graded) ---------------------
@@ -1977,8 +1979,7 @@ class Scene:
         every frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.
         Asynchronous: the result is there after sync().  Band scenes are refused.  store_depth=True avoids the
         depth-only repeat of the frame's pass."""
-        if not isinstance(params, OutlineParams):
-            raise ValueError("outline: params must come from outline_params")
+        _check_params(params, OutlineParams, "outline", "outline_params")
         ptr = self._out_pointer(out)
         check(load_library().tr_scene_outline(self._h, C.addressof(params), ptr))
         return out
@@ -1986,8 +1987,7 @@ class Scene:
     def get_outlined(self, params, strict=True):
         """tr_scene_get_outlined: the current frame outlined on the device, as an [H, W, 3] uint8 array.  Synchronizes;
         the scene's frame stays as it is."""
-        if not isinstance(params, OutlineParams):
-            raise ValueError("get_outlined: params must come from outline_params")
+        _check_params(params, OutlineParams, "get_outlined", "outline_params")
         return self._image("tr_scene_get_outlined", strict, C.addressof(params))
 
     # --- edge anti-aliasing (tr_scene_antialias / tr_scene_get_antialiased) ---------------------------
@@ -1998,8 +1998,7 @@ class Scene:
         twice.  Otherwise `out` is a device pointer (int) to 3 * W * H bytes apart from every frame buffer of the scene,
         or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after
         sync().  Band scenes are refused.  No depth is read."""
-        if not isinstance(params, AaParams):
-            raise ValueError("antialias: params must come from aa_params")
+        _check_params(params, AaParams, "antialias", "aa_params")
         ptr = self._out_pointer(out)
         check(load_library().tr_scene_antialias(self._h, C.addressof(params), ptr))
         return out
@@ -2007,8 +2006,7 @@ class Scene:
     def get_antialiased(self, params, strict=True):
         """tr_scene_get_antialiased: the current frame filtered on the device, as an [H, W, 3] uint8 array.  Synchronizes;
         the scene's frame stays as it is."""
-        if not isinstance(params, AaParams):
-            raise ValueError("get_antialiased: params must come from aa_params")
+        _check_params(params, AaParams, "get_antialiased", "aa_params")
         return self._image("tr_scene_get_antialiased", strict, C.addressof(params))
 
     # --- resize (tr_scene_resize / tr_scene_get_resized) -----------------------------------------------
@@ -2031,10 +2029,7 @@ class Scene:
         p = resize_params(self.width, self.height, width, height, filter, "tr_scene_resize")
         if out is None:
             raise ValueError("tr_scene_resize: out == NULL (the output is no frame of the scene: there is no in-place form)")
-        target = out.data_ptr() if hasattr(out, "data_ptr") else out
-        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < p.width * p.height * 3 or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
-        ptr = self._out_pointer(target, "out", "[height, width, 3]", "pinned_resized", p.width * p.height * 3)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes", "out", "[height, width, 3]", "pinned_resized", p.width * p.height * 3)
         check(load_library().tr_scene_resize(self._h, C.addressof(p), ptr))
         return out
 
@@ -2059,13 +2054,9 @@ class Scene:
         tensor on the scene's device or a device pointer (int) to 3 * width * height bytes (the grid's size) apart from
         every frame buffer of the scene, or an array from pinned_warped; every byte of it is written and the scene's frame
         stays.  Asynchronous: the result is there after sync().  Band scenes are refused.  No depth is needed."""
-        if not isinstance(params, WarpParams):
-            raise ValueError("warp: params must come from warp_params")
+        _check_params(params, WarpParams, "warp", "warp_params")
         w, h = getattr(self, "_warp_size", (self.width, self.height))
-        target = out.data_ptr() if hasattr(out, "data_ptr") else out
-        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < w * h * 3 or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
-        ptr = self._out_pointer(target, "out", "[height, width, 3]", "pinned_warped", w * h * 3)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes", "out", "[height, width, 3]", "pinned_warped", w * h * 3)
         check(load_library().tr_scene_warp(self._h, C.addressof(params), ptr))
         return out
 
@@ -2073,8 +2064,7 @@ class Scene:
         """tr_scene_get_warped: the current frame warped on the device, as a [height, width, 3] uint8 array of the grid's
         size, equal to warp_host(get_frame_buffer(), grid, width, height, params) in every byte.  Synchronizes; the scene's
         frame stays."""
-        if not isinstance(params, WarpParams):
-            raise ValueError("get_warped: params must come from warp_params")
+        _check_params(params, WarpParams, "get_warped", "warp_params")
         w, h = getattr(self, "_warp_size", (self.width, self.height))
         return self._image("tr_scene_get_warped", strict, C.addressof(params), out=np.empty((h, w, 3), np.uint8))
 
@@ -2087,20 +2077,15 @@ class Scene:
         filters twice.  Otherwise `out` is a torch tensor on the scene's device or a device pointer (int) to 3 * W * H
         bytes that overlaps no frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it
         is.  Asynchronous: the result is there after sync().  Band scenes are refused.  No depth is needed."""
-        if not isinstance(params, ConvolveParams):
-            raise ValueError("convolve: params must come from convolve_params")
-        target = out.data_ptr() if hasattr(out, "data_ptr") else out
-        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < self.width * self.height * 3 or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
-        ptr = self._out_pointer(target)
+        _check_params(params, ConvolveParams, "convolve", "convolve_params")
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
         check(load_library().tr_scene_convolve(self._h, C.addressof(params), ptr))
         return out
 
     def get_convolved(self, params, strict=True):
         """tr_scene_get_convolved: the current frame filtered on the device, as an [H, W, 3] uint8 array equal to
         convolve_host(get_frame_buffer(), params) in every byte.  Synchronizes; the scene's frame stays."""
-        if not isinstance(params, ConvolveParams):
-            raise ValueError("get_convolved: params must come from convolve_params")
+        _check_params(params, ConvolveParams, "get_convolved", "convolve_params")
         return self._image("tr_scene_get_convolved", strict, C.addressof(params))
 
     # --- rank (tr_scene_rank / tr_scene_get_ranked) ----------------------------------------------------
@@ -2113,20 +2098,15 @@ class Scene:
         device pointer (int) to 3 * W * H bytes that overlaps no frame buffer of the scene, or an array from
         pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().  Band scenes
         are refused.  No depth is needed."""
-        if not isinstance(params, RankParams):
-            raise ValueError("rank: params must come from rank_params")
-        target = out.data_ptr() if hasattr(out, "data_ptr") else out
-        if hasattr(out, "data_ptr") and (out.numel() * out.element_size() < self.width * self.height * 3 or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous tensor of at least 3 * width * height bytes")
-        ptr = self._out_pointer(target)
+        _check_params(params, RankParams, "rank", "rank_params")
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
         check(load_library().tr_scene_rank(self._h, C.addressof(params), ptr))
         return out
 
     def get_ranked(self, params, strict=True):
         """tr_scene_get_ranked: the current frame filtered on the device, as an [H, W, 3] uint8 array equal to
         rank_host(get_frame_buffer(), params) in every byte.  Synchronizes; the scene's frame stays."""
-        if not isinstance(params, RankParams):
-            raise ValueError("get_ranked: params must come from rank_params")
+        _check_params(params, RankParams, "get_ranked", "rank_params")
         return self._image("tr_scene_get_ranked", strict, C.addressof(params))
 
     # --- YUV output (tr_scene_to_yuv / tr_scene_to_yuv_from / tr_scene_get_yuv) ------------------------
@@ -2146,11 +2126,8 @@ class Scene:
     def _yuv_target(self, target, nbytes, who):
         if target is None:
             raise ValueError("%s: out == NULL (there is no in-place form)" % who)
-        if hasattr(target, "data_ptr"):
-            if target.numel() * target.element_size() < nbytes or not target.is_contiguous():
-                raise ValueError("%s: target must be a contiguous tensor of at least yuv_bytes bytes" % who)
-            return target.data_ptr()
-        return self._out_pointer(target, "target", "flat yuv_bytes", "pinned_yuv", nbytes)
+        text = "%s: target must be a contiguous tensor of at least yuv_bytes bytes" % who
+        return self._target_pointer(target, text, "target", "flat yuv_bytes", "pinned_yuv", nbytes)
 
     def to_yuv_into(self, target, layout="i420", matrix="bt709", range="limited"):
         """tr_scene_to_yuv: enqueue the conversion of the current frame behind the renders issued so far; the planes are
