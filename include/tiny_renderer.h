@@ -1329,6 +1329,69 @@ int tr_scene_get_layered(tr_scene *s, const tr_layer_params *p, const void *imag
 int tr_layer_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z /* NULL without a WHERE flag */,
                   const tr_layer_params *p, const uint8_t *image, uint8_t *out /* may be rgb */);
 
+/* Depth ramp: the scene's CURRENT frame coloured by its own depth on the device -- fog with any falloff, a depth cue
+ * (MULTIPLY), a grey or false-colour depth view, contour bands, a depth slice or matte, a glow by distance (ADD): each
+ * is only another table.  One rule for every pointwise depth operation, as tr_scene_grade is for pointwise colour.
+ * The table holds n entries of rgba8, n = 2..TR_RAMP_MAX_N; entry k is rgba[4 k .. 4 k + 3].  For a pixel with depth z
+ * (what tr_scene_read_z_f32 returns, index x + y * width, y up) and stored colour d:
+ *   position  bits(z) == bits(f32::MIN): nothing is drawn there; the pixel takes no position and the entry `undrawn`
+ *             (r in bits 0..7, g in 8..15, b in 16..23, alpha in 24..31).  Otherwise p = (fl(fl(z - z0) * scale)) as u32:
+ *             every f32 operation rounds once, `as u32` truncates, saturates and takes NaN and negatives to 0.  p counts
+ *             1/256 of a table step.  scale may be negative: nearer is LARGER in this renderer, so a ramp that grows with
+ *             distance has scale < 0.  With pmax = (n - 1) * 256: p = min(p, pmax); with TR_RAMP_REPEAT p = p % pmax.
+ *             i = p >> 8, f = p & 255, j = min(i + 1, n - 1).
+ *   entry     per channel c of r, g, b, a: e_c = (E_i[c] * (256 - f) + E_j[c] * f + 128) >> 8.
+ *   blend     coverage cov = e_a * opacity, opacity 0..256; the output is the layer rule's (above): b from `mode`
+ *             (TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE) of s = e_rgb and d, then (b cov + d (65280 - cov) + 32640) / 65280.
+ * So cov == 0 leaves d; alpha 255 at opacity 256 under NORMAL gives the entry's colour exactly (a depth view); an
+ * `undrawn` alpha of 0 leaves the background alone, a fog-coloured `undrawn` with alpha 255 fogs it out.  Only colour
+ * changes: z, winner words and the shadow buffer stay.  A pixel depends on itself alone: the rule works in place. */
+#define TR_RAMP_MAX_N 1024
+#define TR_RAMP_REPEAT 0x1u
+typedef struct tr_ramp_params {
+    float z0;          /* the depth of position 0; finite */
+    float scale;       /* positions (1/256 of a table step) per unit of depth; finite, not 0, either sign */
+    uint32_t mode;     /* TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE */
+    uint32_t opacity;  /* 0..256 */
+    uint32_t undrawn;  /* the entry of a pixel that is not drawn: r | g << 8 | b << 16 | alpha << 24 */
+    uint32_t flags;    /* TR_RAMP_REPEAT or 0 */
+    uint32_t reserved[2]; /* 0 */
+} tr_ramp_params;
+/* Sets (copies) the scene's ramp table and returns when the copy is done; changing the table waits for the scene's queued
+ * work first (frames issued so far keep the table they were issued under), like tr_scene_set_lut.  n == 0 drops the table
+ * (rgba may then be NULL).  TR_E_INVALID with a tr_last_error text, nothing changed: a NULL scene, n == 1,
+ * n > TR_RAMP_MAX_N, NULL rgba with n > 0. */
+int tr_scene_set_ramp(tr_scene *s, uint32_t n, const uint8_t *rgba /* 4*n, host */);
+/* Ramps the current frame.  Asynchronous and ordered like tr_scene_layer: frames held back are submitted, a pending clear
+ * is made real, a depth left on the chip is made real (the stage always reads depth), k_ramp is enqueued on the scene's
+ * stream; the result is there after tr_scene_sync, and the scene's passes issued so far count as handed on.
+ * out == NULL: in place, by the kernel itself -- no scratch frame, no copy.  A 128 x 16 tile in which nothing is drawn
+ * loads no depth; with an `undrawn` coverage of 0 it is not touched.  A tile whose colour fast-clear flag is up counts as
+ * zeros without a load and is stored whole with its flag lowered (MULTIPLY and DARKEN leave it black behind its flag).
+ * Otherwise out: 3 W H bytes of device memory at any byte address or memory from tr_host_alloc, apart from every frame
+ * buffer of the scene; every byte of it is written and the scene's frame stays as it is.  A logically cleared scene is
+ * `undrawn` over black everywhere: where that is black nothing runs (zeros out of place, nothing in place).
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene or params;
+ * z0 not finite; scale not finite or 0; mode > TR_LAYER_DIFFERENCE; opacity > 256; an unknown flag; reserved not 0; a
+ * scene without a table; a BAND scene (tr_options.band_row0/1); `out` that is ordinary host memory, a pinned block that
+ * is too small, or overlaps a frame buffer of the scene. */
+int tr_scene_ramp(tr_scene *s, const tr_ramp_params *p, void *out /* or NULL */);
+/* The ramped frame into any host memory (3 W H bytes): waits for the scene first, ramps into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_layered.  The scene's frame stays as it is. */
+int tr_scene_get_ramped(tr_scene *s, const tr_ramp_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_ramp calls.  rgb and out: 3 * width * height
+ * bytes, row 0 = top; out may be rgb.  z: width * height floats, index x + y * width with y UP.  table: 4 * n bytes.  The
+ * same parameter checks; n must be 2..TR_RAMP_MAX_N, width and height at least 1. */
+int tr_ramp_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_ramp_params *p, uint32_t n,
+                 const uint8_t *table, uint8_t *out /* may be rgb */);
+/* positions[k] = p of the depth z[k] under the parameters and a table of n entries -- after the clamp or the REPEAT --,
+ * 0xFFFFFFFF for a depth that is not drawn: the means to choose z0 and scale, as tr_dof_coc is for a focus. */
+int tr_ramp_positions(const tr_ramp_params *p, uint32_t n, uint32_t count, const float *z, uint32_t *positions);
+/* Diagnostic, as tr_scene_debug_grade_grid: k_ramp's workgroups are persistent; every later k_ramp launch of the scene
+ * starts at most `cap` of them (0: no cap, the default), so that each walks more tiles.  The result does not change.
+ * Returns the number of workgroups of the scene's most recent k_ramp launch (0: there has been none). */
+int tr_scene_debug_ramp_grid(tr_scene *s, uint32_t cap);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

@@ -185,6 +185,12 @@ SYMBOLS = {
     "tr_scene_layer_from_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_layered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_layer_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_set_ramp": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_ramp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_ramped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_ramp_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_ramp_positions": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_debug_ramp_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -164,6 +164,20 @@ def main(argv=None):
                     help="layer: a picture, a colour or a gradient from the top colour to the bottom one behind the model, blended "
                          "on the GPU where nothing is drawn (Scene.layer, where=\"undrawn\"; after --with and --ao, before the "
                          "depth-of-field and bloom options)")
+    ap.add_argument("--fog", default=None, metavar="R,G,B",
+                    help="depth ramp: fog of that colour, thickening with distance, blended into the model on the GPU (Scene.ramp "
+                         "through ramp_fog; after --with, --ao and --backdrop, before the depth-of-field and bloom options)")
+    ap.add_argument("--fog-kind", default="linear", choices=("linear", "exp", "exp2"), help="with --fog: the falloff (default linear)")
+    ap.add_argument("--fog-density", type=float, default=2.0, metavar="D", help="with --fog and an exponential --fog-kind: the density (default 2)")
+    ap.add_argument("--fog-span", default="auto", metavar="NEAR,FAR|auto",
+                    help="with --fog, --depth-view and --depth-contours: the depths where the ramp starts and where it ends (nearer is "
+                         "larger), or auto: the nearest and farthest drawn depth, found on the GPU (ramp_span_auto; default)")
+    ap.add_argument("--fog-background", action="store_true", help="with --fog: fog out the pixels where nothing is drawn, too")
+    ap.add_argument("--depth-view", default=None, choices=("grey", "colour"),
+                    help="depth ramp: the model coloured by its depth, white (near) to black or through false colours (Scene.ramp "
+                         "through ramp_grey / ramp_false_colour; in the place of --fog's, before it)")
+    ap.add_argument("--depth-contours", type=int, default=None, metavar="N",
+                    help="depth ramp: N black contour bands over the span (1..128; ramp_contours; after --depth-view, before --fog)")
     ap.add_argument("--overlay", default=None, metavar="FILE.tga",
                     help="layer: a picture blended over the finished frame on the GPU (Scene.layer; after the convolve options, "
                          "before --vignette, --out-size and y4m output)")
@@ -239,6 +253,30 @@ def main(argv=None):
                 args.overlay_at = at
             if args.vignette is not None and not 0 <= args.vignette <= 255:
                 raise ValueError("--vignette takes 0..255")
+        except ValueError as e:
+            ap.error(str(e))
+    args.fog_colour = None
+    if args.fog is None and (args.fog_kind != "linear" or args.fog_density != 2.0 or args.fog_background):
+        ap.error("--fog-kind, --fog-density and --fog-background go with --fog R,G,B")
+    if args.fog is None and args.depth_view is None and args.depth_contours is None and args.fog_span != "auto":
+        ap.error("--fog-span goes with --fog, --depth-view or --depth-contours")
+    if args.fog is not None or args.depth_view is not None or args.depth_contours is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--fog, --depth-view and --depth-contours work on the frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        try:
+            if args.fog is not None:
+                args.fog_colour = tuple(int(v) for v in args.fog.split(","))
+                if len(args.fog_colour) != 3 or min(args.fog_colour) < 0 or max(args.fog_colour) > 255:
+                    raise ValueError("--fog takes R,G,B with values 0..255")
+                if not args.fog_density > 0.0:
+                    raise ValueError("--fog-density must be positive")
+            if args.depth_contours is not None and not 1 <= args.depth_contours <= 128:
+                raise ValueError("--depth-contours takes 1..128")
+            if args.fog_span != "auto":
+                span = [float(v) for v in args.fog_span.split(",")]
+                if len(span) != 2 or span[0] == span[1]:
+                    raise ValueError("--fog-span takes NEAR,FAR (two different depths) or auto")
+                args.fog_span = span
         except ValueError as e:
             ap.error(str(e))
     args.outline_params = None
@@ -683,6 +721,22 @@ def _post(args, T, scene, say):
         spec = args.backdrop_spec
         back = _pinned_layer(scene, "backdrop", lambda: T.load_tga(spec) if isinstance(spec, str) else T.layer_gradient(scene.width, scene.height, spec[0], spec[1]))
         scene.layer(back, where="undrawn")
+    if args.fog_colour is not None or args.depth_view is not None or args.depth_contours is not None:
+        # in place, under the blur and the bloom; a frame with nothing drawn has no span and only its background to fog
+        try:
+            z0, scale = T.ramp_span_auto(scene, 256) if args.fog_span == "auto" else T.ramp_span(args.fog_span[0], args.fog_span[1], 256)
+        except ValueError as e:
+            say("depth ramp --- %s: the span is 1,0" % e)
+            z0, scale = T.ramp_span(1.0, 0.0, 256)
+        if args.depth_view is not None:
+            scene.set_ramp(T.ramp_grey(256)[::-1].copy() if args.depth_view == "grey" else T.ramp_false_colour(256))
+            scene.ramp(z0, scale)
+        if args.depth_contours is not None:
+            scene.set_ramp(T.ramp_contours(256, 256 // args.depth_contours))
+            scene.ramp(z0, scale)
+        if args.fog_colour is not None:
+            scene.set_ramp(T.ramp_fog(args.fog_colour, 256, args.fog_kind, args.fog_density))
+            scene.ramp(z0, scale, undrawn=args.fog_colour + ((255,) if args.fog_background else (0,)))
     if args.dof_autofocus:
         # the median depth of what is drawn in the central quarter; a picture with nothing there stays sharp
         w, h = scene.width, scene.height

@@ -15,6 +15,7 @@
 #include "tr_bloom.h"
 #include "tr_grade.h"
 #include "tr_layer.h"
+#include "tr_ramp.h"
 #include "tr_morph.h"
 #include "tr_outline.h"
 #include "tr_pack.h"
@@ -135,6 +136,12 @@ int launch_yuv(const YuvArgs &a, hipStream_t st);
 // rest is copied, a flagged tile as zeros): k_layer.  The whole frame only (no band); z and a.zclean are read only with
 // a WHERE flag.  a.total, a.c* and a.g* are set here.
 int launch_layer(const LayerArgs &a, bool from_scene, hipStream_t st);
+// Depth ramp: a.fb blended with the entries of the table a.table (a.rule.n packed rgba entries, padded to whole 16-byte
+// pieces, 16-byte aligned) chosen by a.z, into a.out -- a.fb itself or a buffer apart from it, at any byte address -- by
+// the rule of tr_ramp.h, through the frame's fast-clear flags of z and of colour: k_ramp, persistent workgroups.  The
+// whole frame only (no band); the caller has made the depth real.  a.lower: null, or a.fbclean (in place): the flags of
+// the flagged tiles stored whole come down.  cap and *grid as for launch_grade (tr_scene_debug_ramp_grid).
+int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
 // Convolve: a.fb filtered through the integer kernel a.rule into a.out (which does not overlap it) by the rule of
 // tr_convolve.h, through the scene's colour fast-clear flags: k_convolve.  The whole frame only (no band); no depth is
 // read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile

@@ -3415,6 +3415,150 @@ __global__ __launch_bounds__(LAYER_THREADS) void k_layer(LayerArgs a)
     }
 }
 
+// Depth ramp (tr_scene_ramp): every pixel of the frame blended with the entry of the scene's 1-D rgba table that its own
+// depth chooses, into `out`, which may BE the frame (a pixel depends on itself alone); tr_ramp.h has the rule.  k_grade's
+// form: PERSISTENT workgroups -- as many as the machine holds at once, never more than there are tiles -- that stage the
+// table (at most 4 KB) into LDS once and walk the 128 x 16 tiles of the frame under k_grade's permutation of a row's
+// columns.  Staging per tile would add up to 4 KB to the 14 KB of colour and depth a tile moves.
+//   * a unit is four pixels of a row: twelve bytes of colour and sixteen of depth; a lane takes two units of a tile, eight
+//     rows apart.  WORDS: width % 4 == 0, fb and out 4-byte and z 16-byte aligned (the launcher checks): three aligned
+//     words and one float4; otherwise guarded bytes and scalar z loads.  z is indexed y up, the frame's rows top down;
+//   * the tile's z flag is workgroup-uniform (one scalar word).  Raised, nothing is drawn in the tile: no z is loaded,
+//     the table is not needed (a workgroup whose tiles are all empty never stages it) and every pixel takes `undrawn`.
+//     Where undrawn's coverage is 0 the tile is unchanged: in place it is not touched, out of place it is copied.  It is
+//     the z flag that says "not drawn", never the colour flag;
+//   * the tile's colour flag is workgroup-uniform too: raised, d = 0 without a load.  In place such a tile stays black
+//     behind its flag under MULTIPLY and DARKEN; under any other mode it is stored whole and lane 0 lowers the flag
+//     behind a barrier (every wave has read it by then) -- k_layer's rule;
+//   * the mode and REPEAT are workgroup-uniform: one scalar switch a unit around the arithmetic of its four pixels, and a
+//     `%` only under REPEAT.  A pixel that is not drawn computes a position like any other (the cast saturates, the clamp
+//     keeps the index inside the table) and then takes `undrawn`: no divergence.
+// z, winner words, the shadow buffer and every flag but the one lowered are left alone.  No atomics, no scratch; LDS is
+// dynamic only (its base stays 16-byte aligned).
+constexpr int RAMP_THREADS = 256, RAMP_UNITS = TILE_W * TILE_H / 4 / RAMP_THREADS;
+constexpr int RAMP_MAX_PER_CU = 8;  // workgroups of 256 lanes a CU holds by its waves (8 x 4 KB of LDS at most)
+
+template <uint32_t MODE>
+__device__ __forceinline__ void ramp_unit(uint32_t d[4], const uint32_t e[4], uint32_t opacity, int32_t n_px)
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (i < n_px) d[i] = layer_px<MODE>(e[i], d[i], ramp_coverage(e[i], opacity));
+}
+
+template <bool WORDS>
+__global__ __launch_bounds__(RAMP_THREADS) void k_ramp(RampArgs a)
+{
+    static_assert(TILE_W == 128 && RAMP_UNITS == 2 && TILE_H == 16, "32 units to a row of a tile, two rounds of eight rows");
+    extern __shared__ __align__(16) uint32_t s_ramp[];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t ntx = a.frame.ntx, n_tiles = a.frame.ntx * a.frame.nty, G = gridDim.x;
+    const RampRule q = a.rule;
+    const bool in_place = a.out == a.fb;
+    const uint32_t und_cov = ramp_coverage(q.undrawn, q.opacity);
+    const bool keeps_black = q.mode == LAYER_MULTIPLY || q.mode == LAYER_DARKEN;
+    bool staged = false;
+    for (uint32_t k = blockIdx.x; k < n_tiles; k += G) {
+        const uint32_t ty = k / ntx, tx = (k % ntx + 5u * ty + 13u * (ty * ntx / G)) % ntx;
+        const uint32_t t = ty * ntx + tx;
+        const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+        const bool empty = a.zclean[t] != 0u;                           // (workgroup-uniform) nothing is drawn in the tile
+        const bool blend = !empty || und_cov != 0u;
+        if (in_place && (!blend || (clean && keeps_black))) continue;
+        if (!empty && !staged) {  // (workgroup-uniform: the barrier is reached by all or none)
+            const uint32_t pieces = (q.n + 3u) / 4u;  // (the device table is padded to whole pieces)
+            for (uint32_t i = threadIdx.x; i < pieces; i += RAMP_THREADS)
+                reinterpret_cast<uint4 *>(s_ramp)[i] = reinterpret_cast<const uint4 *>(a.table)[i];
+            __syncthreads();
+            staged = true;
+        }
+        const int32_t x = (int32_t)tx * TILE_W + 4 * (int32_t)(threadIdx.x % 32u);
+        const int32_t y_first = (int32_t)ty * TILE_H + (int32_t)(threadIdx.x / 32u);
+        const int32_t n_px = WORDS ? 4 : min(4, W - x);  // (WORDS: 4, or the unit is outside)
+        bool inside[RAMP_UNITS];
+        size_t ci[RAMP_UNITS];
+        uint32_t d[RAMP_UNITS][4];
+        float zv[RAMP_UNITS][4];
+        // both units' loads first, then the arithmetic
+#pragma unroll
+        for (int h = 0; h < RAMP_UNITS; h++) {
+            const int32_t y = y_first + 8 * h;
+            inside[h] = x < W && y < H;
+            ci[h] = inside[h] ? ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; i++) d[h][i] = 0u, zv[h][i] = 0.0f;
+            if (!inside[h]) continue;
+            if (!clean) {
+                const uint8_t *c = a.fb + ci[h];
+                if (WORDS) {
+                    const uint32_t *cw = reinterpret_cast<const uint32_t *>(c);
+                    const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+                    d[h][0] = w0 & 0xFFFFFFu;
+                    d[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                    d[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                    d[h][3] = w2 >> 8;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (i < n_px) d[h][i] = grade_pack(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+                }
+            }
+            if (!empty) {
+                const float *zq = a.z + (size_t)y * (size_t)W + (size_t)x;
+                if (WORDS) {
+                    const float4 v = *reinterpret_cast<const float4 *>(zq);
+                    zv[h][0] = v.x, zv[h][1] = v.y, zv[h][2] = v.z, zv[h][3] = v.w;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (i < n_px) zv[h][i] = zq[i];
+                }
+            }
+        }
+        if (blend) {
+#pragma unroll
+            for (int h = 0; h < RAMP_UNITS; h++) {
+                if (!inside[h]) continue;
+                uint32_t e[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) e[i] = empty ? q.undrawn : ramp_source(s_ramp, zv[h][i], q);
+                switch (q.mode) {  // (scalar)
+                case LAYER_ADD: ramp_unit<LAYER_ADD>(d[h], e, q.opacity, n_px); break;
+                case LAYER_MULTIPLY: ramp_unit<LAYER_MULTIPLY>(d[h], e, q.opacity, n_px); break;
+                case LAYER_SCREEN: ramp_unit<LAYER_SCREEN>(d[h], e, q.opacity, n_px); break;
+                case LAYER_LIGHTEN: ramp_unit<LAYER_LIGHTEN>(d[h], e, q.opacity, n_px); break;
+                case LAYER_DARKEN: ramp_unit<LAYER_DARKEN>(d[h], e, q.opacity, n_px); break;
+                case LAYER_DIFFERENCE: ramp_unit<LAYER_DIFFERENCE>(d[h], e, q.opacity, n_px); break;
+                default: ramp_unit<LAYER_NORMAL>(d[h], e, q.opacity, n_px); break;
+                }
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < RAMP_UNITS; h++) {
+            if (!inside[h]) continue;
+            uint8_t *o = a.out + ci[h];
+            if (WORDS) {
+                uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+                ow[0] = d[h][0] | (d[h][1] << 24);
+                ow[1] = (d[h][1] >> 8) | (d[h][2] << 16);
+                ow[2] = (d[h][2] >> 16) | (d[h][3] << 8);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) {
+                        o[3 * i + 0] = (uint8_t)(d[h][i] & 0xFFu);
+                        o[3 * i + 1] = (uint8_t)((d[h][i] >> 8) & 0xFFu);
+                        o[3 * i + 2] = (uint8_t)((d[h][i] >> 16) & 0xFFu);
+                    }
+            }
+        }
+        if (in_place && clean && a.lower != nullptr) {  // (workgroup-uniform) the tile holds the blend over zeros now
+            __syncthreads();
+            if (threadIdx.x == 0u) a.lower[t] = 0u;
+        }
+    }
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -5358,6 +5502,39 @@ int launch_grade(const GradeArgs &a, hipStream_t st, uint32_t cap, uint32_t *gri
         hipLaunchKernelGGL((k_grade<false, true>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_grade<false, false>), dim3(grid), dim3(GRADE_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid_out)
+{
+    *grid_out = 0u;
+    const uint32_t W = a.frame.width, H = a.frame.height, n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    const RampRule &q = a.rule;
+    if (!a.fb || !a.out || !a.z || !a.zclean || !a.table || (uintptr_t)a.table % 16u != 0u) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (both flag sets and z are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (q.n < 2u || q.n > RAMP_MAX_N || q.mode >= LAYER_MODES || q.opacity > 256u || (q.flags & ~RAMP_REPEAT) != 0u) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    // whole words: every unit of four pixels is three aligned words of either buffer, its depths one 16-byte piece
+    const bool words = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u && (uintptr_t)a.z % 16u == 0u;
+    const size_t lds_bytes = (size_t)((q.n + 3u) / 4u) * 16u;
+    // persistent workgroups: as many as the device holds at once (at most 8 x 4 KB of LDS a CU: the waves are the limit)
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        return (int)hipErrorInvalidDevice;
+    uint32_t grid = std::min<uint32_t>((uint32_t)cus * (uint32_t)RAMP_MAX_PER_CU, n_tiles);
+    if (cap != 0u) grid = std::min<uint32_t>(grid, cap);  // (the diagnostic: fewer workgroups, more rounds each)
+    *grid_out = grid;
+    if (words)
+        hipLaunchKernelGGL((k_ramp<true>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
+    else
+        hipLaunchKernelGGL((k_ramp<false>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -403,6 +403,10 @@ struct tr_scene {
     // pieces; lut_c0: its entry 0, what a cleared tile becomes.  lut_n == 0: no table
     uint32_t *d_lut = nullptr;
     uint32_t lut_n = 0, lut_c0 = 0;
+    // tr_scene_set_ramp: the depth ramp's table as k_ramp reads it -- ramp_n packed rgba entries, padded to whole 16-byte
+    // pieces.  ramp_n == 0: no table.  tr_scene_debug_ramp_grid: the cap and the last grid, as for k_grade
+    uint32_t *d_ramp = nullptr;
+    uint32_t ramp_n = 0, ramp_cap = 0, ramp_grid = 0;
     // tr_scene_resize: the two axes' tables of the last (width, height, filter) asked for (width == 0: none) in one device
     // block `d`, the page-locked block `h` they are uploaded from and the event behind the last upload (resize_tables);
     // shape, y_span and x_span: what launch_resize wants to know of them
@@ -2539,6 +2543,7 @@ void destroy(tr_scene *s)
     dev_free(s->d_dof_fb);
     dev_free(s->d_dof_clean);
     dev_free(s->d_lut);
+    dev_free(s->d_ramp);
     dev_free(s->resize.d);
     if (s->resize.h) (void)hipHostFree(s->resize.h);
     if (s->resize.uploaded) (void)hipEventDestroy(s->resize.uploaded);
@@ -2839,7 +2844,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, resize, to_yuv, layer) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, resize, to_yuv, layer, ramp) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -5787,6 +5792,153 @@ int tr_layer_host(uint32_t width, uint32_t height, const uint8_t *rgb, const flo
     if ((p->flags & kLayerWhere) && !z) return tr::fail(TR_E_INVALID, "tr_layer_host: a WHERE flag needs z");
     layer_host(width, height, rgb, z, layer_rule(p, p->width, p->height), image, out);
     return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_RAMP_MAX_N == RAMP_MAX_N && TR_RAMP_REPEAT == RAMP_REPEAT && sizeof(tr_ramp_params) == 32, "tr_ramp.h restates the header");
+
+// tr_ramp_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_ramp_params(const tr_ramp_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (!std::isfinite(p->z0)) return tr::fail(TR_E_INVALID, w + ": z0 must be finite");
+    if (!std::isfinite(p->scale) || p->scale == 0.0f) return tr::fail(TR_E_INVALID, w + ": scale must be finite and not 0");
+    if (p->mode > TR_LAYER_DIFFERENCE) return tr::fail(TR_E_INVALID, w + ": mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if ((p->flags & ~TR_RAMP_REPEAT) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (p->reserved[0] != 0u || p->reserved[1] != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    return TR_OK;
+}
+
+int check_ramp_n(uint32_t n, const char *who)
+{
+    if (n < 2u || n > RAMP_MAX_N) return tr::fail(TR_E_INVALID, std::string(who) + ": the table's length n must be 2..TR_RAMP_MAX_N");
+    return TR_OK;
+}
+
+int check_ramp_scene(const tr_scene *s, const char *who)
+{
+    if (s->ramp_n == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no ramp table (tr_scene_set_ramp)");
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be ramped");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// The rule of checked parameters over a table of n entries.
+RampRule ramp_rule(const tr_ramp_params *p, uint32_t n)
+{
+    RampRule r;
+    r.z0 = p->z0, r.scale = p->scale;
+    r.mode = p->mode, r.opacity = p->opacity, r.undrawn = p->undrawn, r.flags = p->flags;
+    r.n = n;
+    return r;
+}
+
+// Enqueues the ramp of the current frame into `out_device` (null: in place) behind everything issued so far.  A pending
+// clear is made real (the kernel then runs on raised flags), and the stage always reads depth: one left on the chip is
+// made real first.
+int enqueue_ramp(tr_scene *s, const RampRule &r, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    RampArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.table = s->d_ramp;
+    a.frame = s->frame;
+    a.rule = r;
+    return timed_launch(s, K_RAMP, "k_ramp", [&] { return launch_ramp(a, s->stream, s->ramp_cap, &s->ramp_grid); });
+}
+
+}  // namespace
+
+int tr_scene_set_ramp(tr_scene *s, uint32_t n, const uint8_t *rgba)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_set_ramp: null scene");
+    if (n != 0u) {
+        int st = check_ramp_n(n, "tr_scene_set_ramp");
+        if (st != TR_OK) return st;
+        if (!rgba) return tr::fail(TR_E_INVALID, "tr_scene_set_ramp: null table");
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // one word an entry, padded to whole 16-byte pieces (k_ramp stages the table by pieces)
+    const size_t padded = ((size_t)n + 3u) / 4u * 4u;
+    std::vector<uint32_t> words(padded, 0u);
+    if (n) ramp_expand(n, rgba, words.data());
+    int st = swap_device_array(s, s->d_ramp, n != 0u, words.data(), padded);
+    if (st != TR_OK) return st;
+    s->ramp_n = n;
+    return TR_OK;
+}
+
+int tr_scene_ramp(tr_scene *s, const tr_ramp_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_ramp: null scene");
+    int st = check_ramp_params(p, "tr_scene_ramp");
+    if (st == TR_OK) st = check_ramp_scene(s, "tr_scene_ramp");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_ramp", "tr_scene_get_ramped", "ramps", 0u, &target);
+    if (st != TR_OK) return st;
+    const RampRule r = ramp_rule(p, s->ramp_n);
+    // a logically cleared scene is `undrawn` over black everywhere: zeros out of place, itself in place
+    if (s->z_fb_cleared && ramp_keeps_cleared_black(r)) return target ? cleared_out_of_place(s, target) : TR_OK;
+    st = enqueue_ramp(s, r, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_ramped(tr_scene *s, const tr_ramp_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_ramped: null scene");
+    int st = check_ramp_params(p, "tr_scene_get_ramped");
+    if (st == TR_OK && !rgb) st = tr::fail(TR_E_INVALID, "tr_scene_get_ramped: null argument");
+    if (st == TR_OK) st = check_ramp_scene(s, "tr_scene_get_ramped");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const RampRule r = ramp_rule(p, s->ramp_n);
+    return get_stage(s, rgb, frame_bytes(s), ramp_keeps_cleared_black(r) ? cleared : nullptr, [&](uint8_t *o) { return enqueue_ramp(s, r, o); });
+}
+
+// The rule of tr_ramp.h over caller's arrays, on the host.  Needs no GPU.
+int tr_ramp_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_ramp_params *p, uint32_t n, const uint8_t *table,
+                 uint8_t *out)
+{
+    int st = check_ramp_params(p, "tr_ramp_host");
+    if (st == TR_OK) st = check_ramp_n(n, "tr_ramp_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || height < 1u) return tr::fail(TR_E_INVALID, "tr_ramp_host: the frame's width and height must be at least 1");
+    if (!rgb || !z || !table || !out) return tr::fail(TR_E_INVALID, "tr_ramp_host: null argument");
+    ramp_host(width, height, rgb, z, ramp_rule(p, n), table, out);
+    return TR_OK;
+}
+
+int tr_ramp_positions(const tr_ramp_params *p, uint32_t n, uint32_t count, const float *z, uint32_t *positions)
+{
+    int st = check_ramp_params(p, "tr_ramp_positions");
+    if (st == TR_OK) st = check_ramp_n(n, "tr_ramp_positions");
+    if (st != TR_OK) return st;
+    if (count == 0u) return TR_OK;
+    if (!z || !positions) return tr::fail(TR_E_INVALID, "tr_ramp_positions: null argument");
+    const RampRule r = ramp_rule(p, n);
+    for (uint32_t k = 0; k < count; k++) positions[k] = layer_drawn(z[k]) ? ramp_position(z[k], r) : RAMP_NO_POSITION;
+    return TR_OK;
+}
+
+int tr_scene_debug_ramp_grid(tr_scene *s, uint32_t cap)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_ramp_grid: null scene");
+    s->ramp_cap = cap;
+    return (int)s->ramp_grid;
 }
 
 namespace {

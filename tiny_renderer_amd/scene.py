@@ -772,6 +772,190 @@ def layer_letterbox(w, h, bar, colour=(0, 0, 0)):
     return out
 
 
+RAMP_MAX_N, RAMP_REPEAT, RAMP_NO_POSITION = 1024, 1, 0xFFFFFFFF   # (TR_RAMP_MAX_N, TR_RAMP_REPEAT; ramp_positions: not drawn)
+
+
+class RampParams(C.Structure):
+    """tr_ramp_params"""
+    _fields_ = [("z0", C.c_float), ("scale", C.c_float), ("mode", C.c_uint32), ("opacity", C.c_uint32), ("undrawn", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def ramp_params(z0, scale, mode="normal", opacity=256, undrawn=(0, 0, 0, 0), repeat=False, who="ramp"):
+    """tr_ramp_params for Scene.ramp / get_ramped / ramp_host / ramp_positions: a drawn pixel with depth z takes table
+    position ((z - z0) * scale) as u32, in 1/256 of a table step, clamped to the last entry or, with repeat=True, wrapped;
+    scale may be negative (nearer is larger: ramp_span).  mode: a layer mode; opacity 0..256; undrawn: the (r, g, b, a)
+    entry of a pixel that is not drawn -- alpha 0 leaves the background alone.  ValueError, in the library's words, for
+    what it would refuse (include/tiny_renderer.h)."""
+    with np.errstate(over="ignore"):   # (as f32: what the library gets)
+        z32, s32 = np.float32(float(z0)), np.float32(float(scale))
+    if not np.isfinite(z32):
+        raise ValueError("%s: z0 must be finite" % who)
+    if not np.isfinite(s32) or s32 == 0.0:
+        raise ValueError("%s: scale must be finite and not 0" % who)
+    if mode not in LAYER_MODES:
+        raise ValueError("%s: mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE" % who)
+    if isinstance(opacity, bool) or not isinstance(opacity, (int, np.integer)) or not 0 <= opacity <= 256:
+        raise ValueError("%s: opacity must be 0..256" % who)
+    u = [int(v) for v in undrawn]
+    if len(u) != 4 or not all(0 <= v <= 255 for v in u):
+        raise ValueError("%s: undrawn must be four values 0..255 (r, g, b, a)" % who)
+    return RampParams(float(z32), float(s32), LAYER_MODES[mode], int(opacity), u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24),
+                      RAMP_REPEAT if repeat else 0, (C.c_uint32 * 2)(0, 0))
+
+
+def _ramp_table(table, who):
+    """The table of a ramp as the library takes it: a contiguous uint8 [n, 4] array, n = 2..1024."""
+    if not isinstance(table, np.ndarray) or table.dtype != np.uint8 or table.ndim != 2 or table.shape[1] != 4:
+        raise ValueError("%s: the table must be a uint8 array [n, 4] (r, g, b, a)" % who)
+    if not 2 <= table.shape[0] <= RAMP_MAX_N:
+        raise ValueError("%s: the table's length n must be 2..TR_RAMP_MAX_N" % who)
+    return np.ascontiguousarray(table)
+
+
+def ramp_host(rgb, z, table, params, in_place=False):
+    """tr_ramp_host: the rule of Scene.ramp on the host (no GPU needed), by the inline functions k_ramp calls.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer), z [H, W] float32 with row 0 = bottom (read_z_f32), table uint8
+    [n, 4], params from ramp_params.  Returns the ramped frame and leaves its arguments alone; in_place=True hands the
+    library one buffer as rgb and out (a copy of rgb), which the rule allows."""
+    _check_params(params, RampParams, "ramp_host", "ramp_params")
+    tab = _ramp_table(table, "ramp_host")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    zz = np.ascontiguousarray(z, np.float32)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1 or zz.shape != src.shape[:2]:
+        raise ValueError("ramp_host: rgb [H, W, 3] and z [H, W]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_ramp_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data, zz.ctypes.data,
+                                      C.addressof(params), tab.shape[0], tab.ctypes.data, out.ctypes.data))
+    return out
+
+
+def ramp_positions(params, n, z):
+    """tr_ramp_positions: the table position (uint32, z's shape; 1/256 of a step, after the clamp or the wrap) of every
+    depth in z under params (ramp_params) and a table of n entries; RAMP_NO_POSITION where nothing is drawn -- for
+    choosing z0 and scale."""
+    _check_params(params, RampParams, "ramp_positions", "ramp_params")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= RAMP_MAX_N:
+        raise ValueError("ramp_positions: the table's length n must be 2..TR_RAMP_MAX_N")
+    zz = np.ascontiguousarray(z, np.float32)
+    out = np.zeros(zz.shape, np.uint32)
+    check(load_library().tr_ramp_positions(C.addressof(params), int(n), zz.size, zz.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _ramp_n(n, who):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= n <= RAMP_MAX_N:
+        raise ValueError("%s: n must be an integer 2..%d" % (who, RAMP_MAX_N))
+    return int(n)
+
+
+def _ramp_colour(colour, who):
+    c = [int(v) for v in colour]
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise ValueError("%s: colour must be three values 0..255" % who)
+    return c
+
+
+def ramp_span(near, far, n):
+    """(z0, scale) as np.float32 for a table of n entries that starts at the depth `near` and reaches its last entry at
+    `far`: z0 = f32(near), scale = f32((n - 1) * 256 / (f32(far) - f32(near))), the quotient taken in float64.  Nearer is
+    larger in this renderer, so far < near and scale < 0 for a ramp that grows with distance."""
+    n = _ramp_n(n, "ramp_span")
+    with np.errstate(over="ignore"):
+        a, b = np.float32(float(near)), np.float32(float(far))
+    if not np.isfinite(a) or not np.isfinite(b) or a == b:
+        raise ValueError("ramp_span: near and far must be finite and differ")
+    with np.errstate(over="ignore"):
+        scale = np.float32(float((n - 1) * 256) / (float(b) - float(a)))
+    if not np.isfinite(scale) or scale == 0.0:
+        raise ValueError("ramp_span: the span gives no finite non-zero scale")
+    return a, scale
+
+
+def ramp_span_auto(scene, n=256):
+    """ramp_span from the nearest to the farthest drawn depth of the scene's current frame, taken from
+    Scene.get_frame_stats(depth=True) -- reduced on the device, no z is read back.  ValueError where nothing is drawn; a
+    frame of one depth gets a span of one unit behind it."""
+    stats = scene.get_frame_stats(depth=True)
+    if stats.n_drawn == 0:
+        raise ValueError("ramp_span_auto: nothing is drawn")
+    near, far = np.float32(stats.z_max), np.float32(stats.z_min)
+    return ramp_span(near, far if far != near else near - np.float32(1.0), n)
+
+
+def ramp_fog(colour, n=256, kind="linear", density=2.0):
+    """A table [n, 4] for Scene.set_ramp: `colour` everywhere, alpha 0 at entry 0 rising to 255 at the last.  kind
+    "linear": alpha_k = round(255 k / (n - 1)), in integers; "exp": 1 - exp(-density t) and "exp2": 1 - exp(-(density t)^2)
+    with t = k / (n - 1), each divided by its value at t = 1 and rounded to 0..255."""
+    n, c = _ramp_n(n, "ramp_fog"), _ramp_colour(colour, "ramp_fog")
+    k = np.arange(n, dtype=np.int64)
+    if kind == "linear":
+        alpha = (2 * 255 * k + (n - 1)) // (2 * (n - 1))
+    elif kind in ("exp", "exp2"):
+        d = float(density)
+        if not np.isfinite(d) or not d > 0.0:
+            raise ValueError("ramp_fog: density must be finite and > 0")
+        t = k.astype(np.float64) / float(n - 1)
+        x = d * t if kind == "exp" else (d * t) ** 2
+        a = -np.expm1(-x)
+        alpha = np.floor(255.0 * a / a[-1] + 0.5).astype(np.int64)
+        alpha[0], alpha[-1] = 0, 255
+        alpha = np.maximum.accumulate(alpha)
+    else:
+        raise ValueError("ramp_fog: kind must be \"linear\", \"exp\" or \"exp2\"")
+    out = np.empty((n, 4), np.uint8)
+    out[:, :3] = c
+    out[:, 3] = np.clip(alpha, 0, 255)
+    return out
+
+
+def ramp_grey(n=256):
+    """An opaque table [n, 4] from black at entry 0 to white at the last: a grey depth view under mode "normal"."""
+    n = _ramp_n(n, "ramp_grey")
+    k = np.arange(n, dtype=np.int64)
+    out = np.full((n, 4), 255, np.uint8)
+    out[:, :3] = ((2 * 255 * k + (n - 1)) // (2 * (n - 1)))[:, None]
+    return out
+
+
+def ramp_false_colour(n=256):
+    """An opaque table [n, 4] through blue, cyan, green, yellow and red: a false-colour depth view."""
+    n = _ramp_n(n, "ramp_false_colour")
+    anchors = np.array([[0, 0, 160], [0, 0, 255], [0, 255, 255], [0, 255, 0], [255, 255, 0], [255, 0, 0], [160, 0, 0]], np.int64)
+    m = len(anchors) - 1
+    pos = np.arange(n, dtype=np.int64) * m                 # in units of 1 / (n - 1) of a segment
+    seg = np.minimum(pos // (n - 1), m - 1)
+    f = pos - seg * (n - 1)
+    out = np.full((n, 4), 255, np.uint8)
+    out[:, :3] = (2 * (anchors[seg] * (n - 1 - f)[:, None] + anchors[seg + 1] * f[:, None]) + (n - 1)) // (2 * (n - 1))
+    return out
+
+
+def ramp_contours(n, every, colour=(0, 0, 0)):
+    """A table [n, 4] of `colour`: opaque at every `every`-th entry from entry 0, transparent between -- contour bands."""
+    n, c = _ramp_n(n, "ramp_contours"), _ramp_colour(colour, "ramp_contours")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError("ramp_contours: every must be a positive integer")
+    out = np.zeros((n, 4), np.uint8)
+    out[:, :3] = c
+    out[::int(every), 3] = 255
+    return out
+
+
+def ramp_slice(n, lo, hi, colour=(255, 255, 255)):
+    """A table [n, 4] of `colour`: opaque at the entries lo <= k < hi, transparent elsewhere -- a depth slice or matte."""
+    n, c = _ramp_n(n, "ramp_slice"), _ramp_colour(colour, "ramp_slice")
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("ramp_slice: lo and hi must be integers")
+    if not 0 <= lo < hi <= n:
+        raise ValueError("ramp_slice: 0 <= lo < hi <= n")
+    out = np.zeros((n, 4), np.uint8)
+    out[:, :3] = c
+    out[int(lo):int(hi), 3] = 255
+    return out
+
+
 WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
 WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
 
@@ -2221,6 +2405,50 @@ class Scene:
             raise ValueError("pinned_layer: channels must be 3 or 4")
         w, h = _layer_size(width, height, "pinned_layer")
         return self._pinned_array((h, w, channels))
+
+    # --- depth ramp (tr_scene_set_ramp / tr_scene_ramp / tr_scene_get_ramped) -------------------------
+    def set_ramp(self, table):
+        """tr_scene_set_ramp: the scene's ramp table, uint8 [n, 4] of (r, g, b, a), n = 2..1024 (ramp_fog, ramp_grey,
+        ramp_false_colour, ramp_contours, ramp_slice); None drops it.  Waits for the scene's queued work."""
+        if table is None:
+            check(load_library().tr_scene_set_ramp(self._h, 0, None))
+            return
+        tab = _ramp_table(table, "set_ramp")
+        check(load_library().tr_scene_set_ramp(self._h, tab.shape[0], tab.ctypes.data))
+
+    def ramp(self, z0, scale, mode="normal", opacity=256, undrawn=(0, 0, 0, 0), repeat=False, out=None, params=None):
+        """tr_scene_ramp: blends the entry of the scene's ramp table that each pixel's own depth chooses into the current
+        frame on the device (arguments: ramp_params, or params built by it with z0 and scale None).  out=None: in place,
+        by the kernel itself -- every later consumer sees the ramped frame, z, winner words and the shadow buffer stay,
+        calling it twice ramps twice.  Otherwise `out` is a device pointer (int) or tensor of 3 * W * H bytes apart from
+        every frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.
+        Asynchronous: the result is there after sync().  Band scenes are refused.  store_depth=True avoids the depth-only
+        repeat of the frame's pass.  ramp_host is the rule."""
+        p = self._ramp_params("tr_scene_ramp", z0, scale, mode, opacity, undrawn, repeat, params)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_ramp(self._h, C.addressof(p), ptr))
+        return out
+
+    def get_ramped(self, z0, scale, mode="normal", opacity=256, undrawn=(0, 0, 0, 0), repeat=False, strict=True, params=None):
+        """tr_scene_get_ramped: the current frame ramped on the device (arguments as for ramp), as an [H, W, 3] uint8
+        array.  Synchronizes; the scene's frame stays as it is."""
+        p = self._ramp_params("tr_scene_get_ramped", z0, scale, mode, opacity, undrawn, repeat, params)
+        return self._image("tr_scene_get_ramped", strict, C.addressof(p))
+
+    @staticmethod
+    def _ramp_params(who, z0, scale, mode, opacity, undrawn, repeat, params):
+        if params is None:
+            return ramp_params(z0, scale, mode, opacity, undrawn, repeat, who)
+        _check_params(params, RampParams, who, "ramp_params")
+        return params
+
+    def debug_ramp_grid(self, cap=0):
+        """tr_scene_debug_ramp_grid: every later k_ramp launch of the scene starts at most `cap` workgroups (0: no cap, the
+        default), so that each walks more tiles; the result does not change.  Returns the number of workgroups of the
+        scene's most recent k_ramp launch, 0 if there has been none."""
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
+            raise ValueError("debug_ramp_grid: cap must be an integer 0..2^32 - 1")
+        return check(load_library().tr_scene_debug_ramp_grid(self._h, int(cap)))
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
