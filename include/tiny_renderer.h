@@ -1171,6 +1171,75 @@ int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb);
 int tr_rank_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, uint8_t *out /* != rgb */,
                  const tr_rank_params *p);
 
+/* Bilateral: the scene's CURRENT frame through an edge-preserving smoothing filter on the device -- one kernel
+ * (k_bilateral): a weighted mean over a window whose weights fall with a tap's difference from the centre pixel, in
+ * colour or in depth.  The third neighbourhood family beside the linear one (convolve) and the order statistics (rank);
+ * no stack of those expresses it.  Guided by depth it is the "joint" or "cross" bilateral blur that takes the grain out
+ * of ambient occlusion and of shadow borders without bleeding across silhouettes; guided by colour and followed by a
+ * posterising grade table and an outline it is the usual toon look.
+ * Input.  F is the frame as tr_scene_get_frame_buffer returns it: rgb8, row 0 at the top.  z is the depth as tr_dof_host
+ * takes it: index x + y*W, y up; a pixel is not drawn when bits(z) == bits(f32::MIN).
+ * Window.  kw x kh, each odd and 1..15.  spatial[j*kw + i] is a u8 weight for column i from the left and row j from the
+ * TOP; a tap with spatial weight 0 is no tap.  Bytes of spatial at index kw*kh and beyond must be 0, and at least one
+ * weight must be non-zero.  Tap (i, j) of pixel (x, y) reads position (x + i - kw/2, y + j - kh/2).
+ * Edge handling.  Under TR_BILATERAL_BORDER a tap outside the image has colour border[c] and depth f32::MIN; under
+ * TR_BILATERAL_CLAMP its index is clamped per axis, for colour and depth alike.
+ * Distance d of a tap T from the centre C, 0..255:
+ *   TR_BILATERAL_GUIDE_COLOUR  d = max(|Tr-Cr|, |Tg-Cg|, |Tb-Cb|)
+ *   TR_BILATERAL_GUIDE_DEPTH   t = fl(|fl(zT - zC)| * depth_scale), every f32 operation rounded once;
+ *                              d = t < 255.0f ? (uint32_t)t : 255.  A NaN or an infinity therefore gives 255, two
+ *                              undrawn pixels give 0.  depth_scale must be finite and >= 0.
+ * Weight and sums.  w = spatial * range[d], range a table of 256 u8 entries, so w <= 65025.  S is the sum of w over the
+ * taps, A_c the sum of w * T_c.  Output channel: S == 0 ? C_c : (A_c + S/2) / S, an integer division.
+ * Bounds.  S <= 225 * 65025 < 2^24, and A_c + S/2 <= 225 * 65025 * 255 + 7,315,312 = 3,738,124,687 < 2^32: u32
+ * accumulators suffice and each product fits a 24-bit multiply.
+ * Every step is an integer or a single-rounded f32 operation, so the device equals tr_bilateral_host in every byte.  What
+ * follows from the rule: a window whose only weight is the centre's, or an all-zero range table, is the identity; an
+ * all-255 range table is a plain weighted mean; range[d] = 255 for d <= cutoff and 0 beyond averages exactly the taps
+ * within the cutoff of the centre. */
+#define TR_BILATERAL_GUIDE_COLOUR 0u
+#define TR_BILATERAL_GUIDE_DEPTH 1u
+#define TR_BILATERAL_BORDER 0u
+#define TR_BILATERAL_CLAMP 1u
+typedef struct tr_bilateral_params {
+    uint32_t struct_size;   /* = sizeof(tr_bilateral_params) = 512 */
+    uint32_t kw, kh;        /* odd, 1..15 each */
+    uint32_t guide;         /* TR_BILATERAL_GUIDE_COLOUR or TR_BILATERAL_GUIDE_DEPTH */
+    uint32_t edge;          /* TR_BILATERAL_BORDER or TR_BILATERAL_CLAMP */
+    float depth_scale;      /* finite, >= 0; read under the DEPTH guide only, checked always */
+    uint8_t border[3];      /* r, g, b of a tap outside the image under TR_BILATERAL_BORDER */
+    uint8_t pad;            /* 0 */
+    uint8_t spatial[225];   /* spatial[j*kw + i]: column i from the left, row j from the top; 0 beyond kw*kh */
+    uint8_t pad2[3];        /* 0 */
+    uint8_t range[256];     /* range[d]: the weight of a tap at distance d from the centre */
+} tr_bilateral_params;
+/* Filters the current frame -- what the getters mean.  Asynchronous and ordered like tr_scene_rank: frames held back are
+ * submitted, a pending clear is made real, k_bilateral is enqueued on the scene's stream.  Under the COLOUR guide no depth
+ * is read, so a depth left on the chip stays there; under the DEPTH guide the depth is made real first, as for
+ * tr_scene_depth_of_field.  out: 3 * W * H bytes of device memory or of memory from tr_host_alloc, apart from every frame
+ * buffer of the scene; every byte is written and the scene's frame stays.  out == NULL: IN PLACE, through the scene's
+ * scratch frame (a tap reads neighbours) -- every later consumer sees the filtered frame, the colour fast-clear flags
+ * follow (a tile is flagged only where it is zeros in every byte), z, the winner words and the shadow buffer stay;
+ * calling it twice filters twice.  A tile whose existing 3 x 3 neighbourhood is flagged clean in colour, with no non-zero
+ * border colour in reach (TR_BILATERAL_CLAMP, a border of 0, or a halo inside the image), is 0 under both guides: it is
+ * stored without a load, of colour or of depth.  A colour texel behind a raised colour flag counts as zeros, a depth
+ * behind a raised depth flag as f32::MIN; neither is loaded.  A scene that is logically cleared under TR_BILATERAL_CLAMP
+ * or a border of 0: zeros out of place, nothing in place, no kernel; otherwise the clear is made real and the kernel runs.
+ * TR_E_INVALID, each text opening with the call's name: a null scene or params, a wrong struct_size, an even or
+ * out-of-range kw or kh, spatial weights outside the window, an all-zero window, an unknown guide or edge, a depth_scale
+ * that is negative, infinite or a NaN, pad or pad2 != 0; a BAND scene (tr_options.band_row0/1 set: the taps at a band's
+ * border lie in another rank's rows); ordinary host memory as `out`, a pinned buffer that is too small, an `out` that
+ * overlaps a frame buffer of the scene.  The parameters are checked first, then the band, then `out`. */
+int tr_scene_bilateral(tr_scene *s, const tr_bilateral_params *p, void *out /* or NULL */);
+/* The same into any host memory (3 * W * H bytes): waits for the scene first, filters into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_ranked.  The scene's frame stays. */
+int tr_scene_get_bilateral(tr_scene *s, const tr_bilateral_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the inline functions k_bilateral shares.  rgb and out: 3 * width *
+ * height bytes, row 0 = top; out must not be rgb.  z: width * height floats, x + y*W, y up; NULL is allowed under the
+ * COLOUR guide, which does not read it.  The same parameter checks; a width or height of 0 returns TR_OK. */
+int tr_bilateral_host(uint32_t width, uint32_t height, const uint8_t *rgb /* row 0 = top */, const float *z /* x + y*W, y up */,
+                      uint8_t *out /* != rgb */, const tr_bilateral_params *p);
+
 /* YUV output: the scene's CURRENT frame, or any rgb8 image on the device, converted on the device to 8-bit YCbCr planes --
  * the form encoders and video files take, 1.5 bytes a pixel in 4:2:0 where rgb8 has 3 -- as the chain's very last step
  * (render, composite, ..., resize, TO_YUV, read back).  The source F is the image tr_scene_get_frame_buffer would return:

@@ -174,6 +174,9 @@ SYMBOLS = {
     "tr_scene_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_ranked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_rank_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_bilateral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_bilateral": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_bilateral_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_to_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_to_yuv_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_get_yuv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

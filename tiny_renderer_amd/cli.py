@@ -160,6 +160,19 @@ def main(argv=None):
                          "(1..7); applied after --median")
     ap.add_argument("--rank-shape", default=None, choices=("rect", "disc", "cross"),
                     help="the footprint of --erode, --dilate, --median and --despeckle: the whole square (rect; default), a disc or a cross")
+    ap.add_argument("--smooth", type=int, default=None, action=_Once, metavar="R",
+                    help="bilateral: edge-preserving smoothing over a box of radius R (1..7), clamped at the edge, on the GPU "
+                         "(Scene.bilateral; after the rank options and before --overlay)")
+    ap.add_argument("--smooth-range", type=int, default=None, action=_Once, metavar="N",
+                    help="with --smooth or --ao-smooth: only taps within N (0..255) of the centre count, all alike (range_step; default 16)")
+    ap.add_argument("--smooth-guide", default=None, choices=("colour", "depth"),
+                    help="with --smooth: the distance is the largest channel difference (colour; default) or the depth difference times "
+                         "--smooth-depth-scale (depth)")
+    ap.add_argument("--smooth-depth-scale", type=float, default=None, action=_Once, metavar="F",
+                    help="with --smooth-guide depth or --ao-smooth: distance steps per unit of depth (finite, >= 0; default 8)")
+    ap.add_argument("--ao-smooth", type=int, default=None, action=_Once, metavar="R",
+                    help="with --ao: the depth-guided bilateral blur over a box of radius R (1..7) directly behind the occlusion -- "
+                         "its grain goes, the silhouettes stay")
     ap.add_argument("--backdrop", default=None, metavar="FILE.tga|R,G,B[:R,G,B]",
                     help="layer: a picture, a colour or a gradient from the top colour to the bottom one behind the model, blended "
                          "on the GPU where nothing is drawn (Scene.layer, where=\"undrawn\"; after --with and --ao, before the "
@@ -449,6 +462,35 @@ def main(argv=None):
                 args.ranks.append(rank_params(f, 1, n - 2, op="clamp_centre", edge="clamp"))
             else:
                 args.ranks.append(rank_params(f, {"--erode": "min", "--dilate": "max", "--median": "median"}[name], edge="clamp"))
+    args.smooths, args.ao_smooth_params = [], None
+    if args.smooth is None and args.ao_smooth is None:
+        if args.smooth_range is not None or args.smooth_guide is not None or args.smooth_depth_scale is not None:
+            ap.error("--smooth-range, --smooth-guide and --smooth-depth-scale go with --smooth or --ao-smooth")
+    else:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--smooth and --ao-smooth work on the colour frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        if args.ao_smooth is not None and not args.ao:
+            ap.error("--ao-smooth goes with --ao RADIUS")
+        if args.smooth is None and args.smooth_guide is not None:
+            ap.error("--smooth-guide goes with --smooth (--ao-smooth is always guided by depth)")
+        from .scene import bilateral_params, spatial_box, range_step
+        cutoff = 16 if args.smooth_range is None else args.smooth_range
+        scale = 8.0 if args.smooth_depth_scale is None else args.smooth_depth_scale
+        try:
+            for name, r, guide in (("--smooth", args.smooth, args.smooth_guide or "colour"), ("--ao-smooth", args.ao_smooth, "depth")):
+                if r is None:
+                    continue
+                if not 1 <= r <= 7:
+                    raise ValueError(name + " takes a radius 1..7")
+                if not 0 <= cutoff <= 255:
+                    raise ValueError("--smooth-range takes 0..255")
+                p = bilateral_params(spatial_box(2 * r + 1, 2 * r + 1), range_step(cutoff), guide=guide, depth_scale=scale, edge="clamp")
+                if name == "--smooth":
+                    args.smooths.append(p)
+                else:
+                    args.ao_smooth_params = p
+        except ValueError as e:
+            ap.error(str(e))
     args.resize = None
     if args.out_size is not None:
         try:
@@ -716,6 +758,8 @@ def _post(args, T, scene, say):
     """The stage options on the scene's current frame, in their order (after --with and --shutter)."""
     if args.ao:
         scene.ambient_occlusion(radius=args.ao, rings=args.ao_rings, grey=args.ao_grey)
+        if args.ao_smooth_params is not None:   # in place, directly behind the occlusion: the depth it was taken from guides the blur
+            scene.bilateral(args.ao_smooth_params)
     if args.backdrop_spec is not None:
         # in place, where nothing is drawn: depth of field, bloom and everything later see the backdrop
         spec = args.backdrop_spec
@@ -767,6 +811,8 @@ def _post(args, T, scene, say):
         scene.convolve(cp)
     for rp in args.ranks:         # in place, after the convolves: erode, dilate, median, despeckle
         scene.rank(rp)
+    for bp in args.smooths:       # in place, after the ranks: edge-preserving smoothing
+        scene.bilateral(bp)
     if args.overlay is not None:   # in place, after the convolves: --stats, --ssaa, --out-size and y4m output see the layered frame
         scene.layer(_pinned_layer(scene, "overlay", lambda: T.load_tga(args.overlay)), args.overlay_at[0], args.overlay_at[1], args.overlay_mode,
                     args.overlay_opacity)

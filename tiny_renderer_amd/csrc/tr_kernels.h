@@ -11,6 +11,7 @@
 #include "tr_composite.h"
 #include "tr_convolve.h"
 #include "tr_rank.h"
+#include "tr_bilateral.h"
 #include "tr_dof.h"
 #include "tr_bloom.h"
 #include "tr_grade.h"
@@ -152,6 +153,11 @@ int launch_convolve(const ConvolveArgs &a, hipStream_t st);
 // the last, else the general one.  The whole frame only (no band); no depth is read.  a.words is set here.  a.out_clean
 // as for launch_convolve.
 int launch_rank(const RankArgs &a, hipStream_t st);
+// Bilateral: a.fb through the edge-preserving weighted mean a.rule into a.out (which does not overlap it) by the rule of
+// tr_bilateral.h, through the scene's colour fast-clear flags: k_bilateral.  The whole frame only (no band).  Under the
+// DEPTH guide a.z and a.zclean are read and the caller has made the depth real; under the COLOUR guide neither is.
+// a.words is set here.  a.out_clean as for launch_convolve.
+int launch_bilateral(const BilateralArgs &a, hipStream_t st);
 // Frame statistics: the frame a.fb (and, with a.rule.depth, its depth a.z) reduced to the record of tr_stats.h through the
 // frame's fast-clear flags: k_stats, persistent workgroups that each store a partial record to a slot of a.partials, then
 // k_stats_finish, which sums the slots into `out` (STATS_WORDS words of device memory, or the device address of mapped

@@ -38,6 +38,7 @@
 #include "tr_bloom.h"
 #include "tr_convolve.h"
 #include "tr_rank.h"
+#include "tr_bilateral.h"
 #include "tr_grade.h"
 #include "tr_stats.h"
 #include "tr_kernels.h"
@@ -3144,6 +3145,217 @@ __global__ __launch_bounds__(CONV_THREADS) void k_rank(RankArgs a)
     conv_store_share<STORE>(o, px, n_px);
 }
 
+// Bilateral (tr_scene_bilateral): the frame through a weighted mean whose weights fall with a tap's distance from the
+// centre, in colour (GUIDE 0) or in depth (GUIDE 1), into `out`, never in place; tr_bilateral.h has the rule.  The tile,
+// the workgroup, the rotated block-to-tile mapping, the nine-flag test, the staged rows of 160 words that start 16 pixels
+// left of the tile (one packed pixel each, as k_convolve stages them), the window of a lane's eight rows over a staged
+// column and the three store forms are k_convolve's; the colour staging is neigh_stage_colour below.  What differs:
+//   * a weighted mean of zeros is 0, and S == 0 gives the centre, which is 0 too: the constant tile is zeros under both
+//     guides and out_clean gets 1; on that path no depth is loaded;
+//   * GUIDE 1 stages z as a second plane of the same rows and halo, element by element (z: x + y * W for the kernel's
+//     row y).  A z texel is f32::MIN WITHOUT a load behind a raised depth flag (that memory is stale), outside the image
+//     under BORDER, and in a tile outside the grid (k_ao's form; under CLAMP the clamped index lies in the grid);
+//   * the range table is 256 bytes of LDS behind the planes, one word a lane of the first wave, staged once: its 64
+//     words lie in 64 different banks, a lookup is one byte read at a per-lane index;
+//   * the tap loop: a staged pixel (and depth) is read once from LDS and serves the lane's eight centres; the spatial
+//     weight of staged row jj for the lane's row k is a scalar, the eight of them a window that slides by one a row; a
+//     zero weight -- outside the window or in it -- is skipped by a uniform branch.  S and the three A_c of a centre
+//     are u32 (tr_bilateral.h has the bounds), the products 24-bit multiplies;
+//   * the finish is a plain u32 division per pixel and channel.
+// LDS, dynamic: (16 + 2 ry) * 640 bytes of colour, as much again for z under GUIDE 1, and 256 for the table: 10.25 KB at
+// a window one row high under GUIDE 0, 37.75 KB at fifteen rows under GUIDE 1.  fb, z and every flag of the frame are
+// only read.  No atomics, no scratch, no inline assembly.
+static_assert(BILATERAL_MAX_SIDE / 2u <= 15u && (int)(BILATERAL_MAX_SIDE / 2u) < TILE_H, "the halo lies in the eight tiles around");
+static_assert(2 * (TILE_H + 2 * (int)(BILATERAL_MAX_SIDE / 2u)) * CONV_LDS_W * 4 + 256 < 40 * 1024, "the largest window's LDS is below 40 KB");
+
+// The colour staging of a neighbourhood stage, k_convolve's and k_rank's text in one place (k_bilateral calls it; the two
+// older kernels keep their own copies, whose instruction streams a shared helper would change): the tile at (x0, y0) =
+// (tx, ty) and its halo of rx columns and ry rows into s_px as rows of CONV_LDS_W packed pixels (r | g << 8 | b << 16)
+// that start 16 pixels left of the tile.  A texel outside the image is `border`, or under `clamp` the texel at the
+// clamped index; a texel behind a raised flag (czero: bit 3 * ay + ax of the 3 x 3 tiles around) is zeros WITHOUT a load.
+// words: fb is 4-byte aligned and the width a multiple of 4 -- four pixels are three aligned words.  No barrier here.
+__device__ __forceinline__ void neigh_stage_colour(uint32_t *s_px, const uint8_t *fb, bool words, bool clamp, uint32_t border, uint32_t czero, int32_t W, int32_t H,
+                                                   int32_t x0, int32_t y0, int32_t tx, int32_t ty, int32_t rx, int32_t ry)
+{
+    // LDS row r is the kernel's row y0 - ry + r, LDS column c the frame's column x0 - 16 + c; columns c_lo .. c_hi - 1 are read
+    const int32_t rows = TILE_H + 2 * ry, c_lo = 16 - rx, c_hi = 16 + TILE_W + rx;
+    if (words) {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * (CONV_LDS_W / 4); p += CONV_THREADS) {
+            const int32_t r = p / (CONV_LDS_W / 4), j = p % (CONV_LDS_W / 4);
+            if (4 * j + 3 < c_lo || 4 * j >= c_hi) continue;  // (no tap reaches it)
+            const int32_t x = x0 - 16 + 4 * j, y = y0 - ry + r;
+            // (x and the width are multiples of 4: the four pixels lie inside the image's columns or outside together)
+            const bool x_out = x < 0 || x >= W, y_out = y < 0 || y >= H;
+            uint32_t c[4] = { border, border, border, border };
+            if (clamp || !(x_out || y_out)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                c[0] = c[1] = c[2] = c[3] = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    if (!x_out) {
+                        const uint32_t *q4 = reinterpret_cast<const uint32_t *>(q);
+                        const uint32_t w0 = q4[0], w1 = q4[1], w2 = q4[2];
+                        c[0] = w0 & 0xFFFFFFu;
+                        c[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                        c[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                        c[3] = w2 >> 8;
+                    } else {
+                        c[0] = c[1] = c[2] = c[3] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+                    }
+                }
+            }
+            *reinterpret_cast<uint4 *>(&s_px[r * CONV_LDS_W + 4 * j]) = make_uint4(c[0], c[1], c[2], c[3]);
+        }
+    } else {
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * CONV_LDS_W; p += CONV_THREADS) {
+            const int32_t r = p / CONV_LDS_W, c = p % CONV_LDS_W;
+            if (c < c_lo || c >= c_hi) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - ry + r;
+            uint32_t col = border;
+            if (clamp || !(x < 0 || x >= W || y < 0 || y >= H)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                col = 0u;
+                if ((czero & bit) == 0u) {
+                    const uint8_t *q = fb + ((size_t)(H - 1 - cy) * (size_t)W + (size_t)cx) * 3u;
+                    col = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+                }
+            }
+            s_px[r * CONV_LDS_W + c] = col;
+        }
+    }
+}
+
+// The spatial weight of column i, row j (from the top) of the window, for a row index that may lie outside it.  (scalar)
+__device__ __forceinline__ uint32_t bilateral_spatial(const BilateralArgs &a, int32_t i, int32_t j, int32_t kw, int32_t kh)
+{
+    return j >= 0 && j < kh ? bilateral_byte(a.rule.spatial, (uint32_t)(j * kw + i)) : 0u;
+}
+
+template <int GUIDE, int STORE>
+__global__ __launch_bounds__(CONV_THREADS) void k_bilateral(BilateralArgs a)
+{
+    static_assert(TILE_W == 128 && CONV_THREADS == 2 * TILE_W && 8 * TILE_H <= CONV_THREADS && CONV_ROWS == 8, "a lane owns a column and eight rows; the shares are the first lanes");
+    // (TILE_H + 2 ry) rows of CONV_LDS_W packed pixels; GUIDE 1: then as many rows of depths; then the 64 words of the range table
+    extern __shared__ __align__(16) uint32_t s_bl[];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t kw = (int32_t)a.rule.kw, kh = (int32_t)a.rule.kh, rx = kw / 2, ry = kh / 2;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t ty = (int32_t)blockIdx.x / ntx, tx = ((int32_t)blockIdx.x % ntx + 5 * ty) % ntx;
+    const uint32_t t = (uint32_t)(ty * ntx + tx);
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    // bit 3 * ay + ax, the tile at (tx + ax - 1, ty + ay - 1): exists -- it is part of the grid; czero -- and its flag is up
+    uint32_t exists = 0u, czero = 0u;
+#pragma unroll
+    for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+        for (int32_t ax = 0; ax < 3; ax++) {
+            const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+            const uint32_t bit = 1u << (3 * ay + ax);
+            if (nx < 0 || nx >= ntx || ny < 0 || ny >= nty) continue;
+            exists |= bit;
+            if (a.fbclean != nullptr && a.fbclean[ny * ntx + nx] != 0u) czero |= bit;
+        }
+    const bool clamp = a.rule.edge == BILATERAL_CLAMP;
+    const bool halo_inside = x0 - rx >= 0 && x0 + TILE_W + rx <= W && y0 - ry >= 0 && y0 + TILE_H + ry <= H;
+    const bool constant = czero == exists && (clamp || a.rule.border == 0u || halo_inside);
+    const int32_t sx = x0 + (int32_t)(threadIdx.x % 8u) * 16, srow = (int32_t)(threadIdx.x / 8u), sy = y0 + srow;
+    const bool share = threadIdx.x < 8u * TILE_H && sx < W && sy < H;
+    const int32_t n_px = share ? min(16, W - sx) : 0;  // (STORE 2: 16 or none; 1: a multiple of 4)
+    const size_t share_at = share ? ((size_t)(H - 1 - sy) * (size_t)W + (size_t)sx) * 3u : 0u;
+    uint8_t *o = a.out + share_at;
+    uint32_t px[16];
+    if (a.out_clean != nullptr && threadIdx.x == 0u) a.out_clean[t] = constant ? 1u : 0u;
+    if (constant) {  // (workgroup-uniform, ahead of the barriers and of any load of colour or depth)
+        if (!share) return;
+#pragma unroll
+        for (int i = 0; i < 16; i++) px[i] = 0u;
+        conv_store_share<STORE>(o, px, n_px);
+        return;
+    }
+    // LDS row r is the kernel's row y0 - ry + r, LDS column c the frame's column x0 - 16 + c; columns c_lo .. c_hi - 1 are read
+    const int32_t rows = TILE_H + 2 * ry, c_lo = 16 - rx, c_hi = 16 + TILE_W + rx;
+    float *s_z = reinterpret_cast<float *>(s_bl + rows * CONV_LDS_W);
+    uint32_t *s_range = s_bl + (GUIDE == 1 ? 2 : 1) * rows * CONV_LDS_W;
+    if (threadIdx.x < 64u) s_range[threadIdx.x] = a.rule.range[threadIdx.x];
+    neigh_stage_colour(s_bl, a.fb, a.words != 0u, clamp, a.rule.border, czero, W, H, x0, y0, tx, ty, rx, ry);
+    if (GUIDE == 1) {
+        // bit 3 * ay + ax: the z of that tile reads as f32::MIN -- its depth flag is up, or there is no such tile
+        uint32_t zstale = exists ^ 0x1FFu;
+#pragma unroll
+        for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+            for (int32_t ax = 0; ax < 3; ax++) {
+                const uint32_t bit = 1u << (3 * ay + ax);
+                if ((exists & bit) != 0u && a.zclean != nullptr && a.zclean[(ty + ay - 1) * ntx + (tx + ax - 1)] != 0u) zstale |= bit;
+            }
+        const float z_min = bits_f32(TR_F32_MIN_BITS);
+        for (int32_t p = (int32_t)threadIdx.x; p < rows * CONV_LDS_W; p += CONV_THREADS) {
+            const int32_t r = p / CONV_LDS_W, c = p % CONV_LDS_W;
+            if (c < c_lo || c >= c_hi) continue;
+            const int32_t x = x0 - 16 + c, y = y0 - ry + r;
+            float v = z_min;
+            if (clamp || !(x < 0 || x >= W || y < 0 || y >= H)) {
+                const int32_t cx = x < 0 ? 0 : x >= W ? W - 1 : x, cy = y < 0 ? 0 : y >= H ? H - 1 : y;
+                const uint32_t bit = 1u << (3 * (cy / TILE_H - ty + 1) + (cx / TILE_W - tx + 1));
+                if ((zstale & bit) == 0u) v = a.z[(size_t)cy * (size_t)W + (size_t)cx];
+            }
+            s_z[r * CONV_LDS_W + c] = v;
+        }
+    }
+    __syncthreads();
+    const int32_t col = (int32_t)threadIdx.x % TILE_W, row0 = (int32_t)threadIdx.x / TILE_W * CONV_ROWS;
+    const uint8_t *s_rt = reinterpret_cast<const uint8_t *>(s_range);
+    // the lane's eight centres, staged: row k of the tile is staged row ry + k
+    uint32_t centre[CONV_ROWS];
+    float zc[CONV_ROWS];
+    BilateralSums m[CONV_ROWS];
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++) {
+        centre[k] = s_bl[(ry + row0 + k) * CONV_LDS_W + 16 + col];
+        zc[k] = GUIDE == 1 ? s_z[(ry + row0 + k) * CONV_LDS_W + 16 + col] : 0.0f;
+        m[k].s = m[k].a[0] = m[k].a[1] = m[k].a[2] = 0u;
+    }
+    for (int32_t i = 0; i < kw; i++) {
+        // the lane's first staged row at the column of the window's column i
+        const int32_t at = row0 * CONV_LDS_W + 16 + col + i - rx;
+        uint32_t wk[CONV_ROWS];  // the spatial weight of the staged row for the lane's row k: row k + 2 ry - jj of the window
+#pragma unroll
+        for (int k = 0; k < CONV_ROWS; k++) wk[k] = 0u;
+        wk[0] = bilateral_spatial(a, i, 2 * ry, kw, kh);
+        for (int32_t jj = 0; jj < CONV_ROWS + 2 * ry; jj++) {
+            const uint32_t w_next = bilateral_spatial(a, i, 2 * ry - jj - 1, kw, kh);
+            const uint32_t tp = s_bl[at + jj * CONV_LDS_W];
+            const float zt = GUIDE == 1 ? s_z[at + jj * CONV_LDS_W] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < CONV_ROWS; k++) {
+                if (wk[k] == 0u) continue;  // (scalar)
+                const uint32_t d = GUIDE == 1 ? bilateral_depth_distance(zt, zc[k], a.rule.depth_scale) : bilateral_colour_distance(tp, centre[k]);
+                bilateral_tap(m[k], mul24(wk[k], (uint32_t)s_rt[d]), tp);
+            }
+#pragma unroll
+            for (int k = CONV_ROWS - 1; k > 0; k--) wk[k] = wk[k - 1];
+            wk[0] = w_next;
+        }
+    }
+    uint32_t res[CONV_ROWS];
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++) res[k] = bilateral_finish_px(m[k], centre[k]);
+    __syncthreads();  // every staged pixel has been read: the results take the place of the first rows
+    uint32_t *s_out = s_bl;
+#pragma unroll
+    for (int k = 0; k < CONV_ROWS; k++) s_out[(row0 + k) * TILE_W + col] = res[k];
+    __syncthreads();
+    if (!share) return;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&s_out[srow * TILE_W + (sx - x0) + 4 * k]);
+        px[4 * k + 0] = v.x, px[4 * k + 1] = v.y, px[4 * k + 2] = v.z, px[4 * k + 3] = v.w;
+    }
+    conv_store_share<STORE>(o, px, n_px);
+}
+
 // Colour grading (tr_scene_grade): every pixel of the frame mapped through the scene's 3-D lookup table into `out`,
 // which may BE the frame (a pixel depends on itself alone); tr_grade.h has the rule.  The working set is the table, not
 // a neighbourhood, so the workgroups are PERSISTENT: the launcher starts as many as the machine holds at once (by the
@@ -5392,7 +5604,7 @@ int launch_bloom(const BloomArgs &a, hipStream_t st)
     return 0;
 }
 
-// What launch_convolve and launch_rank share: the refusals of a stage that reads neighbours (ok), a.words, the store
+// What launch_convolve, launch_rank and launch_bilateral share: the refusals of a stage that reads neighbours (ok), a.words, the store
 // form (k_convolve's STORE) and the LDS of the staged rows.
 struct NeighPlan {
     bool ok;
@@ -5465,6 +5677,29 @@ int launch_rank(const RankArgs &a0, hipStream_t st)
         { k_rank<3, 0>, k_rank<3, 1>, k_rank<3, 2> },
     };
     hipLaunchKernelGGL(kernels[sel][plan.store], dim3(n_tiles), dim3(CONV_THREADS), plan.lds, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_bilateral(const BilateralArgs &a0, hipStream_t st)
+{
+    BilateralArgs a = a0;
+    const uint32_t n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    const NeighPlan plan = neigh_plan(a);
+    const BilateralRule &q = a.rule;
+    const bool depth = q.guide == BILATERAL_GUIDE_DEPTH;
+    if (!plan.ok || q.kw % 2u == 0u || q.kh % 2u == 0u || q.kw > BILATERAL_MAX_SIDE || q.kh > BILATERAL_MAX_SIDE || q.guide > BILATERAL_GUIDE_DEPTH ||
+        q.edge > BILATERAL_CLAMP || (depth && !a.z))
+        return (int)hipErrorInvalidValue;
+    // the staged colour, as much again for the depth, and the range table
+    const size_t lds = plan.lds * (depth ? 2u : 1u) + 256u;
+    // [GUIDE][STORE]
+    static constexpr void (*kernels[2][3])(BilateralArgs) = {
+        { k_bilateral<0, 0>, k_bilateral<0, 1>, k_bilateral<0, 2> },
+        { k_bilateral<1, 0>, k_bilateral<1, 1>, k_bilateral<1, 2> },
+    };
+    hipLaunchKernelGGL(kernels[depth ? 1 : 0][plan.store], dim3(n_tiles), dim3(CONV_THREADS), lds, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp", "k_bilateral" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_BILATERAL, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -2844,15 +2844,15 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, resize, to_yuv, layer, ramp) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
 //   cleared_out_of_place, while in place a cleared frame is its own result and NOTHING happens, handed_on included; the
 //   enqueue_* into the target, into the frame itself, or through the scratch frame (in_place_via_scratch); handed_on.
-//   The frame-sized stages that go through the scratch frame (depth of field, bloom, antialias, convolve, rank) call
+//   The frame-sized stages that go through the scratch frame (depth of field, bloom, antialias, convolve, rank, bilateral) call
 //   scratch_stage after their checks: it is that order from hipSetDevice on.
-//   tr_scene_get_<stage>: the same checks, then get_stage (those five: get_scratch_stage).
+//   tr_scene_get_<stage>: the same checks, then get_stage (those six: get_scratch_stage).
 //   enqueue_*: the stage's queue choice; its arguments (frame_stage_args: the five fields every such kernel takes);
 //   timed_launch -- the launch under Timed, launch_status under the kernel's name, quiescent = false.
 // A refused call has queued nothing and changed nothing, but for the read-back record of a tr_host_alloc `out` that
@@ -5379,6 +5379,93 @@ int tr_rank_host(uint32_t width, uint32_t height, const uint8_t *rgb, uint8_t *o
     if (!rgb || !out) return tr::fail(TR_E_INVALID, "tr_rank_host: null argument");
     if (out == rgb) return tr::fail(TR_E_INVALID, "tr_rank_host: out is rgb (the rule reads neighbours: not in place)");
     rank_host(width, height, rgb, out, rank_rule(q));
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_BILATERAL_GUIDE_COLOUR == BILATERAL_GUIDE_COLOUR && TR_BILATERAL_GUIDE_DEPTH == BILATERAL_GUIDE_DEPTH && TR_BILATERAL_BORDER == BILATERAL_BORDER &&
+                  TR_BILATERAL_CLAMP == BILATERAL_CLAMP && sizeof(tr_bilateral_params) == 512 && sizeof(BilateralParams) == sizeof(tr_bilateral_params) &&
+                  offsetof(tr_bilateral_params, edge) == offsetof(BilateralParams, edge) && offsetof(tr_bilateral_params, depth_scale) == offsetof(BilateralParams, depth_scale) &&
+                  offsetof(tr_bilateral_params, border) == offsetof(BilateralParams, border) && offsetof(tr_bilateral_params, pad) == offsetof(BilateralParams, pad) &&
+                  offsetof(tr_bilateral_params, spatial) == offsetof(BilateralParams, spatial) && offsetof(tr_bilateral_params, pad2) == offsetof(BilateralParams, pad2) &&
+                  offsetof(tr_bilateral_params, range) == offsetof(BilateralParams, range),
+              "tr_bilateral.h restates the header");
+
+// tr_bilateral_params as every entry point accepts them (`who` names the entry point in the error text); *q: tr_bilateral.h's copy.
+int check_bilateral_params(const tr_bilateral_params *p, const char *who, BilateralParams *q)
+{
+    if (!p) return tr::fail(TR_E_INVALID, std::string(who) + ": null argument");
+    memcpy(q, p, sizeof(BilateralParams));
+    const char *why = bilateral_refusal(*q);
+    return why ? tr::fail(TR_E_INVALID, std::string(who) + why) : TR_OK;
+}
+
+int check_bilateral_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be smoothed: "
+                                                         "its border taps lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// Is the rule's image of a black frame black?  A weighted mean of zeros is 0 and S == 0 gives the centre, which is 0 too,
+// under both guides, so: no border colour comes in -- TR_BILATERAL_CLAMP, or a border of 0.
+bool bilateral_of_black_is_black(const BilateralParams &q) { return q.edge == BILATERAL_CLAMP || (q.border[0] | q.border[1] | q.border[2]) == 0u; }
+
+// Enqueues the current frame, filtered, into `out_device` (which overlaps no frame of the scene) behind everything
+// issued so far; out_clean: null, or where k_bilateral writes the flags of `out_device`.  A pending clear is made real
+// first.  The DEPTH guide reads the depth, which is made real; the COLOUR guide reads none: a depth left on the chip
+// stays there.
+int enqueue_bilateral(tr_scene *s, const BilateralParams &q, uint8_t *out_device, uint32_t *out_clean)
+{
+    const bool depth = q.guide == BILATERAL_GUIDE_DEPTH;
+    int st = flush_clear_color(s);
+    if (st == TR_OK) st = submit_pending(s);
+    if (st == TR_OK && depth) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    BilateralArgs a = {};
+    if (depth) a.z = s->d_z, a.zclean = s->d_zclean;
+    frame_stage_args(a, s, out_device, out_clean);
+    a.rule = bilateral_rule(q);
+    return timed_launch(s, K_BILATERAL, "k_bilateral", [&] { return launch_bilateral(a, s->stream); });
+}
+
+}  // namespace
+
+int tr_scene_bilateral(tr_scene *s, const tr_bilateral_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_bilateral: null scene");
+    BilateralParams q;
+    int st = check_bilateral_params(p, "tr_scene_bilateral", &q);
+    if (st == TR_OK) st = check_bilateral_scene(s, "tr_scene_bilateral");
+    if (st != TR_OK) return st;
+    // a logically cleared frame is black, and so is its image where no border colour comes in: zeros out of place, itself in place
+    return scratch_stage(s, out, "tr_scene_bilateral", "tr_scene_get_bilateral", "smooths", bilateral_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_bilateral(s, q, o, clean); });
+}
+
+int tr_scene_get_bilateral(tr_scene *s, const tr_bilateral_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_bilateral: null scene");
+    if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_bilateral: null argument");
+    BilateralParams q;
+    int st = check_bilateral_params(p, "tr_scene_get_bilateral", &q);
+    if (st == TR_OK) st = check_bilateral_scene(s, "tr_scene_get_bilateral");
+    if (st != TR_OK) return st;
+    return get_scratch_stage(s, rgb, bilateral_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_bilateral(s, q, o, clean); });
+}
+
+// The rule of tr_bilateral.h over a caller's arrays, on the host.  Needs no GPU.
+int tr_bilateral_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, uint8_t *out, const tr_bilateral_params *p)
+{
+    BilateralParams q;
+    int st = check_bilateral_params(p, "tr_bilateral_host", &q);
+    if (st != TR_OK) return st;
+    if (width == 0u || height == 0u) return TR_OK;
+    if (!rgb || !out || (!z && q.guide == BILATERAL_GUIDE_DEPTH)) return tr::fail(TR_E_INVALID, "tr_bilateral_host: null argument");
+    if (out == rgb) return tr::fail(TR_E_INVALID, "tr_bilateral_host: out is rgb (the rule reads neighbours: not in place)");
+    bilateral_host(width, height, rgb, z, out, bilateral_rule(q));
     return TR_OK;
 }
 

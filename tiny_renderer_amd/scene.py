@@ -1367,6 +1367,115 @@ def footprint_line(length, degrees):
     return f
 
 
+BILATERAL_GUIDE_COLOUR, BILATERAL_GUIDE_DEPTH, BILATERAL_BORDER, BILATERAL_CLAMP = 0, 1, 0, 1   # (TR_BILATERAL_*)
+BILATERAL_GUIDES = {"colour": BILATERAL_GUIDE_COLOUR, "depth": BILATERAL_GUIDE_DEPTH}
+BILATERAL_EDGES = {"border": BILATERAL_BORDER, "clamp": BILATERAL_CLAMP}
+
+
+class BilateralParams(C.Structure):
+    """tr_bilateral_params"""
+    _fields_ = [("struct_size", C.c_uint32), ("kw", C.c_uint32), ("kh", C.c_uint32), ("guide", C.c_uint32), ("edge", C.c_uint32),
+                ("depth_scale", C.c_float), ("border", C.c_uint8 * 3), ("pad", C.c_uint8), ("spatial", C.c_uint8 * 225),
+                ("pad2", C.c_uint8 * 3), ("range", C.c_uint8 * 256)]
+
+
+def bilateral_params(spatial, range_table, guide="colour", depth_scale=0.0, edge="clamp", border=(0, 0, 0)):
+    """tr_bilateral_params for Scene.bilateral / Scene.get_bilateral / bilateral_host.  spatial: a 2-D integer array
+    [kh, kw] (both odd, 1..15) of weights 0..255, spatial[j][i] being row j from the top, column i from the left; a weight
+    of 0 is no tap (spatial_box and spatial_gaussian build the usual ones).  range_table: 256 weights 0..255, entry d for a
+    tap at distance d from the centre (range_gaussian, range_step).  guide: "colour" (d = the largest channel difference)
+    or "depth" (d = |zT - zC| * depth_scale, cut at 255).  edge: "clamp" or "border" (a tap outside the image is
+    `border`, r g b, and not drawn).  ValueError, in the library's words, for what it would refuse
+    (include/tiny_renderer.h)."""
+    if guide in BILATERAL_GUIDES:
+        g = BILATERAL_GUIDES[guide]
+    elif not isinstance(guide, (bool, str)) and guide in BILATERAL_GUIDES.values():
+        g = int(guide)
+    else:
+        raise ValueError("bilateral: guide must be TR_BILATERAL_GUIDE_COLOUR or TR_BILATERAL_GUIDE_DEPTH")
+    if edge in BILATERAL_EDGES:
+        e = BILATERAL_EDGES[edge]
+    elif not isinstance(edge, (bool, str)) and edge in BILATERAL_EDGES.values():
+        e = int(edge)
+    else:
+        raise ValueError("bilateral: edge must be TR_BILATERAL_BORDER or TR_BILATERAL_CLAMP")
+    b = [int(v) for v in border]
+    if len(b) != 3 or any(not 0 <= v <= 255 for v in b):
+        raise ValueError("bilateral: border is three values 0..255")
+    w = np.asarray(spatial)
+    if w.ndim != 2 or w.dtype.kind not in "biu" or (w.size and (int(w.min()) < 0 or int(w.max()) > 255)):
+        raise ValueError("bilateral: spatial is a 2-D integer array [kh, kw] of weights 0..255")
+    kh, kw = w.shape
+    if kw % 2 == 0 or kh % 2 == 0 or kw > 15 or kh > 15:
+        raise ValueError("bilateral: kw and kh must be odd and 1..15")
+    r = np.asarray(range_table)
+    if r.shape != (256,) or r.dtype.kind not in "biu" or int(r.min()) < 0 or int(r.max()) > 255:
+        raise ValueError("bilateral: range_table is 256 integer weights 0..255")
+    p = BilateralParams(C.sizeof(BilateralParams), kw, kh, g, e, float(depth_scale), (C.c_uint8 * 3)(*b), 0)
+    C.memmove(p.spatial, np.ascontiguousarray(w, np.uint8).ctypes.data, kw * kh)
+    C.memmove(p.range, np.ascontiguousarray(r, np.uint8).ctypes.data, 256)
+    L = load_library()
+    if L.tr_bilateral_host(0, 0, None, None, None, C.addressof(p)) != 0:   # (an empty image: the parameter checks alone)
+        raise ValueError(L.tr_last_error().decode().replace("tr_bilateral_host", "bilateral", 1))
+    return p
+
+
+def bilateral_host(rgb, params, z=None):
+    """tr_bilateral_host: the rule of Scene.bilateral on the host (no GPU needed), by the inline functions k_bilateral
+    shares.  rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), params from bilateral_params, z [H, W] float32 with
+    row 0 = bottom (read_z_f32) -- needed under the depth guide only.  Returns the filtered frame and leaves its arguments
+    alone."""
+    _check_params(params, BilateralParams, "bilateral_host", "bilateral_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3:
+        raise ValueError("bilateral_host: rgb [H, W, 3]")
+    zz = None
+    if z is not None:
+        zz = np.ascontiguousarray(z, np.float32)
+        if zz.shape != src.shape[:2]:
+            raise ValueError("bilateral_host: z [H, W] beside rgb [H, W, 3]")
+    elif params.guide == BILATERAL_GUIDE_DEPTH:
+        raise ValueError("bilateral_host: the depth guide needs z")
+    out = np.empty_like(src)
+    check(load_library().tr_bilateral_host(src.shape[1], src.shape[0], src.ctypes.data, None if zz is None else zz.ctypes.data, out.ctypes.data,
+                                           C.addressof(params)))
+    return out
+
+
+def spatial_box(kw, kh):
+    """[kh, kw] uint8 of 255: every pixel of the window at the same weight (kw and kh odd, 1..15)."""
+    kw, kh = int(kw), int(kh)
+    if kw % 2 == 0 or kh % 2 == 0 or not 1 <= kw <= 15 or not 1 <= kh <= 15:
+        raise ValueError("spatial_box: kw and kh odd and 1..15")
+    return np.full((kh, kw), 255, np.uint8)
+
+
+def spatial_gaussian(radius, sigma):
+    """[2 r + 1, 2 r + 1] uint8: round(255 exp(-(dx^2 + dy^2) / (2 sigma^2))), radius 0..7, sigma above 0; the centre is
+    255, and a weight that rounds to 0 is no tap."""
+    r = int(radius)
+    if not 0 <= r <= 7 or not float(sigma) > 0.0:
+        raise ValueError("spatial_gaussian: sigma above 0, radius 0..7")
+    d = np.arange(-r, r + 1, dtype=np.float64)
+    return np.floor(255.0 * np.exp(-0.5 * np.add.outer(d * d, d * d) / float(sigma) ** 2) + 0.5).astype(np.uint8)
+
+
+def range_gaussian(sigma):
+    """[256] uint8: round(255 exp(-d^2 / (2 sigma^2))) for the distances d = 0..255, sigma above 0."""
+    if not float(sigma) > 0.0:
+        raise ValueError("range_gaussian: sigma above 0")
+    d = np.arange(256, dtype=np.float64)
+    return np.floor(255.0 * np.exp(-0.5 * (d / float(sigma)) ** 2) + 0.5).astype(np.uint8)
+
+
+def range_step(cutoff):
+    """[256] uint8: 255 for the distances d <= cutoff (0..255) and 0 beyond -- only taps within the cutoff count, all alike."""
+    c = int(cutoff)
+    if not 0 <= c <= 255:
+        raise ValueError("range_step: cutoff 0..255")
+    return np.where(np.arange(256) <= c, 255, 0).astype(np.uint8)
+
+
 BLOOM_MAX_RADIUS, BLOOM_GLOW_ONLY, BLOOM_MAX_STRENGTH = 15, 1, 1024   # (TR_BLOOM_MAX_RADIUS, TR_BLOOM_GLOW_ONLY)
 
 
@@ -2292,6 +2401,27 @@ class Scene:
         rank_host(get_frame_buffer(), params) in every byte.  Synchronizes; the scene's frame stays."""
         _check_params(params, RankParams, "get_ranked", "rank_params")
         return self._image("tr_scene_get_ranked", strict, C.addressof(params))
+
+    # --- bilateral (tr_scene_bilateral / tr_scene_get_bilateral) ----------------------------------------
+    def bilateral(self, params, out=None):
+        """tr_scene_bilateral: the current frame through an edge-preserving weighted mean on the device, guided by colour
+        or by the frame's own depth (params from bilateral_params; spatial_box, spatial_gaussian, range_gaussian and
+        range_step build the usual tables).  out=None: in place -- every later consumer (the getters, resize, resolve, the
+        sparse read-back) sees the filtered frame, z, winner words and the shadow buffer stay, calling it twice filters
+        twice.  Otherwise `out` is a torch tensor on the scene's device or a device pointer (int) to 3 * W * H bytes that
+        overlaps no frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.
+        Asynchronous: the result is there after sync().  Band scenes are refused.  The colour guide needs no depth; the
+        depth guide makes a depth left on the chip real."""
+        _check_params(params, BilateralParams, "bilateral", "bilateral_params")
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_bilateral(self._h, C.addressof(params), ptr))
+        return out
+
+    def get_bilateral(self, params, strict=True):
+        """tr_scene_get_bilateral: the current frame filtered on the device, as an [H, W, 3] uint8 array equal to
+        bilateral_host(get_frame_buffer(), params, read_z_f32()) in every byte.  Synchronizes; the scene's frame stays."""
+        _check_params(params, BilateralParams, "get_bilateral", "bilateral_params")
+        return self._image("tr_scene_get_bilateral", strict, C.addressof(params))
 
     # --- YUV output (tr_scene_to_yuv / tr_scene_to_yuv_from / tr_scene_get_yuv) ------------------------
     def to_yuv(self, layout="i420", matrix="bt709", range="limited", strict=True):
