@@ -3169,7 +3169,7 @@ static_assert(BILATERAL_MAX_SIDE / 2u <= 15u && (int)(BILATERAL_MAX_SIDE / 2u) <
 static_assert(2 * (TILE_H + 2 * (int)(BILATERAL_MAX_SIDE / 2u)) * CONV_LDS_W * 4 + 256 < 40 * 1024, "the largest window's LDS is below 40 KB");
 
 // The colour staging of a neighbourhood stage, k_convolve's and k_rank's text in one place (k_bilateral calls it; the two
-// older kernels keep their own copies, whose instruction streams a shared helper would change): the tile at (x0, y0) =
+// older kernels keep their own copies: on shared helpers they measured slower than on these): the tile at (x0, y0) =
 // (tx, ty) and its halo of rx columns and ry rows into s_px as rows of CONV_LDS_W packed pixels (r | g << 8 | b << 16)
 // that start 16 pixels left of the tile.  A texel outside the image is `border`, or under `clamp` the texel at the
 // clamped index; a texel behind a raised flag (czero: bit 3 * ay + ax of the 3 x 3 tiles around) is zeros WITHOUT a load.

@@ -5236,10 +5236,11 @@ ConvolveRule convolve_rule(const tr_convolve_params *p)
     return r;
 }
 
-int check_convolve_scene(const tr_scene *s, const char *who)
+// The scene as the neighbourhood stages (convolve, rank, bilateral) accept it; `verb`: "convolved", "ranked", "smoothed".
+int check_neigh_scene(const tr_scene *s, const char *who, const char *verb)
 {
     if (!whole_frame(s))
-        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be convolved: "
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be " + verb + ": "
                                                          "its border taps lie in another rank's rows");
     if (s->broken) return unusable();
     return TR_OK;
@@ -5272,7 +5273,7 @@ int tr_scene_convolve(tr_scene *s, const tr_convolve_params *p, void *out)
 {
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_convolve: null scene");
     int st = check_convolve_params(p, "tr_scene_convolve");
-    if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_convolve");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_convolve", "convolved");
     if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its image where the rule gives black: zeros out of place, itself in place
     return scratch_stage(s, out, "tr_scene_convolve", "tr_scene_get_convolved", "convolves", convolve_of_black_is_black(p), [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); });
@@ -5283,7 +5284,7 @@ int tr_scene_get_convolved(tr_scene *s, const tr_convolve_params *p, uint8_t *rg
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_convolved: null scene");
     if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_convolved: null argument");
     int st = check_convolve_params(p, "tr_scene_get_convolved");
-    if (st == TR_OK) st = check_convolve_scene(s, "tr_scene_get_convolved");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_get_convolved", "convolved");
     if (st != TR_OK) return st;
     return get_scratch_stage(s, rgb, convolve_of_black_is_black(p), [&](uint8_t *o, uint32_t *clean) { return enqueue_convolve(s, p, o, clean); });
 }
@@ -5318,15 +5319,6 @@ int check_rank_params(const tr_rank_params *p, const char *who, RankParams *q)
     return why ? tr::fail(TR_E_INVALID, std::string(who) + why) : TR_OK;
 }
 
-int check_rank_scene(const tr_scene *s, const char *who)
-{
-    if (!whole_frame(s))
-        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be ranked: "
-                                                         "its border taps lie in another rank's rows");
-    if (s->broken) return unusable();
-    return TR_OK;
-}
-
 // Is the rule's image of a black frame black?  A neighbourhood of zeros is 0 under every op, so: no border colour comes
 // in -- TR_RANK_CLAMP, or a border of 0.
 bool rank_of_black_is_black(const RankParams &q) { return q.edge == RANK_CLAMP || (q.border[0] | q.border[1] | q.border[2]) == 0u; }
@@ -5352,7 +5344,7 @@ int tr_scene_rank(tr_scene *s, const tr_rank_params *p, void *out)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_rank: null scene");
     RankParams q;
     int st = check_rank_params(p, "tr_scene_rank", &q);
-    if (st == TR_OK) st = check_rank_scene(s, "tr_scene_rank");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_rank", "ranked");
     if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its image where no border colour comes in: zeros out of place, itself in place
     return scratch_stage(s, out, "tr_scene_rank", "tr_scene_get_ranked", "ranks", rank_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); });
@@ -5364,7 +5356,7 @@ int tr_scene_get_ranked(tr_scene *s, const tr_rank_params *p, uint8_t *rgb)
     if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_ranked: null argument");
     RankParams q;
     int st = check_rank_params(p, "tr_scene_get_ranked", &q);
-    if (st == TR_OK) st = check_rank_scene(s, "tr_scene_get_ranked");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_get_ranked", "ranked");
     if (st != TR_OK) return st;
     return get_scratch_stage(s, rgb, rank_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_rank(s, q, o, clean); });
 }
@@ -5401,15 +5393,6 @@ int check_bilateral_params(const tr_bilateral_params *p, const char *who, Bilate
     return why ? tr::fail(TR_E_INVALID, std::string(who) + why) : TR_OK;
 }
 
-int check_bilateral_scene(const tr_scene *s, const char *who)
-{
-    if (!whole_frame(s))
-        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be smoothed: "
-                                                         "its border taps lie in another rank's rows");
-    if (s->broken) return unusable();
-    return TR_OK;
-}
-
 // Is the rule's image of a black frame black?  A weighted mean of zeros is 0 and S == 0 gives the centre, which is 0 too,
 // under both guides, so: no border colour comes in -- TR_BILATERAL_CLAMP, or a border of 0.
 bool bilateral_of_black_is_black(const BilateralParams &q) { return q.edge == BILATERAL_CLAMP || (q.border[0] | q.border[1] | q.border[2]) == 0u; }
@@ -5439,7 +5422,7 @@ int tr_scene_bilateral(tr_scene *s, const tr_bilateral_params *p, void *out)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_bilateral: null scene");
     BilateralParams q;
     int st = check_bilateral_params(p, "tr_scene_bilateral", &q);
-    if (st == TR_OK) st = check_bilateral_scene(s, "tr_scene_bilateral");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_bilateral", "smoothed");
     if (st != TR_OK) return st;
     // a logically cleared frame is black, and so is its image where no border colour comes in: zeros out of place, itself in place
     return scratch_stage(s, out, "tr_scene_bilateral", "tr_scene_get_bilateral", "smooths", bilateral_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_bilateral(s, q, o, clean); });
@@ -5451,7 +5434,7 @@ int tr_scene_get_bilateral(tr_scene *s, const tr_bilateral_params *p, uint8_t *r
     if (!rgb) return tr::fail(TR_E_INVALID, "tr_scene_get_bilateral: null argument");
     BilateralParams q;
     int st = check_bilateral_params(p, "tr_scene_get_bilateral", &q);
-    if (st == TR_OK) st = check_bilateral_scene(s, "tr_scene_get_bilateral");
+    if (st == TR_OK) st = check_neigh_scene(s, "tr_scene_get_bilateral", "smoothed");
     if (st != TR_OK) return st;
     return get_scratch_stage(s, rgb, bilateral_of_black_is_black(q), [&](uint8_t *o, uint32_t *clean) { return enqueue_bilateral(s, q, o, clean); });
 }
