@@ -1461,6 +1461,83 @@ int tr_ramp_positions(const tr_ramp_params *p, uint32_t n, uint32_t count, const
  * Returns the number of workgroups of the scene's most recent k_ramp launch (0: there has been none). */
 int tr_scene_debug_ramp_grid(tr_scene *s, uint32_t cap);
 
+/* Lines: a table of straight segments kept on the scene, drawn into the scene's CURRENT frame on the device and
+ * depth-tested against the frame's own z -- a wireframe over or instead of the shaded mesh, a skeleton, a bounding box,
+ * axes, a grid, normals, a camera path, a crosshair, a frame around an inset.  The first stage that draws.
+ * A segment is a tr_line.  Coordinates are the renderer's own raster coordinates (the reference's vertex_t_raster, what
+ * tr_project_points gives): x runs right and y runs UP; pixel (x, y) is frame row H - 1 - y and depth index x + y * W (what
+ * tr_scene_read_z_f32 returns).  Endpoints may lie outside the frame; |x|, |y| <= 2^20; z finite with |z| <= 2^100.
+ *   pixels  dx = x1 - x0, dy = y1 - y0; the major axis is x iff |dx| >= |dy|.  The endpoints are swapped (with their z) iff
+ *           the second one's major coordinate is smaller, so a segment and its reverse cover the same pixels.  With n =
+ *           |d_major| and db = d_minor after the swap, step k = 0..n is major a0 + k, minor b0 + floor((2 k db + n) / (2 n)),
+ *           exactly; n == 0 is the single pixel (x0, y0).  With `width` w = 1..15 a step covers the minor offsets
+ *           -((w - 1) / 2) .. +(w / 2) (butt caps).  Pixels outside the frame are dropped.
+ *   depth   t = (float)k / (float)n (0 if n == 0), z = z0 + (z1 - z0) * t, zl = z + depth_bias: every f32 operation rounded
+ *           once, the quotient correctly, nothing contracted.
+ *   test    with TR_LINES_DEPTH_TEST a candidate survives at a pixel iff !(zl <= zbuf), the reference's own comparison: it
+ *           survives a NaN depth and f32::MIN (nothing drawn).  Without the flag every candidate survives, no depth is read.
+ *   winner  among a pixel's survivors the greatest key wins -- the total order of the bits of zl,
+ *           bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000): the nearest --, ties to the greatest segment index.  With
+ *           TR_LINES_PAINTER the greatest index wins whatever its depth (drawing order).
+ *   output  only the winner touches the pixel: coverage a = rgba[3] * opacity (0..65280), per channel
+ *           (rgb a + d (65280 - a) + 32640) / 65280, the layer rule's NORMAL.  A pixel without a winner keeps d.
+ * Only colour changes: z, winner words and the shadow buffer stay.  A pixel depends on itself and the table alone: the
+ * rule works in place. */
+#define TR_LINES_MAX_N (1u << 20)
+#define TR_LINES_MAX_WIDTH 15u
+#define TR_LINES_DEPTH_TEST 0x1u
+#define TR_LINES_PAINTER 0x2u
+typedef struct tr_line {
+    int32_t x0, y0;
+    float z0;
+    int32_t x1, y1;
+    float z1;
+    uint8_t rgba[4];
+    uint32_t reserved; /* 0 */
+} tr_line;
+typedef struct tr_lines_params {
+    uint32_t width;    /* 1..15 pixels across the minor axis */
+    uint32_t opacity;  /* 0..256 */
+    uint32_t flags;    /* TR_LINES_DEPTH_TEST, TR_LINES_PAINTER */
+    float depth_bias;  /* added to a step's depth before the test and the order; finite.  Nearer is LARGER: > 0 lifts */
+    uint32_t reserved[4]; /* 0 */
+} tr_lines_params;
+/* Sets (copies) the scene's table of n segments, n = 0..TR_LINES_MAX_N, and returns when the copy is done; like
+ * tr_scene_set_ramp it waits for the scene's queued work first, so frames issued so far keep the table they were issued
+ * under.  Every segment is validated, then the table is binned on the host into the 128 x 16 tiles of the frame: a
+ * segment enters exactly the tiles in which one of its pixels at width 15 lies, computed per tile column or row from
+ * the rule itself, so a diagonal across the frame lands in as many lists as it crosses tiles; no list has a capacity.
+ * n == 0 drops the table (lines may then be NULL).  TR_E_INVALID with a tr_last_error text, nothing changed: a NULL
+ * scene, n > TR_LINES_MAX_N, NULL lines with n > 0, a segment (named by its index) with a coordinate beyond +-2^20, a z
+ * that is not finite or beyond 2^100, or reserved not 0; a table whose lists hold 2^32 entries or more. */
+int tr_scene_set_lines(tr_scene *s, uint32_t n, const tr_line *lines);
+/* Draws the table into the current frame.  Asynchronous and ordered like tr_scene_layer: frames held back are submitted,
+ * a pending clear is made real, under TR_LINES_DEPTH_TEST a depth left on the chip is made real (without the flag it
+ * stays there), k_lines is enqueued on the scene's stream; the result is there after tr_scene_sync, and the scene's
+ * passes issued so far count as handed on.
+ * out == NULL: in place, by the kernel itself.  Only the tiles with a list are visited; a tile whose colour fast-clear
+ * flag is up counts as zeros and is stored whole with its flag lowered iff one of its pixels has a winner, otherwise it is
+ * not touched.  Otherwise out: 3 W H bytes of device memory at any byte address or memory from tr_host_alloc, apart from
+ * every frame buffer of the scene; every byte of it is written (the rest of the frame is copied) and the scene's frame
+ * stays as it is.  A logically cleared scene whose table reaches no tile, or opacity == 0, is its own result: zeros out
+ * of place, nothing in place.
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene or params;
+ * width not 1..15; opacity > 256; an unknown flag; depth_bias not finite; reserved not 0; a scene without a table; a BAND
+ * scene (tr_options.band_row0/1); `out` that is ordinary host memory, a pinned block that is too small, or overlaps a
+ * frame buffer of the scene. */
+int tr_scene_lines(tr_scene *s, const tr_lines_params *p, void *out /* or NULL */);
+/* The frame with the lines into any host memory (3 W H bytes): waits for the scene first, draws into a buffer of the
+ * library's, copies out and returns the frame's sticky status, like tr_scene_get_layered.  The scene's frame stays. */
+int tr_scene_get_lined(tr_scene *s, const tr_lines_params *p, uint8_t *rgb);
+/* The rule above on the host (no GPU needed), by the very inline functions k_lines calls.  rgb and out: 3 * width * height
+ * bytes, row 0 = top; out may be rgb.  z: width * height floats, index x + y * width with y UP; read only under
+ * TR_LINES_DEPTH_TEST (may be NULL without it).  The same checks of the parameters and of every segment; width and height
+ * 1..32768; n may be 0 (lines may then be NULL). */
+int tr_lines_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z /* NULL without the test */,
+                  const tr_lines_params *p, uint32_t n, const tr_line *lines, uint8_t *out /* may be rgb */);
+/* For the tests: the number of non-empty tiles and the number of list entries of the scene's table (0 and 0 without one). */
+int tr_scene_debug_line_bins(tr_scene *s, uint32_t *n_tiles, uint64_t *n_entries);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as
@@ -1744,6 +1821,13 @@ typedef struct tr_uniforms {
 int tr_prepare_uniforms(int kind, tr_uniforms *u, uint32_t width, uint32_t height,
                         const float light[3], const float look_from[3],
                         const float look_at[3], const float up[3]);
+/* Host only: n model-space points (xyz: 3 n floats) through u->vpmv with the arithmetic, in the order, of the draw
+ * chain's vertex transform (store_vertex_transformation_results, shader.rs:150-165): the matrix product column by
+ * column, the homogeneous divide, then `as i32` of x and y (truncating, saturating).  xy[2 k], xy[2 k + 1] and z[k] are
+ * therefore the pixel and the depth the renderer gives a mesh vertex at that point: endpoints for a tr_line.  ok[k] = 0
+ * (and xy, z of it 0) where w is 0, a coordinate leaves +-2^20 or z is not finite within 2^100 -- what
+ * tr_scene_set_lines would refuse --, else 1. */
+int tr_project_points(const tr_uniforms *u, uint32_t n, const float *xyz, int32_t *xy, float *z, uint8_t *ok);
 
 /* Asset loading (app.rs:87-131): obj-rs `parse_obj` and image `open(..).into_rgb8()`
  * counterparts.  Returned objects are owned by the library; free with the matching call. */

@@ -194,6 +194,12 @@ SYMBOLS = {
     "tr_ramp_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_ramp_positions": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_debug_ramp_grid": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "tr_scene_set_lines": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_lines": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_lined": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_lines_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_debug_line_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_project_points": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

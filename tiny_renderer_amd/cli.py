@@ -118,6 +118,15 @@ def main(argv=None):
     ap.add_argument("--outline-colour", default="0,0,0", metavar="r,g,b", help="the ink (default 0,0,0)")
     ap.add_argument("--outline-opacity", type=int, default=256, metavar="N", help="the ink covers N / 256 of the picture (0..256, default 256)")
     ap.add_argument("--outline-only", action="store_true", help="with --outline: the lines alone, on white paper")
+    ap.add_argument("--wireframe", nargs="?", const="255,255,255", default=None, metavar="R,G,B[,A]",
+                    help="lines: the mesh's edges drawn over the frame on the GPU, hidden behind the model by the frame's own depth "
+                         "(Scene.set_lines through wireframe_lines, Scene.lines; after --outline, before --aa, which smooths them)")
+    ap.add_argument("--wire-width", type=int, default=1, metavar="N", help="with --wireframe: the lines' width in pixels, 1..15 (default 1)")
+    ap.add_argument("--wire-bias", type=float, default=0.5, metavar="F",
+                    help="with --wireframe: added to the lines' depth before the test; nearer is larger, so a positive bias lifts an "
+                         "edge off its own surface (default 0.5: DESIGN.md 7za has the sweep it was chosen on)")
+    ap.add_argument("--wire-xray", action="store_true", help="with --wireframe: no depth test, the far side shows through")
+    ap.add_argument("--wire-only", action="store_true", help="with --wireframe: clear the frame, then draw the lines alone (no depth test)")
     ap.add_argument("--aa", action="store_true",
                     help="edge anti-aliasing: smooth the picture's stair-steps at its own size by a luma-driven edge filter on the GPU "
                          "(Scene.antialias; after --outline, so the ink's edges are smoothed too, and before --ssaa resolves)")
@@ -304,6 +313,22 @@ def main(argv=None):
             ink = [int(v) for v in args.outline_colour.split(",")]
             args.outline_params = outline_params(args.outline, depth_step=args.outline_depth, crease=args.outline_crease, ink=ink,
                                                  opacity=args.outline_opacity, only=args.outline_only)
+        except ValueError as e:
+            ap.error(str(e))
+    args.wire_colour = None
+    if args.wireframe is None and (args.wire_width != 1 or args.wire_bias != 0.5 or args.wire_xray or args.wire_only):
+        ap.error("--wire-width, --wire-bias, --wire-xray and --wire-only go with --wireframe")
+    if args.wireframe is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame" or args.frames != 1 or args.shutter:
+            ap.error("--wireframe draws over one frame of one GPU under its camera: use --gpus 1, --frames 1 and --view frame")
+        try:
+            args.wire_colour = tuple(int(v) for v in args.wireframe.split(","))
+            if len(args.wire_colour) not in (3, 4) or min(args.wire_colour) < 0 or max(args.wire_colour) > 255:
+                raise ValueError("--wireframe takes R,G,B[,A] with values 0..255")
+            if not 1 <= args.wire_width <= 15:
+                raise ValueError("--wire-width takes 1..15")
+            if not np.isfinite(np.float32(args.wire_bias)):
+                raise ValueError("--wire-bias must be finite")
         except ValueError as e:
             ap.error(str(e))
     args.aa_params = None
@@ -539,6 +564,7 @@ def main(argv=None):
     else:
         say("loading model from: %s/model.obj" % args.asset_path)
         mesh, texs = T.load_assets(args.asset_path)
+    args.mesh = mesh
     say("number of vertices in a model: %d" % mesh["pos"].shape[0])
     say("number of polygons in a model: %d" % mesh["idx"].shape[0])
     say("cooking up a scene with '%s' shader pipeline" % args.pipeline)
@@ -802,6 +828,13 @@ def _post(args, T, scene, say):
         scene.grade()
     if args.outline_params is not None:
         scene.outline(args.outline_params)
+    if args.wire_colour is not None:
+        # in place, after the outlines and before the filter, which smooths the lines; --wire-only clears first: the lines
+        # then stand alone on black and no depth is read
+        scene.set_lines(T.wireframe_lines(scene, args.mesh, args.wire_colour))
+        if args.wire_only:
+            scene.clear()
+        scene.lines(args.wire_width, depth_test=not (args.wire_xray or args.wire_only), depth_bias=args.wire_bias)
     if args.aa_params is not None:
         scene.antialias(args.aa_params)
     for grid, wp in args.warps:   # in place: --stats, --ssaa and --out-size see the warped frame

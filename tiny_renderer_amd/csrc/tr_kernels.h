@@ -17,6 +17,7 @@
 #include "tr_grade.h"
 #include "tr_layer.h"
 #include "tr_ramp.h"
+#include "tr_lines.h"
 #include "tr_morph.h"
 #include "tr_outline.h"
 #include "tr_pack.h"
@@ -143,6 +144,12 @@ int launch_layer(const LayerArgs &a, bool from_scene, hipStream_t st);
 // whole frame only (no band); the caller has made the depth real.  a.lower: null, or a.fbclean (in place): the flags of
 // the flagged tiles stored whole come down.  cap and *grid as for launch_grade (tr_scene_debug_ramp_grid).
 int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
+// Lines: the table a.lines drawn into a.fb by its per-tile lists (a.offsets, a.entries; tr_lines.h has the rule and the
+// binning), into a.out -- a.fb itself or a buffer apart from it, at any byte address --, through the frame's fast-clear
+// flags of colour and, under LINES_DEPTH_TEST, of z: k_lines.  The whole frame only (no band); under the test the caller
+// has made the depth real.  In place one workgroup per entry of a.tiles (n_listed of them: the non-empty tiles; none, or
+// opacity 0: nothing is launched); out of place one per tile.  a.lower: null, or a.fbclean (in place).
+int launch_lines(const LinesArgs &a, uint32_t n_listed, hipStream_t st);
 // Convolve: a.fb filtered through the integer kernel a.rule into a.out (which does not overlap it) by the rule of
 // tr_convolve.h, through the scene's colour fast-clear flags: k_convolve.  The whole frame only (no band); no depth is
 // read.  a.words and a.rule.mul24 are set here.  a.out_clean: null, or where each workgroup writes the flag of its tile

@@ -3771,6 +3771,144 @@ __global__ __launch_bounds__(RAMP_THREADS) void k_ramp(RampArgs a)
     }
 }
 
+// Lines (tr_scene_lines): the scene's table of segments drawn into the frame, depth-tested against the frame's own z,
+// into `out`, which may BE the frame (a pixel depends on itself and the table alone); tr_lines.h has the rule.  The first
+// kernel here that SCATTERS: a segment's steps land on pixels, and a pixel's winner is a maximum over what lands on it.
+// One workgroup of 256 lanes per 128 x 16 tile: in place over the non-empty tiles alone (a.tiles, the host knows them: the
+// grid is exact), out of place over every tile -- the rest is copied, as k_layer does.
+//   * a tile with a list clears 2048 u64 words in LDS (16 KB) and, under TEST, stages its z (8 KB; f32::MIN without a
+//     load behind a raised z flag or outside the frame), then walks its list: WAVES take segments (the list index and so
+//     the segment's 32 bytes are wave-uniform), LANES take steps k, clipped first to the tile's range along the segment's
+//     major axis, so the part of a long segment outside the tile costs nothing; a step loops over the width's minor
+//     offsets, and every candidate inside the tile that survives the test offers its word by an LDS atomicMax.  A maximum
+//     does not care in which order the lanes arrive: the device equals the host in every byte;
+//   * behind a barrier a pixel with a non-zero word fetches its winner's colour and blends (layer_px<NORMAL>); units as
+//     in k_layer: four pixels of a row, two units a lane, WORDS: three aligned words, otherwise guarded bytes;
+//   * in place an unflagged tile stores only the units with a winner; a tile behind a raised colour flag counts as zeros
+//     and, iff it has a pixel with a winner (one __syncthreads_or), is stored whole and lane 0 lowers the flag behind a
+//     barrier -- otherwise it is not touched.
+// z, winner words, the shadow buffer and every flag but the one lowered are left alone.  No inline assembly, no scratch.
+constexpr int LINES_THREADS = 256, LINES_WAVES = LINES_THREADS / 64, LINES_UNITS = TILE_W * TILE_H / 4 / LINES_THREADS;
+
+template <bool WORDS, bool TEST>
+__global__ __launch_bounds__(LINES_THREADS) void k_lines(LinesArgs a)
+{
+    static_assert(TILE_W == 128 && LINES_UNITS == 2 && TILE_H == 16, "32 units to a row of a tile, two rounds of eight rows");
+    __shared__ unsigned long long s_word[TILE_W * TILE_H];
+    __shared__ float s_z[TEST ? TILE_W * TILE_H : 1];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t t = a.tiles != nullptr ? a.tiles[blockIdx.x] : blockIdx.x;  // (workgroup-uniform)
+    const uint32_t tx = t % a.frame.ntx, ty = t / a.frame.ntx;
+    const bool in_place = a.out == a.fb;
+    const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+    const uint32_t e0 = a.offsets[t], e1 = a.offsets[t + 1u];
+    const bool listed = e1 > e0 && a.rule.opacity != 0u;            // (workgroup-uniform)
+    const int32_t tx0 = (int32_t)tx * TILE_W, ty0 = (int32_t)ty * TILE_H;
+    const int32_t tw = min(TILE_W, W - tx0), th = min(TILE_H, H - ty0);  // the tile inside the frame
+    if (listed) {
+        const bool z_clean = TEST && a.zclean[t] != 0u;  // (workgroup-uniform) nothing is drawn in the tile
+        for (int32_t i = (int32_t)threadIdx.x; i < TILE_W * TILE_H; i += LINES_THREADS) {
+            s_word[i] = 0ull;
+            if (TEST) {
+                const int32_t lx = i % TILE_W, ly = i / TILE_W;
+                float v = bits_f32(TR_F32_MIN_BITS);
+                if (!z_clean && lx < tw && ly < th) v = a.z[(size_t)(ty0 + ly) * (size_t)W + (size_t)(tx0 + lx)];
+                s_z[i] = v;
+            }
+        }
+        __syncthreads();
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64u));
+        const int32_t lane = (int32_t)(threadIdx.x % 64u);
+        const int32_t o_lo = -(((int32_t)a.rule.width - 1) / 2), o_hi = (int32_t)a.rule.width / 2;
+        for (uint32_t e = e0 + wave; e < e1; e += (uint32_t)LINES_WAVES) {
+            const uint32_t index = a.entries[e];
+            const LineGeom g = lines_geom(a.lines[index]);
+            const Recip rn = lines_recip(g);
+            int32_t ks, ke;  // the steps inside the tile's range along the major axis
+            if (g.xmajor) lines_steps(g, tx0, tx0 + tw - 1, &ks, &ke);
+            else lines_steps(g, ty0, ty0 + th - 1, &ks, &ke);
+            for (int32_t k = ks + lane; k <= ke; k += 64) {
+                const int32_t bc = lines_minor(g, k);
+                const float zl = lines_depth(g, k, rn, a.rule.bias);
+                const unsigned long long word = lines_word(zl, index, a.rule.flags);
+                for (int32_t o = o_lo; o <= o_hi; o++) {
+                    const int32_t lx = (g.xmajor ? g.a0 + k : bc + o) - tx0, ly = (g.xmajor ? bc + o : g.a0 + k) - ty0;
+                    if (lx < 0 || lx >= tw || ly < 0 || ly >= th) continue;
+                    const int32_t p = ly * TILE_W + lx;  // (0 .. 2047: inside both arrays)
+                    if (TEST && !lines_survives(zl, s_z[p])) continue;
+                    atomicMax(&s_word[p], word);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    const int32_t x = tx0 + 4 * (int32_t)(threadIdx.x % 32u), row_first = ty0 + (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = min(4, W - x);  // (WORDS: 4, or the unit is outside)
+    uint32_t win[LINES_UNITS][4];        // the winner's index + 1, or 0
+    bool any = false;
+#pragma unroll
+    for (int h = 0; h < LINES_UNITS; h++) {
+        const int32_t y = row_first + 8 * h;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            win[h][i] = 0u;
+            if (listed && y < H && i < n_px) win[h][i] = (uint32_t)s_word[(y - ty0) * TILE_W + (x - tx0) + i];
+            any = any || win[h][i] != 0u;
+        }
+    }
+    if (in_place) {
+        if (!listed) return;
+        if (clean && __syncthreads_or(any ? 1 : 0) == 0) return;  // (workgroup-uniform) no winner: the flag stays up
+    }
+    const bool store_all = !in_place || clean;
+#pragma unroll
+    for (int h = 0; h < LINES_UNITS; h++) {
+        const int32_t y = row_first + 8 * h, r = H - 1 - y;
+        if (x >= W || y >= H) continue;
+        const bool unit_any = (win[h][0] | win[h][1] | win[h][2] | win[h][3]) != 0u;
+        if (!store_all && !unit_any) continue;
+        const size_t ci = ((size_t)r * (size_t)W + (size_t)x) * 3u;
+        uint32_t d[4] = { 0u, 0u, 0u, 0u };
+        if (!clean) {
+            const uint8_t *q = a.fb + ci;
+            if (WORDS) {
+                const uint32_t *qw = reinterpret_cast<const uint32_t *>(q);
+                const uint32_t w0 = qw[0], w1 = qw[1], w2 = qw[2];
+                d[0] = w0 & 0xFFFFFFu;
+                d[1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                d[2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                d[3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) d[i] = grade_pack(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (win[h][i] != 0u) d[i] = lines_px(a.lines[win[h][i] - 1u].rgba, d[i], a.rule.opacity);
+        uint8_t *o = a.out + ci;
+        if (WORDS) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = d[0] | (d[1] << 24);
+            ow[1] = (d[1] >> 8) | (d[2] << 16);
+            ow[2] = (d[2] >> 16) | (d[3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(d[i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((d[i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((d[i] >> 16) & 0xFFu);
+                }
+        }
+    }
+    if (in_place && clean && a.lower != nullptr) {  // (workgroup-uniform) the tile holds the lines over zeros now
+        __syncthreads();
+        if (threadIdx.x == 0u) a.lower[t] = 0u;
+    }
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -5835,6 +5973,41 @@ int launch_layer(const LayerArgs &a_in, bool from_scene, hipStream_t st)
     else if (q.format == LAYER_RGBA8) LAYER_LAUNCH((int)LAYER_RGBA8)
     else LAYER_LAUNCH((int)LAYER_RGB8)
 #undef LAYER_LAUNCH
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_lines(const LinesArgs &a_in, uint32_t n_listed, hipStream_t st)
+{
+    LinesArgs a = a_in;
+    const uint32_t W = a.frame.width, H = a.frame.height, n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    if (!a.fb || !a.out || !a.lines || !a.offsets || !a.entries || !a.tiles || n_listed > n_tiles) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (the flags and the lists are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    const LinesRule &q = a.rule;
+    if (q.width < 1u || q.width > LINES_MAX_WIDTH || q.opacity > 256u || (q.flags & ~(LINES_DEPTH_TEST | LINES_PAINTER)) != 0u) return (int)hipErrorInvalidValue;
+    const bool test = (q.flags & LINES_DEPTH_TEST) != 0u;
+    if (test && (!a.z || !a.zclean)) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    uint32_t grid = n_tiles;
+    if (a.out == a.fb) {
+        // in place: the non-empty tiles, one workgroup each
+        if (n_listed == 0u || q.opacity == 0u) return 0;
+        grid = n_listed;
+    } else {
+        a.tiles = nullptr;  // (workgroup t takes tile t: the tiles without a list are copied)
+    }
+    // whole words: every unit of four pixels is three aligned words of either buffer
+    const bool words = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u;
+    if (words && test) hipLaunchKernelGGL((k_lines<true, true>), dim3(grid), dim3(LINES_THREADS), 0, st, a);
+    else if (words) hipLaunchKernelGGL((k_lines<true, false>), dim3(grid), dim3(LINES_THREADS), 0, st, a);
+    else if (test) hipLaunchKernelGGL((k_lines<false, true>), dim3(grid), dim3(LINES_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((k_lines<false, false>), dim3(grid), dim3(LINES_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp", "k_bilateral" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_BILATERAL, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp", "k_bilateral", "k_lines" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_BILATERAL, K_LINES, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -407,6 +407,12 @@ struct tr_scene {
     // pieces.  ramp_n == 0: no table.  tr_scene_debug_ramp_grid: the cap and the last grid, as for k_grade
     uint32_t *d_ramp = nullptr;
     uint32_t ramp_n = 0, ramp_cap = 0, ramp_grid = 0;
+    // tr_scene_set_lines: the table and its bins in ONE device block of words, so that it changes hands at once -- the
+    // lines_n segments (8 words each), n_tiles + 1 list offsets, the lines_listed non-empty tiles, the lines_entries
+    // list entries, in this order.  lines_n == 0: no table
+    uint32_t *d_lines = nullptr;
+    uint32_t lines_n = 0, lines_listed = 0;
+    uint64_t lines_entries = 0;
     // tr_scene_resize: the two axes' tables of the last (width, height, filter) asked for (width == 0: none) in one device
     // block `d`, the page-locked block `h` they are uploaded from and the event behind the last upload (resize_tables);
     // shape, y_span and x_span: what launch_resize wants to know of them
@@ -2544,6 +2550,7 @@ void destroy(tr_scene *s)
     dev_free(s->d_dof_clean);
     dev_free(s->d_lut);
     dev_free(s->d_ramp);
+    dev_free(s->d_lines);
     dev_free(s->resize.d);
     if (s->resize.h) (void)hipHostFree(s->resize.h);
     if (s->resize.uploaded) (void)hipEventDestroy(s->resize.uploaded);
@@ -2844,7 +2851,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -6009,6 +6016,186 @@ int tr_scene_debug_ramp_grid(tr_scene *s, uint32_t cap)
     if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_ramp_grid: null scene");
     s->ramp_cap = cap;
     return (int)s->ramp_grid;
+}
+
+namespace {
+
+static_assert(TR_LINES_MAX_N == LINES_MAX_N && TR_LINES_MAX_WIDTH == LINES_MAX_WIDTH && TR_LINES_DEPTH_TEST == LINES_DEPTH_TEST &&
+                  TR_LINES_PAINTER == LINES_PAINTER && sizeof(tr_lines_params) == 32 && sizeof(tr_line) == sizeof(Line) &&
+                  offsetof(tr_line, z0) == offsetof(Line, z0) && offsetof(tr_line, x1) == offsetof(Line, x1) && offsetof(tr_line, z1) == offsetof(Line, z1) &&
+                  offsetof(tr_line, rgba) == offsetof(Line, rgba) && offsetof(tr_line, reserved) == offsetof(Line, reserved),
+              "tr_lines.h restates the header");
+
+// tr_lines_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_lines_params(const tr_lines_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->width < 1u || p->width > TR_LINES_MAX_WIDTH) return tr::fail(TR_E_INVALID, w + ": width must be 1..15");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if ((p->flags & ~(TR_LINES_DEPTH_TEST | TR_LINES_PAINTER)) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (!std::isfinite(p->depth_bias)) return tr::fail(TR_E_INVALID, w + ": depth_bias must be finite");
+    if (p->reserved[0] != 0u || p->reserved[1] != 0u || p->reserved[2] != 0u || p->reserved[3] != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    return TR_OK;
+}
+
+// A table of n segments as tr_scene_set_lines and tr_lines_host accept it.
+int check_lines_table(uint32_t n, const tr_line *lines, const char *who)
+{
+    const std::string w(who);
+    if (n > LINES_MAX_N) return tr::fail(TR_E_INVALID, w + ": the table's length n must be 0..TR_LINES_MAX_N");
+    if (n != 0u && !lines) return tr::fail(TR_E_INVALID, w + ": null table");
+    for (uint32_t i = 0; i < n; i++)
+        if (const char *why = lines_refusal(reinterpret_cast<const Line *>(lines)[i]))
+            return tr::fail(TR_E_INVALID, w + ": segment " + std::to_string(i) + ": " + why);
+    return TR_OK;
+}
+
+int check_lines_scene(const tr_scene *s, const char *who)
+{
+    if (s->lines_n == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no table of lines (tr_scene_set_lines)");
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot take lines: "
+                                                         "the table is binned over the whole frame");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+LinesRule lines_rule(const tr_lines_params *p)
+{
+    LinesRule r;
+    r.width = p->width, r.opacity = p->opacity, r.flags = p->flags, r.bias = p->depth_bias;
+    return r;
+}
+
+// Does nothing reach the frame: a table whose lists are empty, or no coverage?
+bool lines_draw_nothing(const tr_scene *s, const LinesRule &r) { return s->lines_entries == 0u || r.opacity == 0u; }
+
+// Enqueues the table drawn over the current frame into `out_device` (null: in place) behind everything issued so far.  A
+// pending clear is made real (the kernel then runs on raised flags).  Depth is needed only under the test; without it a
+// depth left on the chip stays there.
+int enqueue_lines(tr_scene *s, const LinesRule &r, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK && (r.flags & LINES_DEPTH_TEST)) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    LinesArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    if (r.flags & LINES_DEPTH_TEST) a.z = s->d_z, a.zclean = s->d_zclean;
+    a.lines = reinterpret_cast<const Line *>(s->d_lines);
+    a.offsets = s->d_lines + (size_t)s->lines_n * 8u;
+    a.tiles = a.offsets + (size_t)s->n_tiles + 1u;
+    a.entries = a.tiles + s->lines_listed;
+    a.frame = s->frame;
+    a.rule = r;
+    return timed_launch(s, K_LINES, "k_lines", [&] { return launch_lines(a, s->lines_listed, s->stream); });
+}
+
+}  // namespace
+
+int tr_scene_set_lines(tr_scene *s, uint32_t n, const tr_line *lines)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_set_lines: null scene");
+    int st = check_lines_table(n, lines, "tr_scene_set_lines");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> block;
+    std::vector<uint32_t> entries, tiles;
+    if (n != 0u) {
+        std::vector<uint64_t> offsets;
+        lines_bin(s->width, s->height, n, reinterpret_cast<const Line *>(lines), offsets, entries, tiles);
+        if (offsets.back() > 0xFFFFFFFFull) return tr::fail(TR_E_INVALID, "tr_scene_set_lines: the table's lists hold 2^32 entries or more");
+        if (offsets.size() != (size_t)s->n_tiles + 1u) return tr::fail(TR_E_INVALID, "tr_scene_set_lines: a band scene (tr_options.band_row0/1) cannot take lines");
+        block.resize((size_t)n * 8u + offsets.size() + tiles.size() + entries.size());
+        uint32_t *at = block.data();
+        memcpy(at, lines, (size_t)n * 32u), at += (size_t)n * 8u;
+        for (uint64_t o : offsets) *at++ = (uint32_t)o;
+        if (!tiles.empty()) memcpy(at, tiles.data(), tiles.size() * 4u), at += tiles.size();
+        if (!entries.empty()) memcpy(at, entries.data(), entries.size() * 4u);
+    }
+    st = swap_device_array(s, s->d_lines, n != 0u, block.data(), block.size());
+    if (st != TR_OK) return st;
+    s->lines_n = n;
+    s->lines_listed = (uint32_t)tiles.size();
+    s->lines_entries = entries.size();
+    return TR_OK;
+}
+
+int tr_scene_lines(tr_scene *s, const tr_lines_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_lines: null scene");
+    int st = check_lines_params(p, "tr_scene_lines");
+    if (st == TR_OK) st = check_lines_scene(s, "tr_scene_lines");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_lines", "tr_scene_get_lined", "draws", 0u, &target);
+    if (st != TR_OK) return st;
+    const LinesRule r = lines_rule(p);
+    if (lines_draw_nothing(s, r)) {
+        // nothing is drawn: in place nothing happens, out of place a copy -- of black without a kernel
+        if (!target) return TR_OK;
+        if (s->z_fb_cleared) return cleared_out_of_place(s, target);
+    }
+    st = enqueue_lines(s, r, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_lined(tr_scene *s, const tr_lines_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_lined: null scene");
+    int st = check_lines_params(p, "tr_scene_get_lined");
+    if (st == TR_OK && !rgb) st = tr::fail(TR_E_INVALID, "tr_scene_get_lined: null argument");
+    if (st == TR_OK) st = check_lines_scene(s, "tr_scene_get_lined");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const LinesRule r = lines_rule(p);
+    // (a cleared scene is zeros only where nothing is drawn)
+    return get_stage(s, rgb, frame_bytes(s), lines_draw_nothing(s, r) ? cleared : nullptr, [&](uint8_t *o) { return enqueue_lines(s, r, o); });
+}
+
+// The rule of tr_lines.h over caller's arrays, on the host.  Needs no GPU.
+int tr_lines_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_lines_params *p, uint32_t n, const tr_line *lines,
+                  uint8_t *out)
+{
+    int st = check_lines_params(p, "tr_lines_host");
+    if (st == TR_OK) st = check_lines_table(n, lines, "tr_lines_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || height < 1u || width > 32768u || height > 32768u)
+        return tr::fail(TR_E_INVALID, "tr_lines_host: the frame's width and height must be 1..32768");
+    if (!rgb || !out || ((p->flags & TR_LINES_DEPTH_TEST) && !z)) return tr::fail(TR_E_INVALID, "tr_lines_host: null argument");
+    lines_host(width, height, rgb, z, lines_rule(p), n, reinterpret_cast<const Line *>(lines), out);
+    return TR_OK;
+}
+
+int tr_scene_debug_line_bins(tr_scene *s, uint32_t *n_tiles, uint64_t *n_entries)
+{
+    if (!s || !n_tiles || !n_entries) return tr::fail(TR_E_INVALID, "tr_scene_debug_line_bins: null argument");
+    *n_tiles = s->lines_listed;
+    *n_entries = s->lines_entries;
+    return TR_OK;
+}
+
+// A model-space point as the draw chain's vertex transform places it (project_vertex, tr_shaders.h).  Needs no GPU.
+int tr_project_points(const tr_uniforms *u, uint32_t n, const float *xyz, int32_t *xy, float *z, uint8_t *ok)
+{
+    if (!u) return tr::fail(TR_E_INVALID, "tr_project_points: null argument");
+    if (n == 0u) return TR_OK;
+    if (!xyz || !xy || !z || !ok) return tr::fail(TR_E_INVALID, "tr_project_points: null argument");
+    for (uint32_t k = 0; k < n; k++) {
+        int32_t px = 0, py = 0;
+        float pz = 0.0f;
+        bool good = project_vertex(u->vpmv, make3(xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]), px, py, pz);
+        good = good && px >= -LINES_COORD_MAX && px <= LINES_COORD_MAX && py >= -LINES_COORD_MAX && py <= LINES_COORD_MAX && fabsf(pz) <= TR_LINES_Z_MAX;
+        xy[2 * k] = good ? px : 0, xy[2 * k + 1] = good ? py : 0;
+        z[k] = good ? pz : 0.0f;
+        ok[k] = good ? 1u : 0u;
+    }
+    return TR_OK;
 }
 
 namespace {

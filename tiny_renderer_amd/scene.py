@@ -956,6 +956,151 @@ def ramp_slice(n, lo, hi, colour=(255, 255, 255)):
     return out
 
 
+LINES_MAX_N, LINES_MAX_WIDTH, LINES_DEPTH_TEST, LINES_PAINTER, LINES_COORD_MAX = 1 << 20, 15, 1, 2, 1 << 20   # (TR_LINES_*)
+# tr_line as a numpy record: 32 bytes
+LINE_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("z0", "<f4"), ("x1", "<i4"), ("y1", "<i4"), ("z1", "<f4"), ("rgba", "u1", (4,)), ("reserved", "<u4")])
+
+
+class LinesParams(C.Structure):
+    """tr_lines_params"""
+    _fields_ = [("width", C.c_uint32), ("opacity", C.c_uint32), ("flags", C.c_uint32), ("depth_bias", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+def lines_params(width=1, opacity=256, depth_test=True, painter=False, depth_bias=0.0, who="lines"):
+    """tr_lines_params for Scene.lines / get_lined / lines_host: width 1..15 pixels across the minor axis, opacity 0..256,
+    depth_test: a candidate survives iff !(z + depth_bias <= zbuf); painter: the greatest segment index wins whatever its
+    depth; depth_bias: added to every step's depth (nearer is larger: > 0 lifts a line off its surface).  ValueError, in
+    the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= width <= LINES_MAX_WIDTH:
+        raise ValueError("%s: width must be 1..15" % who)
+    if isinstance(opacity, bool) or not isinstance(opacity, (int, np.integer)) or not 0 <= opacity <= 256:
+        raise ValueError("%s: opacity must be 0..256" % who)
+    with np.errstate(over="ignore"):
+        b32 = np.float32(float(depth_bias))
+    if not np.isfinite(b32):
+        raise ValueError("%s: depth_bias must be finite" % who)
+    return LinesParams(int(width), int(opacity), (LINES_DEPTH_TEST if depth_test else 0) | (LINES_PAINTER if painter else 0), float(b32),
+                       (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+def _lines_table(lines, who):
+    """A table of segments as the library takes it: a contiguous LINE_DTYPE array of 0..2^20 records."""
+    if not isinstance(lines, np.ndarray) or lines.dtype != LINE_DTYPE or lines.ndim != 1:
+        raise ValueError("%s: the table must be a one-dimensional array of LINE_DTYPE records (lines_table builds one)" % who)
+    if lines.shape[0] > LINES_MAX_N:
+        raise ValueError("%s: the table's length n must be 0..TR_LINES_MAX_N" % who)
+    return np.ascontiguousarray(lines)
+
+
+def lines_table(xy0, z0, xy1, z1, colour=(255, 255, 255, 255)):
+    """A table for Scene.set_lines / lines_host from endpoints in raster coordinates (x right, y UP, what Scene.project
+    gives): xy0, xy1 integer [n, 2], z0, z1 float [n]; colour: one (r, g, b[, a]) or an [n, 3 or 4] array."""
+    a, b = np.asarray(xy0), np.asarray(xy1)
+    if a.ndim != 2 or a.shape[1] != 2 or b.shape != a.shape:
+        raise ValueError("lines_table: xy0 and xy1 are [n, 2]")
+    n = a.shape[0]
+    za, zb = np.asarray(z0, np.float32).reshape(-1), np.asarray(z1, np.float32).reshape(-1)
+    if za.shape[0] != n or zb.shape[0] != n:
+        raise ValueError("lines_table: z0 and z1 are [n]")
+    c = np.asarray(colour)
+    if c.ndim == 1:
+        c = np.broadcast_to(c, (n, c.shape[0]))
+    if c.ndim != 2 or c.shape[0] != n or c.shape[1] not in (3, 4) or (c.size and (c.min() < 0 or c.max() > 255)):
+        raise ValueError("lines_table: colour is (r, g, b[, a]) or [n, 3 or 4] with values 0..255")
+    t = np.zeros(n, LINE_DTYPE)
+    t["x0"], t["y0"], t["z0"], t["x1"], t["y1"], t["z1"] = a[:, 0], a[:, 1], za, b[:, 0], b[:, 1], zb
+    t["rgba"][:, :c.shape[1]] = c
+    if c.shape[1] == 3:
+        t["rgba"][:, 3] = 255
+    return t
+
+
+def lines_host(rgb, z, lines, params, in_place=False):
+    """tr_lines_host: the rule of Scene.lines on the host (no GPU needed), by the inline functions k_lines calls.  rgb
+    [H, W, 3] uint8 with row 0 = top (get_frame_buffer), z [H, W] float32 with row 0 = bottom (read_z_f32; None is allowed
+    without the depth test), lines a LINE_DTYPE array, params from lines_params.  Returns the frame with the lines and
+    leaves its arguments alone; in_place=True hands the library one buffer as rgb and out, which the rule allows."""
+    _check_params(params, LinesParams, "lines_host", "lines_params")
+    tab = _lines_table(lines, "lines_host")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError("lines_host: rgb [H, W, 3] and z [H, W]")
+    zz = None
+    if z is not None:
+        zz = np.ascontiguousarray(z, np.float32)
+        if zz.shape != src.shape[:2]:
+            raise ValueError("lines_host: rgb [H, W, 3] and z [H, W]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_lines_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data,
+                                       zz.ctypes.data if zz is not None else None, C.addressof(params), tab.shape[0],
+                                       tab.ctypes.data if tab.shape[0] else None, out.ctypes.data))
+    return out
+
+
+def project_points(uniforms, points):
+    """tr_project_points: model-space points [n, 3] through uniforms.vpmv (prepare_uniforms) exactly as the draw chain
+    transforms a vertex.  Returns (xy int32 [n, 2], z float32 [n], ok bool [n]): the pixel (x right, y up) and the depth
+    the renderer gives a mesh vertex there; ok is False where w is 0 or the point leaves what a tr_line may hold."""
+    p = np.ascontiguousarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("project_points: points are [n, 3]")
+    n = p.shape[0]
+    xy, z, ok = np.zeros((n, 2), np.int32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    check(load_library().tr_project_points(C.byref(uniforms), n, p.ctypes.data, xy.ctypes.data, z.ctypes.data, ok.ctypes.data))
+    return xy, z, ok.astype(bool)
+
+
+def mesh_edges(mesh):
+    """The unique edges of a mesh's faces as position-index pairs [m, 2] (int64, the smaller index first, sorted)."""
+    idx = np.asarray(mesh["idx"]).astype(np.int64)
+    p = idx[:, (0, 3, 6)]
+    e = np.concatenate([p[:, (0, 1)], p[:, (1, 2)], p[:, (2, 0)]])
+    e = np.sort(e, axis=1)
+    return np.unique(e[e[:, 0] != e[:, 1]], axis=0)
+
+
+def wireframe_lines(scene, mesh, colour=(255, 255, 255, 255)):
+    """The mesh's unique edges projected by the scene's last camera (Scene.project) as a table for Scene.set_lines; an
+    edge with an endpoint that is not ok is dropped."""
+    e = mesh_edges(mesh)
+    xy, z, ok = scene.project(np.asarray(mesh["pos"], np.float32))
+    e = e[ok[e[:, 0]] & ok[e[:, 1]]]
+    return lines_table(xy[e[:, 0]], z[e[:, 0]], xy[e[:, 1]], z[e[:, 1]], colour)
+
+
+def lines_polyline(points, closed=False):
+    """Model-space endpoints (a [m, 3], b [m, 3]) of the segments joining consecutive points [n, 3]."""
+    p = np.asarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 2:
+        raise ValueError("lines_polyline: points are [n, 3], n >= 2")
+    return (p.copy(), np.roll(p, -1, axis=0)) if closed else (p[:-1].copy(), p[1:].copy())
+
+
+def lines_box(lo, hi):
+    """Model-space endpoints (a [12, 3], b [12, 3]) of the twelve edges of the box from corner lo to corner hi."""
+    lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+    c = np.array([[(hi if (k >> d) & 1 else lo)[d] for d in range(3)] for k in range(8)], np.float32)
+    pairs = [(k, k | (1 << d)) for k in range(8) for d in range(3) if not (k >> d) & 1]
+    return c[[p[0] for p in pairs]], c[[p[1] for p in pairs]]
+
+
+def lines_axes(length=1.0):
+    """Model-space endpoints (a [3, 3], b [3, 3]) of the three axes from the origin; colour them red, green, blue."""
+    return np.zeros((3, 3), np.float32), (np.eye(3) * float(length)).astype(np.float32)
+
+
+def lines_grid(n, step=1.0, y=0.0):
+    """Model-space endpoints (a [2 (2 n + 1), 3], b) of a ground grid in the plane at height y: 2 n + 1 lines each way,
+    `step` apart, centred on the origin."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("lines_grid: n must be a positive integer")
+    t = np.arange(-n, n + 1, dtype=np.float32) * np.float32(step)
+    e, yy = np.full_like(t, n * np.float32(step)), np.full_like(t, np.float32(y))
+    a = np.concatenate([np.stack([t, yy, -e], 1), np.stack([-e, yy, t], 1)])
+    b = np.concatenate([np.stack([t, yy, e], 1), np.stack([e, yy, t], 1)])
+    return a, b
+
+
 WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
 WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
 
@@ -1873,9 +2018,11 @@ class Scene:
 
     def set_light_direction(self, light_direction):
         check(load_library().tr_scene_set_light_direction(self._h, _f3(light_direction)))
+        self._light = tuple(float(v) for v in light_direction)
 
     def set_camera(self, look_from, look_at, up):
         check(load_library().tr_scene_set_camera(self._h, _f3(look_from), _f3(look_at), _f3(up)))
+        self._camera = tuple(tuple(float(v) for v in a) for a in (look_from, look_at, up))   # (for project)
 
     def render(self):
         check(load_library().tr_scene_render(self._h))
@@ -2579,6 +2726,58 @@ class Scene:
         if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= 0xFFFFFFFF:
             raise ValueError("debug_ramp_grid: cap must be an integer 0..2^32 - 1")
         return check(load_library().tr_scene_debug_ramp_grid(self._h, int(cap)))
+
+    # --- lines (tr_scene_set_lines / tr_scene_lines / tr_scene_get_lined) -----------------------------
+    def set_lines(self, lines):
+        """tr_scene_set_lines: the scene's table of segments, a LINE_DTYPE array of up to 2^20 records in raster
+        coordinates (lines_table, wireframe_lines); None or an empty table drops it.  Validates every segment and bins the
+        table into the frame's tiles on the host; waits for the scene's queued work."""
+        if lines is None or len(lines) == 0:
+            check(load_library().tr_scene_set_lines(self._h, 0, None))
+            return
+        tab = _lines_table(lines, "set_lines")
+        check(load_library().tr_scene_set_lines(self._h, tab.shape[0], tab.ctypes.data))
+
+    def lines(self, width=1, opacity=256, depth_test=True, painter=False, depth_bias=0.0, out=None, params=None):
+        """tr_scene_lines: draws the scene's table of segments into the current frame on the device, depth-tested against
+        the frame's own z (arguments: lines_params, or params built by it).  out=None: in place, by the kernel itself --
+        every later consumer sees the lines; z, winner words and the shadow buffer stay.  Otherwise `out` is a device
+        pointer (int) or tensor of 3 * W * H bytes apart from every frame buffer of the scene, or an array from
+        pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there after sync().  Band scenes
+        are refused.  lines_host is the rule."""
+        p = self._lines_params("tr_scene_lines", width, opacity, depth_test, painter, depth_bias, params)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_lines(self._h, C.addressof(p), ptr))
+        return out
+
+    def get_lined(self, width=1, opacity=256, depth_test=True, painter=False, depth_bias=0.0, strict=True, params=None):
+        """tr_scene_get_lined: the current frame with the lines drawn on the device (arguments as for lines), as an
+        [H, W, 3] uint8 array.  Synchronizes; the scene's frame stays as it is."""
+        p = self._lines_params("tr_scene_get_lined", width, opacity, depth_test, painter, depth_bias, params)
+        return self._image("tr_scene_get_lined", strict, C.addressof(p))
+
+    @staticmethod
+    def _lines_params(who, width, opacity, depth_test, painter, depth_bias, params):
+        if params is None:
+            return lines_params(width, opacity, depth_test, painter, depth_bias, who)
+        _check_params(params, LinesParams, who, "lines_params")
+        return params
+
+    def debug_line_bins(self):
+        """tr_scene_debug_line_bins: (non-empty tiles, list entries) of the scene's table of lines."""
+        nt, ne = C.c_uint32(), C.c_uint64()
+        check(load_library().tr_scene_debug_line_bins(self._h, C.byref(nt), C.byref(ne)))
+        return int(nt.value), int(ne.value)
+
+    def project(self, points):
+        """Model-space points [n, 3] as the scene's last camera (set_camera) places them: project_points under
+        prepare_uniforms(0, ..) of the scene's size.  Returns (xy, z, ok)."""
+        cam = getattr(self, "_camera", None)
+        if cam is None:
+            raise ValueError("project: the scene has no camera yet (set_camera)")
+        st, u = prepare_uniforms(0, self.width, self.height, getattr(self, "_light", (0.0, 0.0, 1.0)), *cam)
+        check(st)
+        return project_points(u, points)
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
