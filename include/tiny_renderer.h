@@ -1538,6 +1538,83 @@ int tr_lines_host(uint32_t width, uint32_t height, const uint8_t *rgb, const flo
 /* For the tests: the number of non-empty tiles and the number of list entries of the scene's table (0 and 0 without one). */
 int tr_scene_debug_line_bins(tr_scene *s, uint32_t *n_tiles, uint64_t *n_entries);
 
+/* Distance field: for every pixel of the scene's CURRENT frame the squared Euclidean distance, in pixels, to the nearest
+ * SEED of that frame, on the device -- the answer to "how far is this pixel from the model?", and with it an outer glow, a
+ * stroke of any width, contour rings, a soft drop shadow, an inner glow, a dilate or an erode by a disc of radius up to
+ * 255: its cost does not grow with the square of the reach.  An exact integer quantity: whatever the device does, it
+ * equals tr_distance_host in every bit.
+ *   seeds   a pixel is a seed by `seed`: TR_DIST_SEED_DRAWN: bits(z) != bits(f32::MIN), the depth ramp's "drawn";
+ *           TR_DIST_SEED_KEY: max(r, g, b) >= threshold on the stored bytes, threshold 0..255, no depth is read.
+ *           TR_DIST_INVERT takes the complement: the result is then the distance inside a shape to its border.  Pixels
+ *           outside the frame are never seeds.
+ *   field   with R = radius, 1..TR_DIST_MAX_RADIUS: d2(x, y) = min over seeds (sx, sy) of (x - sx)^2 + (y - sy)^2 as a
+ *           uint16_t where that is <= R * R, else TR_DIST_FAR; a seed has d2 == 0; R * R <= 65025 < 0xFFFF.  A frame
+ *           without seeds is FAR everywhere.  Index x + r * width with row r = 0 the TOP row, like the frame buffer.
+ *   ramp    the field coloured through the scene's ramp table (tr_scene_set_ramp, n entries): dq = floor(sqrt(d2 * 65536)),
+ *           an exact integer square root (dq <= 65280); p = (dq * step) >> 8 in u32, step = 1..65536 table positions
+ *           (1/256 of an entry) per pixel of distance: 256 is one entry a pixel.  Then exactly tr_scene_ramp's rule (above):
+ *           p = min(p, pmax) or, with TR_DIST_REPEAT, p % pmax; entries i, j interpolated; coverage e_a * opacity; the
+ *           layer rule's seven modes; (b cov + d (65280 - cov) + 32640) / 65280.  A FAR pixel takes the entry `far`, packed
+ *           like tr_ramp_params.undrawn.  With TR_DIST_KEEP_SEEDS a seed keeps its colour: a glow or stroke around the
+ *           model without touching it.  Only colour changes: z, winner words and the shadow buffer stay. */
+#define TR_DIST_SEED_DRAWN 0u
+#define TR_DIST_SEED_KEY 1u
+#define TR_DIST_INVERT 0x1u     /* tr_distance_params.flags */
+#define TR_DIST_REPEAT 0x1u     /* tr_distance_ramp_params.flags */
+#define TR_DIST_KEEP_SEEDS 0x2u /* tr_distance_ramp_params.flags */
+#define TR_DIST_MAX_RADIUS 255u
+#define TR_DIST_FAR 0xFFFFu
+typedef struct tr_distance_params {
+    uint32_t seed;        /* TR_DIST_SEED_DRAWN or TR_DIST_SEED_KEY */
+    uint32_t threshold;   /* 0..255; looked at under TR_DIST_SEED_KEY only, but checked always */
+    uint32_t radius;      /* 1..TR_DIST_MAX_RADIUS */
+    uint32_t flags;       /* TR_DIST_INVERT or 0 */
+    uint32_t reserved[4]; /* 0 */
+} tr_distance_params;
+typedef struct tr_distance_ramp_params {
+    tr_distance_params field;
+    uint32_t step;        /* 1..65536: table positions (1/256 of an entry) per pixel of distance */
+    uint32_t mode;        /* TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE */
+    uint32_t opacity;     /* 0..256 */
+    uint32_t far;         /* the entry of a FAR pixel: r | g << 8 | b << 16 | alpha << 24 */
+    uint32_t flags;       /* TR_DIST_REPEAT | TR_DIST_KEEP_SEEDS */
+    uint32_t reserved[3]; /* 0 */
+} tr_distance_ramp_params;
+/* The field of the current frame into `out`: 2 W H bytes of device memory at any 2-byte-aligned address, or memory from
+ * tr_host_alloc, apart from every frame buffer of the scene; every uint16_t of it is written, the frame stays as it is.
+ * Asynchronous and ordered like tr_scene_ramp: frames held back are submitted, a pending clear is made real; under
+ * TR_DIST_SEED_DRAWN a depth left on the chip is made real, under TR_DIST_SEED_KEY it stays where it is.  Three kernels
+ * on the scene's stream (k_dist_mask, k_dist_row, k_dist) through scratch memory kept on the scene from the first call
+ * (a bit, a byte and 1/64 byte a pixel); the result is there after tr_scene_sync, and the scene's passes issued so far
+ * count as handed on.  TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued:
+ * a NULL scene, params or out; seed > 1; threshold > 255; radius not 1..255; an unknown flag; reserved not 0; a BAND
+ * scene (tr_options.band_row0/1); `out` that is ordinary host memory, a pinned block that is too small, an odd address,
+ * or overlaps a frame buffer of the scene. */
+int tr_scene_distance(tr_scene *s, const tr_distance_params *p, void *out);
+/* The field into any host memory (W * H uint16_t): waits for the scene first, computes into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_ramped. */
+int tr_scene_get_distance(tr_scene *s, const tr_distance_params *p, uint16_t *host);
+/* Ramps the current frame by its distance field.  Ordering, `out` (3 W H bytes at any byte address, or NULL) and the
+ * in-place form as tr_scene_ramp; the field goes to scratch memory of the scene (2 more bytes a pixel) and is complete
+ * before the pointwise kernel (k_dist_apply) starts, so TR_DIST_SEED_KEY seeds are read before any colour changes.  In
+ * place a 128 x 16 tile whose pixels are all FAR under a `far` coverage of 0 is not touched; a tile whose colour
+ * fast-clear flag is up counts as zeros and is stored whole with its flag lowered (MULTIPLY and DARKEN leave it black
+ * behind its flag).  The refusals of tr_scene_distance (`out` may be NULL and need not be even), and: step not 1..65536;
+ * mode > TR_LAYER_DIFFERENCE; opacity > 256; a scene without a ramp table. */
+int tr_scene_distance_ramp(tr_scene *s, const tr_distance_ramp_params *p, void *out /* or NULL */);
+/* The frame ramped by its distance field into any host memory (3 W H bytes), like tr_scene_get_ramped. */
+int tr_scene_get_distance_ramped(tr_scene *s, const tr_distance_ramp_params *p, uint8_t *rgb);
+/* The rules above on the host (no GPU needed), by the very inline functions the kernels call.  rgb: 3 * width * height
+ * bytes, row 0 = top; z: width * height floats, index x + y * width with y UP, may be NULL under TR_DIST_SEED_KEY;
+ * out_u16: width * height uint16_t, row 0 = top; table: 4 * n bytes, n = 2..TR_RAMP_MAX_N; out: 3 * width * height
+ * bytes, may be rgb.  The same parameter checks; width and height 1..32768. */
+int tr_distance_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_distance_params *p, uint16_t *out_u16);
+int tr_distance_ramp_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_distance_ramp_params *p, uint32_t n,
+                          const uint8_t *table, uint8_t *out /* may be rgb */);
+/* dq[k] = floor(sqrt(d2[k] * 65536)) and positions[k] = (dq[k] * step) >> 8 -- before the clamp or the REPEAT -- of count
+ * field values d2[k] <= 65025 (TR_E_INVALID otherwise, and for a step not 1..65536); either output may be NULL. */
+int tr_distance_positions(uint32_t step, uint32_t count, const uint16_t *d2, uint32_t *dq, uint32_t *positions);
+
 /* Frame statistics: the scene's CURRENT frame reduced on the device to one record of 6192 bytes -- what a caller needs to
  * choose tr_dof_params.focus (a z value), tr_bloom_params.threshold (a brightness) or a level table for tr_scene_set_lut
  * without reading the frame back.  F is the frame as tr_scene_get_frame_buffer returns it (row 0 = top), z the depth as

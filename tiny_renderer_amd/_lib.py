@@ -200,6 +200,13 @@ SYMBOLS = {
     "tr_lines_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_debug_line_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_project_points": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_distance_ramp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_distance_ramped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_distance_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_distance_ramp_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_distance_positions": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_frame_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_frame_stats_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

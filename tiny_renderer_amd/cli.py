@@ -127,6 +127,17 @@ def main(argv=None):
                          "edge off its own surface (default 0.5: DESIGN.md 7za has the sweep it was chosen on)")
     ap.add_argument("--wire-xray", action="store_true", help="with --wireframe: no depth test, the far side shows through")
     ap.add_argument("--wire-only", action="store_true", help="with --wireframe: clear the frame, then draw the lines alone (no depth test)")
+    ap.add_argument("--glow", default=None, metavar="R,G,B[,A]",
+                    help="distance field: a glow of that colour around the model, added on the GPU and gone --glow-radius pixels away "
+                         "(Scene.distance_ramp through ramp_glow; keeps the model; after --wireframe, before --aa)")
+    ap.add_argument("--glow-radius", type=int, default=24, metavar="N", help="with --glow and --inner-glow: the reach in pixels, 1..255 (default 24)")
+    ap.add_argument("--stroke", default=None, metavar="R,G,B[,A]",
+                    help="distance field: a stroke of that colour around the model's silhouette (Scene.distance_ramp through ramp_stroke; "
+                         "keeps the model; after --glow, before --aa)")
+    ap.add_argument("--stroke-width", type=int, default=4, metavar="N", help="with --stroke: the width in pixels, 1..254 (default 4)")
+    ap.add_argument("--inner-glow", default=None, metavar="R,G,B[,A]",
+                    help="distance field: a glow of that colour inside the model along its silhouette (TR_DIST_INVERT: the seeds are "
+                         "the pixels where nothing is drawn, and they are kept; before --glow)")
     ap.add_argument("--aa", action="store_true",
                     help="edge anti-aliasing: smooth the picture's stair-steps at its own size by a luma-driven edge filter on the GPU "
                          "(Scene.antialias; after --outline, so the ink's edges are smoothed too, and before --ssaa resolves)")
@@ -329,6 +340,28 @@ def main(argv=None):
                 raise ValueError("--wire-width takes 1..15")
             if not np.isfinite(np.float32(args.wire_bias)):
                 raise ValueError("--wire-bias must be finite")
+        except ValueError as e:
+            ap.error(str(e))
+    args.glow_colour = args.stroke_colour = args.inner_glow_colour = None
+    if args.glow is None and args.inner_glow is None and args.glow_radius != 24:
+        ap.error("--glow-radius goes with --glow or --inner-glow")
+    if args.stroke is None and args.stroke_width != 4:
+        ap.error("--stroke-width goes with --stroke")
+    if args.glow is not None or args.stroke is not None or args.inner_glow is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--glow, --stroke and --inner-glow work on the frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        try:
+            for name in ("glow", "stroke", "inner_glow"):
+                text = getattr(args, name)
+                if text is not None:
+                    colour = tuple(int(v) for v in text.split(","))
+                    if len(colour) not in (3, 4) or min(colour) < 0 or max(colour) > 255:
+                        raise ValueError("--%s takes R,G,B[,A] with values 0..255" % name.replace("_", "-"))
+                    setattr(args, name + "_colour", colour)
+            if not 1 <= args.glow_radius <= 255:
+                raise ValueError("--glow-radius takes 1..255")
+            if not 1 <= args.stroke_width <= 254:
+                raise ValueError("--stroke-width takes 1..254")
         except ValueError as e:
             ap.error(str(e))
     args.aa_params = None
@@ -835,6 +868,20 @@ def _post(args, T, scene, say):
         if args.wire_only:
             scene.clear()
         scene.lines(args.wire_width, depth_test=not (args.wire_xray or args.wire_only), depth_bias=args.wire_bias)
+    # in place, after the lines and before the filter: each keeps the seeds (the model), so only its surroundings -- or,
+    # under --inner-glow, its inside near the border -- change
+    if args.inner_glow_colour is not None:
+        table, step = T.ramp_glow(args.inner_glow_colour, args.glow_radius)
+        scene.set_ramp(table)
+        scene.distance_ramp(args.glow_radius, step, invert=True, mode="add", keep_seeds=True)
+    if args.glow_colour is not None:
+        table, step = T.ramp_glow(args.glow_colour, args.glow_radius)
+        scene.set_ramp(table)
+        scene.distance_ramp(args.glow_radius, step, mode="add", keep_seeds=True)
+    if args.stroke_colour is not None:
+        table, step = T.ramp_stroke(args.stroke_colour, args.stroke_width)
+        scene.set_ramp(table)
+        scene.distance_ramp(args.stroke_width + 1, step, keep_seeds=True)
     if args.aa_params is not None:
         scene.antialias(args.aa_params)
     for grid, wp in args.warps:   # in place: --stats, --ssaa and --out-size see the warped frame

@@ -18,6 +18,7 @@
 #include "tr_layer.h"
 #include "tr_ramp.h"
 #include "tr_lines.h"
+#include "tr_distance.h"
 #include "tr_morph.h"
 #include "tr_outline.h"
 #include "tr_pack.h"
@@ -144,6 +145,15 @@ int launch_layer(const LayerArgs &a, bool from_scene, hipStream_t st);
 // whole frame only (no band); the caller has made the depth real.  a.lower: null, or a.fbclean (in place): the flags of
 // the flagged tiles stored whole come down.  cap and *grid as for launch_grade (tr_scene_debug_ramp_grid).
 int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid);
+// Distance field: the three passes of tr_distance.h over the whole frame (no band), each its own kernel.  launch_dist_mask:
+// a.mask from a.fb (KEY) or a.z (DRAWN; the caller has made the depth real) through the fast-clear flags: k_dist_mask.
+// launch_dist_row: a.h and a.summary from a.mask: k_dist_row.  launch_dist: a.field (any 2-byte-aligned address) from
+// a.h, a.summary and a.mask: k_dist.  launch_dist_apply: a.fb blended with the table's entries chosen by a.field (complete,
+// 8-byte aligned) into a.out -- a.fb itself or apart from it --, a.lower as for launch_ramp: k_dist_apply.
+int launch_dist_mask(const DistArgs &a, hipStream_t st);
+int launch_dist_row(const DistArgs &a, hipStream_t st);
+int launch_dist(const DistArgs &a, hipStream_t st);
+int launch_dist_apply(const DistApplyArgs &a, hipStream_t st);
 // Lines: the table a.lines drawn into a.fb by its per-tile lists (a.offsets, a.entries; tr_lines.h has the rule and the
 // binning), into a.out -- a.fb itself or a buffer apart from it, at any byte address --, through the frame's fast-clear
 // flags of colour and, under LINES_DEPTH_TEST, of z: k_lines.  The whole frame only (no band); under the test the caller

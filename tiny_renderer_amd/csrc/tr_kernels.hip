@@ -3909,6 +3909,202 @@ __global__ __launch_bounds__(LINES_THREADS) void k_lines(LinesArgs a)
     }
 }
 
+// Distance field (tr_scene_distance, tr_scene_distance_ramp): tr_distance.h has the rule and the three passes.  The
+// three field kernels share one geometry: a WAVE is 64 consecutive pixels of one row -- one mask word --, a workgroup
+// four such rows; the grid is (words a row, rows / 4).  Rows are counted top down, like the frame buffer's.
+//   k_dist_mask : a lane's pixel is a seed or not; one ballot is the word and lane 0 stores it.  The wave lies in one
+//                 128 x 16 tile: behind a raised z flag (DRAWN) nothing is drawn, behind a raised colour flag (KEY) the
+//                 pixels are black -- constant words without a load.  Bits past the width are 0, also under INVERT.
+//   k_dist_row  : a lane's row distance from the row's words (dist_row_exact: at most nine words, no scan), stored as
+//                 a byte; the wave's least summary byte (five shuffles) goes to summary[row][word].
+//   k_dist      : the column search of dist_column, its bytes read from memory (a wave's tap is 64 consecutive bytes;
+//                 neighbouring rows' waves read the same lines from L2).  Before it, the wave reads the summary bytes of
+//                 its word's column over the 2 R + 1 rows in reach, at most eight a lane: where none is in reach no tap can
+//                 give a value <= R^2 and the wave stores DIST_FAR without a search.
+// No LDS, no atomics, no scratch; every index is guarded by the width and the height.
+constexpr int DIST_THREADS = 256, DIST_ROWS = DIST_THREADS / 64;
+
+template <bool KEY>
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_mask(DistArgs a)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, wpr = dist_words_per_row(W);
+    const uint32_t seg = blockIdx.x, r = blockIdx.y * DIST_ROWS + threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    if (seg >= wpr || r >= H) return;  // (wave-uniform)
+    const uint32_t x = seg * 64u + lane, y = H - 1u - r;
+    const uint32_t t = (y / TILE_H) * a.frame.ntx + (seg * 64u) / TILE_W;
+    const bool flagged = KEY ? (a.fbclean != nullptr && a.fbclean[t] != 0u) : a.zclean[t] != 0u;  // (wave-uniform)
+    bool seed = false;
+    if (flagged) {
+        seed = KEY ? dist_seed_key(0u, a.rule.threshold) : false;
+    } else if (x < W) {
+        if (KEY) {
+            const uint8_t *c = a.fb + ((size_t)r * W + x) * 3u;
+            seed = dist_seed_key(grade_pack(c[0], c[1], c[2]), a.rule.threshold);
+        } else {
+            seed = dist_seed_drawn(a.z[(size_t)y * W + x]);
+        }
+    }
+    seed = x < W && (seed != ((a.rule.flags & DIST_INVERT) != 0u));
+    const unsigned long long word = __ballot(seed ? 1 : 0);
+    if (lane == 0u) a.mask[(size_t)r * wpr + seg] = word;
+}
+
+__global__ __launch_bounds__(DIST_THREADS) void k_dist_row(DistArgs a)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, wpr = dist_words_per_row(W);
+    const uint32_t seg = blockIdx.x, r = blockIdx.y * DIST_ROWS + threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    if (seg >= wpr || r >= H) return;  // (wave-uniform)
+    const uint32_t x = seg * 64u + lane;
+    uint32_t d = DIST_NONE;
+    if (x < W) {
+        d = dist_row_exact(a.mask + (size_t)r * wpr, wpr, x);
+        a.h[(size_t)r * W + x] = (uint8_t)dist_row_byte(d);
+    }
+    uint32_t least = dist_summary_byte(d);
+    for (int off = 32; off > 0; off >>= 1) least = min(least, (uint32_t)__shfl_xor((int)least, off, 64));
+    if (lane == 0u) a.summary[(size_t)r * wpr + seg] = (uint8_t)least;
+}
+
+__global__ __launch_bounds__(DIST_THREADS) void k_dist(DistArgs a)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, wpr = dist_words_per_row(W);
+    const uint32_t seg = blockIdx.x, r = blockIdx.y * DIST_ROWS + threadIdx.x / 64u, lane = threadIdx.x % 64u;
+    if (seg >= wpr || r >= H) return;  // (wave-uniform)
+    const uint32_t x = seg * 64u + lane, R = a.rule.radius;
+    bool reach = false;
+    for (int32_t rr = (int32_t)r - (int32_t)R + (int32_t)lane; rr <= (int32_t)r + (int32_t)R; rr += 64)
+        if (rr >= 0 && rr < (int32_t)H) reach = reach || dist_summary_reach(a.summary[(size_t)rr * wpr + seg], R);
+    const bool search = __ballot(reach ? 1 : 0) != 0ull;  // (wave-uniform)
+    if (x >= W) return;
+    uint32_t d2 = DIST_FAR;
+    if (search) {
+        const uint32_t own = dist_own_row(a.h[(size_t)r * W + x], R, a.mask + (size_t)r * wpr, wpr, x);
+        d2 = dist_column(a.h, W, x, r, H, R, own, nullptr);
+    }
+    a.field[(size_t)r * W + x] = (uint16_t)d2;
+}
+
+// The distance ramp's pointwise half (tr_scene_distance_ramp): every pixel of the frame blended with the table entry
+// that its field value chooses, into `out`, which may BE the frame -- the field is complete before this kernel starts.
+// k_ramp's form, with the u16 field in the place of the depth: persistent workgroups, the table staged in LDS once, a
+// unit of four pixels (twelve bytes of colour, eight of field) and two units a lane; WORDS as there, the field 8-byte
+// aligned.  A tile's pixels are all FAR or not by one __syncthreads_or over the loaded field: all FAR, the table is not
+// needed and every pixel takes `far`; where far's coverage is 0 the tile is unchanged -- in place it is not touched, and
+// a raised colour flag stays up.  A tile behind a raised colour flag counts as zeros; in place it stays black behind its
+// flag under MULTIPLY and DARKEN, under any other mode it is stored whole and lane 0 lowers the flag behind a barrier.
+template <bool WORDS>
+__global__ __launch_bounds__(RAMP_THREADS) void k_dist_apply(DistApplyArgs a)
+{
+    extern __shared__ __align__(16) uint32_t s_ramp[];
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t ntx = a.frame.ntx, n_tiles = a.frame.ntx * a.frame.nty, G = gridDim.x;
+    const DistRampRule q = a.rule;
+    const bool in_place = a.out == a.fb;
+    const uint32_t far_cov = ramp_coverage(q.far, q.opacity);
+    const bool keeps_black = q.mode == LAYER_MULTIPLY || q.mode == LAYER_DARKEN;
+    bool staged = false;
+    for (uint32_t k = blockIdx.x; k < n_tiles; k += G) {
+        const uint32_t ty = k / ntx, tx = (k % ntx + 5u * ty + 13u * (ty * ntx / G)) % ntx;
+        const uint32_t t = ty * ntx + tx;
+        const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+        if (in_place && clean && keeps_black) continue;
+        const int32_t x = (int32_t)tx * TILE_W + 4 * (int32_t)(threadIdx.x % 32u);
+        const int32_t y_first = (int32_t)ty * TILE_H + (int32_t)(threadIdx.x / 32u);
+        const int32_t n_px = WORDS ? 4 : min(4, W - x);  // (WORDS: 4, or the unit is outside)
+        bool inside[RAMP_UNITS];
+        size_t pi[RAMP_UNITS];
+        uint32_t d[RAMP_UNITS][4], f[RAMP_UNITS][4];
+        bool mine = false;
+#pragma unroll
+        for (int h = 0; h < RAMP_UNITS; h++) {
+            const int32_t y = y_first + 8 * h;
+            inside[h] = x < W && y < H;
+            pi[h] = inside[h] ? (size_t)(H - 1 - y) * (size_t)W + (size_t)x : 0u;
+#pragma unroll
+            for (int i = 0; i < 4; i++) d[h][i] = 0u, f[h][i] = DIST_FAR;
+            if (!inside[h]) continue;
+            const uint16_t *fq = a.field + pi[h];
+            if (WORDS) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(fq);
+                f[h][0] = v.x & 0xFFFFu, f[h][1] = v.x >> 16, f[h][2] = v.y & 0xFFFFu, f[h][3] = v.y >> 16;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) f[h][i] = fq[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) mine = mine || f[h][i] != DIST_FAR;
+        }
+        const bool near = __syncthreads_or((int)mine) != 0;  // (workgroup-uniform) the tile has a pixel within reach
+        const bool blend = near || far_cov != 0u;
+        if (in_place && !blend) continue;
+        if (near && !staged) {  // (workgroup-uniform: the barrier is reached by all or none)
+            const uint32_t pieces = (q.n + 3u) / 4u;  // (the device table is padded to whole pieces)
+            for (uint32_t i = threadIdx.x; i < pieces; i += RAMP_THREADS)
+                reinterpret_cast<uint4 *>(s_ramp)[i] = reinterpret_cast<const uint4 *>(a.table)[i];
+            __syncthreads();
+            staged = true;
+        }
+        if (!clean) {
+#pragma unroll
+            for (int h = 0; h < RAMP_UNITS; h++) {
+                if (!inside[h]) continue;
+                const uint8_t *c = a.fb + pi[h] * 3u;
+                if (WORDS) {
+                    const uint32_t *cw = reinterpret_cast<const uint32_t *>(c);
+                    const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+                    d[h][0] = w0 & 0xFFFFFFu;
+                    d[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                    d[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                    d[h][3] = w2 >> 8;
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (i < n_px) d[h][i] = grade_pack(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+                }
+            }
+        }
+        if (blend) {
+#pragma unroll
+            for (int h = 0; h < RAMP_UNITS; h++) {
+                if (!inside[h]) continue;
+                uint32_t e[4], cov[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    e[i] = near ? dist_source(s_ramp, f[h][i], q) : q.far;
+                    cov[i] = dist_coverage(e[i], f[h][i], q);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) d[h][i] = layer_px_by(q.mode, e[i], d[h][i], cov[i]);  // (the mode is scalar)
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < RAMP_UNITS; h++) {
+            if (!inside[h]) continue;
+            uint8_t *o = a.out + pi[h] * 3u;
+            if (WORDS) {
+                uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+                ow[0] = d[h][0] | (d[h][1] << 24);
+                ow[1] = (d[h][1] >> 8) | (d[h][2] << 16);
+                ow[2] = (d[h][2] >> 16) | (d[h][3] << 8);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) {
+                        o[3 * i + 0] = (uint8_t)(d[h][i] & 0xFFu);
+                        o[3 * i + 1] = (uint8_t)((d[h][i] >> 8) & 0xFFu);
+                        o[3 * i + 2] = (uint8_t)((d[h][i] >> 16) & 0xFFu);
+                    }
+            }
+        }
+        if (in_place && clean && a.lower != nullptr) {  // (workgroup-uniform) the tile holds the blend over zeros now
+            __syncthreads();
+            if (threadIdx.x == 0u) a.lower[t] = 0u;
+        }
+    }
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -5908,6 +6104,82 @@ int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid_
         hipLaunchKernelGGL((k_ramp<true>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
     else
         hipLaunchKernelGGL((k_ramp<false>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+static int dist_args_ok(const DistArgs &a)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height;
+    if (W == 0u || H == 0u || !a.mask || !a.h || !a.summary) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (both flag sets are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (a.rule.seed > DIST_SEED_KEY || a.rule.threshold > 255u || a.rule.radius < 1u || a.rule.radius > DIST_MAX_RADIUS || (a.rule.flags & ~DIST_INVERT) != 0u)
+        return (int)hipErrorInvalidValue;
+    if ((H + DIST_ROWS - 1) / DIST_ROWS > 65535u) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static dim3 dist_grid(const DistArgs &a) { return dim3(dist_words_per_row(a.frame.width), (a.frame.height + DIST_ROWS - 1) / DIST_ROWS); }
+
+int launch_dist_mask(const DistArgs &a, hipStream_t st)
+{
+    int rc = dist_args_ok(a);
+    if (rc) return rc;
+    if (!a.fb || (a.rule.seed == DIST_SEED_DRAWN && (!a.z || !a.zclean))) return (int)hipErrorInvalidValue;
+    if (a.rule.seed == DIST_SEED_KEY)
+        hipLaunchKernelGGL((k_dist_mask<true>), dist_grid(a), dim3(DIST_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_dist_mask<false>), dist_grid(a), dim3(DIST_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_dist_row(const DistArgs &a, hipStream_t st)
+{
+    int rc = dist_args_ok(a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_dist_row, dist_grid(a), dim3(DIST_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_dist(const DistArgs &a, hipStream_t st)
+{
+    int rc = dist_args_ok(a);
+    if (rc) return rc;
+    if (!a.field || (uintptr_t)a.field % 2u != 0u) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dist, dist_grid(a), dim3(DIST_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_dist_apply(const DistApplyArgs &a, hipStream_t st)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    const DistRampRule &q = a.rule;
+    if (!a.fb || !a.out || !a.field || (uintptr_t)a.field % 8u != 0u || !a.table || (uintptr_t)a.table % 16u != 0u) return (int)hipErrorInvalidValue;
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (q.n < 2u || q.n > RAMP_MAX_N || q.mode >= LAYER_MODES || q.opacity > 256u || (q.flags & ~(DIST_REPEAT | DIST_KEEP_SEEDS)) != 0u || q.step < 1u ||
+        q.step > DIST_MAX_STEP)
+        return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    const bool words = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u;
+    const size_t lds_bytes = (size_t)((q.n + 3u) / 4u) * 16u;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        return (int)hipErrorInvalidDevice;
+    const uint32_t grid = std::min<uint32_t>((uint32_t)cus * (uint32_t)RAMP_MAX_PER_CU, n_tiles);
+    if (words)
+        hipLaunchKernelGGL((k_dist_apply<true>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
+    else
+        hipLaunchKernelGGL((k_dist_apply<false>), dim3(grid), dim3(RAMP_THREADS), lds_bytes, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -94,8 +94,8 @@ const PipelineDesc kPipelines[P_COUNT] = {
     { "occlusion", 2, { { 1, VS_DEPTH, FS_DEPTH }, { 2, VS_PLAIN, FS_OCCLUSION2 } } },
 };
 
-const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp", "k_bilateral", "k_lines" };
-enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_BILATERAL, K_LINES, K_COUNT };
+const char *kKernelNames[] = { "k_setup", "k_tile", "k_tile_depth", "k_clear", "k_order", "k_bin", "k_lit", "k_resolve", "k_morph", "k_skin", "k_composite", "k_ao", "k_accumulate", "k_dof", "k_shadow_merge", "k_pack_texels", "k_bloom", "k_grade", "k_stats", "k_outline", "k_aa", "k_resize", "k_warp", "k_convolve", "k_yuv", "k_layer", "k_rank", "k_ramp", "k_bilateral", "k_dist", "k_dist_apply", "k_lines" };
+enum KernelId { K_SETUP = 0, K_TILE, K_TILE_DEPTH, K_CLEAR, K_ORDER, K_BIN, K_LIT, K_RESOLVE, K_MORPH, K_SKIN, K_COMPOSITE, K_AO, K_ACCUMULATE, K_DOF, K_SHADOW_MERGE, K_PACK_TEXELS, K_BLOOM, K_GRADE, K_STATS, K_OUTLINE, K_AA, K_RESIZE, K_WARP, K_CONVOLVE, K_YUV, K_LAYER, K_RANK, K_RAMP, K_BILATERAL, K_DIST, K_DIST_APPLY, K_LINES, K_COUNT };
 
 struct EventPair {
     hipEvent_t a, b;
@@ -407,6 +407,12 @@ struct tr_scene {
     // pieces.  ramp_n == 0: no table.  tr_scene_debug_ramp_grid: the cap and the last grid, as for k_grade
     uint32_t *d_ramp = nullptr;
     uint32_t ramp_n = 0, ramp_cap = 0, ramp_grid = 0;
+    // the distance field's scratch, allocated by the first call that needs it and kept: the mask (a bit a pixel, 64-bit
+    // words, rows padded to whole words), the row distances (a byte a pixel), the summary (a byte a word of the mask) and,
+    // for the ramp calls alone, the u16 field
+    uint64_t *d_dist_mask = nullptr;
+    uint8_t *d_dist_h = nullptr, *d_dist_summary = nullptr;
+    uint16_t *d_dist_field = nullptr;
     // tr_scene_set_lines: the table and its bins in ONE device block of words, so that it changes hands at once -- the
     // lines_n segments (8 words each), n_tiles + 1 list offsets, the lines_listed non-empty tiles, the lines_entries
     // list entries, in this order.  lines_n == 0: no table
@@ -2550,6 +2556,10 @@ void destroy(tr_scene *s)
     dev_free(s->d_dof_clean);
     dev_free(s->d_lut);
     dev_free(s->d_ramp);
+    dev_free(s->d_dist_mask);
+    dev_free(s->d_dist_h);
+    dev_free(s->d_dist_summary);
+    dev_free(s->d_dist_field);
     dev_free(s->d_lines);
     dev_free(s->resize.d);
     if (s->resize.h) (void)hipHostFree(s->resize.h);
@@ -2851,7 +2861,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines, distance) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -6177,6 +6187,223 @@ int tr_scene_debug_line_bins(tr_scene *s, uint32_t *n_tiles, uint64_t *n_entries
     if (!s || !n_tiles || !n_entries) return tr::fail(TR_E_INVALID, "tr_scene_debug_line_bins: null argument");
     *n_tiles = s->lines_listed;
     *n_entries = s->lines_entries;
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_DIST_SEED_DRAWN == DIST_SEED_DRAWN && TR_DIST_SEED_KEY == DIST_SEED_KEY && TR_DIST_INVERT == DIST_INVERT && TR_DIST_REPEAT == DIST_REPEAT &&
+                  TR_DIST_KEEP_SEEDS == DIST_KEEP_SEEDS && TR_DIST_MAX_RADIUS == DIST_MAX_RADIUS && TR_DIST_FAR == DIST_FAR &&
+                  sizeof(tr_distance_params) == 32 && sizeof(tr_distance_ramp_params) == 64,
+              "tr_distance.h restates the header");
+
+// tr_distance_params as every entry point accepts them (`who` names the entry point in the error text).
+int check_distance_params(const tr_distance_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->seed > TR_DIST_SEED_KEY) return tr::fail(TR_E_INVALID, w + ": seed must be TR_DIST_SEED_DRAWN or TR_DIST_SEED_KEY");
+    if (p->threshold > 255u) return tr::fail(TR_E_INVALID, w + ": threshold must be 0..255");
+    if (p->radius < 1u || p->radius > TR_DIST_MAX_RADIUS) return tr::fail(TR_E_INVALID, w + ": radius must be 1..TR_DIST_MAX_RADIUS");
+    if ((p->flags & ~TR_DIST_INVERT) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    for (uint32_t v : p->reserved)
+        if (v != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    return TR_OK;
+}
+
+int check_distance_ramp_params(const tr_distance_ramp_params *p, const char *who)
+{
+    const std::string w(who);
+    if (!p) return tr::fail(TR_E_INVALID, w + ": null argument");
+    int st = check_distance_params(&p->field, who);
+    if (st != TR_OK) return st;
+    if (p->step < 1u || p->step > DIST_MAX_STEP) return tr::fail(TR_E_INVALID, w + ": step must be 1..65536");
+    if (p->mode > TR_LAYER_DIFFERENCE) return tr::fail(TR_E_INVALID, w + ": mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if ((p->flags & ~(TR_DIST_REPEAT | TR_DIST_KEEP_SEEDS)) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    for (uint32_t v : p->reserved)
+        if (v != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    return TR_OK;
+}
+
+int check_distance_scene(const tr_scene *s, bool ramp, const char *who)
+{
+    if (ramp && s->ramp_n == 0u) return tr::fail(TR_E_INVALID, std::string(who) + ": the scene has no ramp table (tr_scene_set_ramp)");
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) has no distance field");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+int check_distance_size(uint32_t width, uint32_t height, const char *who)
+{
+    if (width < 1u || height < 1u || width > 32768u || height > 32768u)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": the frame's width and height must be 1..32768");
+    return TR_OK;
+}
+
+DistRule distance_rule(const tr_distance_params *p)
+{
+    DistRule r;
+    r.seed = p->seed, r.threshold = p->threshold, r.radius = p->radius, r.flags = p->flags;
+    return r;
+}
+
+DistRampRule distance_ramp_rule(const tr_distance_ramp_params *p, uint32_t n)
+{
+    DistRampRule r;
+    r.field = distance_rule(&p->field);
+    r.step = p->step, r.mode = p->mode, r.opacity = p->opacity, r.far = p->far, r.flags = p->flags;
+    r.n = n;
+    return r;
+}
+
+size_t field_bytes(const tr_scene *s) { return (size_t)s->width * s->height * 2; }
+
+// Enqueues the field of the current frame into `field_device` behind everything issued so far: a pending clear is made
+// real (the mask kernel then runs on raised flags); under DRAWN a depth left on the chip is made real, under KEY it
+// stays where it is.  The scratch is allocated on first use and kept.
+int enqueue_distance(tr_scene *s, const DistRule &r, uint16_t *field_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK && r.seed == DIST_SEED_DRAWN) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    const size_t words = (size_t)dist_words_per_row(s->width) * s->height;
+    if (!s->d_dist_mask && (st = dev_alloc(&s->d_dist_mask, words))) return st;
+    if (!s->d_dist_h && (st = dev_alloc(&s->d_dist_h, (size_t)s->width * s->height))) return st;
+    if (!s->d_dist_summary && (st = dev_alloc(&s->d_dist_summary, words))) return st;
+    DistArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.z = r.seed == DIST_SEED_DRAWN ? s->d_z : nullptr;
+    a.zclean = r.seed == DIST_SEED_DRAWN ? s->d_zclean : nullptr;
+    a.mask = s->d_dist_mask;
+    a.h = s->d_dist_h;
+    a.summary = s->d_dist_summary;
+    a.field = field_device;
+    a.frame = s->frame;
+    a.rule = r;
+    // (the profile has one name for the three: a call shows 3 launches of "k_dist" and their summed time -- the table of
+    // names is as long as tr_scene_profile_read's callers expect it at most)
+    st = timed_launch(s, K_DIST, "k_dist_mask", [&] { return launch_dist_mask(a, s->stream); });
+    if (st == TR_OK) st = timed_launch(s, K_DIST, "k_dist_row", [&] { return launch_dist_row(a, s->stream); });
+    if (st == TR_OK) st = timed_launch(s, K_DIST, "k_dist", [&] { return launch_dist(a, s->stream); });
+    return st;
+}
+
+// Enqueues the distance ramp of the current frame into `out_device` (null: in place): the field into the scene's
+// scratch, then, in stream order, the pointwise kernel.
+int enqueue_distance_ramp(tr_scene *s, const DistRampRule &r, uint8_t *out_device)
+{
+    int st = TR_OK;
+    if (!s->d_dist_field && (st = dev_alloc(&s->d_dist_field, (size_t)s->width * s->height))) return st;
+    if ((st = enqueue_distance(s, r.field, s->d_dist_field)) != TR_OK) return st;
+    DistApplyArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    a.field = s->d_dist_field;
+    a.table = s->d_ramp;
+    a.frame = s->frame;
+    a.rule = r;
+    return timed_launch(s, K_DIST_APPLY, "k_dist_apply", [&] { return launch_dist_apply(a, s->stream); });
+}
+
+}  // namespace
+
+int tr_scene_distance(tr_scene *s, const tr_distance_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_distance: null scene");
+    int st = check_distance_params(p, "tr_scene_distance");
+    if (st == TR_OK) st = check_distance_scene(s, false, "tr_scene_distance");
+    if (st != TR_OK) return st;
+    if (!out) return tr::fail(TR_E_INVALID, "tr_scene_distance: out == NULL (the field is no frame of the scene: there is no in-place form)");
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = classify_out(out, field_bytes(s), "tr_scene_distance", "tr_scene_get_distance", "field", &target);
+    if (st != TR_OK) return st;
+    if ((uintptr_t)target % 2u != 0u) return tr::fail(TR_E_INVALID, "tr_scene_distance: `out` must be 2-byte aligned");
+    if (refuse_overlap(s, target, frame_bytes(s), "tr_scene_distance", "computes", 0u, field_bytes(s)) != TR_OK)
+        return tr::fail(TR_E_INVALID, "tr_scene_distance: `out` overlaps a frame buffer of the scene (there is no in-place form)");
+    if ((st = enqueue_distance(s, distance_rule(p), (uint16_t *)target)) != TR_OK) return st;
+    handed_on(s);
+    return TR_OK;
+}
+
+int tr_scene_get_distance(tr_scene *s, const tr_distance_params *p, uint16_t *host)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_distance: null scene");
+    int st = check_distance_params(p, "tr_scene_get_distance");
+    if (st == TR_OK && !host) st = tr::fail(TR_E_INVALID, "tr_scene_get_distance: null argument");
+    if (st == TR_OK) st = check_distance_scene(s, false, "tr_scene_get_distance");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const DistRule r = distance_rule(p);
+    return get_stage(s, (uint8_t *)host, field_bytes(s), nullptr, [&](uint8_t *o) { return enqueue_distance(s, r, (uint16_t *)o); });
+}
+
+int tr_scene_distance_ramp(tr_scene *s, const tr_distance_ramp_params *p, void *out)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_distance_ramp: null scene");
+    int st = check_distance_ramp_params(p, "tr_scene_distance_ramp");
+    if (st == TR_OK) st = check_distance_scene(s, true, "tr_scene_distance_ramp");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, "tr_scene_distance_ramp", "tr_scene_get_distance_ramped", "ramps", 0u, &target);
+    if (st != TR_OK) return st;
+    st = enqueue_distance_ramp(s, distance_ramp_rule(p, s->ramp_n), (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_distance_ramped(tr_scene *s, const tr_distance_ramp_params *p, uint8_t *rgb)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_distance_ramped: null scene");
+    int st = check_distance_ramp_params(p, "tr_scene_get_distance_ramped");
+    if (st == TR_OK && !rgb) st = tr::fail(TR_E_INVALID, "tr_scene_get_distance_ramped: null argument");
+    if (st == TR_OK) st = check_distance_scene(s, true, "tr_scene_get_distance_ramped");
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const DistRampRule r = distance_ramp_rule(p, s->ramp_n);
+    return get_stage(s, rgb, frame_bytes(s), nullptr, [&](uint8_t *o) { return enqueue_distance_ramp(s, r, o); });
+}
+
+// The rules of tr_distance.h over caller's arrays, on the host.  Need no GPU.
+int tr_distance_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_distance_params *p, uint16_t *out_u16)
+{
+    int st = check_distance_params(p, "tr_distance_host");
+    if (st == TR_OK) st = check_distance_size(width, height, "tr_distance_host");
+    if (st != TR_OK) return st;
+    if (!rgb || !out_u16 || (p->seed == TR_DIST_SEED_DRAWN && !z)) return tr::fail(TR_E_INVALID, "tr_distance_host: null argument");
+    distance_host(width, height, rgb, z, distance_rule(p), out_u16);
+    return TR_OK;
+}
+
+int tr_distance_ramp_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_distance_ramp_params *p, uint32_t n,
+                          const uint8_t *table, uint8_t *out)
+{
+    int st = check_distance_ramp_params(p, "tr_distance_ramp_host");
+    if (st == TR_OK) st = check_ramp_n(n, "tr_distance_ramp_host");
+    if (st == TR_OK) st = check_distance_size(width, height, "tr_distance_ramp_host");
+    if (st != TR_OK) return st;
+    if (!rgb || !table || !out || (p->field.seed == TR_DIST_SEED_DRAWN && !z)) return tr::fail(TR_E_INVALID, "tr_distance_ramp_host: null argument");
+    distance_ramp_host(width, height, rgb, z, distance_ramp_rule(p, n), table, out);
+    return TR_OK;
+}
+
+int tr_distance_positions(uint32_t step, uint32_t count, const uint16_t *d2, uint32_t *dq, uint32_t *positions)
+{
+    if (step < 1u || step > DIST_MAX_STEP) return tr::fail(TR_E_INVALID, "tr_distance_positions: step must be 1..65536");
+    if (count == 0u) return TR_OK;
+    if (!d2) return tr::fail(TR_E_INVALID, "tr_distance_positions: null argument");
+    for (uint32_t k = 0; k < count; k++)
+        if (d2[k] > DIST_MAX_RADIUS * DIST_MAX_RADIUS) return tr::fail(TR_E_INVALID, "tr_distance_positions: a field value above 65025 has no position");
+    for (uint32_t k = 0; k < count; k++) {
+        if (dq) dq[k] = dist_dq(d2[k]);
+        if (positions) positions[k] = dist_position_raw(d2[k], step);
+    }
     return TR_OK;
 }
 

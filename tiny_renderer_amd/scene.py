@@ -1101,6 +1101,183 @@ def lines_grid(n, step=1.0, y=0.0):
     return a, b
 
 
+DIST_SEEDS = {"drawn": 0, "key": 1}   # (TR_DIST_SEED_*)
+DIST_INVERT, DIST_REPEAT, DIST_KEEP_SEEDS, DIST_MAX_RADIUS, DIST_FAR = 1, 1, 2, 255, 0xFFFF   # (TR_DIST_*)
+
+
+class DistanceParams(C.Structure):
+    """tr_distance_params"""
+    _fields_ = [("seed", C.c_uint32), ("threshold", C.c_uint32), ("radius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+class DistanceRampParams(C.Structure):
+    """tr_distance_ramp_params"""
+    _fields_ = [("field", DistanceParams), ("step", C.c_uint32), ("mode", C.c_uint32), ("opacity", C.c_uint32), ("far", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def _dist_int(v, lo, hi, text):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(text)
+    return int(v)
+
+
+def distance_params(radius, seed="drawn", threshold=0, invert=False, who="distance"):
+    """tr_distance_params for Scene.distance / get_distance / distance_host: the squared distance of every pixel to the
+    nearest seed, kept up to radius (1..255) squared, DIST_FAR beyond.  seed "drawn": a pixel with a depth; "key": a pixel
+    whose largest stored channel is >= threshold (0..255).  invert=True: the complement -- the distance inside a shape to
+    its border.  ValueError, in the library's words, for what it would refuse (include/tiny_renderer.h)."""
+    if seed not in DIST_SEEDS:
+        raise ValueError("%s: seed must be TR_DIST_SEED_DRAWN or TR_DIST_SEED_KEY" % who)
+    t = _dist_int(threshold, 0, 255, "%s: threshold must be 0..255" % who)
+    r = _dist_int(radius, 1, DIST_MAX_RADIUS, "%s: radius must be 1..TR_DIST_MAX_RADIUS" % who)
+    return DistanceParams(DIST_SEEDS[seed], t, r, DIST_INVERT if invert else 0, (C.c_uint32 * 4)(0, 0, 0, 0))
+
+
+def distance_ramp_params(radius, step=256, seed="drawn", threshold=0, invert=False, mode="normal", opacity=256, far=(0, 0, 0, 0), repeat=False,
+                         keep_seeds=False, who="distance_ramp"):
+    """tr_distance_ramp_params for Scene.distance_ramp / get_distance_ramped / distance_ramp_host: distance_params, and
+    for the ramp step (1..65536 table positions, 1/256 of an entry, per pixel of distance: 256 is one entry a pixel), a
+    layer mode, opacity 0..256, the (r, g, b, a) entry `far` of a pixel beyond the radius, repeat (the position wraps)
+    and keep_seeds (a seed keeps its colour)."""
+    f = distance_params(radius, seed, threshold, invert, who)
+    st = _dist_int(step, 1, 65536, "%s: step must be 1..65536" % who)
+    if mode not in LAYER_MODES:
+        raise ValueError("%s: mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE" % who)
+    op = _dist_int(opacity, 0, 256, "%s: opacity must be 0..256" % who)
+    u = [int(v) for v in far]
+    if len(u) != 4 or not all(0 <= v <= 255 for v in u):
+        raise ValueError("%s: far must be four values 0..255 (r, g, b, a)" % who)
+    return DistanceRampParams(f, st, LAYER_MODES[mode], op, u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24),
+                              (DIST_REPEAT if repeat else 0) | (DIST_KEEP_SEEDS if keep_seeds else 0), (C.c_uint32 * 3)(0, 0, 0))
+
+
+def _dist_frame(rgb, z, seed_is_key, who):
+    src = np.ascontiguousarray(rgb, np.uint8)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1:
+        raise ValueError("%s: rgb [H, W, 3] and z [H, W]" % who)
+    if z is None:
+        if not seed_is_key:
+            raise ValueError("%s: z may be None under seed \"key\" only" % who)
+        return src, None
+    zz = np.ascontiguousarray(z, np.float32)
+    if zz.shape != src.shape[:2]:
+        raise ValueError("%s: rgb [H, W, 3] and z [H, W]" % who)
+    return src, zz
+
+
+def distance_host(rgb, z, params):
+    """tr_distance_host: the rule of Scene.distance on the host (no GPU needed), by the inline functions the kernels
+    call.  rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), z [H, W] float32 with row 0 = bottom (read_z_f32) or
+    None under seed "key", params from distance_params.  Returns the field, uint16 [H, W] with row 0 = top."""
+    _check_params(params, DistanceParams, "distance_host", "distance_params")
+    src, zz = _dist_frame(rgb, z, params.seed == DIST_SEEDS["key"], "distance_host")
+    out = np.empty(src.shape[:2], np.uint16)
+    check(load_library().tr_distance_host(src.shape[1], src.shape[0], src.ctypes.data, None if zz is None else zz.ctypes.data,
+                                          C.addressof(params), out.ctypes.data))
+    return out
+
+
+def distance_ramp_host(rgb, z, table, params, in_place=False):
+    """tr_distance_ramp_host: the rule of Scene.distance_ramp on the host (no GPU needed).  Arguments as for distance_host,
+    table uint8 [n, 4], params from distance_ramp_params.  Returns the ramped frame; in_place=True hands the library one
+    buffer as rgb and out (a copy of rgb), which the rule allows."""
+    _check_params(params, DistanceRampParams, "distance_ramp_host", "distance_ramp_params")
+    tab = _ramp_table(table, "distance_ramp_host")
+    src, zz = _dist_frame(rgb, z, params.field.seed == DIST_SEEDS["key"], "distance_ramp_host")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_distance_ramp_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data,
+                                               None if zz is None else zz.ctypes.data, C.addressof(params), tab.shape[0], tab.ctypes.data,
+                                               out.ctypes.data))
+    return out
+
+
+def distance_positions(d2, step=256):
+    """tr_distance_positions: (dq, p) as uint32 arrays of d2's shape -- dq = floor(sqrt(d2 * 65536)), the distance in 1/256
+    of a pixel, and p = (dq * step) >> 8, the table position before the clamp or the wrap -- of field values <= 65025."""
+    dd = np.ascontiguousarray(d2, np.uint16)
+    dq, p = np.zeros(dd.shape, np.uint32), np.zeros(dd.shape, np.uint32)
+    check(load_library().tr_distance_positions(int(step), dd.size, dd.ctypes.data, dq.ctypes.data, p.ctypes.data))
+    return dq, p
+
+
+def _dist_rgba(colour, who):
+    c = [int(v) for v in colour]
+    if len(c) == 3:
+        c.append(255)
+    if len(c) != 4 or not all(0 <= v <= 255 for v in c):
+        raise ValueError("%s: colour must be three or four values 0..255" % who)
+    return c
+
+
+def ramp_glow(colour, radius, falloff="linear"):
+    """(table, step) for Scene.set_ramp and Scene.distance_ramp: a glow of `colour` (r, g, b[, a]) that is strongest at
+    the seeds and gone `radius` pixels (1..255) away.  256 entries over the radius; alpha falls from the colour's to 0 by
+    falloff "linear" (1 - t), "smooth" ((1 - t)^2) or "exp" (exp(-4 t), less its value at t = 1)."""
+    c = _dist_rgba(colour, "ramp_glow")
+    r = _dist_int(radius, 1, DIST_MAX_RADIUS, "ramp_glow: radius must be 1..%d" % DIST_MAX_RADIUS)
+    t = np.arange(256, dtype=np.float64) / 255.0
+    if falloff == "linear":
+        a = 1.0 - t
+    elif falloff == "smooth":
+        a = (1.0 - t) ** 2
+    elif falloff == "exp":
+        a = (np.exp(-4.0 * t) - np.exp(-4.0)) / (1.0 - np.exp(-4.0))
+    else:
+        raise ValueError("ramp_glow: falloff must be \"linear\", \"smooth\" or \"exp\"")
+    table = np.empty((256, 4), np.uint8)
+    table[:, :3] = c[:3]
+    table[:, 3] = np.clip(np.floor(c[3] * a + 0.5), 0, 255).astype(np.uint8)
+    table[-1, 3] = 0
+    return table, -(-255 * 256 // r)   # (the last entry is reached at the radius: ceil(255 * 256 / radius))
+
+
+def ramp_stroke(colour, width):
+    """(table, step) for a stroke of `colour` (r, g, b[, a]) `width` pixels (1..254) wide around the seeds: one entry a
+    pixel (step 256), the colour's alpha up to the width, 0 from one pixel further on, interpolated between."""
+    c = _dist_rgba(colour, "ramp_stroke")
+    w = _dist_int(width, 1, DIST_MAX_RADIUS - 1, "ramp_stroke: width must be 1..%d" % (DIST_MAX_RADIUS - 1))
+    table = np.empty((w + 2, 4), np.uint8)
+    table[:] = c
+    table[-1, 3] = 0
+    return table, 256
+
+
+def ramp_rings(colour, spacing, width):
+    """(table, step) for contour rings of `colour` (r, g, b[, a]) around the seeds under repeat=True: a ring `width`
+    pixels wide every `spacing` pixels (1 <= width < spacing <= 1023), the first on the seeds' border.  One entry a pixel
+    (step 256); the last entry repeats the first, so that the wrap is seamless."""
+    c = _dist_rgba(colour, "ramp_rings")
+    sp = _dist_int(spacing, 2, RAMP_MAX_N - 1, "ramp_rings: spacing must be 2..%d" % (RAMP_MAX_N - 1))
+    w = _dist_int(width, 1, sp - 1, "ramp_rings: width must be 1..spacing - 1")
+    table = np.empty((sp + 1, 4), np.uint8)
+    table[:] = c
+    table[w:sp, 3] = 0
+    return table, 256
+
+
+def _dist_field(field, r, who):
+    f = np.asarray(field)
+    if f.dtype != np.uint16:
+        raise ValueError("%s: field must be a uint16 array (Scene.get_distance, distance_host)" % who)
+    return f, _dist_int(r, 0, DIST_MAX_RADIUS, "%s: r must be 0..%d" % (who, DIST_MAX_RADIUS))
+
+
+def mask_dilate(field, r):
+    """The seeds of a field dilated by a disc of radius r, as a bool array: field <= r * r.  r must not exceed the radius
+    the field was computed with."""
+    f, r = _dist_field(field, r, "mask_dilate")
+    return f <= r * r
+
+
+def mask_erode(field, r):
+    """The shape eroded by a disc of radius r, as a bool array, from a field computed with invert=True (its seeds are the
+    shape's complement, so it holds each pixel's distance to the nearest pixel outside the shape): field > r * r.  r must
+    not exceed the radius the field was computed with."""
+    f, r = _dist_field(field, r, "mask_erode")
+    return f > r * r
+
+
 WARP_CELL, WARP_BORDER, WARP_CLAMP, WARP_PER_CHANNEL, WARP_MAX_SIDE, WARP_NODE_MAX = 16, 0, 1, 1, 8192, 1 << 22   # (TR_WARP_*)
 WARP_EDGES = {"border": WARP_BORDER, "clamp": WARP_CLAMP}
 
@@ -2778,6 +2955,64 @@ class Scene:
         st, u = prepare_uniforms(0, self.width, self.height, getattr(self, "_light", (0.0, 0.0, 1.0)), *cam)
         check(st)
         return project_points(u, points)
+
+    # --- distance field (tr_scene_distance / tr_scene_get_distance / tr_scene_distance_ramp / ..._ramped) ---
+    def pinned_field(self):
+        """A page-locked [H, W] uint16 array for distance (freed with the scene)."""
+        return self._pinned_array((self.height, self.width, 2)).view(np.uint16).reshape(self.height, self.width)
+
+    def distance(self, out, radius=None, seed="drawn", threshold=0, invert=False, params=None):
+        """tr_scene_distance: the squared distance of every pixel of the current frame to its nearest seed (arguments:
+        distance_params, or params built by it), computed on the device into `out`: a device pointer (int) at an even
+        address or a tensor of 2 * W * H bytes apart from every frame buffer of the scene, or an array from pinned_field.
+        uint16, index x + row * W with row 0 = top; DIST_FAR beyond the radius.  Asynchronous: the result is there after
+        sync().  The frame stays as it is.  Band scenes are refused.  distance_host is the rule."""
+        p = self._distance_params("tr_scene_distance", radius, seed, threshold, invert, params)
+        if out is None:
+            raise ValueError("distance: out must not be None (get_distance returns an array)")
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 2 * width * height bytes", shape="[H, W]",
+                                   source="pinned_field", nbytes=self.width * self.height * 2)
+        check(load_library().tr_scene_distance(self._h, C.addressof(p), ptr))
+        return out
+
+    def get_distance(self, radius=None, seed="drawn", threshold=0, invert=False, strict=True, params=None):
+        """tr_scene_get_distance: the field of the current frame (arguments as for distance) as an [H, W] uint16 array,
+        row 0 = top.  Synchronizes; the scene's frame stays as it is."""
+        p = self._distance_params("tr_scene_get_distance", radius, seed, threshold, invert, params)
+        return self._image("tr_scene_get_distance", strict, C.addressof(p), out=np.empty((self.height, self.width), np.uint16))
+
+    def distance_ramp(self, radius=None, step=256, seed="drawn", threshold=0, invert=False, mode="normal", opacity=256, far=(0, 0, 0, 0), repeat=False,
+                      keep_seeds=False, out=None, params=None):
+        """tr_scene_distance_ramp: blends the entry of the scene's ramp table (set_ramp; ramp_glow, ramp_stroke, ramp_rings)
+        that each pixel's distance to the nearest seed chooses into the current frame on the device (arguments:
+        distance_ramp_params, or params built by it).  out=None: in place, by the kernel itself; otherwise as for ramp.
+        Asynchronous: the result is there after sync().  Band scenes are refused.  distance_ramp_host is the rule."""
+        p = self._distance_ramp_params("tr_scene_distance_ramp", radius, step, seed, threshold, invert, mode, opacity, far, repeat, keep_seeds, params)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_distance_ramp(self._h, C.addressof(p), ptr))
+        return out
+
+    def get_distance_ramped(self, radius=None, step=256, seed="drawn", threshold=0, invert=False, mode="normal", opacity=256, far=(0, 0, 0, 0),
+                            repeat=False, keep_seeds=False, strict=True, params=None):
+        """tr_scene_get_distance_ramped: the current frame ramped by its distance field on the device (arguments as for
+        distance_ramp), as an [H, W, 3] uint8 array.  Synchronizes; the scene's frame stays as it is."""
+        p = self._distance_ramp_params("tr_scene_get_distance_ramped", radius, step, seed, threshold, invert, mode, opacity, far, repeat, keep_seeds,
+                                       params)
+        return self._image("tr_scene_get_distance_ramped", strict, C.addressof(p))
+
+    @staticmethod
+    def _distance_params(who, radius, seed, threshold, invert, params):
+        if params is None:
+            return distance_params(radius, seed, threshold, invert, who)
+        _check_params(params, DistanceParams, who, "distance_params")
+        return params
+
+    @staticmethod
+    def _distance_ramp_params(who, radius, step, seed, threshold, invert, mode, opacity, far, repeat, keep_seeds, params):
+        if params is None:
+            return distance_ramp_params(radius, step, seed, threshold, invert, mode, opacity, far, repeat, keep_seeds, who)
+        _check_params(params, DistanceRampParams, who, "distance_ramp_params")
+        return params
 
     # --- frame statistics (tr_scene_frame_stats / tr_scene_get_frame_stats) ---------------------------
     def pinned_stats(self):
