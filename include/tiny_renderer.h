@@ -1538,6 +1538,90 @@ int tr_lines_host(uint32_t width, uint32_t height, const uint8_t *rgb, const flo
 /* For the tests: the number of non-empty tiles and the number of list entries of the scene's table (0 and 0 without one). */
 int tr_scene_debug_line_bins(tr_scene *s, uint32_t *n_tiles, uint64_t *n_entries);
 
+/* Projector: an image cast onto the model in the scene's CURRENT frame from a second camera, on the device -- a slide
+ * projector or spotlight with a cookie, a decal placed from a camera, a caustics or window-light pattern, and with a second
+ * scene's depth as a shadow map a second, shadow-casting light for a frame of any pipeline.  Deferred: it reads the frame's
+ * colour and z alone.  The image is pw x ph pixels of 3 (rgb8) or 4 (rgba8) channels, row 0 = top, rows image_stride
+ * bytes apart, at any byte address.  m (column-major) maps frame raster (x, y, z, 1) -- x right, y UP, pixel (x, y) is
+ * frame row H - 1 - y and depth index x + y * W, z that depth -- to projector raster (X, Y, Z, w); tr_projector_matrix
+ * builds it from two cameras.  For every DRAWN pixel (bits(z) != bits(f32::MIN)), in this order; a pixel that is not
+ * drawn, or that a step rejects, keeps its colour:
+ *   transform  X, Y, Z, w = ((m[i] x + m[4 + i] y) + m[8 + i] z) + m[12 + i], i = 0..3: every f32 operation rounded once,
+ *              nothing contracted (tr_project_points' matrix product).  Rejected unless w > 0 and w is finite.
+ *   divide     r = 1.0f / w, correctly rounded, once; u = X r, v = Y r, zp = Z r.  Rejected unless 0 <= u <= pw - 1 and
+ *              0 <= v <= ph - 1 (a NaN fails).
+ *   position   su = (int32)(u * 256.0f), ix = su >> 8, ax = su & 255; likewise iy, ay.  Texel (ix, iy), y UP, is image row
+ *              ph - 1 - iy.
+ *   image      r, g, b and alpha (255 for rgb8) bilinearly over texels (ix, iy) .. (ix + 1, iy + 1) with the warp stage's
+ *              weights ((256 - ax)(256 - ay), .., sum 2^16) and rounding ((sum + 2^15) >> 16).  A texel of weight 0 is never
+ *              loaded, so no byte outside the image is: at ix + 1 == pw, ax is 0.
+ *   light      f = 256 without TR_PROJECTOR_OCCLUDE.  With it the occluder scene's depth zo(i, j) (index i + j * pw, y UP)
+ *              makes texel (i, j) LIT iff !(zp + depth_bias < zo(i, j)): a NaN on either side is lit, a texel where the
+ *              occluder drew nothing (f32::MIN) is lit.  Hard: f = 256 or 0 by the nearest texel (ix + (ax >= 128),
+ *              iy + (ay >= 128)).  TR_PROJECTOR_SOFT: f = (sum of the bilinear weights of the lit texels + 128) >> 8.
+ *   blend      coverage a = alpha * opacity (0..65280), a' = (a f + 128) >> 8; the pixel becomes the layer rule's blend of
+ *              the sample into it under `mode` with coverage a'.
+ * Nearer is LARGER: depth_bias > 0 lifts the pixel towards the projector (less self-shadowing).  With m the identity,
+ * pw x ph = W x H and no occluder the result is tr_scene_layer's with TR_LAYER_WHERE_DRAWN at (0, 0); scaling all of m
+ * changes nothing.  Only colour changes: z, winner words and the shadow buffer stay.  A pixel depends on itself and the
+ * other inputs alone: the rule works in place.  Not here: N.L falloff (a frame keeps no normals), distance attenuation
+ * (bake it into the image, or follow with tr_scene_ramp), images above 8192 x 8192, clamped or tiled images outside the
+ * projector's rectangle, band scenes, filters wider than 2 x 2 (tr_scene_resize the image first), several projectors in
+ * one call (call it again). */
+#define TR_PROJECTOR_MAX_SIDE 8192u
+#define TR_PROJECTOR_OCCLUDE 0x1u
+#define TR_PROJECTOR_SOFT 0x2u /* only with TR_PROJECTOR_OCCLUDE */
+typedef struct tr_projector_params {
+    float m[16];          /* column-major: frame raster (x, y, z, 1) -> projector raster (X, Y, Z, w); every entry finite */
+    uint32_t pw, ph;      /* the image's (and the occluder's) width and height, each 1..8192 */
+    uint32_t channels;    /* 3 (rgb8) or 4 (rgba8) */
+    uint32_t mode;        /* TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE */
+    uint32_t opacity;     /* 0..256 */
+    uint32_t flags;       /* TR_PROJECTOR_OCCLUDE, TR_PROJECTOR_SOFT */
+    float depth_bias;     /* added to zp before the light test; finite */
+    uint32_t reserved[9]; /* 0 */
+} tr_projector_params;    /* 128 bytes */
+/* Casts the image onto the current frame.  Asynchronous and ordered like tr_scene_layer: frames held back are submitted, a
+ * pending clear is made real, a depth left on the chip is made real (the stage always reads depth), k_projector is
+ * enqueued on the scene's stream; the result is there after tr_scene_sync, and the scene's passes issued so far count as
+ * handed on.  image: pw x ph pixels in device memory or memory from tr_host_alloc, image_stride >= pw * channels; keep it
+ * alive and unchanged until then.  occluder_scene: NULL without TR_PROJECTOR_OCCLUDE; with it a scene of exactly pw x ph on
+ * the same device -- rendered from the projector's camera (TR_OPT_STORE_DEPTH spares the depth-only repeat); it may be s
+ * itself.  Its CURRENT frame's depth is made real first and is read behind its renders issued so far, and it is not
+ * rendered again before the kernel has read it (the ordering of tr_scene_composite's source); a texel of it behind a
+ * raised depth fast-clear flag -- and all of a logically cleared occluder -- counts as f32::MIN: the kernel looks at the
+ * flag per texel and never at the stale memory behind it.
+ * out == NULL: in place, by the kernel itself.  A tile with nothing drawn loads nothing and is not touched; a tile whose
+ * colour fast-clear flag is up counts as zeros and is stored whole with its flag lowered iff one of its pixels is covered
+ * (drawn and accepted by every step); under TR_LAYER_MULTIPLY and TR_LAYER_DARKEN it stays black behind its flag.
+ * Otherwise out: 3 W H bytes of device memory at any byte address or memory from tr_host_alloc, apart from every frame
+ * buffer of the scene and from the image; every byte of it is written (the rest of the frame is copied) and the scene's
+ * frame stays as it is.  A logically cleared scene is its own result: zeros out of place, nothing in place, no kernel;
+ * opacity == 0 in place does nothing (out of place the frame is copied).
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene, params or
+ * image; pw or ph outside 1..8192; channels not 3 or 4; image_stride below the row's bytes; mode > TR_LAYER_DIFFERENCE; an
+ * unknown flag; TR_PROJECTOR_SOFT without TR_PROJECTOR_OCCLUDE; opacity > 256; a depth_bias or an entry of m that is not
+ * finite; reserved not 0; TR_PROJECTOR_OCCLUDE without an occluder scene, or an occluder scene without the flag; an
+ * occluder of another size or on another device; a BAND scene (tr_options.band_row0/1) on either side; an image in
+ * ordinary host memory or a pinned block that is too small; `out` that is ordinary host memory, a pinned block that is
+ * too small, or overlaps a frame buffer of the scene or the image. */
+int tr_scene_projector(tr_scene *s, const tr_projector_params *p, const void *image, uint32_t image_stride,
+                       tr_scene *occluder_scene /* or NULL */, void *out /* or NULL */);
+/* The frame with the image cast on it into any host memory (3 W H bytes): waits for the scene first, works into a buffer
+ * of the library's, copies out and returns the frame's sticky status, like tr_scene_get_layered.  The scene's frame stays. */
+int tr_scene_get_projector(tr_scene *s, const tr_projector_params *p, const void *image, uint32_t image_stride,
+                           tr_scene *occluder_scene /* or NULL */, uint8_t *rgb);
+/* For the tests: the number of k_projector launches this scene has enqueued so far (a refused call and a shortcut add
+ * none).  The kernel has no entry in tr_scene_profile_read's table. */
+int tr_scene_debug_projector_launches(tr_scene *s);
+/* The rule above on the host (no GPU needed), by the very inline functions k_projector calls.  rgb and out: 3 * width *
+ * height bytes, row 0 = top; out may be rgb.  z: width * height floats, index x + y * width with y UP.  image: any host
+ * memory.  occluder_z: pw * ph floats, index i + j * pw with y UP, under TR_PROJECTOR_OCCLUDE; NULL without it.  The same
+ * checks of the parameters; width and height 1..32768. */
+int tr_projector_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_projector_params *p,
+                      const void *image, uint32_t image_stride, const float *occluder_z /* or NULL */, uint8_t *out /* may be rgb */);
+/* (tr_projector_matrix: below, with tr_uniforms) */
+
 /* Distance field: for every pixel of the scene's CURRENT frame the squared Euclidean distance, in pixels, to the nearest
  * SEED of that frame, on the device -- the answer to "how far is this pixel from the model?", and with it an outer glow, a
  * stroke of any width, contour rings, a soft drop shadow, an inner glow, a dilate or an erode by a disc of radius up to
@@ -1905,6 +1989,11 @@ int tr_prepare_uniforms(int kind, tr_uniforms *u, uint32_t width, uint32_t heigh
  * (and xy, z of it 0) where w is 0, a coordinate leaves +-2^20 or z is not finite within 2^100 -- what
  * tr_scene_set_lines would refuse --, else 1. */
 int tr_project_points(const tr_uniforms *u, uint32_t n, const float *xyz, int32_t *xy, float *z, uint8_t *ok);
+/* Host only: tr_projector_params.m = projector->vpmv * view->i_vpmv, the matrix that takes the raster of the frame's camera to the raster of
+ * the projector's camera -- two ordinary tr_prepare_uniforms calls, at W x H and at pw x ph; the view's with kind 2,
+ * which fills i_vpmv beside the same vpmv as kind 0 (an all-zero i_vpmv is refused).  Entry (r, c) is
+ * ((P(r,0) V(0,c) + P(r,1) V(1,c)) + P(r,2) V(2,c)) + P(r,3) V(3,c) in double, rounded to f32 once. */
+int tr_projector_matrix(const tr_uniforms *view, const tr_uniforms *projector, float m[16]);
 
 /* Asset loading (app.rs:87-131): obj-rs `parse_obj` and image `open(..).into_rgb8()`
  * counterparts.  Returned objects are owned by the library; free with the matching call. */

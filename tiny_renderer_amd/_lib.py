@@ -200,6 +200,11 @@ SYMBOLS = {
     "tr_lines_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_scene_debug_line_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_project_points": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_projector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_get_projector": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_scene_debug_projector_launches": (C.c_int, [C.c_void_p]),
+    "tr_projector_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "tr_projector_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_distance_ramp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -197,6 +197,20 @@ def main(argv=None):
                     help="layer: a picture, a colour or a gradient from the top colour to the bottom one behind the model, blended "
                          "on the GPU where nothing is drawn (Scene.layer, where=\"undrawn\"; after --with and --ao, before the "
                          "depth-of-field and bloom options)")
+    ap.add_argument("--projector", default=None, metavar="FILE.tga",
+                    help="projector: cast that image onto the model on the GPU from a second camera at --projector-from looking at "
+                         "--projector-at, a slide projector or a light cookie (after --with, --ao and --backdrop, before --fog and the depth views)")
+    ap.add_argument("--projector-from", default="1.5,1.0,1.5", metavar="X,Y,Z", help="with --projector: where the projector stands (default 1.5,1.0,1.5)")
+    ap.add_argument("--projector-at", default="0,0,0", metavar="X,Y,Z", help="with --projector: what it looks at (default 0,0,0; up is the camera's)")
+    ap.add_argument("--projector-mode", default="add", choices=("normal", "add", "multiply", "screen", "lighten", "darken", "difference"),
+                    help="with --projector: how the image is blended into the frame (default add: light)")
+    ap.add_argument("--projector-opacity", type=int, default=256, metavar="N", help="with --projector: 0..256 (default 256)")
+    ap.add_argument("--projector-shadows", action="store_true",
+                    help="with --projector: the model shadows the projected light -- a second scene of the same mesh, of the image's size, is "
+                         "rendered from the projector and its depth is the shadow map")
+    ap.add_argument("--projector-bias", type=float, default=2.0, metavar="F",
+                    help="with --projector-shadows: added to a pixel's depth before the shadow test (nearer is larger; default 2)")
+    ap.add_argument("--projector-soft", action="store_true", help="with --projector-shadows: filter the shadow's edge over 2 x 2 texels")
     ap.add_argument("--fog", default=None, metavar="R,G,B",
                     help="depth ramp: fog of that colour, thickening with distance, blended into the model on the GPU (Scene.ramp "
                          "through ramp_fog; after --with, --ao and --backdrop, before the depth-of-field and bloom options)")
@@ -286,6 +300,26 @@ def main(argv=None):
                 args.overlay_at = at
             if args.vignette is not None and not 0 <= args.vignette <= 255:
                 raise ValueError("--vignette takes 0..255")
+        except ValueError as e:
+            ap.error(str(e))
+    args.projector_view = None
+    if args.projector is None and (args.projector_from != "1.5,1.0,1.5" or args.projector_at != "0,0,0" or args.projector_mode != "add"
+                                   or args.projector_opacity != 256 or args.projector_shadows or args.projector_bias != 2.0 or args.projector_soft):
+        ap.error("--projector-from, -at, -mode, -opacity, -shadows, -bias and -soft go with --projector FILE.tga")
+    if args.projector is not None:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("--projector works on the frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        try:
+            view = [[float(v) for v in t.split(",")] for t in (args.projector_from, args.projector_at)]
+            if len(view[0]) != 3 or len(view[1]) != 3 or view[0] == view[1]:
+                raise ValueError("--projector-from and --projector-at take X,Y,Z, two different points")
+            if not 0 <= args.projector_opacity <= 256:
+                raise ValueError("--projector-opacity takes 0..256")
+            if not np.isfinite(np.float32(args.projector_bias)):
+                raise ValueError("--projector-bias must be finite")
+            if (args.projector_soft or args.projector_bias != 2.0) and not args.projector_shadows:
+                raise ValueError("--projector-bias and --projector-soft go with --projector-shadows")
+            args.projector_view = view
         except ValueError as e:
             ap.error(str(e))
     args.fog_colour = None
@@ -597,7 +631,7 @@ def main(argv=None):
     else:
         say("loading model from: %s/model.obj" % args.asset_path)
         mesh, texs = T.load_assets(args.asset_path)
-    args.mesh = mesh
+    args.mesh, args.texs = mesh, texs
     say("number of vertices in a model: %d" % mesh["pos"].shape[0])
     say("number of polygons in a model: %d" % mesh["idx"].shape[0])
     say("cooking up a scene with '%s' shader pipeline" % args.pipeline)
@@ -824,6 +858,8 @@ def _post(args, T, scene, say):
         spec = args.backdrop_spec
         back = _pinned_layer(scene, "backdrop", lambda: T.load_tga(spec) if isinstance(spec, str) else T.layer_gradient(scene.width, scene.height, spec[0], spec[1]))
         scene.layer(back, where="undrawn")
+    if args.projector_view is not None:
+        _projector(args, T, scene, say)
     if args.fog_colour is not None or args.depth_view is not None or args.depth_contours is not None:
         # in place, under the blur and the bloom; a frame with nothing drawn has no span and only its background to fog
         try:
@@ -903,6 +939,35 @@ def _post(args, T, scene, say):
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
             % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
                T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
+
+
+def _projector(args, T, scene, say):
+    """--projector: the image cast onto the current frame in place from the projector's camera, under fog and everything
+    later.  With --projector-shadows a second scene of the same mesh and of the image's size is rendered from that camera
+    (it stores its depth) and passed as the occluder; it is made once and kept with the scene."""
+    image = _pinned_layer(scene, "projector", lambda: T.load_tga(args.projector))
+    ph, pw = image.shape[:2]
+    cam = getattr(scene, "_camera", None)
+    if cam is None:   # (frames rendered as a group: the last one's camera)
+        ca = np.float32(args.camera_angle + (2.0 * np.pi * (args.frames - 1) / args.frames if args.frames > 1 else 0.0))
+        cam = ([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0.0, 0.0, 0.0], [0.0, 1.0, 0.0])
+    light = getattr(scene, "_light", (0.0, 0.0, 1.0))
+    stand, at, up = args.projector_view[0], args.projector_view[1], list(cam[2])
+    st, view = T.prepare_uniforms(2, scene.width, scene.height, light, *cam)
+    st2, proj = T.prepare_uniforms(0, pw, ph, light, stand, at, up)
+    if st != 0 or st2 != 0:
+        raise SystemExit("--projector: a camera's matrix is singular")
+    occluder = None
+    if args.projector_shadows:
+        occluder = scene.__dict__.get("_cli_projector_scene")
+        if occluder is None:
+            occluder = scene.__dict__["_cli_projector_scene"] = T.Scene(pw, ph, args.mesh, args.texs, "default", device=args.device, store_depth=True)
+        occluder.clear()
+        occluder.set_light_direction(list(light)), occluder.set_camera(stand, at, up)
+        occluder.render()
+    say("projector --- %s (%d x %d) from %s at %s%s" % (args.projector, pw, ph, stand, at, ", shadowed" if occluder is not None else ""))
+    scene.projector(T.projector_matrix(view, proj), image, occluder, mode=args.projector_mode, opacity=args.projector_opacity,
+                    soft=args.projector_soft, depth_bias=args.projector_bias if occluder is not None else 0.0)
 
 
 def _pinned_layer(scene, name, make):

@@ -4105,6 +4105,137 @@ __global__ __launch_bounds__(RAMP_THREADS) void k_dist_apply(DistApplyArgs a)
     }
 }
 
+// Projector (tr_scene_projector): an image cast onto the frame's drawn pixels from a second camera, optionally shadowed
+// by a second scene's depth, into `out`, which may BE the frame (a pixel depends on itself, the image and the occluder
+// alone); tr_projector.h has the rule.  k_layer's form: one workgroup of 256 lanes per 128 x 16 tile of the frame, every
+// tile launched (where the image lands is known only per pixel).
+//   * units as in k_ramp: four pixels of a row, twelve bytes of colour and sixteen of depth, two units a lane eight rows
+//     apart.  WORDS: width % 4 == 0, fb and out 4-byte and z 16-byte aligned (the launcher checks); otherwise guarded
+//     bytes and scalar z loads.  z is indexed y up, the frame's rows top down;
+//   * the tile's z flag is workgroup-uniform (one scalar word).  Raised, nothing is drawn in the tile and nothing is cast
+//     on it: in place it is not touched and nothing of it is loaded, out of place it is copied (zeros behind a raised
+//     colour flag).  It is the z flag that says "not drawn", never the colour flag;
+//   * the tile's colour flag is workgroup-uniform too: raised, d = 0 without a load.  In place such a tile stays black
+//     behind its flag under MULTIPLY and DARKEN; under any other mode the workgroup votes (__syncthreads_or) whether a
+//     pixel of it is covered -- drawn and accepted by every step --: if so the tile is stored whole and lane 0 lowers the
+//     flag (the vote is the barrier behind which every wave has read it), otherwise it is not touched.  An unflagged tile
+//     in place stores only the units with a covered pixel;
+//   * the image's texels and the occluder's depths are gathered straight from memory by the rule's own functions: byte
+//     loads at any address and stride, float loads; a texel of weight 0 is never loaded, so no byte outside the image
+//     and no float outside the occluder is.  An occluder texel behind a raised z flag of the OCCLUDER's tile grid counts
+//     as f32::MIN without a load: its stale memory never decides a pixel;
+//   * the reciprocal is IEEE's (recip_of, tr_math.h), no hardware approximation; the mode is workgroup-uniform: one
+//     scalar switch a unit around the blend of its four pixels.
+// z, winner words, the shadow buffer and every flag but the one lowered are left alone.  No atomics, no inline assembly,
+// no scratch; the only LDS is the vote's own 256 bytes.
+constexpr int PROJECTOR_THREADS = 256, PROJECTOR_UNITS = TILE_W * TILE_H / 4 / PROJECTOR_THREADS;
+
+struct ProjectorDeviceZ {
+    const float *z;
+    const uint32_t *clean;
+    uint32_t ntx, pw;
+    __device__ __forceinline__ float operator()(int32_t i, int32_t j) const
+    {
+        if (clean[(uint32_t)j / (uint32_t)TILE_H * ntx + (uint32_t)i / (uint32_t)TILE_W] != 0u) return bits_f32(TR_F32_MIN_BITS);
+        return z[(size_t)j * (size_t)pw + (size_t)i];
+    }
+};
+
+template <bool WORDS>
+__global__ __launch_bounds__(PROJECTOR_THREADS) void k_projector(ProjectorArgs a)
+{
+    static_assert(TILE_W == 128 && PROJECTOR_UNITS == 2 && TILE_H == 16, "32 units to a row of a tile, two rounds of eight rows");
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const uint32_t t = blockIdx.x, tx = t % a.frame.ntx, ty = t / a.frame.ntx;
+    const ProjectorRule &q = a.rule;
+    const bool in_place = a.out == a.fb;
+    const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+    const bool empty = a.zclean[t] != 0u;                           // (workgroup-uniform) nothing is drawn in the tile
+    if (in_place && (empty || (clean && (q.mode == LAYER_MULTIPLY || q.mode == LAYER_DARKEN)))) return;
+    const ProjectorDeviceZ zo = { a.occ_z, a.occ_zclean, a.occ_ntx, q.pw };
+    const int32_t x = (int32_t)tx * TILE_W + 4 * (int32_t)(threadIdx.x % 32u);
+    const int32_t y_first = (int32_t)ty * TILE_H + (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = WORDS ? 4 : min(4, W - x);  // (WORDS: 4, or the unit is outside)
+    bool inside[PROJECTOR_UNITS];
+    size_t ci[PROJECTOR_UNITS];
+    uint32_t d[PROJECTOR_UNITS][4], m[PROJECTOR_UNITS];
+#pragma unroll
+    for (int h = 0; h < PROJECTOR_UNITS; h++) {
+        const int32_t y = y_first + 8 * h;
+        inside[h] = x < W && y < H;
+        ci[h] = inside[h] ? ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u : 0u;
+        m[h] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[h][i] = 0u;
+        if (!inside[h]) continue;
+        if (!clean) {
+            const uint8_t *c = a.fb + ci[h];
+            if (WORDS) {
+                const uint32_t *cw = reinterpret_cast<const uint32_t *>(c);
+                const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+                d[h][0] = w0 & 0xFFFFFFu;
+                d[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                d[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                d[h][3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) d[h][i] = grade_pack(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+            }
+        }
+        if (empty) continue;
+        float zv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+        const float *zq = a.z + (size_t)y * (size_t)W + (size_t)x;
+        if (WORDS) {
+            const float4 v = *reinterpret_cast<const float4 *>(zq);
+            zv[0] = v.x, zv[1] = v.y, zv[2] = v.z, zv[3] = v.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) zv[i] = zq[i];
+        }
+        uint32_t s[4] = { 0u, 0u, 0u, 0u }, cov[4] = { 0u, 0u, 0u, 0u };
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (i < n_px && projector_source(q, a.image, zo, x + i, y, zv[i], s[i], cov[i])) m[h] |= 1u << i;
+        if (m[h] == 0u) continue;
+        switch (q.mode) {  // (scalar)
+        case LAYER_ADD: layer_unit<LAYER_ADD>(d[h], s, cov, m[h]); break;
+        case LAYER_MULTIPLY: layer_unit<LAYER_MULTIPLY>(d[h], s, cov, m[h]); break;
+        case LAYER_SCREEN: layer_unit<LAYER_SCREEN>(d[h], s, cov, m[h]); break;
+        case LAYER_LIGHTEN: layer_unit<LAYER_LIGHTEN>(d[h], s, cov, m[h]); break;
+        case LAYER_DARKEN: layer_unit<LAYER_DARKEN>(d[h], s, cov, m[h]); break;
+        case LAYER_DIFFERENCE: layer_unit<LAYER_DIFFERENCE>(d[h], s, cov, m[h]); break;
+        default: layer_unit<LAYER_NORMAL>(d[h], s, cov, m[h]); break;
+        }
+    }
+    bool store_all = !in_place;
+    if (in_place && clean) {  // (workgroup-uniform: the vote is reached by all or none)
+        store_all = __syncthreads_or((int)(m[0] | m[1])) != 0;
+        if (!store_all) return;
+    }
+#pragma unroll
+    for (int h = 0; h < PROJECTOR_UNITS; h++) {
+        if (!inside[h] || (!store_all && m[h] == 0u)) continue;
+        uint8_t *o = a.out + ci[h];
+        if (WORDS) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = d[h][0] | (d[h][1] << 24);
+            ow[1] = (d[h][1] >> 8) | (d[h][2] << 16);
+            ow[2] = (d[h][2] >> 16) | (d[h][3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(d[h][i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((d[h][i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((d[h][i] >> 16) & 0xFFu);
+                }
+        }
+    }
+    if (in_place && clean && a.lower != nullptr && threadIdx.x == 0u) a.lower[t] = 0u;  // the tile holds the blend over zeros now
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -6245,6 +6376,35 @@ int launch_layer(const LayerArgs &a_in, bool from_scene, hipStream_t st)
     else if (q.format == LAYER_RGBA8) LAYER_LAUNCH((int)LAYER_RGBA8)
     else LAYER_LAUNCH((int)LAYER_RGB8)
 #undef LAYER_LAUNCH
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_projector(const ProjectorArgs &a, hipStream_t st)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    const ProjectorRule &q = a.rule;
+    if (!a.fb || !a.out || !a.z || !a.zclean || !a.image) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (both flag sets and z are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (q.pw < 1u || q.pw > PROJECTOR_MAX_SIDE || q.ph < 1u || q.ph > PROJECTOR_MAX_SIDE || (q.bpp != 3u && q.bpp != 4u) || q.stride < q.pw * q.bpp ||
+        q.mode >= LAYER_MODES || q.opacity > 256u || (q.flags & ~(PROJECTOR_OCCLUDE | PROJECTOR_SOFT)) != 0u || q.flags == PROJECTOR_SOFT)
+        return (int)hipErrorInvalidValue;
+    // the occluder: its depth and its flags over its own tile grid
+    if ((q.flags & PROJECTOR_OCCLUDE) && (!a.occ_z || !a.occ_zclean || a.occ_ntx != (q.pw + TILE_W - 1) / TILE_W)) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only; the image is apart from both
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    if (a.image < (const uint8_t *)a.out + bytes && (const uint8_t *)a.out < a.image + projector_image_bytes(q)) return (int)hipErrorInvalidValue;
+    // whole words: every unit of four pixels is three aligned words of either buffer, its depths one 16-byte piece
+    const bool words = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u && (uintptr_t)a.z % 16u == 0u;
+    if (words)
+        hipLaunchKernelGGL((k_projector<true>), dim3(n_tiles), dim3(PROJECTOR_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_projector<false>), dim3(n_tiles), dim3(PROJECTOR_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -407,6 +407,8 @@ struct tr_scene {
     // pieces.  ramp_n == 0: no table.  tr_scene_debug_ramp_grid: the cap and the last grid, as for k_grade
     uint32_t *d_ramp = nullptr;
     uint32_t ramp_n = 0, ramp_cap = 0, ramp_grid = 0;
+    // tr_scene_debug_projector_launches: the k_projector launches of this scene so far
+    uint32_t projector_launches = 0;
     // the distance field's scratch, allocated by the first call that needs it and kept: the mask (a bit a pixel, 64-bit
     // words, rows padded to whole words), the row distances (a byte a pixel), the summary (a byte a word of the mask) and,
     // for the ramp calls alone, the u16 field
@@ -2861,7 +2863,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines, distance) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines, distance, projector) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -5726,8 +5728,10 @@ bool layer_misses(const LayerRule &r, uint32_t W, uint32_t H)
     return r.opacity == 0u || r.x >= (int64_t)W || r.y >= (int64_t)H || (int64_t)r.x + r.width <= 0 || (int64_t)r.y + r.height <= 0;
 }
 
-// `image` of a layer: memory from tr_host_alloc of at least `bytes` bytes (its mapped address) or device memory.
-int classify_layer_image(const void *image, size_t bytes, const char *who, const void **source_out)
+// `image` of a layer (or a projector: what / host_rule are the error texts' words): memory from tr_host_alloc of at least
+// `bytes` bytes (its mapped address) or device memory.
+int classify_layer_image(const void *image, size_t bytes, const char *who, const void **source_out, const char *what = "layer",
+                         const char *host_rule = "tr_layer_host")
 {
     const std::string w(who);
     const void *source = nullptr;
@@ -5735,12 +5739,12 @@ int classify_layer_image(const void *image, size_t bytes, const char *who, const
         std::lock_guard<std::mutex> lock(g_host_mutex);
         auto it = g_host_allocs.find(const_cast<void *>(image));
         if (it != g_host_allocs.end()) {
-            if (it->second.bytes < bytes) return tr::fail(TR_E_INVALID, w + ": the host buffer `image` is smaller than the layer");
+            if (it->second.bytes < bytes) return tr::fail(TR_E_INVALID, w + ": the host buffer `image` is smaller than the " + what);
             source = it->second.device;
         }
     }
     if (!source) {
-        const std::string text = w + ": `image` is neither device memory nor from tr_host_alloc (tr_layer_host takes any host memory)";
+        const std::string text = w + ": `image` is neither device memory nor from tr_host_alloc (" + host_rule + " takes any host memory)";
         hipPointerAttribute_t attr = {};
         if (hipPointerGetAttributes(&attr, image) != hipSuccess) {
             (void)hipGetLastError();  // (ordinary host memory is an error to the runtime: not a sticky one)
@@ -6422,6 +6426,203 @@ int tr_project_points(const tr_uniforms *u, uint32_t n, const float *xyz, int32_
         z[k] = good ? pz : 0.0f;
         ok[k] = good ? 1u : 0u;
     }
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_PROJECTOR_OCCLUDE == PROJECTOR_OCCLUDE && TR_PROJECTOR_SOFT == PROJECTOR_SOFT && TR_PROJECTOR_MAX_SIDE == PROJECTOR_MAX_SIDE &&
+                  sizeof(tr_projector_params) == 128,
+              "tr_projector.h restates the header");
+
+// tr_projector_params and the image's stride as every entry point accepts them (`who` names the entry point in the error
+// text).
+int check_projector_params(const tr_projector_params *p, const void *image, uint32_t stride, const char *who)
+{
+    const std::string w(who);
+    if (!p || !image) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (p->pw < 1u || p->pw > PROJECTOR_MAX_SIDE || p->ph < 1u || p->ph > PROJECTOR_MAX_SIDE) return tr::fail(TR_E_INVALID, w + ": pw and ph must be 1..8192");
+    if (p->channels != 3u && p->channels != 4u) return tr::fail(TR_E_INVALID, w + ": channels must be 3 or 4");
+    if (stride < p->pw * p->channels) return tr::fail(TR_E_INVALID, w + ": image_stride must be at least the bytes of a row");
+    if (p->mode > TR_LAYER_DIFFERENCE) return tr::fail(TR_E_INVALID, w + ": mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE");
+    if ((p->flags & ~(TR_PROJECTOR_OCCLUDE | TR_PROJECTOR_SOFT)) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if ((p->flags & TR_PROJECTOR_SOFT) && !(p->flags & TR_PROJECTOR_OCCLUDE))
+        return tr::fail(TR_E_INVALID, w + ": TR_PROJECTOR_SOFT needs TR_PROJECTOR_OCCLUDE");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    if (!std::isfinite(p->depth_bias)) return tr::fail(TR_E_INVALID, w + ": depth_bias must be finite");
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(p->m[i])) return tr::fail(TR_E_INVALID, w + ": every entry of m must be finite");
+    for (uint32_t v : p->reserved)
+        if (v != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    return TR_OK;
+}
+
+// The flag and the occluder go together (the scene of the device entry points, the depth array of the host's).
+int check_projector_occluder(const tr_projector_params *p, bool have, const char *who)
+{
+    if ((p->flags & TR_PROJECTOR_OCCLUDE) && !have) return tr::fail(TR_E_INVALID, std::string(who) + ": TR_PROJECTOR_OCCLUDE needs an occluder");
+    if (!(p->flags & TR_PROJECTOR_OCCLUDE) && have) return tr::fail(TR_E_INVALID, std::string(who) + ": an occluder needs TR_PROJECTOR_OCCLUDE");
+    return TR_OK;
+}
+
+int check_projector_scenes(const tr_scene *s, const tr_projector_params *p, const tr_scene *occ, const char *who)
+{
+    const std::string w(who);
+    int st = check_projector_occluder(p, occ != nullptr, who);
+    if (st != TR_OK) return st;
+    if (!whole_frame(s)) return tr::fail(TR_E_INVALID, w + ": a band scene (tr_options.band_row0/1) cannot be projected on");
+    if (occ) {
+        if (occ->device != s->device) return tr::fail(TR_E_INVALID, w + ": the scenes are on different devices");
+        if (occ->width != p->pw || occ->height != p->ph) return tr::fail(TR_E_INVALID, w + ": the occluder scene's frame is not pw x ph");
+        if (!whole_frame(occ))
+            return tr::fail(TR_E_INVALID, w + ": the occluder is a band scene (tr_options.band_row0/1): it holds only its rows of the depth");
+    }
+    if (s->broken || (occ && occ->broken)) return unusable();
+    return TR_OK;
+}
+
+// The rule of checked parameters.
+ProjectorRule projector_rule(const tr_projector_params *p, uint32_t stride)
+{
+    ProjectorRule r;
+    memcpy(r.m, p->m, sizeof r.m);
+    r.pw = p->pw, r.ph = p->ph, r.bpp = p->channels, r.mode = p->mode, r.opacity = p->opacity, r.flags = p->flags, r.stride = stride;
+    r.depth_bias = p->depth_bias;
+    return r;
+}
+
+// Enqueues the projection onto the current frame into `out_device` (null: in place) behind everything issued so far.  A
+// pending clear is made real (the kernel then runs on raised flags), and the stage always reads depth: one left on the
+// chip is made real first.  occ (null without OCCLUDE): its frame goes on its way and its depth is made real too; the
+// kernel checks its z flags per texel, nothing is materialised.  A logically cleared occluder shadows nothing: the call
+// goes on without the flag and reads nothing of it.
+int enqueue_projector(tr_scene *s, const ProjectorRule &r, const uint8_t *image, tr_scene *occ, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK) st = depth_in_memory(s);
+    if (st == TR_OK && occ && occ != s) st = submit_pending(occ);
+    if (st != TR_OK) return st;
+    ProjectorRule q = r;
+    if (occ && occ->z_fb_cleared) q.flags = 0u, occ = nullptr;
+    if (occ && occ != s && (st = depth_in_memory(occ)) != TR_OK) return st;
+    ProjectorArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.image = image;
+    if (occ) {
+        a.occ_z = occ->d_z;
+        a.occ_zclean = occ->d_zclean;
+        a.occ_ntx = (occ->width + (uint32_t)TILE_W - 1u) / (uint32_t)TILE_W;
+    }
+    a.frame = s->frame;
+    a.rule = q;
+    // (no profile entry: the table of names is as long as tr_scene_profile_read's callers expect it at most -- the launches
+    // are counted for tr_scene_debug_projector_launches, and scripts/probe_projector.py times the kernel with events)
+    auto launch = [&] {
+        int rc = launch_projector(a, s->stream);
+        if (rc) return launch_status(rc, "k_projector");
+        s->projector_launches += 1u;
+        s->quiescent = false;
+        return (int)TR_OK;
+    };
+    if (occ && occ != s) return cross_scene_launch(s, occ, launch);
+    return launch();
+}
+
+// What both device entry points check of the image: where it lives, and that it is apart from the scene's frame buffers.
+int projector_image(const tr_scene *s, const ProjectorRule &r, const void *image, const char *who, const void **source)
+{
+    const size_t image_bytes = (size_t)projector_image_bytes(r);
+    int st = classify_layer_image(image, image_bytes, who, source, "image", "tr_projector_host");
+    if (st != TR_OK) return st;
+    if (refuse_overlap(s, *source, frame_bytes(s), who, "projects", 0u, image_bytes) != TR_OK)
+        return tr::fail(TR_E_INVALID, std::string(who) + ": `image` overlaps a frame buffer of the scene");
+    return TR_OK;
+}
+
+}  // namespace
+
+int tr_scene_projector(tr_scene *s, const tr_projector_params *p, const void *image, uint32_t image_stride, tr_scene *occ, void *out)
+{
+    const char *who = "tr_scene_projector";
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_projector: null scene");
+    int st = check_projector_params(p, image, image_stride, who);
+    if (st == TR_OK) st = check_projector_scenes(s, p, occ, who);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const ProjectorRule r = projector_rule(p, image_stride);
+    const void *source = nullptr;
+    if ((st = projector_image(s, r, image, who, &source)) != TR_OK) return st;
+    void *target = nullptr;
+    st = frame_out(s, out, who, "tr_scene_get_projector", "projects", 0u, &target);
+    if (st != TR_OK) return st;
+    const uint8_t *img = (const uint8_t *)source;
+    if (target && (const uint8_t *)target < img + projector_image_bytes(r) && img < (const uint8_t *)target + frame_bytes(s))
+        return tr::fail(TR_E_INVALID, "tr_scene_projector: `image` overlaps `out`");
+    if (target && occ && occ != s && refuse_overlap(occ, target, frame_bytes(occ), who, "projects", 0u, frame_bytes(s)) != TR_OK)
+        return tr::fail(TR_E_INVALID, "tr_scene_projector: `out` overlaps a frame buffer of the occluder scene");
+    // a logically cleared scene has nothing drawn: zeros out of place, itself in place; opacity 0 in place changes nothing
+    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
+    if (r.opacity == 0u && !target) return TR_OK;
+    st = enqueue_projector(s, r, img, occ, (uint8_t *)target);
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_projector(tr_scene *s, const tr_projector_params *p, const void *image, uint32_t image_stride, tr_scene *occ, uint8_t *rgb)
+{
+    const char *who = "tr_scene_get_projector";
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_projector: null scene");
+    int st = check_projector_params(p, image, image_stride, who);
+    if (st == TR_OK && !rgb) st = tr::fail(TR_E_INVALID, "tr_scene_get_projector: null argument");
+    if (st == TR_OK) st = check_projector_scenes(s, p, occ, who);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const ProjectorRule r = projector_rule(p, image_stride);
+    const void *source = nullptr;
+    if ((st = projector_image(s, r, image, who, &source)) != TR_OK) return st;
+    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return enqueue_projector(s, r, (const uint8_t *)source, occ, o); });
+}
+
+int tr_scene_debug_projector_launches(tr_scene *s)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_projector_launches: null scene");
+    return (int)s->projector_launches;
+}
+
+// The rule of tr_projector.h over caller's arrays, on the host.  Needs no GPU.
+int tr_projector_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_projector_params *p, const void *image,
+                      uint32_t image_stride, const float *occluder_z, uint8_t *out)
+{
+    int st = check_projector_params(p, image, image_stride, "tr_projector_host");
+    if (st == TR_OK) st = check_projector_occluder(p, occluder_z != nullptr, "tr_projector_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || width > 32768u || height < 1u || height > 32768u)
+        return tr::fail(TR_E_INVALID, "tr_projector_host: the frame's width and height must be 1..32768");
+    if (!rgb || !z || !out) return tr::fail(TR_E_INVALID, "tr_projector_host: null argument");
+    projector_host(width, height, rgb, z, projector_rule(p, image_stride), (const uint8_t *)image, occluder_z, out);
+    return TR_OK;
+}
+
+// projector->vpmv * view->i_vpmv (both column-major), accumulated in double in the order of the header, rounded once.
+int tr_projector_matrix(const tr_uniforms *view, const tr_uniforms *projector, float m[16])
+{
+    if (!view || !projector || !m) return tr::fail(TR_E_INVALID, "tr_projector_matrix: null argument");
+    bool inverse = false;
+    for (float v : view->i_vpmv) inverse = inverse || v != 0.0f;
+    if (!inverse) return tr::fail(TR_E_INVALID, "tr_projector_matrix: view->i_vpmv is all zeros (tr_prepare_uniforms kind 2 fills it)");
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 4; r++) {
+            const double t0 = (double)projector->vpmv[r] * (double)view->i_vpmv[4 * c], t1 = (double)projector->vpmv[4 + r] * (double)view->i_vpmv[4 * c + 1];
+            const double t2 = (double)projector->vpmv[8 + r] * (double)view->i_vpmv[4 * c + 2], t3 = (double)projector->vpmv[12 + r] * (double)view->i_vpmv[4 * c + 3];
+            const double s0 = t0 + t1;
+            const double s1 = s0 + t2;
+            m[4 * c + r] = (float)(s1 + t3);
+        }
     return TR_OK;
 }
 

@@ -1050,6 +1050,85 @@ def project_points(uniforms, points):
     return xy, z, ok.astype(bool)
 
 
+PROJECTOR_MAX_SIDE, PROJECTOR_OCCLUDE, PROJECTOR_SOFT = 8192, 1, 2   # (TR_PROJECTOR_MAX_SIDE, TR_PROJECTOR_OCCLUDE, TR_PROJECTOR_SOFT)
+
+
+class ProjectorParams(C.Structure):
+    """tr_projector_params"""
+    _fields_ = [("m", C.c_float * 16), ("pw", C.c_uint32), ("ph", C.c_uint32), ("channels", C.c_uint32), ("mode", C.c_uint32),
+                ("opacity", C.c_uint32), ("flags", C.c_uint32), ("depth_bias", C.c_float), ("reserved", C.c_uint32 * 9)]
+
+
+def projector_params(m, pw, ph, channels=3, mode="add", opacity=256, occlude=False, soft=False, depth_bias=0.0, who="projector"):
+    """tr_projector_params for Scene.projector / get_projector / projector_host: m, 16 floats column-major (or a [4, 4]
+    array indexed [row, column]), maps frame raster (x, y, z, 1) -- y up -- to the projector's raster (projector_matrix
+    builds it from two cameras); the image is pw x ph pixels (each 1..8192) of 3 or 4 channels; mode: a layer mode;
+    opacity 0..256; occlude: shadow by an occluder's depth, soft: filter that shadow over 2 x 2 texels; depth_bias is
+    added to the pixel's depth before the test (nearer is larger: > 0 lifts).  ValueError, in the library's words, for what
+    it would refuse (include/tiny_renderer.h)."""
+    mm = np.asarray(m, np.float64)
+    if mm.shape == (4, 4):
+        mm = mm.T.reshape(16)   # ([row, column] to column-major)
+    if mm.shape != (16,):
+        raise ValueError("%s: m must be 16 values (column-major) or a [4, 4] array" % who)
+    with np.errstate(over="ignore"):
+        m32, b32 = mm.astype(np.float32), np.float32(float(depth_bias))
+    for v in (pw, ph, channels, opacity):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: pw, ph, channels and opacity must be integers" % who)
+    if not 1 <= pw <= PROJECTOR_MAX_SIDE or not 1 <= ph <= PROJECTOR_MAX_SIDE:
+        raise ValueError("%s: pw and ph must be 1..8192" % who)
+    if channels not in (3, 4):
+        raise ValueError("%s: channels must be 3 or 4" % who)
+    if mode not in LAYER_MODES:
+        raise ValueError("%s: mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE" % who)
+    if soft and not occlude:
+        raise ValueError("%s: TR_PROJECTOR_SOFT needs TR_PROJECTOR_OCCLUDE" % who)
+    if not 0 <= opacity <= 256:
+        raise ValueError("%s: opacity must be 0..256" % who)
+    if not np.isfinite(b32):
+        raise ValueError("%s: depth_bias must be finite" % who)
+    if not np.isfinite(m32).all():
+        raise ValueError("%s: every entry of m must be finite" % who)
+    return ProjectorParams((C.c_float * 16)(*[float(v) for v in m32]), int(pw), int(ph), int(channels), LAYER_MODES[mode], int(opacity),
+                           (PROJECTOR_OCCLUDE if occlude else 0) | (PROJECTOR_SOFT if soft else 0), float(b32), (C.c_uint32 * 9)(*([0] * 9)))
+
+
+def projector_matrix(view_uniforms, projector_uniforms):
+    """tr_projector_matrix: the 16 floats (column-major) of projector.vpmv * view.i_vpmv, accumulated in double and rounded
+    once -- frame raster to projector raster for two prepare_uniforms results, the frame's camera at W x H (kind 2: it
+    fills i_vpmv) and the projector's at pw x ph (kind 0)."""
+    m = np.zeros(16, np.float32)
+    check(load_library().tr_projector_matrix(C.byref(view_uniforms), C.byref(projector_uniforms), m.ctypes.data))
+    return m
+
+
+def projector_host(rgb, z, params, image, occluder_z=None, in_place=False):
+    """tr_projector_host: the rule of Scene.projector on the host (no GPU needed), by the inline functions k_projector
+    calls.  rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), z [H, W] float32 with row 0 = bottom (read_z_f32),
+    params from projector_params, image [ph, pw, 3 | 4] uint8 with its rows at any stride, occluder_z [ph, pw] float32
+    with row 0 = bottom (the projector scene's read_z_f32) under occlude.  Returns the frame with the image cast on it and
+    leaves its arguments alone; in_place=True hands the library one buffer as rgb and out, which the rule allows."""
+    _check_params(params, ProjectorParams, "projector_host", "projector_params")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    zz = np.ascontiguousarray(z, np.float32)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1 or zz.shape != src.shape[:2]:
+        raise ValueError("projector_host: rgb [H, W, 3] and z [H, W]")
+    img = np.asarray(image)
+    fmt, w, h, stride = _layer_array(img, "projector_host")
+    if (w, h, 4 if fmt == "rgba8" else 3) != (params.pw, params.ph, params.channels):
+        raise ValueError("projector_host: image must be [ph, pw, channels] of the params")
+    oz = None
+    if occluder_z is not None:
+        oz = np.ascontiguousarray(occluder_z, np.float32)
+        if oz.shape != (params.ph, params.pw):
+            raise ValueError("projector_host: occluder_z [ph, pw]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_projector_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data, zz.ctypes.data,
+                                           C.addressof(params), img.ctypes.data, stride, None if oz is None else oz.ctypes.data, out.ctypes.data))
+    return out
+
+
 def mesh_edges(mesh):
     """The unique edges of a mesh's faces as position-index pairs [m, 2] (int64, the smaller index first, sorted)."""
     idx = np.asarray(mesh["idx"]).astype(np.int64)
@@ -2945,6 +3024,53 @@ class Scene:
         nt, ne = C.c_uint32(), C.c_uint64()
         check(load_library().tr_scene_debug_line_bins(self._h, C.byref(nt), C.byref(ne)))
         return int(nt.value), int(ne.value)
+
+    # --- projector (tr_scene_projector / tr_scene_get_projector) --------------------------------------
+    def _projector_args(self, who, params, image, occluder, mode, opacity, soft, depth_bias, width, height, format, stride):
+        """(params, image address, stride, occluder handle) of a projector call.  `params`: ProjectorParams, or the matrix
+        m, completed here from the image's shape, the keywords and whether there is an occluder."""
+        src, fmt, w, h, st = self._layer_source(image, who, width, height, format, stride)
+        ch = 4 if fmt == "rgba8" else 3
+        if occluder is not None and not isinstance(occluder, Scene):
+            raise ValueError("%s: occluder must be a Scene" % who)
+        if isinstance(params, ProjectorParams):
+            if (params.pw, params.ph, params.channels) != (w, h, ch):
+                raise ValueError("%s: image must be [ph, pw, channels] of the params" % who)
+            p = params
+        else:
+            p = projector_params(params, w, h, ch, mode, opacity, occluder is not None, soft, depth_bias, who)
+        return p, src, (st if st else w * ch), (occluder._h if occluder is not None else None)
+
+    def projector(self, params, image, occluder=None, out=None, mode="add", opacity=256, soft=False, depth_bias=0.0, width=None, height=None,
+                  format="rgb8", stride=0):
+        """tr_scene_projector: casts `image` onto the drawn pixels of the current frame on the device from a second camera
+        -- a slide projector, a decal, a light cookie; with `occluder`, a Scene of the image's size rendered from the
+        projector's camera (store_depth=True spares a depth-only repeat; it may be this scene), its depth shadows the
+        light.  `params`: projector_params(..), or just the matrix m (projector_matrix) with mode, opacity, soft and
+        depth_bias given here.  `image` as for layer: a torch uint8 tensor [ph, pw, 3 | 4] on the scene's device, a
+        page-locked array of the scene's (pinned_layer), or a device address (int) with width, height, format and
+        stride.  out=None: in place, by the kernel itself -- every later consumer sees the result; z, winner words and
+        the shadow buffer stay.  Otherwise `out` is a device pointer (int) or tensor of 3 * W * H bytes apart from every
+        frame buffer of the scene, or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous:
+        the result is there after sync() -- keep `image` alive until then.  Band scenes are refused.
+        projector_host is the rule."""
+        p, src, st, occ = self._projector_args("tr_scene_projector", params, image, occluder, mode, opacity, soft, depth_bias, width, height, format, stride)
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_projector(self._h, C.addressof(p), src, st, occ, ptr))
+        return out
+
+    def get_projector(self, params, image, occluder=None, strict=True, mode="add", opacity=256, soft=False, depth_bias=0.0, width=None, height=None,
+                      format="rgb8", stride=0):
+        """tr_scene_get_projector: the current frame with `image` cast on it on the device (arguments as for projector), as
+        an [H, W, 3] uint8 array.  Synchronizes; the scene's frame stays as it is."""
+        p, src, st, occ = self._projector_args("tr_scene_get_projector", params, image, occluder, mode, opacity, soft, depth_bias, width, height, format,
+                                               stride)
+        return self._image("tr_scene_get_projector", strict, C.addressof(p), src, st, occ)
+
+    def debug_projector_launches(self):
+        """tr_scene_debug_projector_launches: the k_projector launches this scene has enqueued so far (the kernel has no
+        entry in profile_read)."""
+        return check(load_library().tr_scene_debug_projector_launches(self._h))
 
     def project(self, points):
         """Model-space points [n, 3] as the scene's last camera (set_camera) places them: project_points under
