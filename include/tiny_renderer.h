@@ -1622,6 +1622,99 @@ int tr_projector_host(uint32_t width, uint32_t height, const uint8_t *rgb, const
                       const void *image, uint32_t image_stride, const float *occluder_z /* or NULL */, uint8_t *out /* may be rgb */);
 /* (tr_projector_matrix: below, with tr_uniforms) */
 
+/* Relight: up to eight coloured directional, point and spot lights, with a highlight, laid on the scene's CURRENT frame
+ * on the device from the frame's own depth -- a second light for a frame of any pipeline, a moving lamp per frame, and
+ * followed by tr_scene_projector with an occluder a shadow-casting, falling-off, coloured lamp.  Deferred: it reads the
+ * frame's colour and z alone.  u (column-major) maps frame raster (x, y, z, 1) -- x right, y UP, pixel (x, y) is frame
+ * row H - 1 - y and depth index x + y * W, z that depth -- to model space: the i_vpmv of the view's tr_uniforms
+ * (tr_prepare_uniforms kind 2).  eye is the camera's position in model space.  Every f32 operation is rounded once in
+ * the order written, nothing contracted, '/' and sqrt IEEE's.  For every DRAWN pixel (bits(z) != bits(f32::MIN)):
+ *   position   c[i] = ((u[i] x + u[4 + i] y) + u[8 + i] z) + u[12 + i], i = 0..3; accepted iff w = c[3] is finite and not
+ *              0; r = 1.0f / w once, P = (c0 r, c1 r, c2 r), accepted only if all three are finite.
+ *   normal     horizontally the candidates are (x + 1, y) and (x - 1, y), usable iff inside the frame, drawn and with a
+ *              position; both usable: the first iff |za - zc| <= |zb - zc| (the nearer in depth; the tie takes + ; a NaN
+ *              takes -), one: that one, none: no normal.  dx = P(a) - P or P - P(b).  The same vertically gives dy.
+ *              N = dx x dy, V = eye - P, N = -N if N.V < 0; no normal unless N.N is finite and > 0, N.V is not NaN and
+ *              V.V is finite and > 0.  n = N / sqrt(N.N), v = V / sqrt(V.V), a true division per component.
+ *   light      TR_LIGHT_DIRECTIONAL: L = dir (a unit vector TOWARDS the light), att = 1.  TR_LIGHT_POINT: D = pos - P,
+ *              d2 = D.D (skipped unless finite and > 0), L = D / sqrt(d2), att = 1.0f / (1.0f + falloff * d2).
+ *              TR_LIGHT_SPOT: a point light with c = (-L).dir (dir: the unit axis from the lamp along its beam) and
+ *              att = att * min(1, max(0, (c - cos_outer) * cone_scale)), cone_scale = 1 / (cos_inner - cos_outer).
+ *              diff = n.L; nothing unless diff > 0.  With specular > 0: h = normalize(L + v), s = max(0, n.h), squared
+ *              shininess_log2 times (the exponent 2^k), diff = diff + specular * s.  e = (diff * att) * intensity;
+ *              q = (u32)(min(e, 16) * 256.0f), 0..4096 (a NaN gives 0); per channel acc[c] += q * colour[c].
+ *   sample     s[c] = min(255, (256 * ambient[c] + acc[c] + 128) >> 8).  TR_RELIGHT_SHOW_NORMALS: instead
+ *              s[c] = (u8)((n[c] * 0.5f + 0.5f) * 255.0f), the lights ignored: a normal map of the picture.  Then with
+ *              TR_RELIGHT_ALBEDO s = (s d + 127) / 255 per channel, d the pixel's own colour: under TR_LAYER_ADD the
+ *              result is d + d * s, a coloured light on an already shaded picture; TR_LAYER_MULTIPLY alone lights an
+ *              unshaded one.
+ *   blend      the layer rule's blend of s into the pixel under `mode` with coverage 255 * opacity.
+ * A pixel that is not drawn, has no position or no normal keeps its colour.  Only colour changes: z, winner words and
+ * the shadow buffer stay.  A pixel reads its own colour and its neighbours' DEPTH only: the rule works in place.  Not
+ * here: shadows (follow with tr_scene_projector and an occluder), more than 8 lights in one call (call it again with
+ * TR_LAYER_ADD), area lights, band scenes. */
+#define TR_RELIGHT_MAX_LIGHTS 8u
+#define TR_LIGHT_DIRECTIONAL 0u
+#define TR_LIGHT_POINT 1u
+#define TR_LIGHT_SPOT 2u
+#define TR_RELIGHT_ALBEDO 0x1u
+#define TR_RELIGHT_SHOW_NORMALS 0x2u
+typedef struct tr_light {
+    uint32_t kind;           /* TR_LIGHT_DIRECTIONAL, TR_LIGHT_POINT, TR_LIGHT_SPOT */
+    float pos[3];            /* POINT, SPOT: where the lamp stands, in model space */
+    float dir[3];            /* DIRECTIONAL: the unit vector towards the light; SPOT: the unit axis along the beam */
+    uint8_t colour[4];       /* r, g, b, 0 */
+    float intensity;         /* >= 0 */
+    float falloff;           /* >= 0: att = 1 / (1 + falloff * distance^2) */
+    float cos_outer;         /* SPOT: the cosine of the cone's outer half angle */
+    float cone_scale;        /* SPOT: 1 / (cos_inner - cos_outer), > 0 */
+    float specular;          /* >= 0; 0: no highlight */
+    uint32_t shininess_log2; /* 0..10: the highlight's exponent is 2^k */
+    uint32_t reserved[2];    /* 0 */
+} tr_light;                  /* 64 bytes */
+typedef struct tr_relight_params {
+    float u[16];          /* column-major: frame raster (x, y, z, 1) -> model space; every entry finite */
+    float eye[3];         /* the camera's position in model space; finite */
+    uint8_t ambient[4];   /* r, g, b, 0 */
+    uint32_t mode;        /* TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE */
+    uint32_t opacity;     /* 0..256 */
+    uint32_t flags;       /* TR_RELIGHT_ALBEDO, TR_RELIGHT_SHOW_NORMALS */
+    uint32_t reserved[9]; /* 0 */
+} tr_relight_params;      /* 128 bytes */
+/* Lights the current frame.  Asynchronous and ordered like tr_scene_projector: frames held back are submitted, a pending
+ * clear is made real, a depth left on the chip is made real (the stage always reads depth), k_relight is enqueued on the
+ * scene's stream; the result is there after tr_scene_sync, and the scene's passes issued so far count as handed on.
+ * lights: n_lights entries of host memory, copied by the call (NULL only with n_lights == 0).  n_lights == 0 is no
+ * shortcut: the ambient term still blends into every pixel with a normal.
+ * out == NULL: in place, by the kernel itself.  A tile with nothing drawn loads nothing and is not touched; a tile whose
+ * colour fast-clear flag is up counts as zeros and is stored whole with its flag lowered iff one of its pixels changes;
+ * under TR_LAYER_MULTIPLY and TR_LAYER_DARKEN it stays black behind its flag.  Otherwise out: 3 W H bytes of device
+ * memory at any byte address or memory from tr_host_alloc, apart from every frame buffer of the scene; every byte of it
+ * is written and the scene's frame stays as it is.  A logically cleared scene is its own result: zeros out of place,
+ * nothing in place, no kernel.  opacity == 0: nothing in place, a copy of the frame out of place, and no k_relight.
+ * TR_E_INVALID with a tr_last_error text that names the call, nothing changed and nothing queued: a NULL scene or params,
+ * NULL lights with n_lights > 0; n_lights > 8; a kind above TR_LIGHT_SPOT; mode > TR_LAYER_DIFFERENCE; an unknown flag;
+ * opacity > 256; an entry of u, of eye or a float of a light that is not finite; falloff, intensity or specular below 0;
+ * a SPOT's cone_scale <= 0; shininess_log2 > 10; a fourth colour byte or a reserved word that is not 0; a BAND scene
+ * (tr_options.band_row0/1); `out` that is ordinary host memory, a pinned block that is too small, or overlaps a frame
+ * buffer of the scene. */
+int tr_scene_relight(tr_scene *s, const tr_relight_params *p, const tr_light *lights, uint32_t n_lights, void *out /* or NULL */);
+/* The lit frame into any host memory (3 W H bytes): waits for the scene first, works into a buffer of the library's,
+ * copies out and returns the frame's sticky status, like tr_scene_get_projector.  The scene's frame stays. */
+int tr_scene_get_relit(tr_scene *s, const tr_relight_params *p, const tr_light *lights, uint32_t n_lights, uint8_t *rgb);
+/* For the tests: the number of k_relight launches this scene has enqueued so far (a refused call and a shortcut add
+ * none).  The kernel has no entry in tr_scene_profile_read's table. */
+int tr_scene_debug_relight_launches(tr_scene *s);
+/* The rule above on the host (no GPU needed), by the very inline functions k_relight calls.  rgb and out: 3 * width *
+ * height bytes, row 0 = top; out may be rgb.  z: width * height floats, index x + y * width with y UP.  The same checks
+ * of the parameters; width and height 1..32768. */
+int tr_relight_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_relight_params *p, const tr_light *lights,
+                    uint32_t n_lights, uint8_t *out /* may be rgb */);
+/* Step normal alone, on the host, for choosing parameters and for the tests: normals, 3 floats a pixel, and valid, a byte
+ * a pixel (1: the pixel has a normal; 0: it has none and its floats are 0), both at index x + y * width with y UP like z.
+ * Of p only u and eye are used, but all of it is checked. */
+int tr_relight_normals_host(uint32_t width, uint32_t height, const float *z, const tr_relight_params *p, float *normals, uint8_t *valid);
+
 /* Distance field: for every pixel of the scene's CURRENT frame the squared Euclidean distance, in pixels, to the nearest
  * SEED of that frame, on the device -- the answer to "how far is this pixel from the model?", and with it an outer glow, a
  * stroke of any width, contour rings, a soft drop shadow, an inner glow, a dilate or an erode by a disc of radius up to

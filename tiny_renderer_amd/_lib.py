@@ -205,6 +205,11 @@ SYMBOLS = {
     "tr_scene_debug_projector_launches": (C.c_int, [C.c_void_p]),
     "tr_projector_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "tr_projector_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tr_scene_relight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_get_relit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_scene_debug_relight_launches": (C.c_int, [C.c_void_p]),
+    "tr_relight_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "tr_relight_normals_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_get_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "tr_scene_distance_ramp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

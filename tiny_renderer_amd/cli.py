@@ -211,6 +211,21 @@ def main(argv=None):
     ap.add_argument("--projector-bias", type=float, default=2.0, metavar="F",
                     help="with --projector-shadows: added to a pixel's depth before the shadow test (nearer is larger; default 2)")
     ap.add_argument("--projector-soft", action="store_true", help="with --projector-shadows: filter the shadow's edge over 2 x 2 texels")
+    ap.add_argument("--light-point", action="append", default=[], metavar="X,Y,Z:R,G,B[:INTENSITY[:FALLOFF]]",
+                    help="relight: a coloured point light at X,Y,Z (model space) laid on the frame on the GPU from normals recovered out of "
+                         "its depth (Scene.relight; repeatable, at most 8 lights in all; after --projector, before --fog; write a value that begins "
+                         "with a minus sign as --light-point=-1,2,3:..)")
+    ap.add_argument("--light-spot", action="append", default=[], metavar="X,Y,Z:AX,AY,AZ:R,G,B:INNER,OUTER[:INTENSITY[:FALLOFF]]",
+                    help="relight: a spot light at X,Y,Z shining at AX,AY,AZ, full inside INNER degrees, none outside OUTER (repeatable)")
+    ap.add_argument("--light-dir", action="append", default=[], metavar="X,Y,Z:R,G,B[:INTENSITY]",
+                    help="relight: a directional light; X,Y,Z points towards it (repeatable)")
+    ap.add_argument("--light-ambient", default=None, metavar="R,G,B", help="relight: the ambient term (default 0,0,0)")
+    ap.add_argument("--light-mode", default="add", choices=("normal", "add", "multiply", "screen", "lighten", "darken", "difference"),
+                    help="relight: how the light is blended into the frame (default add)")
+    ap.add_argument("--light-albedo", default=None, choices=("on", "off"),
+                    help="relight: multiply the light by the pixel's own colour first (default: on with --light-mode add, off otherwise)")
+    ap.add_argument("--light-specular", default=None, metavar="S,K", help="relight: a highlight of strength S and exponent 2^K (K 0..10) on every light")
+    ap.add_argument("--show-normals", action="store_true", help="relight: the normal map recovered from the depth instead of the lights")
     ap.add_argument("--fog", default=None, metavar="R,G,B",
                     help="depth ramp: fog of that colour, thickening with distance, blended into the model on the GPU (Scene.ramp "
                          "through ramp_fog; after --with, --ao and --backdrop, before the depth-of-field and bloom options)")
@@ -320,6 +335,17 @@ def main(argv=None):
             if (args.projector_soft or args.projector_bias != 2.0) and not args.projector_shadows:
                 raise ValueError("--projector-bias and --projector-soft go with --projector-shadows")
             args.projector_view = view
+        except ValueError as e:
+            ap.error(str(e))
+    args.relight = None
+    wants_light = bool(args.light_point or args.light_spot or args.light_dir or args.show_normals or args.light_ambient is not None)
+    if not wants_light and (args.light_mode != "add" or args.light_albedo is not None or args.light_specular is not None):
+        ap.error("--light-mode, --light-albedo and --light-specular go with --light-point, --light-spot, --light-dir, --light-ambient or --show-normals")
+    if wants_light:
+        if args.gpus > 1 or args.seconds > 0 or args.view != "frame":
+            ap.error("the --light options work on the frame of one GPU, by frame count: use --gpus 1, --frames and --view frame")
+        try:
+            args.relight = _parse_lights(args)
         except ValueError as e:
             ap.error(str(e))
     args.fog_colour = None
@@ -860,6 +886,8 @@ def _post(args, T, scene, say):
         scene.layer(back, where="undrawn")
     if args.projector_view is not None:
         _projector(args, T, scene, say)
+    if args.relight is not None:
+        _relight(args, T, scene, say)
     if args.fog_colour is not None or args.depth_view is not None or args.depth_contours is not None:
         # in place, under the blur and the bloom; a frame with nothing drawn has no span and only its background to fog
         try:
@@ -939,6 +967,66 @@ def _post(args, T, scene, say):
         say("stats --- pixels %d drawn %d nan %d z [%r, %r] box %r luma 1%% %d 50%% %d 99%% %d"
             % (st.n_pixels, st.n_drawn, st.n_nan, float(st.z_min), float(st.z_max), st.box,
                T.hist_percentile(st.luma, 0.01), T.hist_percentile(st.luma, 0.5), T.hist_percentile(st.luma, 0.99)))
+
+
+def _parse_lights(args):
+    """The --light options as plain values: {"lights": [(kind, groups of floats)], "ambient", "specular"}.  ValueError in
+    the option's words for a malformed one; the values themselves are checked by the builders when the lights are made."""
+    def groups(text, option, shape_min, shape_max):
+        parts = [[float(v) for v in g.split(",")] for g in text.split(":")]
+        sizes = [len(g) for g in parts]
+        if not (len(shape_min) <= len(parts) <= len(shape_max)) or sizes != list(shape_max[:len(parts)]):
+            raise ValueError("%s takes %s" % (option, {"--light-point": "X,Y,Z:R,G,B[:INTENSITY[:FALLOFF]]", "--light-dir": "X,Y,Z:R,G,B[:INTENSITY]",
+                                                       "--light-spot": "X,Y,Z:AX,AY,AZ:R,G,B:INNER,OUTER[:INTENSITY[:FALLOFF]]"}[option]))
+        return parts
+    lights = []
+    for t in args.light_point:
+        lights.append(("point", groups(t, "--light-point", (3, 3), (3, 3, 1, 1))))
+    for t in args.light_spot:
+        lights.append(("spot", groups(t, "--light-spot", (3, 3, 3, 2), (3, 3, 3, 2, 1, 1))))
+    for t in args.light_dir:
+        lights.append(("directional", groups(t, "--light-dir", (3, 3), (3, 3, 1))))
+    if len(lights) > 8:
+        raise ValueError("at most 8 lights in all")
+    ambient = [0, 0, 0] if args.light_ambient is None else [int(v) for v in args.light_ambient.split(",")]
+    if len(ambient) != 3 or min(ambient) < 0 or max(ambient) > 255:
+        raise ValueError("--light-ambient takes R,G,B, each 0..255")
+    specular = (0.0, 0)
+    if args.light_specular is not None:
+        sk = args.light_specular.split(",")
+        if len(sk) != 2 or not 0 <= int(sk[1]) <= 10 or not float(sk[0]) >= 0:
+            raise ValueError("--light-specular takes S,K with S >= 0 and K 0..10")
+        specular = (float(sk[0]), int(sk[1]))
+    return {"lights": lights, "ambient": ambient, "specular": specular}
+
+
+def _relight(args, T, scene, say):
+    """The --light options: the lights laid on the current frame in place, over the projector's image and under fog and
+    everything later.  The matrix is the i_vpmv of the frame's camera; its eye stands 5 units behind look_from."""
+    cam = getattr(scene, "_camera", None)
+    if cam is None:   # (frames rendered as a group: the last one's camera)
+        ca = np.float32(args.camera_angle + (2.0 * np.pi * (args.frames - 1) / args.frames if args.frames > 1 else 0.0))
+        cam = ([float(np.sin(ca)), 0.0, float(np.cos(ca))], [0.0, 0.0, 0.0], [0.0, 1.0, 0.0])
+    st, view = T.prepare_uniforms(2, scene.width, scene.height, getattr(scene, "_light", (0.0, 0.0, 1.0)), *cam)
+    if st != 0:
+        raise SystemExit("--light-*: the camera's matrix is singular")
+    eye = [float(cam[0][i]) + 5.0 * float(view.camera_direction[i]) for i in range(3)]
+    spec, shin = args.relight["specular"]
+    lights = []
+    try:
+        for kind, g in args.relight["lights"]:
+            if kind == "point":
+                lights.append(T.light_point(g[0], g[1], g[2][0] if len(g) > 2 else 1.0, g[3][0] if len(g) > 3 else 0.0, spec, shin))
+            elif kind == "spot":
+                lights.append(T.light_spot(g[0], g[1], g[3][0], g[3][1], g[2], g[4][0] if len(g) > 4 else 1.0, g[5][0] if len(g) > 5 else 0.0, spec, shin))
+            else:
+                lights.append(T.light_directional(g[0], g[1], g[2][0] if len(g) > 2 else 1.0, spec, shin))
+        albedo = None if args.light_albedo is None else args.light_albedo == "on"
+        p = T.relight_params(view, eye, args.relight["ambient"], args.light_mode, 256, albedo, args.show_normals)
+    except ValueError as e:
+        raise SystemExit("--light-*: %s" % e)
+    say("relight --- %d light%s, %s%s" % (len(lights), "" if len(lights) == 1 else "s", args.light_mode, ", normals" if args.show_normals else ""))
+    scene.relight(p, lights)
 
 
 def _projector(args, T, scene, say):

@@ -23,6 +23,7 @@
 #include "tr_outline.h"
 #include "tr_pack.h"
 #include "tr_projector.h"
+#include "tr_relight.h"
 #include "tr_resize.h"
 #include "tr_shadow_merge.h"
 #include "tr_skin.h"
@@ -151,6 +152,11 @@ int launch_ramp(const RampArgs &a, hipStream_t st, uint32_t cap, uint32_t *grid)
 // tr_projector.h, through the frame's fast-clear flags of z and of colour: k_projector, one workgroup a tile.  The whole
 // frame only (no band); the caller has made both depths real.  a.lower: null, or a.fbclean (in place).
 int launch_projector(const ProjectorArgs &a, hipStream_t st);
+// Relight: the lights of a.rule laid on the pixels of a.fb that have a normal, recovered from a.z behind a.zclean, into
+// a.out -- a.fb itself or a buffer apart from it, at any byte address -- by the rule of tr_relight.h, through the frame's
+// fast-clear flags of z and of colour: k_relight, one workgroup a tile.  The whole frame only (no band); the caller has
+// made the depth real.  a.lower: null, or a.fbclean (in place).
+int launch_relight(const RelightArgs &a, hipStream_t st);
 // Distance field: the three passes of tr_distance.h over the whole frame (no band), each its own kernel.  launch_dist_mask:
 // a.mask from a.fb (KEY) or a.z (DRAWN; the caller has made the depth real) through the fast-clear flags: k_dist_mask.
 // launch_dist_row: a.h and a.summary from a.mask: k_dist_row.  launch_dist: a.field (any 2-byte-aligned address) from

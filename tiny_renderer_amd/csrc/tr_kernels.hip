@@ -4236,6 +4236,192 @@ __global__ __launch_bounds__(PROJECTOR_THREADS) void k_projector(ProjectorArgs a
     if (in_place && clean && a.lower != nullptr && threadIdx.x == 0u) a.lower[t] = 0u;  // the tile holds the blend over zeros now
 }
 
+// Relight (tr_scene_relight): coloured directional, point and spot lights laid on the frame's pixels from normals
+// recovered out of its own z buffer, into `out`, which may BE the frame (a pixel's output depends on the depths around
+// it and on its own colour alone); tr_relight.h has the rule.  k_outline's form: one workgroup of 256 lanes per 128 x 16
+// tile of the frame, every tile launched.
+//   * the tile's own z flag is workgroup-uniform.  Raised, nothing is drawn in the tile: in place it is not touched, no
+//     load and no barrier; out of place it is copied (zeros behind a raised colour flag);
+//   * staging: z of the tile and a halo of ONE pixel go to LDS as 18 rows of 136 floats that start 4 pixels left of the
+//     tile (k_outline's rows: a 16-byte piece is aligned in memory and lies in one tile); a piece in a neighbour tile
+//     whose z flag is up, or outside the frame, is filled with f32::MIN without a load.  The lane that stages a depth
+//     computes its POSITION at once (relight_position: the matrix product and the one IEEE reciprocal) into three more
+//     LDS planes, x = NaN where there is none -- once per staged pixel, where a pixel would otherwise pay for its own and
+//     its four neighbours'.  Whether a staged pixel is inside the frame comes from its coordinates, never from LDS.
+//     Only columns 3 .. 132 of a row are looked at.  39 KB of LDS; one barrier;
+//   * a unit is four pixels of a row (k_grade's); a lane takes two units, eight rows apart.  A pixel with a position
+//     reads its four neighbours' entries of every plane and runs the rule's own functions; the light table sits in the
+//     kernel arguments and is read through scalar loads, the loop over it and every branch on a light's kind is
+//     wave-uniform;
+//   * colour: zeros behind a raised colour flag (no load), else the unit's twelve bytes.  Out of place every unit of the
+//     tile is stored.  In place only units with a CHANGED pixel are stored; a flagged tile votes (__syncthreads_or)
+//     whether one of its pixels changes: if so it is stored whole and lane 0 lowers the flag (the vote is the barrier
+//     behind which every wave has read it), otherwise it is not touched.  Under MULTIPLY and DARKEN a flagged tile stays
+//     black behind its flag and returns at once.
+// WIDE: width % 4 == 0, z 16-byte and fb / out 4-byte aligned (the launcher checks): z in 16-byte pieces, a unit as three
+// aligned words; otherwise the same through element accesses guarded by the width.  z, its flags, the winner words and
+// the shadow buffer are only read.  No atomics, no scratch; no inline assembly beyond tr_math.h's conversions.
+constexpr int RELIGHT_LDS_W = TILE_W + 8, RELIGHT_LDS_H = TILE_H + 2, RELIGHT_PLANE = RELIGHT_LDS_W * RELIGHT_LDS_H;
+constexpr int RELIGHT_THREADS = 256, RELIGHT_UNITS = TILE_W * TILE_H / 4 / RELIGHT_THREADS;
+
+// The tap at LDS index i of the four planes (z, then the position's x, y, z).
+__device__ __forceinline__ RelightTap relight_tap(const float *s, int32_t i)
+{
+    RelightTap t;
+    t.z = s[i];
+    t.P = make3(s[RELIGHT_PLANE + i], s[2 * RELIGHT_PLANE + i], s[3 * RELIGHT_PLANE + i]);
+    t.ok = t.P.x == t.P.x;
+    return t;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(RELIGHT_THREADS) void k_relight(RelightArgs a)
+{
+    static_assert(TILE_W == 128 && TILE_H == 16 && RELIGHT_UNITS == 2, "32 units to a row of a tile, two rounds of eight rows");
+    static_assert(RELIGHT_LDS_W % 4 == 0 && 4 * RELIGHT_PLANE * 4 <= 40 * 1024, "16-byte pieces; four planes in 40 KB");
+    __shared__ __attribute__((aligned(16))) float s_t[4 * RELIGHT_PLANE];
+    const uint32_t t = blockIdx.x;
+    const int32_t W = (int32_t)a.frame.width, H = (int32_t)a.frame.height;
+    const int32_t ntx = (int32_t)a.frame.ntx, nty = (int32_t)a.frame.nty;
+    const int32_t tx = (int32_t)t % ntx, ty = (int32_t)t / ntx;
+    const int32_t x0 = tx * TILE_W, y0 = ty * TILE_H;
+    const RelightRule &q = a.rule;
+    const bool in_place = a.out == a.fb;
+    const bool clean = a.fbclean != nullptr && a.fbclean[t] != 0u;  // (workgroup-uniform)
+    const bool empty = a.zclean[t] != 0u;                           // (workgroup-uniform) nothing is drawn in the tile
+    if (in_place && (empty || (clean && (q.mode == LAYER_MULTIPLY || q.mode == LAYER_DARKEN)))) return;
+    if (!empty) {  // (workgroup-uniform: the barrier is reached by all or none)
+        // bit 3 * ay + ax: the tile at (tx + ax - 1, ty + ay - 1) reads as f32::MIN -- flag up, or no such tile
+        uint32_t stale = 0u;
+#pragma unroll
+        for (int32_t ay = 0; ay < 3; ay++)
+#pragma unroll
+            for (int32_t ax = 0; ax < 3; ax++) {
+                const int32_t nx = tx + ax - 1, ny = ty + ay - 1;
+                bool up = nx < 0 || nx >= ntx || ny < 0 || ny >= nty;
+                if (!up) up = a.zclean[ny * ntx + nx] != 0u;
+                if (up) stale |= 1u << (3 * ay + ax);
+            }
+        // LDS row r is frame row y0 - 1 + r, LDS column c frame column x0 - 4 + c
+        const float z_min = bits_f32(TR_F32_MIN_BITS), none = __builtin_nanf("");
+        if (WIDE) {
+            for (int32_t p = (int32_t)threadIdx.x; p < RELIGHT_LDS_H * (RELIGHT_LDS_W / 4); p += RELIGHT_THREADS) {
+                const int32_t r = p / (RELIGHT_LDS_W / 4), j = p % (RELIGHT_LDS_W / 4);
+                const int32_t px = x0 - 4 + 4 * j, py = y0 - 1 + r;
+                const int32_t ax = j < 1 ? 0 : j < 1 + TILE_W / 4 ? 1 : 2, ay = py < y0 ? 0 : py < y0 + TILE_H ? 1 : 2;
+                float zv[4] = { z_min, z_min, z_min, z_min };
+                const bool live = ((stale >> (3 * ay + ax)) & 1u) == 0u && px < W && py < H;  // (WIDE: the piece is inside whole, or outside)
+                if (live) {
+                    const float4 v = *reinterpret_cast<const float4 *>(a.z + (size_t)py * (size_t)W + (size_t)px);
+                    zv[0] = v.x, zv[1] = v.y, zv[2] = v.z, zv[3] = v.w;
+                }
+                float pv[3][4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int32_t c = 4 * j + i;
+                    vec3 P = make3(none, none, none);
+                    if (live && c >= 3 && c <= 4 + TILE_W) {
+                        vec3 got;
+                        if (relight_position(q.u, px + i, py, zv[i], got)) P = got;
+                    }
+                    pv[0][i] = P.x, pv[1][i] = P.y, pv[2][i] = P.z;
+                }
+                const int32_t at = r * RELIGHT_LDS_W + 4 * j;
+                *reinterpret_cast<float4 *>(&s_t[at]) = make_float4(zv[0], zv[1], zv[2], zv[3]);
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    *reinterpret_cast<float4 *>(&s_t[(k + 1) * RELIGHT_PLANE + at]) = make_float4(pv[k][0], pv[k][1], pv[k][2], pv[k][3]);
+            }
+        } else {
+            for (int32_t p = (int32_t)threadIdx.x; p < RELIGHT_PLANE; p += RELIGHT_THREADS) {
+                const int32_t r = p / RELIGHT_LDS_W, c = p % RELIGHT_LDS_W;
+                if (c < 3 || c > 4 + TILE_W) continue;  // (no pixel of the tile looks at it)
+                const int32_t px = x0 - 4 + c, py = y0 - 1 + r;
+                const int32_t ax = c < 4 ? 0 : c < 4 + TILE_W ? 1 : 2, ay = py < y0 ? 0 : py < y0 + TILE_H ? 1 : 2;
+                float v = z_min;
+                vec3 P = make3(none, none, none);
+                if (((stale >> (3 * ay + ax)) & 1u) == 0u && px < W && py < H) {
+                    v = a.z[(size_t)py * (size_t)W + (size_t)px];
+                    vec3 got;
+                    if (relight_position(q.u, px, py, v, got)) P = got;
+                }
+                s_t[p] = v, s_t[RELIGHT_PLANE + p] = P.x, s_t[2 * RELIGHT_PLANE + p] = P.y, s_t[3 * RELIGHT_PLANE + p] = P.z;
+            }
+        }
+        __syncthreads();
+    }
+    // the units of k_grade
+    const int32_t ux = 4 * (int32_t)(threadIdx.x % 32u), x = x0 + ux, row_first = (int32_t)(threadIdx.x / 32u);
+    const int32_t n_px = WIDE ? 4 : min(4, W - x);  // (WIDE: 4, or the unit is outside)
+    bool inside[RELIGHT_UNITS];
+    size_t ci[RELIGHT_UNITS];
+    uint32_t d[RELIGHT_UNITS][4], m[RELIGHT_UNITS];  // m: bit i: pixel i of the unit has changed
+#pragma unroll
+    for (int h = 0; h < RELIGHT_UNITS; h++) {
+        const int32_t row = row_first + 8 * h, y = y0 + row;
+        inside[h] = x < W && y < H;
+        ci[h] = inside[h] ? ((size_t)(H - 1 - y) * (size_t)W + (size_t)x) * 3u : 0u;
+        m[h] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[h][i] = 0u;
+        if (!inside[h]) continue;
+        if (!clean) {
+            const uint8_t *c = a.fb + ci[h];
+            if (WIDE) {
+                const uint32_t *cw = reinterpret_cast<const uint32_t *>(c);
+                const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+                d[h][0] = w0 & 0xFFFFFFu;
+                d[h][1] = (w0 >> 24) | ((w1 & 0xFFFFu) << 8);
+                d[h][2] = (w1 >> 16) | ((w2 & 0xFFu) << 16);
+                d[h][3] = w2 >> 8;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    if (i < n_px) d[h][i] = grade_pack(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+            }
+        }
+        if (empty) continue;
+        // the unit's window: LDS row row + 1, columns 3 + ux .. 8 + ux of it, 4 + ux .. 7 + ux of the rows around
+        const int32_t mid = (row + 1) * RELIGHT_LDS_W + 4 + ux;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (i >= n_px) continue;
+            const RelightTap c = relight_tap(s_t, mid + i);
+            if (!c.ok) continue;
+            uint32_t v;
+            if (relight_px(q, c, relight_tap(s_t, mid + i + 1), relight_tap(s_t, mid + i - 1), relight_tap(s_t, mid + i + RELIGHT_LDS_W),
+                           relight_tap(s_t, mid + i - RELIGHT_LDS_W), d[h][i], v) &&
+                v != d[h][i])
+                d[h][i] = v, m[h] |= 1u << i;
+        }
+    }
+    bool store_all = !in_place;
+    if (in_place && clean) {  // (workgroup-uniform: the vote is reached by all or none)
+        store_all = __syncthreads_or((int)(m[0] | m[1])) != 0;
+        if (!store_all) return;
+    }
+#pragma unroll
+    for (int h = 0; h < RELIGHT_UNITS; h++) {
+        if (!inside[h] || (!store_all && m[h] == 0u)) continue;
+        uint8_t *o = a.out + ci[h];
+        if (WIDE) {
+            uint32_t *ow = reinterpret_cast<uint32_t *>(o);
+            ow[0] = d[h][0] | (d[h][1] << 24);
+            ow[1] = (d[h][1] >> 8) | (d[h][2] << 16);
+            ow[2] = (d[h][2] >> 16) | (d[h][3] << 8);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                if (i < n_px) {
+                    o[3 * i + 0] = (uint8_t)(d[h][i] & 0xFFu);
+                    o[3 * i + 1] = (uint8_t)((d[h][i] >> 8) & 0xFFu);
+                    o[3 * i + 2] = (uint8_t)((d[h][i] >> 16) & 0xFFu);
+                }
+        }
+    }
+    if (in_place && clean && a.lower != nullptr && threadIdx.x == 0u) a.lower[t] = 0u;  // the tile holds the lights over zeros now
+}
+
 // Outlines (tr_scene_outline): ink laid over the frame's colour where its own z buffer has a silhouette, a depth step or
 // a fold, into `out`, which may BE the frame (a pixel's output depends on the depths around it and on its own colour
 // alone); tr_outline.h has the rule.  One workgroup of 256 lanes per 128 x 16 tile of the frame, the tiles of k_ao.
@@ -6405,6 +6591,33 @@ int launch_projector(const ProjectorArgs &a, hipStream_t st)
         hipLaunchKernelGGL((k_projector<true>), dim3(n_tiles), dim3(PROJECTOR_THREADS), 0, st, a);
     else
         hipLaunchKernelGGL((k_projector<false>), dim3(n_tiles), dim3(PROJECTOR_THREADS), 0, st, a);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_relight(const RelightArgs &a, hipStream_t st)
+{
+    const uint32_t W = a.frame.width, H = a.frame.height, n_tiles = a.frame.ntx * a.frame.nty;
+    if (n_tiles == 0) return 0;
+    const RelightRule &q = a.rule;
+    if (!a.fb || !a.out || !a.z || !a.zclean) return (int)hipErrorInvalidValue;
+    // the whole frame's tile grid (both flag sets and z are indexed by it), the rule's limits
+    if (a.frame.ty_base != 0 || a.frame.band_y0 != 0 || a.frame.band_y1 != (int32_t)H) return (int)hipErrorInvalidValue;
+    if (a.frame.ntx != (W + TILE_W - 1) / TILE_W || a.frame.nty != (H + TILE_H - 1) / TILE_H) return (int)hipErrorInvalidValue;
+    if (q.mode >= LAYER_MODES || q.opacity > 256u || (q.flags & ~(RELIGHT_ALBEDO | RELIGHT_SHOW_NORMALS)) != 0u || q.n_lights > RELIGHT_MAX_LIGHTS)
+        return (int)hipErrorInvalidValue;
+    for (uint32_t l = 0; l < q.n_lights; l++)
+        if (q.lights[l].kind > RELIGHT_SPOT || q.lights[l].shininess_log2 > RELIGHT_MAX_SHININESS_LOG2) return (int)hipErrorInvalidValue;
+    // `out` is the frame itself or apart from it; a flag is lowered in place only
+    const size_t bytes = (size_t)W * H * 3u;
+    if (a.out != a.fb && (const uint8_t *)a.out < a.fb + bytes && a.fb < (const uint8_t *)a.out + bytes) return (int)hipErrorInvalidValue;
+    if (a.lower != nullptr && (a.out != a.fb || a.lower != a.fbclean)) return (int)hipErrorInvalidValue;
+    // whole words: every unit of four pixels is three aligned words of either buffer, its depths one 16-byte piece
+    const bool wide = W % 4u == 0u && ((uintptr_t)a.fb | (uintptr_t)a.out) % 4u == 0u && (uintptr_t)a.z % 16u == 0u;
+    if (wide)
+        hipLaunchKernelGGL((k_relight<true>), dim3(n_tiles), dim3(RELIGHT_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((k_relight<false>), dim3(n_tiles), dim3(RELIGHT_THREADS), 0, st, a);
     TR_LAUNCH_CHECK();
     return 0;
 }

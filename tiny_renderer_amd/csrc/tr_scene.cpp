@@ -409,6 +409,8 @@ struct tr_scene {
     uint32_t ramp_n = 0, ramp_cap = 0, ramp_grid = 0;
     // tr_scene_debug_projector_launches: the k_projector launches of this scene so far
     uint32_t projector_launches = 0;
+    // tr_scene_debug_relight_launches: the k_relight launches of this scene so far
+    uint32_t relight_launches = 0;
     // the distance field's scratch, allocated by the first call that needs it and kept: the mask (a bit a pixel, 64-bit
     // words, rows padded to whole words), the row distances (a byte a pixel), the summary (a byte a word of the mask) and,
     // for the ramp calls alone, the u16 field
@@ -2863,7 +2865,7 @@ int finish_read_back(tr_scene *s, int frame_status, void *dst, const void *src, 
 // ---------------------------------------------------------------------------------------------
 // Stage entry points: what tr_scene_<stage>(.., out) and tr_scene_get_<stage>(.., rgb) share
 // ---------------------------------------------------------------------------------------------
-// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines, distance, projector) derives an image from the current frame.  Its own code is
+// A stage (resolve, accumulate, depth of field, bloom, grade, outline, antialias, warp, convolve, rank, bilateral, resize, to_yuv, layer, ramp, lines, distance, projector, relight) derives an image from the current frame.  Its own code is
 // its checks and its enqueue_*; the rest is the helpers below, called in one order ("Adding a stage"):
 //   tr_scene_<stage>: null scene; parameter checks; scene checks (band, table, unusable()); hipSetDevice; classify_out
 //   for a non-null `out`, then refuse_overlap (resolve and resize have none; to_yuv has no in-place form either); the cleared-scene shortcut where the stage has one --
@@ -6623,6 +6625,181 @@ int tr_projector_matrix(const tr_uniforms *view, const tr_uniforms *projector, f
             const double s1 = s0 + t2;
             m[4 * c + r] = (float)(s1 + t3);
         }
+    return TR_OK;
+}
+
+namespace {
+
+static_assert(TR_RELIGHT_MAX_LIGHTS == RELIGHT_MAX_LIGHTS && TR_LIGHT_DIRECTIONAL == RELIGHT_DIRECTIONAL && TR_LIGHT_POINT == RELIGHT_POINT &&
+                  TR_LIGHT_SPOT == RELIGHT_SPOT && TR_RELIGHT_ALBEDO == RELIGHT_ALBEDO && TR_RELIGHT_SHOW_NORMALS == RELIGHT_SHOW_NORMALS &&
+                  sizeof(tr_relight_params) == 128 && sizeof(tr_light) == 64 && sizeof(tr_light) == sizeof(RelightLight) &&
+                  offsetof(tr_light, pos) == offsetof(RelightLight, pos) && offsetof(tr_light, dir) == offsetof(RelightLight, dir) &&
+                  offsetof(tr_light, colour) == offsetof(RelightLight, colour) && offsetof(tr_light, intensity) == offsetof(RelightLight, intensity) &&
+                  offsetof(tr_light, specular) == offsetof(RelightLight, specular) &&
+                  offsetof(tr_light, shininess_log2) == offsetof(RelightLight, shininess_log2),
+              "tr_relight.h restates the header");
+
+// tr_relight_params and the light table as every entry point accepts them (`who` names the entry point in the error text).
+int check_relight_params(const tr_relight_params *p, const tr_light *lights, uint32_t n_lights, const char *who)
+{
+    const std::string w(who);
+    if (!p || (!lights && n_lights > 0u)) return tr::fail(TR_E_INVALID, w + ": null argument");
+    if (n_lights > TR_RELIGHT_MAX_LIGHTS) return tr::fail(TR_E_INVALID, w + ": n_lights must be 0..TR_RELIGHT_MAX_LIGHTS");
+    if (p->mode > TR_LAYER_DIFFERENCE) return tr::fail(TR_E_INVALID, w + ": mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE");
+    if ((p->flags & ~(TR_RELIGHT_ALBEDO | TR_RELIGHT_SHOW_NORMALS)) != 0u) return tr::fail(TR_E_INVALID, w + ": unknown flags");
+    if (p->opacity > 256u) return tr::fail(TR_E_INVALID, w + ": opacity must be 0..256");
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(p->u[i])) return tr::fail(TR_E_INVALID, w + ": every entry of u must be finite");
+    for (int i = 0; i < 3; i++)
+        if (!std::isfinite(p->eye[i])) return tr::fail(TR_E_INVALID, w + ": every entry of eye must be finite");
+    if (p->ambient[3] != 0u) return tr::fail(TR_E_INVALID, w + ": the fourth byte of ambient must be 0");
+    for (uint32_t v : p->reserved)
+        if (v != 0u) return tr::fail(TR_E_INVALID, w + ": reserved must be 0");
+    for (uint32_t k = 0; k < n_lights; k++) {
+        const tr_light &l = lights[k];
+        const std::string wl = w + ": light " + std::to_string(k);
+        if (l.kind > TR_LIGHT_SPOT) return tr::fail(TR_E_INVALID, wl + ": kind must be TR_LIGHT_DIRECTIONAL .. TR_LIGHT_SPOT");
+        const float f[11] = { l.pos[0], l.pos[1], l.pos[2], l.dir[0], l.dir[1], l.dir[2], l.intensity, l.falloff, l.cos_outer, l.cone_scale, l.specular };
+        for (float v : f)
+            if (!std::isfinite(v)) return tr::fail(TR_E_INVALID, wl + ": every float must be finite");
+        if (l.intensity < 0.0f) return tr::fail(TR_E_INVALID, wl + ": intensity must be >= 0");
+        if (l.falloff < 0.0f) return tr::fail(TR_E_INVALID, wl + ": falloff must be >= 0");
+        if (l.specular < 0.0f) return tr::fail(TR_E_INVALID, wl + ": specular must be >= 0");
+        if (l.kind == TR_LIGHT_SPOT && !(l.cone_scale > 0.0f)) return tr::fail(TR_E_INVALID, wl + ": cone_scale must be > 0");
+        if (l.shininess_log2 > RELIGHT_MAX_SHININESS_LOG2) return tr::fail(TR_E_INVALID, wl + ": shininess_log2 must be 0..10");
+        if (l.colour[3] != 0u) return tr::fail(TR_E_INVALID, wl + ": the fourth byte of colour must be 0");
+        if (l.reserved[0] != 0u || l.reserved[1] != 0u) return tr::fail(TR_E_INVALID, wl + ": reserved must be 0");
+    }
+    return TR_OK;
+}
+
+int check_relight_scene(const tr_scene *s, const char *who)
+{
+    if (!whole_frame(s))
+        return tr::fail(TR_E_INVALID, std::string(who) + ": a band scene (tr_options.band_row0/1) cannot be relit: "
+                                                         "its border neighbours lie in another rank's rows");
+    if (s->broken) return unusable();
+    return TR_OK;
+}
+
+// The rule of checked parameters.
+RelightRule relight_rule(const tr_relight_params *p, const tr_light *lights, uint32_t n_lights)
+{
+    RelightRule r = {};
+    memcpy(r.u, p->u, sizeof r.u);
+    memcpy(r.eye, p->eye, sizeof r.eye);
+    r.ambient = grade_pack(p->ambient[0], p->ambient[1], p->ambient[2]);
+    r.mode = p->mode, r.opacity = p->opacity, r.flags = p->flags, r.n_lights = n_lights;
+    if (n_lights > 0u) memcpy(r.lights, lights, (size_t)n_lights * sizeof(tr_light));
+    return r;
+}
+
+// Enqueues the lights onto the current frame into `out_device` (null: in place) behind everything issued so far.  A
+// pending clear is made real (the kernel then runs on raised flags), and the stage always reads depth: one left on the
+// chip is made real first.
+int enqueue_relight(tr_scene *s, const RelightRule &r, uint8_t *out_device)
+{
+    int st = flush_clear_color(s);  // (submits what is held back, too)
+    if (st == TR_OK) st = depth_in_memory(s);
+    if (st != TR_OK) return st;
+    RelightArgs a = {};
+    a.fb = s->d_fb;
+    a.fbclean = s->d_fbclean;
+    a.out = out_device ? out_device : s->d_fb;
+    a.lower = out_device ? nullptr : s->d_fbclean;
+    a.z = s->d_z;
+    a.zclean = s->d_zclean;
+    a.frame = s->frame;
+    a.rule = r;
+    // (no profile entry, like k_projector: the launches are counted for tr_scene_debug_relight_launches, and
+    // scripts/probe_relight.py times the kernel with events)
+    int rc = launch_relight(a, s->stream);
+    if (rc) return launch_status(rc, "k_relight");
+    s->relight_launches += 1u;
+    s->quiescent = false;
+    return TR_OK;
+}
+
+// opacity == 0 out of place: the frame as it is.  Tiles behind a raised colour flag hold stale memory, so the copy is
+// k_layer's, with a layer that misses the frame: it stores zeros for them.  No k_relight runs.
+int relight_copy(tr_scene *s, uint8_t *out_device)
+{
+    LayerRule miss = {};
+    miss.mode = LAYER_NORMAL, miss.format = LAYER_RGB8, miss.opacity = 0u;
+    miss.x = (int32_t)s->width, miss.y = 0, miss.width = 1u, miss.height = 1u, miss.stride = 3u;
+    // The layer lies one column right of the frame, so its clipped rectangle is empty and k_layer loads no byte of it
+    // (layer_into's own road for a layer that misses).  launch_layer still wants an image that is not null and does not
+    // overlap `out`: the frame itself is one -- frame_out has refused an `out` that overlaps it -- and is device memory
+    // of at least the layer's three bytes, should a later k_layer ever look.
+    const uint8_t *never_read = s->d_fb;
+    return enqueue_layer(s, miss, never_read, nullptr, out_device);
+}
+
+}  // namespace
+
+int tr_scene_relight(tr_scene *s, const tr_relight_params *p, const tr_light *lights, uint32_t n_lights, void *out)
+{
+    const char *who = "tr_scene_relight";
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_relight: null scene");
+    int st = check_relight_params(p, lights, n_lights, who);
+    if (st == TR_OK) st = check_relight_scene(s, who);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    void *target = nullptr;
+    st = frame_out(s, out, who, "tr_scene_get_relit", "relights", 0u, &target);
+    if (st != TR_OK) return st;
+    // a logically cleared scene has nothing drawn: zeros out of place, itself in place; opacity 0 changes nothing
+    if (s->z_fb_cleared) return target ? cleared_out_of_place(s, target) : TR_OK;
+    if (p->opacity == 0u) {
+        if (!target) return TR_OK;
+        st = relight_copy(s, (uint8_t *)target);
+    } else {
+        st = enqueue_relight(s, relight_rule(p, lights, n_lights), (uint8_t *)target);
+    }
+    if (st == TR_OK) handed_on(s);
+    return st;
+}
+
+int tr_scene_get_relit(tr_scene *s, const tr_relight_params *p, const tr_light *lights, uint32_t n_lights, uint8_t *rgb)
+{
+    const char *who = "tr_scene_get_relit";
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_get_relit: null scene");
+    int st = check_relight_params(p, lights, n_lights, who);
+    if (st == TR_OK && !rgb) st = tr::fail(TR_E_INVALID, "tr_scene_get_relit: null argument");
+    if (st == TR_OK) st = check_relight_scene(s, who);
+    if (st != TR_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const RelightRule r = relight_rule(p, lights, n_lights);
+    return get_stage(s, rgb, frame_bytes(s), cleared, [&](uint8_t *o) { return r.opacity == 0u ? relight_copy(s, o) : enqueue_relight(s, r, o); });
+}
+
+int tr_scene_debug_relight_launches(tr_scene *s)
+{
+    if (!s) return tr::fail(TR_E_INVALID, "tr_scene_debug_relight_launches: null scene");
+    return (int)s->relight_launches;
+}
+
+// The rule of tr_relight.h over caller's arrays, on the host.  Needs no GPU.
+int tr_relight_host(uint32_t width, uint32_t height, const uint8_t *rgb, const float *z, const tr_relight_params *p, const tr_light *lights,
+                    uint32_t n_lights, uint8_t *out)
+{
+    int st = check_relight_params(p, lights, n_lights, "tr_relight_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || width > 32768u || height < 1u || height > 32768u)
+        return tr::fail(TR_E_INVALID, "tr_relight_host: the frame's width and height must be 1..32768");
+    if (!rgb || !z || !out) return tr::fail(TR_E_INVALID, "tr_relight_host: null argument");
+    relight_host(width, height, rgb, z, relight_rule(p, lights, n_lights), out);
+    return TR_OK;
+}
+
+int tr_relight_normals_host(uint32_t width, uint32_t height, const float *z, const tr_relight_params *p, float *normals, uint8_t *valid)
+{
+    int st = check_relight_params(p, nullptr, 0u, "tr_relight_normals_host");
+    if (st != TR_OK) return st;
+    if (width < 1u || width > 32768u || height < 1u || height > 32768u)
+        return tr::fail(TR_E_INVALID, "tr_relight_normals_host: the frame's width and height must be 1..32768");
+    if (!z || !normals || !valid) return tr::fail(TR_E_INVALID, "tr_relight_normals_host: null argument");
+    relight_normals_host(width, height, z, p->u, p->eye, normals, valid);
     return TR_OK;
 }
 

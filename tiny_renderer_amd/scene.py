@@ -1129,6 +1129,158 @@ def projector_host(rgb, z, params, image, occluder_z=None, in_place=False):
     return out
 
 
+RELIGHT_MAX_LIGHTS, RELIGHT_ALBEDO, RELIGHT_SHOW_NORMALS = 8, 1, 2   # (TR_RELIGHT_MAX_LIGHTS, TR_RELIGHT_ALBEDO, TR_RELIGHT_SHOW_NORMALS)
+LIGHT_KINDS = {"directional": 0, "point": 1, "spot": 2}                # (TR_LIGHT_*)
+
+
+class Light(C.Structure):
+    """tr_light"""
+    _fields_ = [("kind", C.c_uint32), ("pos", C.c_float * 3), ("dir", C.c_float * 3), ("colour", C.c_uint8 * 4), ("intensity", C.c_float),
+                ("falloff", C.c_float), ("cos_outer", C.c_float), ("cone_scale", C.c_float), ("specular", C.c_float),
+                ("shininess_log2", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RelightParams(C.Structure):
+    """tr_relight_params"""
+    _fields_ = [("u", C.c_float * 16), ("eye", C.c_float * 3), ("ambient", C.c_uint8 * 4), ("mode", C.c_uint32), ("opacity", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 9)]
+
+
+def _light(kind, pos, direction, colour, intensity, falloff, cos_outer, cone_scale, specular, shininess_log2, who):
+    """A checked tr_light: ValueError, in the library's words, for what it would refuse."""
+    with np.errstate(over="ignore"):
+        f = np.array(list(pos) + list(direction) + [intensity, falloff, cos_outer, cone_scale, specular], np.float64).astype(np.float32)
+    if f.shape != (11,) or not np.isfinite(f).all():
+        raise ValueError("%s: every float must be finite" % who)
+    if isinstance(shininess_log2, bool) or not isinstance(shininess_log2, (int, np.integer)):
+        raise ValueError("%s: shininess_log2 must be an integer" % who)
+    col = [int(v) for v in colour]
+    if len(col) != 3 or min(col) < 0 or max(col) > 255:
+        raise ValueError("%s: colour takes three values 0..255" % who)
+    if f[6] < 0:
+        raise ValueError("%s: intensity must be >= 0" % who)
+    if f[7] < 0:
+        raise ValueError("%s: falloff must be >= 0" % who)
+    if f[10] < 0:
+        raise ValueError("%s: specular must be >= 0" % who)
+    if kind == LIGHT_KINDS["spot"] and not f[9] > 0:
+        raise ValueError("%s: cone_scale must be > 0" % who)
+    if not 0 <= shininess_log2 <= 10:
+        raise ValueError("%s: shininess_log2 must be 0..10" % who)
+    return Light(kind, (C.c_float * 3)(*[float(v) for v in f[0:3]]), (C.c_float * 3)(*[float(v) for v in f[3:6]]), (C.c_uint8 * 4)(*col, 0),
+                 float(f[6]), float(f[7]), float(f[8]), float(f[9]), float(f[10]), int(shininess_log2), (C.c_uint32 * 2)(0, 0))
+
+
+def _unit3(v, who, what):
+    """v / |v| in double, for the builders: the rule takes direction and axis vectors as given."""
+    a = np.asarray(v, np.float64)
+    n = float(np.sqrt((a * a).sum())) if a.shape == (3,) else 0.0
+    if a.shape != (3,) or not np.isfinite(n) or n == 0.0:
+        raise ValueError("%s: %s must be three finite values, not all 0" % (who, what))
+    return a / n
+
+
+def light_directional(direction, colour=(255, 255, 255), intensity=1.0, specular=0.0, shininess_log2=0):
+    """A TR_LIGHT_DIRECTIONAL tr_light: `direction` points TOWARDS the light (normalised here), in model space."""
+    return _light(0, (0.0, 0.0, 0.0), _unit3(direction, "light_directional", "direction"), colour, intensity, 0.0, 0.0, 0.0, specular, shininess_log2,
+                  "light_directional")
+
+
+def light_point(pos, colour=(255, 255, 255), intensity=1.0, falloff=0.0, specular=0.0, shininess_log2=0):
+    """A TR_LIGHT_POINT tr_light at `pos` (model space): att = 1 / (1 + falloff * distance^2)."""
+    return _light(1, pos, (0.0, 0.0, 0.0), colour, intensity, falloff, 0.0, 0.0, specular, shininess_log2, "light_point")
+
+
+def light_spot(pos, at, inner_deg, outer_deg, colour=(255, 255, 255), intensity=1.0, falloff=0.0, specular=0.0, shininess_log2=0):
+    """A TR_LIGHT_SPOT tr_light at `pos` shining towards `at` (model space): full inside the half angle inner_deg, none
+    outside outer_deg, a linear ramp in the cosine between; 0 <= inner_deg < outer_deg <= 90."""
+    if not 0.0 <= float(inner_deg) < float(outer_deg) <= 90.0:
+        raise ValueError("light_spot: 0 <= inner_deg < outer_deg <= 90")
+    axis = _unit3(np.asarray(at, np.float64) - np.asarray(pos, np.float64), "light_spot", "at - pos")
+    ci, co = np.cos(np.radians(float(inner_deg))), np.cos(np.radians(float(outer_deg)))
+    return _light(2, pos, axis, colour, intensity, falloff, co, 1.0 / (ci - co), specular, shininess_log2, "light_spot")
+
+
+def relight_params(uniforms, eye, ambient=(0, 0, 0), mode="add", opacity=256, albedo=None, show_normals=False, who="relight"):
+    """tr_relight_params for Scene.relight / get_relit / relight_host / relight_normals_host.  uniforms: the view's
+    Uniforms from prepare_uniforms(2, W, H, ..) -- kind 2 fills i_vpmv, frame raster to model space --, or that matrix
+    itself as 16 floats column-major or a [4, 4] array indexed [row, column].  eye: the camera's position in model space
+    (for prepare_uniforms' camera: look_from + 5 * camera_direction).  ambient: r, g, b; mode: a layer mode; opacity
+    0..256; albedo: multiply the light by the pixel's own colour first (default: on under "add", off otherwise);
+    show_normals: the normal map instead of the lights.  ValueError, in the library's words, for what it would refuse."""
+    if isinstance(uniforms, _lib.Uniforms):
+        mm = np.array(list(uniforms.i_vpmv), np.float64)
+        if not mm.any():
+            raise ValueError("%s: uniforms.i_vpmv is all zeros (prepare_uniforms kind 2 fills it)" % who)
+    else:
+        mm = np.asarray(uniforms, np.float64)
+        if mm.shape == (4, 4):
+            mm = mm.T.reshape(16)   # ([row, column] to column-major)
+    if mm.shape != (16,):
+        raise ValueError("%s: u must be Uniforms, 16 values (column-major) or a [4, 4] array" % who)
+    with np.errstate(over="ignore"):
+        u32, e32 = mm.astype(np.float32), np.asarray(eye, np.float64).astype(np.float32)
+    if isinstance(opacity, bool) or not isinstance(opacity, (int, np.integer)):
+        raise ValueError("%s: opacity must be an integer" % who)
+    if mode not in LAYER_MODES:
+        raise ValueError("%s: mode must be TR_LAYER_NORMAL .. TR_LAYER_DIFFERENCE" % who)
+    if not 0 <= opacity <= 256:
+        raise ValueError("%s: opacity must be 0..256" % who)
+    if not np.isfinite(u32).all():
+        raise ValueError("%s: every entry of u must be finite" % who)
+    if e32.shape != (3,) or not np.isfinite(e32).all():
+        raise ValueError("%s: every entry of eye must be finite" % who)
+    amb = [int(v) for v in ambient]
+    if len(amb) != 3 or min(amb) < 0 or max(amb) > 255:
+        raise ValueError("%s: ambient takes three values 0..255" % who)
+    if albedo is None:
+        albedo = mode == "add"
+    return RelightParams((C.c_float * 16)(*[float(v) for v in u32]), (C.c_float * 3)(*[float(v) for v in e32]), (C.c_uint8 * 4)(*amb, 0),
+                         LAYER_MODES[mode], int(opacity), (RELIGHT_ALBEDO if albedo else 0) | (RELIGHT_SHOW_NORMALS if show_normals else 0),
+                         (C.c_uint32 * 9)(*([0] * 9)))
+
+
+def _light_table(lights, who):
+    """(ctypes array or None, n) of a sequence of Light."""
+    ls = list(lights) if lights is not None else []
+    for l in ls:
+        if not isinstance(l, Light):
+            raise ValueError("%s: lights must come from light_directional, light_point or light_spot" % who)
+    if len(ls) > RELIGHT_MAX_LIGHTS:
+        raise ValueError("%s: n_lights must be 0..TR_RELIGHT_MAX_LIGHTS" % who)
+    return ((Light * len(ls))(*ls) if ls else None), len(ls)
+
+
+def relight_host(rgb, z, params, lights=(), in_place=False):
+    """tr_relight_host: the rule of Scene.relight on the host (no GPU needed), by the inline functions k_relight calls.
+    rgb [H, W, 3] uint8 with row 0 = top (get_frame_buffer), z [H, W] float32 with row 0 = bottom (read_z_f32), params
+    from relight_params, lights: up to 8 from light_directional / light_point / light_spot.  Returns the lit frame and
+    leaves its arguments alone; in_place=True hands the library one buffer as rgb and out, which the rule allows."""
+    _check_params(params, RelightParams, "relight_host", "relight_params")
+    table, n = _light_table(lights, "relight_host")
+    src = np.ascontiguousarray(rgb, np.uint8)
+    zz = np.ascontiguousarray(z, np.float32)
+    if src.ndim != 3 or src.shape[2] != 3 or src.shape[0] < 1 or src.shape[1] < 1 or zz.shape != src.shape[:2]:
+        raise ValueError("relight_host: rgb [H, W, 3] and z [H, W]")
+    out = src.copy() if in_place else np.empty_like(src)
+    check(load_library().tr_relight_host(src.shape[1], src.shape[0], out.ctypes.data if in_place else src.ctypes.data, zz.ctypes.data,
+                                         C.addressof(params), table, n, out.ctypes.data))
+    return out
+
+
+def relight_normals_host(z, params):
+    """tr_relight_normals_host: the normals the rule recovers from a depth array, on the host.  z [H, W] float32 with row
+    0 = bottom (read_z_f32); of params (relight_params) u and eye count.  Returns (normals [H, W, 3] float32, valid [H, W]
+    bool), both with row 0 = bottom like z; a pixel without a normal has zeros."""
+    _check_params(params, RelightParams, "relight_normals_host", "relight_params")
+    zz = np.ascontiguousarray(z, np.float32)
+    if zz.ndim != 2 or zz.shape[0] < 1 or zz.shape[1] < 1:
+        raise ValueError("relight_normals_host: z [H, W]")
+    normals, valid = np.empty(zz.shape + (3,), np.float32), np.empty(zz.shape, np.uint8)
+    check(load_library().tr_relight_normals_host(zz.shape[1], zz.shape[0], zz.ctypes.data, C.addressof(params), normals.ctypes.data, valid.ctypes.data))
+    return normals, valid.astype(bool)
+
+
 def mesh_edges(mesh):
     """The unique edges of a mesh's faces as position-index pairs [m, 2] (int64, the smaller index first, sorted)."""
     idx = np.asarray(mesh["idx"]).astype(np.int64)
@@ -3071,6 +3223,33 @@ class Scene:
         """tr_scene_debug_projector_launches: the k_projector launches this scene has enqueued so far (the kernel has no
         entry in profile_read)."""
         return check(load_library().tr_scene_debug_projector_launches(self._h))
+
+    # --- relight (tr_scene_relight / tr_scene_get_relit) ----------------------------------------------
+    def relight(self, params, lights=(), out=None):
+        """tr_scene_relight: lays up to 8 coloured lights (light_directional, light_point, light_spot) with their
+        highlights on the drawn pixels of the current frame on the device, from normals recovered out of the frame's own
+        depth.  params: relight_params(uniforms of prepare_uniforms(2, ..) for the frame's camera, eye, ..).  out=None:
+        in place, by the kernel itself -- every later consumer sees the result; z, winner words and the shadow buffer
+        stay.  Otherwise `out` is a device pointer (int) or tensor of 3 * W * H bytes apart from every frame buffer of
+        the scene, or an array from pinned_frame, and the scene's frame stays as it is.  Asynchronous: the result is there
+        after sync().  Band scenes are refused.  relight_host is the rule."""
+        _check_params(params, RelightParams, "tr_scene_relight", "relight_params")
+        table, n = _light_table(lights, "tr_scene_relight")
+        ptr = self._target_pointer(out, "out must be a contiguous tensor of at least 3 * width * height bytes")
+        check(load_library().tr_scene_relight(self._h, C.addressof(params), table, n, ptr))
+        return out
+
+    def get_relit(self, params, lights=(), strict=True):
+        """tr_scene_get_relit: the current frame with the lights laid on it on the device (arguments as for relight), as an
+        [H, W, 3] uint8 array.  Synchronizes; the scene's frame stays as it is."""
+        _check_params(params, RelightParams, "tr_scene_get_relit", "relight_params")
+        table, n = _light_table(lights, "tr_scene_get_relit")
+        return self._image("tr_scene_get_relit", strict, C.addressof(params), table, n)
+
+    def debug_relight_launches(self):
+        """tr_scene_debug_relight_launches: the k_relight launches this scene has enqueued so far (the kernel has no
+        entry in profile_read)."""
+        return check(load_library().tr_scene_debug_relight_launches(self._h))
 
     def project(self, points):
         """Model-space points [n, 3] as the scene's last camera (set_camera) places them: project_points under
